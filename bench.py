@@ -4,7 +4,13 @@ One "step" = one pass of the hot path over one batch: the layer's two fused Grou
 (gate_up: 61 problems, down: 61 problems), inputs resident in HBM, tile tables planned once.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--config fp16|w8a8|w4a4|mixed] [--variant V]
+                  [--dump-outputs DIR] [--full]
   (N > 1: launched by torch.distributed.run, one rank per GPU)
+
+A plain run sets up, warms up, times the K steps and prints the result line (value, ms_per_step).
+--dump-outputs DIR then writes what the last timed step computed (dump_outputs). --full adds every
+other figure, each from runs of its own: the per-launch roofline, the other configs (`extras`), the MoE
+layer, the single-GPU scaling simulation, the as-reference entry and the CPU baseline.
 
 Multi-GPU (strong scaling, SURVEY.md §8e, north_star): with N ranks the SAME layer is split by
 expert (dist.ep_layer_plan): routed experts by index (LPT on gate_up + down FLOPs), the shared expert
@@ -313,6 +319,42 @@ def ep_combine_step(cfg: str, dev, world: int, rank: int, steps: int, warmup: in
             "allgather_out_MB_received": round(max(b["allgather_out"]) / 1e6, 1)}
 
 
+# --dump-outputs: elements kept per call. As float32 the step's two calls come to 48 MB at most.
+DUMP_ELEMS_PER_CALL = 6_000_000
+
+
+def dump_indices(call: int, problem: int, n: int, total: int):
+    """The flat indices into problem `problem`'s n outputs that dump_outputs keeps, None for all of
+    them (the call's `total` outputs fit DUMP_ELEMS_PER_CALL). Otherwise a seeded (CPU generator: the
+    same indices in every run and build), sorted draw with replacement, in proportion to n."""
+    if total <= DUMP_ELEMS_PER_CALL:
+        return None
+    g = torch.Generator().manual_seed(1000 * call + problem)
+    return torch.randint(n, (max(1, n * DUMP_ELEMS_PER_CALL // total),), generator=g).sort().values
+
+
+def dump_outputs(dirpath: str, inp: dict) -> None:
+    """Write the C of every problem of the step's two calls, as the launches left them, to
+    `dirpath`/gate_up.npy and `dirpath`/down.npy: float32, the problems' rows [0, M) flattened (or
+    the dump_indices sample of them) and concatenated in call order."""
+    import numpy as np
+
+    os.makedirs(dirpath, exist_ok=True)
+    for ci, gg in enumerate(("gate_up", "down")):
+        total = sum(p.M * p.N for p in inp[gg].problems)
+        parts = []
+        for pi, p in enumerate(inp[gg].problems):
+            n = p.M * p.N
+            if n == 0:
+                continue
+            c = p.C[:p.M].reshape(-1)
+            idx = dump_indices(ci, pi, n, total)
+            if idx is not None:
+                c = c[idx.to(c.device)]
+            parts.append(c.float().cpu())
+        np.save(os.path.join(dirpath, gg + ".npy"), torch.cat(parts).numpy())
+
+
 def cpu_info() -> dict:
     """Host CPU model and the threads the baseline may use (the GPU box exports OMP_NUM_THREADS=16:
     its share of a much larger machine, which os.cpu_count() would report)."""
@@ -471,6 +513,13 @@ def main():
     # 0.436 on the kernels' own clock)
     ap.add_argument("--settle-s", type=float, default=0.3, help="seconds of untimed steps before the warm-up")
     ap.add_argument("--config", default="fp16", choices=list(CONFIGS))
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need, each in runs of its own: the per-launch "
+                         "roofline, --extras, the MoE layer, the scaling simulation, the as-reference entry, the "
+                         "CPU baseline; N > 1: the token-owner exchange and --dist-extras")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="N = 1: after the timed steps write the last step's outputs (a seeded sample of the larger "
+                         "calls) to DIR/gate_up.npy and DIR/down.npy as float32")
     ap.add_argument("--no-scaling-sim", action="store_true",
                     help="skip the single-GPU strong-scaling simulation and the as-reference timing (N=1 only)")
     ap.add_argument("--variant", type=int, default=-1, help="-1 = library's choice (MXMOE_GG_VARIANT_AUTO)")
@@ -488,6 +537,10 @@ def main():
     ap.add_argument("--dist-extras", default="ds2_mixed", help="other configs run through the expert split at N > 1")
     ap.add_argument("--extras-warmup", type=int, default=200, help="untimed steps before an extra config's launch timing")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    if args.dump_outputs and args.gpus != 1:
+        ap.error("--dump-outputs writes the single-GPU step's outputs: use --gpus 1")
 
     action, why = resolve_launch(args.gpus, os.environ, torch.cuda.device_count())
     if action == "error":
@@ -522,7 +575,7 @@ def main():
     from mxmoe_amd.groupgemm import GroupGemm
     from mxmoe_amd.harness import build_layer_inputs, refill_layer_inputs, time_launches
 
-    def run_config(cfg: str, steps: int, warmup: int, timed_region: bool):
+    def run_config(cfg: str, steps: int, warmup: int, timed_region: bool, dump_dir=None, per_launch: bool = True):
         variant = args.variant if args.variant >= 0 else None
         shapes = layer_shapes(cfg, world, rank)
         inp = {gg: build_layer_inputs(shapes[gg], device=dev, seed=42 + 1000 * rank + (gg == "down"))
@@ -569,9 +622,11 @@ def main():
                 total_flops = float(flops["gate_up"] + flops["down"])
             res["dt"] = dt
             res["total_flops"] = total_flops
+            if dump_dir:  # the C buffers hold the last timed step's outputs
+                dump_outputs(dump_dir, inp)
         # per-launch device time (HIP events on the launch stream) — the roofline's denominator
         per = {gg: time_launches(lambda g=gg: ggs[g].launch(stream), warmup=3, iters=args.median_iters, stream=stream)
-               for gg in ggs}
+               for gg in ggs} if per_launch else None
         res.update(per=per, flops=flops, variant=variant, tiles={gg: ggs[gg].total_tiles for gg in ggs},
                    bytes={gg: inp[gg].bytes_algorithmic() for gg in inp}, shapes=shapes)
         del ggs, inp
@@ -582,7 +637,7 @@ def main():
     peak = PEAK_TFLOPS[CONFIGS[cfg]["peak"]]
     extras = {}
     if world == 1:
-        main_res = run_config(cfg, args.steps, args.warmup, True)
+        main_res = run_config(cfg, args.steps, args.warmup, True, dump_dir=args.dump_outputs, per_launch=args.full)
         f_gu, f_dn = main_res["flops"]["gate_up"], main_res["flops"]["down"]
         b_step = main_res["bytes"]["gate_up"] + main_res["bytes"]["down"]
     else:
@@ -611,19 +666,20 @@ def main():
             "speedup_compute": round(eres["t1"] / eres["t_compute"], 3),
             "speedup_with_allgather": round(eres["t1"] / eres["dt"], 3),
             "allgather_MB_received_per_rank": eres["allgather_MB_received_per_rank"]}
-        try:  # the token-owner exchange (combine before the exchange): VERDICT r04 item 6
-            cres = ep_combine_step(cfg, dev, world, rank, args.steps, args.warmup, coll_dev, variant=vv)
-            extras["strong_scaling"]["combine_exchange"] = {
-                "what": "same split and compute; routed down rows all_to_all_single'd to their token's owner (the "
-                        "rank holding that token's shared-expert rows), combined there (mxmoe_moe_combine, top-k "
-                        "order), the combined [T, hidden] output all-gathered (dist.EPCombineStep)",
-                "compute_ms": round(ms(cres["t_compute"]), 4), "exchange_ms": round(ms(cres["t_exchange"]), 4),
-                "step_ms": round(ms(cres["dt"]), 4), "speedup_with_exchange": round(eres["t1"] / cres["dt"], 3),
-                "a2a_MB_received_max": cres["a2a_MB_received_max"],
-                "allgather_out_MB_received": cres["allgather_out_MB_received"]}
-        except Exception as e:  # an extra must not lose the headline
-            extras["strong_scaling"]["combine_exchange"] = {"error": f"{type(e).__name__}: {e}"[:300]}
-        for x in [e for e in args.dist_extras.split(",") if e and e != cfg]:
+        if args.full:
+            try:  # the token-owner exchange (combine before the exchange): VERDICT r04 item 6
+                cres = ep_combine_step(cfg, dev, world, rank, args.steps, args.warmup, coll_dev, variant=vv)
+                extras["strong_scaling"]["combine_exchange"] = {
+                    "what": "same split and compute; routed down rows all_to_all_single'd to their token's owner (the "
+                            "rank holding that token's shared-expert rows), combined there (mxmoe_moe_combine, top-k "
+                            "order), the combined [T, hidden] output all-gathered (dist.EPCombineStep)",
+                    "compute_ms": round(ms(cres["t_compute"]), 4), "exchange_ms": round(ms(cres["t_exchange"]), 4),
+                    "step_ms": round(ms(cres["dt"]), 4), "speedup_with_exchange": round(eres["t1"] / cres["dt"], 3),
+                    "a2a_MB_received_max": cres["a2a_MB_received_max"],
+                    "allgather_out_MB_received": cres["allgather_out_MB_received"]}
+            except Exception as e:  # an extra must not lose the headline
+                extras["strong_scaling"]["combine_exchange"] = {"error": f"{type(e).__name__}: {e}"[:300]}
+        for x in [e for e in args.dist_extras.split(",") if e and e != cfg] if args.full else []:
             try:  # BASELINE configs[4]: DeepSeek-V2-Lite mixed w4a4+w8a8 split by expert over the node
                 xr = ep_layer_step(x, dev, world, rank, args.steps, args.warmup, coll_dev, variant=vv,
                                    median_iters=10)
@@ -660,22 +716,29 @@ def main():
                     "ms_per_step": round(ep["dt"] / args.steps * 1e3, 4)}
             except Exception as e:  # an extra must not lose the headline
                 extras["ep_weak_scaling"] = {"error": f"{type(e).__name__}: {e}"[:300]}
-    per = main_res["per"]
-    t_gu, t_dn = per["gate_up"]["mean_ms"], per["down"]["mean_ms"]
-    achieved = (f_gu + f_dn) / ((t_gu + t_dn) * 1e-3) / 1e12
-    # roofline of the step's two launches (this rank's at N > 1): MFMA-bound unless the arithmetic
-    # intensity puts the HBM roof (algorithmic bytes x 8 TB/s) below the MFMA peak
-    if (f_gu + f_dn) / b_step * HBM_GBS / 1e3 < peak:
-        gbs = b_step / ((t_gu + t_dn) * 1e-3) / 1e9
-        roof = {"bound": "hbm", "achieved": round(gbs, 1), "peak": HBM_GBS, "unit": "GB/s", "frac": round(gbs / HBM_GBS, 4),
-                "achieved_tflops": round(achieved, 2)}
-    else:
-        roof = {"bound": "mfma", "achieved": round(achieved, 2), "peak": peak, "unit": "TFLOP/s",
-                "frac": round(achieved / peak, 4)}
+    per = main_res["per"]  # None on a plain N = 1 run: the per-launch timing is a run of its own (--full)
+    roof = None
+    if per is not None:
+        t_gu, t_dn = per["gate_up"]["mean_ms"], per["down"]["mean_ms"]
+        achieved = (f_gu + f_dn) / ((t_gu + t_dn) * 1e-3) / 1e12
+        # roofline of the step's two launches (this rank's at N > 1): MFMA-bound unless the arithmetic
+        # intensity puts the HBM roof (algorithmic bytes x 8 TB/s) below the MFMA peak
+        if (f_gu + f_dn) / b_step * HBM_GBS / 1e3 < peak:
+            gbs = b_step / ((t_gu + t_dn) * 1e-3) / 1e9
+            roof = {"bound": "hbm", "achieved": round(gbs, 1), "peak": HBM_GBS, "unit": "GB/s",
+                    "frac": round(gbs / HBM_GBS, 4), "achieved_tflops": round(achieved, 2)}
+        else:
+            roof = {"bound": "mfma", "achieved": round(achieved, 2), "peak": peak, "unit": "TFLOP/s",
+                    "frac": round(achieved / peak, 4)}
+        pmc = load_pmc_traffic(cfg) if world == 1 else None  # the committed PMC passes are single-GPU runs
+        roof.update(traffic=pmc.get("hbm_bytes_per_step") if isinstance(pmc, dict) else None,
+                    traffic_source=pmc.get("_source") if isinstance(pmc, dict) else None,
+                    kernel=kernel_symbol(nat.list_variants()[main_res["variant"]].split()[1])
+                    + " (gate_up + down launches; achieved = sum FLOPs / sum mean launch time)",
+                    launch_ms={"gate_up": round(t_gu, 4), "down": round(t_dn, 4)})
     value = main_res["total_flops"] * args.steps / main_res["dt"] / 1e12
-    pmc = load_pmc_traffic(cfg) if world == 1 else None  # the committed PMC passes are single-GPU runs
 
-    if rank == 0 and world == 1:
+    if rank == 0 and world == 1 and per is not None:
         for gg in ("gate_up", "down"):
             b = main_res["bytes"][gg]
             f = main_res["flops"][gg]
@@ -684,7 +747,7 @@ def main():
                           "tiles": main_res["tiles"][gg], "algorithmic_MB": round(b / 1e6, 1),
                           "AI_flop_per_B": round(f / b, 1),
                           "roof_tflops": round(min(peak, f / b * HBM_GBS / 1e3), 1)}
-    if world == 1 and args.extras:
+    if world == 1 and args.full and args.extras:
         for x in [e for e in args.extras.split(",") if e and e != cfg]:
             r = run_config(x, 0, args.extras_warmup, False)
             pk = PEAK_TFLOPS[CONFIGS[x]["peak"]]
@@ -702,7 +765,7 @@ def main():
             else:
                 extras[x].update(bound="mfma", roofline_frac=round(ff / (tt * 1e-3) / 1e12 / pk, 4), peak_tflops=pk)
 
-    if world == 1 and not args.no_moe_layer and CONFIGS[cfg].get("model", "qwen2_moe") == "qwen2_moe":
+    if world == 1 and args.full and not args.no_moe_layer and CONFIGS[cfg].get("model", "qwen2_moe") == "qwen2_moe":
         try:  # the MoE layer around the path: not part of value
             from mxmoe_amd.moe import qwen2_layer_bench
 
@@ -743,7 +806,7 @@ def main():
         except Exception as e:  # noqa: BLE001
             extras["moe_layer_ds2"] = {"error": f"{type(e).__name__}: {e}"[:300]}
 
-    if world == 1 and not args.no_scaling_sim:
+    if world == 1 and args.full and not args.no_scaling_sim:
         from mxmoe_amd.harness import build_layer_inputs as _bli, ep_scaling_sim, time_reference_abi
 
         asref = {}
@@ -766,7 +829,7 @@ def main():
             "gate_up_ms": asref["gate_up"], "down_ms": asref["down"],
             "tflops": round((f["gate_up"] + f["down"]) / ((asref["gate_up"] + asref["down"]) * 1e-3) / 1e12, 2)}
 
-    if world == 1:
+    if world == 1 and args.full:
         ref = {"hardware": "RTX-4090", "source": "reference README media/final-perf.png read by eye (BASELINE.md §1)"}
         for c in [cfg] + [x for x in args.extras.split(",") if x in extras]:
             if c in REFERENCE_CHART_TFLOPS:
@@ -775,7 +838,7 @@ def main():
         extras["reference_published_chart"] = ref
 
     cpu = None
-    if world == 1 and rank == 0 and not args.no_cpu_baseline:
+    if world == 1 and rank == 0 and args.full and not args.no_cpu_baseline:
         cpu = cpu_baseline(cfg, main_res["shapes"])
 
     if rank == 0:
@@ -785,6 +848,7 @@ def main():
             "unit": "TFLOP/s",
             "n_gpus": world,
             "steps": args.steps,
+            "full": bool(args.full),
             "warmup": args.warmup,
             "settle_s": args.settle_s,
             "materialise_after_plan": bool(args.materialise_after_plan),
@@ -807,12 +871,7 @@ def main():
                        "seq_len": None, "parallelism": f"ep{world}+allgather" if world > 1 else "single",
                        "problems_per_call": len(main_res["shapes"]["gate_up"]), "variant": main_res["variant"],
                        "variant_name": nat.list_variants()[main_res["variant"]].split()[1]},
-            "roofline": {**roof,
-                         "traffic": pmc.get("hbm_bytes_per_step") if isinstance(pmc, dict) else None,
-                         "traffic_source": pmc.get("_source") if isinstance(pmc, dict) else None,
-                         "kernel": kernel_symbol(nat.list_variants()[main_res["variant"]].split()[1])
-                         + " (gate_up + down launches; achieved = sum FLOPs / sum mean launch time)",
-                         "launch_ms": {"gate_up": round(t_gu, 4), "down": round(t_dn, 4)}},
+            "roofline": roof,
             "cpu_baseline": cpu,
             "extras": extras,
         }

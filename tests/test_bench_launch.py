@@ -57,6 +57,61 @@ def test_bench_refuses_mismatched_world_size_before_gpu_work():
     assert r.returncode == 2 and "n_gpus must equal --gpus" in r.stderr
 
 
+def _fake_step_inputs(sizes):
+    """{"gate_up", "down"} calls of problems with C [max(M, 1), N] fp16 = 0, 1, 2, ... (exact in fp16)."""
+    import types
+
+    import torch
+
+    def call(base):
+        return types.SimpleNamespace(problems=[
+            types.SimpleNamespace(M=m, N=n, C=(torch.arange(max(m, 1) * n) + base).reshape(max(m, 1), n).half())
+            for m, n in sizes])
+
+    return {"gate_up": call(0), "down": call(1)}
+
+
+def test_dump_outputs_writes_small_calls_whole(tmp_path):
+    import numpy as np
+
+    sizes = [(3, 8), (0, 8), (5, 16)]  # the M = 0 problem's one allocated row is not an output
+    bench.dump_outputs(str(tmp_path / "d"), _fake_step_inputs(sizes))
+    for base, name in ((0, "gate_up"), (1, "down")):
+        got = np.load(tmp_path / "d" / f"{name}.npy")
+        want = np.concatenate([np.arange(m * n, dtype=np.float32) + base for m, n in sizes if m])
+        assert got.dtype == np.float32 and np.array_equal(got, want)
+    assert sorted(p.name for p in (tmp_path / "d").iterdir()) == ["down.npy", "gate_up.npy"]
+
+
+def test_dump_outputs_samples_large_calls_the_same_way_every_time(tmp_path, monkeypatch):
+    import numpy as np
+
+    monkeypatch.setattr(bench, "DUMP_ELEMS_PER_CALL", 100)
+    sizes = [(30, 40), (0, 8), (1, 7), (20, 40)]
+    inp = _fake_step_inputs(sizes)
+    bench.dump_outputs(str(tmp_path / "a"), inp)
+    bench.dump_outputs(str(tmp_path / "b"), inp)
+    total = sum(m * n for m, n in sizes)
+    counts = [max(1, m * n * 100 // total) for m, n in sizes if m]
+    for base, name in ((0, "gate_up"), (1, "down")):
+        a = np.load(tmp_path / "a" / f"{name}.npy")
+        assert a.dtype == np.float32 and np.array_equal(a, np.load(tmp_path / "b" / f"{name}.npy"))
+        assert a.size == sum(counts) <= 100
+        at = 0
+        for (m, n), k in zip([s for s in sizes if s[0]], counts):  # every problem: sorted draws of its own C
+            part = a[at:at + k] - base
+            at += k
+            assert (np.diff(part) >= 0).all() and part.min() >= 0 and part.max() < m * n
+            assert (part == np.round(part)).all()
+
+
+def test_dump_outputs_is_refused_with_more_than_one_gpu():
+    # the dumped arrays are the single-GPU step's: refused at the argument check (no GPU work)
+    r = subprocess.run([sys.executable, bench.__file__, "--gpus", "2", "--dump-outputs", "x"],
+                       env={"PATH": "/usr/bin"}, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 2 and "--dump-outputs" in r.stderr
+
+
 def _unresolved_globals(path) -> set:
     """Names a function in ``path`` reads as implicit globals that the module never binds and that are
     not builtins (a pyflakes-style check via symtable: ADVICE r04 found `settle_s` read by
