@@ -55,7 +55,9 @@ def build(force: bool = False, verbose: bool = False, extra: list[str] | None = 
 
 
 REF_HARNESS_SRC = [ROOT / "tests" / "cpp" / "ref_harness_call.cpp", ROOT / "tests" / "cpp" / "layout_check.cpp"]
-REF_HARNESS = ROOT / "tests" / "cpp" / "bin" / "ref_harness_call"
+# built beside the library it links, not under tests/: a build product in the test tree goes missing
+# whenever that tree is replaced (another revision's tests run against this build)
+REF_HARNESS = LIB.parent / "ref_harness_call"
 
 
 def build_ref_harness(force: bool = False, verbose: bool = False) -> Path:
@@ -67,7 +69,7 @@ def build_ref_harness(force: bool = False, verbose: bool = False) -> Path:
     REF_HARNESS.parent.mkdir(parents=True, exist_ok=True)
     cmd = [HIPCC, "-O2", "-std=c++17", f"--offload-arch={ARCH}", "-Wall", "-I", str(ROOT / "include"),
            "-o", str(REF_HARNESS), *map(str, REF_HARNESS_SRC), "-L", str(LIB.parent), "-lmxmoe_gg",
-           "-Wl,-rpath,$ORIGIN/../../../mxmoe_amd/lib"]
+           "-Wl,-rpath,$ORIGIN"]
     if verbose:
         print(" ".join(cmd), file=sys.stderr)
     subprocess.run(cmd, check=True)
