@@ -49,6 +49,36 @@ typedef struct mxmoe_moe_seg {
   int64_t scale_off;   /* fp16-element offset of its scales: [rows] or [width/128][rows]      */
 } mxmoe_moe_seg;
 
+/* The router in front of the layer, one launch: gate logits, top-k selection, softmax weights and
+ * (optionally) the shared expert's gate, from one pass over `hidden`.
+ * Replaces: nothing in the reference, which has no router kernel (its bench draws topk_ids). The
+ * semantics are the models' own `softmax(hidden @ w_gate.T) -> topk` routing code (qwen2_moe,
+ * DeepSeek-V2-Lite, Mixtral) and qwen2_moe's `sigmoid(shared_expert_gate(hidden))`.
+ *   hidden fp16 [T][H], w_gate fp16 [E][H], w_shared_gate fp16 [H] or NULL (all row-major).
+ *   logits   x[e] = sum_h f32(hidden[t][h]) * f32(w_gate[e][h]), f32 accumulation on the MFMA
+ *            (v_mfma_f32_16x16x32_f16; the summation order is the kernel's own).
+ *   selection: the topk largest x[e]; among equal logits (-0 == +0) the lower index wins.
+ *            topk_ids[t][k] (int32) in descending order of logit, ties by ascending index. The
+ *            selection is made on the logits, not on the probabilities.
+ *   weights  m = max_e x[e], p[e] = exp2((x[e] - m) * log2 e) (hardware exp2), f32 [T][topk] as
+ *            mxmoe_moe_combine reads them:
+ *            renormalize == 0: p[id_k] / sum_{e<E} p[e]       (qwen2_moe, DeepSeek-V2-Lite)
+ *            renormalize != 0: p[id_k] / sum_{j<topk} p[id_j] (Mixtral)
+ *   shared_w[t] = rcp(1 + exp2(-s * log2 e)), s = hidden[t] . w_shared_gate (f32 [T], the shared_w
+ *            of mxmoe_moe_combine): one more output column of the same pass, outside the softmax,
+ *            the max and the selection. shared_w must be non-NULL exactly when w_shared_gate is.
+ *   logits   NULL, or f32 [T][E]: receives the very x[e] the selection and the softmax used.
+ * A row whose logits hold NaN or +-Inf still gets topk distinct ids in [0, E) (its weights may be
+ * anything, NaN included). Rows past T and columns past E (E + 1 with the shared gate) pad the last
+ * MFMA block through clamped addresses: nothing outside the operands is read, nothing outside
+ * [T] rows written. No workspace, no allocation.
+ * Limits: T >= 0 (T == 0: OK, no launch), T * topk <= 2^30, 1 <= E <= 256, 1 <= topk <= min(E, 16),
+ * H % 32 == 0; hidden, w_gate and w_shared_gate 16-byte aligned. Anything else: MXMOE_GG_ERR_INVALID
+ * (checked before any HIP call). */
+int mxmoe_moe_gate(const void* hidden, const void* w_gate, const void* w_shared_gate, int64_t T, int H, int E, int topk,
+                   int renormalize, int32_t* topk_ids, float* topk_weights, float* shared_w, float* logits,
+                   void* stream);
+
 /* Stable counting sort of the T*topk expert ids (int32, row-major [T][topk], values in [0, E)):
  *   sorted_expert[s] = expert of slot s (non-decreasing), perm_token[s] = source token of slot s,
  *   inv_slot[t*topk + k] = slot of (token t, choice k), counts[e] = tokens routed to expert e.

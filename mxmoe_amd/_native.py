@@ -92,6 +92,7 @@ EXPORTED_SYMBOLS = (
     "mxmoe_gg_plan_tiles",
     # include/mxmoe_moe.h (MoE-layer plumbing)
     "mxmoe_moe_route", "mxmoe_moe_quant_act", "mxmoe_moe_silu_mul_quant", "mxmoe_moe_silu_mul_quant_il", "mxmoe_moe_quant_slots", "mxmoe_moe_combine",
+    "mxmoe_moe_gate",
 )
 
 
@@ -167,6 +168,9 @@ def _declare(lib: ctypes.CDLL) -> None:
         if hasattr(lib, fn):  # (builds before round 5's fused SiLU epilogue lack them: A/B tools)
             getattr(lib, fn).restype = c.c_int
             getattr(lib, fn).argtypes = [P, P, c.c_int64, c.c_int, c.c_int, c.c_int, P, P, c.c_int, P, P, P]
+    if hasattr(lib, "mxmoe_moe_gate"):  # (the router; builds before it lack the symbol: A/B tools)
+        lib.mxmoe_moe_gate.restype = c.c_int
+        lib.mxmoe_moe_gate.argtypes = [P, P, P, c.c_int64, c.c_int, c.c_int, c.c_int, c.c_int, P, P, P, P, P]
     lib.mxmoe_moe_combine.restype = c.c_int
     lib.mxmoe_moe_combine.argtypes = [P, P, P, P, P, c.c_int64, c.c_int, c.c_int, P, P]
 

@@ -12,6 +12,7 @@
 // All four kernels are HBM-bound byte movers: one workgroup per row (token or slot), 16-B
 // coalesced loads of 8 fp16 per lane, reductions in registers / lane shuffles, stores of the packed
 // codes as one 4-B (int4) / 8-B (int8) / 16-B (fp16) word per lane — no LDS tiling, no MFMA.
+// The router in front of them (mxmoe_moe_gate: logits on the MFMA, top-k, softmax) is moe_gate.h.
 #include <hip/hip_runtime.h>
 
 #include <cstdarg>
@@ -20,6 +21,7 @@
 
 #include "../../include/mxmoe_gg.h"
 #include "../../include/mxmoe_moe.h"
+#include "moe_gate.h"
 
 namespace mxmoe {
 namespace detail {
@@ -444,6 +446,28 @@ static int launch_act(int mode, ActArgs a, int64_t nslots, int w_routed, int w_s
 }
 
 extern "C" {
+
+int mxmoe_moe_gate(const void* hidden, const void* w_gate, const void* w_shared_gate, int64_t T, int H, int E, int topk,
+                   int renormalize, int32_t* topk_ids, float* topk_weights, float* shared_w, float* logits,
+                   void* stream) {
+  if (T < 0 || E < 1 || E > 256 || topk < 1 || topk > 16 || topk > E || H <= 0 || H % 32 ||
+      T * topk > (int64_t)1 << 30)
+    return fail(MXMOE_GG_ERR_INVALID, "mxmoe_moe_gate: need T >= 0, 1 <= E <= 256, 1 <= topk <= min(E, 16), H %% 32 == 0, "
+                "T * topk <= 2^30 (T=%lld H=%d E=%d topk=%d)", (long long)T, H, E, topk);
+  if ((w_shared_gate != nullptr) != (shared_w != nullptr))
+    return fail(MXMOE_GG_ERR_INVALID, "mxmoe_moe_gate: w_shared_gate and shared_w must be given together");
+  if (!aligned16(hidden) || !aligned16(w_gate) || !aligned16(w_shared_gate))
+    return fail(MXMOE_GG_ERR_INVALID, "mxmoe_moe_gate: misaligned pointer (hidden / w_gate / w_shared_gate need 16 B)");
+  if (T == 0) return MXMOE_GG_OK;
+  if (!hidden || !w_gate || !topk_ids || !topk_weights) return fail(MXMOE_GG_ERR_INVALID, "mxmoe_moe_gate: NULL pointer");
+  const gate::GateArgs a{static_cast<const _Float16*>(hidden), static_cast<const _Float16*>(w_gate),
+                         static_cast<const _Float16*>(w_shared_gate), T, H, E, topk, renormalize != 0, topk_ids,
+                         topk_weights, shared_w, logits};
+  gate::gate_launch(a, (hipStream_t)stream);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(MXMOE_GG_ERR_HIP, "gate_kernel launch failed: %s", hipGetErrorString(e));
+  return MXMOE_GG_OK;
+}
 
 int mxmoe_moe_route(const int32_t* topk_ids, int64_t T, int topk, int E, int32_t* sorted_expert,
                     int32_t* perm_token, int32_t* inv_slot, int32_t* counts, void* stream) {

@@ -78,6 +78,48 @@ class Routing:
         return out
 
 
+def gate(hidden: torch.Tensor, w_gate: torch.Tensor, topk: int, *, renormalize: bool = False,
+         w_shared_gate: Optional[torch.Tensor] = None, return_logits: bool = False,
+         stream: Optional[torch.cuda.Stream] = None, out=None):
+    """The router (mxmoe_moe_gate, one launch): hidden fp16 [T, H], w_gate fp16 [E, H] ->
+    (topk_ids int32 [T, topk], topk_weights f32 [T, topk], shared_w f32 [T] or None), and the f32
+    [T, E] logits as a fourth item with ``return_logits``. Selection on the logits (ties: lower index),
+    weights = softmax over all E experts, or over the chosen topk with ``renormalize``; with
+    ``w_shared_gate`` (fp16 [H]) shared_w = sigmoid(hidden @ w_shared_gate). ``out``: the tuple a
+    previous call with the same arguments returned, to relaunch on its buffers."""
+    if hidden.dim() != 2 or hidden.dtype != torch.float16 or not hidden.is_contiguous():
+        raise ValueError("hidden must be a contiguous fp16 [T, H] tensor")
+    T, H = hidden.shape
+    if w_gate.dim() != 2 or w_gate.dtype != torch.float16 or not w_gate.is_contiguous() or w_gate.shape[1] != H:
+        raise ValueError(f"w_gate must be a contiguous fp16 [E, {H}] tensor")
+    E = w_gate.shape[0]
+    sg = w_shared_gate
+    if sg is not None and (sg.dtype != torch.float16 or not sg.is_contiguous() or sg.numel() != H):
+        raise ValueError(f"w_shared_gate must be a contiguous fp16 tensor of {H} elements")
+    dev = hidden.device
+    if out is None:
+        out = (torch.empty(T, topk, dtype=torch.int32, device=dev), torch.empty(T, topk, dtype=torch.float32, device=dev),
+               torch.empty(T, dtype=torch.float32, device=dev) if sg is not None else None)
+        if return_logits:
+            out += (torch.empty(T, E, dtype=torch.float32, device=dev),)
+    else:
+        out = tuple(out)
+        want = [((T, topk), torch.int32), ((T, topk), torch.float32), ((T,), torch.float32) if sg is not None else None]
+        if return_logits:
+            want.append(((T, E), torch.float32))
+        if len(out) != len(want):
+            raise ValueError(f"out must hold {len(want)} items")
+        for o, w in zip(out, want):
+            if (o is None) != (w is None) or (o is not None and (
+                    tuple(o.shape) != w[0] or o.dtype != w[1] or not o.is_contiguous() or o.device != dev)):
+                raise ValueError("out does not match this call's outputs (shape, dtype, contiguity or device)")
+    ids, wts, sw = out[:3]
+    logits = out[3] if return_logits else None
+    nat.check(nat.lib().mxmoe_moe_gate(_ptr(hidden), _ptr(w_gate), _ptr(sg), T, H, E, topk, int(bool(renormalize)),
+                                       _ptr(ids), _ptr(wts), _ptr(sw), _ptr(logits), _stream(stream)))
+    return out
+
+
 def route_device(topk_ids: torch.Tensor, E: int, stream: Optional[torch.cuda.Stream] = None, out=None):
     """The routing launch alone (no host synchronisation): (sorted_expert, perm_token, inv_slot, counts)
     device int32 tensors; `out` reuses a previous result's buffers."""
@@ -532,6 +574,34 @@ class MoEFFN:
         return out
 
 
+class MoEBlock:
+    """A MoE layer from hidden states: the router (``gate``) in front of a ``MoEFFN``.
+
+    w_gate: fp16 [E, H]; topk / renormalize: the model's routing (qwen2_moe: 4, DeepSeek-V2-Lite: 6,
+    both without renormalisation; Mixtral: 2 with); w_shared_gate: fp16 [H], qwen2_moe's
+    shared_expert_gate (only for a layer with a shared expert)."""
+
+    def __init__(self, ffn: MoEFFN, w_gate: torch.Tensor, topk: int, renormalize: bool = False,
+                 w_shared_gate: Optional[torch.Tensor] = None):
+        if tuple(w_gate.shape) != (ffn.E, ffn.H):
+            raise ValueError(f"w_gate must be [{ffn.E}, {ffn.H}], got {tuple(w_gate.shape)}")
+        if w_shared_gate is not None and not ffn.has_shared:
+            raise ValueError("w_shared_gate given for a layer without a shared expert")
+        if w_shared_gate is not None and w_shared_gate.numel() != ffn.H:
+            raise ValueError(f"w_shared_gate must hold {ffn.H} elements")
+        self.ffn, self.topk, self.renormalize = ffn, topk, renormalize
+        self.w_gate = w_gate.contiguous()
+        self.w_shared_gate = None if w_shared_gate is None else w_shared_gate.contiguous()
+
+    def forward(self, hidden: torch.Tensor, return_intermediates: bool = False):
+        ids, wts, sw = gate(hidden, self.w_gate, self.topk, renormalize=self.renormalize,
+                            w_shared_gate=self.w_shared_gate)
+        res = self.ffn.forward(hidden, ids, wts, sw, return_intermediates=return_intermediates)
+        if return_intermediates:
+            out, mid = res
+            mid.update(topk_ids=ids, topk_weights=wts, shared_w=sw)
+            return out, mid
+        return res
 
 
 class PlannedForward:
@@ -631,4 +701,61 @@ def qwen2_layer_bench(rounds: int = 4, iters: int = 30, bs: int = 8192, model: s
     out["gate_up_mode"] = {n: st.mode for n, st in steps.items()}
     names = [ln.split()[1] for ln in nat.list_variants()]
     out["gate_up_variant"] = {n: names[st.g1.variant] for n, st in steps.items()}
+    return out
+
+
+GATE_MODELS = {"qwen2_moe": dict(H=2048, E=60, topk=4, shared_gate=True),
+               "ds2": dict(H=2048, E=64, topk=6, shared_gate=False)}
+HBM_ROOF_BYTES_PER_S = 8e12  # MI355X
+
+
+def gate_bench(bs: int = 8192, model: str = "qwen2_moe", rounds: int = 4, iters: int = 30) -> dict:
+    """The router kernel against the torch composite it replaces (fp16 matmul -> f32 softmax -> topk
+    -> int32 ids, + sigmoid(hidden @ w_sg) for qwen2_moe), same process, interleaved round by round:
+    per side the median of the rounds' medians with min / max (µs) and the composite's run-to-run
+    spread (max - min) / median; the kernel's algorithmic bytes and fraction of the HBM roof.
+    model: "qwen2_moe" (H 2048, E 60, top-4, shared gate) or "ds2" (DeepSeek-V2-Lite: E 64, top-6)."""
+    from .harness import time_launches
+
+    m = GATE_MODELS[model]
+    H, E, topk = m["H"], m["E"], m["topk"]
+    dev = "cuda"
+    g = torch.Generator().manual_seed(0)
+    hidden = torch.randn(bs, H, generator=g).half().to(dev)
+    w_gate = (torch.randn(E, H, generator=g) * H ** -0.5).half().to(dev)
+    w_sg = (torch.randn(H, generator=g) * H ** -0.5).half().to(dev) if m["shared_gate"] else None
+    bufs = gate(hidden, w_gate, topk, w_shared_gate=w_sg)
+
+    def kernel():
+        gate(hidden, w_gate, topk, w_shared_gate=w_sg, out=bufs)
+
+    def composite():
+        logits = (hidden @ w_gate.T).float()
+        wts, ids = torch.topk(torch.softmax(logits, dim=-1), topk, dim=-1)
+        ids = ids.to(torch.int32)
+        sw = torch.sigmoid(hidden @ w_sg) if w_sg is not None else None
+        return ids, wts, sw
+
+    ref_ids = composite()[0]
+    torch.cuda.synchronize()
+    agree = float((bufs[0] == ref_ids).all(dim=1).float().mean())  # fp16-rounded logits can reorder near-ties
+    res = {"kernel": [], "torch": []}
+    for _ in range(rounds):
+        res["kernel"].append(time_launches(kernel, 5, iters)["median_ms"] * 1e3)
+        res["torch"].append(time_launches(composite, 5, iters)["median_ms"] * 1e3)
+
+    def side(v):
+        med = sorted(v)[len(v) // 2]
+        return {"median_us": round(med, 2), "min_us": round(min(v), 2), "max_us": round(max(v), 2),
+                "spread": round((max(v) - min(v)) / med, 4)}
+
+    out = {"model": model, "bs": bs, "H": H, "E": E, "topk": topk, "shared_gate": w_sg is not None,
+           "kernel": side(res["kernel"]), "torch": side(res["torch"])}
+    nbytes = bs * H * 2 + (E + 1) * H * 2 + bs * topk * 8 + (bs * 4 if w_sg is not None else 0)
+    out["bytes"] = nbytes
+    out["hbm_fraction"] = round(nbytes / (out["kernel"]["median_us"] * 1e-6) / HBM_ROOF_BYTES_PER_S, 4)
+    out["speedup"] = round(out["torch"]["median_us"] / out["kernel"]["median_us"], 3)
+    # the bar: the kernel's median no slower than the composite's, within the composite's own spread
+    out["meets_bar"] = bool(out["kernel"]["median_us"] <= out["torch"]["median_us"] * (1 + out["torch"]["spread"]))
+    out["rows_same_ids_as_torch"] = round(agree, 4)
     return out

@@ -1,0 +1,37 @@
+"""Print mxmoe_amd.moe.gate_bench (the router kernel against the torch composite) as JSON lines:
+    python tools/gate_bench.py [--bs 8192 128] [--models qwen2_moe ds2] [--out FILE]"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+from mxmoe_amd.moe import gate_bench  # noqa: E402
+
+
+def main() -> None:
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--bs", type=int, nargs="+", default=[8192, 128])
+    ap.add_argument("--models", nargs="+", default=["qwen2_moe", "ds2"])
+    ap.add_argument("--rounds", type=int, default=4)
+    ap.add_argument("--iters", type=int, default=30)
+    ap.add_argument("--out", default=None, help="also write the list of results to this JSON file")
+    a = ap.parse_args()
+    results = []
+    for model in a.models:
+        for bs in a.bs:
+            r = gate_bench(bs=bs, model=model, rounds=a.rounds, iters=a.iters)
+            results.append(r)
+            print(json.dumps(r), flush=True)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump(results, f, indent=1)
+            f.write("\n")
+
+
+if __name__ == "__main__":
+    main()
