@@ -15,6 +15,8 @@
  *          unspecified), C = fp16_rn(0.f + acc * f32(fp16_rn(sa[m] * sb[n])))
  *   bf16 (fmt MXMOE_GG_FMT_BF16): A,B bf16, fp32 accumulate, C = fp16_rn(acc) (C is fp16 for every
  *          type, as the reference's `half** ptr_Cs`)
+ *   w4a4_g32_sym_MXFP4 (fmt MXMOE_GG_FMT_MXFP4): A,B OCP MXFP4 (e2m1 codes, e8m0 scale per 32-K block),
+ *          f32 accumulate on the block-scaled fp4 MFMA, C = fp16_rn(acc); layouts at MXMOE_GG_FMT_MXFP4
  *
  * Data layout is byte-identical to the reference bench (SeaCatComplexes/MxMoE):
  *   - packed A/B words follow pack_wxax        (mxmoe/kernels/src/include/quantize.cuh:425-475)
@@ -59,8 +61,28 @@ enum {
 enum {
   MXMOE_GG_FMT_DEFAULT = 0, /* fp16 for 16-bit operands, two's-complement integers otherwise */
   MXMOE_GG_FMT_E4M3 = 1,    /* w8a8_g-1_sym_E4M3: OCP fp8 e4m3 codes                         */
-  MXMOE_GG_FMT_BF16 = 2     /* bf16: 16-bit operands are bfloat16                              */
+  MXMOE_GG_FMT_BF16 = 2,    /* bf16: 16-bit operands are bfloat16                              */
+  /* 3: fp6 images of int4 codes (tools-only lab library) */
+  MXMOE_GG_FMT_MXFP4 = 4    /* w4a4_g32_sym_MXFP4: OCP MXFP4, e2m1 codes + e8m0 block scales   */
 };
+
+/* MXFP4 operands (fmt MXMOE_GG_FMT_MXFP4; a_bits = w_bits = 4, gsize = 32, sym; K % 32 == 0).
+ *   codes : A uint8 [M][K/2], B uint8 [N][K/2] (lda / ldb in 16-bit words as for every type). Element
+ *           2i of a row is the low nibble of byte i, element 2i+1 the high nibble; a nibble is the OCP
+ *           e2m1 code: bit 3 the sign, bits 2..0 an index into {0, .5, 1, 1.5, 2, 3, 4, 6}.
+ *   scales: one OCP e8m0 byte per 32-element block, value 2^(code - 127), code 255 = NaN.
+ *           The CANONICAL layout (what the Python helpers quant_mxfp4 / dequant_mxfp4 speak) is
+ *           uint8 [rows][K/32]. scale_a / scale_b take the DEVICE layout (pack_mxfp4_scales):
+ *           uint8 [rows][G * 16] with G = ceil(K/32 / 16), 4-byte aligned; every 16-byte group of a row
+ *           is the canonical group transposed 4 x 4, dev[16 t + 4 g + i] = canon[16 t + 4 i + g]
+ *           (i, g < 4), and bytes for blocks past K/32 hold 127 (2^0) — never 255: the zero-filled
+ *           codes of a K tail times a NaN scale would poison the sum. Dword g of group t then holds,
+ *           for K group g of the MFMA (K = [32 g, 32 g + 32) of each 128), the scales of four
+ *           consecutive MFMAs: two 128-byte (K = 256) stages.
+ *   result: C[m][n] = fp16_rn(sum over blocks b of 2^(sa[m][b]-127) 2^(sb[n][b]-127)
+ *           sum_{k in b} a[m][k] b[n][k]), accumulated in f32 by the block-scaled MFMA (summation order
+ *           unspecified); no per-channel fp16 scales. Runs on the v2x variant only (AUTO picks it for
+ *           every call that holds an MXFP4 problem); no SiLU epilogue. */
 
 /* Epilogue flag, OR-ed into mxmoe_gg_problem.fmt (fp16, w8a8_g-1_sym and w4a4_g-1_sym problems on the
  * v2x, v3 and wo3 variants; weight-only WxA16 problems on wo3, whose scale_b is permuted with the rows;
@@ -114,7 +136,7 @@ typedef struct mxmoe_gg_plan_info {
   int32_t block;
   int32_t lds_bytes;
   int32_t qtype_mask;      /* bit q set if a planned problem has quant type q (0 fp16, 1 w8a8, 2 w4a4,
-                            * 3 w4a16, 4 w8a16, 5 w4a4_g128, 6 w2a16, 7 w8a8 E4M3, 8 bf16); bit 16:
+                            * 3 w4a16, 4 w8a16, 5 w4a4_g128, 6 w2a16, 7 w8a8 E4M3, 8 bf16, 10 MXFP4); bit 16:
                             * a weight-only problem carries MXMOE_GG_EPI_SILU_MUL (small-batch kernel);
                             * selects the kernel specialisation at launch */
   int32_t splitk_slabs;    /* 256-KiB partial-sum slabs the plan's split-K tiles use (0: no split) */

@@ -34,7 +34,11 @@ enum {
   MXMOE_ACT_FP16 = 0,    /* a_bits 16: the row is copied                                  */
   MXMOE_ACT_INT8 = 1,    /* a_bits 8, one scale per token                                 */
   MXMOE_ACT_INT4 = 2,    /* a_bits 4, one scale per token                                 */
-  MXMOE_ACT_INT4_G128 = 3 /* a_bits 4, one scale per (token, 128-element group)           */
+  MXMOE_ACT_INT4_G128 = 3, /* a_bits 4, one scale per (token, 128-element group)          */
+  MXMOE_ACT_MXFP4 = 4    /* OCP MXFP4 (w4a4_g32_sym_MXFP4): e2m1 codes, one e8m0 scale per (token,
+                          * 32-element block), quantised as include/mxmoe_gg.h defines; codes in the
+                          * canonical nibble order, scale bytes in the GroupGEMM's device layout;
+                          * through mxmoe_moe_act_quant with bit 4 of tag_mask only               */
 };
 
 /* One expert's segment of a permuted activation buffer. Slots (rows of the permuted batch) are
@@ -46,7 +50,9 @@ typedef struct mxmoe_moe_seg {
   int32_t rows;        /* tokens routed to this expert                                        */
   int32_t width;       /* elements per row of this segment's output (K of the next GEMM)      */
   int64_t out_off;     /* byte offset of the segment's [rows][width * bits / 8] block in `out` */
-  int64_t scale_off;   /* fp16-element offset of its scales: [rows] or [width/128][rows]      */
+  int64_t scale_off;   /* fp16-element offset of its scales: [rows] or [width/128][rows];
+                        * MXFP4: of its [rows][16 ceil(width/32 / 16)] e8m0 bytes (even offset: the
+                        * block is 4-byte aligned)                                              */
 } mxmoe_moe_seg;
 
 /* The router in front of the layer, one launch: gate logits, top-k selection, softmax weights and
@@ -122,6 +128,21 @@ int mxmoe_moe_silu_mul_quant_il(const void* routed_in, const void* shared_in, in
 int mxmoe_moe_quant_slots(const void* routed_in, const void* shared_in, int64_t T, int topk, int N, int N_shared,
                           const int32_t* sorted_expert, const mxmoe_moe_seg* segs, int nseg, void* out, void* scales,
                           void* stream);
+
+/* The four activation launches above behind one entry point that is told which tags the segments
+ * carry: tag_mask bit t is set when some segment has qtag t. REQUIRED for segments tagged
+ * MXMOE_ACT_MXFP4: the kernel builds with the MXFP4 code run only when bit 4 is set, so the four named
+ * entry points (and any call here without the bit) keep the builds they had before the tag existed
+ * and must not be given such a segment — they would treat it as int4. A mask with a bit above 4 is
+ * MXMOE_GG_ERR_UNSUPPORTED.
+ *   mode 0: mxmoe_moe_quant_act      (routed_in = hidden [T][N], N = K; shared_in != NULL <=> with_shared,
+ *                                     its value is ignored; perm_token required)
+ *   mode 1: mxmoe_moe_silu_mul_quant, 2: mxmoe_moe_quant_slots, 3: mxmoe_moe_silu_mul_quant_il
+ *           (arguments as there; perm_token unused)
+ * (No reference counterpart.) */
+int mxmoe_moe_act_quant(int mode, const void* routed_in, const void* shared_in, int64_t T, int topk, int N, int N_shared,
+                        const int32_t* sorted_expert, const int32_t* perm_token, const mxmoe_moe_seg* segs, int nseg,
+                        uint32_t tag_mask, void* out, void* scales, void* stream);
 
 /* out[t][h] = fp16_rn(acc), acc = +0 then, for k = 0..topk-1 in order,
  *   acc = fma(weights[t][k], f32(y[inv_slot[t*topk + k]][h]), acc),

@@ -27,6 +27,7 @@ MXMOE_GG_ERR_HIP = 4
 # operand formats (MXMOE_GG_FMT_*): fp16 / integer, OCP fp8 e4m3, bfloat16; FMT_F6 (w4a4 as fp6
 # images, gg_f6.h) is understood by the lab library only (measured slower)
 FMT_DEFAULT, FMT_E4M3, FMT_BF16, FMT_F6 = 0, 1, 2, 3
+FMT_MXFP4 = 4  # MXMOE_GG_FMT_MXFP4: w4a4_g32_sym_MXFP4 (OCP e2m1 codes, e8m0 scale per 32-K block)
 EPI_SILU_MUL = 0x100  # MXMOE_GG_EPI_SILU_MUL: fmt flag, C = silu(gate) * up (include/mxmoe_gg.h)
 
 
@@ -92,6 +93,7 @@ EXPORTED_SYMBOLS = (
     "mxmoe_gg_plan_tiles",
     # include/mxmoe_moe.h (MoE-layer plumbing)
     "mxmoe_moe_route", "mxmoe_moe_quant_act", "mxmoe_moe_silu_mul_quant", "mxmoe_moe_silu_mul_quant_il", "mxmoe_moe_quant_slots", "mxmoe_moe_combine",
+    "mxmoe_moe_act_quant",
     "mxmoe_moe_gate",
 )
 
@@ -168,6 +170,10 @@ def _declare(lib: ctypes.CDLL) -> None:
         if hasattr(lib, fn):  # (builds before round 5's fused SiLU epilogue lack them: A/B tools)
             getattr(lib, fn).restype = c.c_int
             getattr(lib, fn).argtypes = [P, P, c.c_int64, c.c_int, c.c_int, c.c_int, P, P, c.c_int, P, P, P]
+    if hasattr(lib, "mxmoe_moe_act_quant"):  # (the tagged activation entry; builds before MXFP4 lack it: A/B tools)
+        lib.mxmoe_moe_act_quant.restype = c.c_int
+        lib.mxmoe_moe_act_quant.argtypes = [c.c_int, P, P, c.c_int64, c.c_int, c.c_int, c.c_int, P, P, P, c.c_int, c.c_uint32,
+                                            P, P, P]
     if hasattr(lib, "mxmoe_moe_gate"):  # (the router; builds before it lack the symbol: A/B tools)
         lib.mxmoe_moe_gate.restype = c.c_int
         lib.mxmoe_moe_gate.argtypes = [P, P, P, c.c_int64, c.c_int, c.c_int, c.c_int, c.c_int, P, P, P, P, P]

@@ -12,6 +12,8 @@ depends only on A[rows] and B[cols]), for every quant type the library runs:
     do, fp16(fma(u - off, scale, zp)) (quantize.cuh:146-213), then an f64 GEMM — fp16 tolerance;
   * w8a8 E4M3: e4m3 codes decoded, exact f64 dot products rounded to f32, the wxax epilogue — fp16
     tolerance (the MFMA's f32 summation order is unspecified);
+  * MXFP4 (w4a4_g32_sym_MXFP4): e2m1 codes and e8m0 block scales decoded (dequant_mxfp4), f64 GEMM —
+    fp16 tolerance (f32 accumulation in the MFMA, order unspecified);
   * fp16 / bf16: f64 GEMM — relative 1e-3 (north_star) with a cancellation floor.
 
 Unlike the reference's CHECK (abs tol 1.0 against an unquantised cutlass GEMM), integer paths must
@@ -22,7 +24,7 @@ from __future__ import annotations
 import numpy as np
 import torch
 
-from .quantize import dequant_weightonly, unpack_wxax, unpack_weightonly_mi355x
+from .quantize import dequant_mxfp4, dequant_weightonly, unpack_mxfp4_scales, unpack_wxax, unpack_weightonly_mi355x
 
 
 def _f16_close(out: torch.Tensor, ref: torch.Tensor, what: str) -> None:
@@ -50,6 +52,11 @@ def expected_sample(p, rows: torch.Tensor, cols: torch.Tensor) -> tuple[torch.Te
         return A.double() @ Bdq.double().T, False
     if not q.is_quant:
         return A.double() @ p.B.index_select(0, cols).cpu().double().T, False
+    if q.fmt == "MXFP4":
+        def deq(codes, scales):
+            return dequant_mxfp4(codes, unpack_mxfp4_scales(scales, p.K))
+        return deq(A, p.scale_a.index_select(0, rows).cpu()) @ \
+            deq(p.B.index_select(0, cols).cpu(), p.scale_b.index_select(0, cols).cpu()).T, False
     if q.is_fp8:
         def dec(t):
             return unpack_wxax(t, 8, p.K).view(torch.float8_e4m3fn).double()

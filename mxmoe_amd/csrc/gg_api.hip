@@ -133,6 +133,13 @@ void launch_v2(const GGArgs& a, int grid, int qmask, hipStream_t s) {
         abort();
     }
 #else
+    // MXFP4 problems (plan-info bit 10, above the mask below): a kernel of their own, or every tile
+    // body beside them — builds apart from the existing ones, which come out unchanged
+    if (qmask & (1 << QT_MXF4)) {
+      if ((qmask & 2047) == (1 << QT_MXF4)) launch_v2_q<ABL, (1 << QT_MXF4)>(a, grid, s);
+      else launch_v2_q<0, 511 | (1 << QT_MXF4)>(a, grid, s);
+      return;
+    }
     switch (qmask & 511) {
       case 1: launch_v2_q<ABL, 1>(a, grid, s); break;
       case 2: launch_v2_q<ABL, 2>(a, grid, s); break;
@@ -278,7 +285,7 @@ Variant make_v0(const char* name) {
   v.geom[QT_F16] = {C16::BM, C16::BN, C16::BKB, C16::kThreads};
   v.geom[QT_I8] = {C8::BM, C8::BN, C8::BKB, C8::kThreads};
   v.geom[QT_I4] = {C4::BM, C4::BN, C4::BKB, C4::kThreads};
-  for (int q : {QT_W4A16, QT_W8A16, QT_I4G, QT_W2A16, QT_F8, QT_BF16, QT_I4F6}) v.geom[q] = {0, 0, 0, 0};  // v2 kernels only
+  for (int q : {QT_W4A16, QT_W8A16, QT_I4G, QT_W2A16, QT_F8, QT_BF16, QT_I4F6, QT_MXF4}) v.geom[q] = {0, 0, 0, 0};  // v2 kernels only
   v.threads = C16::kThreads;
   v.lds_bytes = FusedCfg<C16, C8, C4>::LDS_BYTES;
   v.chunk = FusedCfg<C16, C8, C4>::LDS_BYTES <= 80 * 1024 ? 64 : 32;  // workgroups per XCD at once
@@ -295,7 +302,7 @@ Variant make_v3(const char* name) {
   v.name = name;
   v.kind = Kind::V3;
   for (int q = 0; q < QT_COUNT; ++q) v.geom[q] = {256, BN, 64, CT::NT};  // (weight-only / g128 / fp8 / bf16 cleared below)
-  for (int q : {QT_W4A16, QT_W8A16, QT_I4G, QT_W2A16, QT_F8, QT_BF16, QT_I4F6}) v.geom[q] = {0, 0, 0, 0};  // v2 kernels only
+  for (int q : {QT_W4A16, QT_W8A16, QT_I4G, QT_W2A16, QT_F8, QT_BF16, QT_I4F6, QT_MXF4}) v.geom[q] = {0, 0, 0, 0};  // v2 kernels only
   v.threads = CT::NT;
   v.lds_bytes = CT::LDS_BYTES;
   v.chunk = 32 * (160 * 1024 / CT::LDS_BYTES >= 2 ? 2 : 1);  // workgroups per XCD at once
@@ -343,6 +350,9 @@ Variant v2_base(const char* name, int lds_bytes) {
   v.geom[QT_W2A16] = {256, 256, 16, 512};  // 64-K stages: 16 B of 2-bit codes per row
   v.geom[QT_I4G] = {256, 256, 128, 512};  // w4a4 g128 (gg_tile_g128): 256 / 128-row classes as int4
   v.geom[QT_I4F6] = {0, 0, 0, 0};         // fp6 images: the f6 kernel only
+#ifdef MXMOE_LAB
+  v.geom[QT_MXF4] = {0, 0, 0, 0};         // (the lab library's launch tables carry no MXFP4 build)
+#endif
   v.threads = 512;
   v.lds_bytes = lds_bytes;
   v.chunk = 32;  // one 512-thread workgroup per CU, 32 CUs per XCD
@@ -389,6 +399,7 @@ Variant make_wo2(const char* name) {
 template <int TRACE = 0>
 Variant make_v2p(const char* name) {
   Variant v = make_v2<V2_STAGGER | V2_B3 | V2_BUF | V2_EARLYDMA | (4 << V2_SPREAD_SHIFT)>(name);
+  v.geom[QT_MXF4] = {0, 0, 0, 0};  // (no MXFP4 body in the persistent kernels)
   v.persistent = true;
   v.lds_bytes = 160 * 1024;
   v.launch = &launch_v2p<TRACE>;
@@ -627,6 +638,14 @@ int qtype_of(int a_bits, int w_bits, int gsize, int sym, int fmt, int* qt) {
     return fail(MXMOE_GG_ERR_UNSUPPORTED, "quant type not supported: w%da%d bf16 (only 16-bit bf16 operands)", w_bits,
                 a_bits);
   }
+  if (fmt == MXMOE_GG_FMT_MXFP4) {  // OCP MXFP4: e2m1 codes, one e8m0 scale per 32-K block
+    if (a_bits == 4 && w_bits == 4 && gsize == 32 && sym) {
+      *qt = QT_MXF4;
+      return MXMOE_GG_OK;
+    }
+    return fail(MXMOE_GG_ERR_UNSUPPORTED, "quant type not supported: w%da%d_g%d_%s_MXFP4 (only w4a4_g32_sym_MXFP4)",
+                w_bits, a_bits, gsize, sym ? "sym" : "asym");
+  }
 #ifdef MXMOE_LAB
   if (fmt == MXMOE_GG_FMT_F6) {  // w4a4_g-1_sym with fp6 images of the int4 codes (mxmoe_gg_pack_f6)
     if (a_bits == 4 && w_bits == 4 && gsize == -1 && sym) {
@@ -762,7 +781,7 @@ int build_meta(const HostProblem& p, int idx, const Variant& v, bool check_ptrs,
                 idx, v.name, v.k_stage_bytes, p.K);
   if (qt == QT_I4G && p.K % 128 != 0)
     return fail(MXMOE_GG_ERR_INVALID, "problem %d: w4a4_g128 needs K %% 128 == 0 (K=%d)", idx, p.K);
-  if (qt != QT_F16 && qt != QT_BF16 && qt != QT_F8 && p.K > 131072)
+  if (qt != QT_F16 && qt != QT_BF16 && qt != QT_F8 && qt != QT_MXF4 && p.K > 131072)
     return fail(MXMOE_GG_ERR_INVALID, "problem %d: K=%d exceeds the exact int32 accumulation bound 131072", idx, p.K);
   if (p.N % 8 != 0) return fail(MXMOE_GG_ERR_INVALID, "problem %d: N=%d must be a multiple of 8", idx, p.N);
   // fp6 images: 96 B per K-128 block, K padded to whole blocks (mxmoe_gg_pack_f6)
@@ -789,6 +808,8 @@ int build_meta(const HostProblem& p, int idx, const Variant& v, bool check_ptrs,
       return fail(MXMOE_GG_ERR_INVALID, "problem %d: A/B/C must be 16-byte aligned", idx);
     if (!is_float16(qt) && (((uintptr_t)p.SA | (uintptr_t)p.SB) & 1))
       return fail(MXMOE_GG_ERR_INVALID, "problem %d: scales must be 2-byte aligned", idx);
+    if (qt == QT_MXF4 && (((uintptr_t)p.SA | (uintptr_t)p.SB) & 3))  // (the kernel reads scale dwords)
+      return fail(MXMOE_GG_ERR_INVALID, "problem %d: MXFP4 scales must be 4-byte aligned", idx);
   }
   memset(m, 0, sizeof(*m));
   m->M = p.M;
@@ -846,6 +867,7 @@ int plan_host(const std::vector<HostProblem>& probs, int variant, bool check_ptr
     const GGMeta& m = all[i];
     // int4: 2 MFMA passes per staged byte; g128 adds the per-group f32 fold (~25 %); fp6 images:
     // one fp6 MFMA (the int8 one's cycles) per 96 B of K-128
+    // (MXFP4: per stage the MFMA count and cycles of the int8 tile, so 1.0)
     const double passes = m.qtype == QT_I4 ? 2.0 : m.qtype == QT_I4G ? 2.5 : m.qtype == QT_I4F6 ? 128.0 / 96 / 2 : 1.0;
     return passes * (double)m.kbytes * v.geom[m.qtype].bm * v.geom[m.qtype].bn;
   };
@@ -916,7 +938,7 @@ int plan_host(const std::vector<HostProblem>& probs, int variant, bool check_ptr
     } else {
       const double kel = m.qtype == QT_I4F6 ? 128.0
                        : g.bkb * 8.0 / (is_float16(m.qtype) ? 16 : (m.qtype == QT_I8 || m.qtype == QT_F8) ? 8 : 4);
-      const double rate = is_float16(m.qtype) ? 128 : m.qtype == QT_I4F6 ? 512 : 256, fold = m.qtype == QT_I4G ? 1.25 : 1.0;
+      const double rate = is_float16(m.qtype) ? 128 : (m.qtype == QT_I4F6 || m.qtype == QT_MXF4) ? 512 : 256, fold = m.qtype == QT_I4G ? 1.25 : 1.0;
       bytes = (rows + cols) * g.bkb;
       equiv = 2.0 * rows * cols * kel / rate * fold;
     }
@@ -1465,7 +1487,10 @@ int resolve_variant(int variant, const std::vector<HostProblem>& hp, int* out) {
   int mask = 0;
   for (const HostProblem& p : hp) {
     int qt;
-    if (p.M > 0 && qtype_of(p.a_bits, p.w_bits, p.gsize, p.sym, p.fmt, &qt) == MXMOE_GG_OK) mask |= 1 << qt;
+    if (qtype_of(p.a_bits, p.w_bits, p.gsize, p.sym, p.fmt, &qt) != MXMOE_GG_OK) continue;
+    // (an MXFP4 problem counts even when empty: only v2x plans it, and every variant checks a
+    // problem's type before its shape)
+    if (p.M > 0 || qt == QT_MXF4) mask |= 1 << qt;
   }
   *out = variant_index(kDefaultVariantName);
   const int wo_mask = (1 << QT_W4A16) | (1 << QT_W8A16) | (1 << QT_W2A16);
@@ -1605,8 +1630,9 @@ int mxmoe_gg_default_variant(void) { return variant_index(kDefaultVariantName); 
 int mxmoe_gg_list_variants(char* buf, size_t n) {
   // weight-only kernels cover every group size / sym of a bit width: listed under the base name
   static const char* qnames[QT_COUNT] = {"fp16",          "w8a8_g-1_sym", "w4a4_g-1_sym",      "w4a16", "w8a16",
-                                         "w4a4_g128_sym", "w2a16",        "w8a8_g-1_sym_E4M3", "bf16",  "w4a4_g-1_sym_F6"};
-  static const int wbits[QT_COUNT] = {16, 8, 4, 4, 8, 4, 2, 8, 16, 6};
+                                         "w4a4_g128_sym", "w2a16",        "w8a8_g-1_sym_E4M3", "bf16",  "w4a4_g-1_sym_F6",
+                                         "w4a4_g32_sym_MXFP4"};
+  static const int wbits[QT_COUNT] = {16, 8, 4, 4, 8, 4, 2, 8, 16, 6, 4};
   std::string out;
   const auto& vs = variants();
   for (size_t i = 0; i < vs.size(); ++i) {

@@ -36,10 +36,12 @@ namespace mxmoe {
 // QT_BF16: bf16 A and B, f32 accumulate, fp16 C
 // QT_I4F6: w4a4_g-1_sym with A and B given as fp6 e3m2 images of the int4 codes (gg_f6.h): the
 //          block-scaled fp6 MFMA, f32 accumulate (exact: integer partial sums below 2^24)
+// QT_MXF4: w4a4_g32_sym_MXFP4 (A and B OCP MXFP4: e2m1 codes, one e8m0 scale per 32-K block; the
+//          block-scaled fp4 MFMA applies the scales, f32 accumulate, C = fp16_rn(acc))
 enum QType : int32_t {
   QT_F16 = 0, QT_I8 = 1, QT_I4 = 2, QT_W4A16 = 3, QT_W8A16 = 4, QT_I4G = 5, QT_W2A16 = 6, QT_F8 = 7, QT_BF16 = 8,
-  QT_I4F6 = 9,
-  QT_COUNT = 10
+  QT_I4F6 = 9, QT_MXF4 = 10,
+  QT_COUNT = 11
 };
 // quant types whose epilogue applies the per-channel scales sa[m] * sb[n]
 constexpr bool qt_scaled(int qt) { return qt == QT_I8 || qt == QT_I4 || qt == QT_F8 || qt == QT_I4F6; }
@@ -169,12 +171,24 @@ template <>
 struct AccT<QT_I4F6> {
   typedef v4f type;
 };
+template <>
+struct AccT<QT_MXF4> {
+  typedef v4f type;
+};
 
 // fp8 e4m3 x e4m3 over K = 128 (one 128-B v2 stage), f32 accumulate: the block-scaled MFMA with
 // every 32-element block scale = 2^0 (e8m0 code 127), i.e. the plain fp8 dot product at twice the
 // bf16 MFMA rate (MI355X_MICROARCH.md, Matrix cores). Format code 0 = fp8 e4m3 for both operands.
 __device__ __forceinline__ v4f mfma_f8_k128(const v8i& b, const v8i& a, const v4f& c) {
   return __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(b, a, c, 0, 0, 0, 127, 0, 127);
+}
+// OCP MXFP4 over K = 128: fp4 e2m1 operands (format code 4; 16 B = 32 codes per lane in the low
+// half of the operand, the compiler allocates 4 VGPRs), lane (row r, K group g) supplies the block
+// K = [32 g, 32 g + 32) and byte SEL of its scale registers is that block's e8m0 scale.
+template <int SEL>
+__device__ __forceinline__ v4f mfma_mxf4_k128(const v4i& b, uint32_t sb, const v4i& a, uint32_t sa, const v4f& c) {
+  const v8i bw = {b[0], b[1], b[2], b[3], 0, 0, 0, 0}, aw = {a[0], a[1], a[2], a[3], 0, 0, 0, 0};
+  return __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(bw, aw, c, 4, 4, SEL, (int)sb, SEL, (int)sa);
 }
 __device__ __forceinline__ v8i cat_v4i(const v4i& lo, const v4i& hi) {
   return v8i{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
@@ -975,6 +989,42 @@ __device__ __forceinline__ void gg_tile_v2(const GGMeta& mt, const uint8_t* __re
 #else
   const bool wave_dead = false;
 #endif
+  // MXFP4: the e8m0 block scales come by direct dword loads, one per fragment row per two stages
+  // (device layout: rows of 16-B groups, dword g of group t = K group g's scales of stages 2 t and
+  // 2 t + 1), issued with an odd stage's LDS-DMA for the next two stages and landed by the same
+  // vmcnt(0) + barrier. Buffer loads with the WHOLE byte offset (fragment row, row r16, scale group,
+  // K group g) in the vector offset and a zero scalar offset: a raw buffer's range check covers the
+  // vector offset only, and num_records ends at the tile's last valid row, so a row past M / N (never
+  // stored) reads as zeros and no load leaves the caller's scale array. mx_sa / mx_sb hold the
+  // current stage's two scale bytes in bytes 0 and 1 (an odd stage shifts its pair down).
+  constexpr int MXN = QT == QT_MXF4 ? 1 : 0;
+  [[maybe_unused]] uint32_t mx_sa[MXN * FM + 1], mx_sb[MXN * FN + 1], mx_na[MXN * FM + 1], mx_nb[MXN * FN + 1];
+  [[maybe_unused]] const int mx_srow = ((mt.K / 32 + 15) >> 4) << 4;  // scale bytes per row
+  [[maybe_unused]] const int mx_va = (wm * Cfg::WTM + r16) * mx_srow + 4 * g, mx_vb = (wn * Cfg::WTN + r16) * mx_srow + 4 * g;
+  [[maybe_unused]] auto mx_load = [&](int stage) {  // the scale dwords of absolute K stage `stage` and its pair
+    if constexpr (QT == QT_MXF4) {
+      const __amdgpu_buffer_rsrc_t rsa = __builtin_amdgcn_make_buffer_rsrc(
+          const_cast<uint8_t*>(reinterpret_cast<const uint8_t*>(SA)) + (int64_t)m0 * mx_srow, (short)0,
+          min(M - m0, Cfg::BM) * mx_srow, 0x00020000);
+      const __amdgpu_buffer_rsrc_t rsb = __builtin_amdgcn_make_buffer_rsrc(
+          const_cast<uint8_t*>(reinterpret_cast<const uint8_t*>(SB)) + (int64_t)n0 * mx_srow, (short)0,
+          min(N - n0, Cfg::BN) * mx_srow, 0x00020000);
+      const int t = (stage >> 1) * 16;
+#pragma unroll
+      for (int i = 0; i < FM; ++i) mx_na[i] = __builtin_amdgcn_raw_buffer_load_b32(rsa, mx_va + i * 16 * mx_srow + t, 0, 0);
+#pragma unroll
+      for (int j = 0; j < FN; ++j) mx_nb[j] = __builtin_amdgcn_raw_buffer_load_b32(rsb, mx_vb + j * 16 * mx_srow + t, 0, 0);
+    }
+  };
+  [[maybe_unused]] auto mx_take = [&](int stage) {  // before computing `stage`; an even one's mx_load has landed
+    if constexpr (QT == QT_MXF4) {
+      const bool odd = (stage & 1) != 0;
+#pragma unroll
+      for (int i = 0; i < FM; ++i) mx_sa[i] = odd ? mx_na[i] >> 16 : mx_na[i];
+#pragma unroll
+      for (int j = 0; j < FN; ++j) mx_sb[j] = odd ? mx_nb[j] >> 16 : mx_nb[j];
+    }
+  };
   auto compute = [&](int buf) {
     if (wave_dead) return;
     const uint8_t* As = lds + buf * Cfg::STAGE_BYTES + a_row;
@@ -993,6 +1043,27 @@ __device__ __forceinline__ void gg_tile_v2(const GGMeta& mt, const uint8_t* __re
                               *reinterpret_cast<const v4i*>(As + i * 2048 + off1));
 #pragma unroll
         for (int j = 0; j < FN; ++j) acc[i][j] = mfma_f8_k128(b[j], a, acc[i][j]);
+      }
+    } else if constexpr (QT == QT_MXF4) {
+      // a 128-B stage row is K = 256 = 8 MX blocks, one per 16-B chunk: per fragment pair MFMA 1 on
+      // chunk g, MFMA 2 on chunk 4 + g (the int8 path's two K halves), each lane's 16 B one block.
+      // Bytes 0 and 1 of mx_sa / mx_sb are the scales of this stage's two MFMAs (mx_take).
+      const uint32_t off0 = (uint32_t)((g ^ swz) << 4), off1 = (uint32_t)(((4 + g) ^ swz) << 4);
+      v4i b0[FN], b1[FN];
+#pragma unroll
+      for (int j = 0; j < FN; ++j) {
+        b0[j] = *reinterpret_cast<const v4i*>(Bs + j * 2048 + off0);
+        b1[j] = *reinterpret_cast<const v4i*>(Bs + j * 2048 + off1);
+      }
+#pragma unroll
+      for (int i = 0; i < FM; ++i) {
+        const v4i a0 = *reinterpret_cast<const v4i*>(As + i * 2048 + off0);
+        const v4i a1 = *reinterpret_cast<const v4i*>(As + i * 2048 + off1);
+#pragma unroll
+        for (int j = 0; j < FN; ++j) {
+          acc[i][j] = mfma_mxf4_k128<0>(b0[j], mx_sb[j], a0, mx_sa[i], acc[i][j]);
+          acc[i][j] = mfma_mxf4_k128<1>(b1[j], mx_sb[j], a1, mx_sa[i], acc[i][j]);
+        }
       }
     } else if constexpr (QT == QT_I4) {
       // two 64-B halves; lane group g reads chunk (4 kc + g) ^ swz (16 B, as the int8 path) and
@@ -1467,10 +1538,21 @@ __device__ __forceinline__ void gg_tile_v2(const GGMeta& mt, const uint8_t* __re
   } else if (nst > 0) {
     // ---- mainloop: stage s+1 in flight (LDS-DMA) while stage s is consumed ----
     issue(0, 0);
+    mx_load(ks0);
     __syncthreads();  // vmcnt(0) + barrier: stage 0 landed for every wave
     stash_scale();
+    if constexpr (QT == QT_MXF4) mx_take(ks0);
     for (int s = 0; s < nst; ++s) {
       if (s + 1 < nst) issue(s + 1, (s + 1) & 1);
+      if constexpr (QT == QT_MXF4) {
+        // an even next stage starts a new scale group: its dwords load under this stage's MFMAs
+        const bool next_even = ((ks0 + s + 1) & 1) == 0;
+        if (next_even && s + 1 < nst) mx_load(ks0 + s + 1);
+        compute(s & 1);
+        __syncthreads();
+        if (s + 1 < nst) mx_take(ks0 + s + 1);
+        continue;
+      }
       compute(s & 1);
       if constexpr ((ABL & ABL_B_REGLOAD) != 0) {
 #pragma unroll
@@ -1503,7 +1585,7 @@ __device__ __forceinline__ void gg_tile_v2(const GGMeta& mt, const uint8_t* __re
     for (int j = 0; j < FN; ++j) sbw[j] = *reinterpret_cast<const uint2*>(sl + 256 + wn * Cfg::WTN + j * 16 + 4 * e_g);
   }
   auto pack_frag = [&](int i, int j, _Float16 sai) {
-    if constexpr (QT == QT_F16 || QT == QT_BF16) return pack4_f16(acc[i][j]);
+    if constexpr (QT == QT_F16 || QT == QT_BF16 || QT == QT_MXF4) return pack4_f16(acc[i][j]);
     else if constexpr (QT == QT_F8) return scale_pack4f(acc[i][j], sai, sbw[j]);
     else return scale_pack4<(QT == QT_I4) ? 8 : 0>(acc[i][j], sai, sbw[j]);
   };
@@ -2914,6 +2996,11 @@ __global__ __launch_bounds__(512, 2) void gg_v2_kernel(GGArgs args) {
     if (cls == 0) gg_tile_wo<WoCfg<256>, 2, WP>(mt, A, B, SB, C, td.m0, td.n0, lds, sk);
     else if (cls == 1) gg_tile_wo<WoCfg<128, 1>, 2, WP>(mt, A, B, SB, C, td.m0, td.n0, lds, sk);
     else gg_tile_wo<WoCfg<64, 1>, 2, WP>(mt, A, B, SB, C, td.m0, td.n0, lds, sk);
+  } else if ((QM & (1 << QT_MXF4)) && mt.qtype == QT_MXF4) {
+    // as E4M3: K = 128 MFMAs on whole 16-B chunks, no K halves to stagger -> the plain v2 mainloop
+    constexpr int MXABL = ABL & ~(V2_STAGGER | V2_B3);
+    if (cls == 0) gg_tile_v2<V2Cfg<256>, QT_MXF4, MXABL>(mt, A, B, SA, SB, C, td.m0, td.n0, lds, sk);
+    else gg_tile_v2<V2Cfg<128>, QT_MXF4, MXABL>(mt, A, B, SA, SB, C, td.m0, td.n0, lds, sk);  // no 64-row class
   }
   if constexpr ((ABL & V2_TRACE) != 0) {
     if (threadIdx.x == 0 && blockIdx.x < kTraceBlocks) {

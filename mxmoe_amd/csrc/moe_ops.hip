@@ -218,7 +218,9 @@ __device__ __forceinline__ float amax8(const h8_t& x) {
 // GroupGEMM's fused SiLU epilogue, routed [T*topk][N], shared [T][Ns]); 3: silu_mul_quant on a
 // gate_up output whose gate / up columns alternate in 16-column blocks (the interleaved weights of
 // the fused epilogue, run through the plain epilogue: small-batch calls on wo3)
-template <int MODE, int MAXC>
+// MX: the build that also carries the MXMOE_ACT_MXFP4 tag (launched only for calls whose segments hold
+// one, mxmoe_moe_act_quant: the other tags' builds stay as they are without it)
+template <int MODE, int MAXC, bool MX = false>
 __global__ __launch_bounds__(kThreads) void act_quant_kernel(ActArgs a) {
   constexpr bool SILU = MODE == 1 || MODE == 3;
   __shared__ float wave_amax[kThreads / 64];
@@ -292,6 +294,53 @@ __global__ __launch_bounds__(kThreads) void act_quant_kernel(ActArgs a) {
     for (int c = 0; c < MAXC; ++c) {
       const int idx = c * 512 + lane * 8;
       if (idx < width) *reinterpret_cast<h8_t*>(o + idx) = x[c];
+    }
+    return;
+  }
+  if constexpr (MX) if (sg.qtag == MXMOE_ACT_MXFP4) {
+    // OCP MXFP4 (include/mxmoe_gg.h): a 32-element block is 4 adjacent lanes. Block amax on the
+    // sign-cleared fp16 bit patterns as integers (their order is the values', with Inf / NaN on top),
+    // e = floor(log2 amax) - 2 from the exponent field of f32(amax) (the conversion normalises fp16
+    // subnormals), elements scaled by 2^-e exactly and rounded to the e2m1 grid with v_rndne (an even
+    // multiple of the grid step is an even code in each of the three segments).
+    const int srow = ((sg.width / 32 + 15) >> 4) << 4;  // scale bytes per row (device layout)
+    uint8_t* const o4 = a.out + sg.out_off + (row * (int64_t)sg.width + col0) / 2;
+    uint8_t* const so = reinterpret_cast<uint8_t*>(a.scales + sg.scale_off) + row * (int64_t)srow;
+    const int nblk = sg.width / 32;
+#pragma unroll
+    for (int c = 0; c < MAXC; ++c) {
+      if (c * 512 >= width) break;  // uniform
+      const int idx = c * 512 + lane * 8;
+      const uint4 w = __builtin_bit_cast(uint4, x[c]);
+      const uint32_t cm = 0x7FFF7FFFu;
+      uint32_t m2 = max(max((w.x & cm) & 0xFFFFu, (w.x & cm) >> 16), max((w.y & cm) & 0xFFFFu, (w.y & cm) >> 16));
+      m2 = max(m2, max(max((w.z & cm) & 0xFFFFu, (w.z & cm) >> 16), max((w.w & cm) & 0xFFFFu, (w.w & cm) >> 16)));
+      m2 = max(m2, (uint32_t)__shfl_xor((int)m2, 1, 64));
+      m2 = max(m2, (uint32_t)__shfl_xor((int)m2, 2, 64));
+      if (idx >= width) continue;
+      const bool bad = m2 >= 0x7C00u;  // an Inf or a NaN in the block: NaN scale, zero codes
+      const float am = (float)__builtin_bit_cast(_Float16, (uint16_t)m2);
+      const int e = m2 == 0 ? -127 : (int)((__builtin_bit_cast(uint32_t, am) >> 23) & 0xFF) - 127 - 2;
+      const float inv = __builtin_bit_cast(float, (uint32_t)(127 - e) << 23);  // 2^-e (e in [-127, 13])
+      uint32_t q = 0;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const float y = (float)x[c][j] * inv;  // exact
+        const float ay = fminf(fabsf(y), 6.0f);
+        const float r = ay < 2.0f ? __builtin_rintf(ay * 2.0f)
+                      : ay < 4.0f ? 2.0f + __builtin_rintf(ay) : 4.0f + __builtin_rintf(ay * 0.5f);
+        const uint32_t nib = (uint32_t)r | ((__builtin_bit_cast(uint32_t, y) >> 28) & 8u);
+        q |= nib << (4 * j);
+      }
+      *reinterpret_cast<uint32_t*>(o4 + idx / 2) = bad ? 0u : q;
+      if ((lane & 3) == 0) {
+        const int blk = (col0 + idx) >> 5, c16 = blk & 15;
+        so[(blk & ~15) + 4 * (c16 & 3) + (c16 >> 2)] = bad ? (uint8_t)255 : (uint8_t)(e + 127);
+        if (blk == nblk - 1) {  // the row's last block: the pads of its 16-byte group are 2^0
+#pragma clang loop unroll(disable) vectorize(disable)
+          for (int pc = c16 + 1; pc < 16; ++pc) so[(blk & ~15) + 4 * (pc & 3) + (pc >> 2)] = 127;
+        }
+      }
     }
     return;
   }
@@ -385,37 +434,39 @@ bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 using namespace mxmoe;
 
 // registers sized to the widest row of the launch, in 512-element chunks (1408 -> 3, 2048 -> 4)
-template <int MODE>
+template <int MODE, bool MX>
 static void launch_act_w(const ActArgs& a, int maxw, hipStream_t st) {
   const int64_t blocks = a.parts > 1 ? a.blk_shared + (a.nslots - a.ntk)
                                      : (a.nslots - a.s0 + kThreads / 64 - 1) / (kThreads / 64);
   const dim3 grid((unsigned)blocks), block(kThreads);
   const int nc = (maxw + 511) / 512;
-  if (nc <= 1) hipLaunchKernelGGL((act_quant_kernel<MODE, 1>), grid, block, 0, st, a);
-  else if (nc <= 2) hipLaunchKernelGGL((act_quant_kernel<MODE, 2>), grid, block, 0, st, a);
-  else if (nc <= 3) hipLaunchKernelGGL((act_quant_kernel<MODE, 3>), grid, block, 0, st, a);
-  else if (nc <= 4) hipLaunchKernelGGL((act_quant_kernel<MODE, 4>), grid, block, 0, st, a);
-  else if (nc <= 6) hipLaunchKernelGGL((act_quant_kernel<MODE, 6>), grid, block, 0, st, a);
-  else if (nc <= 8) hipLaunchKernelGGL((act_quant_kernel<MODE, 8>), grid, block, 0, st, a);
-  else if (nc <= 12) hipLaunchKernelGGL((act_quant_kernel<MODE, 12>), grid, block, 0, st, a);
-  else if (nc <= 16) hipLaunchKernelGGL((act_quant_kernel<MODE, 16>), grid, block, 0, st, a);
-  else hipLaunchKernelGGL((act_quant_kernel<MODE, 32>), grid, block, 0, st, a);
+  if (nc <= 1) hipLaunchKernelGGL((act_quant_kernel<MODE, 1, MX>), grid, block, 0, st, a);
+  else if (nc <= 2) hipLaunchKernelGGL((act_quant_kernel<MODE, 2, MX>), grid, block, 0, st, a);
+  else if (nc <= 3) hipLaunchKernelGGL((act_quant_kernel<MODE, 3, MX>), grid, block, 0, st, a);
+  else if (nc <= 4) hipLaunchKernelGGL((act_quant_kernel<MODE, 4, MX>), grid, block, 0, st, a);
+  else if (nc <= 6) hipLaunchKernelGGL((act_quant_kernel<MODE, 6, MX>), grid, block, 0, st, a);
+  else if (nc <= 8) hipLaunchKernelGGL((act_quant_kernel<MODE, 8, MX>), grid, block, 0, st, a);
+  else if (nc <= 12) hipLaunchKernelGGL((act_quant_kernel<MODE, 12, MX>), grid, block, 0, st, a);
+  else if (nc <= 16) hipLaunchKernelGGL((act_quant_kernel<MODE, 16, MX>), grid, block, 0, st, a);
+  else hipLaunchKernelGGL((act_quant_kernel<MODE, 32, MX>), grid, block, 0, st, a);
 }
 
 // slots [0, nslots): one launch; rows of different widths (routed [0, ntk), shared [ntk, nslots)):
 // one launch with each shared row split over a workgroup's 4 waves when a quarter of the shared row
 // fits the routed rows' register width, else two launches, each with the register row of its width
 template <int MODE>
-static void launch_act_m(const ActArgs& a, int maxw, hipStream_t st) {
-  launch_act_w<MODE>(a, maxw, st);
+static void launch_act_m(const ActArgs& a, int maxw, bool mx, hipStream_t st) {
+  if (mx) launch_act_w<MODE, true>(a, maxw, st);
+  else launch_act_w<MODE, false>(a, maxw, st);
 }
-static void launch_act_any(int mode, const ActArgs& a, int maxw, hipStream_t st) {
-  if (mode == 1) launch_act_m<1>(a, maxw, st);
-  else if (mode == 2) launch_act_m<2>(a, maxw, st);
-  else if (mode == 3) launch_act_m<3>(a, maxw, st);
-  else launch_act_m<0>(a, maxw, st);
+static void launch_act_any(int mode, const ActArgs& a, int maxw, bool mx, hipStream_t st) {
+  if (mode == 1) launch_act_m<1>(a, maxw, mx, st);
+  else if (mode == 2) launch_act_m<2>(a, maxw, mx, st);
+  else if (mode == 3) launch_act_m<3>(a, maxw, mx, st);
+  else launch_act_m<0>(a, maxw, mx, st);
 }
-static int launch_act(int mode, ActArgs a, int64_t nslots, int w_routed, int w_shared, void* stream) {
+// mx: a segment of the call carries MXMOE_ACT_MXFP4 (the MX builds of the kernel)
+static int launch_act(int mode, ActArgs a, int64_t nslots, int w_routed, int w_shared, void* stream, bool mx = false) {
   if (nslots == 0) return MXMOE_GG_OK;
   a.parts = 1;
   a.blk_shared = 0;
@@ -425,7 +476,7 @@ static int launch_act(int mode, ActArgs a, int64_t nslots, int w_routed, int w_s
     a.blk_shared = (a.ntk + kThreads / 64 - 1) / (kThreads / 64);
     a.s0 = 0;
     a.nslots = nslots;
-    launch_act_any(mode, a, w_routed, (hipStream_t)stream);
+    launch_act_any(mode, a, w_routed, mx, (hipStream_t)stream);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(MXMOE_GG_ERR_HIP, "act_quant_kernel launch failed: %s", hipGetErrorString(e));
     return MXMOE_GG_OK;
@@ -434,15 +485,43 @@ static int launch_act(int mode, ActArgs a, int64_t nslots, int w_routed, int w_s
   a.s0 = 0;
   a.nslots = split ? a.ntk : nslots;
   const int w0 = split ? w_routed : (nslots > a.ntk ? (w_routed > w_shared ? w_routed : w_shared) : w_routed);
-  launch_act_any(mode, a, w0, (hipStream_t)stream);
+  launch_act_any(mode, a, w0, mx, (hipStream_t)stream);
   if (split) {
     a.s0 = a.ntk;
     a.nslots = nslots;
-    launch_act_any(mode, a, w_shared, (hipStream_t)stream);
+    launch_act_any(mode, a, w_shared, mx, (hipStream_t)stream);
   }
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail(MXMOE_GG_ERR_HIP, "act_quant_kernel launch failed: %s", hipGetErrorString(e));
   return MXMOE_GG_OK;
+}
+
+// the activation entry points' bodies; mx: the call's segments may carry MXMOE_ACT_MXFP4
+static int quant_act_impl(const char* fn, const void* hidden, int64_t T, int K, int topk, int with_shared,
+                          const int32_t* sorted_expert, const int32_t* perm_token, const mxmoe_moe_seg* segs, int nseg,
+                          void* out, void* scales, void* stream, bool mx) {
+  if (T < 0 || topk <= 0 || nseg <= 0 || K <= 0 || K % 128 || K > kMaxWidth)
+    return fail(MXMOE_GG_ERR_INVALID, "%s: need K %% 128 == 0, K <= %d, topk > 0, nseg > 0 (K=%d)", fn, kMaxWidth, K);
+  if (T > 0 && (!hidden || !sorted_expert || !perm_token || !segs || !out || !aligned16(hidden) || !aligned16(out)))
+    return fail(MXMOE_GG_ERR_INVALID, "%s: NULL or misaligned pointer (hidden / out need 16 B)", fn);
+  const ActArgs a{static_cast<const _Float16*>(hidden), static_cast<const _Float16*>(hidden), T * topk, 0, 0, K, 0, 0,
+                  sorted_expert, perm_token, segs, nseg, static_cast<uint8_t*>(out), static_cast<_Float16*>(scales)};
+  return launch_act(0, a, T * topk + (with_shared ? T : 0), K, K, stream, mx);
+}
+static int slots_impl(const char* fn, int mode, const void* routed_in, const void* shared_in, int64_t T, int topk, int N,
+                      int N_shared, const int32_t* sorted_expert, const mxmoe_moe_seg* segs, int nseg, void* out,
+                      void* scales, void* stream, bool mx) {
+  if (T < 0 || topk <= 0 || nseg <= 0 || N <= 0 || N % 128 || N > kMaxWidth ||
+      (shared_in && (N_shared <= 0 || N_shared % 128 || N_shared > kMaxWidth)))
+    return fail(MXMOE_GG_ERR_INVALID, "%s: widths must be multiples of 128 and <= %d (N=%d, N_shared=%d)", fn, kMaxWidth,
+                N, N_shared);
+  if (T > 0 && (!routed_in || !sorted_expert || !segs || !out || !aligned16(routed_in) || !aligned16(out) ||
+                (shared_in && !aligned16(shared_in))))
+    return fail(MXMOE_GG_ERR_INVALID, "%s: NULL or misaligned pointer (16 B)", fn);
+  const ActArgs a{static_cast<const _Float16*>(routed_in), static_cast<const _Float16*>(shared_in), T * topk, 0, 0, 0,
+                  N, N_shared, sorted_expert, nullptr, segs, nseg, static_cast<uint8_t*>(out),
+                  static_cast<_Float16*>(scales)};
+  return launch_act(mode, a, T * topk + (shared_in ? T : 0), N, shared_in ? N_shared : N, stream, mx);
 }
 
 extern "C" {
@@ -486,62 +565,43 @@ int mxmoe_moe_route(const int32_t* topk_ids, int64_t T, int topk, int E, int32_t
 int mxmoe_moe_quant_act(const void* hidden, int64_t T, int K, int topk, int with_shared,
                         const int32_t* sorted_expert, const int32_t* perm_token, const mxmoe_moe_seg* segs, int nseg,
                         void* out, void* scales, void* stream) {
-  if (T < 0 || topk <= 0 || nseg <= 0 || K <= 0 || K % 128 || K > kMaxWidth)
-    return fail(MXMOE_GG_ERR_INVALID, "mxmoe_moe_quant_act: need K %% 128 == 0, K <= %d, topk > 0, nseg > 0 (K=%d)",
-                kMaxWidth, K);
-  if (T > 0 && (!hidden || !sorted_expert || !perm_token || !segs || !out || !aligned16(hidden) || !aligned16(out)))
-    return fail(MXMOE_GG_ERR_INVALID, "mxmoe_moe_quant_act: NULL or misaligned pointer (hidden / out need 16 B)");
-  const ActArgs a{static_cast<const _Float16*>(hidden), static_cast<const _Float16*>(hidden), T * topk, 0, 0, K, 0, 0,
-                  sorted_expert, perm_token, segs, nseg, static_cast<uint8_t*>(out), static_cast<_Float16*>(scales)};
-  return launch_act(0, a, T * topk + (with_shared ? T : 0), K, K, stream);
+  return quant_act_impl("mxmoe_moe_quant_act", hidden, T, K, topk, with_shared, sorted_expert, perm_token, segs, nseg, out,
+                        scales, stream, false);
 }
 
 int mxmoe_moe_silu_mul_quant(const void* routed_in, const void* shared_in, int64_t T, int topk, int N, int N_shared,
                              const int32_t* sorted_expert, const mxmoe_moe_seg* segs, int nseg, void* out,
                              void* scales, void* stream) {
-  if (T < 0 || topk <= 0 || nseg <= 0 || N <= 0 || N % 128 || N > kMaxWidth ||
-      (shared_in && (N_shared <= 0 || N_shared % 128 || N_shared > kMaxWidth)))
-    return fail(MXMOE_GG_ERR_INVALID, "mxmoe_moe_silu_mul_quant: widths must be multiples of 128 and <= %d (N=%d, "
-                "N_shared=%d)", kMaxWidth, N, N_shared);
-  if (T > 0 && (!routed_in || !sorted_expert || !segs || !out || !aligned16(routed_in) || !aligned16(out) ||
-                (shared_in && !aligned16(shared_in))))
-    return fail(MXMOE_GG_ERR_INVALID, "mxmoe_moe_silu_mul_quant: NULL or misaligned pointer (16 B)");
-  const ActArgs a{static_cast<const _Float16*>(routed_in), static_cast<const _Float16*>(shared_in), T * topk, 0, 0, 0,
-                  N, N_shared, sorted_expert, nullptr, segs, nseg, static_cast<uint8_t*>(out),
-                  static_cast<_Float16*>(scales)};
-  return launch_act(1, a, T * topk + (shared_in ? T : 0), N, shared_in ? N_shared : N, stream);
+  return slots_impl("mxmoe_moe_silu_mul_quant", 1, routed_in, shared_in, T, topk, N, N_shared, sorted_expert, segs, nseg,
+                    out, scales, stream, false);
 }
 
 int mxmoe_moe_silu_mul_quant_il(const void* routed_in, const void* shared_in, int64_t T, int topk, int N,
                                 int N_shared, const int32_t* sorted_expert, const mxmoe_moe_seg* segs, int nseg,
                                 void* out, void* scales, void* stream) {
-  if (T < 0 || topk <= 0 || nseg <= 0 || N <= 0 || N % 128 || N > kMaxWidth ||
-      (shared_in && (N_shared <= 0 || N_shared % 128 || N_shared > kMaxWidth)))
-    return fail(MXMOE_GG_ERR_INVALID, "mxmoe_moe_silu_mul_quant_il: widths must be multiples of 128 and <= %d (N=%d, "
-                "N_shared=%d)", kMaxWidth, N, N_shared);
-  if (T > 0 && (!routed_in || !sorted_expert || !segs || !out || !aligned16(routed_in) || !aligned16(out) ||
-                (shared_in && !aligned16(shared_in))))
-    return fail(MXMOE_GG_ERR_INVALID, "mxmoe_moe_silu_mul_quant_il: NULL or misaligned pointer (16 B)");
-  const ActArgs a{static_cast<const _Float16*>(routed_in), static_cast<const _Float16*>(shared_in), T * topk, 0, 0, 0,
-                  N, N_shared, sorted_expert, nullptr, segs, nseg, static_cast<uint8_t*>(out),
-                  static_cast<_Float16*>(scales)};
-  return launch_act(3, a, T * topk + (shared_in ? T : 0), N, shared_in ? N_shared : N, stream);
+  return slots_impl("mxmoe_moe_silu_mul_quant_il", 3, routed_in, shared_in, T, topk, N, N_shared, sorted_expert, segs,
+                    nseg, out, scales, stream, false);
 }
 
 int mxmoe_moe_quant_slots(const void* routed_in, const void* shared_in, int64_t T, int topk, int N, int N_shared,
                           const int32_t* sorted_expert, const mxmoe_moe_seg* segs, int nseg, void* out, void* scales,
                           void* stream) {
-  if (T < 0 || topk <= 0 || nseg <= 0 || N <= 0 || N % 128 || N > kMaxWidth ||
-      (shared_in && (N_shared <= 0 || N_shared % 128 || N_shared > kMaxWidth)))
-    return fail(MXMOE_GG_ERR_INVALID, "mxmoe_moe_quant_slots: widths must be multiples of 128 and <= %d (N=%d, "
-                "N_shared=%d)", kMaxWidth, N, N_shared);
-  if (T > 0 && (!routed_in || !sorted_expert || !segs || !out || !aligned16(routed_in) || !aligned16(out) ||
-                (shared_in && !aligned16(shared_in))))
-    return fail(MXMOE_GG_ERR_INVALID, "mxmoe_moe_quant_slots: NULL or misaligned pointer (16 B)");
-  const ActArgs a{static_cast<const _Float16*>(routed_in), static_cast<const _Float16*>(shared_in), T * topk, 0, 0, 0,
-                  N, N_shared, sorted_expert, nullptr, segs, nseg, static_cast<uint8_t*>(out),
-                  static_cast<_Float16*>(scales)};
-  return launch_act(2, a, T * topk + (shared_in ? T : 0), N, shared_in ? N_shared : N, stream);
+  return slots_impl("mxmoe_moe_quant_slots", 2, routed_in, shared_in, T, topk, N, N_shared, sorted_expert, segs, nseg, out,
+                    scales, stream, false);
+}
+
+int mxmoe_moe_act_quant(int mode, const void* routed_in, const void* shared_in, int64_t T, int topk, int N, int N_shared,
+                        const int32_t* sorted_expert, const int32_t* perm_token, const mxmoe_moe_seg* segs, int nseg,
+                        uint32_t tag_mask, void* out, void* scales, void* stream) {
+  if (mode < 0 || mode > 3) return fail(MXMOE_GG_ERR_INVALID, "mxmoe_moe_act_quant: mode must be 0..3 (mode=%d)", mode);
+  if (tag_mask >> (MXMOE_ACT_MXFP4 + 1))
+    return fail(MXMOE_GG_ERR_UNSUPPORTED, "mxmoe_moe_act_quant: unknown activation tag in mask %#x", tag_mask);
+  const bool mx = (tag_mask >> MXMOE_ACT_MXFP4) & 1;
+  if (mode == 0)
+    return quant_act_impl("mxmoe_moe_act_quant", routed_in, T, N, topk, shared_in != nullptr, sorted_expert, perm_token,
+                          segs, nseg, out, scales, stream, mx);
+  return slots_impl("mxmoe_moe_act_quant", mode, routed_in, shared_in, T, topk, N, N_shared, sorted_expert, segs, nseg, out,
+                    scales, stream, mx);
 }
 
 int mxmoe_moe_combine(const void* y, const int32_t* inv_slot, const float* weights, const void* shared,

@@ -24,7 +24,8 @@ import torch
 from . import _native as nat
 
 
-FMT_CODES = {"": nat.FMT_DEFAULT, "E4M3": nat.FMT_E4M3, "bf16": nat.FMT_BF16, "F6": nat.FMT_F6}
+FMT_CODES = {"": nat.FMT_DEFAULT, "E4M3": nat.FMT_E4M3, "bf16": nat.FMT_BF16, "F6": nat.FMT_F6,
+             "MXFP4": nat.FMT_MXFP4}
 
 
 @dataclasses.dataclass(frozen=True)
@@ -34,7 +35,8 @@ class QParams:
     ``fmt``: "" (fp16 / two's-complement integers), "E4M3" (w8a8_g-1_sym_E4M3: OCP fp8 codes),
     "bf16" (16-bit bfloat16 operands) or "F6" (w4a4_g-1_sym with A and B as fp6 images of the int4
     codes, ``_native.pack_f6``: same results on the fp6 MFMA — lab library only, measured slower
-    than the int4 path). The reference's ``_accfp16`` strategies (fp16 MMA with an fp16
+    than the int4 path) or "MXFP4" (w4a4_g32_sym_MXFP4: OCP e2m1 codes with one e8m0
+    scale per 32-K block, ``quantize.quant_mxfp4`` / ``pack_mxfp4_scales``). The reference's ``_accfp16`` strategies (fp16 MMA with an fp16
     accumulator, tile_config.py:94-97) run as their f32-accumulating base type: MFMA has no fp16
     accumulator, and the f32 sum is the more accurate result of the same products."""
 
@@ -70,7 +72,7 @@ class QParams:
         if not self.is_quant:
             return "bf16" if self.fmt == "bf16" else "fp16"
         return f"w{self.w_bits}a{self.a_bits}_g{self.gsize}_{'sym' if self.sym else 'asym'}" + \
-            ("_E4M3" if self.is_fp8 else "_F6" if self.fmt == "F6" else "")
+            ("_E4M3" if self.is_fp8 else "_F6" if self.fmt == "F6" else "_MXFP4" if self.fmt == "MXFP4" else "")
 
     @staticmethod
     def from_qcfg(qcfg: str) -> "QParams":
@@ -84,7 +86,8 @@ class QParams:
         g = int(qcfg.split("_g")[1].split("_")[0])
         if qcfg.endswith("_bf16"):
             raise ValueError(f"{qcfg}: weight-only with bf16 activations is not built on MI355X")
-        fmt = "E4M3" if qcfg.endswith("_E4M3") else "F6" if qcfg.endswith("_F6") else ""
+        fmt = "E4M3" if qcfg.endswith("_E4M3") else "F6" if qcfg.endswith("_F6") else \
+            "MXFP4" if qcfg.endswith("_MXFP4") else ""
         return QParams(a_bits=a, w_bits=w, gsize=g, sym="asym" not in qcfg, fmt=fmt)
 
 
@@ -94,6 +97,7 @@ W8A8 = QParams(8, 8, -1, True)
 W8A8_E4M3 = QParams(8, 8, -1, True, "E4M3")  # w8a8_g-1_sym_E4M3: OCP fp8 operands, f32 accumulate
 W4A4 = QParams(4, 4, -1, True)
 W4A4_F6 = QParams(4, 4, -1, True, "F6")  # w4a4_g-1_sym on fp6 images (lab library: nat.pack_f6 of A and B)
+W4A4_MXFP4 = QParams(4, 4, 32, True, "MXFP4")  # w4a4_g32_sym_MXFP4: e2m1 codes, e8m0 block scales (include/mxmoe_gg.h)
 W4A4_G128 = QParams(4, 4, 128, True)  # w4a4_g128_sym: one scale per 128-K group (cta_gemm.cuh:610-772)
 # weight-only (any group size that is -1 or a multiple of 64 dividing K, sym or asym, 2 / 4 / 8 bits)
 W4A16_G128_ASYM = QParams(16, 4, 128, False)
@@ -102,7 +106,7 @@ W4A16_G128_SYM = QParams(16, 4, 128, True)
 W8A16_ASYM = QParams(16, 8, -1, False)
 W2A16_G128_ASYM = QParams(16, 2, 128, False)
 
-SUPPORTED = {q.qcfg: q for q in (FP16, BF16, W8A8, W8A8_E4M3, W4A4, W4A4_G128, W4A16_G128_ASYM, W4A16_ASYM, W4A16_G128_SYM, W8A16_ASYM,
+SUPPORTED = {q.qcfg: q for q in (FP16, BF16, W8A8, W8A8_E4M3, W4A4, W4A4_MXFP4, W4A4_G128, W4A16_G128_ASYM, W4A16_ASYM, W4A16_G128_SYM, W8A16_ASYM,
                                   QParams(16, 4, -1, True), QParams(16, 8, -1, True), QParams(16, 8, 128, True),
                                   QParams(16, 8, 128, False), W2A16_G128_ASYM, QParams(16, 2, -1, False),
                                   QParams(16, 2, -1, True), QParams(16, 2, 128, True))}
@@ -114,7 +118,8 @@ class Problem:
 
     fp16 / bf16: A [M,K], B [N,K] 16-bit.  quant (incl. E4M3 codes): A uint8 [M, K*a_bits/8] / B uint8 [N, K*w_bits/8]
     in pack_wxax layout, scale_a fp16 [M], scale_b fp16 [N] (w4a4_g128: [K/128][M] and [K/128][N],
-    the permute_scale layout).  C fp16 [M, ldc] (ldc >= N).
+    the permute_scale layout; MXFP4: codes uint8 [rows, K/2] as quant_mxfp4 returns them, scales uint8
+    [rows, 16 * ceil(K/32 / 16)] in the device layout of pack_mxfp4_scales).  C fp16 [M, ldc] (ldc >= N).
     """
 
     A: torch.Tensor
@@ -151,6 +156,13 @@ class Problem:
             need(self.A, (torch.float16,) if self.q.is_weight_only else codes, "A")
             need(self.B, codes, "B (packed codes)")
         need(self.C, (torch.float16,), "C")
+        if self.q.fmt == "MXFP4":
+            if self.K % 32:
+                raise ValueError(f"{self.q.qcfg}: K={self.K} must be a multiple of the 32-element MX block")
+            need(self.A, (torch.uint8,), "A (e2m1 codes)")
+            need(self.B, (torch.uint8,), "B (e2m1 codes)")
+            need(self.scale_a, (torch.uint8,), "scale_a (e8m0, pack_mxfp4_scales)")
+            need(self.scale_b, (torch.uint8,), "scale_b (e8m0, pack_mxfp4_scales)")
 
     def to_c(self) -> nat.GGProblemC:
         def ptr(t):

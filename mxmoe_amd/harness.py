@@ -21,7 +21,8 @@ from typing import Optional, Sequence
 import torch
 
 from .groupgemm import GroupGemm, Problem, QParams
-from .quantize import pack_e4m3, pack_weightonly_mi355x, pack_wxax, quant_e4m3, quant_rtn_sym, quant_weightonly
+from .quantize import (pack_e4m3, pack_mxfp4_scales, pack_weightonly_mi355x, pack_wxax, quant_e4m3, quant_mxfp4,
+                       quant_rtn_sym, quant_weightonly)
 from .workload import QShape
 
 
@@ -44,6 +45,8 @@ class LayerInputs:
             tot += (s.M * s.K * ab + s.N * s.K * wb) // 8 + 2 * s.M * s.N
             if not plain and ab == 16:  # weight-only: scale (+ zp) per column and group
                 tot += 2 * s.N * (1 if s.gsize == -1 else s.K // s.gsize) * (1 if s.sym else 2)
+            elif s.fmt == "MXFP4":  # one e8m0 byte per 32-K block
+                tot += (s.M + s.N) * (s.K // 32)
             elif not plain:
                 tot += 2 * (s.M + s.N) * (1 if s.gsize == -1 else s.K // s.gsize)
         return tot
@@ -66,6 +69,10 @@ def build_layer_inputs(shapes: Sequence[QShape], device="cuda", seed: int = 42,
             qb, sb = quant_e4m3(b)
             probs.append(Problem(A=pack_e4m3(qa), B=pack_e4m3(qb), C=C, M=M, N=N, K=K, q=q, scale_a=sa, scale_b=sb))
             del qa, qb
+        elif q.fmt == "MXFP4":
+            (qa, sa), (qb, sb) = quant_mxfp4(a), quant_mxfp4(b)
+            probs.append(Problem(A=qa, B=qb, C=C, M=M, N=N, K=K, q=q, scale_a=pack_mxfp4_scales(sa),
+                                 scale_b=pack_mxfp4_scales(sb)))
         elif q.fmt == "bf16":
             probs.append(Problem(A=a.to(torch.bfloat16), B=b.to(torch.bfloat16), C=C, M=M, N=N, K=K, q=q))
         elif q.is_weight_only:

@@ -31,8 +31,13 @@ import torch
 from . import _native as nat
 from .groupgemm import GroupGemm, Problem, QParams
 
-ACT_FP16, ACT_INT8, ACT_INT4, ACT_INT4_G128 = 0, 1, 2, 3
-_BITS = {ACT_FP16: 16, ACT_INT8: 8, ACT_INT4: 4, ACT_INT4_G128: 4}
+ACT_FP16, ACT_INT8, ACT_INT4, ACT_INT4_G128, ACT_MXFP4 = 0, 1, 2, 3, 4
+_BITS = {ACT_FP16: 16, ACT_INT8: 8, ACT_INT4: 4, ACT_INT4_G128: 4, ACT_MXFP4: 4}
+
+
+def _mx_scale_row(width: int) -> int:
+    """e8m0 scale bytes per row of an MXFP4 segment (the GroupGEMM's device layout, include/mxmoe_gg.h)."""
+    return 16 * ((width // 32 + 15) // 16)
 
 
 def qtag_of(a_bits: int, gsize: int) -> int:
@@ -45,7 +50,17 @@ def qtag_of(a_bits: int, gsize: int) -> int:
         return ACT_INT4
     if a_bits == 4 and gsize == 128:
         return ACT_INT4_G128
+    if a_bits == 4 and gsize == 32:  # w4a4_g32_sym_MXFP4 (no integer g32 type exists)
+        return ACT_MXFP4
     raise ValueError(f"activation quantisation a{a_bits} g{gsize} not supported")
+
+
+def _tag_mask(qtags: Sequence[int]) -> int:
+    """mxmoe_moe_act_quant's tag_mask: bit t set when a segment carries tag t."""
+    m = 0
+    for t in qtags:
+        m |= 1 << t
+    return m
 
 
 def _stream(stream: Optional[torch.cuda.Stream]) -> ctypes.c_void_p:
@@ -172,6 +187,9 @@ class ActBatch:
         tag = self.qtags[e]
         if tag == ACT_FP16:
             return None
+        if tag == ACT_MXFP4:  # e8m0 bytes [rows, 16 G] inside the fp16 store
+            n = s.rows * _mx_scale_row(s.width) // 2
+            return self.scales[s.scale_off:s.scale_off + n].view(torch.uint8).view(s.rows, _mx_scale_row(s.width))
         n = s.rows * (s.width // 128 if tag == ACT_INT4_G128 else 1)
         return self.scales[s.scale_off:s.scale_off + n]
 
@@ -182,9 +200,14 @@ def _make_segments(rows: Sequence[int], first: Sequence[int], widths: Sequence[i
     for r, f, w, tag in zip(rows, first, widths, qtags):
         if w % 128:
             raise ValueError(f"segment width {w} must be a multiple of 128")
+        if tag == ACT_MXFP4:
+            soff += soff % 2  # its scale bytes are read as dwords: a 4-byte aligned block
         segs.append(nat.MoeSegC(tag, f, r, w, off, soff))
         off += (r * w * _BITS[tag] // 8 + 15) // 16 * 16  # 16-B aligned A operands
-        soff += 0 if tag == ACT_FP16 else r * (w // 128 if tag == ACT_INT4_G128 else 1)
+        if tag == ACT_MXFP4:
+            soff += r * _mx_scale_row(w) // 2  # (fp16 elements: two e8m0 bytes each)
+        else:
+            soff += 0 if tag == ACT_FP16 else r * (w // 128 if tag == ACT_INT4_G128 else 1)
     arr = (nat.MoeSegC * len(segs))(*segs)
     dev_segs = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(device)
     out = torch.empty(max(off, 16), dtype=torch.uint8, device=device)
@@ -206,6 +229,11 @@ def quant_act(hidden: torch.Tensor, r: Routing, qtags: Sequence[int], with_share
     h = hidden.contiguous()
 
     def launch(st=stream):
+        if ACT_MXFP4 in qtags:  # the builds that carry the MXFP4 tag (mxmoe_moe_act_quant, mode 0)
+            nat.check(nat.lib().mxmoe_moe_act_quant(0, _ptr(h), _ptr(h) if with_shared else None, T, r.topk, K, K,
+                                                    _ptr(r.sorted_expert), _ptr(r.perm_token), _ptr(dsegs), nseg,
+                                                    _tag_mask(qtags), _ptr(out), _ptr(scales), _stream(st)))
+            return
         nat.check(nat.lib().mxmoe_moe_quant_act(_ptr(h), T, K, r.topk, int(with_shared), _ptr(r.sorted_expert),
                                                 _ptr(r.perm_token), _ptr(dsegs), nseg, _ptr(out), _ptr(scales),
                                                 _stream(st)))
@@ -238,7 +266,14 @@ def silu_mul_quant(routed: torch.Tensor, shared: Optional[torch.Tensor], r: Rout
     fn = (nat.lib().mxmoe_moe_quant_slots if activated else
           nat.lib().mxmoe_moe_silu_mul_quant_il if interleaved else nat.lib().mxmoe_moe_silu_mul_quant)
 
+    mode = 2 if activated else 3 if interleaved else 1
+
     def launch(st=stream):
+        if ACT_MXFP4 in qtags:  # the builds that carry the MXFP4 tag
+            nat.check(nat.lib().mxmoe_moe_act_quant(mode, _ptr(routed), _ptr(shared), r.T, r.topk, N, Ns,
+                                                    _ptr(r.sorted_expert), None, _ptr(dsegs), nseg, _tag_mask(qtags),
+                                                    _ptr(out), _ptr(scales), _stream(st)))
+            return
         nat.check(fn(_ptr(routed), _ptr(shared), r.T, r.topk, N, Ns, _ptr(r.sorted_expert), _ptr(dsegs), nseg,
                      _ptr(out), _ptr(scales), _stream(st)))
 
@@ -382,7 +417,8 @@ def gg_mxmoe_share_fused(inp: Sequence[torch.Tensor], experts: Sequence[torch.Te
         if pi >= len(inp):
             raise ValueError(f"gg_mxmoe_share_fused: {len(inp)} inputs for more non-empty experts")
         a_bits, w_bits, gsize, sym = (int(x) for x in qparams_per_exp[e])
-        q = QParams(a_bits, w_bits, gsize, bool(sym))
+        # (4, 4, 32, 1) is w4a4_g32_sym_MXFP4: the only g32 type, so the tuple needs no format field
+        q = QParams(a_bits, w_bits, gsize, bool(sym), "MXFP4" if (a_bits, w_bits, gsize) == (4, 4, 32) else "")
         n, k = (shared_N, shared_K) if e == E else (N, K)
 
         def opt(t):
@@ -448,7 +484,8 @@ def prepare_weight(w: torch.Tensor, q: QParams, interleave: bool = False) -> Exp
     gate_up weight ([gate; up] rows) reordered for the fused SiLU epilogue (interleave_gate_up; the
     per-row scales follow their rows)."""
     from .groupgemm import interleave_gate_up
-    from .quantize import pack_weightonly_mi355x, pack_wxax, quant_rtn_sym, quant_weightonly
+    from .quantize import (pack_mxfp4_scales, pack_weightonly_mi355x, pack_wxax, quant_mxfp4, quant_rtn_sym,
+                           quant_weightonly)
 
     N, K = w.shape
     if interleave:
@@ -458,6 +495,9 @@ def prepare_weight(w: torch.Tensor, q: QParams, interleave: bool = False) -> Exp
     if q.is_weight_only:
         codes, sz = quant_weightonly(w, q.w_bits, q.gsize, q.sym)
         return ExpertWeights(pack_weightonly_mi355x(codes, q.w_bits), sz, q, N, K)
+    if q.fmt == "MXFP4":
+        codes, sc = quant_mxfp4(w)
+        return ExpertWeights(codes, pack_mxfp4_scales(sc), q, N, K)
     qw, sw = quant_rtn_sym(w, q.w_bits, q.gsize)
     return ExpertWeights(pack_wxax(qw, q.w_bits), sw, q, N, K)
 

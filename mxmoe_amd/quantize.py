@@ -208,3 +208,79 @@ def dequant_weightonly(codes: torch.Tensor, sz: torch.Tensor, bits: int, gsize: 
     off = (1 << (bits - 1)) - 1 if sym else 0
     u = codes.to(torch.float64).reshape(N, G, g) - off
     return (u * s[..., None] + z[..., None]).reshape(N, K).half()  # exact in f64, then one rounding
+
+
+# ---- OCP MXFP4 (w4a4_g32_sym_MXFP4): e2m1 codes, one e8m0 scale per 32-element block ------------------
+MXFP4_BLOCK = 32
+# magnitude of code bits 2..0; bit 3 of a code is the sign
+E2M1_VALUES = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)
+
+
+def e8m0_decode(codes: torch.Tensor) -> torch.Tensor:
+    """uint8 e8m0 codes -> float64 2^(code - 127), code 255 -> NaN (torch.float8_e8m0fnu's decode)."""
+    v = torch.ldexp(torch.ones((), dtype=torch.float64, device=codes.device), codes.to(torch.int32) - 127)
+    return torch.where(codes == 255, torch.full_like(v, float("nan")), v)
+
+
+def quant_mxfp4(x: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
+    """fp16 [rows, K] (K % 32 == 0) -> (codes uint8 [rows, K/2], scales uint8 [rows, K/32]), the canonical
+    MXFP4 operand format of include/mxmoe_gg.h. RTN as OCP MX v1.0, per 32-element block:
+    e = floor(log2(amax)) - 2 clamped to [-127, 127] (an all-zero block: -127), scale code e + 127,
+    element code = f32(x) / 2^e (exact) saturated to +-6 and rounded to the e2m1 grid with ties to the
+    even code; the sign of -0 and of values that round to 0 is kept. A block holding a NaN or an Inf
+    gets scale code 255 (NaN) and all-zero codes."""
+    if x.dtype != torch.float16:
+        raise TypeError("quant_mxfp4 expects fp16 input")
+    rows, K = x.shape
+    if K % MXFP4_BLOCK:
+        raise ValueError(f"K={K} must be a multiple of the MX block size {MXFP4_BLOCK}")
+    xf = x.float().reshape(rows, K // MXFP4_BLOCK, MXFP4_BLOCK)
+    bad = ~torch.isfinite(xf).all(dim=-1)
+    xf = torch.where(bad[..., None], torch.zeros_like(xf), xf)
+    amax = xf.abs().amax(dim=-1)
+    # frexp: amax = m * 2^ex with m in [0.5, 1), so floor(log2(amax)) = ex - 1 (exact, subnormals included)
+    ex = torch.frexp(amax).exponent.to(torch.int32)
+    e = torch.where(amax == 0, torch.full_like(ex, -127), (ex - 3).clamp(-127, 127))
+    # x / 2^e in two exact steps (2^127 * 2^-e' style products never leave the f32 range: |x| < 2^16, e >= -127)
+    h = torch.div(e, 2, rounding_mode="floor")
+    one = torch.ones((), dtype=torch.float32, device=x.device)
+    y = xf * torch.ldexp(one, -h)[..., None] * torch.ldexp(one, -(e - h))[..., None]
+    a = y.abs().clamp(max=6.0)
+    # grid steps 0.5 below 2, 1 below 4, 2 up to 6; torch.round is half-to-even, and an even rounded
+    # multiple is an even code in every segment
+    idx = torch.where(a < 2, torch.round(a * 2), torch.where(a < 4, 2 + torch.round(a), 4 + torch.round(a / 2)))
+    nib = idx.to(torch.uint8) | (torch.signbit(y).to(torch.uint8) << 3)
+    nib = torch.where(bad[..., None], torch.zeros_like(nib), nib).reshape(rows, K // 2, 2)
+    codes = nib[..., 0] | (nib[..., 1] << 4)
+    scales = torch.where(bad, torch.full_like(e, 255), e + 127).to(torch.uint8)
+    return codes.contiguous(), scales.contiguous()
+
+
+def dequant_mxfp4(codes: torch.Tensor, scales: torch.Tensor) -> torch.Tensor:
+    """Canonical MXFP4 (codes uint8 [rows, K/2], scales uint8 [rows, K/32]) -> float64 [rows, K]
+    (exact; NaN where the block's scale code is 255)."""
+    rows, kb = codes.shape
+    nib = torch.stack([codes & 0xF, codes >> 4], dim=-1).reshape(rows, 2 * kb)
+    table = torch.tensor(E2M1_VALUES, dtype=torch.float64, device=codes.device)
+    v = table[(nib & 7).long()] * torch.where((nib & 8) != 0, -1.0, 1.0).to(torch.float64)
+    s = e8m0_decode(scales)
+    return (v.reshape(rows, -1, MXFP4_BLOCK) * s[..., None]).reshape(rows, 2 * kb)
+
+
+def pack_mxfp4_scales(scales: torch.Tensor) -> torch.Tensor:
+    """Canonical e8m0 scales uint8 [rows, K/32] -> the device layout the GroupGEMM reads
+    (include/mxmoe_gg.h): uint8 [rows, 16 G], G = ceil(K/32 / 16), every 16-byte group transposed 4 x 4
+    (dev[4 g + i] = canon[4 i + g]), bytes past K/32 = 127."""
+    rows, nb = scales.shape
+    G = (nb + 15) // 16
+    pad = torch.full((rows, 16 * G), 127, dtype=torch.uint8, device=scales.device)
+    pad[:, :nb] = scales
+    return pad.reshape(rows, G, 4, 4).transpose(2, 3).reshape(rows, 16 * G).contiguous()
+
+
+def unpack_mxfp4_scales(dev: torch.Tensor, K: int) -> torch.Tensor:
+    """Inverse of pack_mxfp4_scales: device layout uint8 [rows, 16 G] -> canonical uint8 [rows, K/32]."""
+    rows = dev.shape[0]
+    G = dev.shape[1] // 16
+    canon = dev.reshape(rows, G, 4, 4).transpose(2, 3).reshape(rows, 16 * G)
+    return canon[:, :K // MXFP4_BLOCK].contiguous()
