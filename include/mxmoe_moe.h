@@ -85,6 +85,43 @@ int mxmoe_moe_gate(const void* hidden, const void* w_gate, const void* w_shared_
                    int renormalize, int32_t* topk_ids, float* topk_weights, float* shared_w, float* logits,
                    void* stream);
 
+/* mxmoe_moe_gate with the routing rules of DeepSeek-V3 / R1 (sigmoid scores, e_score_correction_bias,
+ * group-limited top-k, routed_scaling_factor), DeepSeek-V2 (softmax, group_limited_greedy) and
+ * GLM-4.5-style layers (sigmoid + bias, one group): the same single launch and the same K loop.
+ * Replaces: nothing in the reference (no router kernel); the semantics are the models' public routing
+ * code, with the two deviations named below (tie rule, -inf fill).
+ *   hidden, w_gate, w_shared_gate, T, H, E, topk, renormalize, shared_w, logits: as mxmoe_moe_gate; the
+ *            logits x[e] and the shared gate column are computed exactly as there, under both scorings.
+ *   scoring  MXMOE_GATE_SOFTMAX: selection values v[e] = x[e] (the selection stays on the logits).
+ *            e_bias and scores must be NULL and group_top 1.
+ *            MXMOE_GATE_SIGMOID: s[e] = rcp(1 + exp2(-x[e] * log2 e)) in f32 (the shared gate's
+ *            arithmetic), v[e] = s[e] + e_bias[e] (one f32 add; e_bias f32 [E] or NULL: v = s).
+ *   scores   NULL, or f32 [T][E] (sigmoid only): receives the very s[e] used.
+ *   groups   n_group == 1: no group stage. Otherwise group G holds experts [G gs, (G + 1) gs),
+ *            gs = E / n_group; its score is max v (group_top == 1) or the f32 sum (one add) of its two
+ *            largest v (group_top == 2: DeepSeek-V3). The topk_group groups with the largest score are
+ *            kept; among equal scores (-0 == +0) the lower group index wins. Experts of the other
+ *            groups are never selected: the -inf fill of serving stacks. (The HF DeepSeek-V3 code fills
+ *            dropped groups with 0.0 instead, which can select a masked expert when a kept v is
+ *            negative; that is not reproduced.)
+ *   selection: the topk largest v among the kept experts; topk_ids in descending order of v, ties
+ *            (-0 == +0) to the lower index. A row whose values hold NaN or +-Inf still gets topk
+ *            distinct ids in [0, E).
+ *   weights  SOFTMAX: mxmoe_moe_gate's weights (softmax over all E experts, or over the chosen ones with
+ *            renormalize), then one f32 multiply by routed_scale.
+ *            SIGMOID: s[id_k] (the unbiased score), or with renormalize s[id_k] / (sum_j s[id_j] + 1e-20),
+ *            then one f32 multiply by routed_scale.
+ *            routed_scale == 1.0 multiplies by one: the weights are unchanged bit for bit.
+ * Limits: mxmoe_moe_gate's, and 1 <= n_group <= 8, E % n_group == 0, gs % 4 == 0 (gs = 20 works),
+ * 1 <= topk_group <= n_group (so 1 when n_group is 1), topk <= topk_group * gs, group_top 1 or 2 and
+ * <= gs, routed_scale finite, e_bias and scores 4-byte aligned. Anything else: MXMOE_GG_ERR_INVALID
+ * (checked before any HIP call). E > 256 is out of scope. */
+enum { MXMOE_GATE_SOFTMAX = 0, MXMOE_GATE_SIGMOID = 1 };
+int mxmoe_moe_gate_ex(const void* hidden, const void* w_gate, const void* w_shared_gate, int64_t T, int H, int E, int topk,
+                      int renormalize, int scoring, const float* e_bias, int n_group, int topk_group, int group_top,
+                      float routed_scale, int32_t* topk_ids, float* topk_weights, float* shared_w, float* logits,
+                      float* scores, void* stream);
+
 /* Stable counting sort of the T*topk expert ids (int32, row-major [T][topk], values in [0, E)):
  *   sorted_expert[s] = expert of slot s (non-decreasing), perm_token[s] = source token of slot s,
  *   inv_slot[t*topk + k] = slot of (token t, choice k), counts[e] = tokens routed to expert e.

@@ -94,7 +94,7 @@ EXPORTED_SYMBOLS = (
     # include/mxmoe_moe.h (MoE-layer plumbing)
     "mxmoe_moe_route", "mxmoe_moe_quant_act", "mxmoe_moe_silu_mul_quant", "mxmoe_moe_silu_mul_quant_il", "mxmoe_moe_quant_slots", "mxmoe_moe_combine",
     "mxmoe_moe_act_quant",
-    "mxmoe_moe_gate",
+    "mxmoe_moe_gate", "mxmoe_moe_gate_ex",
 )
 
 
@@ -177,6 +177,10 @@ def _declare(lib: ctypes.CDLL) -> None:
     if hasattr(lib, "mxmoe_moe_gate"):  # (the router; builds before it lack the symbol: A/B tools)
         lib.mxmoe_moe_gate.restype = c.c_int
         lib.mxmoe_moe_gate.argtypes = [P, P, P, c.c_int64, c.c_int, c.c_int, c.c_int, c.c_int, P, P, P, P, P]
+    if hasattr(lib, "mxmoe_moe_gate_ex"):  # (sigmoid / bias / group-limited routing; builds before it: A/B tools)
+        lib.mxmoe_moe_gate_ex.restype = c.c_int
+        lib.mxmoe_moe_gate_ex.argtypes = [P, P, P, c.c_int64, c.c_int, c.c_int, c.c_int, c.c_int, c.c_int, P, c.c_int, c.c_int,
+                                          c.c_int, c.c_float, P, P, P, P, P, P]
     lib.mxmoe_moe_combine.restype = c.c_int
     lib.mxmoe_moe_combine.argtypes = [P, P, P, P, P, c.c_int64, c.c_int, c.c_int, P, P]
 

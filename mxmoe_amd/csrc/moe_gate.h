@@ -2,7 +2,9 @@
 // gate logits (fp16 x fp16 -> f32 on v_mfma_f32_16x16x32_f16), top-k selection on the logits,
 // softmax weights and the optional shared-expert gate. No reference counterpart: the reference has no
 // router kernel; the semantics are the models' own softmax -> topk code (qwen2_moe, DeepSeek-V2-Lite,
-// Mixtral) and qwen2_moe's sigmoid(shared_expert_gate(hidden)).
+// Mixtral) and qwen2_moe's sigmoid(shared_expert_gate(hidden)). mxmoe_moe_gate_ex (gate_modes_kernel)
+// adds, behind a compile-time mode of the same body, sigmoid scores with a selection bias,
+// group-limited top-k and a scaling factor (DeepSeek-V3 / R1, DeepSeek-V2, GLM-4.5-style).
 //
 // Form. A workgroup of NW = 8 waves (4 beyond 192 columns) owns 16 * MR token rows and every column
 // (E experts, + 1 for the shared gate, padded to NB blocks of 16). Both operands are K-contiguous,
@@ -58,227 +60,150 @@ __device__ __forceinline__ float key_value(uint32_t k) {
 }
 __device__ __forceinline__ float exp_rel(float x, float m) { return __builtin_amdgcn_exp2f((x - m) * kLog2e); }
 
-template <int NB, int MR, int NW, int U>
-__global__ __launch_bounds__(64 * NW) void gate_kernel(GateArgs a) {
-  constexpr int kSlots = NW == 8 ? 4 : 3;  // partial-sum tiles in LDS at a time, per (token block, column block)
-  static_assert(NW == 4 || NW == 8, "4 or 8 waves");
-  static_assert(MR >= 1 && MR <= 4 && MR * kSlots * NB * 1024 <= 64 * 1024, "partial sums must fit 64 KiB of LDS");
-  __shared__ gf4_t red[MR * kSlots * NB * 64];
-  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int c16 = lane & 15, g = lane >> 4;
-  const int64_t row0 = (int64_t)blockIdx.x * (16 * MR);
-  const int E = a.E;
+// mxmoe_moe_gate_ex's routing rules (include/mxmoe_moe.h) on top of GateArgs: sigmoid scores with a
+// selection bias, group-limited top-k and a scaling factor on the weights
+struct GateModeArgs {
+  GateArgs g;
+  const float* e_bias;  // [E] or NULL (sigmoid only)
+  float* scores;        // [T][E] or NULL (sigmoid only)
+  int n_group, topk_group, group_top;
+  float routed_scale;
+};
 
-  // fragment rows: tokens past T and columns past E (+ 1) read a clamped, existing row; what they
-  // produce is never used (masked by index below) and never stored
-  const _Float16* hp[MR];
-  const _Float16* wp[NB];
-#pragma unroll
-  for (int i = 0; i < MR; ++i) {
-    int64_t r = row0 + 16 * i + c16;
-    r = r < a.T ? r : a.T - 1;
-    hp[i] = a.hidden + r * a.H + 8 * g;
-  }
+// what a kernel is compiled for: mxmoe_moe_gate's rule (gate_kernel, which gets no GateModeArgs), or
+// mxmoe_moe_gate_ex's with softmax / sigmoid scoring (gate_modes_kernel)
+enum GateMode { kGatePlain = 0, kGateSoftmaxEx = 1, kGateSigmoidEx = 2 };
+
+// Row t of an f32 [T][E] output from the lane's registers (experts 16 j + 4 g + r): 16-B stores when
+// E % 4 == 0 and the buffer is 16-byte aligned
+template <int NB>
+__device__ __forceinline__ void gate_store_row(float* out, int64_t t, int E, int g, const gf4_t (&x)[NB]) {
+  float* row = out + t * E;
+  const bool vec = (E & 3) == 0 && ((uintptr_t)out & 15) == 0;
 #pragma unroll
   for (int j = 0; j < NB; ++j) {
-    const int c = 16 * j + c16;
-    const _Float16* p = c < E ? a.w_gate + (int64_t)c * a.H : (c == E && a.w_shared) ? a.w_shared : a.w_gate;
-    wp[j] = p + 8 * g;
-  }
-
-  gf4_t acc[MR][NB];
-#pragma unroll
-  for (int i = 0; i < MR; ++i)
-#pragma unroll
-    for (int j = 0; j < NB; ++j) acc[i][j] = gf4_t{0.0f, 0.0f, 0.0f, 0.0f};
-
-  const int nsteps = a.H >> 5;
-  // U consecutive K-32 steps s0 .. s0 + U - 1 of every fragment row (U * 64 contiguous bytes of each
-  // row). A step past H loads step 0 instead and is skipped by mma (wave-uniform): nothing here
-  // consumes a loaded register, so a prefetched group stays in flight across the previous one's MFMAs
-  auto load = [&](int s0, gh8_t(&h)[U][MR], gh8_t(&w)[U][NB]) {
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const int off = s0 + u < nsteps ? (s0 + u) * 32 : 0;
-#pragma unroll
-      for (int i = 0; i < MR; ++i) h[u][i] = *reinterpret_cast<const gh8_t*>(hp[i] + off);
-#pragma unroll
-      for (int j = 0; j < NB; ++j) w[u][j] = *reinterpret_cast<const gh8_t*>(wp[j] + off);
-    }
-  };
-  auto mma = [&](int s0, const gh8_t(&h)[U][MR], const gh8_t(&w)[U][NB]) {
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      if (s0 + u < nsteps) {
-#pragma unroll
-        for (int i = 0; i < MR; ++i)
-#pragma unroll
-          for (int j = 0; j < NB; ++j)
-            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(w[u][j], h[u][i], acc[i][j], 0, 0, 0);
-      }
-    }
-  };
-  {
-    // wave w: groups (q NW + w) U, q = 0, 1, ...; two register buffers, the next group's loads issued
-    // before the current group's MFMAs
-    constexpr int kStride = NW * U;
-    gh8_t hA[U][MR], wA[U][NB], hB[U][MR], wB[U][NB];
-    int s = wave * U;
-    if (s < nsteps) {
-      load(s, hA, wA);
-      for (;;) {
-        const bool more1 = s + kStride < nsteps;
-        if (more1) load(s + kStride, hB, wB);
-        mma(s, hA, wA);
-        if (!more1) break;
-        const bool more2 = s + 2 * kStride < nsteps;
-        if (more2) load(s + 2 * kStride, hA, wA);
-        mma(s + kStride, hB, wB);
-        if (!more2) break;
-        s += 2 * kStride;
-      }
-    }
-  }
-
-  // split-K reduction, in a fixed order. 8 waves: waves 4-7 first hand everything to waves 0-3
-  if constexpr (NW == 8) {
-    if (wave >= 4) {
-#pragma unroll
-      for (int i = 0; i < MR; ++i)
-#pragma unroll
-        for (int j = 0; j < NB; ++j) red[(((wave - 4) * MR + i) * NB + j) * 64 + lane] = acc[i][j];
-    }
-    __syncthreads();
-    if (wave < 4) {
-#pragma unroll
-      for (int i = 0; i < MR; ++i)
-#pragma unroll
-        for (int j = 0; j < NB; ++j) acc[i][j] += red[((wave * MR + i) * NB + j) * 64 + lane];
-    }
-    __syncthreads();
-  }
-  // then wave w < 4 hands its partial of token block i != w to wave i (slot (w - i - 1) & 3)
-#pragma unroll
-  for (int i = 0; i < MR; ++i) {
-    if (i != wave && wave < 4) {
-      const int slot = (wave - i - 1) & 3;
-#pragma unroll
-      for (int j = 0; j < NB; ++j) red[((i * 3 + slot) * NB + j) * 64 + lane] = acc[i][j];
-    }
-  }
-  __syncthreads();
-  if (wave >= MR || row0 + 16 * wave >= a.T) return;  // wave-uniform
-  gf4_t x[NB];
-#pragma unroll
-  for (int j = 0; j < NB; ++j) {
-    x[j] = acc[0][j];
-#pragma unroll
-    for (int i = 1; i < MR; ++i)
-      if (i == wave) x[j] = acc[i][j];
-#pragma unroll
-    for (int sl = 0; sl < 3; ++sl) x[j] += red[((wave * 3 + sl) * NB + j) * 64 + lane];
-  }
-
-  // this lane: token t, experts 16 j + 4 g + r
-  const int64_t t = row0 + 16 * wave + c16;
-  const bool live = t < a.T;
-
-  if (a.logits && live) {
-    float* lrow = a.logits + t * E;
-    const bool vec = (E & 3) == 0 && ((uintptr_t)a.logits & 15) == 0;
-#pragma unroll
-    for (int j = 0; j < NB; ++j) {
-      const int e0 = 16 * j + 4 * g;
-      if (vec) {
-        if (e0 < E) *reinterpret_cast<gf4_t*>(lrow + e0) = x[j];
-      } else {
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-          if (e0 + r < E) lrow[e0 + r] = x[j][r];
-      }
-    }
-  }
-
-  if (a.w_shared) {  // column E: one more output column, outside the softmax and the selection
-    float s = 0.0f;
-#pragma unroll
-    for (int j = 0; j < NB; ++j)
+    const int e0 = 16 * j + 4 * g;
+    if (vec) {
+      if (e0 < E) *reinterpret_cast<gf4_t*>(row + e0) = x[j];
+    } else {
 #pragma unroll
       for (int r = 0; r < 4; ++r)
-        if (16 * j + 4 * g + r == E) s = x[j][r];
-    if (live && g == ((E & 15) >> 2)) a.shared_w[t] = __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(s * -kLog2e));
+        if (e0 + r < E) row[e0 + r] = x[j][r];
+    }
   }
+}
 
-  uint32_t key[NB][4];
+// Sigmoid scoring: x becomes the scores s (the logits are stored by then), key = the keys of the
+// selection values v = s + bias
+template <int NB>
+__device__ __forceinline__ void gate_sigmoid_keys(const GateModeArgs& m, int64_t t, bool live, int g, gf4_t (&x)[NB],
+                                                  uint32_t (&key)[NB][4]) {
+  const int E = m.g.E;
 #pragma unroll
   for (int j = 0; j < NB; ++j)
 #pragma unroll
-    for (int r = 0; r < 4; ++r) key[j][r] = 16 * j + 4 * g + r < E ? order_key(x[j][r]) : 0u;
-
-  // top-k: k rounds of (largest key, lowest index) over the lane's registers and the token's 4 lane
-  // groups; choice kk is kept by lane group kk & 3 in slot kk >> 2
-  uint32_t sk[4] = {0, 0, 0, 0}, mkey = 0;
-  int se[4] = {0, 0, 0, 0};
-  for (int kk = 0; kk < a.topk; ++kk) {
-    uint32_t bk = 0;
-    int be = 0x7fffffff;
+    for (int r = 0; r < 4; ++r) x[j][r] = __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(x[j][r] * -kLog2e));
+  if (m.scores && live) gate_store_row<NB>(m.scores, t, E, g, x);
+  const bool vec = (E & 3) == 0 && ((uintptr_t)m.e_bias & 15) == 0;
 #pragma unroll
-    for (int j = 0; j < NB; ++j)
+  for (int j = 0; j < NB; ++j) {
+    const int e0 = 16 * j + 4 * g;
+    gf4_t b{0.0f, 0.0f, 0.0f, 0.0f};
+    if (m.e_bias) {
+      if (vec) {
+        if (e0 < E) b = *reinterpret_cast<const gf4_t*>(m.e_bias + e0);
+      } else {
 #pragma unroll
-      for (int r = 0; r < 4; ++r)
-        if (key[j][r] > bk) {
-          bk = key[j][r];
-          be = 16 * j + 4 * g + r;
-        }
-#pragma unroll
-    for (int d = 16; d <= 32; d <<= 1) {
-      const uint32_t ok = (uint32_t)__shfl_xor((int)bk, d, 64);
-      const int oe = __shfl_xor(be, d, 64);
-      if (ok > bk || (ok == bk && oe < be)) {
-        bk = ok;
-        be = oe;
+        for (int r = 0; r < 4; ++r)
+          if (e0 + r < E) b[r] = m.e_bias[e0 + r];
       }
     }
 #pragma unroll
-    for (int j = 0; j < NB; ++j)
-#pragma unroll
-      for (int r = 0; r < 4; ++r)
-        if (16 * j + 4 * g + r == be) key[j][r] = 0u;
-    if (kk == 0) mkey = bk;
-    if ((kk & 3) == g) {
-#pragma unroll
-      for (int q = 0; q < 4; ++q)
-        if (q == (kk >> 2)) {
-          sk[q] = bk;
-          se[q] = be;
-        }
-    }
+    for (int r = 0; r < 4; ++r) key[j][r] = e0 + r < E ? order_key(x[j][r] + b[r]) : 0u;
   }
+}
 
-  const float m = key_value(mkey);  // the first choice is the row's maximum
-  float p[4];
+// Group stage: the two largest keys of every group (in-lane, then over the token's 4 lane groups),
+// topk_group rounds of (largest group key, lowest group) over at most 8 groups, and the keys of the
+// other groups' experts zeroed, which is how a padded column is never chosen either. gs % 4 == 0: a
+// lane's 4 registers of a block share a group; a group of 20 straddles 16-column blocks, so the
+// group of block j is (16 j + 4 g) / gs and not a function of j alone
+template <int NB>
+__device__ __forceinline__ void gate_group_limit(const GateModeArgs& m, int g, uint32_t (&key)[NB][4]) {
+  const int gs = m.g.E / m.n_group;
+  uint32_t gkey[8];
 #pragma unroll
-  for (int q = 0; q < 4; ++q) p[q] = 4 * q + g < a.topk ? exp_rel(key_value(sk[q]), m) : 0.0f;
-  float sum = 0.0f;
-  if (a.renorm) {
-    sum = ((p[0] + p[1]) + p[2]) + p[3];
-  } else {
+  for (int G = 0; G < 8; ++G) {
+    gkey[G] = 0u;
+    if (G < m.n_group) {  // wave-uniform
+      const int lo = G * gs, hi = lo + gs;
+      uint32_t t1 = 0, t2 = 0;
 #pragma unroll
-    for (int j = 0; j < NB; ++j)
+      for (int j = 0; j < NB; ++j) {
+        const int e0 = 16 * j + 4 * g;
+        const bool in = e0 >= lo && e0 < hi;
 #pragma unroll
-      for (int r = 0; r < 4; ++r) sum += 16 * j + 4 * g + r < E ? exp_rel(x[j][r], m) : 0.0f;
-  }
-  sum += __shfl_xor(sum, 16, 64);
-  sum += __shfl_xor(sum, 32, 64);
-  if (!live) return;
+        for (int r = 0; r < 4; ++r) {
+          const uint32_t k = in ? key[j][r] : 0u;
+          t2 = max(t2, min(t1, k));
+          t1 = max(t1, k);
+        }
+      }
 #pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    const int kk = 4 * q + g;
-    if (kk < a.topk) {
-      a.ids[t * a.topk + kk] = se[q];
-      a.weights[t * a.topk + kk] = p[q] / sum;
+      for (int d = 16; d <= 32; d <<= 1) {
+        const uint32_t o1 = (uint32_t)__shfl_xor((int)t1, d, 64), o2 = (uint32_t)__shfl_xor((int)t2, d, 64);
+        t2 = max(min(t1, o1), max(t2, o2));
+        t1 = max(t1, o1);
+      }
+      gkey[G] = m.group_top == 2 ? order_key(key_value(t1) + key_value(t2)) : t1;
     }
   }
+  uint32_t keep = 0;
+  for (int q = 0; q < m.topk_group; ++q) {
+    uint32_t bk = 0;
+    int bg = 0;
+#pragma unroll
+    for (int G = 0; G < 8; ++G)
+      if (gkey[G] > bk) {
+        bk = gkey[G];
+        bg = G;
+      }
+#pragma unroll
+    for (int G = 0; G < 8; ++G)
+      if (G == bg) gkey[G] = 0u;
+    keep |= 1u << bg;
+  }
+#pragma unroll
+  for (int j = 0; j < NB; ++j) {
+    const int e0 = 16 * j + 4 * g;
+    int grp = 0;
+#pragma unroll
+    for (int G = 1; G < 8; ++G) grp += e0 >= G * gs;
+    if (!((keep >> grp) & 1u)) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) key[j][r] = 0u;
+    }
+  }
+}
+
+// Both kernels are the one body of moe_gate_body.inc (K loop, split-K reduction, logits, shared gate,
+// top-k rounds, weights), which reads `a`, `ex` and MODE; the mxmoe_moe_gate_ex stages in it are
+// `if constexpr (MODE ...)`. It is shared as text and not as a function on purpose: through a
+// __forceinline__ function taking the arguments by reference or by value the compiler allocated
+// 1-2 registers differently in most gate_kernel instantiations, and mxmoe_moe_gate's kernels are to
+// stay the ones measured in DESIGN.md §4 "Router", bit for bit.
+template <int NB, int MR, int NW, int U>
+__global__ __launch_bounds__(64 * NW) void gate_kernel(GateArgs a) {
+  constexpr int MODE = kGatePlain;
+  const GateModeArgs* const ex = nullptr;
+#include "moe_gate_body.inc"
+}
+template <int NB, int MR, int NW, int U, int MODE>
+__global__ __launch_bounds__(64 * NW) void gate_modes_kernel(GateModeArgs mm) {
+  static_assert(MODE == kGateSoftmaxEx || MODE == kGateSigmoidEx, "an mxmoe_moe_gate_ex mode");
+  const GateArgs& a = mm.g;
+  const GateModeArgs* const ex = &mm;
+#include "moe_gate_body.inc"
 }
 
 // A/B build knobs (-D; DESIGN.md §4 "Router", profiles/r07/gate/ab_builds.jsonl): waves per workgroup
@@ -343,6 +268,42 @@ inline void gate_launch(const GateArgs& a, hipStream_t st) {
   else if (nb <= 8) gate_launch_nb<8>(a, st);
   else if (nb <= 12) gate_launch_nb<12>(a, st);
   else gate_launch_nb<kGateMaxBlocks>(a, st);
+}
+
+// gate_modes_kernel: gate_kernel's forms (the same NW, U and rows per workgroup by T), and a 16-block
+// form for 256 experts without a shared gate
+template <int NB, int MR, int NW, int U>
+inline void gate_modes_launch_one(const GateModeArgs& m, bool sigmoid, hipStream_t st) {
+  const dim3 blocks((unsigned)((m.g.T + 16 * MR - 1) / (16 * MR))), threads(64 * NW);
+  if (sigmoid) hipLaunchKernelGGL((gate_modes_kernel<NB, MR, NW, U, kGateSigmoidEx>), blocks, threads, 0, st, m);
+  else hipLaunchKernelGGL((gate_modes_kernel<NB, MR, NW, U, kGateSoftmaxEx>), blocks, threads, 0, st, m);
+}
+// (16 blocks would fit 8 waves - 64 KiB of partial sums, 241 VGPRs - and ran no faster than 4 at
+// H = 7168: DESIGN.md §4 "Router: the other routing rules")
+template <int NB>
+inline void gate_modes_launch_nb(const GateModeArgs& m, bool sigmoid, hipStream_t st) {
+  constexpr int NW = NB <= 12 ? MXMOE_GATE_NW : 4;
+  constexpr int MAXMR = NB <= 4 ? 4 : NB <= 8 ? 2 : 1;
+  const int mr = gate_rows_per_wg(m.g.T, MAXMR);
+  if constexpr (MAXMR >= 4) {
+    if (mr == 4) return gate_modes_launch_one<NB, 4, NW, gate_group_steps(NB, 4)>(m, sigmoid, st);
+  }
+  if constexpr (MAXMR >= 2) {
+    if (mr == 2) return gate_modes_launch_one<NB, 2, NW, gate_group_steps(NB, 2)>(m, sigmoid, st);
+  }
+  gate_modes_launch_one<NB, 1, NW, gate_group_steps(NB, 1)>(m, sigmoid, st);
+}
+// one launch; the caller has validated the arguments (T > 0)
+inline void gate_modes_launch(const GateModeArgs& m, bool sigmoid, hipStream_t st) {
+  const int nb = (m.g.E + (m.g.w_shared ? 1 : 0) + 15) / 16;
+  if (nb <= 1) gate_modes_launch_nb<1>(m, sigmoid, st);
+  else if (nb <= 2) gate_modes_launch_nb<2>(m, sigmoid, st);
+  else if (nb <= 4) gate_modes_launch_nb<4>(m, sigmoid, st);
+  else if (nb <= 5) gate_modes_launch_nb<5>(m, sigmoid, st);
+  else if (nb <= 8) gate_modes_launch_nb<8>(m, sigmoid, st);
+  else if (nb <= 12) gate_modes_launch_nb<12>(m, sigmoid, st);
+  else if (nb <= 16) gate_modes_launch_nb<16>(m, sigmoid, st);
+  else gate_modes_launch_nb<kGateMaxBlocks>(m, sigmoid, st);
 }
 
 }  // namespace gate

@@ -12,9 +12,11 @@
 // All four kernels are HBM-bound byte movers: one workgroup per row (token or slot), 16-B
 // coalesced loads of 8 fp16 per lane, reductions in registers / lane shuffles, stores of the packed
 // codes as one 4-B (int4) / 8-B (int8) / 16-B (fp16) word per lane — no LDS tiling, no MFMA.
-// The router in front of them (mxmoe_moe_gate: logits on the MFMA, top-k, softmax) is moe_gate.h.
+// The router in front of them (mxmoe_moe_gate: logits on the MFMA, top-k, softmax; mxmoe_moe_gate_ex:
+// sigmoid scores, selection bias, group-limited top-k) is moe_gate.h.
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <string>
@@ -524,27 +526,66 @@ static int slots_impl(const char* fn, int mode, const void* routed_in, const voi
   return launch_act(mode, a, T * topk + (shared_in ? T : 0), N, shared_in ? N_shared : N, stream, mx);
 }
 
+// what mxmoe_moe_gate and mxmoe_moe_gate_ex check alike, before any HIP call
+static int gate_check(const char* fn, const void* hidden, const void* w_gate, const void* w_shared_gate, int64_t T, int H,
+                      int E, int topk, const int32_t* topk_ids, const float* topk_weights, const float* shared_w) {
+  if (T < 0 || E < 1 || E > 256 || topk < 1 || topk > 16 || topk > E || H <= 0 || H % 32 ||
+      T * topk > (int64_t)1 << 30)
+    return fail(MXMOE_GG_ERR_INVALID, "%s: need T >= 0, 1 <= E <= 256, 1 <= topk <= min(E, 16), H %% 32 == 0, "
+                "T * topk <= 2^30 (T=%lld H=%d E=%d topk=%d)", fn, (long long)T, H, E, topk);
+  if ((w_shared_gate != nullptr) != (shared_w != nullptr))
+    return fail(MXMOE_GG_ERR_INVALID, "%s: w_shared_gate and shared_w must be given together", fn);
+  if (!aligned16(hidden) || !aligned16(w_gate) || !aligned16(w_shared_gate))
+    return fail(MXMOE_GG_ERR_INVALID, "%s: misaligned pointer (hidden / w_gate / w_shared_gate need 16 B)", fn);
+  if (T > 0 && (!hidden || !w_gate || !topk_ids || !topk_weights)) return fail(MXMOE_GG_ERR_INVALID, "%s: NULL pointer", fn);
+  return MXMOE_GG_OK;
+}
+
 extern "C" {
 
 int mxmoe_moe_gate(const void* hidden, const void* w_gate, const void* w_shared_gate, int64_t T, int H, int E, int topk,
                    int renormalize, int32_t* topk_ids, float* topk_weights, float* shared_w, float* logits,
                    void* stream) {
-  if (T < 0 || E < 1 || E > 256 || topk < 1 || topk > 16 || topk > E || H <= 0 || H % 32 ||
-      T * topk > (int64_t)1 << 30)
-    return fail(MXMOE_GG_ERR_INVALID, "mxmoe_moe_gate: need T >= 0, 1 <= E <= 256, 1 <= topk <= min(E, 16), H %% 32 == 0, "
-                "T * topk <= 2^30 (T=%lld H=%d E=%d topk=%d)", (long long)T, H, E, topk);
-  if ((w_shared_gate != nullptr) != (shared_w != nullptr))
-    return fail(MXMOE_GG_ERR_INVALID, "mxmoe_moe_gate: w_shared_gate and shared_w must be given together");
-  if (!aligned16(hidden) || !aligned16(w_gate) || !aligned16(w_shared_gate))
-    return fail(MXMOE_GG_ERR_INVALID, "mxmoe_moe_gate: misaligned pointer (hidden / w_gate / w_shared_gate need 16 B)");
-  if (T == 0) return MXMOE_GG_OK;
-  if (!hidden || !w_gate || !topk_ids || !topk_weights) return fail(MXMOE_GG_ERR_INVALID, "mxmoe_moe_gate: NULL pointer");
+  const int st = gate_check("mxmoe_moe_gate", hidden, w_gate, w_shared_gate, T, H, E, topk, topk_ids, topk_weights, shared_w);
+  if (st != MXMOE_GG_OK || T == 0) return st;
   const gate::GateArgs a{static_cast<const _Float16*>(hidden), static_cast<const _Float16*>(w_gate),
                          static_cast<const _Float16*>(w_shared_gate), T, H, E, topk, renormalize != 0, topk_ids,
                          topk_weights, shared_w, logits};
   gate::gate_launch(a, (hipStream_t)stream);
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail(MXMOE_GG_ERR_HIP, "gate_kernel launch failed: %s", hipGetErrorString(e));
+  return MXMOE_GG_OK;
+}
+
+int mxmoe_moe_gate_ex(const void* hidden, const void* w_gate, const void* w_shared_gate, int64_t T, int H, int E, int topk,
+                      int renormalize, int scoring, const float* e_bias, int n_group, int topk_group, int group_top,
+                      float routed_scale, int32_t* topk_ids, float* topk_weights, float* shared_w, float* logits,
+                      float* scores, void* stream) {
+  const char* fn = "mxmoe_moe_gate_ex";
+  if (scoring != MXMOE_GATE_SOFTMAX && scoring != MXMOE_GATE_SIGMOID)
+    return fail(MXMOE_GG_ERR_INVALID, "%s: scoring must be MXMOE_GATE_SOFTMAX or MXMOE_GATE_SIGMOID (got %d)", fn, scoring);
+  const int st = gate_check(fn, hidden, w_gate, w_shared_gate, T, H, E, topk, topk_ids, topk_weights, shared_w);
+  if (st != MXMOE_GG_OK) return st;
+  if (n_group < 1 || n_group > 8 || E % n_group || (E / n_group) % 4 || topk_group < 1 || topk_group > n_group ||
+      (int64_t)topk > (int64_t)topk_group * (E / n_group))
+    return fail(MXMOE_GG_ERR_INVALID, "%s: need 1 <= n_group <= 8, E %% n_group == 0, (E / n_group) %% 4 == 0, "
+                "1 <= topk_group <= n_group (1 without groups), topk <= topk_group * E / n_group "
+                "(E=%d topk=%d n_group=%d topk_group=%d)", fn, E, topk, n_group, topk_group);
+  if (group_top < 1 || group_top > 2 || group_top > E / n_group)
+    return fail(MXMOE_GG_ERR_INVALID, "%s: group_top must be 1 or 2 and at most E / n_group (got %d)", fn, group_top);
+  if (scoring == MXMOE_GATE_SOFTMAX && (e_bias || scores || group_top != 1))
+    return fail(MXMOE_GG_ERR_INVALID, "%s: softmax scoring takes no e_bias, no scores output and group_top == 1", fn);
+  if (!std::isfinite(routed_scale)) return fail(MXMOE_GG_ERR_INVALID, "%s: routed_scale must be finite", fn);
+  if (((uintptr_t)e_bias | (uintptr_t)scores) & 3)
+    return fail(MXMOE_GG_ERR_INVALID, "%s: misaligned pointer (e_bias / scores need 4 B)", fn);
+  if (T == 0) return MXMOE_GG_OK;
+  const gate::GateModeArgs m{{static_cast<const _Float16*>(hidden), static_cast<const _Float16*>(w_gate),
+                              static_cast<const _Float16*>(w_shared_gate), T, H, E, topk, renormalize != 0, topk_ids,
+                              topk_weights, shared_w, logits},
+                             e_bias, scores, n_group, topk_group, group_top, routed_scale};
+  gate::gate_modes_launch(m, scoring == MXMOE_GATE_SIGMOID, (hipStream_t)stream);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(MXMOE_GG_ERR_HIP, "gate_modes_kernel launch failed: %s", hipGetErrorString(e));
   return MXMOE_GG_OK;
 }
 

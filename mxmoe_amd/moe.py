@@ -24,6 +24,7 @@ from __future__ import annotations
 
 import ctypes
 import dataclasses
+import math
 from typing import Optional, Sequence
 
 import torch
@@ -93,15 +94,59 @@ class Routing:
         return out
 
 
+GATE_SCORING = {"softmax": 0, "sigmoid": 1}  # MXMOE_GATE_SOFTMAX / MXMOE_GATE_SIGMOID (include/mxmoe_moe.h)
+
+
+def gate_routing_args(E: int, topk: int, scoring: str = "softmax", e_bias: Optional[torch.Tensor] = None,
+                      n_group: int = 1, topk_group: int = 1, group_top: Optional[int] = None,
+                      routed_scaling_factor: float = 1.0, return_scores: bool = False):
+    """Check the routing arguments ``gate`` and ``MoEBlock`` share as mxmoe_moe_gate_ex does (ValueError);
+    returns (group_top resolved, whether the call is mxmoe_moe_gate's, i.e. everything at its default)."""
+    if scoring not in GATE_SCORING:
+        raise ValueError(f"scoring must be 'softmax' or 'sigmoid', got {scoring!r}")
+    n_group, topk_group = int(n_group), int(topk_group)
+    if not 1 <= n_group <= 8 or E % n_group or (E // n_group) % 4:
+        raise ValueError(f"n_group must be in [1, 8] and split E = {E} into groups of a multiple of 4 experts, got {n_group}")
+    gs = E // n_group
+    if not 1 <= topk_group <= n_group:
+        raise ValueError(f"topk_group must be in [1, n_group = {n_group}], got {topk_group}")
+    if topk > topk_group * gs:
+        raise ValueError(f"topk = {topk} exceeds the {topk_group * gs} experts of {topk_group} kept groups")
+    if group_top is None:
+        group_top = 2 if scoring == "sigmoid" and n_group > 1 else 1
+    if group_top not in (1, 2) or group_top > gs:
+        raise ValueError(f"group_top must be 1 or 2 and at most the group size {gs}, got {group_top}")
+    if scoring == "softmax" and (e_bias is not None or group_top != 1 or return_scores):
+        raise ValueError("softmax scoring takes no e_bias, no return_scores and group_top = 1")
+    if e_bias is not None and (e_bias.dtype != torch.float32 or not e_bias.is_contiguous() or tuple(e_bias.shape) != (E,)):
+        raise ValueError(f"e_bias must be a contiguous f32 [{E}] tensor")
+    if not math.isfinite(routed_scaling_factor):
+        raise ValueError(f"routed_scaling_factor must be finite, got {routed_scaling_factor}")
+    plain = (scoring == "softmax" and n_group == 1 and float(routed_scaling_factor) == 1.0)
+    return group_top, plain
+
+
 def gate(hidden: torch.Tensor, w_gate: torch.Tensor, topk: int, *, renormalize: bool = False,
          w_shared_gate: Optional[torch.Tensor] = None, return_logits: bool = False,
-         stream: Optional[torch.cuda.Stream] = None, out=None):
-    """The router (mxmoe_moe_gate, one launch): hidden fp16 [T, H], w_gate fp16 [E, H] ->
+         stream: Optional[torch.cuda.Stream] = None, out=None, scoring: str = "softmax",
+         e_bias: Optional[torch.Tensor] = None, n_group: int = 1, topk_group: int = 1,
+         group_top: Optional[int] = None, routed_scaling_factor: float = 1.0, return_scores: bool = False):
+    """The router (mxmoe_moe_gate / mxmoe_moe_gate_ex, one launch): hidden fp16 [T, H], w_gate fp16 [E, H] ->
     (topk_ids int32 [T, topk], topk_weights f32 [T, topk], shared_w f32 [T] or None), and the f32
     [T, E] logits as a fourth item with ``return_logits``. Selection on the logits (ties: lower index),
     weights = softmax over all E experts, or over the chosen topk with ``renormalize``; with
     ``w_shared_gate`` (fp16 [H]) shared_w = sigmoid(hidden @ w_shared_gate). ``out``: the tuple a
-    previous call with the same arguments returned, to relaunch on its buffers."""
+    previous call with the same arguments returned, to relaunch on its buffers.
+
+    The other models' rules (semantics: include/mxmoe_moe.h, mxmoe_moe_gate_ex): ``scoring="sigmoid"``
+    selects on sigmoid(logit) + ``e_bias`` (f32 [E]) and weighs by the unbiased score (over the chosen
+    scores' sum with ``renormalize``); ``n_group`` / ``topk_group`` keep the topk_group best of n_group
+    contiguous expert groups, a group scored by its best selection value (``group_top=1``, the softmax
+    default) or the sum of its two best (2, the default for sigmoid with groups);
+    ``routed_scaling_factor`` multiplies the weights; ``return_scores`` appends the f32 [T, E] sigmoid
+    scores after the logits, if any. DeepSeek-V3: scoring="sigmoid", e_bias, n_group=8, topk_group=4,
+    renormalize=True, routed_scaling_factor=2.5. With all of these at their defaults the call is
+    mxmoe_moe_gate's."""
     if hidden.dim() != 2 or hidden.dtype != torch.float16 or not hidden.is_contiguous():
         raise ValueError("hidden must be a contiguous fp16 [T, H] tensor")
     T, H = hidden.shape
@@ -111,17 +156,17 @@ def gate(hidden: torch.Tensor, w_gate: torch.Tensor, topk: int, *, renormalize: 
     sg = w_shared_gate
     if sg is not None and (sg.dtype != torch.float16 or not sg.is_contiguous() or sg.numel() != H):
         raise ValueError(f"w_shared_gate must be a contiguous fp16 tensor of {H} elements")
+    group_top, plain = gate_routing_args(E, topk, scoring, e_bias, n_group, topk_group, group_top,
+                                         routed_scaling_factor, return_scores)
     dev = hidden.device
+    if e_bias is not None and e_bias.device != dev:
+        raise ValueError("e_bias must be on hidden's device")
+    want = [((T, topk), torch.int32), ((T, topk), torch.float32), ((T,), torch.float32) if sg is not None else None]
+    want += [((T, E), torch.float32)] * (int(bool(return_logits)) + int(bool(return_scores)))
     if out is None:
-        out = (torch.empty(T, topk, dtype=torch.int32, device=dev), torch.empty(T, topk, dtype=torch.float32, device=dev),
-               torch.empty(T, dtype=torch.float32, device=dev) if sg is not None else None)
-        if return_logits:
-            out += (torch.empty(T, E, dtype=torch.float32, device=dev),)
+        out = tuple(None if w is None else torch.empty(*w[0], dtype=w[1], device=dev) for w in want)
     else:
         out = tuple(out)
-        want = [((T, topk), torch.int32), ((T, topk), torch.float32), ((T,), torch.float32) if sg is not None else None]
-        if return_logits:
-            want.append(((T, E), torch.float32))
         if len(out) != len(want):
             raise ValueError(f"out must hold {len(want)} items")
         for o, w in zip(out, want):
@@ -130,8 +175,15 @@ def gate(hidden: torch.Tensor, w_gate: torch.Tensor, topk: int, *, renormalize: 
                 raise ValueError("out does not match this call's outputs (shape, dtype, contiguity or device)")
     ids, wts, sw = out[:3]
     logits = out[3] if return_logits else None
-    nat.check(nat.lib().mxmoe_moe_gate(_ptr(hidden), _ptr(w_gate), _ptr(sg), T, H, E, topk, int(bool(renormalize)),
-                                       _ptr(ids), _ptr(wts), _ptr(sw), _ptr(logits), _stream(stream)))
+    scores = out[-1] if return_scores else None
+    if plain:
+        nat.check(nat.lib().mxmoe_moe_gate(_ptr(hidden), _ptr(w_gate), _ptr(sg), T, H, E, topk, int(bool(renormalize)),
+                                           _ptr(ids), _ptr(wts), _ptr(sw), _ptr(logits), _stream(stream)))
+    else:
+        nat.check(nat.lib().mxmoe_moe_gate_ex(_ptr(hidden), _ptr(w_gate), _ptr(sg), T, H, E, topk, int(bool(renormalize)),
+                                              GATE_SCORING[scoring], _ptr(e_bias), int(n_group), int(topk_group), group_top,
+                                              float(routed_scaling_factor), _ptr(ids), _ptr(wts), _ptr(sw), _ptr(logits),
+                                              _ptr(scores), _stream(stream)))
     return out
 
 
@@ -619,23 +671,29 @@ class MoEBlock:
 
     w_gate: fp16 [E, H]; topk / renormalize: the model's routing (qwen2_moe: 4, DeepSeek-V2-Lite: 6,
     both without renormalisation; Mixtral: 2 with); w_shared_gate: fp16 [H], qwen2_moe's
-    shared_expert_gate (only for a layer with a shared expert)."""
+    shared_expert_gate (only for a layer with a shared expert); scoring, e_bias, n_group, topk_group,
+    group_top, routed_scaling_factor: ``gate``'s (DeepSeek-V3 / V2, GLM-4.5)."""
 
     def __init__(self, ffn: MoEFFN, w_gate: torch.Tensor, topk: int, renormalize: bool = False,
-                 w_shared_gate: Optional[torch.Tensor] = None):
+                 w_shared_gate: Optional[torch.Tensor] = None, scoring: str = "softmax",
+                 e_bias: Optional[torch.Tensor] = None, n_group: int = 1, topk_group: int = 1,
+                 group_top: Optional[int] = None, routed_scaling_factor: float = 1.0):
         if tuple(w_gate.shape) != (ffn.E, ffn.H):
             raise ValueError(f"w_gate must be [{ffn.E}, {ffn.H}], got {tuple(w_gate.shape)}")
         if w_shared_gate is not None and not ffn.has_shared:
             raise ValueError("w_shared_gate given for a layer without a shared expert")
         if w_shared_gate is not None and w_shared_gate.numel() != ffn.H:
             raise ValueError(f"w_shared_gate must hold {ffn.H} elements")
+        gate_routing_args(ffn.E, topk, scoring, e_bias, n_group, topk_group, group_top, routed_scaling_factor)
         self.ffn, self.topk, self.renormalize = ffn, topk, renormalize
+        self.routing = dict(scoring=scoring, e_bias=None if e_bias is None else e_bias.contiguous(), n_group=n_group,
+                            topk_group=topk_group, group_top=group_top, routed_scaling_factor=routed_scaling_factor)
         self.w_gate = w_gate.contiguous()
         self.w_shared_gate = None if w_shared_gate is None else w_shared_gate.contiguous()
 
     def forward(self, hidden: torch.Tensor, return_intermediates: bool = False):
         ids, wts, sw = gate(hidden, self.w_gate, self.topk, renormalize=self.renormalize,
-                            w_shared_gate=self.w_shared_gate)
+                            w_shared_gate=self.w_shared_gate, **self.routing)
         res = self.ffn.forward(hidden, ids, wts, sw, return_intermediates=return_intermediates)
         if return_intermediates:
             out, mid = res
@@ -745,34 +803,88 @@ def qwen2_layer_bench(rounds: int = 4, iters: int = 30, bs: int = 8192, model: s
 
 
 GATE_MODELS = {"qwen2_moe": dict(H=2048, E=60, topk=4, shared_gate=True),
-               "ds2": dict(H=2048, E=64, topk=6, shared_gate=False)}
+               "ds2": dict(H=2048, E=64, topk=6, shared_gate=False),
+               # DeepSeek-V3 / R1 (noaux_tc) and the full DeepSeek-V2 (group_limited_greedy)
+               "ds3": dict(H=7168, E=256, topk=8, shared_gate=False, renormalize=True, bias=True,
+                           routing=dict(scoring="sigmoid", n_group=8, topk_group=4, routed_scaling_factor=2.5)),
+               "ds2_full": dict(H=5120, E=160, topk=6, shared_gate=False,
+                                routing=dict(scoring="softmax", n_group=8, topk_group=3, group_top=1,
+                                             routed_scaling_factor=16.0))}
 HBM_ROOF_BYTES_PER_S = 8e12  # MI355X
+
+
+def _group_mask(group_scores: torch.Tensor, topk_group: int, gs: int) -> torch.Tensor:
+    """The published group stage (DeepSeek-V2 / V3 MoEGate.forward): bool [T, E], the kept groups' experts."""
+    T, n_group = group_scores.shape
+    group_idx = torch.topk(group_scores, k=topk_group, dim=-1, sorted=False)[1]
+    group_mask = torch.zeros_like(group_scores)
+    group_mask.scatter_(1, group_idx, 1)
+    return group_mask.unsqueeze(-1).expand(T, n_group, gs).reshape(T, -1).bool()
+
+
+def gate_composite(logits: torch.Tensor, topk: int, renormalize: bool = False, e_bias: Optional[torch.Tensor] = None,
+                   scoring: str = "softmax", n_group: int = 1, topk_group: int = 1, group_top: Optional[int] = None,
+                   routed_scaling_factor: float = 1.0):
+    """The models' public routing code on f32 logits, in torch: softmax -> topk (qwen2_moe,
+    DeepSeek-V2-Lite), DeepSeek-V2's group_limited_greedy, DeepSeek-V3's noaux_tc (masked_fill 0.0 as
+    published). Returns (int32 ids, f32 weights)."""
+    T, E = logits.shape
+    if scoring == "softmax":
+        scores = torch.softmax(logits, dim=-1)
+        choice = scores
+        if n_group > 1:
+            group_scores = scores.view(T, n_group, -1).max(dim=-1).values
+            choice = scores.masked_fill(~_group_mask(group_scores, topk_group, E // n_group), 0.0)
+        wts, ids = torch.topk(choice, topk, dim=-1)
+    else:
+        scores = logits.sigmoid()
+        choice = scores if e_bias is None else scores + e_bias.unsqueeze(0)
+        if n_group > 1:
+            group_scores = choice.view(T, n_group, -1).topk(2, dim=-1)[0].sum(dim=-1)
+            choice = choice.masked_fill(~_group_mask(group_scores, topk_group, E // n_group), 0.0)
+        ids = torch.topk(choice, topk, dim=-1)[1]
+        wts = scores.gather(1, ids)
+    if renormalize:
+        wts = wts / (wts.sum(dim=-1, keepdim=True) + 1e-20)
+    if routed_scaling_factor != 1.0:
+        wts = wts * routed_scaling_factor
+    return ids.to(torch.int32), wts
 
 
 def gate_bench(bs: int = 8192, model: str = "qwen2_moe", rounds: int = 4, iters: int = 30) -> dict:
     """The router kernel against the torch composite it replaces (fp16 matmul -> f32 softmax -> topk
-    -> int32 ids, + sigmoid(hidden @ w_sg) for qwen2_moe), same process, interleaved round by round:
+    -> int32 ids, + sigmoid(hidden @ w_sg) for qwen2_moe; for ds3 / ds2_full the public group-limited
+    routing code, ``gate_composite``), same process, interleaved round by round:
     per side the median of the rounds' medians with min / max (µs) and the composite's run-to-run
     spread (max - min) / median; the kernel's algorithmic bytes and fraction of the HBM roof.
-    model: "qwen2_moe" (H 2048, E 60, top-4, shared gate) or "ds2" (DeepSeek-V2-Lite: E 64, top-6)."""
+    model: "qwen2_moe" (H 2048, E 60, top-4, shared gate), "ds2" (DeepSeek-V2-Lite: E 64, top-6),
+    "ds3" (DeepSeek-V3: H 7168, E 256, top-8, 8 groups / 4 kept, sigmoid + bias, renormalised, factor
+    2.5) or "ds2_full" (DeepSeek-V2: H 5120, E 160, top-6, 8 groups / 3 kept, softmax, factor 16)."""
     from .harness import time_launches
 
     m = GATE_MODELS[model]
     H, E, topk = m["H"], m["E"], m["topk"]
+    routing = dict(m.get("routing", {}))
+    renorm = bool(m.get("renormalize", False))
     dev = "cuda"
     g = torch.Generator().manual_seed(0)
     hidden = torch.randn(bs, H, generator=g).half().to(dev)
     w_gate = (torch.randn(E, H, generator=g) * H ** -0.5).half().to(dev)
     w_sg = (torch.randn(H, generator=g) * H ** -0.5).half().to(dev) if m["shared_gate"] else None
-    bufs = gate(hidden, w_gate, topk, w_shared_gate=w_sg)
+    if m.get("bias"):
+        routing["e_bias"] = (torch.randint(-64, 65, (E,), generator=g).float() / 256).to(dev)
+    bufs = gate(hidden, w_gate, topk, renormalize=renorm, w_shared_gate=w_sg, **routing)
 
     def kernel():
-        gate(hidden, w_gate, topk, w_shared_gate=w_sg, out=bufs)
+        gate(hidden, w_gate, topk, renormalize=renorm, w_shared_gate=w_sg, out=bufs, **routing)
 
     def composite():
         logits = (hidden @ w_gate.T).float()
-        wts, ids = torch.topk(torch.softmax(logits, dim=-1), topk, dim=-1)
-        ids = ids.to(torch.int32)
+        if routing:
+            ids, wts = gate_composite(logits, topk, renorm, **routing)
+        else:
+            wts, ids = torch.topk(torch.softmax(logits, dim=-1), topk, dim=-1)
+            ids = ids.to(torch.int32)
         sw = torch.sigmoid(hidden @ w_sg) if w_sg is not None else None
         return ids, wts, sw
 
@@ -792,6 +904,10 @@ def gate_bench(bs: int = 8192, model: str = "qwen2_moe", rounds: int = 4, iters:
     out = {"model": model, "bs": bs, "H": H, "E": E, "topk": topk, "shared_gate": w_sg is not None,
            "kernel": side(res["kernel"]), "torch": side(res["torch"])}
     nbytes = bs * H * 2 + (E + 1) * H * 2 + bs * topk * 8 + (bs * 4 if w_sg is not None else 0)
+    if routing:
+        nbytes += E * 4 if "e_bias" in routing else 0
+        out["routing"] = {k: v for k, v in routing.items() if k != "e_bias"}
+        out["routing"].update(renormalize=renorm, e_bias="e_bias" in routing)
     out["bytes"] = nbytes
     out["hbm_fraction"] = round(nbytes / (out["kernel"]["median_us"] * 1e-6) / HBM_ROOF_BYTES_PER_S, 4)
     out["speedup"] = round(out["torch"]["median_us"] / out["kernel"]["median_us"], 3)

@@ -1,5 +1,5 @@
 """Print mxmoe_amd.moe.gate_bench (the router kernel against the torch composite) as JSON lines:
-    python tools/gate_bench.py [--bs 8192 128] [--models qwen2_moe ds2] [--out FILE]"""
+    python tools/gate_bench.py [--bs 8192 128] [--models qwen2_moe ds2 ds3 ds2_full] [--out FILE]"""
 from __future__ import annotations
 
 import argparse
