@@ -63,7 +63,8 @@ enum {
   MXMOE_GG_FMT_E4M3 = 1,    /* w8a8_g-1_sym_E4M3: OCP fp8 e4m3 codes                         */
   MXMOE_GG_FMT_BF16 = 2,    /* bf16: 16-bit operands are bfloat16                              */
   /* 3: fp6 images of int4 codes (tools-only lab library) */
-  MXMOE_GG_FMT_MXFP4 = 4    /* w4a4_g32_sym_MXFP4: OCP MXFP4, e2m1 codes + e8m0 block scales   */
+  MXMOE_GG_FMT_MXFP4 = 4    /* w4a4_g32_sym_MXFP4 and w4a16_g32_sym_MXFP4: OCP MXFP4, e2m1 codes + e8m0
+                             * block scales (a_bits selects: 4 = both operands, 16 = fp16 A, weights only) */
 };
 
 /* MXFP4 operands (fmt MXMOE_GG_FMT_MXFP4; a_bits = w_bits = 4, gsize = 32, sym; K % 32 == 0).
@@ -83,6 +84,28 @@ enum {
  *           sum_{k in b} a[m][k] b[n][k]), accumulated in f32 by the block-scaled MFMA (summation order
  *           unspecified); no per-channel fp16 scales. Runs on the v2x variant only (AUTO picks it for
  *           every call that holds an MXFP4 problem); no SiLU epilogue. */
+
+/* Weight-only MXFP4 (fmt MXMOE_GG_FMT_MXFP4 with a_bits = 16, w_bits = 4, gsize = 32, sym: w4a16_g32_sym_MXFP4;
+ * plan-info qtype_mask bit 11). fp16 activations on MXFP4 weights, on the fp16 MFMA.
+ *   A      : fp16 [M][K]; scale_a unused (may be NULL).
+ *   B      : uint8 [N][K/2] CANONICAL e2m1 codes (element 2i the low nibble of byte i) and scale_b the e8m0
+ *            bytes in the DEVICE layout above ([N][16 ceil(K/32 / 16)], 4-byte aligned, pads 127): byte for
+ *            byte the B operand of a w4a4_g32_sym_MXFP4 problem, so one copy of a layer's MXFP4 weights
+ *            serves both types. NOT the K-interleaved mxmoe_gg_repack_weightonly layout: there is no repack.
+ *   limits : K % 64 == 0 (the weight-only stage), N % 8 == 0, K <= 2^20; lda / ldb / ldc as for the other
+ *            weight-only types.
+ *   result : b[n][k] = e2m1(code) * 2^(sb[n][k/32] - 127) as an fp16 value (the hardware convert
+ *            v_cvt_scalef32_pk_f16_fp4 with the f32 scale `byte << 23`); C[m][n] = fp16_rn(sum_k f32(A[m][k])
+ *            * f32(b[n][k])), accumulated in f32 by v_mfma_f32_16x16x32_f16 (summation order unspecified).
+ *            b is exact for every code whenever the scale byte is in [104, 140]. Outside that range the
+ *            result is RECORDED, NOT SPECIFIED: bytes 1..103 underflow (values below fp16's
+ *            subnormal grid round to it or to zero), byte 0 is taken as a zero scale (b = +-0, not 2^-127),
+ *            bytes 141..254 overflow to +-inf for the larger codes and byte 255 gives inf / NaN — an inf
+ *            times a zero of A is NaN, so such a scale poisons its whole output column and no other.
+ *            quantize.quant_mxfp4 of fp16 weights yields bytes 101..140, 0 (all-zero block) or 255.
+ *   runs on: the small-batch kernel wo3 (AUTO picks it under the weight-only rule: mean M <= 512) and v2x;
+ *            a call that also holds a w4a4_g32_sym_MXFP4 problem stays on v2x. MXMOE_GG_EPI_SILU_MUL: on wo3
+ *            only, as for the other weight-only types (scale_b rows permuted with the B rows). */
 
 /* Epilogue flag, OR-ed into mxmoe_gg_problem.fmt (fp16, w8a8_g-1_sym and w4a4_g-1_sym problems on the
  * v2x, v3 and wo3 variants; weight-only WxA16 problems on wo3, whose scale_b is permuted with the rows;
@@ -136,7 +159,7 @@ typedef struct mxmoe_gg_plan_info {
   int32_t block;
   int32_t lds_bytes;
   int32_t qtype_mask;      /* bit q set if a planned problem has quant type q (0 fp16, 1 w8a8, 2 w4a4,
-                            * 3 w4a16, 4 w8a16, 5 w4a4_g128, 6 w2a16, 7 w8a8 E4M3, 8 bf16, 10 MXFP4); bit 16:
+                            * 3 w4a16, 4 w8a16, 5 w4a4_g128, 6 w2a16, 7 w8a8 E4M3, 8 bf16, 10 MXFP4, 11 weight-only MXFP4); bit 16:
                             * a weight-only problem carries MXMOE_GG_EPI_SILU_MUL (small-batch kernel);
                             * selects the kernel specialisation at launch */
   int32_t splitk_slabs;    /* 256-KiB partial-sum slabs the plan's split-K tiles use (0: no split) */

@@ -14,6 +14,7 @@ depends only on A[rows] and B[cols]), for every quant type the library runs:
     tolerance (the MFMA's f32 summation order is unspecified);
   * MXFP4 (w4a4_g32_sym_MXFP4): e2m1 codes and e8m0 block scales decoded (dequant_mxfp4), f64 GEMM —
     fp16 tolerance (f32 accumulation in the MFMA, order unspecified);
+  * weight-only MXFP4 (w4a16_g32_sym_MXFP4): fp16 A, B decoded as above, f64 GEMM — fp16 tolerance;
   * fp16 / bf16: f64 GEMM — relative 1e-3 (north_star) with a cancellation floor.
 
 Unlike the reference's CHECK (abs tol 1.0 against an unquantised cutlass GEMM), integer paths must
@@ -44,6 +45,9 @@ def expected_sample(p, rows: torch.Tensor, cols: torch.Tensor) -> tuple[torch.Te
     """Reference values of C[rows][:, cols] for one problem (CPU) and whether they are bit-exact."""
     q = p.q
     A = p.A.index_select(0, rows).cpu()
+    if q.is_weight_only and q.fmt == "MXFP4":  # canonical e2m1 codes, e8m0 scales in the device layout
+        Bdq = dequant_mxfp4(p.B.index_select(0, cols).cpu(), unpack_mxfp4_scales(p.scale_b.index_select(0, cols).cpu(), p.K))
+        return A.double() @ Bdq.T, False
     if q.is_weight_only:
         codes = unpack_weightonly_mi355x(p.B.index_select(0, cols).cpu(), q.w_bits, p.K)
         G = 1 if q.gsize == -1 else p.K // q.gsize

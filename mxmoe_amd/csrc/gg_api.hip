@@ -135,9 +135,12 @@ void launch_v2(const GGArgs& a, int grid, int qmask, hipStream_t s) {
 #else
     // MXFP4 problems (plan-info bit 10, above the mask below): a kernel of their own, or every tile
     // body beside them — builds apart from the existing ones, which come out unchanged
-    if (qmask & (1 << QT_MXF4)) {
-      if ((qmask & 2047) == (1 << QT_MXF4)) launch_v2_q<ABL, (1 << QT_MXF4)>(a, grid, s);
-      else launch_v2_q<0, 511 | (1 << QT_MXF4)>(a, grid, s);
+    // (weight-only MXFP4, bit 11, likewise: alone, or the widest build with every body)
+    if (qmask & ((1 << QT_MXF4) | (1 << QT_MXF4W))) {
+      if ((qmask & 4095) == (1 << QT_MXF4)) launch_v2_q<ABL, (1 << QT_MXF4)>(a, grid, s);
+      else if ((qmask & 4095) == (1 << QT_MXF4W)) launch_v2_q<ABL, (1 << QT_MXF4W)>(a, grid, s);
+      else if (!(qmask & (1 << QT_MXF4W))) launch_v2_q<0, 511 | (1 << QT_MXF4)>(a, grid, s);
+      else launch_v2_q<0, 511 | (1 << QT_MXF4) | (1 << QT_MXF4W)>(a, grid, s);
       return;
     }
     switch (qmask & 511) {
@@ -228,14 +231,18 @@ void launch_wo2_q(const GGArgs& a, int grid, hipStream_t s) {
 }
 // quant-type sets launched at the variant's NWG (the rest, with 8-bit weight-only problems, run the
 // 2-WG/CU build): keep in step with the switch below
-constexpr bool wo2_full_nwg(int qm) { return qm == 8 || qm == 64 || qm == 10 || qm == 1 || qm == 2 || qm == 4 || qm == 6; }
+constexpr int kQmaskMxW = 1 << QT_MXF4W;  // weight-only MXFP4 (above the 9 bits the switches below see)
+constexpr int kWo2Types = 511 | kQmaskMxW;
+constexpr bool wo2_full_nwg(int qm) {
+  return qm == 8 || qm == 64 || qm == 10 || qm == 1 || qm == 2 || qm == 4 || qm == 6 || qm == kQmaskMxW;
+}
 // plan-info qtype_mask bit: a weight-only problem carries MXMOE_GG_EPI_SILU_MUL (selects the WO_SILU
 // build; with it only the w4a16 and w4a16 + w8a8 sets run at the variant's NWG)
 constexpr int kQmaskWoSilu = 1 << 16;
-constexpr bool wo2_full_nwg_silu(int qm) { return qm == 8 || qm == 10; }
+constexpr bool wo2_full_nwg_silu(int qm) { return qm == 8 || qm == 10 || qm == kQmaskMxW; }
 template <int NWG>
 int wo2_launch_lds(int qmask) {
-  const bool full = (qmask & kQmaskWoSilu) ? wo2_full_nwg_silu(qmask & 511) : wo2_full_nwg(qmask & 511);
+  const bool full = (qmask & kQmaskWoSilu) ? wo2_full_nwg_silu(qmask & kWo2Types) : wo2_full_nwg(qmask & kWo2Types);
   return full ? wo2_lds_bytes<NWG>() : wo2_lds_bytes<2>();
 }
 template <int ABL, int NWG>
@@ -252,6 +259,11 @@ void launch_wo2(const GGArgs& a, int grid, int qmask, hipStream_t s) {
 #else
   if (qmask & kQmaskWoSilu) {  // weight-only problems with the fused SiLU epilogue (WO_SILU builds)
     constexpr int AS = ABL | WO_SILU;
+    if (qmask & kQmaskMxW) {  // weight-only MXFP4: alone at the variant's NWG, else the wide 2-WG/CU build
+      if ((qmask & kWo2Types) == kQmaskMxW) launch_wo2_q<AS, kQmaskMxW, NWG>(a, grid, s);
+      else launch_wo2_q<AS, 95 | kQmaskMxW, 2>(a, grid, s);
+      return;
+    }
     switch (qmask & 511) {
       case 8: launch_wo2_q<AS, 8, NWG>(a, grid, s); break;    // w4a16
       case 10: launch_wo2_q<AS, 10, NWG>(a, grid, s); break;  // w4a16 + w8a8 (any other mix: the wide
@@ -259,6 +271,11 @@ void launch_wo2(const GGArgs& a, int grid, int qmask, hipStream_t s) {
       case 16: launch_wo2_q<AS, 16, 2>(a, grid, s); break;
       default: launch_wo2_q<AS, 95, 2>(a, grid, s); break;
     }
+    return;
+  }
+  if (qmask & kQmaskMxW) {
+    if ((qmask & kWo2Types) == kQmaskMxW) launch_wo2_q<ABL, kQmaskMxW, NWG>(a, grid, s);
+    else launch_wo2_q<ABL, 95 | kQmaskMxW, 2>(a, grid, s);
     return;
   }
   switch (qmask & 511) {
@@ -285,7 +302,7 @@ Variant make_v0(const char* name) {
   v.geom[QT_F16] = {C16::BM, C16::BN, C16::BKB, C16::kThreads};
   v.geom[QT_I8] = {C8::BM, C8::BN, C8::BKB, C8::kThreads};
   v.geom[QT_I4] = {C4::BM, C4::BN, C4::BKB, C4::kThreads};
-  for (int q : {QT_W4A16, QT_W8A16, QT_I4G, QT_W2A16, QT_F8, QT_BF16, QT_I4F6, QT_MXF4}) v.geom[q] = {0, 0, 0, 0};  // v2 kernels only
+  for (int q : {QT_W4A16, QT_W8A16, QT_I4G, QT_W2A16, QT_F8, QT_BF16, QT_I4F6, QT_MXF4, QT_MXF4W}) v.geom[q] = {0, 0, 0, 0};  // v2 kernels only
   v.threads = C16::kThreads;
   v.lds_bytes = FusedCfg<C16, C8, C4>::LDS_BYTES;
   v.chunk = FusedCfg<C16, C8, C4>::LDS_BYTES <= 80 * 1024 ? 64 : 32;  // workgroups per XCD at once
@@ -302,7 +319,7 @@ Variant make_v3(const char* name) {
   v.name = name;
   v.kind = Kind::V3;
   for (int q = 0; q < QT_COUNT; ++q) v.geom[q] = {256, BN, 64, CT::NT};  // (weight-only / g128 / fp8 / bf16 cleared below)
-  for (int q : {QT_W4A16, QT_W8A16, QT_I4G, QT_W2A16, QT_F8, QT_BF16, QT_I4F6, QT_MXF4}) v.geom[q] = {0, 0, 0, 0};  // v2 kernels only
+  for (int q : {QT_W4A16, QT_W8A16, QT_I4G, QT_W2A16, QT_F8, QT_BF16, QT_I4F6, QT_MXF4, QT_MXF4W}) v.geom[q] = {0, 0, 0, 0};  // v2 kernels only
   v.threads = CT::NT;
   v.lds_bytes = CT::LDS_BYTES;
   v.chunk = 32 * (160 * 1024 / CT::LDS_BYTES >= 2 ? 2 : 1);  // workgroups per XCD at once
@@ -348,10 +365,12 @@ Variant v2_base(const char* name, int lds_bytes) {
   v.geom[QT_W4A16] = {256, 256, 32, 512};  // 64-K stages: 32 B of 4-bit codes per row
   v.geom[QT_W8A16] = {256, 256, 64, 512};
   v.geom[QT_W2A16] = {256, 256, 16, 512};  // 64-K stages: 16 B of 2-bit codes per row
+  v.geom[QT_MXF4W] = {256, 256, 32, 512};  // weight-only MXFP4: the 4-bit stage
   v.geom[QT_I4G] = {256, 256, 128, 512};  // w4a4 g128 (gg_tile_g128): 256 / 128-row classes as int4
   v.geom[QT_I4F6] = {0, 0, 0, 0};         // fp6 images: the f6 kernel only
 #ifdef MXMOE_LAB
   v.geom[QT_MXF4] = {0, 0, 0, 0};         // (the lab library's launch tables carry no MXFP4 build)
+  v.geom[QT_MXF4W] = {0, 0, 0, 0};
 #endif
   v.threads = 512;
   v.lds_bytes = lds_bytes;
@@ -399,7 +418,7 @@ Variant make_wo2(const char* name) {
 template <int TRACE = 0>
 Variant make_v2p(const char* name) {
   Variant v = make_v2<V2_STAGGER | V2_B3 | V2_BUF | V2_EARLYDMA | (4 << V2_SPREAD_SHIFT)>(name);
-  v.geom[QT_MXF4] = {0, 0, 0, 0};  // (no MXFP4 body in the persistent kernels)
+  v.geom[QT_MXF4] = v.geom[QT_MXF4W] = {0, 0, 0, 0};  // (no MXFP4 body in the persistent kernels)
   v.persistent = true;
   v.lds_bytes = 160 * 1024;
   v.launch = &launch_v2p<TRACE>;
@@ -643,7 +662,12 @@ int qtype_of(int a_bits, int w_bits, int gsize, int sym, int fmt, int* qt) {
       *qt = QT_MXF4;
       return MXMOE_GG_OK;
     }
-    return fail(MXMOE_GG_ERR_UNSUPPORTED, "quant type not supported: w%da%d_g%d_%s_MXFP4 (only w4a4_g32_sym_MXFP4)",
+    if (a_bits == 16 && w_bits == 4 && gsize == 32 && sym) {  // weight-only: fp16 A on the same B operand
+      *qt = QT_MXF4W;
+      return MXMOE_GG_OK;
+    }
+    return fail(MXMOE_GG_ERR_UNSUPPORTED,
+                "quant type not supported: w%da%d_g%d_%s_MXFP4 (only w4a4_g32_sym_MXFP4 and w4a16_g32_sym_MXFP4)",
                 w_bits, a_bits, gsize, sym ? "sym" : "asym");
   }
 #ifdef MXMOE_LAB
@@ -681,7 +705,7 @@ int qtype_of(int a_bits, int w_bits, int gsize, int sym, int fmt, int* qt) {
               sym ? "sym" : "asym");
 }
 
-bool is_weightonly(int qt) { return qt == QT_W4A16 || qt == QT_W8A16 || qt == QT_W2A16; }
+bool is_weightonly(int qt) { return qt == QT_W4A16 || qt == QT_W8A16 || qt == QT_W2A16 || qt == QT_MXF4W; }
 bool is_float16(int qt) { return qt == QT_F16 || qt == QT_BF16; }  // 16-bit operands, no scales
 
 size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
@@ -714,9 +738,12 @@ WsLayout ws_layout(int P, int grid, int slabs) {
 // Validate one problem and fill its table row.
 // Weight-only WxA16: A fp16 [M][K], B codes [N][K * w_bits / 8] (mxmoe_gg_repack_weightonly
 // layout), scale_b = scale / zp in the reference permute_scale layout; K in 64-element stages.
+// Weight-only MXFP4 (QT_MXF4W, g32): B canonical e2m1 codes, scale_b e8m0 bytes in the MXFP4 device
+// layout — no repack, no fp16 scale groups: the kernel sees one group over all K stages.
 int build_meta_weightonly(const HostProblem& p, int idx, int qt, const Variant& v, bool check_ptrs, GGMeta* m) {
+  const bool mx = qt == QT_MXF4W;
   if (p.K % 64) return fail(MXMOE_GG_ERR_INVALID, "problem %d: weight-only needs K %% 64 == 0 (K=%d)", idx, p.K);
-  if (p.gsize != -1 && (p.gsize <= 0 || p.gsize % 64 || p.K % p.gsize))
+  if (!mx && p.gsize != -1 && (p.gsize <= 0 || p.gsize % 64 || p.K % p.gsize))
     return fail(MXMOE_GG_ERR_UNSUPPORTED, "problem %d: weight-only group size %d must be -1 or a multiple of 64 dividing K=%d",
                 idx, p.gsize, p.K);
   if (p.N % 8 != 0) return fail(MXMOE_GG_ERR_INVALID, "problem %d: N=%d must be a multiple of 8", idx, p.N);
@@ -735,9 +762,13 @@ int build_meta_weightonly(const HostProblem& p, int idx, int qt, const Variant& 
     if (!p.SB) return fail(MXMOE_GG_ERR_INVALID, "problem %d: NULL scale pointer (weight-only scale_b)", idx);
     if (((uintptr_t)p.A | (uintptr_t)p.B | (uintptr_t)p.C) & 15)
       return fail(MXMOE_GG_ERR_INVALID, "problem %d: A/B/C must be 16-byte aligned", idx);
+    if (mx && (((uintptr_t)p.SB) & 3))  // (the kernel reads scale dwords)
+      return fail(MXMOE_GG_ERR_INVALID, "problem %d: MXFP4 scales must be 4-byte aligned", idx);
     if (((uintptr_t)p.SB) & (p.sym ? 1 : 3))
       return fail(MXMOE_GG_ERR_INVALID, "problem %d: scales must be %d-byte aligned", idx, p.sym ? 2 : 4);
   }
+  // the scale loads address a 256-column tile's rows with a 32-bit offset
+  if (mx && p.K > (1 << 20)) return fail(MXMOE_GG_ERR_INVALID, "problem %d: K=%d exceeds 2^20 (MXFP4 weight-only)", idx, p.K);
   memset(m, 0, sizeof(*m));
   m->M = p.M;
   m->N = p.N;
@@ -745,7 +776,7 @@ int build_meta_weightonly(const HostProblem& p, int idx, int qt, const Variant& 
   m->qtype = qt;
   m->tiles_n = (p.N + v.geom[qt].bn - 1) / v.geom[qt].bn;
   m->kbytes = (int32_t)arow;
-  m->reserved = p.gsize == -1 ? std::max(1, p.K / 64) : p.gsize / 64;  // 64-K stages per scale group
+  m->reserved = (p.gsize == -1 || mx) ? std::max(1, p.K / 64) : p.gsize / 64;  // 64-K stages per scale group
   m->reserved2 = (p.sym ? 1 : 0) | (silu ? META_SILU : 0);
   m->lda_b = lda_b;
   m->ldb_b = ldb_b;
@@ -933,7 +964,8 @@ int plan_host(const std::vector<HostProblem>& probs, int variant, bool check_ptr
     const double rows = class_rows(cls, g), cols = g.bn;
     double bytes, equiv;
     if (is_weightonly(m.qtype)) {  // 64 K elements per stage, fp16 A
-      bytes = rows * 128 + cols * 64 * (m.qtype == QT_W2A16 ? 2 : m.qtype == QT_W4A16 ? 4 : 8) / 8.0;
+      // (weight-only MXFP4: the 4-bit stage; its 2 scale bytes per column are 1/16 of the codes)
+      bytes = rows * 128 + cols * 64 * (m.qtype == QT_W2A16 ? 2 : (m.qtype == QT_W4A16 || m.qtype == QT_MXF4W) ? 4 : 8) / 8.0;
       equiv = 2.0 * rows * cols * 64 / 128;
     } else {
       const double kel = m.qtype == QT_I4F6 ? 128.0
@@ -1493,7 +1525,9 @@ int resolve_variant(int variant, const std::vector<HostProblem>& hp, int* out) {
     if (p.M > 0 || qt == QT_MXF4) mask |= 1 << qt;
   }
   *out = variant_index(kDefaultVariantName);
-  const int wo_mask = (1 << QT_W4A16) | (1 << QT_W8A16) | (1 << QT_W2A16);
+  // (weight-only MXFP4 counts as weight-only; beside a w4a4 MXFP4 problem the call keeps v2x, the
+  // only variant with that body)
+  const int wo_mask = (1 << QT_W4A16) | (1 << QT_W8A16) | (1 << QT_W2A16) | (1 << QT_MXF4W);
   const int small_mask = wo_mask | (1 << QT_I8) | (1 << QT_F16) | (1 << QT_I4);
   // (fused SiLU calls too: the small-batch kernel's fp16 / w8a8 / w4a4 bodies carry the epilogue)
   if (mask != 0 && (mask & ~small_mask) == 0) {
@@ -1631,22 +1665,23 @@ int mxmoe_gg_list_variants(char* buf, size_t n) {
   // weight-only kernels cover every group size / sym of a bit width: listed under the base name
   static const char* qnames[QT_COUNT] = {"fp16",          "w8a8_g-1_sym", "w4a4_g-1_sym",      "w4a16", "w8a16",
                                          "w4a4_g128_sym", "w2a16",        "w8a8_g-1_sym_E4M3", "bf16",  "w4a4_g-1_sym_F6",
-                                         "w4a4_g32_sym_MXFP4"};
-  static const int wbits[QT_COUNT] = {16, 8, 4, 4, 8, 4, 2, 8, 16, 6, 4};
+                                         "w4a4_g32_sym_MXFP4", "w4a16_g32_sym_MXFP4"};
+  static const int wbits[QT_COUNT] = {16, 8, 4, 4, 8, 4, 2, 8, 16, 6, 4, 4};
   std::string out;
   const auto& vs = variants();
   for (size_t i = 0; i < vs.size(); ++i) {
-    char line[1024];
-    int off = snprintf(line, sizeof(line), "%zu %s", i, vs[i].name);
+    char line[2048];
+    size_t off = (size_t)snprintf(line, sizeof(line), "%zu %s", i, vs[i].name);
     for (int q = 0; q < QT_COUNT; ++q) {
       const TileGeom& g = vs[i].geom[q];
       if (g.bn == 0) continue;  // quant type not implemented by this variant
       const int bits = wbits[q];
       const int waves = g.threads / 64;
       const int wm = 2, wn = waves / wm;
-      off += snprintf(line + off, sizeof(line) - off,
-                      " %s=TileConfig(BM=%d, BN=%d, BK=%d, WM=%d, WN=%d, WK=1, STAGE=2)", qnames[q], g.bm, g.bn,
-                      g.bkb * 8 / bits, wm, wn);
+      if (off >= sizeof(line) - 1) break;  // (snprintf returns the untruncated length)
+      off += (size_t)snprintf(line + off, sizeof(line) - off,
+                              " %s=TileConfig(BM=%d, BN=%d, BK=%d, WM=%d, WN=%d, WK=1, STAGE=2)", qnames[q], g.bm, g.bn,
+                              g.bkb * 8 / bits, wm, wn);
     }
     out += line;
     out += "\n";

@@ -38,10 +38,11 @@ namespace mxmoe {
 //          block-scaled fp6 MFMA, f32 accumulate (exact: integer partial sums below 2^24)
 // QT_MXF4: w4a4_g32_sym_MXFP4 (A and B OCP MXFP4: e2m1 codes, one e8m0 scale per 32-K block; the
 //          block-scaled fp4 MFMA applies the scales, f32 accumulate, C = fp16_rn(acc))
+// QT_MXF4W: w4a16_g32_sym_MXFP4 (fp16 A, B as QT_MXF4's B: weight-only, gg_tile_wo's WO_FMT_MX body)
 enum QType : int32_t {
   QT_F16 = 0, QT_I8 = 1, QT_I4 = 2, QT_W4A16 = 3, QT_W8A16 = 4, QT_I4G = 5, QT_W2A16 = 6, QT_F8 = 7, QT_BF16 = 8,
-  QT_I4F6 = 9, QT_MXF4 = 10,
-  QT_COUNT = 11
+  QT_I4F6 = 9, QT_MXF4 = 10, QT_MXF4W = 11,
+  QT_COUNT = 12
 };
 // quant types whose epilogue applies the per-channel scales sa[m] * sb[n]
 constexpr bool qt_scaled(int qt) { return qt == QT_I8 || qt == QT_I4 || qt == QT_F8 || qt == QT_I4F6; }
@@ -2355,11 +2356,35 @@ __device__ __forceinline__ v8h wo_dequant(const uint32_t* w, uint32_t moff2, uin
   return out;
 }
 
-template <class Cfg, int BITS, int WABL = 0>
+// MXFP4 codes (canonical nibble order: element 2i the low nibble of byte i): 8 codes of one dword ->
+// 8 fp16 values e2m1(code) * scale, four v_cvt_scalef32_pk_f16_fp4 (one per byte). `scale` is the
+// block's e8m0 byte << 23 as an f32: 2^(byte - 127) for bytes 1..254, +0 for byte 0, +inf for 255.
+__device__ __forceinline__ v8h wo_dequant_mx(uint32_t w, uint32_t scale_bits) {
+  typedef _Float16 h2 __attribute__((ext_vector_type(2)));
+  const float sc = __builtin_bit_cast(float, scale_bits);
+  const h2 p0 = __builtin_amdgcn_cvt_scalef32_pk_f16_fp4(w, sc, 0);
+  const h2 p1 = __builtin_amdgcn_cvt_scalef32_pk_f16_fp4(w, sc, 1);
+  const h2 p2 = __builtin_amdgcn_cvt_scalef32_pk_f16_fp4(w, sc, 2);
+  const h2 p3 = __builtin_amdgcn_cvt_scalef32_pk_f16_fp4(w, sc, 3);
+  return v8h{p0[0], p0[1], p1[0], p1[1], p2[0], p2[1], p3[0], p3[1]};
+}
+
+// FMT: WO_FMT_INT integer codes in the repacked layout (scale / zp groups of whole stages);
+// WO_FMT_MX (BITS = 4) OCP MXFP4 — canonical e2m1 codes and e8m0 block scales in the device layout of
+// include/mxmoe_gg.h, the B operand of the w4a4 MXFP4 tile as it is. Same stage, DMA pieces and chunk
+// swizzle as 4-bit integer codes; lane (r16, g) reads the dword at byte 4 g of each 16-B K half (8
+// consecutive K: one 16x16x32 operand). Scales: one dwordx4 per column and 8 stages (the layout's
+// 16-B group: 16 blocks), a range-checked buffer load whose num_records ends at the tile's last valid
+// row; stage u of a group has its two bytes in byte u / 2 of dwords 2 (u & 1) and 2 (u & 1) + 1. The
+// integer paths' group machinery sees one group (mt.reserved >= the K stages) and stays idle.
+constexpr int WO_FMT_INT = 0, WO_FMT_MX = 1;
+template <class Cfg, int BITS, int WABL = 0, int FMT = WO_FMT_INT>
 __device__ __forceinline__ void gg_tile_wo(const GGMeta& mt, const uint8_t* __restrict__ A,
                                            const uint8_t* __restrict__ B, const _Float16* __restrict__ SB,
                                            _Float16* __restrict__ C, int m0, int n0, uint8_t* lds, const SplitK& sk) {
   constexpr int FM = Cfg::FM, FN = Cfg::FN, GA = Cfg::GA;
+  constexpr bool MX = FMT == WO_FMT_MX;
+  static_assert(!MX || BITS == 4, "MXFP4 codes are 4-bit");
   constexpr int RB = Cfg::KS * BITS / 8;        // B bytes per row per stage
   // B DMA granule per lane: 16 B, or 4 B for 2-bit codes (16-B rows: 4 lanes per row, so every
   // wave still issues whole instructions and the vmcnt bookkeeping stays uniform)
@@ -2453,7 +2478,7 @@ __device__ __forceinline__ void gg_tile_wo(const GGMeta& mt, const uint8_t* __re
   const uint32_t moff2 = sym ? (BITS == 4 ? 0xE407E407u : BITS == 2 ? 0xE401E401u : 0xE47FE47Fu) : 0xE400E400u;
   uint32_t s2[FN], z2[FN], s2n[FN], z2n[FN];  // current group, next group (prefetched)
   WoK wok;
-  if constexpr ((WABL & WO_NIBPOS) != 0 && BITS != 8) {
+  if constexpr ((WABL & WO_NIBPOS) != 0 && BITS != 8 && !MX) {
     wok.nibpos = true;
     const int off = sym ? (BITS == 4 ? 7 : 1) : 0;
 #pragma unroll
@@ -2467,7 +2492,7 @@ __device__ __forceinline__ void gg_tile_wo(const GGMeta& mt, const uint8_t* __re
       wok.moffq[q] = h | (h << 16);
     }
   }
-  if constexpr ((WABL & WO_ANDOR) != 0) {
+  if constexpr ((WABL & WO_ANDOR) != 0 && !MX) {  // (MXFP4: hardware converts, no constants)
     wok.perm8 = true;
     if constexpr (BITS == 8) asm volatile("" : "+v"(wok.hi8));
     else if constexpr ((WABL & WO_NIBPOS) != 0 && BITS == 4)
@@ -2481,7 +2506,10 @@ __device__ __forceinline__ void gg_tile_wo(const GGMeta& mt, const uint8_t* __re
 #pragma unroll
     for (int j = 0; j < FN; ++j) {
       const int n = min(ncol0 + j * 16 + r16, N - 1);
-      if (sym) {
+      if constexpr (MX) {  // (block scales: mx_load below)
+        so[j] = 0;
+        zo[j] = 0;
+      } else if (sym) {
         const uint32_t s = __builtin_bit_cast(uint16_t, SB[(int64_t)grp * N + n]);
         so[j] = s | (s << 16);
         zo[j] = 0;
@@ -2492,6 +2520,61 @@ __device__ __forceinline__ void gg_tile_wo(const GGMeta& mt, const uint8_t* __re
       }
     }
   };
+
+  // MXFP4 block scales: mxq[j] = the 16-B scale group (absolute stages 8 t .. 8 t + 7) of column j,
+  // transposed back to block order on arrival (8 v_perm_b32 per column and 8 stages) and used as a
+  // queue: dword 0 holds the current stage pair's four bytes, the dwords move down after every odd
+  // stage. mx_s = the absolute stage the next dequant belongs to (stages are dequantised in order in
+  // every loop form; a split-K slice may start anywhere in a group: mx_begin advances the queue).
+  constexpr int MXN = MX ? FN : 1;
+  typedef unsigned int v4u __attribute__((ext_vector_type(4)));
+  [[maybe_unused]] v4u mxq[MXN];
+  [[maybe_unused]] int mx_s = ks0;
+  [[maybe_unused]] const int mx_srow = ((mt.K / 32 + 15) >> 4) << 4;  // scale bytes per row
+  [[maybe_unused]] auto mx_load = [&](int t) {
+    if constexpr (MX) {
+      const __amdgpu_buffer_rsrc_t rss = __builtin_amdgcn_make_buffer_rsrc(
+          const_cast<uint8_t*>(reinterpret_cast<const uint8_t*>(SB)) + (int64_t)n0 * mx_srow, (short)0,
+          min(N - n0, Cfg::BN) * mx_srow, 0x00020000);
+#pragma unroll
+      for (int j = 0; j < FN; ++j)
+        mxq[j] = __builtin_amdgcn_raw_buffer_load_b128(rss, (wn * Cfg::WTN + j * 16 + r16) * mx_srow + t * 16, 0, 0);
+      // landed here, once per 8 stages: a load still pending at the loop head would make the compiler
+      // wait vmcnt(0) before every stage's first scale use (it does not see the loops' counted waits)
+#pragma unroll
+      for (int j = 0; j < FN; ++j) asm volatile("" : "+v"(mxq[j]));
+#pragma unroll
+      for (int j = 0; j < FN; ++j) {  // device byte 4 d + b = block 4 b + d  ->  dword b = blocks 4 b .. 4 b + 3
+        const uint32_t t0 = wo_perm(mxq[j][1], mxq[j][0], 0x05010400u), t1 = wo_perm(mxq[j][1], mxq[j][0], 0x07030602u);
+        const uint32_t t2 = wo_perm(mxq[j][3], mxq[j][2], 0x05010400u), t3 = wo_perm(mxq[j][3], mxq[j][2], 0x07030602u);
+        mxq[j] = v4u{wo_perm(t2, t0, 0x05040100u), wo_perm(t2, t0, 0x07060302u), wo_perm(t3, t1, 0x05040100u),
+                     wo_perm(t3, t1, 0x07060302u)};
+      }
+    }
+  };
+  [[maybe_unused]] auto mx_shift = [&]() {  // the next stage pair moves to dword 0
+#pragma unroll
+    for (int j = 0; j < MXN; ++j) mxq[j] = v4u{mxq[j][1], mxq[j][2], mxq[j][3], mxq[j][3]};
+  };
+  // f32 bits (byte << 23) of column j's scale for K half kc of stage mx_s
+  [[maybe_unused]] auto mx_scale = [&](int j, int kc) -> uint32_t {
+    return __builtin_amdgcn_ubfe(mxq[j][0], (uint32_t)((mx_s & 1) * 16 + kc * 8), 8u) << 23;
+  };
+  [[maybe_unused]] auto mx_next = [&]() {  // the stage's dequant is done
+    if constexpr (MX) {
+      ++mx_s;
+      if ((mx_s & 1) == 0) {
+        if ((mx_s & 7) != 0) mx_shift();
+        else if (mx_s < ks0 + nst) mx_load(mx_s >> 3);
+      }
+    }
+  };
+  if constexpr (MX) {
+    if (nst > 0) {
+      mx_load(ks0 >> 3);
+      for (int p = (ks0 & 7) >> 1; p > 0; --p) mx_shift();
+    }
+  }
 
   v4f acc[FM][FN];
 #pragma unroll
@@ -2514,7 +2597,13 @@ __device__ __forceinline__ void gg_tile_wo(const GGMeta& mt, const uint8_t* __re
 #pragma unroll
       for (int j = 0; j < FN; ++j) raw[j][0] = *reinterpret_cast<const uint32_t*>(Bs + j * 16 * RB + g * 4);
     }
-    if constexpr (BITS == 4) {
+    if constexpr (BITS == 4 && MX) {  // canonical order: K half kc is chunk kc, lane group g its dword g
+#pragma unroll
+      for (int j = 0; j < FN; ++j) {
+        raw[j][0] = *reinterpret_cast<const uint32_t*>(Bs + j * 16 * RB + ((0 ^ bsw) << 4) + g * 4);
+        raw[j][1] = *reinterpret_cast<const uint32_t*>(Bs + j * 16 * RB + ((1 ^ bsw) << 4) + g * 4);
+      }
+    } else if constexpr (BITS == 4) {
 #pragma unroll
       for (int j = 0; j < FN; ++j) {
         const uint2 v = *reinterpret_cast<const uint2*>(Bs + j * 16 * RB + (((g >> 1) ^ bsw) << 4) + (g & 1) * 8);
@@ -2528,7 +2617,9 @@ __device__ __forceinline__ void gg_tile_wo(const GGMeta& mt, const uint8_t* __re
       v8h b[FN];
 #pragma unroll
       for (int j = 0; j < FN; ++j) {
-        if constexpr (BITS == 2) {
+        if constexpr (MX) {
+          b[j] = wo_dequant_mx(raw[j][kc], mx_scale(j, kc));
+        } else if constexpr (BITS == 2) {
           const uint32_t w = raw[j][0] >> (8 * kc);
           b[j] = wo_dequant<2>(&w, moff2, s2[j], z2[j], wok);
         } else if constexpr (BITS == 4) {
@@ -2553,6 +2644,7 @@ __device__ __forceinline__ void gg_tile_wo(const GGMeta& mt, const uint8_t* __re
         for (int j = 0; j < FN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(b[j], a, acc[i][j], 0, 0, 0);
       }
     }
+    mx_next();
   };
 
   // wait until stage t's LDS-DMA (this wave's) has landed, `later` stages having been issued after it
@@ -2583,6 +2675,9 @@ __device__ __forceinline__ void gg_tile_wo(const GGMeta& mt, const uint8_t* __re
     for (int j = 0; j < FN; ++j) {
       if constexpr (BITS == 2) {
         f.rb[j][0][0] = *reinterpret_cast<const uint32_t*>(Bs + j * 16 * RB + g * 4);
+      } else if constexpr (MX) {
+        f.rb[j][0][0] = *reinterpret_cast<const uint32_t*>(Bs + j * 16 * RB + ((0 ^ bsw) << 4) + g * 4);
+        f.rb[j][0][1] = *reinterpret_cast<const uint32_t*>(Bs + j * 16 * RB + ((1 ^ bsw) << 4) + g * 4);
       } else if constexpr (BITS == 4) {
         const uint2 v = *reinterpret_cast<const uint2*>(Bs + j * 16 * RB + (((g >> 1) ^ bsw) << 4) + (g & 1) * 8);
         f.rb[j][0][0] = v.x;
@@ -2606,7 +2701,9 @@ __device__ __forceinline__ void gg_tile_wo(const GGMeta& mt, const uint8_t* __re
   auto dq_half = [&](const Frag& f, int kc, v8h (&b)[FN]) {
 #pragma unroll
     for (int j = 0; j < FN; ++j) {
-      if constexpr (BITS == 2) {
+      if constexpr (MX) {
+        b[j] = wo_dequant_mx(f.rb[j][0][kc], mx_scale(j, kc));
+      } else if constexpr (BITS == 2) {
         const uint32_t w = f.rb[j][0][0] >> (8 * kc);
         b[j] = wo_dequant<2>(&w, moff2, s2[j], z2[j], wok);
       } else if constexpr (BITS == 4) {
@@ -2615,6 +2712,7 @@ __device__ __forceinline__ void gg_tile_wo(const GGMeta& mt, const uint8_t* __re
         b[j] = wo_dequant<8>(f.rb[j][kc], moff2, s2[j], z2[j], wok);
       }
     }
+    if (kc == 1) mx_next();  // (both K halves of a stage are dequantised in order, kc = 1 last)
   };
   auto mm_half = [&](const v8h (&a)[FM], const v8h (&b)[FN]) {
 #pragma unroll
@@ -2720,7 +2818,7 @@ __device__ __forceinline__ void gg_tile_wo(const GGMeta& mt, const uint8_t* __re
     load_scales(ks0 / gstages, s2, z2);
     bool one_group = false;
     if constexpr ((WABL & WO_PCH) != 0 && (WABL & WO_SPLIT) != 0 && (WABL & WO_ADEAD) == 0)
-      one_group = (ks0 % gstages) + nst <= gstages;
+      one_group = MX || (ks0 % gstages) + nst <= gstages;
     if constexpr ((WABL & WO_PCH) != 0 && (WABL & WO_SPLIT) != 0 && (WABL & WO_ADEAD) == 0) {
      if (one_group) {
       // WO_PCH: no scale slots, no group counters; the steady loop unrolled by NBUF (ring buffer
@@ -2753,7 +2851,9 @@ __device__ __forceinline__ void gg_tile_wo(const GGMeta& mt, const uint8_t* __re
     // stage opens a group (scale slot DMA before the stage's own pieces, as below; slot read after
     // the barrier) — no group counters
     // (not for 2-bit codes: their 4-deep ring unrolled 4x spilled the 3-WG/CU build)
-    constexpr bool kTwo = (WABL & WO_PCH) != 0 && (WABL & WO_SPLIT) != 0 && (WABL & WO_ADEAD) == 0 && BITS != 2;
+    // (MXFP4: block scales travel apart from the groups — always one group, the loops below compiled out)
+    constexpr bool kMxOne = MX && (WABL & WO_PCH) != 0 && (WABL & WO_SPLIT) != 0 && (WABL & WO_ADEAD) == 0;
+    constexpr bool kTwo = (WABL & WO_PCH) != 0 && (WABL & WO_SPLIT) != 0 && (WABL & WO_ADEAD) == 0 && BITS != 2 && !MX;
     bool two_group = false;
     if constexpr (kTwo) two_group = !one_group && gstages == 2 && (ks0 & 1) == 0;
     if constexpr (kTwo) {
@@ -2815,6 +2915,7 @@ __device__ __forceinline__ void gg_tile_wo(const GGMeta& mt, const uint8_t* __re
       }
      }
     }
+    if constexpr (!kMxOne) {
     if (!one_group && !two_group) {
     const int nl = min(ncol0 + (lane & 31), N - 1);
     int ipos = ks0 % gstages, igrp = ks0 / gstages;  // issue stream: stage t's place in its group
@@ -2895,6 +2996,7 @@ __device__ __forceinline__ void gg_tile_wo(const GGMeta& mt, const uint8_t* __re
       for (int s = 0; s < nst; ++s) step(s, std::true_type());
     }
     }  // (!one_group)
+    }
     wait_vmcnt<0>();
     lds_barrier();  // ring -> epilogue staging
   } else if (nst > 0) {
@@ -2996,6 +3098,11 @@ __global__ __launch_bounds__(512, 2) void gg_v2_kernel(GGArgs args) {
     if (cls == 0) gg_tile_wo<WoCfg<256>, 2, WP>(mt, A, B, SB, C, td.m0, td.n0, lds, sk);
     else if (cls == 1) gg_tile_wo<WoCfg<128, 1>, 2, WP>(mt, A, B, SB, C, td.m0, td.n0, lds, sk);
     else gg_tile_wo<WoCfg<64, 1>, 2, WP>(mt, A, B, SB, C, td.m0, td.n0, lds, sk);
+  } else if ((QM & (1 << QT_MXF4W)) && mt.qtype == QT_MXF4W) {
+    constexpr int WP = ABL & (WO_PIPE | WO_STAG);
+    if (cls == 0) gg_tile_wo<WoCfg<256>, 4, WP, WO_FMT_MX>(mt, A, B, SB, C, td.m0, td.n0, lds, sk);
+    else if (cls == 1) gg_tile_wo<WoCfg<128, 1>, 4, WP, WO_FMT_MX>(mt, A, B, SB, C, td.m0, td.n0, lds, sk);
+    else gg_tile_wo<WoCfg<64, 1>, 4, WP, WO_FMT_MX>(mt, A, B, SB, C, td.m0, td.n0, lds, sk);
   } else if ((QM & (1 << QT_MXF4)) && mt.qtype == QT_MXF4) {
     // as E4M3: K = 128 MFMAs on whole 16-B chunks, no K halves to stagger -> the plain v2 mainloop
     constexpr int MXABL = ABL & ~(V2_STAGGER | V2_B3);
@@ -3065,6 +3172,7 @@ __global__ __launch_bounds__(512, 2 * NWG) void gg_wo2_kernel(GGArgs args) {
   } else if ((QM & (1 << QT_W4A16)) && mt.qtype == QT_W4A16) gg_tile_wo<Cfg, 4, WP>(mt, A, B, SB, C, td.m0, td.n0, lds, sk);
   else if ((QM & (1 << QT_W8A16)) && mt.qtype == QT_W8A16) gg_tile_wo<Cfg, 8, WP>(mt, A, B, SB, C, td.m0, td.n0, lds, sk);
   else if ((QM & (1 << QT_W2A16)) && mt.qtype == QT_W2A16) gg_tile_wo<Cfg, 2, WP>(mt, A, B, SB, C, td.m0, td.n0, lds, sk);
+  else if ((QM & (1 << QT_MXF4W)) && mt.qtype == QT_MXF4W) gg_tile_wo<Cfg, 4, WP, WO_FMT_MX>(mt, A, B, SB, C, td.m0, td.n0, lds, sk);
   if constexpr ((ABL & V2_TRACE) != 0) {  // (as gg_v2_kernel; the class field holds the problem index)
     if (threadIdx.x == 0 && blockIdx.x < kTraceBlocks) {
       wait_vmcnt<0>();

@@ -36,7 +36,8 @@ class QParams:
     "bf16" (16-bit bfloat16 operands) or "F6" (w4a4_g-1_sym with A and B as fp6 images of the int4
     codes, ``_native.pack_f6``: same results on the fp6 MFMA — lab library only, measured slower
     than the int4 path) or "MXFP4" (w4a4_g32_sym_MXFP4: OCP e2m1 codes with one e8m0
-    scale per 32-K block, ``quantize.quant_mxfp4`` / ``pack_mxfp4_scales``). The reference's ``_accfp16`` strategies (fp16 MMA with an fp16
+    scale per 32-K block, ``quantize.quant_mxfp4`` / ``pack_mxfp4_scales``; with ``a_bits = 16``
+    w4a16_g32_sym_MXFP4, fp16 activations on the same B codes and scales). The reference's ``_accfp16`` strategies (fp16 MMA with an fp16
     accumulator, tile_config.py:94-97) run as their f32-accumulating base type: MFMA has no fp16
     accumulator, and the f32 sum is the more accurate result of the same products."""
 
@@ -98,6 +99,8 @@ W8A8_E4M3 = QParams(8, 8, -1, True, "E4M3")  # w8a8_g-1_sym_E4M3: OCP fp8 operan
 W4A4 = QParams(4, 4, -1, True)
 W4A4_F6 = QParams(4, 4, -1, True, "F6")  # w4a4_g-1_sym on fp6 images (lab library: nat.pack_f6 of A and B)
 W4A4_MXFP4 = QParams(4, 4, 32, True, "MXFP4")  # w4a4_g32_sym_MXFP4: e2m1 codes, e8m0 block scales (include/mxmoe_gg.h)
+# w4a16_g32_sym_MXFP4: fp16 activations on the same MXFP4 weight tensors (weight-only: the small-batch form)
+W4A16_MXFP4 = QParams(16, 4, 32, True, "MXFP4")
 W4A4_G128 = QParams(4, 4, 128, True)  # w4a4_g128_sym: one scale per 128-K group (cta_gemm.cuh:610-772)
 # weight-only (any group size that is -1 or a multiple of 64 dividing K, sym or asym, 2 / 4 / 8 bits)
 W4A16_G128_ASYM = QParams(16, 4, 128, False)
@@ -106,7 +109,7 @@ W4A16_G128_SYM = QParams(16, 4, 128, True)
 W8A16_ASYM = QParams(16, 8, -1, False)
 W2A16_G128_ASYM = QParams(16, 2, 128, False)
 
-SUPPORTED = {q.qcfg: q for q in (FP16, BF16, W8A8, W8A8_E4M3, W4A4, W4A4_MXFP4, W4A4_G128, W4A16_G128_ASYM, W4A16_ASYM, W4A16_G128_SYM, W8A16_ASYM,
+SUPPORTED = {q.qcfg: q for q in (FP16, BF16, W8A8, W8A8_E4M3, W4A4, W4A4_MXFP4, W4A16_MXFP4, W4A4_G128, W4A16_G128_ASYM, W4A16_ASYM, W4A16_G128_SYM, W8A16_ASYM,
                                   QParams(16, 4, -1, True), QParams(16, 8, -1, True), QParams(16, 8, 128, True),
                                   QParams(16, 8, 128, False), W2A16_G128_ASYM, QParams(16, 2, -1, False),
                                   QParams(16, 2, -1, True), QParams(16, 2, 128, True))}
@@ -156,7 +159,12 @@ class Problem:
             need(self.A, (torch.float16,) if self.q.is_weight_only else codes, "A")
             need(self.B, codes, "B (packed codes)")
         need(self.C, (torch.float16,), "C")
-        if self.q.fmt == "MXFP4":
+        if self.q.fmt == "MXFP4" and self.q.is_weight_only:  # fp16 A (checked above), no scale_a
+            if self.K % 64:
+                raise ValueError(f"{self.q.qcfg}: K={self.K} must be a multiple of the 64-element weight-only stage")
+            need(self.B, (torch.uint8,), "B (e2m1 codes)")
+            need(self.scale_b, (torch.uint8,), "scale_b (e8m0, pack_mxfp4_scales)")
+        elif self.q.fmt == "MXFP4":
             if self.K % 32:
                 raise ValueError(f"{self.q.qcfg}: K={self.K} must be a multiple of the 32-element MX block")
             need(self.A, (torch.uint8,), "A (e2m1 codes)")

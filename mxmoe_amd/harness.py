@@ -43,7 +43,9 @@ class LayerInputs:
             ab = 16 if plain else s.a_bits
             wb = 16 if plain else s.w_bits
             tot += (s.M * s.K * ab + s.N * s.K * wb) // 8 + 2 * s.M * s.N
-            if not plain and ab == 16:  # weight-only: scale (+ zp) per column and group
+            if s.fmt == "MXFP4" and ab == 16:  # weight-only MXFP4: one e8m0 byte per 32-K block of B
+                tot += s.N * (s.K // 32)
+            elif not plain and ab == 16:  # weight-only: scale (+ zp) per column and group
                 tot += 2 * s.N * (1 if s.gsize == -1 else s.K // s.gsize) * (1 if s.sym else 2)
             elif s.fmt == "MXFP4":  # one e8m0 byte per 32-K block
                 tot += (s.M + s.N) * (s.K // 32)
@@ -69,6 +71,9 @@ def build_layer_inputs(shapes: Sequence[QShape], device="cuda", seed: int = 42,
             qb, sb = quant_e4m3(b)
             probs.append(Problem(A=pack_e4m3(qa), B=pack_e4m3(qb), C=C, M=M, N=N, K=K, q=q, scale_a=sa, scale_b=sb))
             del qa, qb
+        elif q.fmt == "MXFP4" and q.is_weight_only:
+            qb, sb = quant_mxfp4(b)
+            probs.append(Problem(A=a, B=qb, C=C, M=M, N=N, K=K, q=q, scale_b=pack_mxfp4_scales(sb)))
         elif q.fmt == "MXFP4":
             (qa, sa), (qb, sb) = quant_mxfp4(a), quant_mxfp4(b)
             probs.append(Problem(A=qa, B=qb, C=C, M=M, N=N, K=K, q=q, scale_a=pack_mxfp4_scales(sa),
@@ -195,6 +200,8 @@ def slice_scale_b(p: Problem, n0: int, n1: int) -> Optional[torch.Tensor]:
     if p.scale_b is None:
         return None
     q = p.q
+    if q.fmt == "MXFP4":  # [N][16 ceil(K/32 / 16)] e8m0 rows
+        return p.scale_b[n0:n1]
     G = 1 if q.gsize == -1 else p.K // q.gsize
     if G == 1 and not (q.is_weight_only and not q.sym):
         return p.scale_b[n0:n1]

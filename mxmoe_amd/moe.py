@@ -469,8 +469,9 @@ def gg_mxmoe_share_fused(inp: Sequence[torch.Tensor], experts: Sequence[torch.Te
         if pi >= len(inp):
             raise ValueError(f"gg_mxmoe_share_fused: {len(inp)} inputs for more non-empty experts")
         a_bits, w_bits, gsize, sym = (int(x) for x in qparams_per_exp[e])
-        # (4, 4, 32, 1) is w4a4_g32_sym_MXFP4: the only g32 type, so the tuple needs no format field
-        q = QParams(a_bits, w_bits, gsize, bool(sym), "MXFP4" if (a_bits, w_bits, gsize) == (4, 4, 32) else "")
+        # (4, 4, 32, 1) is w4a4_g32_sym_MXFP4 and (16, 4, 32, 1) w4a16_g32_sym_MXFP4: the only g32 types, so
+        # the tuple needs no format field
+        q = QParams(a_bits, w_bits, gsize, bool(sym), "MXFP4" if (w_bits, gsize) == (4, 32) and a_bits in (4, 16) else "")
         n, k = (shared_N, shared_K) if e == E else (N, K)
 
         def opt(t):
@@ -544,12 +545,12 @@ def prepare_weight(w: torch.Tensor, q: QParams, interleave: bool = False) -> Exp
         w = interleave_gate_up(w)[0]  # (per-row quantisation commutes with the row order)
     if not q.is_quant:
         return ExpertWeights(w.contiguous(), None, q, N, K)
+    if q.fmt == "MXFP4":  # w4a4 and w4a16 alike: canonical codes + device-layout scales, no repack
+        codes, sc = quant_mxfp4(w)
+        return ExpertWeights(codes, pack_mxfp4_scales(sc), q, N, K)
     if q.is_weight_only:
         codes, sz = quant_weightonly(w, q.w_bits, q.gsize, q.sym)
         return ExpertWeights(pack_weightonly_mi355x(codes, q.w_bits), sz, q, N, K)
-    if q.fmt == "MXFP4":
-        codes, sc = quant_mxfp4(w)
-        return ExpertWeights(codes, pack_mxfp4_scales(sc), q, N, K)
     qw, sw = quant_rtn_sym(w, q.w_bits, q.gsize)
     return ExpertWeights(pack_wxax(qw, q.w_bits), sw, q, N, K)
 
@@ -592,6 +593,27 @@ class MoEFFN:
         self.tag1 = [qtag_of(q[0].a_bits, q[0].gsize) for q in qcfg]
         self.tag2 = [qtag_of(q[1].a_bits, q[1].gsize) for q in qcfg]
         self.gate_up_mode: Optional[str] = None  # None: the library decides; "interleaved": A/B override
+
+    def a16_view(self) -> "MoEFFN":
+        """This layer (every qcfg w4a4_g32_sym_MXFP4) with fp16 activations: a layer whose qcfgs are
+        w4a16_g32_sym_MXFP4 on the SAME weight tensors — the two types share the B codes and scales
+        byte for byte, so nothing is requantised or copied. Plain gate_up layout (no SiLU epilogue),
+        as the w4a4 layer's. The form for decode-size batches (the small-batch kernel) and where
+        4-bit activations cost accuracy."""
+        from .groupgemm import W4A16_MXFP4
+
+        if any(q.qcfg != "w4a4_g32_sym_MXFP4" for pair in self.qcfg for q in pair):
+            raise ValueError("a16_view needs every qcfg of the layer to be w4a4_g32_sym_MXFP4")
+        v = object.__new__(MoEFFN)
+        v.E, v.has_shared, v.H, v.N, v.Ns = self.E, self.has_shared, self.H, self.N, self.Ns
+        v.qcfg = [(W4A16_MXFP4, W4A16_MXFP4) for _ in self.qcfg]
+        v.fuse_silu = False
+        v.w1 = [dataclasses.replace(w, q=W4A16_MXFP4) for w in self.w1]
+        v.w2 = [dataclasses.replace(w, q=W4A16_MXFP4) for w in self.w2]
+        v.tag1 = [ACT_FP16] * len(self.qcfg)
+        v.tag2 = [ACT_FP16] * len(self.qcfg)
+        v.gate_up_mode = None
+        return v
 
     def gate_up_call(self, a1: ActBatch, T: int, topk: int, dev):
         """The planned gate_up GroupGEMM of one call and its output buffers: (GroupGemm, h1, h1s, mode),

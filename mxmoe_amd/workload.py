@@ -90,7 +90,7 @@ class QShape:
 
 def parse_qstr(qstr: str) -> dict:
     """gen_workload.py:51-57; also the SUPPORTED_QCFG forms that reference parser cannot read
-    (``bf16``, ``fp16[_accfp16]``, ``..._E4M3``, ``w4a4_g32_sym_MXFP4``; ``_accfp16`` runs as its f32-accumulating base)."""
+    (``bf16``, ``fp16[_accfp16]``, ``..._E4M3``, ``w4a4_g32_sym_MXFP4``, ``w4a16_g32_sym_MXFP4``; ``_accfp16`` runs as its f32-accumulating base)."""
     if qstr in ("fp16", "fp16_accfp16", "bf16"):
         d = dict(FP16_QCFG)
         if qstr == "bf16":

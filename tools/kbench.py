@@ -66,6 +66,7 @@ def main():
           "w4a4g128": dict(qstr="w4a4_g128_sym"), "w2a16": dict(qstr="w2a16_g128_asym"),
           "e4m3": dict(qstr="w8a8_g-1_sym_E4M3"), "bf16": dict(qstr="bf16"), "ds2_mixed": {},
           "mxfp4": dict(qstr="w4a4_g32_sym_MXFP4"),
+          "mxfp4a16": dict(qstr="w4a16_g32_sym_MXFP4"),
           "w4a16_w8a8": {}}[args.cfg]
     if args.cfg == "w4a16_w8a8":  # bench config w4a16_w8a8_bs512's scheme (w4a16 + 1/16 w8a8)
         from mxmoe_amd.workload import w4a16_w8a8_qconfig
