@@ -63,8 +63,10 @@ enum {
   MXMOE_GG_FMT_E4M3 = 1,    /* w8a8_g-1_sym_E4M3: OCP fp8 e4m3 codes                         */
   MXMOE_GG_FMT_BF16 = 2,    /* bf16: 16-bit operands are bfloat16                              */
   /* 3: fp6 images of int4 codes (tools-only lab library) */
-  MXMOE_GG_FMT_MXFP4 = 4    /* w4a4_g32_sym_MXFP4 and w4a16_g32_sym_MXFP4: OCP MXFP4, e2m1 codes + e8m0
+  MXMOE_GG_FMT_MXFP4 = 4,   /* w4a4_g32_sym_MXFP4 and w4a16_g32_sym_MXFP4: OCP MXFP4, e2m1 codes + e8m0
                              * block scales (a_bits selects: 4 = both operands, 16 = fp16 A, weights only) */
+  MXMOE_GG_FMT_MXFP8 = 5    /* w4a8_g32_sym_MXFP8: OCP MXFP8 (e4m3) activations on MXFP4 weights; w_bits = 8
+                             * under this format is reserved (a later w8a8_g32_sym_MXFP8) and UNSUPPORTED */
 };
 
 /* MXFP4 operands (fmt MXMOE_GG_FMT_MXFP4; a_bits = w_bits = 4, gsize = 32, sym; K % 32 == 0).
@@ -107,8 +109,26 @@ enum {
  *            a call that also holds a w4a4_g32_sym_MXFP4 problem stays on v2x. MXMOE_GG_EPI_SILU_MUL: on wo3
  *            only, as for the other weight-only types (scale_b rows permuted with the B rows). */
 
-/* Epilogue flag, OR-ed into mxmoe_gg_problem.fmt (fp16, w8a8_g-1_sym and w4a4_g-1_sym problems on the
- * v2x, v3 and wo3 variants; weight-only WxA16 problems on wo3, whose scale_b is permuted with the rows;
+/* MXFP8 activations on MXFP4 weights (fmt MXMOE_GG_FMT_MXFP8 with a_bits = 8, w_bits = 4, gsize = 32, sym:
+ * w4a8_g32_sym_MXFP8; plan-info qtype_mask bit 12). One block-scaled MFMA with a format per operand
+ * (e4m3 x e2m1), no dequantisation.
+ *   A      : uint8 [M][K] OCP e4m3 codes (torch.float8_e4m3fn's bit patterns) in logical K order, lda in 16-bit
+ *            words; scale_a one e8m0 byte per 32 elements in the DEVICE layout above ([M][16 ceil(K/32 / 16)],
+ *            4-byte aligned, pads 127) — the layout is indexed by (K = 128 MFMA, K group of 32), which means the
+ *            same for an 8-bit operand.
+ *   B      : uint8 [N][K/2] canonical e2m1 codes and scale_b in the device layout: byte for byte the B operand
+ *            of a w4a4_g32_sym_MXFP4 problem (no repack, no second layout).
+ *   limits : K % 32 == 0, N % 8 == 0; alignment as for w4a4_g32_sym_MXFP4.
+ *   result : C[m][n] = fp16_rn(sum over blocks b of 2^(sa[m][b]-127) 2^(sb[n][b]-127) sum_{k in b} e4m3(a[m][k])
+ *            e2m1(b[n][k])), accumulated in f32 by the block-scaled MFMA (summation order unspecified); no
+ *            per-channel fp16 scales. A scale byte 255 is NaN and poisons its output row / column only.
+ *   runs on: v2x (256 / 128-row tiles, ring of K = 128 stages) and the small-batch kernel wo3 (64 x 128 tiles;
+ *            AUTO picks it below a weighted mean M of its own); a call that also holds a
+ *            w4a4_g32_sym_MXFP4 problem stays on v2x. MXMOE_GG_EPI_SILU_MUL is accepted on both (the fp16
+ *            body's epilogue path: f32 accumulators rounded to fp16, then the SiLU arithmetic below). */
+
+/* Epilogue flag, OR-ed into mxmoe_gg_problem.fmt (fp16, w8a8_g-1_sym, w4a4_g-1_sym and w4a8_g32_sym_MXFP8
+ * problems on the v2x, v3 (not the MX type) and wo3 variants; weight-only WxA16 problems on wo3, whose scale_b is permuted with the rows;
  * no reference counterpart — it fuses the MoE layer's silu_mul_then_quant
  * activation, ref_bind.cu:595-757, into the gate_up GroupGEMM). B holds N = 2 Nh rows interleaved
  * in 16-row blocks: rows [32 b, 32 b + 16) are gate rows [16 b, 16 b + 16) and rows
@@ -159,7 +179,8 @@ typedef struct mxmoe_gg_plan_info {
   int32_t block;
   int32_t lds_bytes;
   int32_t qtype_mask;      /* bit q set if a planned problem has quant type q (0 fp16, 1 w8a8, 2 w4a4,
-                            * 3 w4a16, 4 w8a16, 5 w4a4_g128, 6 w2a16, 7 w8a8 E4M3, 8 bf16, 10 MXFP4, 11 weight-only MXFP4); bit 16:
+                            * 3 w4a16, 4 w8a16, 5 w4a4_g128, 6 w2a16, 7 w8a8 E4M3, 8 bf16, 10 MXFP4, 11 weight-only MXFP4,
+                            * 12 w4a8 MXFP8); bit 16:
                             * a weight-only problem carries MXMOE_GG_EPI_SILU_MUL (small-batch kernel);
                             * selects the kernel specialisation at launch */
   int32_t splitk_slabs;    /* 256-KiB partial-sum slabs the plan's split-K tiles use (0: no split) */

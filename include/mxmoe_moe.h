@@ -35,10 +35,19 @@ enum {
   MXMOE_ACT_INT8 = 1,    /* a_bits 8, one scale per token                                 */
   MXMOE_ACT_INT4 = 2,    /* a_bits 4, one scale per token                                 */
   MXMOE_ACT_INT4_G128 = 3, /* a_bits 4, one scale per (token, 128-element group)          */
-  MXMOE_ACT_MXFP4 = 4    /* OCP MXFP4 (w4a4_g32_sym_MXFP4): e2m1 codes, one e8m0 scale per (token,
+  MXMOE_ACT_MXFP4 = 4,   /* OCP MXFP4 (w4a4_g32_sym_MXFP4): e2m1 codes, one e8m0 scale per (token,
                           * 32-element block), quantised as include/mxmoe_gg.h defines; codes in the
                           * canonical nibble order, scale bytes in the GroupGEMM's device layout;
                           * through mxmoe_moe_act_quant with bit 4 of tag_mask only               */
+  /* 5 is NOT assigned: a tag_mask with bit 5 stays "unknown activation tag" */
+  MXMOE_ACT_MXFP8 = 6    /* OCP MXFP8, e4m3 elements (w4a8_g32_sym_MXFP8): one code byte per element
+                          * (torch.float8_e4m3fn's bit patterns), one e8m0 scale per (token, 32-element
+                          * block) in the device layout, as MXFP4's. Per block: e = floor(log2 amax) - 8
+                          * clamped to [-127, 127], scale code e + 127; an all-zero block: scale code 0
+                          * and zero codes; a block holding Inf or NaN: scale 255 and zero codes; each
+                          * element is multiplied by 2^-e exactly, saturated at +-448 and rounded to
+                          * e4m3 once, to nearest even (-0 keeps its sign). quantize.quant_mxfp8 is
+                          * the same rule. Through mxmoe_moe_act_quant with bit 6 of tag_mask only  */
 };
 
 /* One expert's segment of a permuted activation buffer. Slots (rows of the permuted batch) are
@@ -51,7 +60,7 @@ typedef struct mxmoe_moe_seg {
   int32_t width;       /* elements per row of this segment's output (K of the next GEMM)      */
   int64_t out_off;     /* byte offset of the segment's [rows][width * bits / 8] block in `out` */
   int64_t scale_off;   /* fp16-element offset of its scales: [rows] or [width/128][rows];
-                        * MXFP4: of its [rows][16 ceil(width/32 / 16)] e8m0 bytes (even offset: the
+                        * MXFP4 / MXFP8: of its [rows][16 ceil(width/32 / 16)] e8m0 bytes (even offset: the
                         * block is 4-byte aligned)                                              */
 } mxmoe_moe_seg;
 
@@ -170,8 +179,8 @@ int mxmoe_moe_quant_slots(const void* routed_in, const void* shared_in, int64_t 
  * carry: tag_mask bit t is set when some segment has qtag t. REQUIRED for segments tagged
  * MXMOE_ACT_MXFP4: the kernel builds with the MXFP4 code run only when bit 4 is set, so the four named
  * entry points (and any call here without the bit) keep the builds they had before the tag existed
- * and must not be given such a segment — they would treat it as int4. A mask with a bit above 4 is
- * MXMOE_GG_ERR_UNSUPPORTED.
+ * and must not be given such a segment — they would treat it as int4. MXMOE_ACT_MXFP8 segments
+ * likewise need bit 6. A mask with bit 5 or a bit above 6 is MXMOE_GG_ERR_UNSUPPORTED.
  *   mode 0: mxmoe_moe_quant_act      (routed_in = hidden [T][N], N = K; shared_in != NULL <=> with_shared,
  *                                     its value is ignored; perm_token required)
  *   mode 1: mxmoe_moe_silu_mul_quant, 2: mxmoe_moe_quant_slots, 3: mxmoe_moe_silu_mul_quant_il

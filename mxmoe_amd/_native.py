@@ -28,6 +28,7 @@ MXMOE_GG_ERR_HIP = 4
 # images, gg_f6.h) is understood by the lab library only (measured slower)
 FMT_DEFAULT, FMT_E4M3, FMT_BF16, FMT_F6 = 0, 1, 2, 3
 FMT_MXFP4 = 4  # MXMOE_GG_FMT_MXFP4: w4a4_g32_sym_MXFP4 (OCP e2m1 codes, e8m0 scale per 32-K block)
+FMT_MXFP8 = 5  # MXMOE_GG_FMT_MXFP8: w4a8_g32_sym_MXFP8 (OCP e4m3 activation codes on MXFP4 weights)
 EPI_SILU_MUL = 0x100  # MXMOE_GG_EPI_SILU_MUL: fmt flag, C = silu(gate) * up (include/mxmoe_gg.h)
 
 

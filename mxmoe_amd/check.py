@@ -15,6 +15,7 @@ depends only on A[rows] and B[cols]), for every quant type the library runs:
   * MXFP4 (w4a4_g32_sym_MXFP4): e2m1 codes and e8m0 block scales decoded (dequant_mxfp4), f64 GEMM —
     fp16 tolerance (f32 accumulation in the MFMA, order unspecified);
   * weight-only MXFP4 (w4a16_g32_sym_MXFP4): fp16 A, B decoded as above, f64 GEMM — fp16 tolerance;
+  * MXFP8 activations (w4a8_g32_sym_MXFP8): e4m3 A codes (dequant_mxfp8), B as MXFP4, f64 GEMM — fp16 tolerance;
   * fp16 / bf16: f64 GEMM — relative 1e-3 (north_star) with a cancellation floor.
 
 Unlike the reference's CHECK (abs tol 1.0 against an unquantised cutlass GEMM), integer paths must
@@ -25,7 +26,7 @@ from __future__ import annotations
 import numpy as np
 import torch
 
-from .quantize import dequant_mxfp4, dequant_weightonly, unpack_mxfp4_scales, unpack_wxax, unpack_weightonly_mi355x
+from .quantize import dequant_mxfp4, dequant_mxfp8, dequant_weightonly, unpack_mxfp4_scales, unpack_wxax, unpack_weightonly_mi355x
 
 
 def _f16_close(out: torch.Tensor, ref: torch.Tensor, what: str) -> None:
@@ -61,6 +62,10 @@ def expected_sample(p, rows: torch.Tensor, cols: torch.Tensor) -> tuple[torch.Te
             return dequant_mxfp4(codes, unpack_mxfp4_scales(scales, p.K))
         return deq(A, p.scale_a.index_select(0, rows).cpu()) @ \
             deq(p.B.index_select(0, cols).cpu(), p.scale_b.index_select(0, cols).cpu()).T, False
+    if q.fmt == "MXFP8":  # e4m3 A codes, e2m1 B codes, e8m0 scales in the device layout: f64 GEMM
+        Adq = dequant_mxfp8(A, unpack_mxfp4_scales(p.scale_a.index_select(0, rows).cpu(), p.K))
+        Bdq = dequant_mxfp4(p.B.index_select(0, cols).cpu(), unpack_mxfp4_scales(p.scale_b.index_select(0, cols).cpu(), p.K))
+        return Adq @ Bdq.T, False
     if q.is_fp8:
         def dec(t):
             return unpack_wxax(t, 8, p.K).view(torch.float8_e4m3fn).double()

@@ -136,9 +136,16 @@ void launch_v2(const GGArgs& a, int grid, int qmask, hipStream_t s) {
     // MXFP4 problems (plan-info bit 10, above the mask below): a kernel of their own, or every tile
     // body beside them — builds apart from the existing ones, which come out unchanged
     // (weight-only MXFP4, bit 11, likewise: alone, or the widest build with every body)
+    // (w4a8_g32_sym_MXFP8, bit 12: alone in a build of its own — a ring of three K = 128 stages in the
+    // variant's LDS image — or the every-body build with it)
+    if (qmask & (1 << QT_MXF8A)) {
+      if ((qmask & 8191) == (1 << QT_MXF8A)) launch_v2_q<ABL, (1 << QT_MXF8A)>(a, grid, s);
+      else launch_v2_q<0, 511 | (1 << QT_MXF4) | (1 << QT_MXF4W) | (1 << QT_MXF8A)>(a, grid, s);
+      return;
+    }
     if (qmask & ((1 << QT_MXF4) | (1 << QT_MXF4W))) {
-      if ((qmask & 4095) == (1 << QT_MXF4)) launch_v2_q<ABL, (1 << QT_MXF4)>(a, grid, s);
-      else if ((qmask & 4095) == (1 << QT_MXF4W)) launch_v2_q<ABL, (1 << QT_MXF4W)>(a, grid, s);
+      if ((qmask & 8191) == (1 << QT_MXF4)) launch_v2_q<ABL, (1 << QT_MXF4)>(a, grid, s);
+      else if ((qmask & 8191) == (1 << QT_MXF4W)) launch_v2_q<ABL, (1 << QT_MXF4W)>(a, grid, s);
       else if (!(qmask & (1 << QT_MXF4W))) launch_v2_q<0, 511 | (1 << QT_MXF4)>(a, grid, s);
       else launch_v2_q<0, 511 | (1 << QT_MXF4) | (1 << QT_MXF4W)>(a, grid, s);
       return;
@@ -232,9 +239,10 @@ void launch_wo2_q(const GGArgs& a, int grid, hipStream_t s) {
 // quant-type sets launched at the variant's NWG (the rest, with 8-bit weight-only problems, run the
 // 2-WG/CU build): keep in step with the switch below
 constexpr int kQmaskMxW = 1 << QT_MXF4W;  // weight-only MXFP4 (above the 9 bits the switches below see)
-constexpr int kWo2Types = 511 | kQmaskMxW;
+constexpr int kQmaskMx8 = 1 << QT_MXF8A;  // w4a8_g32_sym_MXFP8 (gg_tile_v2's 64 x 128 body)
+constexpr int kWo2Types = 511 | kQmaskMxW | kQmaskMx8;
 constexpr bool wo2_full_nwg(int qm) {
-  return qm == 8 || qm == 64 || qm == 10 || qm == 1 || qm == 2 || qm == 4 || qm == 6 || qm == kQmaskMxW;
+  return qm == 8 || qm == 64 || qm == 10 || qm == 1 || qm == 2 || qm == 4 || qm == 6 || qm == kQmaskMxW || qm == kQmaskMx8;
 }
 // plan-info qtype_mask bit: a weight-only problem carries MXMOE_GG_EPI_SILU_MUL (selects the WO_SILU
 // build; with it only the w4a16 and w4a16 + w8a8 sets run at the variant's NWG)
@@ -259,6 +267,10 @@ void launch_wo2(const GGArgs& a, int grid, int qmask, hipStream_t s) {
 #else
   if (qmask & kQmaskWoSilu) {  // weight-only problems with the fused SiLU epilogue (WO_SILU builds)
     constexpr int AS = ABL | WO_SILU;
+    if (qmask & kQmaskMx8) {  // (beside weight-only problems with the flag: the widest 2-WG/CU build)
+      launch_wo2_q<AS, 95 | kQmaskMxW | kQmaskMx8, 2>(a, grid, s);
+      return;
+    }
     if (qmask & kQmaskMxW) {  // weight-only MXFP4: alone at the variant's NWG, else the wide 2-WG/CU build
       if ((qmask & kWo2Types) == kQmaskMxW) launch_wo2_q<AS, kQmaskMxW, NWG>(a, grid, s);
       else launch_wo2_q<AS, 95 | kQmaskMxW, 2>(a, grid, s);
@@ -271,6 +283,11 @@ void launch_wo2(const GGArgs& a, int grid, int qmask, hipStream_t s) {
       case 16: launch_wo2_q<AS, 16, 2>(a, grid, s); break;
       default: launch_wo2_q<AS, 95, 2>(a, grid, s); break;
     }
+    return;
+  }
+  if (qmask & kQmaskMx8) {  // w4a8_g32_sym_MXFP8: alone at the variant's NWG, else the wide 2-WG/CU build
+    if ((qmask & kWo2Types) == kQmaskMx8) launch_wo2_q<ABL, kQmaskMx8, NWG>(a, grid, s);
+    else launch_wo2_q<ABL, 95 | kQmaskMxW | kQmaskMx8, 2>(a, grid, s);
     return;
   }
   if (qmask & kQmaskMxW) {
@@ -302,7 +319,7 @@ Variant make_v0(const char* name) {
   v.geom[QT_F16] = {C16::BM, C16::BN, C16::BKB, C16::kThreads};
   v.geom[QT_I8] = {C8::BM, C8::BN, C8::BKB, C8::kThreads};
   v.geom[QT_I4] = {C4::BM, C4::BN, C4::BKB, C4::kThreads};
-  for (int q : {QT_W4A16, QT_W8A16, QT_I4G, QT_W2A16, QT_F8, QT_BF16, QT_I4F6, QT_MXF4, QT_MXF4W}) v.geom[q] = {0, 0, 0, 0};  // v2 kernels only
+  for (int q : {QT_W4A16, QT_W8A16, QT_I4G, QT_W2A16, QT_F8, QT_BF16, QT_I4F6, QT_MXF4, QT_MXF4W, QT_MXF8A}) v.geom[q] = {0, 0, 0, 0};  // v2 kernels only
   v.threads = C16::kThreads;
   v.lds_bytes = FusedCfg<C16, C8, C4>::LDS_BYTES;
   v.chunk = FusedCfg<C16, C8, C4>::LDS_BYTES <= 80 * 1024 ? 64 : 32;  // workgroups per XCD at once
@@ -319,7 +336,7 @@ Variant make_v3(const char* name) {
   v.name = name;
   v.kind = Kind::V3;
   for (int q = 0; q < QT_COUNT; ++q) v.geom[q] = {256, BN, 64, CT::NT};  // (weight-only / g128 / fp8 / bf16 cleared below)
-  for (int q : {QT_W4A16, QT_W8A16, QT_I4G, QT_W2A16, QT_F8, QT_BF16, QT_I4F6, QT_MXF4, QT_MXF4W}) v.geom[q] = {0, 0, 0, 0};  // v2 kernels only
+  for (int q : {QT_W4A16, QT_W8A16, QT_I4G, QT_W2A16, QT_F8, QT_BF16, QT_I4F6, QT_MXF4, QT_MXF4W, QT_MXF8A}) v.geom[q] = {0, 0, 0, 0};  // v2 kernels only
   v.threads = CT::NT;
   v.lds_bytes = CT::LDS_BYTES;
   v.chunk = 32 * (160 * 1024 / CT::LDS_BYTES >= 2 ? 2 : 1);  // workgroups per XCD at once
@@ -371,6 +388,7 @@ Variant v2_base(const char* name, int lds_bytes) {
 #ifdef MXMOE_LAB
   v.geom[QT_MXF4] = {0, 0, 0, 0};         // (the lab library's launch tables carry no MXFP4 build)
   v.geom[QT_MXF4W] = {0, 0, 0, 0};
+  v.geom[QT_MXF8A] = {0, 0, 0, 0};
 #endif
   v.threads = 512;
   v.lds_bytes = lds_bytes;
@@ -402,6 +420,9 @@ Variant make_wo2(const char* name) {
   v.geom[QT_I8] = {64, 128, 128, 512};  // w8a8 (beside weight-only problems): 64 x 128 int8 tiles
   v.geom[QT_F16] = {64, 128, 128, 512};  // fp16: 64 x 128 tiles (64-K stages)
   v.geom[QT_I4] = {64, 128, 128, 512};   // w4a4: 64 x 128 tiles (256-K stages)
+#ifndef MXMOE_LAB
+  v.geom[QT_MXF8A] = {64, 128, 128, 512};  // w4a8_g32_sym_MXFP8: 64 x 128 tiles (128-K stages)
+#endif
   v.lds_bytes = wo2_lds_bytes<NWG>();
   v.chunk = 32 * NWG;  // NWG workgroups per CU, 32 CUs per XCD
   v.tail_bm = 0;
@@ -418,7 +439,7 @@ Variant make_wo2(const char* name) {
 template <int TRACE = 0>
 Variant make_v2p(const char* name) {
   Variant v = make_v2<V2_STAGGER | V2_B3 | V2_BUF | V2_EARLYDMA | (4 << V2_SPREAD_SHIFT)>(name);
-  v.geom[QT_MXF4] = v.geom[QT_MXF4W] = {0, 0, 0, 0};  // (no MXFP4 body in the persistent kernels)
+  v.geom[QT_MXF4] = v.geom[QT_MXF4W] = v.geom[QT_MXF8A] = {0, 0, 0, 0};  // (no MX body in the persistent kernels)
   v.persistent = true;
   v.lds_bytes = 160 * 1024;
   v.launch = &launch_v2p<TRACE>;
@@ -631,6 +652,8 @@ constexpr double kWoSmallMeanRows = 512.0;
 // / 1536 (int4), the general kernels beyond.
 constexpr double kSmallMeanRows = 80.0;
 constexpr double kSmallMeanRowsI4 = 112.0;
+// calls with a w4a8_g32_sym_MXFP8 problem (and no weight-only one): the int4 cut
+constexpr double kSmallMeanRowsMx8 = 112.0;
 constexpr double kSplitCUs = 256.0;  // MI355X compute units: the planner's notion of "one CU's share"
 
 int variant_index(const char* name) {
@@ -669,6 +692,14 @@ int qtype_of(int a_bits, int w_bits, int gsize, int sym, int fmt, int* qt) {
     return fail(MXMOE_GG_ERR_UNSUPPORTED,
                 "quant type not supported: w%da%d_g%d_%s_MXFP4 (only w4a4_g32_sym_MXFP4 and w4a16_g32_sym_MXFP4)",
                 w_bits, a_bits, gsize, sym ? "sym" : "asym");
+  }
+  if (fmt == MXMOE_GG_FMT_MXFP8) {  // OCP MXFP8 (e4m3) activations on MXFP4 weights
+    if (a_bits == 8 && w_bits == 4 && gsize == 32 && sym) {
+      *qt = QT_MXF8A;
+      return MXMOE_GG_OK;
+    }
+    return fail(MXMOE_GG_ERR_UNSUPPORTED, "quant type not supported: w%da%d_g%d_%s_MXFP8 (only w4a8_g32_sym_MXFP8)", w_bits,
+                a_bits, gsize, sym ? "sym" : "asym");
   }
 #ifdef MXMOE_LAB
   if (fmt == MXMOE_GG_FMT_F6) {  // w4a4_g-1_sym with fp6 images of the int4 codes (mxmoe_gg_pack_f6)
@@ -794,14 +825,16 @@ int build_meta(const HostProblem& p, int idx, const Variant& v, bool check_ptrs,
                 idx, v.name, p.w_bits, p.a_bits);
   const bool silu = (p.fmt & MXMOE_GG_EPI_SILU_MUL) != 0;
   if (p.fmt & ~(0xFF | MXMOE_GG_EPI_SILU_MUL)) return fail(MXMOE_GG_ERR_INVALID, "problem %d: unknown fmt flags %#x", idx, p.fmt);
-  if (silu && !(qt == QT_F16 || qt == QT_I8 || qt == QT_I4 || (is_weightonly(qt) && v.silu_wo)))
+  if (silu && !(qt == QT_F16 || qt == QT_I8 || qt == QT_I4 || qt == QT_MXF8A || (is_weightonly(qt) && v.silu_wo)))
     return fail(MXMOE_GG_ERR_UNSUPPORTED,
-                "problem %d: the SiLU epilogue needs fp16, w8a8_g-1_sym or w4a4_g-1_sym (weight-only: the small-batch "
-                "kernel wo3)", idx);
+                "problem %d: the SiLU epilogue needs fp16, w8a8_g-1_sym, w4a4_g-1_sym or w4a8_g32_sym_MXFP8 (weight-only: "
+                "the small-batch kernel wo3)", idx);
   if (silu && !has_silu_epilogue(v))
     return fail(MXMOE_GG_ERR_UNSUPPORTED, "problem %d: variant %s has no SiLU epilogue", idx, v.name);
   if (silu && p.N % 32) return fail(MXMOE_GG_ERR_INVALID, "problem %d: the SiLU epilogue needs N %% 32 == 0 (N=%d)", idx, p.N);
   if (is_weightonly(qt)) return build_meta_weightonly(p, idx, qt, v, check_ptrs, m);
+  if (qt == QT_MXF8A && p.K % 32)
+    return fail(MXMOE_GG_ERR_INVALID, "problem %d: w4a8_g32_sym_MXFP8 needs K %% 32 == 0 (K=%d)", idx, p.K);
   const int abits = is_float16(qt) ? 16 : p.a_bits;
   const int64_t kbits = (int64_t)p.K * abits;  // (fp6 images: K of the int4 codes they encode)
   if (kbits % 128 != 0)
@@ -812,7 +845,7 @@ int build_meta(const HostProblem& p, int idx, const Variant& v, bool check_ptrs,
                 idx, v.name, v.k_stage_bytes, p.K);
   if (qt == QT_I4G && p.K % 128 != 0)
     return fail(MXMOE_GG_ERR_INVALID, "problem %d: w4a4_g128 needs K %% 128 == 0 (K=%d)", idx, p.K);
-  if (qt != QT_F16 && qt != QT_BF16 && qt != QT_F8 && qt != QT_MXF4 && p.K > 131072)
+  if (qt != QT_F16 && qt != QT_BF16 && qt != QT_F8 && qt != QT_MXF4 && qt != QT_MXF8A && p.K > 131072)
     return fail(MXMOE_GG_ERR_INVALID, "problem %d: K=%d exceeds the exact int32 accumulation bound 131072", idx, p.K);
   if (p.N % 8 != 0) return fail(MXMOE_GG_ERR_INVALID, "problem %d: N=%d must be a multiple of 8", idx, p.N);
   // fp6 images: 96 B per K-128 block, K padded to whole blocks (mxmoe_gg_pack_f6)
@@ -821,11 +854,12 @@ int build_meta(const HostProblem& p, int idx, const Variant& v, bool check_ptrs,
 #else
   const int64_t kbytes = kbits / 8;
 #endif
+  const int64_t kbytes_b = qt == QT_MXF8A ? kbytes / 2 : kbytes;  // (w4a8 MXFP8: 4-bit B rows under 8-bit A rows)
   const int64_t lda_b = p.lda ? p.lda * 2 : kbytes;
-  const int64_t ldb_b = p.ldb ? p.ldb * 2 : kbytes;
+  const int64_t ldb_b = p.ldb ? p.ldb * 2 : kbytes_b;
   const int64_t ncols = silu ? p.N / 2 : p.N;  // columns of C
   const int64_t ldc = p.ldc ? p.ldc : ncols;
-  if (lda_b < kbytes || ldb_b < kbytes || (lda_b % 16) || (ldb_b % 16))
+  if (lda_b < kbytes || ldb_b < kbytes_b || (lda_b % 16) || (ldb_b % 16))
     return fail(MXMOE_GG_ERR_INVALID, "problem %d: lda/ldb must be >= K row and a multiple of 8 words", idx);
   // the buffer-form LDS-DMA addresses a 256-row tile with 32-bit offsets below 2^31
   if (lda_b >= (int64_t)1 << 23 || ldb_b >= (int64_t)1 << 23)
@@ -841,6 +875,8 @@ int build_meta(const HostProblem& p, int idx, const Variant& v, bool check_ptrs,
       return fail(MXMOE_GG_ERR_INVALID, "problem %d: scales must be 2-byte aligned", idx);
     if (qt == QT_MXF4 && (((uintptr_t)p.SA | (uintptr_t)p.SB) & 3))  // (the kernel reads scale dwords)
       return fail(MXMOE_GG_ERR_INVALID, "problem %d: MXFP4 scales must be 4-byte aligned", idx);
+    if (qt == QT_MXF8A && (((uintptr_t)p.SA | (uintptr_t)p.SB) & 3))
+      return fail(MXMOE_GG_ERR_INVALID, "problem %d: w4a8_g32_sym_MXFP8 scales must be 4-byte aligned", idx);
   }
   memset(m, 0, sizeof(*m));
   m->M = p.M;
@@ -969,7 +1005,7 @@ int plan_host(const std::vector<HostProblem>& probs, int variant, bool check_ptr
       equiv = 2.0 * rows * cols * 64 / 128;
     } else {
       const double kel = m.qtype == QT_I4F6 ? 128.0
-                       : g.bkb * 8.0 / (is_float16(m.qtype) ? 16 : (m.qtype == QT_I8 || m.qtype == QT_F8) ? 8 : 4);
+                       : g.bkb * 8.0 / (is_float16(m.qtype) ? 16 : (m.qtype == QT_I8 || m.qtype == QT_F8 || m.qtype == QT_MXF8A) ? 8 : 4);
       const double rate = is_float16(m.qtype) ? 128 : (m.qtype == QT_I4F6 || m.qtype == QT_MXF4) ? 512 : 256, fold = m.qtype == QT_I4G ? 1.25 : 1.0;
       bytes = (rows + cols) * g.bkb;
       equiv = 2.0 * rows * cols * kel / rate * fold;
@@ -1528,7 +1564,8 @@ int resolve_variant(int variant, const std::vector<HostProblem>& hp, int* out) {
   // (weight-only MXFP4 counts as weight-only; beside a w4a4 MXFP4 problem the call keeps v2x, the
   // only variant with that body)
   const int wo_mask = (1 << QT_W4A16) | (1 << QT_W8A16) | (1 << QT_W2A16) | (1 << QT_MXF4W);
-  const int small_mask = wo_mask | (1 << QT_I8) | (1 << QT_F16) | (1 << QT_I4);
+  // (w4a8_g32_sym_MXFP8 has a wo3 body; its row limit is kSmallMeanRowsMx8)
+  const int small_mask = wo_mask | (1 << QT_I8) | (1 << QT_F16) | (1 << QT_I4) | (1 << QT_MXF8A);
   // (fused SiLU calls too: the small-batch kernel's fp16 / w8a8 / w4a4 bodies carry the epilogue)
   if (mask != 0 && (mask & ~small_mask) == 0) {
     // (w8a8 / fp16 problems may ride along: the reference's small-batch w4a16 + w8a8 pairing)
@@ -1543,7 +1580,8 @@ int resolve_variant(int variant, const std::vector<HostProblem>& hp, int* out) {
     }
     const bool kskew = wsum0 > 0 && kmax >= 2.0 * ksum / wsum0;
     const double limit = (mask & wo_mask) ? kWoSmallMeanRows
-                                          : ((mask & (1 << QT_I4)) ? kSmallMeanRowsI4 : kSmallMeanRows) * (kskew ? 2.0 : 1.0);
+                                          : ((mask & (1 << QT_MXF8A)) ? kSmallMeanRowsMx8
+                                             : (mask & (1 << QT_I4)) ? kSmallMeanRowsI4 : kSmallMeanRows) * (kskew ? 2.0 : 1.0);
     // weight-only: the 3-WG/CU 64-row kernel while the rows per weight byte are few (small batches:
     // the 64-row tile is bound by its instruction stream and barriers, a second and third resident
     // workgroup fill each other's waits — +15-70 % on the qwen2_moe calls at bs 128-2048,
@@ -1665,8 +1703,8 @@ int mxmoe_gg_list_variants(char* buf, size_t n) {
   // weight-only kernels cover every group size / sym of a bit width: listed under the base name
   static const char* qnames[QT_COUNT] = {"fp16",          "w8a8_g-1_sym", "w4a4_g-1_sym",      "w4a16", "w8a16",
                                          "w4a4_g128_sym", "w2a16",        "w8a8_g-1_sym_E4M3", "bf16",  "w4a4_g-1_sym_F6",
-                                         "w4a4_g32_sym_MXFP4", "w4a16_g32_sym_MXFP4"};
-  static const int wbits[QT_COUNT] = {16, 8, 4, 4, 8, 4, 2, 8, 16, 6, 4, 4};
+                                         "w4a4_g32_sym_MXFP4", "w4a16_g32_sym_MXFP4", "w4a8_g32_sym_MXFP8"};
+  static const int wbits[QT_COUNT] = {16, 8, 4, 4, 8, 4, 2, 8, 16, 6, 4, 4, 8};  // (bits of a staged K byte row)
   std::string out;
   const auto& vs = variants();
   for (size_t i = 0; i < vs.size(); ++i) {

@@ -39,10 +39,12 @@ namespace mxmoe {
 // QT_MXF4: w4a4_g32_sym_MXFP4 (A and B OCP MXFP4: e2m1 codes, one e8m0 scale per 32-K block; the
 //          block-scaled fp4 MFMA applies the scales, f32 accumulate, C = fp16_rn(acc))
 // QT_MXF4W: w4a16_g32_sym_MXFP4 (fp16 A, B as QT_MXF4's B: weight-only, gg_tile_wo's WO_FMT_MX body)
+// QT_MXF8A: w4a8_g32_sym_MXFP8 (A OCP MXFP8: e4m3 codes + e8m0 block scales, B as QT_MXF4's B; the
+//           block-scaled MFMA with one format per operand, f32 accumulate, C = fp16_rn(acc))
 enum QType : int32_t {
   QT_F16 = 0, QT_I8 = 1, QT_I4 = 2, QT_W4A16 = 3, QT_W8A16 = 4, QT_I4G = 5, QT_W2A16 = 6, QT_F8 = 7, QT_BF16 = 8,
-  QT_I4F6 = 9, QT_MXF4 = 10, QT_MXF4W = 11,
-  QT_COUNT = 12
+  QT_I4F6 = 9, QT_MXF4 = 10, QT_MXF4W = 11, QT_MXF8A = 12,
+  QT_COUNT = 13
 };
 // quant types whose epilogue applies the per-channel scales sa[m] * sb[n]
 constexpr bool qt_scaled(int qt) { return qt == QT_I8 || qt == QT_I4 || qt == QT_F8 || qt == QT_I4F6; }
@@ -176,6 +178,10 @@ template <>
 struct AccT<QT_MXF4> {
   typedef v4f type;
 };
+template <>
+struct AccT<QT_MXF8A> {
+  typedef v4f type;
+};
 
 // fp8 e4m3 x e4m3 over K = 128 (one 128-B v2 stage), f32 accumulate: the block-scaled MFMA with
 // every 32-element block scale = 2^0 (e8m0 code 127), i.e. the plain fp8 dot product at twice the
@@ -190,6 +196,15 @@ template <int SEL>
 __device__ __forceinline__ v4f mfma_mxf4_k128(const v4i& b, uint32_t sb, const v4i& a, uint32_t sa, const v4f& c) {
   const v8i bw = {b[0], b[1], b[2], b[3], 0, 0, 0, 0}, aw = {a[0], a[1], a[2], a[3], 0, 0, 0, 0};
   return __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(bw, aw, c, 4, 4, SEL, (int)sb, SEL, (int)sa);
+}
+// MXFP8 activations x MXFP4 weights over K = 128: src0 = the B fragment, fp4 e2m1 (format code 4, 16 B
+// per lane: lane (row r, K group g) supplies the nibbles of K = [32 g, 32 g + 32)), src1 = the A fragment,
+// fp8 e4m3 (format code 0, 32 B per lane: registers 0-3 the bytes of K = [16 g, 16 g + 16), registers
+// 4-7 those of K = [64 + 16 g, 64 + 16 g + 16)); byte 0 of sb / sa is the e8m0 scale of the MX block
+// K = [32 g, 32 g + 32) of either operand (the map: gg_tile_v2's QT_MXF8A body).
+__device__ __forceinline__ v4f mfma_mxf8a_k128(const v4i& b, uint32_t sb, const v8i& a, uint32_t sa, const v4f& c) {
+  const v8i bw = {b[0], b[1], b[2], b[3], 0, 0, 0, 0};
+  return __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(bw, a, c, 4, 0, 0, (int)sb, 0, (int)sa);
 }
 __device__ __forceinline__ v8i cat_v4i(const v4i& lo, const v4i& hi) {
   return v8i{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
@@ -1164,7 +1179,132 @@ __device__ __forceinline__ void gg_tile_v2(const GGMeta& mt, const uint8_t* __re
   // Waves 4-7 instead defer the second K half of every stage past the barrier, holding its
   // fragments in registers: after each barrier they start on MFMAs while waves 0-3 start on LDS
   // reads. Every accumulator still sees its K chunks in order -> bit-identical results.
-  if constexpr ((ABL & V2_STAGGER) != 0 && ((ABL >> V2_SPREAD_SHIFT) & 7) != 0) {
+  if constexpr (QT == QT_MXF8A) {
+    // w4a8_g32_sym_MXFP8: one K = 128 MFMA step per stage — 128 B of an A row (e4m3), 64 B of a B row
+    // (e2m1). Stage image: A as every v2 stage (128-B rows, 16-B chunks XOR-swizzled by (row >> 1) & 7),
+    // B in 64-B rows (four chunks, XOR-swizzled by T[(row >> 2) & 3], T = {0, 2, 3, 1}: every 16-lane
+    // group of the ds_read_b128 covers the 16 slots of the 256-B bank row once).
+    // Lane map (measured: tests/test_mxfp8_a8_gpu.py T1 / T2 pin it): with an fp8 operand beside an fp4
+    // one, lane group g's eight fp8 registers are K = [16 g, 16 g + 16) (registers 0-3) and
+    // K = [64 + 16 g, 64 + 16 g + 16) (registers 4-7) — the 16-B chunks g and g + 4 of the stage row, as
+    // in the unit-scale fp8 body — while its fp4 registers are K = [32 g, 32 g + 32) and its scale
+    // registers (both operands) are the scales of the MX block K = [32 g, 32 g + 32): an fp8 lane's bytes
+    // are NOT one block, the hardware pairs every element with its block's scale across lanes.
+    // Ring of MXR stages (3 where the LDS image allows: 48 KiB per 256 x 256 stage, 16 KiB per
+    // 64 x 128), D = MXR - 1 stages ahead, one barrier per stage: the barrier that publishes stage s
+    // also frees the buffer of stage s - 1, which stage s + D refills. Buffer-form LDS-DMA (rows
+    // clamped; K-tail chunks offset past num_records: zeros).
+    // Scales: dword g of 16-B group t of a scale row = the K group g scales of stages 4 t .. 4 t + 3
+    // (include/mxmoe_gg.h), by direct range-checked buffer loads as the QT_MXF4 body's (whole byte
+    // offset in the vector offset, num_records ends at the tile's last valid row), issued BEFORE the
+    // stage's DMA pieces, so the counted wait that leaves only the newest pieces in flight covers them.
+    // One register set: a stage first takes its scale bytes out of the group's dwords (byte
+    // (ks0 + s) & 3, by a shift: a split-K slice may start at any stage of a group), and a group's last
+    // stage then loads the next group's dwords over them — no copy of a register a load may still be
+    // writing (the compiler would drain the ring for it).
+    constexpr int MXR = ((ABL & V2_B3) != 0 || Cfg::BM <= 128) ? 3 : 2, D = MXR - 1;
+    constexpr int MXA = Cfg::A_BYTES, MXB = Cfg::BN * 64, MXS = MXA + MXB;
+    constexpr int GB8 = Cfg::BN / 128;  // 1-KiB B pieces (16 rows x 64 B) per wave per stage
+    constexpr int NP = GA + GB8;
+    static_assert(MXR * MXS <= 160 * 1024 && Cfg::BN % 128 == 0, "MXFP8 ring");
+    const int K = mt.K, kb_b = K >> 1;  // bytes of an A / a B row
+    uint32_t va[GA], vb[GB8];
+    int ca[GA], cb[GB8];  // 16-B chunk of the row this lane brings
+    {
+      const int rsub = lane >> 3, p = lane & 7;
+#pragma unroll
+      for (int j = 0; j < GA; ++j) {
+        const int row = (wave * GA + j) * 8 + rsub;
+        ca[j] = p ^ ((row >> 1) & 7);
+        va[j] = (uint32_t)((min(m0 + row, M - 1) - m0) * lda) + (ca[j] << 4);
+      }
+      const int rs16 = lane >> 2, p4 = lane & 3;
+#pragma unroll
+      for (int j = 0; j < GB8; ++j) {
+        const int row = (wave * GB8 + j) * 16 + rs16;
+        cb[j] = p4 ^ ((0x78 >> (2 * ((row >> 2) & 3))) & 3);
+        vb[j] = (uint32_t)((min(n0 + row, N - 1) - n0) * ldb) + (cb[j] << 4);
+      }
+    }
+    const __amdgpu_buffer_rsrc_t rA = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(A) + (int64_t)m0 * lda,
+                                                                        (short)0, 0x7fffffff, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rB = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(B) + (int64_t)n0 * ldb,
+                                                                        (short)0, 0x7fffffff, 0x00020000);
+    auto issue8 = [&](int t, int slot) {  // stage t of this tile -> ring slot `slot` (= t % MXR)
+      uint8_t* As = lds + slot * MXS;
+      uint8_t* Bs = As + MXA;
+      const int ka = (ks0 + t) * 128, kb = (ks0 + t) * 64;
+      const bool full = ka + 128 <= K;
+#pragma unroll
+      for (int j = 0; j < GA; ++j) bdma(rA, full || ka + ca[j] * 16 < K ? va[j] : 0x80000000u, ka, As + (wave * GA + j) * 1024);
+#pragma unroll
+      for (int j = 0; j < GB8; ++j)
+        bdma(rB, full || kb + cb[j] * 16 < kb_b ? vb[j] : 0x80000000u, kb, Bs + (wave * GB8 + j) * 1024);
+    };
+    const int srow = ((K / 32 + 15) >> 4) << 4;  // scale bytes per row (device layout)
+    const __amdgpu_buffer_rsrc_t rsa = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<uint8_t*>(reinterpret_cast<const uint8_t*>(SA)) + (int64_t)m0 * srow, (short)0,
+        min(M - m0, Cfg::BM) * srow, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsb = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<uint8_t*>(reinterpret_cast<const uint8_t*>(SB)) + (int64_t)n0 * srow, (short)0,
+        min(N - n0, Cfg::BN) * srow, 0x00020000);
+    const int sva = (wm * Cfg::WTM + r16) * srow + 4 * g, svb = (wn * Cfg::WTN + r16) * srow + 4 * g;
+    uint32_t qa[FM], qb[FN];  // the scale dwords of the current group (four stages per dword)
+    auto sload = [&](int stage) {  // the group of absolute K stage `stage`
+      const int t = (stage >> 2) * 16;
+#pragma unroll
+      for (int i = 0; i < FM; ++i) qa[i] = __builtin_amdgcn_raw_buffer_load_b32(rsa, sva + i * 16 * srow + t, 0, 0);
+#pragma unroll
+      for (int j = 0; j < FN; ++j) qb[j] = __builtin_amdgcn_raw_buffer_load_b32(rsb, svb + j * 16 * srow + t, 0, 0);
+    };
+    const uint32_t b_row8 = (uint32_t)(wn * Cfg::WTN + r16) * 64u;
+    const uint32_t offa0 = (uint32_t)((g ^ swz) << 4), offa1 = (uint32_t)(((4 + g) ^ swz) << 4);
+    const uint32_t offb = (uint32_t)((g ^ ((0x78 >> (2 * (r16 >> 2))) & 3)) << 4);
+    if (nst > 0) {
+      sload(ks0);
+#pragma unroll
+      for (int t = 0; t < D; ++t)
+        if (t < nst) issue8(t, t);
+      int slot = 0, islot = D;  // ring slots of stage s and of stage s + D
+      // one stage: STEADY = stage s + D exists (and with it s + 1), its pieces are issued unconditionally
+      auto stage = [&](int s, auto steady) {
+        constexpr bool STEADY = decltype(steady)::value;
+        // stage s landed: at most the D - 1 newer stages' pieces stay in flight
+        if (STEADY || s + D - 1 < nst) wait_vmcnt<(D - 1) * NP>();
+        else wait_vmcnt<0>();
+        lds_barrier();
+        const int st = ks0 + s, sh = (st & 3) * 8;
+        uint32_t sai[FM], sbj[FN];  // this stage's scale bytes (byte 0)
+#pragma unroll
+        for (int i = 0; i < FM; ++i) sai[i] = qa[i] >> sh;
+#pragma unroll
+        for (int j = 0; j < FN; ++j) sbj[j] = qb[j] >> sh;
+        __builtin_amdgcn_sched_barrier(0);  // (the loads below overwrite the dwords just read)
+        if ((st & 3) == 3 && (STEADY || s + 1 < nst)) sload(st + 1);
+        if (STEADY || s + D < nst) issue8(s + D, islot);
+        if (!wave_dead) {
+          const uint8_t* As = lds + slot * MXS + a_row;
+          const uint8_t* Bs = lds + slot * MXS + MXA + b_row8;
+          v4i b[FN];
+#pragma unroll
+          for (int j = 0; j < FN; ++j) b[j] = *reinterpret_cast<const v4i*>(Bs + j * 1024 + offb);
+#pragma unroll
+          for (int i = 0; i < FM; ++i) {
+            const v8i a = cat_v4i(*reinterpret_cast<const v4i*>(As + i * 2048 + offa0),
+                                  *reinterpret_cast<const v4i*>(As + i * 2048 + offa1));
+#pragma unroll
+            for (int j = 0; j < FN; ++j) acc[i][j] = mfma_mxf8a_k128(b[j], sbj[j], a, sai[i], acc[i][j]);
+          }
+        }
+        slot = slot + 1 == MXR ? 0 : slot + 1;
+        islot = islot + 1 == MXR ? 0 : islot + 1;
+      };
+      int s = 0;
+      for (; s + D < nst; ++s) stage(s, std::true_type());
+      for (; s < nst; ++s) stage(s, std::false_type());
+      __syncthreads();  // every wave done with the ring: the split-K flag / epilogue staging reuse it
+    }
+  } else if constexpr ((ABL & V2_STAGGER) != 0 && ((ABL >> V2_SPREAD_SHIFT) & 7) != 0) {
     // Staggered v2 with the stage's LDS-DMA spread over the MFMAs. Each steady-state iteration (every
     // piece it issues is a full 128-B stage) is one basic block, ordered by sched_group_barrier as
     //   early waves: ds_read half 0 | {k MFMA, 1 DMA piece} x (GA+GB) | rest of half 0 | ds_read half 1 | MFMA half 1
@@ -1586,7 +1726,7 @@ __device__ __forceinline__ void gg_tile_v2(const GGMeta& mt, const uint8_t* __re
     for (int j = 0; j < FN; ++j) sbw[j] = *reinterpret_cast<const uint2*>(sl + 256 + wn * Cfg::WTN + j * 16 + 4 * e_g);
   }
   auto pack_frag = [&](int i, int j, _Float16 sai) {
-    if constexpr (QT == QT_F16 || QT == QT_BF16 || QT == QT_MXF4) return pack4_f16(acc[i][j]);
+    if constexpr (QT == QT_F16 || QT == QT_BF16 || QT == QT_MXF4 || QT == QT_MXF8A) return pack4_f16(acc[i][j]);
     else if constexpr (QT == QT_F8) return scale_pack4f(acc[i][j], sai, sbw[j]);
     else return scale_pack4<(QT == QT_I4) ? 8 : 0>(acc[i][j], sai, sbw[j]);
   };
@@ -1601,7 +1741,7 @@ __device__ __forceinline__ void gg_tile_v2(const GGMeta& mt, const uint8_t* __re
       *reinterpret_cast<uint2*>(reg + ml * 128 + ((q ^ (ml & 7)) << 4) + (e_g & 1) * 8) = pk;
     }
   };
-  if constexpr (QT == QT_F16 || QT == QT_I8 || QT == QT_I4) {
+  if constexpr (QT == QT_F16 || QT == QT_I8 || QT == QT_I4 || QT == QT_MXF8A) {
     if ((mt.reserved2 & META_SILU) != 0) {
       // fused SiLU: fragments 2 jp (gate) and 2 jp + 1 (up) hold the same 16 output columns; the
       // wave's 32 output columns are staged as 64-B rows and stored 16 rows per instruction
@@ -3108,6 +3248,11 @@ __global__ __launch_bounds__(512, 2) void gg_v2_kernel(GGArgs args) {
     constexpr int MXABL = ABL & ~(V2_STAGGER | V2_B3);
     if (cls == 0) gg_tile_v2<V2Cfg<256>, QT_MXF4, MXABL>(mt, A, B, SA, SB, C, td.m0, td.n0, lds, sk);
     else gg_tile_v2<V2Cfg<128>, QT_MXF4, MXABL>(mt, A, B, SA, SB, C, td.m0, td.n0, lds, sk);  // no 64-row class
+  } else if ((QM & (1 << QT_MXF8A)) && mt.qtype == QT_MXF8A) {
+    // a mainloop of its own (K = 128 stages, ring of 3 in the 160-KiB image, of 2 in the 132-KiB one)
+    constexpr int M8ABL = ABL & V2_B3;
+    if (cls == 0) gg_tile_v2<V2Cfg<256>, QT_MXF8A, M8ABL>(mt, A, B, SA, SB, C, td.m0, td.n0, lds, sk);
+    else gg_tile_v2<V2Cfg<128>, QT_MXF8A, M8ABL>(mt, A, B, SA, SB, C, td.m0, td.n0, lds, sk);  // no 64-row class
   }
   if constexpr ((ABL & V2_TRACE) != 0) {
     if (threadIdx.x == 0 && blockIdx.x < kTraceBlocks) {
@@ -3173,6 +3318,11 @@ __global__ __launch_bounds__(512, 2 * NWG) void gg_wo2_kernel(GGArgs args) {
   else if ((QM & (1 << QT_W8A16)) && mt.qtype == QT_W8A16) gg_tile_wo<Cfg, 8, WP>(mt, A, B, SB, C, td.m0, td.n0, lds, sk);
   else if ((QM & (1 << QT_W2A16)) && mt.qtype == QT_W2A16) gg_tile_wo<Cfg, 2, WP>(mt, A, B, SB, C, td.m0, td.n0, lds, sk);
   else if ((QM & (1 << QT_MXF4W)) && mt.qtype == QT_MXF4W) gg_tile_wo<Cfg, 4, WP, WO_FMT_MX>(mt, A, B, SB, C, td.m0, td.n0, lds, sk);
+  else if ((QM & (1 << QT_MXF8A)) && mt.qtype == QT_MXF8A) {
+    // w4a8_g32_sym_MXFP8 on the 64 x 128 tile: ring of three 16-KiB K = 128 stages (48 KiB)
+    const _Float16* SA = static_cast<const _Float16*>(args.ptr_SA[td.prob]);
+    gg_tile_v2<V2Cfg<64, 128, 4, 2>, QT_MXF8A, V2_B3>(mt, A, B, SA, SB, C, td.m0, td.n0, lds, sk);
+  }
   if constexpr ((ABL & V2_TRACE) != 0) {  // (as gg_v2_kernel; the class field holds the problem index)
     if (threadIdx.x == 0 && blockIdx.x < kTraceBlocks) {
       wait_vmcnt<0>();

@@ -220,7 +220,7 @@ __device__ __forceinline__ float amax8(const h8_t& x) {
 // GroupGEMM's fused SiLU epilogue, routed [T*topk][N], shared [T][Ns]); 3: silu_mul_quant on a
 // gate_up output whose gate / up columns alternate in 16-column blocks (the interleaved weights of
 // the fused epilogue, run through the plain epilogue: small-batch calls on wo3)
-// MX: the build that also carries the MXMOE_ACT_MXFP4 tag (launched only for calls whose segments hold
+// MX: the build that also carries the MXMOE_ACT_MXFP4 and MXMOE_ACT_MXFP8 tags (launched only for calls whose segments hold
 // one, mxmoe_moe_act_quant: the other tags' builds stay as they are without it)
 template <int MODE, int MAXC, bool MX = false>
 __global__ __launch_bounds__(kThreads) void act_quant_kernel(ActArgs a) {
@@ -335,6 +335,50 @@ __global__ __launch_bounds__(kThreads) void act_quant_kernel(ActArgs a) {
         q |= nib << (4 * j);
       }
       *reinterpret_cast<uint32_t*>(o4 + idx / 2) = bad ? 0u : q;
+      if ((lane & 3) == 0) {
+        const int blk = (col0 + idx) >> 5, c16 = blk & 15;
+        so[(blk & ~15) + 4 * (c16 & 3) + (c16 >> 2)] = bad ? (uint8_t)255 : (uint8_t)(e + 127);
+        if (blk == nblk - 1) {  // the row's last block: the pads of its 16-byte group are 2^0
+#pragma clang loop unroll(disable) vectorize(disable)
+          for (int pc = c16 + 1; pc < 16; ++pc) so[(blk & ~15) + 4 * (pc & 3) + (pc >> 2)] = 127;
+        }
+      }
+    }
+    return;
+  }
+  if constexpr (MX) if (sg.qtag == MXMOE_ACT_MXFP8) {
+    // OCP MXFP8, e4m3 elements (include/mxmoe_gg.h, w4a8_g32_sym_MXFP8): blocks, amax and scale bytes
+    // as the MXFP4 tag above with e = floor(log2 amax) - 8 (e4m3's largest binade); elements scaled by
+    // 2^-e exactly, clamped to +-448 (v_med3_f32 keeps the sign of -0) and rounded ONCE to e4m3, to
+    // nearest even, by the hardware convert (OCP e4m3 on gfx950). One code byte per element.
+    const int srow = ((sg.width / 32 + 15) >> 4) << 4;  // scale bytes per row (device layout)
+    uint8_t* const o8 = a.out + sg.out_off + row * (int64_t)sg.width + col0;
+    uint8_t* const so = reinterpret_cast<uint8_t*>(a.scales + sg.scale_off) + row * (int64_t)srow;
+    const int nblk = sg.width / 32;
+#pragma unroll
+    for (int c = 0; c < MAXC; ++c) {
+      if (c * 512 >= width) break;  // uniform
+      const int idx = c * 512 + lane * 8;
+      const uint4 w = __builtin_bit_cast(uint4, x[c]);
+      const uint32_t cm = 0x7FFF7FFFu;
+      uint32_t m2 = max(max((w.x & cm) & 0xFFFFu, (w.x & cm) >> 16), max((w.y & cm) & 0xFFFFu, (w.y & cm) >> 16));
+      m2 = max(m2, max(max((w.z & cm) & 0xFFFFu, (w.z & cm) >> 16), max((w.w & cm) & 0xFFFFu, (w.w & cm) >> 16)));
+      m2 = max(m2, (uint32_t)__shfl_xor((int)m2, 1, 64));
+      m2 = max(m2, (uint32_t)__shfl_xor((int)m2, 2, 64));
+      if (idx >= width) continue;
+      const bool bad = m2 >= 0x7C00u;  // an Inf or a NaN in the block: NaN scale, zero codes
+      const float am = (float)__builtin_bit_cast(_Float16, (uint16_t)m2);
+      const int e = m2 == 0 ? -127 : (int)((__builtin_bit_cast(uint32_t, am) >> 23) & 0xFF) - 127 - 8;
+      const float inv = __builtin_bit_cast(float, (uint32_t)(127 - e) << 23);  // 2^-e (e in [-127, 7])
+      float y[8];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) y[j] = __builtin_amdgcn_fmed3f((float)x[c][j] * inv, -448.0f, 448.0f);  // product exact
+      int q0 = 0, q1 = 0;
+      q0 = __builtin_amdgcn_cvt_pk_fp8_f32(y[0], y[1], q0, false);
+      q0 = __builtin_amdgcn_cvt_pk_fp8_f32(y[2], y[3], q0, true);
+      q1 = __builtin_amdgcn_cvt_pk_fp8_f32(y[4], y[5], q1, false);
+      q1 = __builtin_amdgcn_cvt_pk_fp8_f32(y[6], y[7], q1, true);
+      *reinterpret_cast<uint2*>(o8 + idx) = bad ? uint2{0u, 0u} : uint2{(uint32_t)q0, (uint32_t)q1};
       if ((lane & 3) == 0) {
         const int blk = (col0 + idx) >> 5, c16 = blk & 15;
         so[(blk & ~15) + 4 * (c16 & 3) + (c16 >> 2)] = bad ? (uint8_t)255 : (uint8_t)(e + 127);
@@ -467,7 +511,7 @@ static void launch_act_any(int mode, const ActArgs& a, int maxw, bool mx, hipStr
   else if (mode == 3) launch_act_m<3>(a, maxw, mx, st);
   else launch_act_m<0>(a, maxw, mx, st);
 }
-// mx: a segment of the call carries MXMOE_ACT_MXFP4 (the MX builds of the kernel)
+// mx: a segment of the call carries MXMOE_ACT_MXFP4 or MXMOE_ACT_MXFP8 (the MX builds of the kernel)
 static int launch_act(int mode, ActArgs a, int64_t nslots, int w_routed, int w_shared, void* stream, bool mx = false) {
   if (nslots == 0) return MXMOE_GG_OK;
   a.parts = 1;
@@ -635,9 +679,9 @@ int mxmoe_moe_act_quant(int mode, const void* routed_in, const void* shared_in, 
                         const int32_t* sorted_expert, const int32_t* perm_token, const mxmoe_moe_seg* segs, int nseg,
                         uint32_t tag_mask, void* out, void* scales, void* stream) {
   if (mode < 0 || mode > 3) return fail(MXMOE_GG_ERR_INVALID, "mxmoe_moe_act_quant: mode must be 0..3 (mode=%d)", mode);
-  if (tag_mask >> (MXMOE_ACT_MXFP4 + 1))
+  if (tag_mask & ~((2u << MXMOE_ACT_MXFP4) - 1u | 1u << MXMOE_ACT_MXFP8))  // (tag 5 is not assigned)
     return fail(MXMOE_GG_ERR_UNSUPPORTED, "mxmoe_moe_act_quant: unknown activation tag in mask %#x", tag_mask);
-  const bool mx = (tag_mask >> MXMOE_ACT_MXFP4) & 1;
+  const bool mx = ((tag_mask >> MXMOE_ACT_MXFP4) & 1) || ((tag_mask >> MXMOE_ACT_MXFP8) & 1);
   if (mode == 0)
     return quant_act_impl("mxmoe_moe_act_quant", routed_in, T, N, topk, shared_in != nullptr, sorted_expert, perm_token,
                           segs, nseg, out, scales, stream, mx);

@@ -25,7 +25,7 @@ from . import _native as nat
 
 
 FMT_CODES = {"": nat.FMT_DEFAULT, "E4M3": nat.FMT_E4M3, "bf16": nat.FMT_BF16, "F6": nat.FMT_F6,
-             "MXFP4": nat.FMT_MXFP4}
+             "MXFP4": nat.FMT_MXFP4, "MXFP8": nat.FMT_MXFP8}
 
 
 @dataclasses.dataclass(frozen=True)
@@ -37,7 +37,9 @@ class QParams:
     codes, ``_native.pack_f6``: same results on the fp6 MFMA — lab library only, measured slower
     than the int4 path) or "MXFP4" (w4a4_g32_sym_MXFP4: OCP e2m1 codes with one e8m0
     scale per 32-K block, ``quantize.quant_mxfp4`` / ``pack_mxfp4_scales``; with ``a_bits = 16``
-    w4a16_g32_sym_MXFP4, fp16 activations on the same B codes and scales). The reference's ``_accfp16`` strategies (fp16 MMA with an fp16
+    w4a16_g32_sym_MXFP4, fp16 activations on the same B codes and scales) or "MXFP8"
+    (w4a8_g32_sym_MXFP8: OCP e4m3 activation codes with e8m0 block scales, ``quantize.quant_mxfp8``,
+    on the same MXFP4 B codes and scales). The reference's ``_accfp16`` strategies (fp16 MMA with an fp16
     accumulator, tile_config.py:94-97) run as their f32-accumulating base type: MFMA has no fp16
     accumulator, and the f32 sum is the more accurate result of the same products."""
 
@@ -73,7 +75,8 @@ class QParams:
         if not self.is_quant:
             return "bf16" if self.fmt == "bf16" else "fp16"
         return f"w{self.w_bits}a{self.a_bits}_g{self.gsize}_{'sym' if self.sym else 'asym'}" + \
-            ("_E4M3" if self.is_fp8 else "_F6" if self.fmt == "F6" else "_MXFP4" if self.fmt == "MXFP4" else "")
+            ("_E4M3" if self.is_fp8 else "_F6" if self.fmt == "F6" else "_MXFP4" if self.fmt == "MXFP4" else
+             "_MXFP8" if self.fmt == "MXFP8" else "")
 
     @staticmethod
     def from_qcfg(qcfg: str) -> "QParams":
@@ -88,7 +91,7 @@ class QParams:
         if qcfg.endswith("_bf16"):
             raise ValueError(f"{qcfg}: weight-only with bf16 activations is not built on MI355X")
         fmt = "E4M3" if qcfg.endswith("_E4M3") else "F6" if qcfg.endswith("_F6") else \
-            "MXFP4" if qcfg.endswith("_MXFP4") else ""
+            "MXFP4" if qcfg.endswith("_MXFP4") else "MXFP8" if qcfg.endswith("_MXFP8") else ""
         return QParams(a_bits=a, w_bits=w, gsize=g, sym="asym" not in qcfg, fmt=fmt)
 
 
@@ -101,6 +104,8 @@ W4A4_F6 = QParams(4, 4, -1, True, "F6")  # w4a4_g-1_sym on fp6 images (lab libra
 W4A4_MXFP4 = QParams(4, 4, 32, True, "MXFP4")  # w4a4_g32_sym_MXFP4: e2m1 codes, e8m0 block scales (include/mxmoe_gg.h)
 # w4a16_g32_sym_MXFP4: fp16 activations on the same MXFP4 weight tensors (weight-only: the small-batch form)
 W4A16_MXFP4 = QParams(16, 4, 32, True, "MXFP4")
+# w4a8_g32_sym_MXFP8: MXFP8 (e4m3) activations on the same MXFP4 weight tensors, one block-scaled MFMA
+W4A8_MXFP8 = QParams(8, 4, 32, True, "MXFP8")
 W4A4_G128 = QParams(4, 4, 128, True)  # w4a4_g128_sym: one scale per 128-K group (cta_gemm.cuh:610-772)
 # weight-only (any group size that is -1 or a multiple of 64 dividing K, sym or asym, 2 / 4 / 8 bits)
 W4A16_G128_ASYM = QParams(16, 4, 128, False)
@@ -109,7 +114,7 @@ W4A16_G128_SYM = QParams(16, 4, 128, True)
 W8A16_ASYM = QParams(16, 8, -1, False)
 W2A16_G128_ASYM = QParams(16, 2, 128, False)
 
-SUPPORTED = {q.qcfg: q for q in (FP16, BF16, W8A8, W8A8_E4M3, W4A4, W4A4_MXFP4, W4A16_MXFP4, W4A4_G128, W4A16_G128_ASYM, W4A16_ASYM, W4A16_G128_SYM, W8A16_ASYM,
+SUPPORTED = {q.qcfg: q for q in (FP16, BF16, W8A8, W8A8_E4M3, W4A4, W4A4_MXFP4, W4A16_MXFP4, W4A8_MXFP8, W4A4_G128, W4A16_G128_ASYM, W4A16_ASYM, W4A16_G128_SYM, W8A16_ASYM,
                                   QParams(16, 4, -1, True), QParams(16, 8, -1, True), QParams(16, 8, 128, True),
                                   QParams(16, 8, 128, False), W2A16_G128_ASYM, QParams(16, 2, -1, False),
                                   QParams(16, 2, -1, True), QParams(16, 2, 128, True))}
@@ -122,7 +127,8 @@ class Problem:
     fp16 / bf16: A [M,K], B [N,K] 16-bit.  quant (incl. E4M3 codes): A uint8 [M, K*a_bits/8] / B uint8 [N, K*w_bits/8]
     in pack_wxax layout, scale_a fp16 [M], scale_b fp16 [N] (w4a4_g128: [K/128][M] and [K/128][N],
     the permute_scale layout; MXFP4: codes uint8 [rows, K/2] as quant_mxfp4 returns them, scales uint8
-    [rows, 16 * ceil(K/32 / 16)] in the device layout of pack_mxfp4_scales).  C fp16 [M, ldc] (ldc >= N).
+    [rows, 16 * ceil(K/32 / 16)] in the device layout of pack_mxfp4_scales; MXFP8: A uint8 [M, K] e4m3
+    codes as quant_mxfp8 returns them, B and both scales as MXFP4's).  C fp16 [M, ldc] (ldc >= N).
     """
 
     A: torch.Tensor
@@ -168,6 +174,13 @@ class Problem:
             if self.K % 32:
                 raise ValueError(f"{self.q.qcfg}: K={self.K} must be a multiple of the 32-element MX block")
             need(self.A, (torch.uint8,), "A (e2m1 codes)")
+            need(self.B, (torch.uint8,), "B (e2m1 codes)")
+            need(self.scale_a, (torch.uint8,), "scale_a (e8m0, pack_mxfp4_scales)")
+            need(self.scale_b, (torch.uint8,), "scale_b (e8m0, pack_mxfp4_scales)")
+        elif self.q.fmt == "MXFP8":
+            if self.K % 32:
+                raise ValueError(f"{self.q.qcfg}: K={self.K} must be a multiple of the 32-element MX block")
+            need(self.A, (torch.uint8, torch.float8_e4m3fn), "A (e4m3 codes)")
             need(self.B, (torch.uint8,), "B (e2m1 codes)")
             need(self.scale_a, (torch.uint8,), "scale_a (e8m0, pack_mxfp4_scales)")
             need(self.scale_b, (torch.uint8,), "scale_b (e8m0, pack_mxfp4_scales)")

@@ -21,7 +21,7 @@ from typing import Optional, Sequence
 import torch
 
 from .groupgemm import GroupGemm, Problem, QParams
-from .quantize import (pack_e4m3, pack_mxfp4_scales, pack_weightonly_mi355x, pack_wxax, quant_e4m3, quant_mxfp4,
+from .quantize import (pack_e4m3, pack_mxfp4_scales, pack_weightonly_mi355x, pack_wxax, quant_e4m3, quant_mxfp4, quant_mxfp8,
                        quant_rtn_sym, quant_weightonly)
 from .workload import QShape
 
@@ -47,7 +47,7 @@ class LayerInputs:
                 tot += s.N * (s.K // 32)
             elif not plain and ab == 16:  # weight-only: scale (+ zp) per column and group
                 tot += 2 * s.N * (1 if s.gsize == -1 else s.K // s.gsize) * (1 if s.sym else 2)
-            elif s.fmt == "MXFP4":  # one e8m0 byte per 32-K block
+            elif s.fmt in ("MXFP4", "MXFP8"):  # one e8m0 byte per 32-K block
                 tot += (s.M + s.N) * (s.K // 32)
             elif not plain:
                 tot += 2 * (s.M + s.N) * (1 if s.gsize == -1 else s.K // s.gsize)
@@ -76,6 +76,10 @@ def build_layer_inputs(shapes: Sequence[QShape], device="cuda", seed: int = 42,
             probs.append(Problem(A=a, B=qb, C=C, M=M, N=N, K=K, q=q, scale_b=pack_mxfp4_scales(sb)))
         elif q.fmt == "MXFP4":
             (qa, sa), (qb, sb) = quant_mxfp4(a), quant_mxfp4(b)
+            probs.append(Problem(A=qa, B=qb, C=C, M=M, N=N, K=K, q=q, scale_a=pack_mxfp4_scales(sa),
+                                 scale_b=pack_mxfp4_scales(sb)))
+        elif q.fmt == "MXFP8":  # MXFP8 activations on the MXFP4 weight operand
+            (qa, sa), (qb, sb) = quant_mxfp8(a), quant_mxfp4(b)
             probs.append(Problem(A=qa, B=qb, C=C, M=M, N=N, K=K, q=q, scale_a=pack_mxfp4_scales(sa),
                                  scale_b=pack_mxfp4_scales(sb)))
         elif q.fmt == "bf16":
@@ -200,7 +204,7 @@ def slice_scale_b(p: Problem, n0: int, n1: int) -> Optional[torch.Tensor]:
     if p.scale_b is None:
         return None
     q = p.q
-    if q.fmt == "MXFP4":  # [N][16 ceil(K/32 / 16)] e8m0 rows
+    if q.fmt in ("MXFP4", "MXFP8"):  # [N][16 ceil(K/32 / 16)] e8m0 rows
         return p.scale_b[n0:n1]
     G = 1 if q.gsize == -1 else p.K // q.gsize
     if G == 1 and not (q.is_weight_only and not q.sym):

@@ -33,7 +33,9 @@ from . import _native as nat
 from .groupgemm import GroupGemm, Problem, QParams
 
 ACT_FP16, ACT_INT8, ACT_INT4, ACT_INT4_G128, ACT_MXFP4 = 0, 1, 2, 3, 4
-_BITS = {ACT_FP16: 16, ACT_INT8: 8, ACT_INT4: 4, ACT_INT4_G128: 4, ACT_MXFP4: 4}
+ACT_MXFP8 = 6  # MXMOE_ACT_MXFP8 (w4a8_g32_sym_MXFP8); 5 is not assigned (include/mxmoe_moe.h)
+_BITS = {ACT_FP16: 16, ACT_INT8: 8, ACT_INT4: 4, ACT_INT4_G128: 4, ACT_MXFP4: 4, ACT_MXFP8: 8}
+_MX_TAGS = (ACT_MXFP4, ACT_MXFP8)  # block-scaled tags: e8m0 scale rows, the MX builds of the activation kernel
 
 
 def _mx_scale_row(width: int) -> int:
@@ -53,6 +55,8 @@ def qtag_of(a_bits: int, gsize: int) -> int:
         return ACT_INT4_G128
     if a_bits == 4 and gsize == 32:  # w4a4_g32_sym_MXFP4 (no integer g32 type exists)
         return ACT_MXFP4
+    if a_bits == 8 and gsize == 32:  # w4a8_g32_sym_MXFP8 (likewise)
+        return ACT_MXFP8
     raise ValueError(f"activation quantisation a{a_bits} g{gsize} not supported")
 
 
@@ -239,7 +243,7 @@ class ActBatch:
         tag = self.qtags[e]
         if tag == ACT_FP16:
             return None
-        if tag == ACT_MXFP4:  # e8m0 bytes [rows, 16 G] inside the fp16 store
+        if tag in _MX_TAGS:  # e8m0 bytes [rows, 16 G] inside the fp16 store
             n = s.rows * _mx_scale_row(s.width) // 2
             return self.scales[s.scale_off:s.scale_off + n].view(torch.uint8).view(s.rows, _mx_scale_row(s.width))
         n = s.rows * (s.width // 128 if tag == ACT_INT4_G128 else 1)
@@ -252,11 +256,11 @@ def _make_segments(rows: Sequence[int], first: Sequence[int], widths: Sequence[i
     for r, f, w, tag in zip(rows, first, widths, qtags):
         if w % 128:
             raise ValueError(f"segment width {w} must be a multiple of 128")
-        if tag == ACT_MXFP4:
+        if tag in _MX_TAGS:
             soff += soff % 2  # its scale bytes are read as dwords: a 4-byte aligned block
         segs.append(nat.MoeSegC(tag, f, r, w, off, soff))
         off += (r * w * _BITS[tag] // 8 + 15) // 16 * 16  # 16-B aligned A operands
-        if tag == ACT_MXFP4:
+        if tag in _MX_TAGS:
             soff += r * _mx_scale_row(w) // 2  # (fp16 elements: two e8m0 bytes each)
         else:
             soff += 0 if tag == ACT_FP16 else r * (w // 128 if tag == ACT_INT4_G128 else 1)
@@ -281,7 +285,7 @@ def quant_act(hidden: torch.Tensor, r: Routing, qtags: Sequence[int], with_share
     h = hidden.contiguous()
 
     def launch(st=stream):
-        if ACT_MXFP4 in qtags:  # the builds that carry the MXFP4 tag (mxmoe_moe_act_quant, mode 0)
+        if any(t in _MX_TAGS for t in qtags):  # the builds that carry the MX tags (mxmoe_moe_act_quant, mode 0)
             nat.check(nat.lib().mxmoe_moe_act_quant(0, _ptr(h), _ptr(h) if with_shared else None, T, r.topk, K, K,
                                                     _ptr(r.sorted_expert), _ptr(r.perm_token), _ptr(dsegs), nseg,
                                                     _tag_mask(qtags), _ptr(out), _ptr(scales), _stream(st)))
@@ -321,7 +325,7 @@ def silu_mul_quant(routed: torch.Tensor, shared: Optional[torch.Tensor], r: Rout
     mode = 2 if activated else 3 if interleaved else 1
 
     def launch(st=stream):
-        if ACT_MXFP4 in qtags:  # the builds that carry the MXFP4 tag
+        if any(t in _MX_TAGS for t in qtags):  # the builds that carry the MX tags
             nat.check(nat.lib().mxmoe_moe_act_quant(mode, _ptr(routed), _ptr(shared), r.T, r.topk, N, Ns,
                                                     _ptr(r.sorted_expert), None, _ptr(dsegs), nseg, _tag_mask(qtags),
                                                     _ptr(out), _ptr(scales), _stream(st)))
@@ -470,8 +474,9 @@ def gg_mxmoe_share_fused(inp: Sequence[torch.Tensor], experts: Sequence[torch.Te
             raise ValueError(f"gg_mxmoe_share_fused: {len(inp)} inputs for more non-empty experts")
         a_bits, w_bits, gsize, sym = (int(x) for x in qparams_per_exp[e])
         # (4, 4, 32, 1) is w4a4_g32_sym_MXFP4 and (16, 4, 32, 1) w4a16_g32_sym_MXFP4: the only g32 types, so
-        # the tuple needs no format field
-        q = QParams(a_bits, w_bits, gsize, bool(sym), "MXFP4" if (w_bits, gsize) == (4, 32) and a_bits in (4, 16) else "")
+        # the tuple needs no format field ((8, 4, 32, 1) is w4a8_g32_sym_MXFP8)
+        q = QParams(a_bits, w_bits, gsize, bool(sym), "MXFP4" if (w_bits, gsize) == (4, 32) and a_bits in (4, 16) else
+                    "MXFP8" if (a_bits, w_bits, gsize) == (8, 4, 32) else "")
         n, k = (shared_N, shared_K) if e == E else (N, K)
 
         def opt(t):
@@ -545,7 +550,7 @@ def prepare_weight(w: torch.Tensor, q: QParams, interleave: bool = False) -> Exp
         w = interleave_gate_up(w)[0]  # (per-row quantisation commutes with the row order)
     if not q.is_quant:
         return ExpertWeights(w.contiguous(), None, q, N, K)
-    if q.fmt == "MXFP4":  # w4a4 and w4a16 alike: canonical codes + device-layout scales, no repack
+    if q.fmt in ("MXFP4", "MXFP8"):  # w4a4, w4a16 and w4a8 alike: canonical codes + device-layout scales, no repack
         codes, sc = quant_mxfp4(w)
         return ExpertWeights(codes, pack_mxfp4_scales(sc), q, N, K)
     if q.is_weight_only:
@@ -564,7 +569,7 @@ class MoEFFN:
 
     # gate_up qcfgs with the SiLU epilogue: fp16 / w8a8 / w4a4 on every product kernel, weight-only
     # on the small-batch kernel (wo3; a large call of those falls back to the interleaved form)
-    FUSE_QCFGS = ("fp16", "w8a8_g-1_sym", "w4a4_g-1_sym")
+    FUSE_QCFGS = ("fp16", "w8a8_g-1_sym", "w4a4_g-1_sym", "w4a8_g32_sym_MXFP8")
     FUSE_WEIGHT_ONLY = True
 
     def __init__(self, gate_up: Sequence[torch.Tensor], down: Sequence[torch.Tensor],
@@ -612,6 +617,28 @@ class MoEFFN:
         v.w2 = [dataclasses.replace(w, q=W4A16_MXFP4) for w in self.w2]
         v.tag1 = [ACT_FP16] * len(self.qcfg)
         v.tag2 = [ACT_FP16] * len(self.qcfg)
+        v.gate_up_mode = None
+        return v
+
+    def a8_view(self) -> "MoEFFN":
+        """This layer (every qcfg w4a4_g32_sym_MXFP4, or every one w4a16_g32_sym_MXFP4) with MXFP8
+        activations: a layer whose qcfgs are w4a8_g32_sym_MXFP8 on the SAME weight tensors — the three MX
+        types share the B codes and scales byte for byte. The gate_up layout (plain or interleaved for the
+        SiLU epilogue) stays the source layer's, and with it whether the epilogue is fused."""
+        from .groupgemm import W4A8_MXFP8
+
+        names = {q.qcfg for pair in self.qcfg for q in pair}
+        if names not in ({"w4a4_g32_sym_MXFP4"}, {"w4a16_g32_sym_MXFP4"}):
+            raise ValueError("a8_view needs every qcfg of the layer to be w4a4_g32_sym_MXFP4, or every one "
+                             "w4a16_g32_sym_MXFP4")
+        v = object.__new__(MoEFFN)
+        v.E, v.has_shared, v.H, v.N, v.Ns = self.E, self.has_shared, self.H, self.N, self.Ns
+        v.qcfg = [(W4A8_MXFP8, W4A8_MXFP8) for _ in self.qcfg]
+        v.fuse_silu = self.fuse_silu
+        v.w1 = [dataclasses.replace(w, q=W4A8_MXFP8) for w in self.w1]
+        v.w2 = [dataclasses.replace(w, q=W4A8_MXFP8) for w in self.w2]
+        v.tag1 = [ACT_MXFP8] * len(self.qcfg)
+        v.tag2 = [ACT_MXFP8] * len(self.qcfg)
         v.gate_up_mode = None
         return v
 

@@ -284,3 +284,45 @@ def unpack_mxfp4_scales(dev: torch.Tensor, K: int) -> torch.Tensor:
     G = dev.shape[1] // 16
     canon = dev.reshape(rows, G, 4, 4).transpose(2, 3).reshape(rows, 16 * G)
     return canon[:, :K // MXFP4_BLOCK].contiguous()
+
+
+# ---- OCP MXFP8, e4m3 elements (w4a8_g32_sym_MXFP8 activations): e4m3 codes, one e8m0 scale per block ----
+E4M3_MAX = 448.0
+
+
+def quant_mxfp8(x: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
+    """fp16 [rows, K] (K % 32 == 0) -> (codes uint8 [rows, K], scales uint8 [rows, K/32]): OCP MXFP8 with
+    e4m3 elements (torch.float8_e4m3fn's bit patterns), the A operand of w4a8_g32_sym_MXFP8
+    (include/mxmoe_gg.h). RTN as OCP MX v1.0, per 32-element block: e = floor(log2(amax)) - 8 clamped to
+    [-127, 127], scale code e + 127; each element is multiplied by 2^-e exactly, saturated at +-448 and
+    rounded to e4m3 once, to nearest even; the sign of -0 and of values that round to 0 is kept. An
+    all-zero block gets scale code 0 and zero codes, a block holding a NaN or an Inf scale code 255
+    (NaN) and zero codes."""
+    if x.dtype != torch.float16:
+        raise TypeError("quant_mxfp8 expects fp16 input")
+    rows, K = x.shape
+    if K % MXFP4_BLOCK:
+        raise ValueError(f"K={K} must be a multiple of the MX block size {MXFP4_BLOCK}")
+    xf = x.float().reshape(rows, K // MXFP4_BLOCK, MXFP4_BLOCK)
+    bad = ~torch.isfinite(xf).all(dim=-1)
+    xf = torch.where(bad[..., None], torch.zeros_like(xf), xf)
+    amax = xf.abs().amax(dim=-1)
+    ex = torch.frexp(amax).exponent.to(torch.int32)  # floor(log2(amax)) = ex - 1 (quant_mxfp4)
+    e = torch.where(amax == 0, torch.full_like(ex, -127), (ex - 9).clamp(-127, 127))
+    h = torch.div(e, 2, rounding_mode="floor")  # x / 2^e in two exact steps, as quant_mxfp4
+    one = torch.ones((), dtype=torch.float32, device=x.device)
+    y = xf * torch.ldexp(one, -h)[..., None] * torch.ldexp(one, -(e - h))[..., None]
+    y = y.clamp(-E4M3_MAX, E4M3_MAX)  # (keeps the sign of -0)
+    codes = y.to(torch.float8_e4m3fn).view(torch.uint8)  # one rounding, to nearest even
+    codes = torch.where(bad[..., None], torch.zeros_like(codes), codes).reshape(rows, K)
+    scales = torch.where(bad, torch.full_like(e, 255), e + 127).to(torch.uint8)
+    return codes.contiguous(), scales.contiguous()
+
+
+def dequant_mxfp8(codes: torch.Tensor, scales: torch.Tensor) -> torch.Tensor:
+    """MXFP8 (codes uint8 [rows, K], scales uint8 [rows, K/32], canonical layout) -> float64 [rows, K]
+    (exact; NaN where the block's scale code is 255)."""
+    rows, K = codes.shape
+    v = codes.contiguous().view(torch.float8_e4m3fn).to(torch.float64)
+    s = e8m0_decode(scales)
+    return (v.reshape(rows, -1, MXFP4_BLOCK) * s[..., None]).reshape(rows, K)

@@ -50,7 +50,7 @@ class QShape:
     a_bits: int = 16
     gsize: int = -1
     sym: bool = True
-    fmt: str = ""  # "" | "E4M3" | "bf16" | "MXFP4" (written to JSON only when set: reference files are unchanged)
+    fmt: str = ""  # "" | "E4M3" | "bf16" | "MXFP4" | "MXFP8" (written to JSON only when set: reference files are unchanged)
 
     @property
     def M(self) -> int:
@@ -69,7 +69,7 @@ class QShape:
         if self.w_bits == 16 and self.a_bits == 16:
             return "bf16" if self.fmt == "bf16" else "fp16"
         return f"w{self.w_bits}a{self.a_bits}_g{self.gsize}_{'sym' if self.sym else 'asym'}" + \
-            ("_E4M3" if self.fmt == "E4M3" else "_MXFP4" if self.fmt == "MXFP4" else "")
+            ("_E4M3" if self.fmt == "E4M3" else "_MXFP4" if self.fmt == "MXFP4" else "_MXFP8" if self.fmt == "MXFP8" else "")
 
     @property
     def flops(self) -> int:
@@ -90,7 +90,7 @@ class QShape:
 
 def parse_qstr(qstr: str) -> dict:
     """gen_workload.py:51-57; also the SUPPORTED_QCFG forms that reference parser cannot read
-    (``bf16``, ``fp16[_accfp16]``, ``..._E4M3``, ``w4a4_g32_sym_MXFP4``, ``w4a16_g32_sym_MXFP4``; ``_accfp16`` runs as its f32-accumulating base)."""
+    (``bf16``, ``fp16[_accfp16]``, ``..._E4M3``, ``w4a4_g32_sym_MXFP4``, ``w4a16_g32_sym_MXFP4``, ``w4a8_g32_sym_MXFP8``; ``_accfp16`` runs as its f32-accumulating base)."""
     if qstr in ("fp16", "fp16_accfp16", "bf16"):
         d = dict(FP16_QCFG)
         if qstr == "bf16":
@@ -106,6 +106,8 @@ def parse_qstr(qstr: str) -> dict:
         d["fmt"] = "E4M3"
     if qstr.endswith("_MXFP4"):
         d["fmt"] = "MXFP4"
+    if qstr.endswith("_MXFP8"):
+        d["fmt"] = "MXFP8"
     return d
 
 

@@ -12,6 +12,12 @@ kernel (wo3) and onto v2x, against w4a16_g-1_sym through AUTO (the same kernels,
 w4a4_g32_sym_MXFP4 on v2x (the same weights, 4-bit activations); ratios are to the first side.
 
 python tools/mxfp4_bench.py --set a16 --bs 128,512,2048,8192 --out profiles/r09/mxfp4_a16/bench.json
+
+--set a8: w4a8_g32_sym_MXFP8 (MXFP8 activations on the same weights) — through AUTO, forced onto wo3 and
+onto v2x (one of the two is AUTO's choice, the other "the other kernel"), against w4a4_g32_sym_MXFP4 on
+v2x, w8a8_g-1_sym and w4a4_g-1_sym through AUTO; ratios are to the first side.
+
+python tools/mxfp4_bench.py --set a8 --bs 128,512,2048,8192 --out profiles/r11/mxfp8_a8/bench.json
 """
 from __future__ import annotations
 
@@ -34,7 +40,10 @@ from mxmoe_amd.workload import load_workload, qwen2_layer11_workload  # noqa: E4
 SETS = {"a4": {"mxfp4": ("w4a4_g32_sym_MXFP4", None), "w4a4": ("w4a4_g-1_sym", None), "w8a8": ("w8a8_g-1_sym", None)},
         "a16": {"a16": ("w4a16_g32_sym_MXFP4", None), "a16_wo3": ("w4a16_g32_sym_MXFP4", "wo3_64x256_w8_3wg"),
                 "a16_v2x": ("w4a16_g32_sym_MXFP4", "v2x_256x256_w8_b3_buf_spread_edma"),
-                "w4a16": ("w4a16_g-1_sym", None), "mxfp4": ("w4a4_g32_sym_MXFP4", None)}}
+                "w4a16": ("w4a16_g-1_sym", None), "mxfp4": ("w4a4_g32_sym_MXFP4", None)},
+        "a8": {"a8": ("w4a8_g32_sym_MXFP8", None), "a8_wo3": ("w4a8_g32_sym_MXFP8", "wo3_64x256_w8_3wg"),
+               "a8_v2x": ("w4a8_g32_sym_MXFP8", "v2x_256x256_w8_b3_buf_spread_edma"),
+               "mxfp4": ("w4a4_g32_sym_MXFP4", None), "w8a8": ("w8a8_g-1_sym", None), "w4a4": ("w4a4_g-1_sym", None)}}
 
 
 def main():
