@@ -13,6 +13,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <array>
 #include <cstdarg>
 #include <cstdlib>
 #include <cstdio>
@@ -56,443 +57,475 @@ int fail(int code, const char* fmt, ...) {
     if (e_ != hipSuccess) return fail(MXMOE_GG_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
   } while (0)
 
-// Planner A/B switches (MXMOE_GG_BAND, _REGION, _REGION_ROT, _ALIGN, _TAIL_CHUNK, _XCD_RR) are
-// read only by the tools-only lab build (-DMXMOE_LAB, libmxmoe_gg_lab.so): the product library's
-// tile placement never depends on the caller's environment.
-const char* planner_knob(const char* name) {
-#ifdef MXMOE_LAB
-  return getenv(name);
-#else
-  (void)name;
-  return nullptr;
-#endif
-}
+// the small-batch weight-only tile's loop options (gg_tile_wo)
+constexpr int kWo3 = WO_SCLATE | WO_ANDOR | WO_MSKIP | WO_SPLIT | WO_NIBPOS;
+// the round-3 AUTO default's mainloop flags (variant v2x_256x256_w8_b3_buf_spread_edma, without the
+// weight-only options)
+constexpr int kV2x = V2_STAGGER | V2_B3 | V2_BUF | V2_EARLYDMA | (4 << V2_SPREAD_SHIFT);
+[[maybe_unused]] constexpr int kV2xProduct = kV2x | WO_PIPE | WO_STAG | V2_I4NOPAIR | V2_I4EDMA;
+[[maybe_unused]] constexpr int kWo3Product = kWo3 | WO_PCH;
 
 struct TileGeom {
   int bm, bn, bkb, threads;
 };
+
+// AUTO policy: v2x (the staggered 256x256 v2 on v2s3's LDS image with the buffer-form, spread
+// LDS-DMA) for every call with fp16 / bf16 / w8a8 / E4M3 / weight-only problems: same-run A/B on the
+// qwen2_moe layer-11 calls, +5-11 % over v2s and +3-9 % over v2s3 at every K (the round-1/2 short-K
+// rule between those two is gone: profiles/r03/lab/). int4-only sets run 256x128 tiles, 2 WG/CU
+// (v3), unless they are low-fill enough to need split-K (v2 kernels only).
+constexpr const char* kDefaultVariantName = "v2x_256x256_w8_b3_buf_spread_edma";
+constexpr const char* kInt4Variant = "v3_256x128_w4_dma_ring3_2wg";
+constexpr const char* kWoSmallVariant = "wo3_64x256_w8_3wg";
+constexpr const char* kF6Variant = "f6_256x256_w8_ring3";  // (lab library)
+// weight-only calls whose rows per weight byte are this small or smaller run kWoSmallVariant:
+// the weight-bytes-weighted mean M over the call's problems (qwen2_moe layer 11: ~60 at bs = 128,
+// ~250 at bs = 2048, ~1030 at bs = 8192, where v2x's 256-row tiles are as fast or faster)
+constexpr double kWoSmallMeanRows = 512.0;
+// calls of fp16 / w8a8 / w4a4 problems only (no weight-only one) take wo3 below a mean M of
+// kSmallMeanRows (kSmallMeanRowsI4 with int4 problems), twice that when the call is K-skewed (its
+// longest K >= 2x the weighted mean K: the qwen2_moe down call, whose shared expert has 4x the
+// routed K — few long tiles the general kernels balance poorly). Measured on qwen2_moe layer 11
+// (mean M ~ bs / 8; profiles/r03/wo2/wo3_fp16_w8a8.jsonl, wo3_w4a4_mixed.jsonl, wo3_mid.jsonl):
+// gate_up wins to bs 512 (fp16 -3.5 .. w4a4 +33 %) and 768 with int4, down calls to bs 1024 (fp16)
+// / 1536 (int4), the general kernels beyond.
+constexpr double kSmallMeanRows = 80.0;
+constexpr double kSmallMeanRowsI4 = 112.0;
+// calls with a w4a8_g32_sym_MXFP8 problem (and no weight-only one): the int4 cut
+constexpr double kSmallMeanRowsMx8 = 112.0;
+constexpr double kSplitCUs = 256.0;  // MI355X compute units: the planner's notion of "one CU's share"
+
+// What AUTO does with a call that has a problem of the type (resolve_variant):
+//   General    v2x;
+//   WeightOnly the small-batch kernel (kWoSmallVariant) up to a mean M of auto_rows, v2x beyond;
+//   Small      may ride on the small-batch kernel: a call of Small types only takes it up to the
+//              largest auto_rows among them (x 2 when K-skewed), beside a weight-only problem up to that one's;
+//   Alone      cannot share a call: a kernel of its own (auto_alone).
+enum class AutoClass { General, WeightOnly, Small, Alone };
+
+// Everything the host knows about a quant type, one row per QType.
+struct QTypeInfo {
+  int qt;                    // the row's QType
+  const char* name;          // mxmoe_gg_list_variants (weight-only: every group size / sym of a bit width under the base name)
+  int staged_bits;           // bits per K element of a staged row (the listing's BK = bkb * 8 / staged_bits)
+  bool weight_only;          // fp16 A on quantised B (gg_tile_wo; validated by build_meta_weightonly)
+  bool float16;              // 16-bit operands, no scales
+  const char* dword_scales;  // block scales the kernel reads as dwords (4-byte aligned): what the error calls them
+  int k_mult;                // K granularity of its own, beyond 16-byte rows (0 = none), what the error calls the type,
+  const char* k_what;        // and whether the rule is checked before the row rule
+  bool k_first;
+  bool group_fold;           // k_mult-element scale groups folded in f32: GGMeta::reserved counts them, and the
+                             // type never splits K (summing f32 partial folds would change the rounding)
+  bool int32_bound;          // exact int32 accumulation: K <= 131072
+  bool silu;                 // its tile body carries the fused SiLU epilogue (weight-only: Variant::silu_wo kernels)
+  bool small_class;          // takes the 64-row class (Variant::tail2_bm)
+  // cost model (full_tile_cost, stage_time)
+  double passes;             // MFMA passes per staged byte: int4 2; g128 adds the per-group f32 fold (~25 %); fp6 images: one
+                             // fp6 MFMA (the int8 one's cycles) per 96 B of K-128; MXFP4: the int8 tile's count and cycles, so 1
+  int el_bits;               // K elements per stage = bkb * 8 / el_bits (0: 128, the fp6 images' K-128 blocks)
+  double rate;               // MFMA flop per LDS byte-time, fp16 = 128
+  double fold;               // per-group f32 fold on top of the MFMAs
+  int code_bits;             // weight-only: bits per staged B code (MXFP4: its 2 scale bytes per column are 1/16 of the codes)
+  AutoClass auto_class;
+  double auto_rows;          // WeightOnly / Small: the mean-M limit of the small-batch kernel
+  const char* auto_alone;    // the variant AUTO takes for a call of this type only (Small: unless it splits K)
+  bool auto_counts_empty;    // an empty problem still counts for AUTO (only v2x plans the type; types are checked before shapes)
+};
+constexpr AutoClass kGen = AutoClass::General, kWo = AutoClass::WeightOnly, kSm = AutoClass::Small;
+constexpr QTypeInfo kQTypes[] = {
+    // qt, name, bits | wo, f16 | dword scales | K rule | fold, i32, silu, 64-row | passes, el, rate, fold, code | AUTO
+    {QT_F16, "fp16", 16, false, true, nullptr, 0, nullptr, false, false, false, true, true,
+     1.0, 16, 128, 1.0, 0, kSm, kSmallMeanRows, nullptr, false},
+    {QT_I8, "w8a8_g-1_sym", 8, false, false, nullptr, 0, nullptr, false, false, true, true, false,
+     1.0, 8, 256, 1.0, 0, kSm, kSmallMeanRows, nullptr, false},
+    {QT_I4, "w4a4_g-1_sym", 4, false, false, nullptr, 0, nullptr, false, false, true, true, false,
+     2.0, 4, 256, 1.0, 0, kSm, kSmallMeanRowsI4, kInt4Variant, false},
+    {QT_W4A16, "w4a16", 4, true, false, nullptr, 0, nullptr, false, false, false, true, true,
+     1.0, 0, 0, 1.0, 4, kWo, kWoSmallMeanRows, nullptr, false},
+    {QT_W8A16, "w8a16", 8, true, false, nullptr, 0, nullptr, false, false, false, true, true,
+     1.0, 0, 0, 1.0, 8, kWo, kWoSmallMeanRows, nullptr, false},
+    {QT_I4G, "w4a4_g128_sym", 4, false, false, nullptr, 128, "w4a4_g128", false, true, true, false, false,
+     2.5, 4, 256, 1.25, 0, kGen, 0, nullptr, false},
+    {QT_W2A16, "w2a16", 2, true, false, nullptr, 0, nullptr, false, false, false, true, true,
+     1.0, 0, 0, 1.0, 2, kWo, kWoSmallMeanRows, nullptr, false},
+    {QT_F8, "w8a8_g-1_sym_E4M3", 8, false, false, nullptr, 0, nullptr, false, false, false, false, false,
+     1.0, 8, 256, 1.0, 0, kGen, 0, nullptr, false},
+    {QT_BF16, "bf16", 16, false, true, nullptr, 0, nullptr, false, false, false, false, true,
+     1.0, 16, 128, 1.0, 0, kGen, 0, nullptr, false},
+    {QT_I4F6, "w4a4_g-1_sym_F6", 6, false, false, nullptr, 0, nullptr, false, false, true, false, false,
+     128.0 / 96 / 2, 0, 512, 1.0, 0, AutoClass::Alone, 0, kF6Variant, false},
+    {QT_MXF4, "w4a4_g32_sym_MXFP4", 4, false, false, "MXFP4", 0, nullptr, false, false, false, false, false,
+     1.0, 4, 512, 1.0, 0, kGen, 0, nullptr, true},
+    {QT_MXF4W, "w4a16_g32_sym_MXFP4", 4, true, false, "MXFP4", 0, nullptr, false, false, false, true, true,
+     1.0, 0, 0, 1.0, 4, kWo, kWoSmallMeanRows, nullptr, false},
+    {QT_MXF8A, "w4a8_g32_sym_MXFP8", 8, false, false, "w4a8_g32_sym_MXFP8", 32, "w4a8_g32_sym_MXFP8", true, false,
+     false, true, false, 1.0, 8, 256, 1.0, 0, kSm, kSmallMeanRowsMx8, nullptr, false},
+};
+constexpr bool qtypes_in_order() {
+  for (int i = 0; i < QT_COUNT; ++i)
+    if (kQTypes[i].qt != i) return false;
+  return true;
+}
+static_assert(sizeof(kQTypes) / sizeof(kQTypes[0]) == QT_COUNT, "one row per QType");
+static_assert(qtypes_in_order(), "row i describes QType i");
+constexpr const QTypeInfo& qinfo(int qt) { return kQTypes[qt]; }
+constexpr int auto_mask(AutoClass c) {  // 1 << QType of the class's types
+  int m = 0;
+  for (const QTypeInfo& t : kQTypes)
+    if (t.auto_class == c) m |= 1 << t.qt;
+  return m;
+}
+
+// One compiled kernel of a variant's family: the tile bodies of the quant types in `qmask`.
+struct Build {
+  int qmask;      // 1 << QType it has a body for (wo2: | kQmaskWoSilu, a WO_SILU build)
+  bool fallback;  // also runs any subset of qmask no entry matches exactly
+  int lds_bytes;  // reported in the plan info
+  void (*launch)(const GGArgs&, int grid, hipStream_t);
+};
+template <size_t N>
+using Builds = std::array<Build, N>;
+template <size_t A, size_t B>
+constexpr Builds<A + B> operator+(const Builds<A>& a, const Builds<B>& b) {
+  Builds<A + B> r{};
+  for (size_t i = 0; i < A + B; ++i) r[i] = i < A ? a[i] : b[i - A];
+  return r;
+}
+struct BuildTable {
+  const Build* rows;
+  int n;
+};
+template <size_t N>
+constexpr BuildTable table_of(const Builds<N>& b) { return {b.data(), (int)N}; }
+// The build a quant-type set (`key`: the call's mask, cut to the bits the family looks at) launches:
+// the entry with that mask, else the first fallback — they are listed narrowest first — that has every
+// type of the call the fallbacks know at all. -1: not compiled (the lab tables).
+constexpr int pick_build(BuildTable t, int key) {
+  int known = 0;
+  for (int i = 0; i < t.n; ++i) {
+    if (t.rows[i].qmask == key) return i;
+    if (t.rows[i].fallback) known |= t.rows[i].qmask;
+  }
+  for (int i = 0; i < t.n; ++i)
+    if (t.rows[i].fallback && (key & known & ~t.rows[i].qmask) == 0) return i;
+  return -1;
+}
+constexpr bool exact_entries_pick_themselves(BuildTable t, int (*pick)(int)) {
+  for (int i = 0; i < t.n; ++i)
+    if (t.rows[pick(t.rows[i].qmask)].qmask != t.rows[i].qmask) return false;
+  return true;
+}
+template <auto Kernel, int THREADS>
+void launch_k(const GGArgs& a, int grid, hipStream_t s) {
+  hipLaunchKernelGGL(Kernel, dim3(grid), dim3(THREADS), 0, s, a);
+}
 
 enum class Kind { V0, V2, V3 };  // (the fp6 kernel is planned as V3: no split-K, no XCD regions)
 
 struct Variant {
   const char* name;
   Kind kind;
-  TileGeom geom[QT_COUNT];  // indexed by QType (main tile)
+  TileGeom geom[QT_COUNT] = {};  // indexed by QType (main tile); bn == 0: no tile body for the type. Every
+                                 // make_* below sets the types its kernel has one for
   int threads;
-  int lds_bytes;
+  int lds_bytes;       // the family's LDS image (a build's own: Build::lds_bytes)
   int chunk;           // tiles per XCD chunk (workgroups that run together on one XCD)
-  int k_stage_bytes;   // K bytes per row must be a multiple of this (0 = any multiple of 16)
-  int tail_bm;         // v2: height of the tail-tile class (0 = none)
+  int k_stage_bytes = 0;  // K bytes per row must be a multiple of this (0 = any multiple of 16; v2: K tails are
+                          // handled in-kernel, fp6 image rows are whole stages by construction)
+  int tail_bm = 0;     // v2: height of the tail-tile class (0 = none)
   int tail2_bm = 0;    // v2: height of the small-remainder class (0 = none)
   bool persistent = false;  // v2p / v2q: a workgroup walks a planned tile list
   bool silu_epi = false;    // the fp16 / w8a8 / w4a4 tile bodies carry the fused SiLU epilogue
   bool silu_wo = false;     // ... and its weight-only tiles (wo2: the WO_SILU builds)
   int persist_len = 0;      // v2q: 0 = one list per CU (static); L > 0 = lists of L consecutive XCD-queue
                             // tiles, one per block, the hardware dispatching blocks as CUs free up
-  int (*lds_of)(int qmask) = nullptr;  // LDS of the build a quant-type set launches (default lds_bytes)
-  void (*launch)(const GGArgs&, int grid, int qmask, hipStream_t);  // qmask: 1 << QType present
+  BuildTable builds;        // the family's compiled kernels
+  int (*pick)(int qmask);   // index in `builds` of the one a plan's quant-type set (1 << QType present,
+                            // kQmaskWoSilu) launches: the launch and the plan info's LDS size both use it
 };
+Variant variant_base(const char* name, Kind kind, int threads, int lds_bytes, int chunk, int tail_bm, BuildTable builds,
+                     int (*pick)(int)) {
+  Variant v;
+  v.name = name, v.kind = kind, v.threads = threads, v.lds_bytes = lds_bytes, v.chunk = chunk, v.tail_bm = tail_bm;
+  v.builds = builds, v.pick = pick;
+  return v;
+}
+constexpr int pick_only(int) { return 0; }  // (families of one build)
+
+[[maybe_unused]] constexpr int kMx4 = 1 << QT_MXF4;   // w4a4_g32_sym_MXFP4
+[[maybe_unused]] constexpr int kMxW = 1 << QT_MXF4W;  // weight-only MXFP4
+[[maybe_unused]] constexpr int kMx8 = 1 << QT_MXF8A;  // w4a8_g32_sym_MXFP8 (gg_tile_v2's 64 x 128 body)
+// plan-info qtype_mask bit: a weight-only problem carries MXMOE_GG_EPI_SILU_MUL (selects the WO_SILU
+// builds of wo2)
+constexpr int kQmaskWoSilu = 1 << 16;
+// the MX types have tile bodies in the product library's v2 / wo2 build tables only
+#ifdef MXMOE_LAB
+constexpr bool kMxBodies = false;
+#else
+constexpr bool kMxBodies = true;
+#endif
 
 template <class C16, class C8, class C4>
-void launch_v0(const GGArgs& a, int grid, int qmask, hipStream_t s) {
-  hipLaunchKernelGGL((gg_fused_kernel<C16, C8, C4>), dim3(grid), dim3(C16::kThreads), 0, s, a);
-}
-
-template <int ABL, int QM>
-void launch_v2_q(const GGArgs& a, int grid, hipStream_t s) {
-  hipLaunchKernelGGL((gg_v2_kernel<ABL, QM>), dim3(grid), dim3(512), 0, s, a);
-}
-template <int ABL>
-void launch_v2(const GGArgs& a, int grid, int qmask, hipStream_t s) {
-  if constexpr ((ABL & kAblMask) != 0) {
-    launch_v2_q<ABL, 7>(a, grid, s);
-  } else if constexpr ((ABL & kWoAblMask) != 0) {
-    launch_v2_q<ABL, 8>(a, grid, s);  // weight-only ablations: w4a16 tiles only
-  } else {
-#if defined(MXMOE_LAB) && defined(MXMOE_LAB_FAST)
-    switch (qmask & 511) {
-      case 1: launch_v2_q<ABL, 1>(a, grid, s); break;
-      case 2: launch_v2_q<ABL, 2>(a, grid, s); break;
-      case 8: launch_v2_q<ABL, 8>(a, grid, s); break;
-      default:
-        fprintf(stderr, "libmxmoe_gg_lab (fast): quant-type mix %#x not compiled\n", qmask);
-        abort();
-    }
-#elif defined(MXMOE_LAB)
-    // lab build: fp16, w8a8, w4a4, w8a8 + w4a4 (LP-1 mixed), w4a16, bf16 only (fast builds)
-    switch (qmask & 511) {
-      case 1: launch_v2_q<ABL, 1>(a, grid, s); break;
-      case 2: launch_v2_q<ABL, 2>(a, grid, s); break;
-      case 4: launch_v2_q<ABL, 4>(a, grid, s); break;
-      case 6: launch_v2_q<ABL, 6>(a, grid, s); break;
-      case 8: launch_v2_q<ABL, 8>(a, grid, s); break;
-      case 128: launch_v2_q<ABL, 128>(a, grid, s); break;
-      case 256: launch_v2_q<ABL, 256>(a, grid, s); break;
-      default:
-        fprintf(stderr, "libmxmoe_gg_lab: quant-type mix %#x not compiled in the lab build\n", qmask);
-        abort();
-    }
-#else
-    // MXFP4 problems (plan-info bit 10, above the mask below): a kernel of their own, or every tile
-    // body beside them — builds apart from the existing ones, which come out unchanged
-    // (weight-only MXFP4, bit 11, likewise: alone, or the widest build with every body)
-    // (w4a8_g32_sym_MXFP8, bit 12: alone in a build of its own — a ring of three K = 128 stages in the
-    // variant's LDS image — or the every-body build with it)
-    if (qmask & (1 << QT_MXF8A)) {
-      if ((qmask & 8191) == (1 << QT_MXF8A)) launch_v2_q<ABL, (1 << QT_MXF8A)>(a, grid, s);
-      else launch_v2_q<0, 511 | (1 << QT_MXF4) | (1 << QT_MXF4W) | (1 << QT_MXF8A)>(a, grid, s);
-      return;
-    }
-    if (qmask & ((1 << QT_MXF4) | (1 << QT_MXF4W))) {
-      if ((qmask & 8191) == (1 << QT_MXF4)) launch_v2_q<ABL, (1 << QT_MXF4)>(a, grid, s);
-      else if ((qmask & 8191) == (1 << QT_MXF4W)) launch_v2_q<ABL, (1 << QT_MXF4W)>(a, grid, s);
-      else if (!(qmask & (1 << QT_MXF4W))) launch_v2_q<0, 511 | (1 << QT_MXF4)>(a, grid, s);
-      else launch_v2_q<0, 511 | (1 << QT_MXF4) | (1 << QT_MXF4W)>(a, grid, s);
-      return;
-    }
-    switch (qmask & 511) {
-      case 1: launch_v2_q<ABL, 1>(a, grid, s); break;
-      case 2: launch_v2_q<ABL, 2>(a, grid, s); break;
-      case 4: launch_v2_q<ABL, 4>(a, grid, s); break;
-      case 6: launch_v2_q<ABL, 6>(a, grid, s); break;
-      case 7: launch_v2_q<ABL, 7>(a, grid, s); break;
-      case 8: launch_v2_q<ABL, 8>(a, grid, s); break;    // w4a16 only
-      case 10: launch_v2_q<ABL, 10>(a, grid, s); break;  // w4a16 + w8a8 (the reference's hz_fused pairing)
-      case 16: launch_v2_q<ABL, 16>(a, grid, s); break;  // w8a16 only
-      case 32: launch_v2_q<ABL, 32>(a, grid, s); break;  // w4a4 g128 only
-      case 64: launch_v2_q<ABL, 64>(a, grid, s); break;  // w2a16 only
-      case 128: launch_v2_q<ABL, 128>(a, grid, s); break;  // w8a8 E4M3 only
-      case 256: launch_v2_q<ABL, 256>(a, grid, s); break;  // bf16 only
-      // any other mix: every tile body in one kernel. The staggered int bodies leave no register
-      // room for that (the compiler spilled inside their K loops), so the fallback is plain v2;
-      // the 2-bit weight-only body only joins it when the mix has one (it costs 12 B of prologue
-      // spill there, tests/test_codegen.py)
-      default:
-        if (qmask & ((1 << QT_F8) | (1 << QT_BF16))) launch_v2_q<0, 511>(a, grid, s);
-        else if (qmask & (1 << QT_W2A16)) launch_v2_q<0, 127>(a, grid, s);
-        else launch_v2_q<0, 63>(a, grid, s);
-        break;
-    }
-#endif
-  }
-}
-
-// v3 is specialised on the set of quant types the plan contains (mask 1 << QType)
-template <int BN, int WN, int NBUF, int DIST, int QM, int OPT>
-void launch_v3_q(const GGArgs& a, int grid, hipStream_t s) {
-  hipLaunchKernelGGL((gg_v3_kernel<BN, WN, NBUF, DIST, QM, OPT>), dim3(grid), dim3(V3Cfg<256, BN, WN>::NT), 0, s, a);
-}
-template <int BN, int WN, int NBUF, int DIST, int OPT = 0>
-void launch_v3(const GGArgs& a, int grid, int qmask, hipStream_t s) {
-  switch (qmask & 7) {
-    case 1: launch_v3_q<BN, WN, NBUF, DIST, 1, OPT>(a, grid, s); break;
-    case 2: launch_v3_q<BN, WN, NBUF, DIST, 2, OPT>(a, grid, s); break;
-    case 4: launch_v3_q<BN, WN, NBUF, DIST, 4, OPT>(a, grid, s); break;
-    case 6: launch_v3_q<BN, WN, NBUF, DIST, 6, OPT>(a, grid, s); break;
-    default: launch_v3_q<BN, WN, NBUF, DIST, 7, OPT>(a, grid, s); break;
-  }
-}
-
-template <int QM, int TRACE>
-void launch_v2p_q(const GGArgs& a, int grid, hipStream_t s) {
-  hipLaunchKernelGGL((gg_v2p_kernel<QM, TRACE>), dim3(grid), dim3(512), 0, s, a);
-}
-template <int TRACE = 0>
-void launch_v2p(const GGArgs& a, int grid, int qmask, hipStream_t s) {
-  switch (qmask & 511) {
-    case 1: launch_v2p_q<1, TRACE>(a, grid, s); break;
-    case 2: launch_v2p_q<2, TRACE>(a, grid, s); break;
-    case 256: launch_v2p_q<256, TRACE>(a, grid, s); break;
-    default: launch_v2p_q<511, TRACE>(a, grid, s); break;  // every tile body
-  }
-}
-
-#ifdef MXMOE_LAB
-template <int QM, int TRACE, int SAUX, int FILLALL>
-void launch_v2q_q(const GGArgs& a, int grid, hipStream_t s) {
-  hipLaunchKernelGGL((gg_v2q_kernel<QM, TRACE, SAUX, FILLALL>), dim3(grid), dim3(512), 0, s, a);
-}
-template <int TRACE = 0, int SAUX = 16, int FILLALL = 0>
-void launch_v2q(const GGArgs& a, int grid, int qmask, hipStream_t s) {
-  switch (qmask & 511) {
-    case 1: launch_v2q_q<1, TRACE, SAUX, FILLALL>(a, grid, s); break;
-    case 2: launch_v2q_q<2, TRACE, SAUX, FILLALL>(a, grid, s); break;
-#ifndef MXMOE_LAB_FAST
-    case 4: launch_v2q_q<4, TRACE, SAUX, FILLALL>(a, grid, s); break;
-    case 6: launch_v2q_q<6, TRACE, SAUX, FILLALL>(a, grid, s); break;
-    case 256: launch_v2q_q<256, TRACE, SAUX, FILLALL>(a, grid, s); break;
-    default: launch_v2q_q<511, TRACE, SAUX, FILLALL>(a, grid, s); break;  // every tile body
-#else
-    default:
-      fprintf(stderr, "libmxmoe_gg_lab (fast): v2q quant-type mix %#x not compiled\n", qmask);
-      abort();
-#endif
-  }
-}
-
-#endif  // MXMOE_LAB
-
-template <int ABL, int QM, int NWG>
-void launch_wo2_q(const GGArgs& a, int grid, hipStream_t s) {
-  hipLaunchKernelGGL((gg_wo2_kernel<ABL, QM, NWG>), dim3(grid), dim3(512), 0, s, a);
-}
-// quant-type sets launched at the variant's NWG (the rest, with 8-bit weight-only problems, run the
-// 2-WG/CU build): keep in step with the switch below
-constexpr int kQmaskMxW = 1 << QT_MXF4W;  // weight-only MXFP4 (above the 9 bits the switches below see)
-constexpr int kQmaskMx8 = 1 << QT_MXF8A;  // w4a8_g32_sym_MXFP8 (gg_tile_v2's 64 x 128 body)
-constexpr int kWo2Types = 511 | kQmaskMxW | kQmaskMx8;
-constexpr bool wo2_full_nwg(int qm) {
-  return qm == 8 || qm == 64 || qm == 10 || qm == 1 || qm == 2 || qm == 4 || qm == 6 || qm == kQmaskMxW || qm == kQmaskMx8;
-}
-// plan-info qtype_mask bit: a weight-only problem carries MXMOE_GG_EPI_SILU_MUL (selects the WO_SILU
-// build; with it only the w4a16 and w4a16 + w8a8 sets run at the variant's NWG)
-constexpr int kQmaskWoSilu = 1 << 16;
-constexpr bool wo2_full_nwg_silu(int qm) { return qm == 8 || qm == 10 || qm == kQmaskMxW; }
-template <int NWG>
-int wo2_launch_lds(int qmask) {
-  const bool full = (qmask & kQmaskWoSilu) ? wo2_full_nwg_silu(qmask & kWo2Types) : wo2_full_nwg(qmask & kWo2Types);
-  return full ? wo2_lds_bytes<NWG>() : wo2_lds_bytes<2>();
-}
-template <int ABL, int NWG>
-void launch_wo2(const GGArgs& a, int grid, int qmask, hipStream_t s) {
-#ifdef MXMOE_LAB_FAST
-  switch (qmask & 511) {  // fast lab build: the w4a16 and w4a16 + w8a8 sets only
-    case 8: launch_wo2_q<ABL, 8, NWG>(a, grid, s); break;
-    case 10: launch_wo2_q<ABL, 10, NWG>(a, grid, s); break;
-    case 16: launch_wo2_q<ABL, 16, NWG>(a, grid, s); break;  // (lab: w8a16 at the variant's NWG)
-    default:
-      fprintf(stderr, "libmxmoe_gg_lab (fast): wo2 quant-type mix %#x not compiled\n", qmask);
-      abort();
-  }
-#else
-  if (qmask & kQmaskWoSilu) {  // weight-only problems with the fused SiLU epilogue (WO_SILU builds)
-    constexpr int AS = ABL | WO_SILU;
-    if (qmask & kQmaskMx8) {  // (beside weight-only problems with the flag: the widest 2-WG/CU build)
-      launch_wo2_q<AS, 95 | kQmaskMxW | kQmaskMx8, 2>(a, grid, s);
-      return;
-    }
-    if (qmask & kQmaskMxW) {  // weight-only MXFP4: alone at the variant's NWG, else the wide 2-WG/CU build
-      if ((qmask & kWo2Types) == kQmaskMxW) launch_wo2_q<AS, kQmaskMxW, NWG>(a, grid, s);
-      else launch_wo2_q<AS, 95 | kQmaskMxW, 2>(a, grid, s);
-      return;
-    }
-    switch (qmask & 511) {
-      case 8: launch_wo2_q<AS, 8, NWG>(a, grid, s); break;    // w4a16
-      case 10: launch_wo2_q<AS, 10, NWG>(a, grid, s); break;  // w4a16 + w8a8 (any other mix: the wide
-                                                              // 2-WG/CU builds below)
-      case 16: launch_wo2_q<AS, 16, 2>(a, grid, s); break;
-      default: launch_wo2_q<AS, 95, 2>(a, grid, s); break;
-    }
-    return;
-  }
-  if (qmask & kQmaskMx8) {  // w4a8_g32_sym_MXFP8: alone at the variant's NWG, else the wide 2-WG/CU build
-    if ((qmask & kWo2Types) == kQmaskMx8) launch_wo2_q<ABL, kQmaskMx8, NWG>(a, grid, s);
-    else launch_wo2_q<ABL, 95 | kQmaskMxW | kQmaskMx8, 2>(a, grid, s);
-    return;
-  }
-  if (qmask & kQmaskMxW) {
-    if ((qmask & kWo2Types) == kQmaskMxW) launch_wo2_q<ABL, kQmaskMxW, NWG>(a, grid, s);
-    else launch_wo2_q<ABL, 95 | kQmaskMxW, 2>(a, grid, s);
-    return;
-  }
-  switch (qmask & 511) {
-    case 8: launch_wo2_q<ABL, 8, NWG>(a, grid, s); break;    // w4a16 only
-    case 64: launch_wo2_q<ABL, 64, NWG>(a, grid, s); break;  // w2a16 only
-    case 10: launch_wo2_q<ABL, 10, NWG>(a, grid, s); break;  // w4a16 + w8a8 (hz_fused pairing)
-    case 1: launch_wo2_q<ABL, 1, NWG>(a, grid, s); break;    // fp16 only
-    case 2: launch_wo2_q<ABL, 2, NWG>(a, grid, s); break;    // w8a8 only
-    case 4: launch_wo2_q<ABL, 4, NWG>(a, grid, s); break;    // w4a4 only
-    case 6: launch_wo2_q<ABL, 6, NWG>(a, grid, s); break;    // w4a4 + w8a8 (LP-1 mixed)
-    // the 8-bit body does not fit 80 VGPRs (3 workgroups per CU) without spilling: calls with w8a16
-    // problems run the 2-WG/CU build of the same tiles (same plan: placement only assumes more slots)
-    case 16: launch_wo2_q<ABL, 16, 2>(a, grid, s); break;  // w8a16 only
-    default: launch_wo2_q<ABL, 95, 2>(a, grid, s); break;  // any mix of fp16, w8a8, w4a4 and weight-only
-  }
-#endif
-}
-
+constexpr Builds<1> kV0Builds = {{{7, true, FusedCfg<C16, C8, C4>::LDS_BYTES, &launch_k<&gg_fused_kernel<C16, C8, C4>, C16::kThreads>}}};
 template <class C16, class C8, class C4>
 Variant make_v0(const char* name) {
-  Variant v;
-  v.name = name;
-  v.kind = Kind::V0;
+  constexpr int lds = FusedCfg<C16, C8, C4>::LDS_BYTES;
+  Variant v = variant_base(name, Kind::V0, C16::kThreads, lds, lds <= 80 * 1024 ? 64 : 32 /* workgroups per XCD at once */, 0,
+                           table_of(kV0Builds<C16, C8, C4>), &pick_only);
   v.geom[QT_F16] = {C16::BM, C16::BN, C16::BKB, C16::kThreads};
   v.geom[QT_I8] = {C8::BM, C8::BN, C8::BKB, C8::kThreads};
   v.geom[QT_I4] = {C4::BM, C4::BN, C4::BKB, C4::kThreads};
-  for (int q : {QT_W4A16, QT_W8A16, QT_I4G, QT_W2A16, QT_F8, QT_BF16, QT_I4F6, QT_MXF4, QT_MXF4W, QT_MXF8A}) v.geom[q] = {0, 0, 0, 0};  // v2 kernels only
-  v.threads = C16::kThreads;
-  v.lds_bytes = FusedCfg<C16, C8, C4>::LDS_BYTES;
-  v.chunk = FusedCfg<C16, C8, C4>::LDS_BYTES <= 80 * 1024 ? 64 : 32;  // workgroups per XCD at once
-  v.k_stage_bytes = 0;
-  v.tail_bm = 0;
-  v.launch = &launch_v0<C16, C8, C4>;
   return v;
 }
 
+// ---- v2: specialised on the set of quant types the plan contains (QM) and the mainloop flags (ABL)
+template <int ABL>
+constexpr int kV2Lds = (ABL & V2_B3) ? 160 * 1024 : V2Cfg<256>::LDS_BYTES + V2_LDS_EXTRA;
+template <int ABL, int LDS, int... QM>
+constexpr Builds<sizeof...(QM)> v2_rows(bool fallback = false) {
+  return {{Build{QM, fallback, LDS, &launch_k<&gg_v2_kernel<ABL, QM>, 512>}...}};
+}
+// Exact sets run a kernel of the variant's flags: fp16, w8a8, w4a4, w4a4 + w8a8 (LP-1 mixed), all three, w4a16,
+// w4a16 + w8a8 (the reference's hz_fused pairing), w8a16, w4a4 g128, w2a16, E4M3, bf16, and each MX type alone
+// (w4a8_g32_sym_MXFP8: a ring of three K = 128 stages in the variant's LDS image).
+// Any other mix: every tile body in one kernel. The staggered int bodies leave no register
+// room for that (the compiler spilled inside their K loops), so the fallbacks are plain v2 (ABL = 0; the
+// plan info still reports the variant's LDS image); the 2-bit weight-only body only joins when the mix has
+// one (it costs 12 B of prologue spill there, tests/test_codegen.py), the MX bodies likewise — builds apart
+// from the narrower ones, which come out unchanged.
+// (lab builds: fp16, w8a8, w4a4, w8a8 + w4a4, w4a16, E4M3, bf16 only; fast: fp16, w8a8, w4a16)
+template <int ABL>
+constexpr auto kV2Builds =
+#if defined(MXMOE_LAB) && defined(MXMOE_LAB_FAST)
+    v2_rows<ABL, kV2Lds<ABL>, 1, 2, 8>();
+#elif defined(MXMOE_LAB)
+    v2_rows<ABL, kV2Lds<ABL>, 1, 2, 4, 6, 8, 128, 256>();
+#else
+    v2_rows<ABL, kV2Lds<ABL>, 1, 2, 4, 6, 7, 8, 10, 16, 32, 64, 128, 256, kMx4, kMxW, kMx8>() +
+    v2_rows<0, kV2Lds<ABL>, 63, 127, 511, 511 | kMx4, 511 | kMx4 | kMxW, 511 | kMx4 | kMxW | kMx8>(true);
+#endif
+// timing ablations: int8 tiles only (kAblMask) / w4a16 tiles only (kWoAblMask), whatever the call holds
+template <int ABL>
+constexpr auto kV2AblBuilds = v2_rows<ABL, kV2Lds<ABL>, (ABL & kAblMask) ? 7 : 8>(true);
+template <int ABL>
+constexpr BuildTable v2_builds() {
+  if constexpr ((ABL & (kAblMask | kWoAblMask)) != 0) return table_of(kV2AblBuilds<ABL>);
+  else return table_of(kV2Builds<ABL>);
+}
+template <int ABL>
+constexpr int pick_v2(int qmask) {
+#ifdef MXMOE_LAB
+  return pick_build(v2_builds<ABL>(), qmask & 511);
+#else
+  // (all 13 type bits beside an MX type, the low 9 otherwise: the only other bit is the lab's fp6 type, which no
+  // product variant plans)
+  return pick_build(v2_builds<ABL>(), qmask & ((qmask & (kMx4 | kMxW | kMx8)) ? 8191 : 511));
+#endif
+}
+#ifndef MXMOE_LAB
+static_assert(exact_entries_pick_themselves(v2_builds<kV2xProduct>(), &pick_v2<kV2xProduct>));
+constexpr const Build& v2x_picked(int qmask) { return kV2Builds<kV2xProduct>[pick_v2<kV2xProduct>(qmask)]; }
+static_assert(v2x_picked(2).launch == &launch_k<&gg_v2_kernel<kV2xProduct, 2>, 512>);  // exact: the variant's flags
+static_assert(v2x_picked(3).launch == &launch_k<&gg_v2_kernel<0, 63>, 512>);           // fallback: plain v2
+static_assert(v2x_picked((1 << QT_F16) | (1 << QT_I4G)).qmask == 63 && v2x_picked((1 << QT_W2A16) | (1 << QT_I8)).qmask == 127);
+static_assert(v2x_picked((1 << QT_I8) | (1 << QT_F8)).qmask == 511 && v2x_picked((1 << QT_BF16) | (1 << QT_W2A16)).qmask == 511);
+static_assert(v2x_picked(kMx4 | (1 << QT_F16)).qmask == (511 | kMx4) && v2x_picked(kMx4 | kMxW).qmask == (511 | kMx4 | kMxW));
+static_assert(v2x_picked(kMxW | (1 << QT_I8)).qmask == (511 | kMx4 | kMxW));
+static_assert(v2x_picked(kMx8 | (1 << QT_W4A16)).qmask == (511 | kMx4 | kMxW | kMx8) && v2x_picked(kMx8 | kMx4).qmask == v2x_picked(8191).qmask);
+#endif
+
+// the v2 family's plan parameters: 256 x 256 tiles + 128 / 64-row classes, one 512-thread workgroup per CU (32 CUs
+// per XCD); the 64-row class takes <= 64 remaining rows of fp16 / weight-only problems (small batches)
+Variant v2_base(const char* name, int lds_bytes, BuildTable builds, int (*pick)(int), int threads = 512) {
+  Variant v = variant_base(name, Kind::V2, threads, lds_bytes, 32, 128, builds, pick);
+  v.tail2_bm = 64;
+  return v;
+}
+// gg_v2_kernel's tile bodies (mx: the MX types' too)
+void set_v2_geom(Variant* v, bool mx) {
+  // (w4a4 g128, gg_tile_g128: 256 / 128-row classes as int4)
+  for (int q : {QT_F16, QT_I8, QT_I4, QT_I4G, QT_F8, QT_BF16}) v->geom[q] = {256, 256, 128, 512};
+  v->geom[QT_W4A16] = {256, 256, 32, 512};  // 64-K stages: 32 B of 4-bit codes per row
+  v->geom[QT_W8A16] = {256, 256, 64, 512};
+  v->geom[QT_W2A16] = {256, 256, 16, 512};  // 64-K stages: 16 B of 2-bit codes per row
+  if (mx) {
+    v->geom[QT_MXF4] = v->geom[QT_MXF8A] = {256, 256, 128, 512};
+    v->geom[QT_MXF4W] = {256, 256, 32, 512};  // weight-only MXFP4: the 4-bit stage
+  }
+}
+template <int ABL = 0>
+Variant make_v2(const char* name) {
+  Variant v = v2_base(name, kV2Lds<ABL>, v2_builds<ABL>(), &pick_v2<ABL>);
+  set_v2_geom(&v, kMxBodies);
+  v.silu_epi = true;  // gg_tile_v2's epilogue
+  return v;
+}
+
+// ---- v3: fp16 / w8a8 / w4a4, specialised on the set the plan contains
+template <int BN, int WN, int NBUF, int DIST, int OPT, int... QM>
+constexpr Builds<sizeof...(QM)> v3_rows(bool fallback = false) {
+  return {{Build{QM, fallback, V3Cfg<256, BN, WN, NBUF, DIST>::LDS_BYTES,
+                 &launch_k<&gg_v3_kernel<BN, WN, NBUF, DIST, QM, OPT>, V3Cfg<256, BN, WN>::NT>}...}};
+}
+template <int BN, int WN, int NBUF, int DIST, int OPT>
+constexpr auto kV3Builds = v3_rows<BN, WN, NBUF, DIST, OPT, 1, 2, 4, 6>() + v3_rows<BN, WN, NBUF, DIST, OPT, 7>(true);
+template <int BN, int WN, int NBUF, int DIST, int OPT>
+constexpr int pick_v3(int qmask) { return pick_build(table_of(kV3Builds<BN, WN, NBUF, DIST, OPT>), qmask & 7); }
+static_assert(exact_entries_pick_themselves(table_of(kV3Builds<128, 2, 3, 2, 0>), &pick_v3<128, 2, 3, 2, 0>));
+static_assert(pick_v3<128, 2, 3, 2, 0>(3) == 4 && pick_v3<128, 2, 3, 2, 0>(5) == 4 && pick_v3<128, 2, 3, 2, 0>(0) == 4);
 template <int BN, int WN, int NBUF, int DIST, int OPT = 0>
 Variant make_v3(const char* name) {
   typedef V3Cfg<256, BN, WN, NBUF, DIST> CT;
-  Variant v;
-  v.name = name;
-  v.kind = Kind::V3;
-  for (int q = 0; q < QT_COUNT; ++q) v.geom[q] = {256, BN, 64, CT::NT};  // (weight-only / g128 / fp8 / bf16 cleared below)
-  for (int q : {QT_W4A16, QT_W8A16, QT_I4G, QT_W2A16, QT_F8, QT_BF16, QT_I4F6, QT_MXF4, QT_MXF4W, QT_MXF8A}) v.geom[q] = {0, 0, 0, 0};  // v2 kernels only
-  v.threads = CT::NT;
-  v.lds_bytes = CT::LDS_BYTES;
-  v.chunk = 32 * (160 * 1024 / CT::LDS_BYTES >= 2 ? 2 : 1);  // workgroups per XCD at once
-  v.k_stage_bytes = 0;
-  v.tail_bm = 128;
-  v.launch = &launch_v3<BN, WN, NBUF, DIST, OPT>;
+  Variant v = variant_base(name, Kind::V3, CT::NT, CT::LDS_BYTES, 32 * (160 * 1024 / CT::LDS_BYTES >= 2 ? 2 : 1), 128,
+                           table_of(kV3Builds<BN, WN, NBUF, DIST, OPT>), &pick_v3<BN, WN, NBUF, DIST, OPT>);
+  for (int q : {QT_F16, QT_I8, QT_I4}) v.geom[q] = {256, BN, 64, CT::NT};
   v.silu_epi = true;  // epilogue_v3
   return v;
 }
 
 #ifdef MXMOE_LAB
-template <int NBUF, int DIST, int OPT>
-void launch_f6(const GGArgs& a, int grid, int qmask, hipStream_t s) {
-  (void)qmask;  // QT_I4F6 only
-  hipLaunchKernelGGL((gg_f6_kernel<NBUF, DIST, OPT>), dim3(grid), dim3(512), 0, s, a);
-}
-
 // fp6 w4a4 tiles (gg_f6.h): 256 x 256 (+ 128-row tail class), one 512-thread workgroup per CU
+template <int NBUF, int DIST, int OPT>
+constexpr Builds<1> kF6Builds = {{{1 << QT_I4F6, true, F6Cfg<256, 256, 2, 4, NBUF, DIST>::LDS_BYTES, &launch_k<&gg_f6_kernel<NBUF, DIST, OPT>, 512>}}};
 template <int NBUF, int DIST, int OPT = 0>
 Variant make_f6(const char* name) {
   typedef F6Cfg<256, 256, 2, 4, NBUF, DIST> CT;
-  Variant v;
-  v.name = name;
-  v.kind = Kind::V3;
-  for (int q = 0; q < QT_COUNT; ++q) v.geom[q] = {0, 0, 0, 0};
+  Variant v = variant_base(name, Kind::V3, CT::NT, CT::LDS_BYTES, 32, 128, table_of(kF6Builds<NBUF, DIST, OPT>), &pick_only);
   v.geom[QT_I4F6] = {256, 256, CT::SKB, CT::NT};
-  v.threads = CT::NT;
-  v.lds_bytes = CT::LDS_BYTES;
-  v.chunk = 32;
-  v.k_stage_bytes = 0;  // (image rows are whole stages by construction)
-  v.tail_bm = 128;
-  v.launch = &launch_f6<NBUF, DIST, OPT>;
   return v;
 }
 #endif  // MXMOE_LAB
 
-// the v2 family's geometry (launch set by the caller)
-Variant v2_base(const char* name, int lds_bytes) {
-  Variant v;
-  v.name = name;
-  v.kind = Kind::V2;
-  for (int q = 0; q < QT_COUNT; ++q) v.geom[q] = {256, 256, 128, 512};
-  v.geom[QT_W4A16] = {256, 256, 32, 512};  // 64-K stages: 32 B of 4-bit codes per row
-  v.geom[QT_W8A16] = {256, 256, 64, 512};
-  v.geom[QT_W2A16] = {256, 256, 16, 512};  // 64-K stages: 16 B of 2-bit codes per row
-  v.geom[QT_MXF4W] = {256, 256, 32, 512};  // weight-only MXFP4: the 4-bit stage
-  v.geom[QT_I4G] = {256, 256, 128, 512};  // w4a4 g128 (gg_tile_g128): 256 / 128-row classes as int4
-  v.geom[QT_I4F6] = {0, 0, 0, 0};         // fp6 images: the f6 kernel only
-#ifdef MXMOE_LAB
-  v.geom[QT_MXF4] = {0, 0, 0, 0};         // (the lab library's launch tables carry no MXFP4 build)
-  v.geom[QT_MXF4W] = {0, 0, 0, 0};
-  v.geom[QT_MXF8A] = {0, 0, 0, 0};
+// ---- wo2: 64-row tiles at NWG workgroups per CU (gg_wo2_kernel): the weight-only types, and fp16 / w8a8 / w4a4 /
+// w4a8_g32_sym_MXFP8 problems beside them on gg_tile_v2's 64 x 128 bodies. SILU: a WO_SILU build (weight-only
+// problems with the fused SiLU epilogue, Build::qmask | kQmaskWoSilu)
+template <int ABL, int NWG, bool SILU, int... QM>
+constexpr Builds<sizeof...(QM)> wo2_rows(bool fallback = false) {
+  return {{Build{QM | (SILU ? kQmaskWoSilu : 0), fallback, wo2_lds_bytes<NWG>(),
+                 &launch_k<&gg_wo2_kernel<ABL | (SILU ? WO_SILU : 0), QM, NWG>, 512>}...}};
+}
+// At the variant's NWG: w4a16, w2a16, w4a16 + w8a8 (hz_fused pairing), fp16, w8a8, w4a4, w4a4 + w8a8 (LP-1 mixed),
+// weight-only MXFP4 and w4a8_g32_sym_MXFP8, each alone. The 8-bit body does not fit 80 VGPRs (3 workgroups
+// per CU) without spilling: calls with w8a16 problems, and any other mix, run 2-WG/CU builds of the same tiles
+// (same plan: placement only assumes more slots). WO_SILU builds: only the w4a16, w4a16 + w8a8 and weight-only
+// MXFP4 sets at the variant's NWG; w4a8_g32_sym_MXFP8 beside flagged problems always takes the widest.
+// (fast lab build: the w4a16, w4a16 + w8a8 and w8a16 sets only, all at the variant's NWG)
+template <int ABL, int NWG>
+constexpr auto kWo2Builds =
+#ifdef MXMOE_LAB_FAST
+    wo2_rows<ABL, NWG, false, 8, 10, 16>();
+#else
+    wo2_rows<ABL, NWG, false, 8, 64, 10, 1, 2, 4, 6, kMxW, kMx8>() + wo2_rows<ABL, 2, false, 16>() +
+    wo2_rows<ABL, 2, false, 95, 95 | kMxW, 95 | kMxW | kMx8>(true) +
+    wo2_rows<ABL, NWG, true, 8, 10, kMxW>() + wo2_rows<ABL, 2, true, 16>() +
+    wo2_rows<ABL, 2, true, 95, 95 | kMxW, 95 | kMxW | kMx8>(true);
 #endif
-  v.threads = 512;
-  v.lds_bytes = lds_bytes;
-  v.chunk = 32;  // one 512-thread workgroup per CU, 32 CUs per XCD
-  v.k_stage_bytes = 0;  // K tails handled in-kernel (last stage)
-  v.tail_bm = 128;
-  v.tail2_bm = 64;  // <= 64 remaining rows, fp16 / weight-only problems (small batches)
-  return v;
+template <int ABL, int NWG>
+constexpr int pick_wo2(int qmask) {
+#ifdef MXMOE_LAB_FAST
+  return pick_build(table_of(kWo2Builds<ABL, NWG>), qmask & 511);
+#else
+  return pick_build(table_of(kWo2Builds<ABL, NWG>), qmask & (511 | kMxW | kMx8 | kQmaskWoSilu));  // (the type bits wo2 looks at)
+#endif
 }
-
-template <int ABL = 0>
-Variant make_v2(const char* name) {
-  Variant v = v2_base(name, (ABL & V2_B3) ? 160 * 1024 : V2Cfg<256>::LDS_BYTES + V2_LDS_EXTRA);
-  v.launch = &launch_v2<ABL>;
-  v.silu_epi = true;  // gg_tile_v2's epilogue
-  return v;
+#ifndef MXMOE_LAB_FAST
+static_assert(exact_entries_pick_themselves(table_of(kWo2Builds<kWo3Product, 3>), &pick_wo2<kWo3Product, 3>));
+constexpr bool wo3_picks(int qmask, int build_mask, int nwg) {  // (SiLU builds: both masks | kQmaskWoSilu)
+  const Build& b = kWo2Builds<kWo3Product, 3>[pick_wo2<kWo3Product, 3>(qmask)];
+  return b.qmask == build_mask && b.lds_bytes == (nwg == 3 ? wo2_lds_bytes<3>() : wo2_lds_bytes<2>());
 }
-
-
-bool is_weightonly(int qt);
-
-// wo2: weight-only problems only, 64-row tiles, NWG workgroups per CU (gg_wo2_kernel)
+constexpr int kS = kQmaskWoSilu, kW4 = 1 << QT_W4A16;
+static_assert(wo3_picks(kW4, 8, 3) && wo3_picks(1 << QT_W8A16, 16, 2) && wo3_picks(kMx8, kMx8, 3));
+static_assert(wo3_picks(kW4 | (1 << QT_F16), 95, 2) && wo3_picks(kW4 | (1 << QT_W8A16), 95, 2));
+static_assert(wo3_picks(kMxW | (1 << QT_I8), 95 | kMxW, 2) && wo3_picks(kMx8 | kW4, 95 | kMxW | kMx8, 2));
+static_assert(wo3_picks(kS | kW4, kS | 8, 3) && wo3_picks(kS | (1 << QT_W2A16), kS | 95, 2));
+static_assert(wo3_picks(kS | kMxW | kW4, kS | 95 | kMxW, 2) && wo3_picks(kS | kMx8 | kW4, kS | 95 | kMxW | kMx8, 2));
+static_assert(wo3_picks(kS | kMx8 | kMxW, kS | 95 | kMxW | kMx8, 2));
+#endif
 template <int ABL = 0, int NWG = 2>
 Variant make_wo2(const char* name) {
-  Variant v = v2_base(name, wo2_lds_bytes<NWG>());  // (no v2 kernel instantiated for the wo flags)
-  for (int q = 0; q < QT_COUNT; ++q)
-    if (!is_weightonly(q)) v.geom[q] = {0, 0, 0, 0};
-    else v.geom[q].bm = 64;
-  v.geom[QT_I8] = {64, 128, 128, 512};  // w8a8 (beside weight-only problems): 64 x 128 int8 tiles
-  v.geom[QT_F16] = {64, 128, 128, 512};  // fp16: 64 x 128 tiles (64-K stages)
-  v.geom[QT_I4] = {64, 128, 128, 512};   // w4a4: 64 x 128 tiles (256-K stages)
-#ifndef MXMOE_LAB
-  v.geom[QT_MXF8A] = {64, 128, 128, 512};  // w4a8_g32_sym_MXFP8: 64 x 128 tiles (128-K stages)
-#endif
-  v.lds_bytes = wo2_lds_bytes<NWG>();
+  Variant v = v2_base(name, wo2_lds_bytes<NWG>(), table_of(kWo2Builds<ABL, NWG>), &pick_wo2<ABL, NWG>);
+  v.geom[QT_W4A16] = {64, 256, 32, 512};  // 64-K stages: 32 B of 4-bit codes per row
+  v.geom[QT_W8A16] = {64, 256, 64, 512};
+  v.geom[QT_W2A16] = {64, 256, 16, 512};
+  // 64 x 128 tiles: w8a8 (int8), fp16 (64-K stages), w4a4 (256-K stages)
+  v.geom[QT_I8] = v.geom[QT_F16] = v.geom[QT_I4] = {64, 128, 128, 512};
+  if (kMxBodies) {
+    v.geom[QT_MXF4W] = {64, 256, 32, 512};   // weight-only MXFP4: the 4-bit stage
+    v.geom[QT_MXF8A] = {64, 128, 128, 512};  // w4a8_g32_sym_MXFP8: 64 x 128 tiles (128-K stages)
+  }
   v.chunk = 32 * NWG;  // NWG workgroups per CU, 32 CUs per XCD
-  v.tail_bm = 0;
-  v.tail2_bm = 0;
-  v.launch = &launch_wo2<ABL, NWG>;
-  v.lds_of = &wo2_launch_lds<NWG>;
+  v.tail_bm = v.tail2_bm = 0;
   v.silu_epi = true;  // its fp16 / w8a8 / w4a4 problems run gg_tile_v2 64 x 128 bodies (their epilogue)
 #ifndef MXMOE_LAB_FAST
-  v.silu_wo = true;   // weight-only problems: the WO_SILU builds (launch_wo2)
+  v.silu_wo = true;   // weight-only problems: the WO_SILU builds
 #endif
   return v;
 }
 
+// ---- v2p: the persistent v2x (lab; no MX body in the persistent kernels)
+template <int TRACE, int... QM>
+constexpr Builds<sizeof...(QM)> v2p_rows(bool fallback = false) {
+  return {{Build{QM, fallback, 160 * 1024, &launch_k<&gg_v2p_kernel<QM, TRACE>, 512>}...}};
+}
+template <int TRACE>
+constexpr auto kV2pBuilds = v2p_rows<TRACE, 1, 2, 256>() + v2p_rows<TRACE, 511>(true);  // (511: every tile body)
+template <int TRACE>
+constexpr int pick_v2p(int qmask) { return pick_build(table_of(kV2pBuilds<TRACE>), qmask & 511); }
 template <int TRACE = 0>
 Variant make_v2p(const char* name) {
-  Variant v = make_v2<V2_STAGGER | V2_B3 | V2_BUF | V2_EARLYDMA | (4 << V2_SPREAD_SHIFT)>(name);
-  v.geom[QT_MXF4] = v.geom[QT_MXF4W] = v.geom[QT_MXF8A] = {0, 0, 0, 0};  // (no MX body in the persistent kernels)
+  Variant v = v2_base(name, 160 * 1024, table_of(kV2pBuilds<TRACE>), &pick_v2p<TRACE>);
+  set_v2_geom(&v, false);
   v.persistent = true;
-  v.lds_bytes = 160 * 1024;
-  v.launch = &launch_v2p<TRACE>;
+  v.silu_epi = true;  // (its tile body's; has_silu_epilogue: not from a persistent kernel)
   return v;
 }
 
 #ifdef MXMOE_LAB
 // v2q: the persistent v2x with the register epilogue and the next tile's ring fill before it
 // (gg_v2q.h); planned like v2p (per-workgroup tile lists)
+template <int TRACE, int SAUX, int FILLALL, int... QM>
+constexpr Builds<sizeof...(QM)> v2q_rows(bool fallback = false) {
+  return {{Build{QM, fallback, 160 * 1024, &launch_k<&gg_v2q_kernel<QM, TRACE, SAUX, FILLALL>, 512>}...}};
+}
+template <int TRACE, int SAUX, int FILLALL>
+constexpr auto kV2qBuilds =
+#ifdef MXMOE_LAB_FAST
+    v2q_rows<TRACE, SAUX, FILLALL, 1, 2>();
+#else
+    v2q_rows<TRACE, SAUX, FILLALL, 1, 2, 4, 6, 256>() + v2q_rows<TRACE, SAUX, FILLALL, 511>(true);
+#endif
+template <int TRACE, int SAUX, int FILLALL>
+constexpr int pick_v2q(int qmask) { return pick_build(table_of(kV2qBuilds<TRACE, SAUX, FILLALL>), qmask & 511); }
 template <int TRACE = 0, int SAUX = 16, int FILLALL = 0>
 Variant make_v2q(const char* name, int persist_len = 0) {
   Variant v = make_v2p<0>(name);
-  v.launch = &launch_v2q<TRACE, SAUX, FILLALL>;
+  v.builds = table_of(kV2qBuilds<TRACE, SAUX, FILLALL>);
+  v.pick = &pick_v2q<TRACE, SAUX, FILLALL>;
   v.persist_len = persist_len;
   return v;
 }
-// v4d (gg_v4.h): 256 x 256 tiles (+ 128 / 64-row classes), 4 waves at one per SIMD, fp16 / w8a8 only
-template <int QM, int OPT>
-void launch_v4_q(const GGArgs& a, int grid, hipStream_t s) {
-  hipLaunchKernelGGL((gg_v4_kernel<QM, OPT>), dim3(grid), dim3(256), 0, s, a);
+// v4d (gg_v4.h): 256 x 256 tiles (+ 128 / 64-row classes), 4 waves at one per SIMD, fp16 / w8a8 / w4a4 only
+template <int OPT, int... QM>
+constexpr Builds<sizeof...(QM)> v4_rows(bool fallback = false) {
+  return {{Build{QM, fallback, V4Cfg<256>::LDS_BYTES, &launch_k<&gg_v4_kernel<QM, OPT>, 256>}...}};
 }
-template <int OPT = 0>
-void launch_v4(const GGArgs& a, int grid, int qmask, hipStream_t s) {
-  switch (qmask & 511) {
-    case 1: launch_v4_q<1, OPT>(a, grid, s); break;
-    case 2: launch_v4_q<2, OPT>(a, grid, s); break;
-    case 4: launch_v4_q<4, OPT>(a, grid, s); break;
-#ifndef MXMOE_LAB_FAST
-    case 6: launch_v4_q<6, OPT>(a, grid, s); break;
-    default: launch_v4_q<7, OPT>(a, grid, s); break;
+template <int OPT>
+constexpr auto kV4Builds =
+#ifdef MXMOE_LAB_FAST
+    v4_rows<OPT, 1, 2, 4>() + v4_rows<OPT, 3>(true);  // (the fast build's only mix; any other set lands there too)
 #else
-    default: launch_v4_q<3, OPT>(a, grid, s); break;
+    v4_rows<OPT, 1, 2, 4, 6>() + v4_rows<OPT, 7>(true);
 #endif
-  }
-}
+template <int OPT>
+constexpr int pick_v4(int qmask) { return pick_build(table_of(kV4Builds<OPT>), qmask & 511); }
 template <int OPT = 0>
 Variant make_v4(const char* name) {
-  Variant v = v2_base(name, V4Cfg<256>::LDS_BYTES);
-  for (int q = 0; q < QT_COUNT; ++q)
-    if (q != QT_F16 && q != QT_I8 && q != QT_I4) v.geom[q] = {0, 0, 0, 0};
-  v.geom[QT_F16].threads = v.geom[QT_I8].threads = v.geom[QT_I4].threads = 256;
-  v.threads = 256;
-  v.launch = &launch_v4<OPT>;
+  Variant v = v2_base(name, V4Cfg<256>::LDS_BYTES, table_of(kV4Builds<OPT>), &pick_v4<OPT>, 256);
+  for (int q : {QT_F16, QT_I8, QT_I4}) v.geom[q] = {256, 256, 128, 256};
   return v;
 }
 #endif  // MXMOE_LAB
-
-// the small-batch weight-only tile's loop options (gg_tile_wo)
-constexpr int kWo3 = WO_SCLATE | WO_ANDOR | WO_MSKIP | WO_SPLIT | WO_NIBPOS;
-
-// the round-3 AUTO default's mainloop flags (variant v2x_256x256_w8_b3_buf_spread_edma, without the
-// weight-only options)
-constexpr int kV2x = V2_STAGGER | V2_B3 | V2_BUF | V2_EARLYDMA | (4 << V2_SPREAD_SHIFT);
 
 typedef TileCfg<128, 128, 2, 2, 2> T128x128;
 typedef TileCfg<256, 128, 2, 2, 1> T256x128;
@@ -524,7 +557,7 @@ const std::vector<Variant>& variants() {
       // w4a4 on v2x -7.5 / -5.1 %: profiles/r05/nopair/)
       // + the early-wave DMA issue on int4 tiles too (V2_I4EDMA: with the unpaired reads it now pays,
       // lab A/B w4a4 / mixed / ds2_mixed gate_up -2.7..-2.8 %, down -1.3..-3.7 %: profiles/r05/i4edma/)
-      make_v2<kV2x | WO_PIPE | WO_STAG | V2_I4NOPAIR | V2_I4EDMA>("v2x_256x256_w8_b3_buf_spread_edma"),
+      make_v2<kV2xProduct>("v2x_256x256_w8_b3_buf_spread_edma"),
       // round 3 (AUTO for small-batch weight-only calls): the 64-row weight-only tile at three
       // workgroups per CU (gg_wo2_kernel<.., 3>; weight-only problems only) — profiles/r03/wo2/;
       // round 4: scale groups by LDS-DMA, register constants for the code -> fp16 step, codes
@@ -534,7 +567,7 @@ const std::vector<Variant>& variants() {
       // the group bookkeeping, unrolled by the ring depth (WO_PCH): ~58 fewer SALU and ~17 fewer VALU
       // per 3 stages, bit-identical; lab A/B -2.6 to -4.0 % on the per-channel bs 512 / 128 calls,
       // g128 unchanged (profiles/r06/pch/)
-      make_wo2<kWo3 | WO_PCH, 3>("wo3_64x256_w8_3wg"),
+      make_wo2<kWo3Product, 3>("wo3_64x256_w8_3wg"),
 #elif defined(MXMOE_LAB_FAST)
       // fast lab build (`python -m mxmoe_amd.build --lab-fast`): the product default and the
       // experiments under test only, fp16 / w8a8 bodies only
@@ -555,7 +588,7 @@ const std::vector<Variant>& variants() {
       // the small-batch weight-only tile: where its time goes (ablations: WRONG RESULTS by design)
       make_wo2<0, 3>("x_wo3_r3"),  // the round-3 loop
       make_wo2<kWo3, 3>("x_wo3"),
-      make_wo2<kWo3 | WO_PCH, 3>("x_wo3_pch"),  // round 6: one-group loop (per-channel scales)
+      make_wo2<kWo3Product, 3>("x_wo3_pch"),  // round 6: one-group loop (per-channel scales)
       make_wo2<kWo3, 2>("x_wo2"),
       make_wo2<kWo3 | WO_BUF, 3>("x_wo3_buf"),
       make_wo2<kWo3 | WO_ADEAD, 3>("x_wo3_adead"),
@@ -573,9 +606,9 @@ const std::vector<Variant>& variants() {
       make_v2<kV2x | V2_I4NOPAIR>("x_v2x_i4nopair"),
       make_v2<kV2x | V2_I4NOPAIR | V2_I4EDMA>("x_v2x_i4edma"),
       // the product's default and small-batch kernels, for planner A/B runs (MXMOE_GG_XCD_PACK, _MIX)
-      make_v2<kV2x | WO_PIPE | WO_STAG | V2_I4NOPAIR | V2_I4EDMA>("x_v2x_product"),
+      make_v2<kV2xProduct>("x_v2x_product"),
       make_wo2<kWo3, 3>("x_wo3"),
-      make_wo2<kWo3 | WO_PCH, 3>("x_wo3_pch"),  // round 6: one-group loop (per-channel scales)
+      make_wo2<kWo3Product, 3>("x_wo3_pch"),  // round 6: one-group loop (per-channel scales)
       // round 6: v4d, one wave per SIMD (gg_v4.h; fp16 / w8a8)
       make_v4("x_v4d_256x256_w4_1wave"),
       make_v2<kV2x | V2_PLAINST>("x_v2x_plainst"),
@@ -628,34 +661,6 @@ const std::vector<Variant>& variants() {
   return v;
 }
 
-// AUTO policy: v2x (the staggered 256x256 v2 on v2s3's LDS image with the buffer-form, spread
-// LDS-DMA) for every call with fp16 / bf16 / w8a8 / E4M3 / weight-only problems: same-run A/B on the
-// qwen2_moe layer-11 calls, +5-11 % over v2s and +3-9 % over v2s3 at every K (the round-1/2 short-K
-// rule between those two is gone: profiles/r03/lab/). int4-only sets run 256x128 tiles, 2 WG/CU
-// (v3), unless they are low-fill enough to need split-K (v2 kernels only).
-constexpr const char* kDefaultVariantName = "v2x_256x256_w8_b3_buf_spread_edma";
-constexpr const char* kInt4Variant = "v3_256x128_w4_dma_ring3_2wg";
-constexpr const char* kWoSmallVariant = "wo3_64x256_w8_3wg";
-#ifdef MXMOE_LAB
-constexpr const char* kF6Variant = "f6_256x256_w8_ring3";
-#endif
-// weight-only calls whose rows per weight byte are this small or smaller run kWoSmallVariant:
-// the weight-bytes-weighted mean M over the call's problems (qwen2_moe layer 11: ~60 at bs = 128,
-// ~250 at bs = 2048, ~1030 at bs = 8192, where v2x's 256-row tiles are as fast or faster)
-constexpr double kWoSmallMeanRows = 512.0;
-// calls of fp16 / w8a8 / w4a4 problems only (no weight-only one) take wo3 below a mean M of
-// kSmallMeanRows (kSmallMeanRowsI4 with int4 problems), twice that when the call is K-skewed (its
-// longest K >= 2x the weighted mean K: the qwen2_moe down call, whose shared expert has 4x the
-// routed K — few long tiles the general kernels balance poorly). Measured on qwen2_moe layer 11
-// (mean M ~ bs / 8; profiles/r03/wo2/wo3_fp16_w8a8.jsonl, wo3_w4a4_mixed.jsonl, wo3_mid.jsonl):
-// gate_up wins to bs 512 (fp16 -3.5 .. w4a4 +33 %) and 768 with int4, down calls to bs 1024 (fp16)
-// / 1536 (int4), the general kernels beyond.
-constexpr double kSmallMeanRows = 80.0;
-constexpr double kSmallMeanRowsI4 = 112.0;
-// calls with a w4a8_g32_sym_MXFP8 problem (and no weight-only one): the int4 cut
-constexpr double kSmallMeanRowsMx8 = 112.0;
-constexpr double kSplitCUs = 256.0;  // MI355X compute units: the planner's notion of "one CU's share"
-
 int variant_index(const char* name) {
   for (size_t i = 0; i < variants().size(); ++i)
     if (!strcmp(variants()[i].name, name)) return (int)i;
@@ -664,80 +669,46 @@ int variant_index(const char* name) {
 
 int qtype_of(int a_bits, int w_bits, int gsize, int sym, int fmt, int* qt) {
   fmt &= 0xFF;  // (epilogue flags, MXMOE_GG_EPI_*, live above the operand format)
+  auto take = [&](int q) { return *qt = q, (int)MXMOE_GG_OK; };
   if (fmt == MXMOE_GG_FMT_E4M3) {  // w8a8_g-1_sym_E4M3 (tile_config.py:45, 104-106, 192)
-    if (a_bits == 8 && w_bits == 8 && gsize == -1 && sym) {
-      *qt = QT_F8;
-      return MXMOE_GG_OK;
-    }
+    if (a_bits == 8 && w_bits == 8 && gsize == -1 && sym) return take(QT_F8);
     return fail(MXMOE_GG_ERR_UNSUPPORTED, "quant type not supported: w%da%d_g%d_%s_E4M3 (only w8a8_g-1_sym_E4M3)",
                 w_bits, a_bits, gsize, sym ? "sym" : "asym");
   }
   if (fmt == MXMOE_GG_FMT_BF16) {  // bf16 (tile_config.py:42, 99-102)
-    if (a_bits == 16 && w_bits == 16) {
-      *qt = QT_BF16;
-      return MXMOE_GG_OK;
-    }
+    if (a_bits == 16 && w_bits == 16) return take(QT_BF16);
     return fail(MXMOE_GG_ERR_UNSUPPORTED, "quant type not supported: w%da%d bf16 (only 16-bit bf16 operands)", w_bits,
                 a_bits);
   }
   if (fmt == MXMOE_GG_FMT_MXFP4) {  // OCP MXFP4: e2m1 codes, one e8m0 scale per 32-K block
-    if (a_bits == 4 && w_bits == 4 && gsize == 32 && sym) {
-      *qt = QT_MXF4;
-      return MXMOE_GG_OK;
-    }
-    if (a_bits == 16 && w_bits == 4 && gsize == 32 && sym) {  // weight-only: fp16 A on the same B operand
-      *qt = QT_MXF4W;
-      return MXMOE_GG_OK;
-    }
+    if (a_bits == 4 && w_bits == 4 && gsize == 32 && sym) return take(QT_MXF4);
+    if (a_bits == 16 && w_bits == 4 && gsize == 32 && sym) return take(QT_MXF4W);  // weight-only: fp16 A on the same B operand
     return fail(MXMOE_GG_ERR_UNSUPPORTED,
                 "quant type not supported: w%da%d_g%d_%s_MXFP4 (only w4a4_g32_sym_MXFP4 and w4a16_g32_sym_MXFP4)",
                 w_bits, a_bits, gsize, sym ? "sym" : "asym");
   }
   if (fmt == MXMOE_GG_FMT_MXFP8) {  // OCP MXFP8 (e4m3) activations on MXFP4 weights
-    if (a_bits == 8 && w_bits == 4 && gsize == 32 && sym) {
-      *qt = QT_MXF8A;
-      return MXMOE_GG_OK;
-    }
+    if (a_bits == 8 && w_bits == 4 && gsize == 32 && sym) return take(QT_MXF8A);
     return fail(MXMOE_GG_ERR_UNSUPPORTED, "quant type not supported: w%da%d_g%d_%s_MXFP8 (only w4a8_g32_sym_MXFP8)", w_bits,
                 a_bits, gsize, sym ? "sym" : "asym");
   }
 #ifdef MXMOE_LAB
   if (fmt == MXMOE_GG_FMT_F6) {  // w4a4_g-1_sym with fp6 images of the int4 codes (mxmoe_gg_pack_f6)
-    if (a_bits == 4 && w_bits == 4 && gsize == -1 && sym) {
-      *qt = QT_I4F6;
-      return MXMOE_GG_OK;
-    }
+    if (a_bits == 4 && w_bits == 4 && gsize == -1 && sym) return take(QT_I4F6);
     return fail(MXMOE_GG_ERR_UNSUPPORTED, "quant type not supported: w%da%d_g%d_%s as fp6 images (only w4a4_g-1_sym)",
                 w_bits, a_bits, gsize, sym ? "sym" : "asym");
   }
 #endif
   if (fmt != MXMOE_GG_FMT_DEFAULT) return fail(MXMOE_GG_ERR_UNSUPPORTED, "unknown operand format %d", fmt);
-  if (a_bits == 16 && w_bits == 16) {
-    *qt = QT_F16;
-    return MXMOE_GG_OK;
-  }
-  if (a_bits == 8 && w_bits == 8 && gsize == -1 && sym) {
-    *qt = QT_I8;
-    return MXMOE_GG_OK;
-  }
-  if (a_bits == 4 && w_bits == 4 && gsize == -1 && sym) {
-    *qt = QT_I4;
-    return MXMOE_GG_OK;
-  }
-  if (a_bits == 4 && w_bits == 4 && gsize == 128 && sym) {  // w4a4_g128_sym (cta_gemm.cuh:610-772)
-    *qt = QT_I4G;
-    return MXMOE_GG_OK;
-  }
-  if (a_bits == 16 && (w_bits == 2 || w_bits == 4 || w_bits == 8)) {  // weight-only; group size checked per problem
-    *qt = w_bits == 2 ? QT_W2A16 : w_bits == 4 ? QT_W4A16 : QT_W8A16;
-    return MXMOE_GG_OK;
-  }
+  if (a_bits == 16 && w_bits == 16) return take(QT_F16);
+  if (a_bits == 8 && w_bits == 8 && gsize == -1 && sym) return take(QT_I8);
+  if (a_bits == 4 && w_bits == 4 && gsize == -1 && sym) return take(QT_I4);
+  if (a_bits == 4 && w_bits == 4 && gsize == 128 && sym) return take(QT_I4G);  // w4a4_g128_sym (cta_gemm.cuh:610-772)
+  if (a_bits == 16 && (w_bits == 2 || w_bits == 4 || w_bits == 8))  // weight-only; group size checked per problem
+    return take(w_bits == 2 ? QT_W2A16 : w_bits == 4 ? QT_W4A16 : QT_W8A16);
   return fail(MXMOE_GG_ERR_UNSUPPORTED, "quant type not supported: w%da%d_g%d_%s", w_bits, a_bits, gsize,
               sym ? "sym" : "asym");
 }
-
-bool is_weightonly(int qt) { return qt == QT_W4A16 || qt == QT_W8A16 || qt == QT_W2A16 || qt == QT_MXF4W; }
-bool is_float16(int qt) { return qt == QT_F16 || qt == QT_BF16; }  // 16-bit operands, no scales
 
 size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
@@ -766,52 +737,58 @@ WsLayout ws_layout(int P, int grid, int slabs) {
   return l;
 }
 
-// Validate one problem and fill its table row.
-// Weight-only WxA16: A fp16 [M][K], B codes [N][K * w_bits / 8] (mxmoe_gg_repack_weightonly
-// layout), scale_b = scale / zp in the reference permute_scale layout; K in 64-element stages.
-// Weight-only MXFP4 (QT_MXF4W, g32): B canonical e2m1 codes, scale_b e8m0 bytes in the MXFP4 device
-// layout — no repack, no fp16 scale groups: the kernel sees one group over all K stages.
-int build_meta_weightonly(const HostProblem& p, int idx, int qt, const Variant& v, bool check_ptrs, GGMeta* m) {
-  const bool mx = qt == QT_MXF4W;
-  if (p.K % 64) return fail(MXMOE_GG_ERR_INVALID, "problem %d: weight-only needs K %% 64 == 0 (K=%d)", idx, p.K);
-  if (!mx && p.gsize != -1 && (p.gsize <= 0 || p.gsize % 64 || p.K % p.gsize))
-    return fail(MXMOE_GG_ERR_UNSUPPORTED, "problem %d: weight-only group size %d must be -1 or a multiple of 64 dividing K=%d",
-                idx, p.gsize, p.K);
-  if (p.N % 8 != 0) return fail(MXMOE_GG_ERR_INVALID, "problem %d: N=%d must be a multiple of 8", idx, p.N);
-  const bool silu = (p.fmt & MXMOE_GG_EPI_SILU_MUL) != 0;  // (build_meta checked N % 32 and the variant)
-  const int64_t arow = (int64_t)p.K * 2, brow = (int64_t)p.K * p.w_bits / 8;
+// The strides of a problem whose dense A / B rows are arow / brow bytes, checked, and its table row filled but for
+// GGMeta::reserved and the type's reserved2 bits.
+int meta_row(const HostProblem& p, int idx, int qt, const Variant& v, int64_t arow, int64_t brow, bool dma_rows, GGMeta* m) {
+  const bool silu = (p.fmt & MXMOE_GG_EPI_SILU_MUL) != 0;
   const int64_t lda_b = p.lda ? p.lda * 2 : arow;
   const int64_t ldb_b = p.ldb ? p.ldb * 2 : brow;
   const int64_t ncols = silu ? p.N / 2 : p.N;  // columns of C
   const int64_t ldc = p.ldc ? p.ldc : ncols;
   if (lda_b < arow || ldb_b < brow || (lda_b % 16) || (ldb_b % 16))
     return fail(MXMOE_GG_ERR_INVALID, "problem %d: lda/ldb must be >= K row and a multiple of 8 words", idx);
+  // the buffer-form LDS-DMA addresses a 256-row tile with 32-bit offsets below 2^31
+  if (dma_rows && (lda_b >= (int64_t)1 << 23 || ldb_b >= (int64_t)1 << 23))
+    return fail(MXMOE_GG_ERR_INVALID, "problem %d: A / B row strides must be below 8 MiB", idx);
   if (ldc < ncols || (ldc % 8))
     return fail(MXMOE_GG_ERR_INVALID, "problem %d: ldc must be >= %s and a multiple of 8", idx, silu ? "N / 2" : "N");
+  memset(m, 0, sizeof(*m));
+  m->M = p.M, m->N = p.N, m->K = p.K, m->qtype = qt;
+  m->tiles_n = (p.N + v.geom[qt].bn - 1) / v.geom[qt].bn;
+  m->kbytes = (int32_t)arow;
+  m->reserved2 = silu ? META_SILU : 0;
+  m->lda_b = lda_b, m->ldb_b = ldb_b, m->ldc = ldc;
+  return MXMOE_GG_OK;
+}
+
+// Validate one problem and fill its table row.
+// Weight-only WxA16: A fp16 [M][K], B codes [N][K * w_bits / 8] (mxmoe_gg_repack_weightonly
+// layout), scale_b = scale / zp in the reference permute_scale layout; K in 64-element stages.
+// Weight-only MXFP4 (g32, QTypeInfo::dword_scales): B canonical e2m1 codes, scale_b e8m0 bytes in the MXFP4
+// device layout — no repack, no fp16 scale groups: the kernel sees one group over all K stages.
+int build_meta_weightonly(const HostProblem& p, int idx, int qt, const Variant& v, bool check_ptrs, GGMeta* m) {
+  const bool mx = qinfo(qt).dword_scales != nullptr;
+  if (p.K % 64) return fail(MXMOE_GG_ERR_INVALID, "problem %d: weight-only needs K %% 64 == 0 (K=%d)", idx, p.K);
+  if (!mx && p.gsize != -1 && (p.gsize <= 0 || p.gsize % 64 || p.K % p.gsize))
+    return fail(MXMOE_GG_ERR_UNSUPPORTED, "problem %d: weight-only group size %d must be -1 or a multiple of 64 dividing K=%d",
+                idx, p.gsize, p.K);
+  if (p.N % 8 != 0) return fail(MXMOE_GG_ERR_INVALID, "problem %d: N=%d must be a multiple of 8", idx, p.N);
+  // (the SiLU flag: build_meta checked N % 32 and the variant)
+  if (int st = meta_row(p, idx, qt, v, (int64_t)p.K * 2, (int64_t)p.K * p.w_bits / 8, false, m)) return st;
   if (check_ptrs && p.M > 0 && p.N > 0) {
     if (!p.A || !p.B || !p.C) return fail(MXMOE_GG_ERR_INVALID, "problem %d: NULL A/B/C", idx);
     if (!p.SB) return fail(MXMOE_GG_ERR_INVALID, "problem %d: NULL scale pointer (weight-only scale_b)", idx);
     if (((uintptr_t)p.A | (uintptr_t)p.B | (uintptr_t)p.C) & 15)
       return fail(MXMOE_GG_ERR_INVALID, "problem %d: A/B/C must be 16-byte aligned", idx);
     if (mx && (((uintptr_t)p.SB) & 3))  // (the kernel reads scale dwords)
-      return fail(MXMOE_GG_ERR_INVALID, "problem %d: MXFP4 scales must be 4-byte aligned", idx);
+      return fail(MXMOE_GG_ERR_INVALID, "problem %d: %s scales must be 4-byte aligned", idx, qinfo(qt).dword_scales);
     if (((uintptr_t)p.SB) & (p.sym ? 1 : 3))
       return fail(MXMOE_GG_ERR_INVALID, "problem %d: scales must be %d-byte aligned", idx, p.sym ? 2 : 4);
   }
   // the scale loads address a 256-column tile's rows with a 32-bit offset
   if (mx && p.K > (1 << 20)) return fail(MXMOE_GG_ERR_INVALID, "problem %d: K=%d exceeds 2^20 (MXFP4 weight-only)", idx, p.K);
-  memset(m, 0, sizeof(*m));
-  m->M = p.M;
-  m->N = p.N;
-  m->K = p.K;
-  m->qtype = qt;
-  m->tiles_n = (p.N + v.geom[qt].bn - 1) / v.geom[qt].bn;
-  m->kbytes = (int32_t)arow;
   m->reserved = (p.gsize == -1 || mx) ? std::max(1, p.K / 64) : p.gsize / 64;  // 64-K stages per scale group
-  m->reserved2 = (p.sym ? 1 : 0) | (silu ? META_SILU : 0);
-  m->lda_b = lda_b;
-  m->ldb_b = ldb_b;
-  m->ldc = ldc;
+  m->reserved2 |= p.sym ? 1 : 0;
   return MXMOE_GG_OK;
 }
 
@@ -825,17 +802,19 @@ int build_meta(const HostProblem& p, int idx, const Variant& v, bool check_ptrs,
                 idx, v.name, p.w_bits, p.a_bits);
   const bool silu = (p.fmt & MXMOE_GG_EPI_SILU_MUL) != 0;
   if (p.fmt & ~(0xFF | MXMOE_GG_EPI_SILU_MUL)) return fail(MXMOE_GG_ERR_INVALID, "problem %d: unknown fmt flags %#x", idx, p.fmt);
-  if (silu && !(qt == QT_F16 || qt == QT_I8 || qt == QT_I4 || qt == QT_MXF8A || (is_weightonly(qt) && v.silu_wo)))
+  const QTypeInfo& t = qinfo(qt);
+  if (silu && !(t.silu && (!t.weight_only || v.silu_wo)))
     return fail(MXMOE_GG_ERR_UNSUPPORTED,
                 "problem %d: the SiLU epilogue needs fp16, w8a8_g-1_sym, w4a4_g-1_sym or w4a8_g32_sym_MXFP8 (weight-only: "
                 "the small-batch kernel wo3)", idx);
   if (silu && !has_silu_epilogue(v))
     return fail(MXMOE_GG_ERR_UNSUPPORTED, "problem %d: variant %s has no SiLU epilogue", idx, v.name);
   if (silu && p.N % 32) return fail(MXMOE_GG_ERR_INVALID, "problem %d: the SiLU epilogue needs N %% 32 == 0 (N=%d)", idx, p.N);
-  if (is_weightonly(qt)) return build_meta_weightonly(p, idx, qt, v, check_ptrs, m);
-  if (qt == QT_MXF8A && p.K % 32)
-    return fail(MXMOE_GG_ERR_INVALID, "problem %d: w4a8_g32_sym_MXFP8 needs K %% 32 == 0 (K=%d)", idx, p.K);
-  const int abits = is_float16(qt) ? 16 : p.a_bits;
+  if (t.weight_only) return build_meta_weightonly(p, idx, qt, v, check_ptrs, m);
+  const bool k_rule_fails = t.k_mult && p.K % t.k_mult != 0;  // the type's own K granularity
+  if (k_rule_fails && t.k_first)
+    return fail(MXMOE_GG_ERR_INVALID, "problem %d: %s needs K %% %d == 0 (K=%d)", idx, t.k_what, t.k_mult, p.K);
+  const int abits = t.float16 ? 16 : p.a_bits;
   const int64_t kbits = (int64_t)p.K * abits;  // (fp6 images: K of the int4 codes they encode)
   if (kbits % 128 != 0)
     return fail(MXMOE_GG_ERR_INVALID, "problem %d: K=%d must be a multiple of %d for %d-bit data (16-B rows)", idx,
@@ -843,54 +822,69 @@ int build_meta(const HostProblem& p, int idx, const Variant& v, bool check_ptrs,
   if (v.k_stage_bytes && (kbits / 8) % v.k_stage_bytes != 0)
     return fail(MXMOE_GG_ERR_INVALID, "problem %d: variant %s needs K*bits/8 to be a multiple of %d bytes (K=%d)",
                 idx, v.name, v.k_stage_bytes, p.K);
-  if (qt == QT_I4G && p.K % 128 != 0)
-    return fail(MXMOE_GG_ERR_INVALID, "problem %d: w4a4_g128 needs K %% 128 == 0 (K=%d)", idx, p.K);
-  if (qt != QT_F16 && qt != QT_BF16 && qt != QT_F8 && qt != QT_MXF4 && qt != QT_MXF8A && p.K > 131072)
+  if (k_rule_fails)
+    return fail(MXMOE_GG_ERR_INVALID, "problem %d: %s needs K %% %d == 0 (K=%d)", idx, t.k_what, t.k_mult, p.K);
+  if (t.int32_bound && p.K > 131072)
     return fail(MXMOE_GG_ERR_INVALID, "problem %d: K=%d exceeds the exact int32 accumulation bound 131072", idx, p.K);
   if (p.N % 8 != 0) return fail(MXMOE_GG_ERR_INVALID, "problem %d: N=%d must be a multiple of 8", idx, p.N);
-  // fp6 images: 96 B per K-128 block, K padded to whole blocks (mxmoe_gg_pack_f6)
-#ifdef MXMOE_LAB
-  const int64_t kbytes = qt == QT_I4F6 ? (int64_t)MXMOE_GG_F6_ROW_BYTES(p.K) : kbits / 8;
-#else
-  const int64_t kbytes = kbits / 8;
-#endif
-  const int64_t kbytes_b = qt == QT_MXF8A ? kbytes / 2 : kbytes;  // (w4a8 MXFP8: 4-bit B rows under 8-bit A rows)
-  const int64_t lda_b = p.lda ? p.lda * 2 : kbytes;
-  const int64_t ldb_b = p.ldb ? p.ldb * 2 : kbytes_b;
-  const int64_t ncols = silu ? p.N / 2 : p.N;  // columns of C
-  const int64_t ldc = p.ldc ? p.ldc : ncols;
-  if (lda_b < kbytes || ldb_b < kbytes_b || (lda_b % 16) || (ldb_b % 16))
-    return fail(MXMOE_GG_ERR_INVALID, "problem %d: lda/ldb must be >= K row and a multiple of 8 words", idx);
-  // the buffer-form LDS-DMA addresses a 256-row tile with 32-bit offsets below 2^31
-  if (lda_b >= (int64_t)1 << 23 || ldb_b >= (int64_t)1 << 23)
-    return fail(MXMOE_GG_ERR_INVALID, "problem %d: A / B row strides must be below 8 MiB", idx);
-  if (ldc < ncols || (ldc % 8))
-    return fail(MXMOE_GG_ERR_INVALID, "problem %d: ldc must be >= %s and a multiple of 8", idx, silu ? "N / 2" : "N");
+  // rows staged at another width than their codes (fp6 images of int4 codes: 96 B per K-128 block, K padded
+  // to whole blocks, mxmoe_gg_pack_f6)
+  const int64_t kbytes = t.staged_bits == abits ? kbits / 8 : ((int64_t)p.K + 127) / 128 * (128 * t.staged_bits / 8);
+  const int64_t kbytes_b = kbytes * p.w_bits / abits;  // (w4a8 MXFP8: 4-bit B rows under 8-bit A rows)
+  if ((st = meta_row(p, idx, qt, v, kbytes, kbytes_b, true, m))) return st;
   if (check_ptrs && p.M > 0 && p.N > 0) {  // empty problems are dropped by the planner
     if (!p.A || !p.B || !p.C) return fail(MXMOE_GG_ERR_INVALID, "problem %d: NULL A/B/C", idx);
-    if (!is_float16(qt) && (!p.SA || !p.SB)) return fail(MXMOE_GG_ERR_INVALID, "problem %d: NULL scale pointer", idx);
+    if (!t.float16 && (!p.SA || !p.SB)) return fail(MXMOE_GG_ERR_INVALID, "problem %d: NULL scale pointer", idx);
     if (((uintptr_t)p.A | (uintptr_t)p.B | (uintptr_t)p.C) & 15)
       return fail(MXMOE_GG_ERR_INVALID, "problem %d: A/B/C must be 16-byte aligned", idx);
-    if (!is_float16(qt) && (((uintptr_t)p.SA | (uintptr_t)p.SB) & 1))
+    if (!t.float16 && (((uintptr_t)p.SA | (uintptr_t)p.SB) & 1))
       return fail(MXMOE_GG_ERR_INVALID, "problem %d: scales must be 2-byte aligned", idx);
-    if (qt == QT_MXF4 && (((uintptr_t)p.SA | (uintptr_t)p.SB) & 3))  // (the kernel reads scale dwords)
-      return fail(MXMOE_GG_ERR_INVALID, "problem %d: MXFP4 scales must be 4-byte aligned", idx);
-    if (qt == QT_MXF8A && (((uintptr_t)p.SA | (uintptr_t)p.SB) & 3))
-      return fail(MXMOE_GG_ERR_INVALID, "problem %d: w4a8_g32_sym_MXFP8 scales must be 4-byte aligned", idx);
+    if (t.dword_scales && (((uintptr_t)p.SA | (uintptr_t)p.SB) & 3))  // (the kernel reads scale dwords)
+      return fail(MXMOE_GG_ERR_INVALID, "problem %d: %s scales must be 4-byte aligned", idx, t.dword_scales);
   }
-  memset(m, 0, sizeof(*m));
-  m->M = p.M;
-  m->N = p.N;
-  m->K = p.K;
-  m->qtype = qt;
-  m->tiles_n = (p.N + v.geom[qt].bn - 1) / v.geom[qt].bn;
-  m->kbytes = (int32_t)kbytes;
-  m->reserved = qt == QT_I4G ? p.K / 128 : 0;  // w4a4 g128: scale groups
-  m->reserved2 = silu ? META_SILU : 0;
-  m->lda_b = lda_b;
-  m->ldb_b = ldb_b;
-  m->ldc = ldc;
+  m->reserved = t.group_fold ? p.K / t.k_mult : 0;  // w4a4 g128: scale groups
   return MXMOE_GG_OK;
+}
+
+// The planner's A/B switches: defaults are what the product plans with. Only the tools-only lab build
+// (-DMXMOE_LAB, libmxmoe_gg_lab.so) reads them from the environment (MXMOE_GG_<NAME>), once per plan: the
+// product library's tile placement never depends on the caller's environment.
+struct PlannerOpts {
+  double split_ratio_mul = 1.0;  // SPLIT_RATIO_MUL: scales the split-K ratio
+  int splitk_all = 0;            // SPLITK_ALL = S > 1: every problem in at least S K slices (where it has >= 4 S stages)
+  int band = 4;                  // BAND: m-tiles per band (n-major inside a band): a 32-tile chunk is band x (32 / band)
+  int ngroup = 1;                // NGROUP = G: inside a band, n-tiles in groups of G, m-major inside a group (1: n-major)
+  int region = 2;                // REGION: XCD regions 0 off, 1 at the queue head, 2 after the chunked tiles (measured 1-5 %
+                                 // faster than at the head on the w8a8 gate_up / down / mixed calls, profiles/r02/region/)
+  bool region_rot = false;       // REGION_ROT: XCD x starts its sweep x/8 along the swept axis (XCDs stream different panels)
+  bool align = true;             // ALIGN: problem-aligned chunks
+  int xcd_pack = 4;              // XCD_PACK: 0 off, 1 always head, 2 always tail, 3 head for long region tiles, 4 (pack_xcds)
+  int tail_chunk = 16;           // TAIL_CHUNK: tail chunk size
+  bool xcd_rr = false;           // XCD_RR: plain round-robin chunks
+  int tail_split = 0;            // TAIL_SPLIT: 1 on, 2 weight-only tiles too (split_tails)
+  bool mix = false;              // MIX (mix_residency)
+  bool lowfill_lpt = false;      // LOWFILL_LPT (lowfill_lpt)
+};
+PlannerOpts planner_opts() {
+  PlannerOpts o;
+#ifdef MXMOE_LAB
+  auto flag = [](const char* name, char c) { return getenv(name) && getenv(name)[0] == c; };
+  auto positive = [](const char* name, int dflt) { return getenv(name) && atoi(getenv(name)) > 0 ? atoi(getenv(name)) : dflt; };
+  if (const char* e = getenv("MXMOE_GG_SPLIT_RATIO_MUL")) o.split_ratio_mul = atof(e);
+  if (const char* e = getenv("MXMOE_GG_SPLITK_ALL")) o.splitk_all = atoi(e);
+  o.band = positive("MXMOE_GG_BAND", o.band);
+  o.ngroup = positive("MXMOE_GG_NGROUP", o.ngroup);
+  o.region = flag("MXMOE_GG_REGION", '0') ? 0 : flag("MXMOE_GG_REGION", '1') ? 1 : 2;
+  o.region_rot = flag("MXMOE_GG_REGION_ROT", '1');
+  o.align = !flag("MXMOE_GG_ALIGN", '0');
+  if (const char* e = getenv("MXMOE_GG_XCD_PACK")) o.xcd_pack = atoi(e);
+  o.tail_chunk = positive("MXMOE_GG_TAIL_CHUNK", o.tail_chunk);
+  o.xcd_rr = flag("MXMOE_GG_XCD_RR", '1');
+  o.tail_split = flag("MXMOE_GG_TAIL_SPLIT", '1') ? 1 : flag("MXMOE_GG_TAIL_SPLIT", '2') ? 2 : 0;
+  o.mix = flag("MXMOE_GG_MIX", '1');
+  o.lowfill_lpt = flag("MXMOE_GG_LOWFILL_LPT", '1');
+#endif
+  return o;
 }
 
 struct Plan {
@@ -900,445 +894,423 @@ struct Plan {
   int total_tiles = 0;
   int launch_grid = 0;          // workgroups launched (= tiles.size() unless persistent)
   int slabs = 0;                // split-K partial slabs
-  int tail_slabs = 0;           // of which for the tail split (plan_host)
+  int tail_slabs = 0;           // of which for the tail split (split_tails)
 };
 
-// Tile generation + scheduling.
-//  1. per problem: m-tiles of the variant's height (v2: 256-row tiles while > tail_bm rows remain,
-//     then one tail_bm (128) or tail2_bm (64) tile), n-tiles of width bn; 4-m-tile bands, n-major
-//     inside a band, so 32 consecutive tiles form a ~4 x 8 block sharing A rows and B columns;
-//  2. problems by descending per-tile cost (K bytes x tile area x MFMA passes), longest first;
-//  3. XCD regions: a problem of >= 8 chunks of tiles (the shared expert at large batch) is cut
-//     into 8 rectangles of its tile grid, one per XCD, at the head of that XCD's queue (region_of);
-//  4. the rest is cut into chunks of about `chunk` tiles that do not straddle problems; each chunk
-//     in turn joins the queue of the XCD with the least modelled time so far (tile_time); XCD x's
-//     i-th tile is blockIdx 8 i + x (blocks b and b + 8 share an XCD under the round-robin
-//     dispatch; placement affects speed and HBM traffic only, never results).
-int plan_host(const std::vector<HostProblem>& probs, int variant, bool check_ptrs, Plan* plan) {
-  const Variant& v = variants()[variant];
-  const int P = (int)probs.size();
-  std::vector<GGMeta> all(P);
-  for (int i = 0; i < P; ++i) {
-    int st = build_meta(probs[i], i, v, check_ptrs, &all[i]);
-    if (st) return st;
-  }
-  std::vector<int> order;
-  for (int i = 0; i < P; ++i)
-    if (probs[i].M > 0 && probs[i].N > 0) order.push_back(i);
-  // K stages of a problem in its tile body (v2: 128 B per stage; weight-only: 64 elements)
-  auto stages_of = [&](const GGMeta& m) {
-    if (is_weightonly(m.qtype)) return m.K / 64;
-    return (m.kbytes + v.geom[m.qtype].bkb - 1) / v.geom[m.qtype].bkb;
-  };
-  auto full_tile_cost = [&](int i) {
-    const GGMeta& m = all[i];
-    // int4: 2 MFMA passes per staged byte; g128 adds the per-group f32 fold (~25 %); fp6 images:
-    // one fp6 MFMA (the int8 one's cycles) per 96 B of K-128
-    // (MXFP4: per stage the MFMA count and cycles of the int8 tile, so 1.0)
-    const double passes = m.qtype == QT_I4 ? 2.0 : m.qtype == QT_I4G ? 2.5 : m.qtype == QT_I4F6 ? 128.0 / 96 / 2 : 1.0;
-    return passes * (double)m.kbytes * v.geom[m.qtype].bm * v.geom[m.qtype].bn;
-  };
-  // m-tiles of a problem: (m0, class); v2 classes 256 / 128 / 64 rows (see Variant::tail_bm)
-  auto class_rows = [&](int cls, const TileGeom& g) { return cls == 0 ? g.bm : cls == 1 ? v.tail_bm : v.tail2_bm; };
-  auto m_tiles = [&](const GGMeta& m) {
-    const TileGeom& g = v.geom[m.qtype];
-    std::vector<std::pair<int, int>> mt;
-    for (int m0 = 0; m0 < m.M;) {
-      const int rem = m.M - m0;
-      const bool small_class = is_float16(m.qtype) || is_weightonly(m.qtype);
-      if (v.kind != Kind::V0 && v.tail2_bm && small_class && rem <= v.tail2_bm) {
-        mt.push_back({m0, 2});
-        m0 += v.tail2_bm;
-      } else if (v.kind != Kind::V0 && v.tail_bm && rem <= v.tail_bm) {
-        mt.push_back({m0, 1});
-        m0 += v.tail_bm;
-      } else {
-        mt.push_back({m0, 0});
-        m0 += g.bm;
-      }
-    }
-    return mt;
-  };
-  // split-K (v2 kernels): a problem whose largest tile is far longer than one CU's share of the
-  // whole call (low-fill calls: small batches, long-K shared experts, per-rank work lists) has its
-  // tiles cut into split[i] K slices of >= 4 stages each, at most 8
-  std::vector<int> split(P, 1);
-  if (v.kind == Kind::V2) {
-    double total = 0;
-    std::vector<double> biggest(P, 0.0);
-    for (int i : order) {
-      const GGMeta& m = all[i];
-      const TileGeom& g = v.geom[m.qtype];
-      const double per_row = full_tile_cost(i) / g.bm;
-      for (const auto& t : m_tiles(m)) {
-        const double c = per_row * class_rows(t.second, g);
-        total += c * m.tiles_n;
-        biggest[i] = std::max(biggest[i], c);
-      }
-    }
-    const double share = total / (kSplitCUs * v.chunk / 32);  // workgroup slots: CUs x workgroups per CU
-    const char* rmul_env = planner_knob("MXMOE_GG_SPLIT_RATIO_MUL");  // lab A/B: scale the ratio
-    const double rmul = rmul_env ? atof(rmul_env) : 1.0;
-    for (int i : order) {
-      const double ratio = rmul * biggest[i] / std::max(share, 1.0);
-      // (w4a4 g128 never splits: summing f32 partial folds would change the rounding)
-      if (ratio > 2.0 && all[i].qtype != QT_I4G) split[i] = std::max(1, std::min({8, (int)ratio, stages_of(all[i]) / 4}));
-    }
-    // lab A/B switch: every problem split into at least S K slices (where it has >= 4 S stages)
-    const char* sall = planner_knob("MXMOE_GG_SPLITK_ALL");
-    if (sall && atoi(sall) > 1)
-      for (int i : order)
-        if (all[i].qtype != QT_I4G)
-          split[i] = std::max(split[i], std::max(1, std::min({8, atoi(sall), stages_of(all[i]) / 4})));
-  }
-  // Tile time model (per K stage, in "bytes": one stage's LDS-DMA bytes or its MFMA work at the
-  // fp16 rate of 128 flop/B, whichever is larger, plus a fixed 24 KiB-equivalent per stage).
-  // Fitted to the tile timelines (profiles/r01/session3/trace_bs512.jsonl): 64-row /
-  // 256-row tile time ratios 1.3 (fp16) and 2.1 (w4a16), where tile area alone says 4.
-  auto stage_time = [&](const GGMeta& m, int cls) {
-    const TileGeom& g = v.geom[m.qtype];
-    const double rows = class_rows(cls, g), cols = g.bn;
-    double bytes, equiv;
-    if (is_weightonly(m.qtype)) {  // 64 K elements per stage, fp16 A
-      // (weight-only MXFP4: the 4-bit stage; its 2 scale bytes per column are 1/16 of the codes)
-      bytes = rows * 128 + cols * 64 * (m.qtype == QT_W2A16 ? 2 : (m.qtype == QT_W4A16 || m.qtype == QT_MXF4W) ? 4 : 8) / 8.0;
-      equiv = 2.0 * rows * cols * 64 / 128;
-    } else {
-      const double kel = m.qtype == QT_I4F6 ? 128.0
-                       : g.bkb * 8.0 / (is_float16(m.qtype) ? 16 : (m.qtype == QT_I8 || m.qtype == QT_F8 || m.qtype == QT_MXF8A) ? 8 : 4);
-      const double rate = is_float16(m.qtype) ? 128 : (m.qtype == QT_I4F6 || m.qtype == QT_MXF4) ? 512 : 256, fold = m.qtype == QT_I4G ? 1.25 : 1.0;
-      bytes = (rows + cols) * g.bkb;
-      equiv = 2.0 * rows * cols * kel / rate * fold;
-    }
-    return std::max(bytes, equiv) + 24576.0;
-  };
-  // problems by the modelled time of their first (tallest) tile, longest first
-  std::vector<double> tile_cost(P, 0.0);
-  for (int i : order) tile_cost[i] = stage_time(all[i], m_tiles(all[i])[0].second) * stages_of(all[i]) / split[i];
-  std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return tile_cost[a] > tile_cost[b]; });
+constexpr TileDesc kEmptySlot = {-1, 0, 0, 0, 0, 0, -1, -1};
 
-  // m-tiles per band (n-major inside a band): a 32-tile chunk is band x (32 / band) tiles
-  const char* band_env = planner_knob("MXMOE_GG_BAND");  // A/B switch (default 4)
-  const size_t band = band_env && atoi(band_env) > 0 ? (size_t)atoi(band_env) : 4;
-  const char* ngroup_env = planner_knob("MXMOE_GG_NGROUP");  // A/B switch (default 1)
-  const int ngroup = ngroup_env && atoi(ngroup_env) > 0 ? atoi(ngroup_env) : 1;
-  plan->meta.clear();
-  plan->order = order;
-  plan->slabs = 0;
-  plan->tail_slabs = 0;
-  const int chunk = v.chunk;
-  // XCD regions. Within one XCD, consecutive tiles run together (the XCD hands each freed CU its
-  // next block), so a band's A rows and B columns are re-read from that XCD's L2 while they are
-  // hot; but under chunked LPT a 4-m-tile band of the 44 n-tile shared expert lands on ~5 XCDs and
-  // each fetches the band's A panels again (and every band its B panels): 528 MB of panel reads
-  // for 78 MB of operands at bs=8192. One rectangle per XCD (r m-tiles x c n-tiles, enumerated in
-  // bands of `band` along the cheaper axis) reads r A panels + ceil(r / band) * c B panels (or the
-  // transpose) — the split of the grid into 8 rectangles is chosen to minimise that sum.
-  // placement: after the chunked tiles (default; measured 1-5 % faster than at the queue head on the
-  // w8a8 gate_up / down / mixed calls, profiles/r02/region/)
-  const char* region_env = planner_knob("MXMOE_GG_REGION");  // A/B switch: 0 off, 1 queue head, 2 tail (default)
-  const bool regions_on = !(region_env && region_env[0] == '0');
-  const bool regions_last = !(region_env && region_env[0] == '1');
-  const char* rot_env = planner_knob("MXMOE_GG_REGION_ROT");  // A/B switch (default off)
-  const bool region_rot = rot_env && rot_env[0] == '1';
-  const char* align_env = planner_knob("MXMOE_GG_ALIGN");  // A/B switch: problem-aligned chunks (default on)
-  const bool align_on = !(align_env && align_env[0] == '0');
-  struct Region {
-    int gm = 0, gn = 0, r = 0, c = 0;
-    bool nband = false;  // true: bands of n-tiles, m-major inside
-  };
-  auto region_of = [&](int i, Region* out) {
-    const GGMeta& m = all[i];
-    const int mt = (int)m_tiles(m).size(), nt = m.tiles_n;
-    if (!regions_on || v.kind != Kind::V2 || split[i] != 1 || (int64_t)mt * nt < 8 * (int64_t)chunk) return false;
-    const TileGeom& g = v.geom[m.qtype];
-    const double a_panel = (double)g.bm * m.kbytes, b_panel = (double)g.bn * m.K * probs[i].w_bits / 8.0;
-    double best = 0;
-    for (int gm = 1; gm <= 8; gm *= 2) {
-      const int gn = 8 / gm;
-      if (mt < gm || nt < gn) continue;
-      const int r = (mt + gm - 1) / gm, c = (nt + gn - 1) / gn;
-      // every region non-empty and within 25 % of the largest (the LPT fill evens out the rest)
-      const int r_last = mt - (gm - 1) * r, c_last = nt - (gn - 1) * c;
-      if (r_last <= 0 || c_last <= 0 || 4 * (int64_t)r_last * c_last < 3 * (int64_t)r * c) continue;
-      const int b = (int)band;
-      const double mband = r * a_panel + (double)((r + b - 1) / b) * c * b_panel;
-      const double nband = c * b_panel + (double)((c + b - 1) / b) * r * a_panel;
-      const double cost = std::min(mband, nband);
-      if (out->gm == 0 || cost < best) {
-        *out = Region{gm, gn, r, c, nband < mband};
-        best = cost;
-      }
+// K stages of a problem in its tile body (v2: 128 B per stage; weight-only: 64 elements)
+int stages_of(const Variant& v, const GGMeta& m) {
+  if (qinfo(m.qtype).weight_only) return m.K / 64;
+  return (m.kbytes + v.geom[m.qtype].bkb - 1) / v.geom[m.qtype].bkb;
+}
+double full_tile_cost(const Variant& v, const GGMeta& m) {
+  return qinfo(m.qtype).passes * (double)m.kbytes * v.geom[m.qtype].bm * v.geom[m.qtype].bn;
+}
+// rows of an m-tile class; v2 classes 256 / 128 / 64 rows (see Variant::tail_bm)
+int class_rows(const Variant& v, int cls, const TileGeom& g) { return cls == 0 ? g.bm : cls == 1 ? v.tail_bm : v.tail2_bm; }
+// m-tiles of a problem: (m0, class). v2: 256-row tiles while > tail_bm rows remain, then one tail_bm (128)
+// or tail2_bm (64) tile
+std::vector<std::pair<int, int>> m_tiles(const Variant& v, const GGMeta& m) {
+  const TileGeom& g = v.geom[m.qtype];
+  std::vector<std::pair<int, int>> mt;
+  for (int m0 = 0; m0 < m.M;) {
+    const int rem = m.M - m0;
+    if (v.kind != Kind::V0 && v.tail2_bm && qinfo(m.qtype).small_class && rem <= v.tail2_bm) {
+      mt.push_back({m0, 2});
+      m0 += v.tail2_bm;
+    } else if (v.kind != Kind::V0 && v.tail_bm && rem <= v.tail_bm) {
+      mt.push_back({m0, 1});
+      m0 += v.tail_bm;
+    } else {
+      mt.push_back({m0, 0});
+      m0 += g.bm;
     }
-    return out->gm != 0;
-  };
-  int groups = 0, n_region = 0;
-  bool region_a16 = false;
-  std::vector<TileDesc> seq;                // chunked tiles
-  std::vector<int> seq_end;                 // per seq tile: end of its problem's run in seq
-  std::vector<std::vector<TileDesc>> region_tiles(8);  // per XCD
-  for (int row = 0; row < (int)order.size(); ++row) {
-    GGMeta m = all[order[row]];
+  }
+  return mt;
+}
+
+// split-K (v2 kernels): a problem whose largest tile is far longer than one CU's share of the
+// whole call (low-fill calls: small batches, long-K shared experts, per-rank work lists) has its
+// tiles cut into split[i] K slices of >= 4 stages each, at most 8
+std::vector<int> split_factors(const Variant& v, const std::vector<GGMeta>& all, const std::vector<int>& order,
+                               const PlannerOpts& o) {
+  std::vector<int> split(all.size(), 1);
+  if (v.kind != Kind::V2) return split;
+  double total = 0;
+  std::vector<double> biggest(all.size(), 0.0);
+  for (int i : order) {
+    const GGMeta& m = all[i];
     const TileGeom& g = v.geom[m.qtype];
-    const std::vector<std::pair<int, int>> mt = m_tiles(m);  // (m0, cls)
-    m.tile_begin = (int32_t)seq.size();
-    const int nt = m.tiles_n, S = split[order[row]], nst = stages_of(m);
+    const double per_row = full_tile_cost(v, m) / g.bm;
+    for (const auto& t : m_tiles(v, m)) {
+      const double c = per_row * class_rows(v, t.second, g);
+      total += c * m.tiles_n;
+      biggest[i] = std::max(biggest[i], c);
+    }
+  }
+  const double share = total / (kSplitCUs * v.chunk / 32);  // workgroup slots: CUs x workgroups per CU
+  for (int i : order) {
+    const double ratio = o.split_ratio_mul * biggest[i] / std::max(share, 1.0);
+    if (ratio > 2.0 && !qinfo(all[i].qtype).group_fold)
+      split[i] = std::max(1, std::min({8, (int)ratio, stages_of(v, all[i]) / 4}));
+  }
+  if (o.splitk_all > 1)
+    for (int i : order)
+      if (!qinfo(all[i].qtype).group_fold)
+        split[i] = std::max(split[i], std::max(1, std::min({8, o.splitk_all, stages_of(v, all[i]) / 4})));
+  return split;
+}
+
+// Tile time model (per K stage, in "bytes": one stage's LDS-DMA bytes or its MFMA work at the
+// fp16 rate of 128 flop/B, whichever is larger, plus a fixed 24 KiB-equivalent per stage).
+// Fitted to the tile timelines (profiles/r01/session3/trace_bs512.jsonl): 64-row /
+// 256-row tile time ratios 1.3 (fp16) and 2.1 (w4a16), where tile area alone says 4.
+double stage_time(const Variant& v, const GGMeta& m, int cls) {
+  const TileGeom& g = v.geom[m.qtype];
+  const QTypeInfo& t = qinfo(m.qtype);
+  const double rows = class_rows(v, cls, g), cols = g.bn;
+  double bytes, equiv;
+  if (t.weight_only) {  // 64 K elements per stage, fp16 A
+    bytes = rows * 128 + cols * 64 * t.code_bits / 8.0;
+    equiv = 2.0 * rows * cols * 64 / 128;
+  } else {
+    const double kel = t.el_bits ? g.bkb * 8.0 / t.el_bits : 128.0;
+    bytes = (rows + cols) * g.bkb;
+    equiv = 2.0 * rows * cols * kel / t.rate * t.fold;
+  }
+  return std::max(bytes, equiv) + 24576.0;
+}
+// modelled time of a planned tile (td.prob: a row of `meta`)
+struct TileTimer {
+  const Variant& v;
+  const std::vector<GGMeta>& meta;
+  double operator()(const TileDesc& td) const { return stage_time(v, meta[td.prob], td.cls & 0xFF) * (td.ks1 - td.ks0); }
+};
+
+// XCD regions. Within one XCD, consecutive tiles run together (the XCD hands each freed CU its
+// next block), so a band's A rows and B columns are re-read from that XCD's L2 while they are
+// hot; but under chunked LPT a 4-m-tile band of the 44 n-tile shared expert lands on ~5 XCDs and
+// each fetches the band's A panels again (and every band its B panels): 528 MB of panel reads
+// for 78 MB of operands at bs=8192. One rectangle per XCD (r m-tiles x c n-tiles, enumerated in
+// bands of `band` along the cheaper axis) reads r A panels + ceil(r / band) * c B panels (or the
+// transpose) — the split of the grid into 8 rectangles is chosen to minimise that sum.
+struct Region {
+  int gm = 0, gn = 0, r = 0, c = 0;
+  bool nband = false;  // true: bands of n-tiles, m-major inside
+};
+// the regions of a problem of >= 8 chunks of tiles (mt x m.tiles_n, unsplit), if it is cut into any
+bool region_of(const Variant& v, const GGMeta& m, int w_bits, int mt, const PlannerOpts& o, Region* out) {
+  const int nt = m.tiles_n;
+  if (o.region == 0 || v.kind != Kind::V2 || (int64_t)mt * nt < 8 * (int64_t)v.chunk) return false;
+  const TileGeom& g = v.geom[m.qtype];
+  const double a_panel = (double)g.bm * m.kbytes, b_panel = (double)g.bn * m.K * w_bits / 8.0;
+  double best = 0;
+  for (int gm = 1; gm <= 8; gm *= 2) {
+    const int gn = 8 / gm;
+    if (mt < gm || nt < gn) continue;
+    const int r = (mt + gm - 1) / gm, c = (nt + gn - 1) / gn;
+    // every region non-empty and within 25 % of the largest (the LPT fill evens out the rest)
+    const int r_last = mt - (gm - 1) * r, c_last = nt - (gn - 1) * c;
+    if (r_last <= 0 || c_last <= 0 || 4 * (int64_t)r_last * c_last < 3 * (int64_t)r * c) continue;
+    const int b = o.band;
+    const double mband = r * a_panel + (double)((r + b - 1) / b) * c * b_panel;
+    const double nband = c * b_panel + (double)((c + b - 1) / b) * r * a_panel;
+    const double cost = std::min(mband, nband);
+    if (out->gm == 0 || cost < best) {
+      *out = Region{gm, gn, r, c, nband < mband};
+      best = cost;
+    }
+  }
+  return out->gm != 0;
+}
+
+// The call's tiles in enumeration order, before they are placed on XCDs.
+struct TileLists {
+  std::vector<TileDesc> seq;                          // chunked tiles, problem after problem
+  std::vector<int> seq_end;                           // per seq tile: end of its problem's run in seq
+  std::vector<std::vector<TileDesc>> region_tiles{8}; // region problems' tiles, per XCD
+  int groups = 0;                                     // split-K groups so far
+  int n_region = 0;                                   // region problems
+  bool region_a16 = false;                            // ... one of them with 16-bit A
+};
+// Tile enumeration, problems in `plan->order` (table-row order): a region problem's rectangles go to
+// region_tiles; every other problem's tiles to seq in 4-m-tile bands, n-major inside a band, so 32
+// consecutive tiles form a ~4 x 8 block sharing A rows and B columns. Fills plan->meta and counts plan->slabs.
+TileLists enumerate_tiles(const Variant& v, const std::vector<GGMeta>& all, const std::vector<HostProblem>& probs,
+                          const std::vector<int>& split, const PlannerOpts& o, Plan* plan) {
+  TileLists tl;
+  const int band = o.band;
+  for (int row = 0; row < (int)plan->order.size(); ++row) {
+    const int i = plan->order[row];
+    GGMeta m = all[i];
+    const TileGeom& g = v.geom[m.qtype];
+    const std::vector<std::pair<int, int>> mt = m_tiles(v, m);  // (m0, cls)
+    m.tile_begin = (int32_t)tl.seq.size();
+    const int nt = m.tiles_n, S = split[i], nst = stages_of(v, m);
     Region rg;
-    if (region_of(order[row], &rg)) {
-      ++n_region;
-      region_a16 = region_a16 || probs[order[row]].a_bits == 16;
+    if (S == 1 && region_of(v, m, probs[i].w_bits, (int)mt.size(), o, &rg)) {
+      ++tl.n_region;
+      tl.region_a16 = tl.region_a16 || probs[i].a_bits == 16;
       for (int x = 0; x < 8; ++x) {
         const int mb0 = (x / rg.gn) * rg.r, mb1 = std::min((int)mt.size(), mb0 + rg.r);
         const int nb0 = (x % rg.gn) * rg.c, nb1 = std::min(nt, nb0 + rg.c);
         auto put = [&](int mi, int n) {
-          region_tiles[x].push_back(TileDesc{row, mt[mi].first, n * g.bn, mt[mi].second, 0, nst, -1, -1});
+          tl.region_tiles[x].push_back(TileDesc{row, mt[mi].first, n * g.bn, mt[mi].second, 0, nst, -1, -1});
         };
-        // (MXMOE_GG_REGION_ROT: XCD x starts its sweep x/8 of the way along the swept axis, so the
-        // XCDs do not all stream the same panels at the same time)
         const int span_n = nb1 - nb0, span_m = mb1 - mb0;
-        const int rot_n = region_rot && span_n > 0 ? (x * span_n / 8) : 0;
-        const int rot_m = region_rot && span_m > 0 ? (x * span_m / 8) : 0;
+        const int rot_n = o.region_rot && span_n > 0 ? (x * span_n / 8) : 0;
+        const int rot_m = o.region_rot && span_m > 0 ? (x * span_m / 8) : 0;
         if (rg.nband) {
-          for (int nb = nb0; nb < nb1; nb += (int)band)
+          for (int nb = nb0; nb < nb1; nb += band)
             for (int k = 0; k < span_m; ++k) {
               const int mi = mb0 + (k + rot_m) % span_m;
-              for (int n = nb; n < std::min(nb1, nb + (int)band); ++n) put(mi, n);
+              for (int n = nb; n < std::min(nb1, nb + band); ++n) put(mi, n);
             }
         } else {
-          for (int mb = mb0; mb < mb1; mb += (int)band)
+          for (int mb = mb0; mb < mb1; mb += band)
             for (int k = 0; k < span_n; ++k) {
               const int n = nb0 + (k + rot_n) % span_n;
-              for (int mi = mb; mi < std::min(mb1, mb + (int)band); ++mi) put(mi, n);
+              for (int mi = mb; mi < std::min(mb1, mb + band); ++mi) put(mi, n);
             }
         }
       }
       plan->meta.push_back(m);
       continue;
     }
-    // (lab A/B, MXMOE_GG_NGROUP = G: inside a band, n-tiles in groups of G, m-major inside a group —
-    // G = 1 is the default n-major order, G >= tiles_n m-major)
     for (size_t mb = 0; mb < mt.size(); mb += band)
-      for (int ng = 0; ng < nt; ng += ngroup)
+      for (int ng = 0; ng < nt; ng += o.ngroup)
         for (size_t mi = mb; mi < std::min(mt.size(), mb + band); ++mi)
-          for (int n = ng; n < std::min(nt, ng + ngroup); ++n) {
-          if (S == 1) {
-            seq.push_back(TileDesc{row, mt[mi].first, n * g.bn, mt[mi].second, 0, nst, -1, -1});
-            continue;
+          for (int n = ng; n < std::min(nt, ng + o.ngroup); ++n) {
+            if (S == 1) {
+              tl.seq.push_back(TileDesc{row, mt[mi].first, n * g.bn, mt[mi].second, 0, nst, -1, -1});
+              continue;
+            }
+            const int grp = tl.groups++, slab = plan->slabs;
+            plan->slabs += S;
+            for (int k = 0; k < S; ++k)  // slices of one tile are consecutive: they start together
+              tl.seq.push_back(TileDesc{row, mt[mi].first, n * g.bn, mt[mi].second | (k << 8) | (S << 16),
+                                        k * nst / S, (k + 1) * nst / S, slab, grp});
           }
-          const int grp = groups++, slab = plan->slabs;
-          plan->slabs += S;
-          for (int k = 0; k < S; ++k)  // slices of one tile are consecutive: they start together
-            seq.push_back(TileDesc{row, mt[mi].first, n * g.bn, mt[mi].second | (k << 8) | (S << 16),
-                                   k * nst / S, (k + 1) * nst / S, slab, grp});
-        }
-    seq_end.resize(seq.size(), (int)seq.size());
+    tl.seq_end.resize(tl.seq.size(), (int)tl.seq.size());
     plan->meta.push_back(m);
   }
-  size_t T_head = 0;
-  for (const auto& h : region_tiles) T_head += h.size();
-  const int T = (int)(seq.size() + T_head);
-  if (T > (1 << 28)) return fail(MXMOE_GG_ERR_INVALID, "too many tiles (%d)", T);
-  auto tile_time = [&](const TileDesc& td) {
-    return stage_time(plan->meta[td.prob], td.cls & 0xFF) * (td.ks1 - td.ks0);
-  };
-  // XCD queues (XCD x's i-th tile is block 8 i + x). Chunks in LPT order: full chunks join the
-  // XCD queue with the least modelled time; the last 16 chunks' worth of tiles go in chunks of
-  // `tail_chunk`, each to the XCD whose simulated finish grows least (ties: least total time) —
-  // every XCD simulated as `chunk` workgroup slots taking its queue in order, as the hardware
-  // hands a freed slot the XCD's next block. Plain round-robin chunks let a low-fill call's few
-  // long tiles pile onto 2-3 XCDs (bs=512: per-XCD busy time 40 % apart).
-  struct XcdSim {
-    std::vector<double> slot;  // min-heap of slot free times
-    double finish = 0, load = 0;
-    void add(double t) {
-      std::pop_heap(slot.begin(), slot.end(), std::greater<double>());
-      slot.back() += t;
-      finish = std::max(finish, slot.back());
-      std::push_heap(slot.begin(), slot.end(), std::greater<double>());
-      load += t;
-    }
-  };
-  std::vector<XcdSim> sim(8);
-  for (auto& x : sim) x.slot.assign(chunk, 0.0);
-  std::vector<std::vector<int>> queue(8);  // indices into `all_tiles`: region tiles first, then chunks
-  std::vector<TileDesc> all_tiles(seq);
-  auto put_regions = [&]() {
-    for (int x = 0; x < 8; ++x)
-      for (const TileDesc& td : region_tiles[x]) {
-        sim[x].add(tile_time(td));
-        queue[x].push_back((int)all_tiles.size());
-        all_tiles.push_back(td);
-      }
-  };
-  const int TS = (int)seq.size();
-  // XCD packing (lab A/B: MXMOE_GG_XCD_PACK = 1 region tiles at the queue head,
-  // 2 at the tail). A call with region problems (the shared expert) and small ones (routed experts):
-  // every small problem goes WHOLE to one XCD — LPT over the problems' modelled loads, so its A / B
-  // panels live in one L2 — and the region problems' tiles, taken in rectangle order, are the filler
-  // that levels the XCDs: tile by tile to the XCD of least modelled load, then cut into consecutive
-  // pieces (XCD x's piece overlaps its rectangle, so the panel reuse of the rectangles is kept).
-  // Default (pack 4, product): packing for the MoE call shape — ONE region problem (the shared expert)
-  // beside >= 8 whole small problems — with the region tiles at the queue head when they are the long
-  // ones (down: K 4x the routed K; LPT) or when the region problem's A is 16-bit (its panels stream
-  // twice the bytes per flop: the fp16 gate_up call's head placement cut its counter bytes 2.97 ->
-  // 2.35 GB and ran 2.4 % faster, where w8a8 gate_up at the head ran 4 % slower, profiles/r06/pack/;
-  // an arithmetic-intensity cut in its place also sent the int calls of small batches to the head,
-  // 3-8 % slower at bs 2048, profiles/r06/plan3/); every other call keeps the chunked placement. Lab A/B:
-  // MXMOE_GG_XCD_PACK = 0 off, 1 always head, 2 always tail, 3 head only for long region tiles.
-  const char* pack_env = planner_knob("MXMOE_GG_XCD_PACK");
-  const int pack = pack_env ? atoi(pack_env) : 4;
-  bool packed = false;
-  int n_small = 0;
-  for (int s0 = 0; s0 < TS; s0 = seq_end[s0]) ++n_small;
-  const bool moe_shape = n_region == 1 && n_small >= 8;
-  if (pack > 0 && T_head > 0 && v.kind == Kind::V2 && !v.persistent && (pack != 4 || moe_shape)) {
-    std::vector<std::pair<int, int>> runs;  // [s0, s1) of one problem's tiles in seq
-    for (int s0 = 0; s0 < TS; s0 = seq_end[s0]) runs.push_back({s0, seq_end[s0]});
-    std::vector<double> rl(runs.size(), 0.0);
-    for (size_t r = 0; r < runs.size(); ++r)
-      for (int s = runs[r].first; s < runs[r].second; ++s) rl[r] += tile_time(seq[s]);
-    std::vector<int> ro(runs.size());
-    for (size_t r = 0; r < ro.size(); ++r) ro[r] = (int)r;
-    std::stable_sort(ro.begin(), ro.end(), [&](int a, int b) { return rl[a] > rl[b]; });
-    double load[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    std::vector<std::vector<int>> small_q(8);
-    for (int r : ro) {
-      int x = 0;
-      for (int y = 1; y < 8; ++y)
-        if (load[y] < load[x]) x = y;
-      load[x] += rl[r];
-      for (int s = runs[r].first; s < runs[r].second; ++s) small_q[x].push_back(s);
-    }
-    std::vector<TileDesc> big;
-    for (int x = 0; x < 8; ++x) big.insert(big.end(), region_tiles[x].begin(), region_tiles[x].end());
-    int cnt[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    for (const TileDesc& td : big) {
-      int x = 0;
-      for (int y = 1; y < 8; ++y)
-        if (load[y] < load[x]) x = y;
-      load[x] += tile_time(td);
-      ++cnt[x];
-    }
-    // the XCD's queue as its slots take it: region tiles first (pack 1) or last, and the queue's last
-    // 2 * chunk tiles longest first (the tail tiles of the routed bands are the short ones: LPT at the
-    // end evens the slots' finish; earlier tiles keep the band order)
-    // pack 3: at the head when the region tiles are the long ones (the down call's shared expert, 4x
-    // the routed K: LPT), at the tail otherwise (gate_up: every tile the same length)
-    bool head = pack == 1;
-    if (pack >= 3) {
-      double tb = 0, ts = 0;
-      for (const TileDesc& td : big) tb += tile_time(td);
-      for (int e = 0; e < TS; ++e) ts += tile_time(seq[e]);
-      head = !big.empty() && TS > 0 && tb / big.size() >= 1.5 * ts / TS;
-      if (pack == 4) head = head || region_a16;  // a 16-bit region problem (fp16 / bf16 / weight-only A)
-    }
-    // XCD x's region tiles: first its own rectangle (region_tiles[x], in band order) up to cnt[x]; the
-    // rectangles' surplus tails then fill the XCDs that take more than their own (a piece stays one
-    // rectangle plus at most a band's worth of a neighbour: the panel reuse the rectangles bought)
-    std::vector<size_t> rb(9, 0);
-    for (int x = 0; x < 8; ++x) rb[x + 1] = rb[x] + region_tiles[x].size();
-    std::vector<std::vector<int>> pieces(8);
-    auto assign_pieces = [&]() {
-      std::vector<int> pool;
-      for (int x = 0; x < 8; ++x) {
-        pieces[x].clear();
-        const size_t own = rb[x + 1] - rb[x], take = std::min(own, (size_t)cnt[x]);
-        for (size_t k = 0; k < own; ++k) (k < take ? pieces[x] : pool).push_back((int)(rb[x] + k));
-      }
-      size_t p = 0;
-      for (int x = 0; x < 8; ++x)
-        while ((int)pieces[x].size() < cnt[x] && p < pool.size()) pieces[x].push_back(pool[p++]);
-    };
-    auto build_q = [&](int x, std::vector<int>* q) {
-      q->clear();
-      std::vector<int> bq;
-      for (int k : pieces[x]) bq.push_back(-1 - k);  // (big tiles: -1 - index)
-      if (head) *q = bq;
-      q->insert(q->end(), small_q[x].begin(), small_q[x].end());
-      if (!head) q->insert(q->end(), bq.begin(), bq.end());
-      const size_t n = q->size(), tail = std::min(n, (size_t)(2 * chunk));
-      auto tt = [&](int e) { return e < 0 ? tile_time(big[-1 - e]) : tile_time(seq[e]); };
-      std::stable_sort(q->end() - tail, q->end(), [&](int a, int b) { return tt(a) > tt(b); });
-    };
-    auto finish_of = [&](const std::vector<int>& q) {
-      XcdSim xs;
-      xs.slot.assign(chunk, 0.0);
-      for (int e : q) xs.add(e < 0 ? tile_time(big[-1 - e]) : tile_time(seq[e]));
-      return xs.finish;
-    };
-    // local search: move one region tile from the XCD that finishes last to the one that finishes
-    // first while the modelled makespan drops (the loads above are level; the slots' finish is not)
-    std::vector<std::vector<int>> q(8);
-    double fin[8];
-    auto rebuild = [&]() {
-      assign_pieces();
-      for (int x = 0; x < 8; ++x) {
-        build_q(x, &q[x]);
-        fin[x] = finish_of(q[x]);
-      }
-    };
-    rebuild();
-    // (compared as the sorted finish vector, latest first: a move that takes one of several XCDs off
-    // the makespan counts as a gain)
-    auto key = [&]() {
-      std::vector<double> f(fin, fin + 8);
-      std::sort(f.begin(), f.end(), std::greater<double>());
-      return f;
-    };
-    for (int it = 0; it < 128; ++it) {
-      int hi = 0, lo = 0;
-      for (int x = 1; x < 8; ++x) {
-        if (fin[x] > fin[hi]) hi = x;
-        if (fin[x] < fin[lo]) lo = x;
-      }
-      if (cnt[hi] == 0 || hi == lo) break;
-      const std::vector<double> before = key();
-      --cnt[hi];
-      ++cnt[lo];
-      rebuild();
-      if (!(key() < before)) {  // no gain: undo and stop
-        ++cnt[hi];
-        --cnt[lo];
-        rebuild();
-        break;
-      }
-    }
-    const int base = (int)all_tiles.size();
-    all_tiles.insert(all_tiles.end(), big.begin(), big.end());
-    for (int x = 0; x < 8; ++x) {
-      queue[x].clear();
-      for (int e : q[x]) queue[x].push_back(e < 0 ? base + (-1 - e) : e);
-    }
-    packed = true;
+  return tl;
+}
+
+// One XCD simulated as `chunk` workgroup slots taking its queue in order (the hardware hands a freed slot the next block).
+struct XcdSim {
+  std::vector<double> slot;  // min-heap of slot free times
+  double finish = 0, load = 0;
+  void add(double t) {
+    std::pop_heap(slot.begin(), slot.end(), std::greater<double>());
+    slot.back() += t;
+    finish = std::max(finish, slot.back());
+    std::push_heap(slot.begin(), slot.end(), std::greater<double>());
+    load += t;
   }
-  if (!regions_last && !packed) put_regions();
-  const char* tc_env = planner_knob("MXMOE_GG_TAIL_CHUNK");  // A/B switch: tail chunk size (default 16)
-  const int tail_chunk = tc_env && atoi(tc_env) > 0 ? atoi(tc_env) : 16;
-  const char* rr_env = planner_knob("MXMOE_GG_XCD_RR");  // A/B switch: plain round-robin chunks
-  const bool round_robin = rr_env && rr_env[0] == '1';
-  for (int s0 = 0, c = 0; s0 < TS && !packed; ++c) {
+};
+// XCD queues (XCD x's i-th tile is block 8 i + x, round-robin dispatch; placement affects speed and HBM traffic only).
+struct XcdQueues {
+  std::vector<XcdSim> sim{8};
+  std::vector<std::vector<int>> queue{8};  // indices into `tiles`
+  std::vector<TileDesc> tiles;             // the chunked tiles (TileLists::seq) first
+};
+void put_regions(const TileLists& tl, const TileTimer& tile_time, XcdQueues* q) {
+  for (int x = 0; x < 8; ++x)
+    for (const TileDesc& td : tl.region_tiles[x]) {
+      q->sim[x].add(tile_time(td));
+      q->queue[x].push_back((int)q->tiles.size());
+      q->tiles.push_back(td);
+    }
+}
+
+// XCD packing, step 1: every small problem WHOLE to one XCD (LPT over the problems' modelled loads), then
+// how many region tiles each XCD takes to level the loads, and where in the queue they go.
+struct XcdPacking {
+  std::vector<std::vector<int>> small_q{8};  // per XCD: seq indices of its small problems' tiles
+  std::vector<TileDesc> big;                 // the region tiles in rectangle order
+  int cnt[8] = {0, 0, 0, 0, 0, 0, 0, 0};     // region tiles per XCD
+  bool head = false;                         // region tiles at the queue head
+};
+XcdPacking pack_loads(const TileLists& tl, const TileTimer& tile_time, int pack) {
+  XcdPacking p;
+  const int TS = (int)tl.seq.size();
+  std::vector<std::pair<int, int>> runs;  // [s0, s1) of one problem's tiles in seq
+  for (int s0 = 0; s0 < TS; s0 = tl.seq_end[s0]) runs.push_back({s0, tl.seq_end[s0]});
+  std::vector<double> rl(runs.size(), 0.0);
+  for (size_t r = 0; r < runs.size(); ++r)
+    for (int s = runs[r].first; s < runs[r].second; ++s) rl[r] += tile_time(tl.seq[s]);
+  std::vector<int> ro(runs.size());
+  for (size_t r = 0; r < ro.size(); ++r) ro[r] = (int)r;
+  std::stable_sort(ro.begin(), ro.end(), [&](int a, int b) { return rl[a] > rl[b]; });
+  double load[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  for (int r : ro) {
+    int x = 0;
+    for (int y = 1; y < 8; ++y)
+      if (load[y] < load[x]) x = y;
+    load[x] += rl[r];
+    for (int s = runs[r].first; s < runs[r].second; ++s) p.small_q[x].push_back(s);
+  }
+  for (int x = 0; x < 8; ++x) p.big.insert(p.big.end(), tl.region_tiles[x].begin(), tl.region_tiles[x].end());
+  for (const TileDesc& td : p.big) {
+    int x = 0;
+    for (int y = 1; y < 8; ++y)
+      if (load[y] < load[x]) x = y;
+    load[x] += tile_time(td);
+    ++p.cnt[x];
+  }
+  // pack 3: at the head when the region tiles are the long ones (the down call's shared expert, 4x
+  // the routed K: LPT), at the tail otherwise (gate_up: every tile the same length)
+  p.head = pack == 1;
+  if (pack >= 3) {
+    double tb = 0, ts = 0;
+    for (const TileDesc& td : p.big) tb += tile_time(td);
+    for (int e = 0; e < TS; ++e) ts += tile_time(tl.seq[e]);
+    p.head = !p.big.empty() && TS > 0 && tb / p.big.size() >= 1.5 * ts / TS;
+    if (pack == 4) p.head = p.head || tl.region_a16;  // a 16-bit region problem (fp16 / bf16 / weight-only A)
+  }
+  return p;
+}
+
+// XCD packing (lab A/B: MXMOE_GG_XCD_PACK = 1 region tiles at the queue head,
+// 2 at the tail). A call with region problems (the shared expert) and small ones (routed experts):
+// every small problem goes WHOLE to one XCD — LPT over the problems' modelled loads, so its A / B
+// panels live in one L2 — and the region problems' tiles, taken in rectangle order, are the filler
+// that levels the XCDs: tile by tile to the XCD of least modelled load, then cut into consecutive
+// pieces (XCD x's piece overlaps its rectangle, so the panel reuse of the rectangles is kept).
+// Default (pack 4, product): packing for the MoE call shape — ONE region problem (the shared expert)
+// beside >= 8 whole small problems — with the region tiles at the queue head when they are the long
+// ones (down: K 4x the routed K; LPT) or when the region problem's A is 16-bit (its panels stream
+// twice the bytes per flop: the fp16 gate_up call's head placement cut its counter bytes 2.97 ->
+// 2.35 GB and ran 2.4 % faster, where w8a8 gate_up at the head ran 4 % slower, profiles/r06/pack/;
+// an arithmetic-intensity cut in its place also sent the int calls of small batches to the head,
+// 3-8 % slower at bs 2048, profiles/r06/plan3/); every other call keeps the chunked placement. Lab A/B:
+// MXMOE_GG_XCD_PACK = 0 off, 1 always head, 2 always tail, 3 head only for long region tiles.
+// Returns false (queues untouched) when the call is not packed.
+bool pack_xcds(const Variant& v, const TileLists& tl, const TileTimer& tile_time, const PlannerOpts& o, XcdQueues* out) {
+  const int pack = o.xcd_pack, chunk = v.chunk, TS = (int)tl.seq.size();
+  size_t T_head = 0;
+  for (const auto& h : tl.region_tiles) T_head += h.size();
+  int n_small = 0;
+  for (int s0 = 0; s0 < TS; s0 = tl.seq_end[s0]) ++n_small;
+  const bool moe_shape = tl.n_region == 1 && n_small >= 8;
+  if (!(pack > 0 && T_head > 0 && v.kind == Kind::V2 && !v.persistent && (pack != 4 || moe_shape))) return false;
+  XcdPacking p = pack_loads(tl, tile_time, pack);
+  const std::vector<TileDesc>& big = p.big;
+  // XCD x's region tiles: first its own rectangle (region_tiles[x], in band order) up to cnt[x]; the
+  // rectangles' surplus tails then fill the XCDs that take more than their own (a piece stays one
+  // rectangle plus at most a band's worth of a neighbour: the panel reuse the rectangles bought)
+  std::vector<size_t> rb(9, 0);
+  for (int x = 0; x < 8; ++x) rb[x + 1] = rb[x] + tl.region_tiles[x].size();
+  std::vector<std::vector<int>> pieces(8);
+  auto assign_pieces = [&]() {
+    std::vector<int> pool;
+    for (int x = 0; x < 8; ++x) {
+      pieces[x].clear();
+      const size_t own = rb[x + 1] - rb[x], take = std::min(own, (size_t)p.cnt[x]);
+      for (size_t k = 0; k < own; ++k) (k < take ? pieces[x] : pool).push_back((int)(rb[x] + k));
+    }
+    size_t n = 0;
+    for (int x = 0; x < 8; ++x)
+      while ((int)pieces[x].size() < p.cnt[x] && n < pool.size()) pieces[x].push_back(pool[n++]);
+  };
+  auto tt = [&](int e) { return e < 0 ? tile_time(big[-1 - e]) : tile_time(tl.seq[e]); };
+  // the XCD's queue as its slots take it: region tiles first (head) or last, and the queue's last
+  // 2 * chunk tiles longest first (the tail tiles of the routed bands are the short ones: LPT at the
+  // end evens the slots' finish; earlier tiles keep the band order)
+  auto build_q = [&](int x, std::vector<int>* q) {
+    q->clear();
+    std::vector<int> bq;
+    for (int k : pieces[x]) bq.push_back(-1 - k);  // (big tiles: -1 - index)
+    if (p.head) *q = bq;
+    q->insert(q->end(), p.small_q[x].begin(), p.small_q[x].end());
+    if (!p.head) q->insert(q->end(), bq.begin(), bq.end());
+    const size_t n = q->size(), tail = std::min(n, (size_t)(2 * chunk));
+    std::stable_sort(q->end() - tail, q->end(), [&](int a, int b) { return tt(a) > tt(b); });
+  };
+  auto finish_of = [&](const std::vector<int>& q) {
+    XcdSim xs;
+    xs.slot.assign(chunk, 0.0);
+    for (int e : q) xs.add(tt(e));
+    return xs.finish;
+  };
+  // local search: move one region tile from the XCD that finishes last to the one that finishes
+  // first while the modelled makespan drops (the loads above are level; the slots' finish is not)
+  std::vector<std::vector<int>> q(8);
+  double fin[8];
+  auto rebuild = [&]() {
+    assign_pieces();
+    for (int x = 0; x < 8; ++x) {
+      build_q(x, &q[x]);
+      fin[x] = finish_of(q[x]);
+    }
+  };
+  rebuild();
+  // (compared as the sorted finish vector, latest first: a move that takes one of several XCDs off
+  // the makespan counts as a gain)
+  auto key = [&]() {
+    std::vector<double> f(fin, fin + 8);
+    std::sort(f.begin(), f.end(), std::greater<double>());
+    return f;
+  };
+  for (int it = 0; it < 128; ++it) {
+    int hi = 0, lo = 0;
+    for (int x = 1; x < 8; ++x) {
+      if (fin[x] > fin[hi]) hi = x;
+      if (fin[x] < fin[lo]) lo = x;
+    }
+    if (p.cnt[hi] == 0 || hi == lo) break;
+    const std::vector<double> before = key();
+    --p.cnt[hi];
+    ++p.cnt[lo];
+    rebuild();
+    if (!(key() < before)) {  // no gain: undo and stop
+      ++p.cnt[hi];
+      --p.cnt[lo];
+      rebuild();
+      break;
+    }
+  }
+  const int base = (int)out->tiles.size();
+  out->tiles.insert(out->tiles.end(), big.begin(), big.end());
+  for (int x = 0; x < 8; ++x) {
+    out->queue[x].clear();
+    for (int e : q[x]) out->queue[x].push_back(e < 0 ? base + (-1 - e) : e);
+  }
+  return true;
+}
+
+// Chunked LPT placement of the chunked tiles (tl.seq, problems longest first): full chunks of about
+// `chunk` tiles that do not straddle problems join the XCD queue with the least modelled time; the last
+// 16 chunks' worth of tiles go in chunks of `tail_chunk`, each to the XCD whose simulated finish grows
+// least (ties: least total time). Plain round-robin chunks let a low-fill call's few long tiles pile
+// onto 2-3 XCDs (bs=512: per-XCD busy time 40 % apart).
+void place_chunks(const Variant& v, const TileLists& tl, const TileTimer& tile_time, const PlannerOpts& o, XcdQueues* q) {
+  const int chunk = v.chunk, TS = (int)tl.seq.size();
+  for (int s0 = 0, c = 0; s0 < TS; ++c) {
     const bool head = TS - s0 > 16 * chunk;
-    int len = (round_robin || head) ? chunk : std::min(chunk, tail_chunk);
-    if (head && !round_robin && align_on) {
+    int len = (o.xcd_rr || head) ? chunk : std::min(chunk, o.tail_chunk);
+    if (head && !o.xcd_rr && o.align) {
       // whole problems per chunk: split the rest of this problem's run into near-equal chunks of
       // about `chunk` tiles (a 33-tile expert stays on one XCD instead of spilling 1 tile onto
       // another that re-fetches its A rows), at most 64
-      const int rem = seq_end[s0] - s0, nc = std::max(1, (rem + chunk / 2) / chunk);
+      const int rem = tl.seq_end[s0] - s0, nc = std::max(1, (rem + chunk / 2) / chunk);
       len = std::min(64, (rem + nc - 1) / nc);
     }
     const int s1 = std::min(TS, s0 + len);
     // (a chunk can be a whole XCD's slots: 96 for the 3-WG/CU kernel — sized per chunk, not fixed)
     std::vector<double> times(std::max(0, s1 - s0));
-    for (int s = s0; s < s1; ++s) times[s - s0] = tile_time(seq[s]);
+    for (int s = s0; s < s1; ++s) times[s - s0] = tile_time(tl.seq[s]);
     int best = c % 8;
-    if (!round_robin && head) {  // full chunks: least total time (cheap; the tail evens out)
+    if (!o.xcd_rr && head) {  // full chunks: least total time (cheap; the tail evens out)
       best = 0;
       for (int x = 1; x < 8; ++x)
-        if (sim[x].load < sim[best].load) best = x;
-    } else if (!round_robin) {  // tail: least simulated finish
+        if (q->sim[x].load < q->sim[best].load) best = x;
+    } else if (!o.xcd_rr) {  // tail: least simulated finish
       double best_finish = 0, best_load = 0;
       for (int x = 0; x < 8; ++x) {
-        XcdSim trial = sim[x];
+        XcdSim trial = q->sim[x];
         for (int s = s0; s < s1; ++s) trial.add(times[s - s0]);
         if (x == 0 || trial.finish < best_finish || (trial.finish == best_finish && trial.load < best_load)) {
           best = x;
@@ -1348,195 +1320,250 @@ int plan_host(const std::vector<HostProblem>& probs, int variant, bool check_ptr
       }
     }
     for (int s = s0; s < s1; ++s) {
-      sim[best].add(times[s - s0]);
-      queue[best].push_back(s);
+      q->sim[best].add(times[s - s0]);
+      q->queue[best].push_back(s);
     }
     s0 = s1;
   }
-  if (regions_last && !packed) put_regions();
+}
 
 #ifdef MXMOE_LAB
-  // Tail split (v2, not persistent). An XCD hands its blocks to its CUs in queue order, so the
-  // queue's last tiles run while most of the XCD's CUs have gone idle for good (w8a8 down at
-  // bs=8192: 194 tiles per XCD = 6 rounds of 32 + 2; tile timelines put the ragged finish at
-  // 6-8 % of CU time). Per XCD, the tiles that start after the first CU's last tile ended are cut
-  // along K into S consecutive slices (the split-K path above), S in 2..8 (>= 3 stages a slice,
-  // each slice priced at 2 extra stages for its fill and partial-sum traffic) chosen to minimise
-  // the XCD's simulated finish; kept only if that gains >= 1 %.
-  // MEASURED NEGATIVE: 1.5-2 % slower on the w8a8 / fp16 / mixed gate_up calls, the
-  // only layer-11 calls it cuts (the partial-sum round trip costs more than the ragged finish
-  // it removes). Lab library only, opt-in: MXMOE_GG_TAIL_SPLIT=1.
-  const char* ts_env = planner_knob("MXMOE_GG_TAIL_SPLIT");
-  if (v.kind == Kind::V2 && !v.persistent && ts_env && (ts_env[0] == '1' || ts_env[0] == '2')) {
-    auto simulate = [&](const std::vector<double>& t, std::vector<double>* starts) {
-      std::vector<double> slot(chunk, 0.0);  // min-heap of slot free times
-      double finish = 0;
-      for (size_t j = 0; j < t.size(); ++j) {
-        std::pop_heap(slot.begin(), slot.end(), std::greater<double>());
-        if (starts) (*starts)[j] = slot.back();
-        slot.back() += t[j];
-        finish = std::max(finish, slot.back());
-        std::push_heap(slot.begin(), slot.end(), std::greater<double>());
-      }
-      return std::make_pair(finish, *std::min_element(slot.begin(), slot.end()));
-    };
-    for (int x = 0; x < 8; ++x) {
-      std::vector<int>& q = queue[x];
-      const size_t n = q.size();
-      if (n <= (size_t)chunk) continue;  // one round: nothing runs after a CU went idle
-      std::vector<double> t(n), st(n);
-      for (size_t j = 0; j < n; ++j) t[j] = tile_time(all_tiles[q[j]]);
-      const auto base = simulate(t, &st);
-      size_t j0 = n;
-      while (j0 > 0 && st[j0 - 1] >= base.second) --j0;  // starts are non-decreasing in queue order
-      auto splittable = [&](const TileDesc& td) {
-        const int qt = plan->meta[td.prob].qtype;
-        // ('2': weight-only tiles too — the small-batch wo3 calls run ~1.3 rounds of equal tiles)
-        return ((td.cls >> 16) & 0xFF) <= 1 && (!is_weightonly(qt) || ts_env[0] == '2') && qt != QT_I4G &&
-               td.ks1 - td.ks0 >= 6;
-      };
-      int best_s = 1;
-      double best_finish = base.first;
-      for (int S = 2; S <= 8; ++S) {
-        std::vector<double> t2(t.begin(), t.begin() + j0);
-        for (size_t j = j0; j < n; ++j) {
-          const TileDesc& td = all_tiles[q[j]];
-          const int nst = td.ks1 - td.ks0;
-          if (!splittable(td) || nst / S < 3) {
-            t2.push_back(t[j]);
-            continue;
-          }
-          const double per_stage = t[j] / nst;
-          for (int k = 0; k < S; ++k) t2.push_back(per_stage * ((k + 1) * nst / S - k * nst / S + 2));
-        }
-        const double f = simulate(t2, nullptr).first;
-        if (f < best_finish) {
-          best_finish = f;
-          best_s = S;
-        }
-      }
-      if (best_s == 1 || best_finish > 0.99 * base.first) continue;
-      std::vector<int> q2(q.begin(), q.begin() + j0);
+// Tail split (v2, not persistent). An XCD hands its blocks to its CUs in queue order, so the
+// queue's last tiles run while most of the XCD's CUs have gone idle for good (w8a8 down at
+// bs=8192: 194 tiles per XCD = 6 rounds of 32 + 2; tile timelines put the ragged finish at
+// 6-8 % of CU time). Per XCD, the tiles that start after the first CU's last tile ended are cut
+// along K into S consecutive slices (the split-K path), S in 2..8 (>= 3 stages a slice,
+// each slice priced at 2 extra stages for its fill and partial-sum traffic) chosen to minimise
+// the XCD's simulated finish; kept only if that gains >= 1 %.
+// MEASURED NEGATIVE: 1.5-2 % slower on the w8a8 / fp16 / mixed gate_up calls, the
+// only layer-11 calls it cuts (the partial-sum round trip costs more than the ragged finish
+// it removes). Lab library only, opt-in: MXMOE_GG_TAIL_SPLIT=1.
+void split_tails(const Variant& v, const TileTimer& tile_time, int mode, int* groups, XcdQueues* xq, Plan* plan) {
+  const int chunk = v.chunk;
+  std::vector<TileDesc>& all_tiles = xq->tiles;
+  auto simulate = [&](const std::vector<double>& t, std::vector<double>* starts) {
+    std::vector<double> slot(chunk, 0.0);  // min-heap of slot free times
+    double finish = 0;
+    for (size_t j = 0; j < t.size(); ++j) {
+      std::pop_heap(slot.begin(), slot.end(), std::greater<double>());
+      if (starts) (*starts)[j] = slot.back();
+      slot.back() += t[j];
+      finish = std::max(finish, slot.back());
+      std::push_heap(slot.begin(), slot.end(), std::greater<double>());
+    }
+    return std::make_pair(finish, *std::min_element(slot.begin(), slot.end()));
+  };
+  auto splittable = [&](const TileDesc& td) {
+    const QTypeInfo& t = qinfo(plan->meta[td.prob].qtype);
+    // (mode 2: weight-only tiles too — the small-batch wo3 calls run ~1.3 rounds of equal tiles)
+    return ((td.cls >> 16) & 0xFF) <= 1 && (!t.weight_only || mode == 2) && !t.group_fold && td.ks1 - td.ks0 >= 6;
+  };
+  for (int x = 0; x < 8; ++x) {
+    std::vector<int>& q = xq->queue[x];
+    const size_t n = q.size();
+    if (n <= (size_t)chunk) continue;  // one round: nothing runs after a CU went idle
+    std::vector<double> t(n), st(n);
+    for (size_t j = 0; j < n; ++j) t[j] = tile_time(all_tiles[q[j]]);
+    const auto base = simulate(t, &st);
+    size_t j0 = n;
+    while (j0 > 0 && st[j0 - 1] >= base.second) --j0;  // starts are non-decreasing in queue order
+    int best_s = 1;
+    double best_finish = base.first;
+    for (int S = 2; S <= 8; ++S) {
+      std::vector<double> t2(t.begin(), t.begin() + j0);
       for (size_t j = j0; j < n; ++j) {
-        const TileDesc td = all_tiles[q[j]];
-        const int nst = td.ks1 - td.ks0, S = best_s;
+        const TileDesc& td = all_tiles[q[j]];
+        const int nst = td.ks1 - td.ks0;
         if (!splittable(td) || nst / S < 3) {
-          q2.push_back(q[j]);
+          t2.push_back(t[j]);
           continue;
         }
-        const int grp = groups++, slab = plan->slabs;
-        plan->slabs += S;
-        plan->tail_slabs += S;
-        for (int k = 0; k < S; ++k) {
-          q2.push_back((int)all_tiles.size());
-          all_tiles.push_back(TileDesc{td.prob, td.m0, td.n0, (td.cls & 0xFF) | (k << 8) | (S << 16),
-                                       td.ks0 + k * nst / S, td.ks0 + (k + 1) * nst / S, slab, grp});
-        }
+        const double per_stage = t[j] / nst;
+        for (int k = 0; k < S; ++k) t2.push_back(per_stage * ((k + 1) * nst / S - k * nst / S + 2));
       }
-      q.swap(q2);
-    }
-  }
-#endif
-#ifdef MXMOE_LAB
-  // Mixed residency (lab A/B, MXMOE_GG_MIX = 1): each XCD queue interleaved so a
-  // CU's co-resident workgroups (wo3: three) hold one full-height tile (a shared-expert tile, MFMA-
-  // heavy) beside the routed tiles of ~35 rows (weight-stream-heavy) instead of all-shared, then
-  // all-routed rounds: the routed tiles' stream then runs under the shared tiles' MFMAs. "Full" =
-  // a tile whose modelled time is at least 1.3x the queue's median.
-  const char* mix_env = planner_knob("MXMOE_GG_MIX");
-  if (mix_env && mix_env[0] == '1' && v.kind == Kind::V2 && !v.persistent) {
-    for (auto& q : queue) {
-      if (q.size() < 4) continue;
-      std::vector<double> t(q.size());
-      for (size_t j = 0; j < q.size(); ++j) t[j] = tile_time(all_tiles[q[j]]);
-      std::vector<double> srt(t);
-      std::nth_element(srt.begin(), srt.begin() + srt.size() / 2, srt.end());
-      const double med = srt[srt.size() / 2];
-      std::vector<int> lo, hi;
-      for (size_t j = 0; j < q.size(); ++j) ((t[j] >= 1.3 * med) ? hi : lo).push_back(q[j]);
-      if (hi.empty() || lo.empty()) continue;
-      std::vector<int> out;
-      size_t a = 0, b = 0;
-      while (a < hi.size() || b < lo.size()) {  // keep the hi : lo proportion along the queue
-        if (b >= lo.size() || (a < hi.size() && a * lo.size() <= b * hi.size())) out.push_back(hi[a++]);
-        else out.push_back(lo[b++]);
+      const double f = simulate(t2, nullptr).first;
+      if (f < best_finish) {
+        best_finish = f;
+        best_s = S;
       }
-      q.swap(out);
     }
+    if (best_s == 1 || best_finish > 0.99 * base.first) continue;
+    std::vector<int> q2(q.begin(), q.begin() + j0);
+    for (size_t j = j0; j < n; ++j) {
+      const TileDesc td = all_tiles[q[j]];
+      const int nst = td.ks1 - td.ks0, S = best_s;
+      if (!splittable(td) || nst / S < 3) {
+        q2.push_back(q[j]);
+        continue;
+      }
+      const int grp = (*groups)++, slab = plan->slabs;
+      plan->slabs += S;
+      plan->tail_slabs += S;
+      for (int k = 0; k < S; ++k) {
+        q2.push_back((int)all_tiles.size());
+        all_tiles.push_back(TileDesc{td.prob, td.m0, td.n0, (td.cls & 0xFF) | (k << 8) | (S << 16),
+                                     td.ks0 + k * nst / S, td.ks0 + (k + 1) * nst / S, slab, grp});
+      }
+    }
+    q.swap(q2);
   }
-#endif
+}
+
+// Mixed residency (lab A/B, MXMOE_GG_MIX = 1): each XCD queue interleaved so a
+// CU's co-resident workgroups (wo3: three) hold one full-height tile (a shared-expert tile, MFMA-
+// heavy) beside the routed tiles of ~35 rows (weight-stream-heavy) instead of all-shared, then
+// all-routed rounds: the routed tiles' stream then runs under the shared tiles' MFMAs. "Full" =
+// a tile whose modelled time is at least 1.3x the queue's median.
+void mix_residency(const TileTimer& tile_time, XcdQueues* xq) {
+  for (auto& q : xq->queue) {
+    if (q.size() < 4) continue;
+    std::vector<double> t(q.size());
+    for (size_t j = 0; j < q.size(); ++j) t[j] = tile_time(xq->tiles[q[j]]);
+    std::vector<double> srt(t);
+    std::nth_element(srt.begin(), srt.begin() + srt.size() / 2, srt.end());
+    const double med = srt[srt.size() / 2];
+    std::vector<int> lo, hi;
+    for (size_t j = 0; j < q.size(); ++j) ((t[j] >= 1.3 * med) ? hi : lo).push_back(q[j]);
+    if (hi.empty() || lo.empty()) continue;
+    std::vector<int> out;
+    size_t a = 0, b = 0;
+    while (a < hi.size() || b < lo.size()) {  // keep the hi : lo proportion along the queue
+      if (b >= lo.size() || (a < hi.size() && a * lo.size() <= b * hi.size())) out.push_back(hi[a++]);
+      else out.push_back(lo[b++]);
+    }
+    q.swap(out);
+  }
+}
+
+// Low-fill LPT (lab opt-in, MXMOE_GG_LOWFILL_LPT=1): a call of at most 4 tiles per CU is laid out
+// as one list in descending modelled tile time (stable: a tile's split-K slices and a band's
+// m-tiles stay adjacent); block b then lands on XCD b % 8 and each XCD hands its sublist to its
+// CUs in LPT order. At 2-3 tiles per CU the XCD chunks concentrate the long tiles (the
+// shared expert's split slices) on 2-3 XCDs, and the tile traces show 15-36 % ragged finish.
+void lowfill_lpt(const Variant& v, const TileTimer& tile_time, Plan* plan) {
+  if (plan->total_tiles > 4 * 8 * v.chunk) return;
+  std::vector<TileDesc> list;
+  for (const TileDesc& td : plan->tiles)
+    if (td.prob >= 0) list.push_back(td);
+  std::stable_sort(list.begin(), list.end(), [&](const TileDesc& a, const TileDesc& b) { return tile_time(a) > tile_time(b); });
+  plan->tiles = list;
+  plan->launch_grid = (int)list.size();
+}
+#endif  // MXMOE_LAB
+
+// The tile table: XCD x's i-th tile is block 8 i + x.
+void emit_tiles(const XcdQueues& xq, Plan* plan) {
   size_t qmax = 0;
-  for (const auto& q : queue) qmax = std::max(qmax, q.size());
+  for (const auto& q : xq.queue) qmax = std::max(qmax, q.size());
   int grid = 0;
-  plan->tiles.assign(8 * qmax, TileDesc{-1, 0, 0, 0, 0, 0, -1, -1});
+  plan->tiles.assign(8 * qmax, kEmptySlot);
   for (int x = 0; x < 8; ++x)
-    for (size_t i = 0; i < queue[x].size(); ++i) {
+    for (size_t i = 0; i < xq.queue[x].size(); ++i) {
       const int b = (int)(8 * i) + x;
-      plan->tiles[b] = all_tiles[queue[x][i]];
+      plan->tiles[b] = xq.tiles[xq.queue[x][i]];
       grid = std::max(grid, b + 1);
     }
   plan->tiles.resize(grid);
   plan->total_tiles = 0;
-  for (const auto& q : queue) plan->total_tiles += (int)q.size();
-#ifdef MXMOE_LAB
-  // Low-fill LPT (lab opt-in, MXMOE_GG_LOWFILL_LPT=1): a call of at most 4 tiles per CU is laid out
-  // as one list in descending modelled tile time (stable: a tile's split-K slices and a band's
-  // m-tiles stay adjacent); block b then lands on XCD b % 8 and each XCD hands its sublist to its
-  // CUs in LPT order. At 2-3 tiles per CU the XCD chunks above concentrate the long tiles (the
-  // shared expert's split slices) on 2-3 XCDs, and the tile traces show 15-36 % ragged finish.
-  const char* lpt_env = planner_knob("MXMOE_GG_LOWFILL_LPT");
-  if (lpt_env && lpt_env[0] == '1' && v.kind == Kind::V2 && !v.persistent && plan->total_tiles <= 4 * 8 * chunk) {
-    std::vector<TileDesc> list;
-    for (const TileDesc& td : plan->tiles)
-      if (td.prob >= 0) list.push_back(td);
-    std::stable_sort(list.begin(), list.end(),
-                     [&](const TileDesc& a, const TileDesc& b) { return tile_time(a) > tile_time(b); });
-    plan->tiles = list;
-    grid = (int)list.size();
-  }
-#endif
+  for (const auto& q : xq.queue) plan->total_tiles += (int)q.size();
   plan->launch_grid = grid;
-  if (v.persistent && v.persist_len > 0) {
+}
+// The persistent kernels' tile table: per-workgroup tile lists [k][G] with a terminating row of empty slots.
+void emit_persistent(const Variant& v, const XcdQueues& xq, const TileTimer& tile_time, bool any_tiles, Plan* plan) {
+  if (v.persist_len > 0) {
     // v2q with block lists: XCD x's queue cut into groups of L consecutive tiles, group g run by
     // block 8 g + x (that XCD under round-robin placement: speed only); the hardware hands a freed
-    // CU the next block, as for the one-tile blocks. Table [k][G] with a terminating row.
+    // CU the next block, as for the one-tile blocks.
     const int L = v.persist_len;
     size_t ngroups = 0;
-    for (const auto& q : queue) ngroups = std::max(ngroups, (q.size() + L - 1) / L);
+    for (const auto& q : xq.queue) ngroups = std::max(ngroups, (q.size() + L - 1) / L);
     const int G = (int)(8 * ngroups);
-    plan->tiles.assign((size_t)(L + 1) * G, TileDesc{-1, 0, 0, 0, 0, 0, -1, -1});
+    plan->tiles.assign((size_t)(L + 1) * G, kEmptySlot);
     for (int x = 0; x < 8; ++x)
-      for (size_t j = 0; j < queue[x].size(); ++j) {
+      for (size_t j = 0; j < xq.queue[x].size(); ++j) {
         const size_t g = j / L, k = j % L;
-        plan->tiles[k * G + 8 * g + x] = all_tiles[queue[x][j]];
+        plan->tiles[k * G + 8 * g + x] = xq.tiles[xq.queue[x][j]];
       }
-    plan->launch_grid = T > 0 ? G : 0;
-  } else if (v.persistent) {
-    // v2p: each XCD's queue handed out to its `chunk` workgroups in queue order, every tile to the
-    // workgroup whose modelled finish is earliest (what the hardware's dispatch does with blocks,
-    // planned once here); workgroup w = 8 * slot + x sits on XCD x under round-robin placement
-    // (speed only). Table [k][G] with a terminating row of empty slots.
-    const int G = 8 * chunk;
-    std::vector<std::vector<int>> lists(G);
-    for (int x = 0; x < 8; ++x) {
-      std::vector<std::pair<double, int>> heap;
-      for (int sl = 0; sl < chunk; ++sl) heap.push_back({0.0, sl});
-      std::make_heap(heap.begin(), heap.end(), std::greater<std::pair<double, int>>());
-      for (int idx : queue[x]) {
-        std::pop_heap(heap.begin(), heap.end(), std::greater<std::pair<double, int>>());
-        auto& top = heap.back();
-        lists[8 * top.second + x].push_back(idx);
-        top.first += tile_time(all_tiles[idx]);
-        std::push_heap(heap.begin(), heap.end(), std::greater<std::pair<double, int>>());
-      }
-    }
-    size_t maxlen = 0;
-    for (const auto& l : lists) maxlen = std::max(maxlen, l.size());
-    plan->tiles.assign((maxlen + 1) * G, TileDesc{-1, 0, 0, 0, 0, 0, -1, -1});
-    for (int w = 0; w < G; ++w)
-      for (size_t k = 0; k < lists[w].size(); ++k) plan->tiles[k * G + w] = all_tiles[lists[w][k]];
-    plan->launch_grid = T > 0 ? G : 0;
+    plan->launch_grid = any_tiles ? G : 0;
+    return;
   }
+  // v2p: each XCD's queue handed out to its `chunk` workgroups in queue order, every tile to the
+  // workgroup whose modelled finish is earliest (what the hardware's dispatch does with blocks,
+  // planned once here); workgroup w = 8 * slot + x sits on XCD x under round-robin placement
+  // (speed only).
+  const int G = 8 * v.chunk;
+  std::vector<std::vector<int>> lists(G);
+  for (int x = 0; x < 8; ++x) {
+    std::vector<std::pair<double, int>> heap;
+    for (int sl = 0; sl < v.chunk; ++sl) heap.push_back({0.0, sl});
+    std::make_heap(heap.begin(), heap.end(), std::greater<std::pair<double, int>>());
+    for (int idx : xq.queue[x]) {
+      std::pop_heap(heap.begin(), heap.end(), std::greater<std::pair<double, int>>());
+      auto& top = heap.back();
+      lists[8 * top.second + x].push_back(idx);
+      top.first += tile_time(xq.tiles[idx]);
+      std::push_heap(heap.begin(), heap.end(), std::greater<std::pair<double, int>>());
+    }
+  }
+  size_t maxlen = 0;
+  for (const auto& l : lists) maxlen = std::max(maxlen, l.size());
+  plan->tiles.assign((maxlen + 1) * G, kEmptySlot);
+  for (int w = 0; w < G; ++w)
+    for (size_t k = 0; k < lists[w].size(); ++k) plan->tiles[k * G + w] = xq.tiles[lists[w][k]];
+  plan->launch_grid = any_tiles ? G : 0;
+}
+
+// Tile generation + scheduling: validation, one table row per problem (build_meta; empty problems are dropped);
+// m-tile classes and split-K factors (m_tiles, split_factors); problems by descending modelled time of their
+// first (tallest) tile (stage_time); tile enumeration, a problem of >= 8 chunks of tiles (the shared expert at
+// large batch) cut into one rectangle per XCD (enumerate_tiles, region_of); placement — the MoE call shape packed
+// problem by problem (pack_xcds), any other call in chunks of about `chunk` tiles, each to the XCD with the least
+// modelled time so far, the regions after them (place_chunks); emission in dispatch order (emit_tiles).
+int plan_host(const std::vector<HostProblem>& probs, int variant, bool check_ptrs, Plan* plan) {
+  const Variant& v = variants()[variant];
+  const PlannerOpts o = planner_opts();
+  const int P = (int)probs.size();
+  std::vector<GGMeta> all(P);
+  for (int i = 0; i < P; ++i) {
+    int st = build_meta(probs[i], i, v, check_ptrs, &all[i]);
+    if (st) return st;
+  }
+  std::vector<int> order;
+  for (int i = 0; i < P; ++i)
+    if (probs[i].M > 0 && probs[i].N > 0) order.push_back(i);
+  const std::vector<int> split = split_factors(v, all, order, o);
+  std::vector<double> tile_cost(P, 0.0);
+  for (int i : order) tile_cost[i] = stage_time(v, all[i], m_tiles(v, all[i])[0].second) * stages_of(v, all[i]) / split[i];
+  std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return tile_cost[a] > tile_cost[b]; });
+
+  plan->meta.clear();
+  plan->order = order;
+  plan->slabs = 0;
+  plan->tail_slabs = 0;
+  TileLists tl = enumerate_tiles(v, all, probs, split, o, plan);
+  size_t T = tl.seq.size();
+  for (const auto& h : tl.region_tiles) T += h.size();
+  if (T > ((size_t)1 << 28)) return fail(MXMOE_GG_ERR_INVALID, "too many tiles (%d)", (int)T);
+  const TileTimer tile_time{v, plan->meta};
+
+  XcdQueues xq;
+  for (auto& x : xq.sim) x.slot.assign(v.chunk, 0.0);
+  xq.tiles = tl.seq;
+  if (!pack_xcds(v, tl, tile_time, o, &xq)) {
+    if (o.region == 1) put_regions(tl, tile_time, &xq);
+    place_chunks(v, tl, tile_time, o, &xq);
+    if (o.region != 1) put_regions(tl, tile_time, &xq);
+  }
+#ifdef MXMOE_LAB
+  const bool plain_v2 = v.kind == Kind::V2 && !v.persistent;
+  if (o.tail_split && plain_v2) split_tails(v, tile_time, o.tail_split, &tl.groups, &xq, plan);
+  if (o.mix && plain_v2) mix_residency(tile_time, &xq);
+#endif
+  emit_tiles(xq, plan);
+#ifdef MXMOE_LAB
+  if (o.lowfill_lpt && plain_v2) lowfill_lpt(v, tile_time, plan);
+#endif
+  if (v.persistent) emit_persistent(v, xq, tile_time, T > 0, plan);
   return MXMOE_GG_OK;
 }
 
@@ -1556,43 +1583,37 @@ int resolve_variant(int variant, const std::vector<HostProblem>& hp, int* out) {
   for (const HostProblem& p : hp) {
     int qt;
     if (qtype_of(p.a_bits, p.w_bits, p.gsize, p.sym, p.fmt, &qt) != MXMOE_GG_OK) continue;
-    // (an MXFP4 problem counts even when empty: only v2x plans it, and every variant checks a
-    // problem's type before its shape)
-    if (p.M > 0 || qt == QT_MXF4) mask |= 1 << qt;
+    if (p.M > 0 || qinfo(qt).auto_counts_empty) mask |= 1 << qt;
   }
   *out = variant_index(kDefaultVariantName);
   // (weight-only MXFP4 counts as weight-only; beside a w4a4 MXFP4 problem the call keeps v2x, the
-  // only variant with that body)
-  const int wo_mask = (1 << QT_W4A16) | (1 << QT_W8A16) | (1 << QT_W2A16) | (1 << QT_MXF4W);
-  // (w4a8_g32_sym_MXFP8 has a wo3 body; its row limit is kSmallMeanRowsMx8)
-  const int small_mask = wo_mask | (1 << QT_I8) | (1 << QT_F16) | (1 << QT_I4) | (1 << QT_MXF8A);
+  // only variant with that body; w4a8_g32_sym_MXFP8 has a wo3 body)
+  constexpr int wo_mask = auto_mask(AutoClass::WeightOnly), small_mask = wo_mask | auto_mask(AutoClass::Small);
   // (fused SiLU calls too: the small-batch kernel's fp16 / w8a8 / w4a4 bodies carry the epilogue)
   if (mask != 0 && (mask & ~small_mask) == 0) {
     // (w8a8 / fp16 problems may ride along: the reference's small-batch w4a16 + w8a8 pairing)
-    double wsum0 = 0, ksum = 0;
+    double wsum = 0, ksum = 0, msum = 0;
     int kmax = 0;
     for (const HostProblem& p : hp) {
       if (p.M <= 0 || p.N <= 0) continue;
       const double w = (double)p.N * p.K;
-      wsum0 += w;
+      wsum += w;
       ksum += w * p.K;
+      msum += w * p.M;
       kmax = std::max(kmax, p.K);
     }
-    const bool kskew = wsum0 > 0 && kmax >= 2.0 * ksum / wsum0;
-    const double limit = (mask & wo_mask) ? kWoSmallMeanRows
-                                          : ((mask & (1 << QT_MXF8A)) ? kSmallMeanRowsMx8
-                                             : (mask & (1 << QT_I4)) ? kSmallMeanRowsI4 : kSmallMeanRows) * (kskew ? 2.0 : 1.0);
+    const bool kskew = wsum > 0 && kmax >= 2.0 * ksum / wsum;
+    double wo_rows = 0, small_rows = 0;  // the largest limit among the types present, per class
+    for (const QTypeInfo& t : kQTypes)
+      if (mask & (1 << t.qt)) {
+        double& rows = t.weight_only ? wo_rows : small_rows;
+        rows = std::max(rows, t.auto_rows);
+      }
+    const double limit = (mask & wo_mask) ? wo_rows : small_rows * (kskew ? 2.0 : 1.0);
     // weight-only: the 3-WG/CU 64-row kernel while the rows per weight byte are few (small batches:
     // the 64-row tile is bound by its instruction stream and barriers, a second and third resident
     // workgroup fill each other's waits — +15-70 % on the qwen2_moe calls at bs 128-2048,
     // profiles/r03/wo2/); v2x's 256-row tiles at large batch
-    double wsum = 0, msum = 0;
-    for (const HostProblem& p : hp) {
-      if (p.M <= 0 || p.N <= 0) continue;
-      const double w = (double)p.N * p.K;
-      wsum += w;
-      msum += w * p.M;
-    }
     if (wsum > 0 && msum / wsum <= limit) {
       const int wi = variant_index(kWoSmallVariant);
       if (!strcmp(variants()[wi].name, kWoSmallVariant)) {
@@ -1601,21 +1622,22 @@ int resolve_variant(int variant, const std::vector<HostProblem>& hp, int* out) {
       }
     }
   }
-#ifdef MXMOE_LAB
-  if ((mask & (1 << QT_I4F6)) && mask != (1 << QT_I4F6))
-    return fail(MXMOE_GG_ERR_UNSUPPORTED,
-                "fp6-image w4a4 problems (MXMOE_GG_FMT_F6) cannot share a call with other quant types: plan them "
-                "as a call of their own");
-  if (mask == (1 << QT_I4F6)) {  // fp6 images: the fp6 kernel (no other variant reads them)
-    *out = variant_index(kF6Variant);
-    return MXMOE_GG_OK;
-  }
-#endif
-  if (mask == (1 << QT_I4)) {
-    // int4-only: the 256x128 2-WG/CU kernel, unless the call is low-fill enough for the v2s plan
-    // to split K (that kernel cannot)
-    Plan p;
-    if (plan_host(hp, *out, false, &p) == MXMOE_GG_OK && p.slabs == p.tail_slabs) *out = variant_index(kInt4Variant);
+  for (const QTypeInfo& t : kQTypes) {
+    if (!(mask & (1 << t.qt)) || !t.auto_alone) continue;
+    if (t.auto_class == AutoClass::Alone) {  // fp6 images: the fp6 kernel (no other variant reads them)
+      if (mask != (1 << t.qt))
+        return fail(MXMOE_GG_ERR_UNSUPPORTED,
+                    "fp6-image w4a4 problems (MXMOE_GG_FMT_F6) cannot share a call with other quant types: plan them "
+                    "as a call of their own");
+      *out = variant_index(t.auto_alone);
+      return MXMOE_GG_OK;
+    }
+    if (mask == (1 << t.qt)) {
+      // int4-only: the 256x128 2-WG/CU kernel, unless the call is low-fill enough for the v2s plan
+      // to split K (that kernel cannot)
+      Plan p;
+      if (plan_host(hp, *out, false, &p) == MXMOE_GG_OK && p.slabs == p.tail_slabs) *out = variant_index(t.auto_alone);
+    }
   }
   return MXMOE_GG_OK;
 }
@@ -1631,12 +1653,21 @@ std::vector<HostProblem> to_host(const mxmoe_gg_problem* problems, int problem_c
 }
 
 // Host image of the workspace for a plan; pointer columns from `hp` in table-row order.
-std::vector<uint8_t> workspace_image(const Plan& plan, const std::vector<const void*> cols[5], WsLayout* out) {
+// The 5 pointer columns (A, B, scale_a, scale_b, C) of the planned problems in table-row order, one after the other.
+std::vector<const void*> pointer_columns(const std::vector<int>& order, const std::vector<HostProblem>& hp) {
+  std::vector<const void*> cols;
+  cols.reserve(5 * order.size());
+  for (int c = 0; c < 5; ++c)
+    for (int r : order) cols.push_back(c == 0 ? hp[r].A : c == 1 ? hp[r].B : c == 2 ? hp[r].SA : c == 3 ? hp[r].SB : hp[r].C);
+  return cols;
+}
+
+std::vector<uint8_t> workspace_image(const Plan& plan, const std::vector<const void*>& cols, WsLayout* out) {
   const int P = (int)plan.meta.size();
   const WsLayout l = ws_layout(P, (int)plan.tiles.size(), plan.slabs);
   std::vector<uint8_t> img(l.total - l.slabs, 0);  // counters start at zero; slabs need no init
   memcpy(img.data(), plan.meta.data(), (size_t)P * sizeof(GGMeta));
-  for (int c = 0; c < 5; ++c) memcpy(img.data() + l.meta + c * l.ptr, cols[c].data(), (size_t)P * sizeof(void*));
+  for (int c = 0; c < 5; ++c) memcpy(img.data() + l.meta + c * l.ptr, cols.data() + c * P, (size_t)P * sizeof(void*));
   memcpy(img.data() + l.meta + 5 * l.ptr, plan.tiles.data(), plan.tiles.size() * sizeof(TileDesc));
   *out = l;
   return img;
@@ -1668,13 +1699,27 @@ void fill_info(const Plan& plan, int variant, const WsLayout& l, void* ws, mxmoe
   info->qtype_mask = 0;
   for (const GGMeta& m : plan.meta) {
     info->qtype_mask |= 1 << m.qtype;
-    if (is_weightonly(m.qtype) && (m.reserved2 & META_SILU)) info->qtype_mask |= kQmaskWoSilu;
+    if (qinfo(m.qtype).weight_only && (m.reserved2 & META_SILU)) info->qtype_mask |= kQmaskWoSilu;
   }
-  info->lds_bytes = v.lds_of ? v.lds_of(info->qtype_mask) : v.lds_bytes;
+  const int build = v.pick(info->qtype_mask);  // (the build mxmoe_gg_launch will run)
+  info->lds_bytes = build >= 0 ? v.builds.rows[build].lds_bytes : v.lds_bytes;
   info->splitk_slabs = plan.slabs;
   info->workspace_bytes = (int64_t)l.total;
   info->workspace = ws;
   info->signature = plan_signature(plan);
+}
+
+template <class T>
+int debug_read(const T& symbol, void* dst, size_t bytes, int reset) {  // mxmoe_gg_debug_*: read / clear a __device__ array
+  const size_t n = std::min(bytes, sizeof(T));
+  if (dst && n) HIP_TRY(hipMemcpyFromSymbol(dst, symbol, n, 0, hipMemcpyDeviceToHost));
+  if (reset) {
+    void* p = nullptr;
+    HIP_TRY(hipGetSymbolAddress(&p, symbol));
+    HIP_TRY(hipMemset(p, 0, sizeof(T)));
+    HIP_TRY(hipDeviceSynchronize());
+  }
+  return MXMOE_GG_OK;
 }
 
 }  // namespace
@@ -1700,11 +1745,6 @@ int mxmoe_gg_variant_count(void) { return (int)variants().size(); }
 int mxmoe_gg_default_variant(void) { return variant_index(kDefaultVariantName); }
 
 int mxmoe_gg_list_variants(char* buf, size_t n) {
-  // weight-only kernels cover every group size / sym of a bit width: listed under the base name
-  static const char* qnames[QT_COUNT] = {"fp16",          "w8a8_g-1_sym", "w4a4_g-1_sym",      "w4a16", "w8a16",
-                                         "w4a4_g128_sym", "w2a16",        "w8a8_g-1_sym_E4M3", "bf16",  "w4a4_g-1_sym_F6",
-                                         "w4a4_g32_sym_MXFP4", "w4a16_g32_sym_MXFP4", "w4a8_g32_sym_MXFP8"};
-  static const int wbits[QT_COUNT] = {16, 8, 4, 4, 8, 4, 2, 8, 16, 6, 4, 4, 8};  // (bits of a staged K byte row)
   std::string out;
   const auto& vs = variants();
   for (size_t i = 0; i < vs.size(); ++i) {
@@ -1713,12 +1753,12 @@ int mxmoe_gg_list_variants(char* buf, size_t n) {
     for (int q = 0; q < QT_COUNT; ++q) {
       const TileGeom& g = vs[i].geom[q];
       if (g.bn == 0) continue;  // quant type not implemented by this variant
-      const int bits = wbits[q];
+      const int bits = qinfo(q).staged_bits;
       const int waves = g.threads / 64;
       const int wm = 2, wn = waves / wm;
       if (off >= sizeof(line) - 1) break;  // (snprintf returns the untruncated length)
       off += (size_t)snprintf(line + off, sizeof(line) - off,
-                              " %s=TileConfig(BM=%d, BN=%d, BK=%d, WM=%d, WN=%d, WK=1, STAGE=2)", qnames[q], g.bm, g.bn,
+                              " %s=TileConfig(BM=%d, BN=%d, BK=%d, WM=%d, WN=%d, WK=1, STAGE=2)", qinfo(q).name, g.bm, g.bn,
                               g.bkb * 8 / bits, wm, wn);
     }
     out += line;
@@ -1886,14 +1926,7 @@ int mxmoe_gg_plan(const mxmoe_gg_problem* problems, int problem_count, int varia
   Plan plan;
   st = plan_host(hp, variant, true, &plan);
   if (st) return st;
-  std::vector<const void*> cols[5];
-  for (int r : plan.order) {
-    cols[0].push_back(hp[r].A);
-    cols[1].push_back(hp[r].B);
-    cols[2].push_back(hp[r].SA);
-    cols[3].push_back(hp[r].SB);
-    cols[4].push_back(hp[r].C);
-  }
+  std::vector<const void*> cols = pointer_columns(plan.order, hp);
   WsLayout l;
   std::vector<uint8_t> img = workspace_image(plan, cols, &l);
   if (!workspace || workspace_bytes < l.total)
@@ -1952,13 +1985,9 @@ int mxmoe_gg_rebind(const mxmoe_gg_problem* problems, int problem_count, const m
   if ((int)order.size() != info->problem_count)
     return fail(MXMOE_GG_ERR_INVALID, "mxmoe_gg_rebind: problems differ from the planned call; plan again");
   const WsLayout l = ws_layout(info->problem_count, info->tile_slots, info->splitk_slabs);
+  const std::vector<const void*> ptrs = pointer_columns(order, hp);
   std::vector<uint8_t> cols(5 * l.ptr, 0);
-  for (int c = 0; c < 5; ++c)
-    for (size_t i = 0; i < order.size(); ++i) {
-      const HostProblem& q = hp[order[i]];
-      const void* p = c == 0 ? q.A : c == 1 ? q.B : c == 2 ? q.SA : c == 3 ? q.SB : q.C;
-      memcpy(cols.data() + c * l.ptr + i * sizeof(void*), &p, sizeof(void*));
-    }
+  for (int c = 0; c < 5; ++c) memcpy(cols.data() + c * l.ptr, ptrs.data() + c * order.size(), order.size() * sizeof(void*));
   HIP_TRY(hipMemcpyAsync(static_cast<uint8_t*>(info->workspace) + l.meta, cols.data(), cols.size(),
                          hipMemcpyHostToDevice, (hipStream_t)stream));
   HIP_TRY(hipStreamSynchronize((hipStream_t)stream));  // pageable host columns must outlive the copy
@@ -1985,7 +2014,13 @@ int mxmoe_gg_launch(const mxmoe_gg_plan_info* info, void* stream) {
   a.n_slots = info->grid;
   a.counters = reinterpret_cast<int32_t*>(const_cast<uint8_t*>(ws) + l.meta + 5 * l.ptr + l.tiles);
   a.slabs = const_cast<uint8_t*>(ws) + l.meta + 5 * l.ptr + l.tiles + l.counters;
-  variants()[info->variant].launch(a, info->grid, info->qtype_mask, (hipStream_t)stream);
+  const Variant& v = variants()[info->variant];
+  const int build = v.pick(info->qtype_mask);
+  if (build < 0) {  // (the lab libraries compile a few quant-type sets per kernel only)
+    fprintf(stderr, "libmxmoe_gg: variant %s: quant-type mix %#x not compiled\n", v.name, info->qtype_mask);
+    abort();
+  }
+  v.builds.rows[build].launch(a, info->grid, (hipStream_t)stream);
   HIP_TRY(hipGetLastError());
   return MXMOE_GG_OK;
 }
@@ -2116,18 +2151,12 @@ int groupgemm_mxmoe_fmt(void** ptr_As, void** ptr_Bs, void** ptr_scale_a, void**
     key.insert(key.end(), {p.M, p.N, p.K, p.a_bits, p.w_bits, p.gsize, p.sym, p.fmt});
   if (d.cached && key == d.key) {
     const Variant& v = variants()[d.variant];
-    std::vector<const void*> cols;
-    cols.reserve(5 * d.plan.order.size());
-    for (int c = 0; c < 5; ++c)
-      for (int r : d.plan.order) {
-        GGMeta m;
-        if (c == 0) {
-          st = build_meta(hp[r], r, v, true, &m);
-          if (st) return st;
-        }
-        const HostProblem& q = hp[r];
-        cols.push_back(c == 0 ? q.A : c == 1 ? q.B : c == 2 ? q.SA : c == 3 ? q.SB : q.C);
-      }
+    for (int r : d.plan.order) {
+      GGMeta m;
+      st = build_meta(hp[r], r, v, true, &m);
+      if (st) return st;
+    }
+    std::vector<const void*> cols = pointer_columns(d.plan.order, hp);
     if (cols != d.cols) {  // new buffers, same shapes: upload the 5 pointer columns only
       const size_t P = d.plan.order.size();
       std::memset(d.pinned, 0, 5 * d.layout.ptr);
@@ -2150,14 +2179,7 @@ int groupgemm_mxmoe_fmt(void** ptr_As, void** ptr_Bs, void** ptr_scale_a, void**
   st = plan_host(hp, variant, true, &plan);
   if (st) return st;
   if (plan.total_tiles == 0) return MXMOE_GG_OK;
-  std::vector<const void*> cols[5];
-  for (int r : plan.order) {
-    cols[0].push_back(hp[r].A);
-    cols[1].push_back(hp[r].B);
-    cols[2].push_back(hp[r].SA);
-    cols[3].push_back(hp[r].SB);
-    cols[4].push_back(hp[r].C);
-  }
+  std::vector<const void*> cols = pointer_columns(plan.order, hp);
   WsLayout l;
   std::vector<uint8_t> img = workspace_image(plan, cols, &l);
   // 4. upload from pinned memory and launch, both on the legacy stream, no further host sync: the
@@ -2173,39 +2195,16 @@ int groupgemm_mxmoe_fmt(void** ptr_As, void** ptr_Bs, void** ptr_scale_a, void**
   d.key = std::move(key);
   d.variant = variant;
   d.layout = l;
-  d.cols.clear();
-  for (int c = 0; c < 5; ++c) d.cols.insert(d.cols.end(), cols[c].begin(), cols[c].end());
+  d.cols = std::move(cols);
   d.plan = std::move(plan);
   d.cached = true;
   return MXMOE_GG_OK;
 }
 
-
-int mxmoe_gg_debug_trace(void* dst, size_t bytes, int reset) {
-  const size_t n = std::min(bytes, sizeof(g_gg_trace));
-  if (dst && n) HIP_TRY(hipMemcpyFromSymbol(dst, HIP_SYMBOL(g_gg_trace), n, 0, hipMemcpyDeviceToHost));
-  if (reset) {
-    void* p = nullptr;
-    HIP_TRY(hipGetSymbolAddress(&p, HIP_SYMBOL(g_gg_trace)));
-    HIP_TRY(hipMemset(p, 0, sizeof(g_gg_trace)));
-    HIP_TRY(hipDeviceSynchronize());
-  }
-  return MXMOE_GG_OK;
-}
-
+int mxmoe_gg_debug_trace(void* dst, size_t bytes, int reset) { return debug_read(g_gg_trace, dst, bytes, reset); }
 #ifdef MXMOE_LAB
 // lab library only (not in include/mxmoe_gg.h): the spread mainloop's per-wave stage stamps
-int mxmoe_gg_debug_stamps(void* dst, size_t bytes, int reset) {
-  const size_t n = std::min(bytes, sizeof(g_gg_stamp));
-  if (dst && n) HIP_TRY(hipMemcpyFromSymbol(dst, HIP_SYMBOL(g_gg_stamp), n, 0, hipMemcpyDeviceToHost));
-  if (reset) {
-    void* p = nullptr;
-    HIP_TRY(hipGetSymbolAddress(&p, HIP_SYMBOL(g_gg_stamp)));
-    HIP_TRY(hipMemset(p, 0, sizeof(g_gg_stamp)));
-    HIP_TRY(hipDeviceSynchronize());
-  }
-  return MXMOE_GG_OK;
-}
+int mxmoe_gg_debug_stamps(void* dst, size_t bytes, int reset) { return debug_read(g_gg_stamp, dst, bytes, reset); }
 #endif
 
 // Inverse of the reference's permute_weight(Row) + pack_weightonly (quantize.cuh:318-421), then

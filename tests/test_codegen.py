@@ -43,6 +43,13 @@ def test_no_scratch_no_spills(asm):
         assert k["private"] == 0 and k["vgpr_spill"] == 0 and k["sgpr_spill"] == 0, (name, k)
 
 
+def test_product_kernel_set(asm):
+    """The kernels the product library instantiates are exactly the committed list: a build-table change
+    that adds, drops or re-parametrises a kernel shows here, before it costs build time or library size."""
+    want = (Path(__file__).parent / "golden" / "product_kernels.txt").read_text().split()
+    assert sorted(set(re.findall(r"\.symbol:\s+(\S+)\.kd", asm))) == want
+
+
 def test_v2_keeps_two_waves_per_simd(asm):
     ks = _kernels(asm)
     v2 = [k for n, k in ks.items() if "gg_v2_kernel" in n]
