@@ -321,6 +321,85 @@ int mxmoe_gg_debug_trace(void* dst, size_t bytes, int reset);
 int mxmoe_gg_plan_tiles(const mxmoe_gg_problem* problems, int problem_count, int variant, int32_t* tiles,
                         int32_t* rows, int* slots);
 
+/* ---- Device planning: a fixed-capacity plan whose row counts live in device memory ("Device
+ * planning / graph forward"). No reference counterpart: the reference plans on the host every call.
+ *
+ * mxmoe_gg_plan_dynamic runs once, on the host. problems[i].M is the CAPACITY of problem i, A / scale_a / C are
+ * BASE pointers; the problems listed in joint_idx (distinct indices: a MoE layer's routed experts) also share the
+ * bound sum rows <= rows_total. Each launch then reads one mxmoe_gg_dyn_row per problem from device memory:
+ * a small planner kernel turns the rows into the plan table's M, the A / scale_a / C pointer columns and the
+ * tile table, and the variant's unchanged GEMM kernel runs at the fixed grid `tile_slots` (unused slots exit at
+ * once). Nothing in a launch depends on the host, so it can be captured into a hipGraph and replayed while the
+ * row table changes.
+ *   validation  as mxmoe_gg_plan (same errors from the same type tables), at the capacities.
+ *   variant     v2x, v3 and wo3 (the product's kernels); persistent and lab variants: MXMOE_GG_ERR_UNSUPPORTED.
+ *               MXMOE_GG_VARIANT_AUTO resolves ONCE, as mxmoe_gg_resolve_variant does for the balanced call: every
+ *               joint problem with min(M, ceil(rows_total / n_joint)) rows, the others with their M. The kernel
+ *               does not follow the routing afterwards.
+ *   tiles       the host planner's rule (256-row tiles while more than 128 rows remain, then one 128-row or, for
+ *               the types that take it, 64-row tile; wo3: 64-row tiles), tiles_n = cdiv(N, BN); problems in a
+ *               fixed order, longest K stages first; no split-K (splitk_slabs = 0) and no XCD packing.
+ *   capacity    info.grid = info.tile_slots = info.total_tiles = the capacity bound: with tn_i = tiles_n and
+ *               bm the tile height, slots = sum_{i not joint} tn_i cdiv(M_i, bm)
+ *                 + min( sum_{joint} tn_i cdiv(M_i, bm),
+ *                        max over n in [1, min(n_joint, rows_total)] of
+ *                          [sum of the n largest tn_i] + max tn_i * floor((rows_total - n) / bm) )
+ *               (an expert with r > 0 rows has floor((r - 1) / bm) + 1 m-tiles; n counts the non-empty experts,
+ *               whose first rows cannot also fill tiles; derivation at dyn_capacity_slots, mxmoe_amd/csrc/gg_dyn.h).
+ *   extents     NULL, or per problem the bytes behind its A / scale_a / C base pointers. NULL: the problem's own
+ *               capacity (M rows at its strides), so an offset can only move rows inside [base, base + M rows).
+ *   safety      whatever the row table holds, no tile is planned outside the capacities: rows are clamped to
+ *               [0, M_i] and the joint sum to rows_total (in problem order), an offset that is negative,
+ *               misaligned (A / C 16 B, scale_a 2 B, block scales 4 B) or would put a row outside its extent
+ *               gives the problem 0 rows, and tile emission stops at tile_slots. Each case ORs a
+ *               MXMOE_GG_DYN_* bit into a status word in the workspace (mxmoe_gg_dynamic_status).
+ * The workspace holds mxmoe_gg_dynamic_workspace_size bytes and belongs to this plan alone; mxmoe_gg_rebind
+ * and mxmoe_gg_launch are not for dynamic plans. */
+typedef struct mxmoe_gg_dyn_row {
+  int32_t rows;     /* rows of the problem in this launch */
+  int32_t reserved; /* 0 */
+  int64_t a_off;    /* byte offsets added to the planned A / scale_a / C base pointers */
+  int64_t sa_off;
+  int64_t c_off;
+} mxmoe_gg_dyn_row;
+
+typedef struct mxmoe_gg_dyn_extent {
+  int64_t a_bytes, sa_bytes, c_bytes; /* bytes addressable behind the A / scale_a / C base pointers */
+} mxmoe_gg_dyn_extent;
+
+enum {
+  MXMOE_GG_DYN_ROWS_CLAMPED = 1,  /* a row count was negative or above its capacity */
+  MXMOE_GG_DYN_JOINT_CLAMPED = 2, /* the joint problems' rows exceeded rows_total */
+  MXMOE_GG_DYN_SLOTS_CUT = 4,     /* more tiles than tile_slots (cannot happen with admissible rows) */
+  MXMOE_GG_DYN_BAD_OFFSET = 8     /* an offset was refused: that problem ran with 0 rows */
+};
+
+int mxmoe_gg_dynamic_workspace_size(const mxmoe_gg_problem* problems, int problem_count, int variant,
+                                    const int32_t* joint_idx, int n_joint, int64_t rows_total, size_t* bytes);
+
+int mxmoe_gg_plan_dynamic(const mxmoe_gg_problem* problems, int problem_count, int variant, const int32_t* joint_idx,
+                          int n_joint, int64_t rows_total, const mxmoe_gg_dyn_extent* extents, void* workspace,
+                          size_t workspace_bytes, void* stream, mxmoe_gg_plan_info* info);
+
+/* Two launches on `stream` (the planner kernel, then the GEMM kernel at grid tile_slots); no allocation, no
+ * synchronisation. dyn: DEVICE array of problem_count rows, read by the planner kernel when it runs. */
+int mxmoe_gg_launch_dynamic(const mxmoe_gg_plan_info* info, const mxmoe_gg_dyn_row* dyn, void* stream);
+
+/* The plan's status word (OR of MXMOE_GG_DYN_* since the plan or the last reset) into *status: synchronises
+ * `stream`, so not for use under capture. reset != 0 zeroes the word afterwards. */
+int mxmoe_gg_dynamic_status(const mxmoe_gg_plan_info* info, void* stream, int32_t* status, int reset);
+
+/* Diagnostics: the tile table the planner kernel would write for the HOST row table `dyn`, computed on the
+ * host by the very functions the kernel runs, without touching a device (pointers are not checked) — in
+ * mxmoe_gg_plan_tiles' format, 8 int32 per slot, prob = the caller's problem index. slot_limit > 0 plans with
+ * that many tile slots instead of the capacity bound. planned_rows (optional, problem_count int32) receives
+ * the rows each problem was planned with, *status the MXMOE_GG_DYN_* bits. Writes min(*slots, tile_slots)
+ * slots and sets *slots to tile_slots. */
+int mxmoe_gg_dynamic_tiles(const mxmoe_gg_problem* problems, int problem_count, int variant, const int32_t* joint_idx,
+                           int n_joint, int64_t rows_total, const mxmoe_gg_dyn_extent* extents,
+                           const mxmoe_gg_dyn_row* dyn, int slot_limit, int32_t* tiles, int32_t* planned_rows,
+                           int* slots, int32_t* status);
+
 #ifdef __cplusplus
 }
 #endif

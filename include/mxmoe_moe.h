@@ -139,6 +139,38 @@ int mxmoe_moe_gate_ex(const void* hidden, const void* w_gate, const void* w_shar
 int mxmoe_moe_route(const int32_t* topk_ids, int64_t T, int topk, int E, int32_t* sorted_expert,
                     int32_t* perm_token, int32_t* inv_slot, int32_t* counts, void* stream);
 
+/* The segment table on the device: what a host builds from the routing counts after copying them back
+ * (mxmoe_amd/moe.py, _make_segments), from the DEVICE counts[E] of mxmoe_moe_route, in one small launch — the
+ * piece that lets a whole layer run without the host ("Device planning / graph forward").
+ * No reference counterpart: the reference moves the counts to the host (ref_bind.cu:456).
+ * A table describes one activation buffer: qtags DEVICE int32 [nseg] (MXMOE_ACT_*, nseg = E + 1 with the
+ * shared expert), the routed segments' width and the shared one's. Written, per segment in expert order:
+ *   segs[e]   {qtag, first_slot = rows before e (shared: T * topk), rows = counts[e] (shared: T), width,
+ *              out_off, scale_off}: out_off advances by the segment's bytes rounded up to 16, scale_off by its
+ *              scale elements ([rows], g128 [width/128][rows], MXFP4 / MXFP8 rows * 16 ceil(width/32 / 16) / 2
+ *              after rounding scale_off up to even, fp16 none);
+ *   dyn[e]    (optional, mxmoe_gg_dyn_row of include/mxmoe_gg.h: the row table of the GroupGEMM that reads the
+ *              buffer) {rows, a_off = out_off, sa_off = 2 * scale_off, c_off = 2 * first_slot * ldc; shared: 0}.
+ * status (DEVICE int32, optional): bit MXMOE_MOE_SEG_COUNT_MISMATCH is OR-ed in when the counts do not sum to
+ * T * topk (ids outside [0, E) were dropped by the routing) or a count had to be clamped to keep the routed rows
+ * within T * topk. One launch fills up to two tables (a layer's gate_up and down inputs). */
+typedef struct mxmoe_moe_seg_table {
+  const int32_t* qtags;  /* DEVICE int32 [nseg] */
+  int32_t width;         /* elements per row of a routed segment (multiple of 128) */
+  int32_t width_shared;  /* ... of the shared segment (with_shared) */
+  int64_t ldc;           /* row stride, in fp16 elements, of the routed experts' C in the next GroupGEMM */
+  mxmoe_moe_seg* segs;   /* DEVICE out [nseg] */
+  void* dyn;             /* DEVICE out mxmoe_gg_dyn_row [nseg], or NULL */
+} mxmoe_moe_seg_table;
+enum { MXMOE_MOE_SEG_COUNT_MISMATCH = 1 };
+int mxmoe_moe_segments(const int32_t* counts, int E, int64_t T, int topk, int with_shared,
+                       const mxmoe_moe_seg_table* tables, int n_tables, int32_t* status, void* stream);
+
+/* Diagnostics: mxmoe_moe_segments' function run on the host. Every pointer (counts, the one table's qtags, segs,
+ * dyn, status) is HOST memory; no device is touched. */
+int mxmoe_moe_segments_host(const int32_t* counts, int E, int64_t T, int topk, int with_shared,
+                            const mxmoe_moe_seg_table* table, int32_t* status);
+
 /* Gather + quantise the permuted activations: slot s < T*topk reads hidden[perm_token[s]] and is
  * written to segment sorted_expert[s]; with_shared != 0 adds slots T*topk + t, which read hidden[t]
  * into the last segment (nseg - 1: the shared expert). hidden: fp16 [T][K]; segs: DEVICE array of nseg segments, every

@@ -92,6 +92,9 @@ EXPORTED_SYMBOLS = (
     "mxmoe_gg_variant_tile", "mxmoe_gg_variant_caps", "mxmoe_gg_resolve_variant", "mxmoe_gg_workspace_size", "mxmoe_gg_plan", "mxmoe_gg_rebind", "mxmoe_gg_forget_workspace", "mxmoe_gg_launch", "mxmoe_gg_run",
     "groupgemm_mxmoe", "groupgemm_mxmoe_fmt", "mxmoe_gg_release_shim_workspaces", "mxmoe_gg_repack_weightonly", "mxmoe_gg_debug_trace",
     "mxmoe_gg_plan_tiles",
+    # device planning (fixed-capacity plans: DESIGN.md §4)
+    "mxmoe_gg_dynamic_workspace_size", "mxmoe_gg_plan_dynamic", "mxmoe_gg_launch_dynamic", "mxmoe_gg_dynamic_status",
+    "mxmoe_gg_dynamic_tiles", "mxmoe_moe_segments", "mxmoe_moe_segments_host",
     # include/mxmoe_moe.h (MoE-layer plumbing)
     "mxmoe_moe_route", "mxmoe_moe_quant_act", "mxmoe_moe_silu_mul_quant", "mxmoe_moe_silu_mul_quant_il", "mxmoe_moe_quant_slots", "mxmoe_moe_combine",
     "mxmoe_moe_act_quant",
@@ -105,11 +108,59 @@ class MoeSegC(ctypes.Structure):
     _fields_ = [("qtag", ctypes.c_int32), ("first_slot", ctypes.c_int32), ("rows", ctypes.c_int32),
                 ("width", ctypes.c_int32), ("out_off", ctypes.c_int64), ("scale_off", ctypes.c_int64)]
 
+
+class GGDynRowC(ctypes.Structure):
+    """mxmoe_gg_dyn_row (include/mxmoe_gg.h): one problem's rows and byte offsets for a dynamic launch."""
+
+    _fields_ = [("rows", ctypes.c_int32), ("reserved", ctypes.c_int32), ("a_off", ctypes.c_int64),
+                ("sa_off", ctypes.c_int64), ("c_off", ctypes.c_int64)]
+
+
+class GGDynExtentC(ctypes.Structure):
+    """mxmoe_gg_dyn_extent: bytes behind a problem's A / scale_a / C base pointers."""
+
+    _fields_ = [("a_bytes", ctypes.c_int64), ("sa_bytes", ctypes.c_int64), ("c_bytes", ctypes.c_int64)]
+
+
+class MoeSegTableC(ctypes.Structure):
+    """mxmoe_moe_seg_table (include/mxmoe_moe.h): one activation buffer's segment table for mxmoe_moe_segments."""
+
+    _fields_ = [("qtags", ctypes.c_void_p), ("width", ctypes.c_int32), ("width_shared", ctypes.c_int32),
+                ("ldc", ctypes.c_int64), ("segs", ctypes.c_void_p), ("dyn", ctypes.c_void_p)]
+
+
+# mxmoe_gg_dynamic_status bits (MXMOE_GG_DYN_*) and mxmoe_moe_segments' (MXMOE_MOE_SEG_COUNT_MISMATCH)
+DYN_ROWS_CLAMPED, DYN_JOINT_CLAMPED, DYN_SLOTS_CUT, DYN_BAD_OFFSET = 1, 2, 4, 8
+SEG_COUNT_MISMATCH = 1
+
 _lib = None
 
 
 def _declare(lib: ctypes.CDLL) -> None:
     c = ctypes
+    if hasattr(lib, "mxmoe_gg_plan_dynamic"):  # (device planning; builds before it lack the symbols: A/B tools)
+        idx, ext, dyn = c.POINTER(c.c_int32), c.POINTER(GGDynExtentC), c.c_void_p
+        lib.mxmoe_gg_dynamic_workspace_size.restype = c.c_int
+        lib.mxmoe_gg_dynamic_workspace_size.argtypes = [c.POINTER(GGProblemC), c.c_int, c.c_int, idx, c.c_int, c.c_int64,
+                                                        c.POINTER(c.c_size_t)]
+        lib.mxmoe_gg_plan_dynamic.restype = c.c_int
+        lib.mxmoe_gg_plan_dynamic.argtypes = [c.POINTER(GGProblemC), c.c_int, c.c_int, idx, c.c_int, c.c_int64, ext,
+                                              c.c_void_p, c.c_size_t, c.c_void_p, c.POINTER(GGPlanInfo)]
+        lib.mxmoe_gg_launch_dynamic.restype = c.c_int
+        lib.mxmoe_gg_launch_dynamic.argtypes = [c.POINTER(GGPlanInfo), dyn, c.c_void_p]
+        lib.mxmoe_gg_dynamic_status.restype = c.c_int
+        lib.mxmoe_gg_dynamic_status.argtypes = [c.POINTER(GGPlanInfo), c.c_void_p, c.POINTER(c.c_int32), c.c_int]
+        lib.mxmoe_gg_dynamic_tiles.restype = c.c_int
+        lib.mxmoe_gg_dynamic_tiles.argtypes = [c.POINTER(GGProblemC), c.c_int, c.c_int, idx, c.c_int, c.c_int64, ext,
+                                               c.POINTER(GGDynRowC), c.c_int, c.c_void_p, c.c_void_p,
+                                               c.POINTER(c.c_int), c.POINTER(c.c_int32)]
+    if hasattr(lib, "mxmoe_moe_segments"):
+        lib.mxmoe_moe_segments.restype = c.c_int
+        lib.mxmoe_moe_segments.argtypes = [c.c_void_p, c.c_int, c.c_int64, c.c_int, c.c_int, c.POINTER(MoeSegTableC),
+                                           c.c_int, c.c_void_p, c.c_void_p]
+        lib.mxmoe_moe_segments_host.restype = c.c_int
+        lib.mxmoe_moe_segments_host.argtypes = [c.c_void_p, c.c_int, c.c_int64, c.c_int, c.c_int, c.POINTER(MoeSegTableC),
+                                                c.POINTER(c.c_int32)]
     lib.mxmoe_gg_abi_version.restype = c.c_int
     lib.mxmoe_gg_abi_version.argtypes = []
     lib.mxmoe_gg_last_error.restype = c.c_char_p
@@ -364,3 +415,48 @@ def workspace_size(problems, problem_count: int, variant: int) -> int:
     n = ctypes.c_size_t()
     check(lib().mxmoe_gg_workspace_size(problems, problem_count, variant, ctypes.byref(n)))
     return n.value
+
+
+def _joint_array(joint):
+    joint = [int(j) for j in joint]
+    return (ctypes.c_int32 * max(len(joint), 1))(*joint), len(joint)
+
+
+def dynamic_tiles(problems, variant: int, joint, rows_total: int, dyn_rows, extents=None, slot_limit: int = 0):
+    """Host run of the device tile planner (mxmoe_gg_dynamic_tiles; no device needed). ``problems``: GGProblemC at
+    their capacities, ``dyn_rows``: one (rows, a_off, sa_off, c_off) per problem. Returns (tiles [tile_slots, 8]
+    int32 in ``plan_tiles``' format with prob = the problem's index, the rows each problem was planned with,
+    the MXMOE_GG_DYN_* status bits)."""
+    import numpy as np
+
+    P = len(problems)
+    arr = (GGProblemC * max(P, 1))(*problems)
+    jarr, nj = _joint_array(joint)
+    rows = (GGDynRowC * max(P, 1))(*[GGDynRowC(int(r[0]), 0, int(r[1]), int(r[2]), int(r[3])) for r in dyn_rows])
+    ext = None if extents is None else (GGDynExtentC * max(P, 1))(*[GGDynExtentC(*map(int, e)) for e in extents])
+    n, st = ctypes.c_int(0), ctypes.c_int32(0)
+    args = (arr, P, variant, jarr, nj, int(rows_total), ext, rows, int(slot_limit))
+    check(lib().mxmoe_gg_dynamic_tiles(*args, None, None, ctypes.byref(n), ctypes.byref(st)))
+    tiles = np.zeros((n.value, 8), dtype=np.int32)
+    planned = np.zeros(max(P, 1), dtype=np.int32)
+    check(lib().mxmoe_gg_dynamic_tiles(*args, tiles.ctypes.data, planned.ctypes.data, ctypes.byref(n), ctypes.byref(st)))
+    return tiles, planned[:P], st.value
+
+
+def segments_host(counts, T: int, topk: int, qtags, width: int, width_shared: int = 0, ldc: int = 0):
+    """Host run of mxmoe_moe_segments' function (mxmoe_moe_segments_host): (list of MoeSegC, list of GGDynRowC,
+    status) for the routing counts; len(qtags) == len(counts) + 1 adds the shared segment."""
+    import numpy as np
+
+    E = len(counts)
+    nseg = len(qtags)
+    c = np.ascontiguousarray(counts, dtype=np.int32)
+    tags = np.ascontiguousarray(qtags, dtype=np.int32)
+    segs = (MoeSegC * nseg)()
+    dyn = (GGDynRowC * nseg)()
+    tb = MoeSegTableC(tags.ctypes.data, int(width), int(width_shared), int(ldc), ctypes.addressof(segs),
+                      ctypes.addressof(dyn))
+    st = ctypes.c_int32(0)
+    check(lib().mxmoe_moe_segments_host(c.ctypes.data, E, int(T), int(topk), int(nseg == E + 1), ctypes.byref(tb),
+                                        ctypes.byref(st)))
+    return list(segs), list(dyn), st.value

@@ -26,6 +26,7 @@
 
 #include "../../include/mxmoe_gg.h"
 #include "gg_device.h"
+#include "gg_dyn.h"
 #ifdef MXMOE_LAB
 #include "gg_f6.h"   // lab-only fp6 w4a4 route: measured slower than the int4 path
 #include "gg_v2q.h"  // lab-only persistent kernel: not compiled into the product library
@@ -2031,6 +2032,238 @@ int mxmoe_gg_run(const mxmoe_gg_problem* problems, int problem_count, int varian
   int st = mxmoe_gg_plan(problems, problem_count, variant, workspace, workspace_bytes, stream, &info);
   if (st) return st;
   return mxmoe_gg_launch(&info, stream);
+}
+
+// ---- Device planning (include/mxmoe_gg.h, gg_dyn.h): the static half of a fixed-capacity plan.
+// Workspace: the planned layout (plan table | 5 pointer columns | tile table, no split-K areas), then the
+// dynamic plan's own data: geometry rows | table order | per-workgroup scratch (rows, tile prefix) | status.
+namespace {
+constexpr int32_t kDynMagic = 0x44594E;  // mxmoe_gg_plan_info::reserved of a dynamic plan
+static_assert(sizeof(GGMeta) == kDynMetaWords * 4 && offsetof(GGMeta, M) == kDynMetaM * 4 &&
+                  offsetof(GGMeta, tile_begin) == kDynMetaTileBegin * 4 && sizeof(TileDesc) == kDynTileWords * 4 &&
+                  offsetof(TileDesc, ks1) == 20 && offsetof(TileDesc, grp) == 28,
+              "gg_dyn.h writes GGMeta / TileDesc by their raw layout");
+static_assert(sizeof(mxmoe_gg_dyn_row) == sizeof(DynRow) && offsetof(mxmoe_gg_dyn_row, c_off) == offsetof(DynRow, c_off),
+              "mxmoe_gg_dyn_row is DynRow");
+struct DynLayout {
+  size_t geom, order, rows, cum, status, total;
+};
+DynLayout dyn_layout(int P, int slots) {
+  DynLayout d;
+  const size_t p = (size_t)std::max(P, 1);
+  size_t o = align_up(ws_layout(P, slots, 0).total, 256);
+  d.geom = o, o += align_up(p * sizeof(DynGeom), 256);
+  d.order = o, o += align_up(p * sizeof(int32_t), 256);
+  d.rows = o, o += align_up(kDynMaxBlocks * p * sizeof(int32_t), 256);
+  d.cum = o, o += align_up(kDynMaxBlocks * (p + 1) * sizeof(int32_t), 256);
+  d.status = o, o += 256;
+  d.total = o;
+  return d;
+}
+struct DynPlan {
+  int variant = 0;
+  std::vector<GGMeta> meta;    // row i = the caller's problem i (M and tile_begin are the device planner's)
+  std::vector<DynGeom> geom;
+  std::vector<int32_t> order;  // tile-table order: problem indices, longest K stages first
+  int64_t rows_total = 0;
+  int slots = 0;
+  int qtype_mask = 0;
+};
+// bytes of one row's activation scales (0: the type has none)
+int64_t sa_row_bytes(int qt, int K) {
+  const QTypeInfo& t = qinfo(qt);
+  if (t.weight_only || t.float16) return 0;
+  if (t.dword_scales) return 16 * (((int64_t)K / 32 + 15) / 16);  // e8m0 bytes, the device layout
+  if (t.group_fold) return 2 * ((int64_t)K / t.k_mult);
+  return 2;
+}
+bool dyn_variant_ok(const Variant& v) {
+  if (v.persistent || (v.kind != Kind::V2 && v.kind != Kind::V3)) return false;
+  return !strcmp(v.name, kDefaultVariantName) || !strcmp(v.name, kInt4Variant) || !strcmp(v.name, kWoSmallVariant);
+}
+int plan_dynamic_host(const mxmoe_gg_problem* problems, int P, int variant, const int32_t* joint_idx, int n_joint,
+                      int64_t rows_total, const mxmoe_gg_dyn_extent* extents, bool check_ptrs, DynPlan* out) {
+  if (P < 0 || (P > 0 && !problems) || n_joint < 0 || n_joint > P || (n_joint > 0 && !joint_idx) || rows_total < 0 ||
+      rows_total > INT32_MAX)
+    return fail(MXMOE_GG_ERR_INVALID, "bad arguments to the dynamic plan (problems %d, joint %d, rows_total %lld)", P,
+                n_joint, (long long)rows_total);
+  std::vector<char> joint(P, 0);
+  for (int j = 0; j < n_joint; ++j) {
+    if (joint_idx[j] < 0 || joint_idx[j] >= P || joint[joint_idx[j]])
+      return fail(MXMOE_GG_ERR_INVALID, "joint_idx[%d] = %d is out of range or listed twice", j, joint_idx[j]);
+    joint[joint_idx[j]] = 1;
+  }
+  const std::vector<HostProblem> hp = to_host(problems, P);
+  std::vector<HostProblem> balanced = hp;  // what AUTO sees: the joint rows spread evenly
+  const int64_t share = n_joint ? (rows_total + n_joint - 1) / n_joint : 0;
+  for (int i = 0; i < P; ++i)
+    if (joint[i]) balanced[i].M = (int)std::min<int64_t>(hp[i].M, share);
+  int st = resolve_variant(variant, balanced, &variant);
+  if (st) return st;
+  const Variant& v = variants()[variant];
+  if (!dyn_variant_ok(v))
+    return fail(MXMOE_GG_ERR_UNSUPPORTED, "variant %s has no dynamic plan (v2x, v3 and wo3 only)", v.name);
+  out->variant = variant;
+  out->rows_total = rows_total;
+  out->meta.assign(P, GGMeta{});
+  out->geom.assign(P, DynGeom{});
+  out->qtype_mask = 0;
+  std::vector<double> cost(P, 0.0);
+  for (int i = 0; i < P; ++i) {
+    GGMeta& m = out->meta[i];
+    if ((st = build_meta(hp[i], i, v, check_ptrs, &m))) return st;
+    const QTypeInfo& t = qinfo(m.qtype);
+    const TileGeom& tg = v.geom[m.qtype];
+    DynGeom& g = out->geom[i];
+    g.cap = hp[i].M;
+    g.bm = tg.bm, g.bn = tg.bn;
+    g.tail_bm = v.tail_bm;  // (m_tiles' rule; dyn_variant_ok leaves no V0 kernel)
+    g.tail2_bm = t.small_class ? v.tail2_bm : 0;
+    g.tiles_n = m.tiles_n;
+    g.nst = stages_of(v, m);
+    g.joint = joint[i];
+    g.a_row = m.lda_b, g.sa_row = sa_row_bytes(m.qtype, hp[i].K), g.c_row = m.ldc * 2;
+    g.a_bytes = extents ? extents[i].a_bytes : g.cap * g.a_row;
+    g.sa_bytes = extents ? extents[i].sa_bytes : g.cap * g.sa_row;
+    g.c_bytes = extents ? extents[i].c_bytes : g.cap * g.c_row;
+    if (g.a_bytes < 0 || g.sa_bytes < 0 || g.c_bytes < 0) return fail(MXMOE_GG_ERR_INVALID, "problem %d: negative extent", i);
+    g.base_a = (uint64_t)(uintptr_t)hp[i].A, g.base_sa = (uint64_t)(uintptr_t)hp[i].SA, g.base_c = (uint64_t)(uintptr_t)hp[i].C;
+    g.sa_align = t.dword_scales ? 4 : 2;
+    cost[i] = stage_time(v, m, 0) * g.nst;
+    out->qtype_mask |= 1 << m.qtype;
+    if (t.weight_only && (m.reserved2 & META_SILU)) out->qtype_mask |= kQmaskWoSilu;
+    m.M = 0;  // the device planner's columns
+    m.tile_begin = 0;
+  }
+  if (P > 0 && v.pick(out->qtype_mask) < 0)
+    return fail(MXMOE_GG_ERR_UNSUPPORTED, "variant %s: quant-type mix %#x not compiled", v.name, out->qtype_mask);
+  out->order.resize(P);
+  for (int i = 0; i < P; ++i) out->order[i] = i;
+  std::stable_sort(out->order.begin(), out->order.end(), [&](int a, int b) { return cost[a] > cost[b]; });
+  std::vector<int32_t> scratch(std::max(P, 1));
+  const int64_t slots = dyn_capacity_slots(out->geom.data(), P, rows_total, scratch.data());
+  if (slots > ((int64_t)1 << 28)) return fail(MXMOE_GG_ERR_INVALID, "too many tile slots (%lld)", (long long)slots);
+  out->slots = (int)slots;
+  return MXMOE_GG_OK;
+}
+}  // namespace
+
+int mxmoe_gg_dynamic_workspace_size(const mxmoe_gg_problem* problems, int problem_count, int variant,
+                                    const int32_t* joint_idx, int n_joint, int64_t rows_total, size_t* bytes) {
+  if (!bytes) return fail(MXMOE_GG_ERR_INVALID, "bytes is NULL");
+  DynPlan plan;
+  if (int st = plan_dynamic_host(problems, problem_count, variant, joint_idx, n_joint, rows_total, nullptr, false, &plan))
+    return st;
+  *bytes = dyn_layout(problem_count, plan.slots).total;
+  return MXMOE_GG_OK;
+}
+
+int mxmoe_gg_plan_dynamic(const mxmoe_gg_problem* problems, int problem_count, int variant, const int32_t* joint_idx,
+                          int n_joint, int64_t rows_total, const mxmoe_gg_dyn_extent* extents, void* workspace,
+                          size_t workspace_bytes, void* stream, mxmoe_gg_plan_info* info) {
+  if (!info) return fail(MXMOE_GG_ERR_INVALID, "bad arguments to mxmoe_gg_plan_dynamic");
+  DynPlan plan;
+  if (int st = plan_dynamic_host(problems, problem_count, variant, joint_idx, n_joint, rows_total, extents, true, &plan))
+    return st;
+  const int P = problem_count;
+  const WsLayout l = ws_layout(P, plan.slots, 0);
+  const DynLayout d = dyn_layout(P, plan.slots);
+  if (!workspace || workspace_bytes < d.total)
+    return fail(MXMOE_GG_ERR_WORKSPACE, "workspace too small: need %zu bytes, have %zu", d.total, workspace_bytes);
+  std::vector<uint8_t> img(d.total, 0);  // (scratch and status start at zero)
+  if (P > 0) memcpy(img.data(), plan.meta.data(), (size_t)P * sizeof(GGMeta));
+  for (int i = 0; i < P; ++i) {  // the static columns (B, scale_b) and, until the first launch, the base pointers
+    const mxmoe_gg_problem& p = problems[i];
+    const void* cols[5] = {p.A, p.B, p.scale_a, p.scale_b, p.C};
+    for (int c = 0; c < 5; ++c) memcpy(img.data() + l.meta + c * l.ptr + (size_t)i * sizeof(void*), &cols[c], sizeof(void*));
+  }
+  TileDesc* tiles = reinterpret_cast<TileDesc*>(img.data() + l.meta + 5 * l.ptr);
+  for (int s = 0; s < plan.slots; ++s) tiles[s] = kEmptySlot;
+  if (P > 0) {
+    memcpy(img.data() + d.geom, plan.geom.data(), (size_t)P * sizeof(DynGeom));
+    memcpy(img.data() + d.order, plan.order.data(), (size_t)P * sizeof(int32_t));
+  }
+  memcpy(img.data() + d.status + 8, &plan.rows_total, sizeof(int64_t));
+  HIP_TRY(hipMemcpyAsync(workspace, img.data(), img.size(), hipMemcpyHostToDevice, (hipStream_t)stream));
+  HIP_TRY(hipStreamSynchronize((hipStream_t)stream));  // pageable host image must outlive the copy
+  mxmoe_gg_forget_workspace(workspace);                // (a dynamic plan is never rebound)
+  const Variant& v = variants()[plan.variant];
+  info->variant = plan.variant;
+  info->problem_count = P;
+  info->total_tiles = info->grid = info->tile_slots = plan.slots;
+  info->block = v.threads;
+  info->qtype_mask = plan.qtype_mask;
+  const int build = P > 0 ? v.pick(plan.qtype_mask) : -1;
+  info->lds_bytes = build >= 0 ? v.builds.rows[build].lds_bytes : v.lds_bytes;
+  info->splitk_slabs = 0;
+  info->workspace_bytes = (int64_t)d.total;
+  info->workspace = workspace;
+  uint64_t h = 1469598103934665603ull;
+  for (size_t i = 0; i < d.status && i < img.size(); ++i) h = (h ^ img[i]) * 1099511628211ull;
+  info->signature = h;
+  info->reserved = kDynMagic;
+  return MXMOE_GG_OK;
+}
+
+int mxmoe_gg_launch_dynamic(const mxmoe_gg_plan_info* info, const mxmoe_gg_dyn_row* dyn, void* stream) {
+  if (!info || info->reserved != kDynMagic || !info->workspace || info->problem_count < 0 || info->tile_slots < 0)
+    return fail(MXMOE_GG_ERR_INVALID, "mxmoe_gg_launch_dynamic: not a plan of mxmoe_gg_plan_dynamic");
+  if (int st = check_variant(info->variant)) return st;
+  const int P = info->problem_count, slots = info->tile_slots;
+  if (P == 0 || slots == 0) return MXMOE_GG_OK;
+  if (!dyn || ((uintptr_t)dyn & 7)) return fail(MXMOE_GG_ERR_INVALID, "mxmoe_gg_launch_dynamic: NULL or misaligned row table");
+  const WsLayout l = ws_layout(P, slots, 0);
+  const DynLayout d = dyn_layout(P, slots);
+  uint8_t* ws = static_cast<uint8_t*>(info->workspace);
+  DynArgs a;
+  a.geom = reinterpret_cast<const DynGeom*>(ws + d.geom);
+  a.order = reinterpret_cast<const int32_t*>(ws + d.order);
+  a.rows = reinterpret_cast<int32_t*>(ws + d.rows);
+  a.cum = reinterpret_cast<int32_t*>(ws + d.cum);
+  a.status = reinterpret_cast<int32_t*>(ws + d.status);
+  a.meta = reinterpret_cast<int32_t*>(ws);
+  a.ptr_A = reinterpret_cast<const void**>(ws + l.meta);
+  a.ptr_SA = reinterpret_cast<const void**>(ws + l.meta + 2 * l.ptr);
+  a.ptr_C = reinterpret_cast<void**>(ws + l.meta + 4 * l.ptr);
+  a.tiles = reinterpret_cast<int32_t*>(ws + l.meta + 5 * l.ptr);
+  a.dyn = reinterpret_cast<const DynRow*>(dyn);
+  a.rows_total = reinterpret_cast<const int64_t*>(ws + d.status + 8);  // (static plan data, beside the status word)
+  a.P = P, a.tile_slots = slots;
+  detail::launch_dyn_plan(a, (hipStream_t)stream);
+  HIP_TRY(hipGetLastError());
+  return mxmoe_gg_launch(info, stream);
+}
+
+int mxmoe_gg_dynamic_status(const mxmoe_gg_plan_info* info, void* stream, int32_t* status, int reset) {
+  if (!info || info->reserved != kDynMagic || !info->workspace || !status)
+    return fail(MXMOE_GG_ERR_INVALID, "mxmoe_gg_dynamic_status: not a plan of mxmoe_gg_plan_dynamic");
+  void* word = static_cast<uint8_t*>(info->workspace) + dyn_layout(info->problem_count, info->tile_slots).status;
+  HIP_TRY(hipMemcpyAsync(status, word, sizeof(int32_t), hipMemcpyDeviceToHost, (hipStream_t)stream));
+  if (reset) HIP_TRY(hipMemsetAsync(word, 0, sizeof(int32_t), (hipStream_t)stream));
+  HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+  return MXMOE_GG_OK;
+}
+
+int mxmoe_gg_dynamic_tiles(const mxmoe_gg_problem* problems, int problem_count, int variant, const int32_t* joint_idx,
+                           int n_joint, int64_t rows_total, const mxmoe_gg_dyn_extent* extents,
+                           const mxmoe_gg_dyn_row* dyn, int slot_limit, int32_t* tiles, int32_t* planned_rows,
+                           int* slots, int32_t* status) {
+  if (!slots || *slots < 0 || (*slots > 0 && !tiles) || (problem_count > 0 && !dyn))
+    return fail(MXMOE_GG_ERR_INVALID, "bad arguments to mxmoe_gg_dynamic_tiles");
+  DynPlan plan;
+  if (int st = plan_dynamic_host(problems, problem_count, variant, joint_idx, n_joint, rows_total, extents, false, &plan))
+    return st;
+  const int P = problem_count, tile_slots = slot_limit > 0 ? slot_limit : plan.slots;
+  std::vector<int32_t> rows(std::max(P, 1)), cum(P + 1);
+  const int32_t st = dyn_plan_rows(plan.geom.data(), plan.order.data(), P, rows_total, tile_slots,
+                                   reinterpret_cast<const DynRow*>(dyn), rows.data(), cum.data());
+  const int n = std::min(*slots, tile_slots);
+  for (int s = 0; s < n; ++s) dyn_tile_at(plan.geom.data(), plan.order.data(), P, rows.data(), cum.data(), s, tiles + 8 * (size_t)s);
+  if (planned_rows)
+    for (int i = 0; i < P; ++i) planned_rows[i] = rows[i];
+  if (status) *status = st;
+  *slots = tile_slots;
+  return MXMOE_GG_OK;
 }
 
 // Reference-compatible entry point (registry.cuh:28-39): device pointer arrays, host copies of

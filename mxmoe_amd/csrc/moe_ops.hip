@@ -24,11 +24,19 @@
 #include "../../include/mxmoe_gg.h"
 #include "../../include/mxmoe_moe.h"
 #include "moe_gate.h"
+#define MXMOE_DYN_KERNEL  // gg_dyn.h: the GroupGEMM's device tile planner kernel is compiled here
+#include "gg_dyn.h"
 
 namespace mxmoe {
 namespace detail {
 int set_error(int code, const std::string& msg);  // gg_api.hip (thread-local mxmoe_gg_last_error)
+
+void launch_dyn_plan(const DynArgs& a, hipStream_t stream) {
+  const int want = (a.tile_slots + kDynSlotsPerBlock - 1) / kDynSlotsPerBlock;
+  const int blocks = want < 1 ? 1 : want > kDynMaxBlocks ? kDynMaxBlocks : want;
+  hipLaunchKernelGGL(dyn_plan_kernel, dim3(blocks), dim3(256), 0, stream, a);
 }
+}  // namespace detail
 
 namespace {
 
@@ -474,6 +482,85 @@ __global__ __launch_bounds__(kThreads) void combine_kernel(const _Float16* __res
 
 bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
+// ---------------------------------------------------------------------------------------------
+// segments: the segment table (and the next GroupGEMM's row table) from the routing counts. One function
+// for the kernel and the host diagnostic. Offsets as mxmoe_amd/moe.py's _make_segments lays them out: 16-B
+// aligned out_off, even scale_off for the block-scaled tags, the shared segment last with rows = T.
+// A count is clamped so the routed rows never exceed T * topk (route counts every id at most once, so a
+// clamp means the counts are not route's); a clamp or a sum below T * topk (ids outside [0, E)) sets bit 0
+// of the returned status.
+__host__ __device__ inline int act_bits(int tag) {
+  return tag == MXMOE_ACT_INT8 || tag == MXMOE_ACT_MXFP8 ? 8
+         : tag == MXMOE_ACT_INT4 || tag == MXMOE_ACT_INT4_G128 || tag == MXMOE_ACT_MXFP4 ? 4 : 16;
+}
+__host__ __device__ inline int32_t fill_segments(const int32_t* counts, int E, int64_t T, int topk, bool with_shared,
+                                                 const mxmoe_moe_seg_table& tb) {
+  const int64_t ntk = T * topk;
+  int64_t off = 0, soff = 0, first = 0;
+  int32_t status = 0;
+  mxmoe_gg_dyn_row* dyn = static_cast<mxmoe_gg_dyn_row*>(tb.dyn);
+  for (int e = 0; e < E + (with_shared ? 1 : 0); ++e) {
+    const bool shared = e == E;
+    int64_t r = shared ? T : counts[e];
+    if (!shared && (r < 0 || r > ntk - first)) {
+      status |= MXMOE_MOE_SEG_COUNT_MISMATCH;
+      r = r < 0 ? 0 : ntk - first;
+    }
+    const int tag = tb.qtags[e], w = shared ? tb.width_shared : tb.width;
+    const bool mx = tag == MXMOE_ACT_MXFP4 || tag == MXMOE_ACT_MXFP8;
+    if (mx) soff += soff & 1;  // its scale bytes are read as dwords: a 4-byte aligned block
+    const int64_t f = shared ? ntk : first;
+    tb.segs[e] = mxmoe_moe_seg{tag, (int32_t)f, (int32_t)r, w, off, soff};
+    if (dyn) dyn[e] = mxmoe_gg_dyn_row{(int32_t)r, 0, off, soff * 2, shared ? 0 : f * tb.ldc * 2};
+    off += (r * w * act_bits(tag) / 8 + 15) / 16 * 16;
+    if (mx) soff += r * (16 * ((w / 32 + 15) / 16)) / 2;  // (fp16 elements: two e8m0 bytes each)
+    else soff += tag == MXMOE_ACT_FP16 ? 0 : r * (tag == MXMOE_ACT_INT4_G128 ? w / 128 : 1);
+    if (!shared) first += r;
+  }
+  if (first != ntk) status |= MXMOE_MOE_SEG_COUNT_MISMATCH;
+  return status;
+}
+struct SegArgs {
+  const int32_t* counts;
+  int E, topk, with_shared, n_tables;
+  int64_t T;
+  int32_t* status;
+  mxmoe_moe_seg_table tables[2];
+};
+// thread t fills table t (a layer has two: the gate_up and the down GEMM's inputs). The counts and tags are first
+// copied into LDS by the whole workgroup: the sequential walk then waits on no global load (from global memory
+// it took 41 us for 61 segments, profiles/r12/graph_forward/). More than kSegLdsExperts experts: from global.
+constexpr int kSegLdsExperts = 1024;
+__global__ __launch_bounds__(kThreads) void segments_kernel(SegArgs a) {
+  __shared__ int32_t s_counts[kSegLdsExperts];
+  __shared__ int32_t s_tags[2][kSegLdsExperts + 1];
+  const int nseg = a.E + (a.with_shared ? 1 : 0);
+  const bool lds = a.E <= kSegLdsExperts;  // (uniform)
+  if (lds) {
+    for (int i = threadIdx.x; i < a.E; i += blockDim.x) s_counts[i] = a.counts[i];
+    for (int t = 0; t < a.n_tables; ++t)
+      for (int i = threadIdx.x; i < nseg; i += blockDim.x) s_tags[t][i] = a.tables[t].qtags[i];
+    __syncthreads();
+  }
+  if ((int)threadIdx.x >= a.n_tables) return;
+  mxmoe_moe_seg_table tb = a.tables[threadIdx.x];
+  if (lds) tb.qtags = s_tags[threadIdx.x];
+  const int32_t st = fill_segments(lds ? s_counts : a.counts, a.E, a.T, a.topk, a.with_shared != 0, tb);
+  if (st && a.status && threadIdx.x == 0) *a.status = *a.status | st;  // (every table sees the same counts)
+}
+
+int segments_check(const int32_t* counts, int E, int64_t T, int topk, const mxmoe_moe_seg_table* tables, int n_tables) {
+  if (!counts || E < 1 || E > 4096 || T < 0 || topk < 1 || T * topk > (int64_t)1 << 30 || !tables || n_tables < 1 ||
+      n_tables > 2)
+    return fail(MXMOE_GG_ERR_INVALID, "mxmoe_moe_segments: need counts, 1 <= E <= 4096, T >= 0, topk >= 1, 1 or 2 tables");
+  for (int t = 0; t < n_tables; ++t)
+    if (!tables[t].qtags || !tables[t].segs || tables[t].width <= 0 || tables[t].width % 128 || tables[t].width_shared < 0 ||
+        tables[t].width_shared % 128 || tables[t].ldc < 0 || tables[t].ldc % 8)
+      return fail(MXMOE_GG_ERR_INVALID, "mxmoe_moe_segments: table %d: NULL pointer, a width that is no multiple of 128 "
+                  "or an ldc that is no multiple of 8", t);
+  return MXMOE_GG_OK;
+}
+
 }  // namespace
 }  // namespace mxmoe
 
@@ -644,6 +731,31 @@ int mxmoe_moe_route(const int32_t* topk_ids, int64_t T, int topk, int E, int32_t
                      sorted_expert, perm_token, inv_slot, counts);
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail(MXMOE_GG_ERR_HIP, "route_kernel launch failed: %s", hipGetErrorString(e));
+  return MXMOE_GG_OK;
+}
+
+int mxmoe_moe_segments(const int32_t* counts, int E, int64_t T, int topk, int with_shared,
+                       const mxmoe_moe_seg_table* tables, int n_tables, int32_t* status, void* stream) {
+  if (int st = segments_check(counts, E, T, topk, tables, n_tables)) return st;
+  SegArgs a{counts, E, topk, with_shared, n_tables, T, status, {}};
+  for (int t = 0; t < n_tables; ++t) {
+    if (with_shared && tables[t].width_shared == 0)
+      return fail(MXMOE_GG_ERR_INVALID, "mxmoe_moe_segments: table %d: with_shared needs width_shared", t);
+    a.tables[t] = tables[t];
+  }
+  hipLaunchKernelGGL(segments_kernel, dim3(1), dim3(kThreads), 0, (hipStream_t)stream, a);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(MXMOE_GG_ERR_HIP, "segments_kernel launch failed: %s", hipGetErrorString(e));
+  return MXMOE_GG_OK;
+}
+
+int mxmoe_moe_segments_host(const int32_t* counts, int E, int64_t T, int topk, int with_shared,
+                            const mxmoe_moe_seg_table* table, int32_t* status) {
+  if (int st = segments_check(counts, E, T, topk, table, 1)) return st;
+  if (with_shared && table->width_shared == 0)
+    return fail(MXMOE_GG_ERR_INVALID, "mxmoe_moe_segments_host: with_shared needs width_shared");
+  const int32_t st = fill_segments(counts, E, T, topk, with_shared != 0, *table);
+  if (status) *status = st;
   return MXMOE_GG_OK;
 }
 

@@ -289,6 +289,78 @@ class GroupGemm:
     __call__ = launch
 
 
+class DynamicGroupGemm:
+    """A GroupGEMM planned once at fixed capacity whose row counts live on the device (mxmoe_gg_plan_dynamic,
+    include/mxmoe_gg.h; DESIGN.md §4 "Device planning / graph forward").
+
+    ``problems``: every problem at its capacity ``M``, with ``A`` / ``scale_a`` / ``C`` the base tensors the
+    per-launch byte offsets are added to (a tensor may be larger than M rows: a shared store). ``joint``:
+    indices of the problems that share ``sum rows <= rows_total`` (a MoE layer's routed experts).
+    ``launch(dyn)`` takes a device row table (``row_table``): uint8 [P, 32], rows of
+    {int32 rows, int32 0, int64 a_off, int64 sa_off, int64 c_off}; it issues two kernel launches, allocates and
+    synchronises nothing, and can be captured into a graph. ``status()`` reads the OR of the MXMOE_GG_DYN_* bits
+    (a clamped count, a refused offset) — it synchronises. Variants: v2x, v3 and wo3; ``variant=None`` resolves
+    AUTO once, for the balanced call (every joint problem at ceil(rows_total / len(joint)) rows)."""
+
+    def __init__(self, problems: Sequence[Problem], joint: Sequence[int], rows_total: int,
+                 variant: Optional[int] = None, device: Optional[torch.device] = None,
+                 stream: Optional[torch.cuda.Stream] = None, extents: Optional[Sequence[tuple]] = None):
+        self.problems = list(problems)
+        if device is None:
+            device = self.problems[0].C.device if self.problems else torch.device("cuda")
+        self.device = device
+        for p in self.problems:
+            for t in (p.A, p.B, p.C, p.scale_a, p.scale_b):
+                if t is not None and t.device != device:
+                    raise ValueError(f"all tensors must live on {device}, got {t.device}")
+        P = len(self.problems)
+        self.joint = [int(j) for j in joint]
+        self.rows_total = int(rows_total)
+        if extents is None:  # what the tensors hold behind their first element
+            def nbytes(t):
+                return 0 if t is None else t.numel() * t.element_size()
+
+            extents = [(nbytes(p.A), nbytes(p.scale_a), nbytes(p.C)) for p in self.problems]
+        self._c_problems = (nat.GGProblemC * max(P, 1))(*[p.to_c() for p in self.problems])
+        jarr, nj = nat._joint_array(self.joint)
+        ext = (nat.GGDynExtentC * max(P, 1))(*[nat.GGDynExtentC(*map(int, e)) for e in extents])
+        v = nat.VARIANT_AUTO if variant is None else int(variant)
+        n = ctypes.c_size_t()
+        nat.check(nat.lib().mxmoe_gg_dynamic_workspace_size(self._c_problems, P, v, jarr, nj, self.rows_total,
+                                                            ctypes.byref(n)))
+        self.workspace = torch.empty(n.value, dtype=torch.uint8, device=device)
+        self.info = nat.GGPlanInfo()
+        nat.check(nat.lib().mxmoe_gg_plan_dynamic(self._c_problems, P, v, jarr, nj, self.rows_total, ext,
+                                                  ctypes.c_void_p(self.workspace.data_ptr()), n.value,
+                                                  ctypes.c_void_p(_stream_handle(stream)), ctypes.byref(self.info)))
+        self.variant = int(self.info.variant)
+
+    @property
+    def tile_slots(self) -> int:
+        return self.info.tile_slots
+
+    @staticmethod
+    def row_table(rows: Sequence[tuple], device) -> torch.Tensor:
+        """A device row table from (rows, a_off, sa_off, c_off) tuples (a host-built one: tests, fixed routings)."""
+        arr = (nat.GGDynRowC * max(len(rows), 1))(*[nat.GGDynRowC(int(r[0]), 0, int(r[1]), int(r[2]), int(r[3]))
+                                                    for r in rows])
+        return torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).view(-1, 32).to(device)
+
+    def launch(self, dyn: torch.Tensor, stream: Optional[torch.cuda.Stream] = None) -> None:
+        if dyn.device != self.device or not dyn.is_contiguous() or dyn.numel() * dyn.element_size() < 32 * len(self.problems):
+            raise ValueError(f"dyn must be a contiguous row table of {len(self.problems)} 32-byte rows on {self.device}")
+        nat.check(nat.lib().mxmoe_gg_launch_dynamic(ctypes.byref(self.info), ctypes.c_void_p(dyn.data_ptr()),
+                                                    ctypes.c_void_p(_stream_handle(stream))))
+
+    __call__ = launch
+
+    def status(self, reset: bool = False, stream: Optional[torch.cuda.Stream] = None) -> int:
+        st = ctypes.c_int32(0)
+        nat.check(nat.lib().mxmoe_gg_dynamic_status(ctypes.byref(self.info), ctypes.c_void_p(_stream_handle(stream)),
+                                                    ctypes.byref(st), int(reset)))
+        return st.value
+
+
 def group_gemm(problems: Sequence[Problem], variant: Optional[int] = None,
                stream: Optional[torch.cuda.Stream] = None) -> None:
     """Plan + launch once (the reference host API's per-call behaviour)."""

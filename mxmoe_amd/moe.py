@@ -30,7 +30,7 @@ from typing import Optional, Sequence
 import torch
 
 from . import _native as nat
-from .groupgemm import GroupGemm, Problem, QParams
+from .groupgemm import DynamicGroupGemm, GroupGemm, Problem, QParams
 
 ACT_FP16, ACT_INT8, ACT_INT4, ACT_INT4_G128, ACT_MXFP4 = 0, 1, 2, 3, 4
 ACT_MXFP8 = 6  # MXMOE_ACT_MXFP8 (w4a8_g32_sym_MXFP8); 5 is not assigned (include/mxmoe_moe.h)
@@ -788,6 +788,161 @@ class PlannedForward:
         return self.out
 
 
+class GraphForward:
+    """A MoE layer (``MoEFFN``, or a ``MoEBlock`` with its router) planned once for ``T`` tokens whatever the
+    routing: every buffer is allocated and both GroupGEMMs are planned here, at capacity (DynamicGroupGemm),
+    and ``launch`` only issues kernel launches — gate (block only) -> route -> segments -> quant_act -> gate_up
+    -> SiLU / quant -> down -> combine — with nothing copied to the host, so it can be captured with
+    ``torch.cuda.graph`` and replayed while the routing changes (DESIGN.md §4 "Device planning / graph forward").
+
+    The segment tables and the GroupGEMMs' row tables are written on the device from the routing counts
+    (mxmoe_moe_segments), the tile tables by the device planner. Activation stores are sized for the worst case
+    over the layer's tags; h1, y and out have their usual sizes. The gate_up mode ("fused" / "interleaved" /
+    "plain") is fixed here from the chosen variant's capabilities, as ``MoEFFN.gate_up_call`` does per call.
+    ``inv_slot`` starts zeroed: an id outside [0, E) spoils that token's value but every access stays inside the
+    buffers; ``status()`` reports it (bit SEG_STATUS_SHIFT: the counts did not sum to T * topk; low bits: the
+    MXMOE_GG_DYN_* bits of the two GroupGEMMs — all zero for a clean run)."""
+
+    SEG_STATUS_SHIFT = 4
+
+    def __init__(self, layer, T: int, topk: Optional[int] = None, device=None):
+        self.block = layer if isinstance(layer, MoEBlock) else None
+        self.ffn = ffn = layer.ffn if self.block is not None else layer
+        if self.block is not None:
+            if topk is not None and topk != self.block.topk:
+                raise ValueError(f"topk = {topk} differs from the block's {self.block.topk}")
+            topk = self.block.topk
+        if topk is None or topk < 1 or T < 1:
+            raise ValueError("GraphForward needs T >= 1 and, for a MoEFFN, topk >= 1")
+        dev = torch.device(device) if device is not None else ffn.w1[0].B.device
+        self.T, self.topk, self.device = T, topk, dev
+        E, H, N, Ns, shared = ffn.E, ffn.H, ffn.N, ffn.Ns, ffn.has_shared
+        n, nseg = T * topk, ffn.E + (1 if ffn.has_shared else 0)
+        self.nseg = nseg
+        i32 = dict(dtype=torch.int32, device=dev)
+        # routing: zeroed once (slots an invalid id leaves unwritten then point at slot / expert 0)
+        self.route_bufs = tuple(torch.zeros(n, **i32) for _ in range(3)) + (torch.zeros(E, **i32),)
+        self.gate_out = None
+        if self.block is not None:
+            self.gate_out = (torch.zeros(T, topk, **i32), torch.zeros(T, topk, dtype=torch.float32, device=dev),
+                             torch.zeros(T, dtype=torch.float32, device=dev) if self.block.w_shared_gate is not None else None)
+        self.tags = [torch.tensor(t, **i32) for t in (ffn.tag1, ffn.tag2)]
+        self.segs = [torch.zeros(nseg * ctypes.sizeof(nat.MoeSegC), dtype=torch.uint8, device=dev) for _ in range(2)]
+        self.dyn = [torch.zeros(nseg, ctypes.sizeof(nat.GGDynRowC), dtype=torch.uint8, device=dev) for _ in range(2)]
+        self.seg_status = torch.zeros(1, **i32)
+
+        def stores(tags, w, ws):
+            """Worst-case activation and scale stores over the tags present (16-B / dword padding per segment)."""
+            def scale_row(tag, width):
+                return (_mx_scale_row(width) // 2 if tag in _MX_TAGS else width // 128 if tag == ACT_INT4_G128 else
+                        0 if tag == ACT_FP16 else 1)
+
+            nbytes = n * w * max(_BITS[t] for t in tags[:E]) // 8 + 16 * E
+            nscale = n * max(scale_row(t, w) for t in tags[:E]) + E
+            if shared:
+                nbytes += T * ws * _BITS[tags[E]] // 8 + 16
+                nscale += T * scale_row(tags[E], ws) + 1
+            return (torch.zeros(nbytes, dtype=torch.uint8, device=dev),
+                    torch.zeros(max(nscale, 1), dtype=torch.float16, device=dev))
+
+        self.a1, self.s1 = stores(ffn.tag1, H, H)
+        self.a2, self.s2 = stores(ffn.tag2, N, Ns)
+        self.mask1, self.mask2 = _tag_mask(ffn.tag1), _tag_mask(ffn.tag2)
+
+        def plan(ws, store, scales, tags, C_routed, C_shared, silu):
+            ps = []
+            for e in range(nseg):
+                w = ws[e]
+                tag = tags[e]
+                A = store.view(torch.float16) if tag == ACT_FP16 else store
+                sa = None if tag == ACT_FP16 else scales.view(torch.uint8) if tag in _MX_TAGS else scales
+                ps.append(Problem(A=A, B=w.B, C=C_shared if e == E else C_routed, M=T if e == E else n, N=w.N, K=w.K,
+                                  q=w.q, scale_a=sa, scale_b=w.scale_b, silu=silu))
+            return DynamicGroupGemm(ps, joint=range(E), rows_total=n, device=dev)
+
+        if ffn.gate_up_mode not in (None, "interleaved"):
+            raise ValueError(f"gate_up_mode must be None or 'interleaved', got {ffn.gate_up_mode!r}")
+        self.mode = "plain" if not ffn.fuse_silu else "interleaved" if ffn.gate_up_mode == "interleaved" else "fused"
+        while True:
+            f = 1 if self.mode == "fused" else 2
+            self.h1 = torch.zeros(n, f * N, dtype=torch.float16, device=dev)
+            self.h1s = torch.zeros(T, f * Ns, dtype=torch.float16, device=dev) if shared else None
+            try:
+                self.g1 = plan(ffn.w1, self.a1, self.s1, ffn.tag1, self.h1, self.h1s, self.mode == "fused")
+                break
+            except nat.GGError as err:  # the variant chosen at capacity has no SiLU epilogue for these types
+                if self.mode != "fused" or err.status != nat.MXMOE_GG_ERR_UNSUPPORTED:
+                    raise
+                self.mode = "interleaved"
+        self.y = torch.zeros(n, H, dtype=torch.float16, device=dev)
+        self.ys = torch.zeros(T, H, dtype=torch.float16, device=dev) if shared else None
+        self.g2 = plan(ffn.w2, self.a2, self.s2, ffn.tag2, self.y, self.ys, False)
+        self.out = torch.zeros(T, H, dtype=torch.float16, device=dev)
+        self._tables = (nat.MoeSegTableC * 2)(
+            nat.MoeSegTableC(self.tags[0].data_ptr(), H, H if shared else 0, self.h1.shape[1], self.segs[0].data_ptr(),
+                             self.dyn[0].data_ptr()),
+            nat.MoeSegTableC(self.tags[1].data_ptr(), N, Ns, H, self.segs[1].data_ptr(), self.dyn[1].data_ptr()))
+
+    def launch(self, hidden: torch.Tensor, topk_ids: Optional[torch.Tensor] = None,
+               topk_weights: Optional[torch.Tensor] = None, shared_w: Optional[torch.Tensor] = None,
+               stream: Optional[torch.cuda.Stream] = None) -> torch.Tensor:
+        """Launches only; returns ``self.out`` (fp16 [T, H]). A MoEFFN takes int32 ids and f32 weights [T, topk]
+        (contiguous, as nothing may be converted here) and the optional f32 shared_w [T]; a MoEBlock routes itself."""
+        ffn, T, topk, lib = self.ffn, self.T, self.topk, nat.lib()
+        if tuple(hidden.shape) != (T, ffn.H) or hidden.dtype != torch.float16 or not hidden.is_contiguous():
+            raise ValueError(f"hidden must be a contiguous fp16 [{T}, {ffn.H}] tensor")
+        if self.block is not None:
+            if topk_ids is not None or topk_weights is not None or shared_w is not None:
+                raise ValueError("a MoEBlock routes itself: launch(hidden)")
+            b = self.block
+            topk_ids, topk_weights, shared_w = gate(hidden, b.w_gate, topk, renormalize=b.renormalize,
+                                                    w_shared_gate=b.w_shared_gate, stream=stream, out=self.gate_out,
+                                                    **b.routing)
+        else:
+            for t, dt, shape, what in ((topk_ids, torch.int32, (T, topk), "topk_ids"),
+                                       (topk_weights, torch.float32, (T, topk), "topk_weights"),
+                                       (shared_w, torch.float32, (T,), "shared_w")):
+                if t is None and what == "shared_w":
+                    continue
+                if t is None or t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous():
+                    raise ValueError(f"{what} must be a contiguous {dt} {list(shape)} tensor")
+        st = _stream(stream)
+        sorted_e, perm, inv, counts = route_device(topk_ids, ffn.E, stream, out=self.route_bufs)
+        shared = ffn.has_shared
+        nat.check(lib.mxmoe_moe_segments(_ptr(counts), ffn.E, T, topk, int(shared), self._tables, 2,
+                                         _ptr(self.seg_status), st))
+        if any(t in _MX_TAGS for t in ffn.tag1):
+            nat.check(lib.mxmoe_moe_act_quant(0, _ptr(hidden), _ptr(hidden) if shared else None, T, topk, ffn.H, ffn.H,
+                                              _ptr(sorted_e), _ptr(perm), _ptr(self.segs[0]), self.nseg, self.mask1,
+                                              _ptr(self.a1), _ptr(self.s1), st))
+        else:
+            nat.check(lib.mxmoe_moe_quant_act(_ptr(hidden), T, ffn.H, topk, int(shared), _ptr(sorted_e), _ptr(perm),
+                                              _ptr(self.segs[0]), self.nseg, _ptr(self.a1), _ptr(self.s1), st))
+        self.g1.launch(self.dyn[0], stream)
+        mode = {"plain": 1, "fused": 2, "interleaved": 3}[self.mode]
+        if any(t in _MX_TAGS for t in ffn.tag2):
+            nat.check(lib.mxmoe_moe_act_quant(mode, _ptr(self.h1), _ptr(self.h1s), T, topk, ffn.N, ffn.Ns, _ptr(sorted_e),
+                                              None, _ptr(self.segs[1]), self.nseg, self.mask2, _ptr(self.a2),
+                                              _ptr(self.s2), st))
+        else:
+            fn = (lib.mxmoe_moe_silu_mul_quant, lib.mxmoe_moe_quant_slots, lib.mxmoe_moe_silu_mul_quant_il)[mode - 1]
+            nat.check(fn(_ptr(self.h1), _ptr(self.h1s), T, topk, ffn.N, ffn.Ns, _ptr(sorted_e), _ptr(self.segs[1]),
+                         self.nseg, _ptr(self.a2), _ptr(self.s2), st))
+        self.g2.launch(self.dyn[1], stream)
+        nat.check(lib.mxmoe_moe_combine(_ptr(self.y), _ptr(inv), _ptr(topk_weights), _ptr(self.ys), _ptr(shared_w), T, topk,
+                                        ffn.H, _ptr(self.out), st))
+        return self.out
+
+    __call__ = launch
+
+    def status(self, reset: bool = False) -> int:
+        """0 for a clean history; synchronises (not for use under capture)."""
+        seg = int(self.seg_status.item())
+        if reset:
+            self.seg_status.zero_()
+        return self.g1.status(reset) | self.g2.status(reset) | (seg << self.SEG_STATUS_SHIFT)
+
+
 def qwen2_layer_bench(rounds: int = 4, iters: int = 30, bs: int = 8192, model: str = "qwen2_moe",
                       interleaved: bool = False, scheme: str = "lp1") -> dict:
     """qwen2_moe layer 11 (LP-1 mixed w4a4 + w8a8 qconfig, the committed routing histogram) — or
@@ -849,6 +1004,124 @@ def qwen2_layer_bench(rounds: int = 4, iters: int = 30, bs: int = 8192, model: s
     names = [ln.split()[1] for ln in nat.list_variants()]
     out["gate_up_variant"] = {n: names[st.g1.variant] for n, st in steps.items()}
     return out
+
+
+def graph_forward_bench(batches: Sequence[int] = (128,), model: str = "qwen2_moe", rounds: int = 4,
+                        iters: int = 20):
+    """One MoE FFN layer (qwen2_moe layer 11 with the LP-1 mixed w4a4 + w8a8 qconfig, or model="ds2": the
+    DeepSeek-V2-Lite mixed layer) at every batch size of ``batches`` (yields one dict each), random weights,
+    routing drawn from the committed histogram (top-4 / top-6 distinct experts per token), three ways in one process, the sides alternating over rounds:
+      eager    MoEFFN.forward, wall time per call with a synchronise per call (host round trip, two host plans);
+      planned  PlannedForward, device time (host-planned for this very routing: XCD-packed, split-K allowed);
+      graph    GraphForward replayed from a captured graph, wall time (with a synchronise) and device time.
+    Per side the median of the rounds' medians with min / max (µs); the two GroupGEMMs alone on both plans, the
+    planner + GEMM pair against the GEMM at the capacity grid (their difference is the planner kernel), the
+    segment kernel, and the tile slots launched against the tiles the routing uses."""
+    import time
+
+    from .harness import time_launches
+    from .workload import ds2_mixed_qconfig, ds2_workload, load_workload, mixed_qconfig_lp1, qwen2_layer11_workload
+
+    if model == "ds2":
+        shapes, topk = load_workload(ds2_workload(8192, qconfig=ds2_mixed_qconfig()))["layer-1"], 6
+    else:
+        shapes, topk = load_workload(qwen2_layer11_workload(8192, qconfig=mixed_qconfig_lp1()))["layer-11"], 4
+    E = len(shapes["gate_up"]) - 1
+    H = shapes["gate_up"][0].K
+    N, Ns = shapes["down"][0].K, shapes["down"][-1].K
+    qcfg = [(QParams(a.a_bits, a.w_bits, a.gsize, a.sym), QParams(b.a_bits, b.w_bits, b.gsize, b.sym))
+            for a, b in zip(shapes["gate_up"], shapes["down"])]
+    dev = "cuda"
+    g = torch.Generator().manual_seed(0)
+    hist = torch.tensor([max(s.M, 1) for s in shapes["gate_up"][:E]], dtype=torch.float64)
+    mk = lambda n, k: ((torch.rand(n, k, generator=g) * 2 - 1) * 0.05).half().to(dev)
+    layer = MoEFFN([mk(2 * N, H) for _ in range(E)] + [mk(2 * Ns, H)], [mk(H, N) for _ in range(E)] + [mk(H, Ns)], qcfg,
+                   num_routed=E)
+
+    def one(bs: int) -> dict:
+        ids = torch.multinomial((hist / hist.sum()).expand(bs, E), topk, replacement=False, generator=g).to(torch.int32).to(dev)
+        hidden = ((torch.rand(bs, H, generator=g) * 2 - 1)).half().to(dev)
+        wts = torch.softmax(torch.rand(bs, topk, generator=g), dim=1).to(dev)
+
+        want = layer.forward(hidden, ids, wts)
+        pf = PlannedForward(layer, hidden, ids, wts)
+        gf = GraphForward(layer, bs, topk)
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            gf.launch(hidden, ids, wts)
+        side.synchronize()
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph, stream=side):
+            gf.launch(hidden, ids, wts)
+        torch.cuda.current_stream().wait_stream(side)
+        graph.replay()
+        pf()
+        torch.cuda.synchronize()
+        same = bool(torch.equal(gf.out.view(torch.int16), want.view(torch.int16)))
+        same_planned = bool(torch.equal(gf.out.view(torch.int16), pf.out.view(torch.int16)))
+
+        def wall(fn):
+            ts = []
+            for i in range(iters + 3):
+                t0 = time.perf_counter()
+                fn()
+                torch.cuda.synchronize()
+                if i >= 3:
+                    ts.append((time.perf_counter() - t0) * 1e6)
+            return sorted(ts)[len(ts) // 2]
+
+        def device(fn):
+            return time_launches(fn, 3, iters)["median_ms"] * 1e3
+
+        lib = nat.lib()
+        st = _stream(None)
+        sides = {
+            "eager_wall": lambda: wall(lambda: layer.forward(hidden, ids, wts)),
+            "planned_device": lambda: device(pf),
+            "graph_wall": lambda: wall(graph.replay),
+            "graph_device": lambda: device(graph.replay),
+            "planned_gate_up": lambda: device(pf.g1.launch),
+            "planned_down": lambda: device(pf.g2.launch),
+            "dynamic_gate_up": lambda: device(lambda: gf.g1.launch(gf.dyn[0])),
+            "dynamic_down": lambda: device(lambda: gf.g2.launch(gf.dyn[1])),
+            "capacity_gemm_gate_up": lambda: device(lambda: nat.check(lib.mxmoe_gg_launch(ctypes.byref(gf.g1.info), st))),
+            "capacity_gemm_down": lambda: device(lambda: nat.check(lib.mxmoe_gg_launch(ctypes.byref(gf.g2.info), st))),
+            "segments": lambda: device(lambda: nat.check(lib.mxmoe_moe_segments(
+                _ptr(gf.route_bufs[3]), E, bs, topk, 1, gf._tables, 2, _ptr(gf.seg_status), st))),
+        }
+        res = {k: [] for k in sides}
+        for _ in range(rounds):
+            for k, fn in sides.items():
+                res[k].append(fn())
+
+        def stat(v):
+            med = sorted(v)[len(v) // 2]
+            return {"median_us": round(med, 1), "min_us": round(min(v), 1), "max_us": round(max(v), 1),
+                    "spread": round((max(v) - min(v)) / med, 4)}
+
+        out = {"model": model, "bs": bs, "E": E, "topk": topk, "gate_up_mode": {"planned": pf.mode, "graph": gf.mode}}
+        out.update({k: stat(v) for k, v in res.items()})
+        names = [ln.split()[1] for ln in nat.list_variants()]
+        counts = gf.route_bufs[3].cpu().tolist() + [bs]
+        out["plans"] = {}
+        for name, dyn, host in (("gate_up", gf.g1, pf.g1), ("down", gf.g2, pf.g2)):
+            tiles = nat.dynamic_tiles(list(dyn._c_problems), dyn.variant, dyn.joint, dyn.rows_total,
+                                      [(c, 0, 0, 0) for c in counts])[0]
+            out["plans"][name] = {"graph_variant": names[dyn.variant], "planned_variant": names[host.variant],
+                                  "tile_slots": dyn.tile_slots, "tiles_used": int((tiles[:, 0] >= 0).sum()),
+                                  "planned_tiles": host.total_tiles, "planned_splitk_slabs": int(host.info.splitk_slabs)}
+        m = lambda k: out[k]["median_us"]
+        out["planner_kernel_us"] = {"gate_up": round(m("dynamic_gate_up") - m("capacity_gemm_gate_up"), 1),
+                                    "down": round(m("dynamic_down") - m("capacity_gemm_down"), 1)}
+        out["graph_wall_over_eager_wall"] = round(m("graph_wall") / m("eager_wall"), 4)
+        out["graph_device_over_planned_device"] = round(m("graph_device") / m("planned_device"), 4)
+        out["bit_identical_to_eager"], out["bit_identical_to_planned"] = same, same_planned
+        out["status"] = gf.status()
+        return out
+
+    for bs in batches:  # (a generator: a caller can print each size as it completes)
+        yield one(bs)
 
 
 GATE_MODELS = {"qwen2_moe": dict(H=2048, E=60, topk=4, shared_gate=True),
