@@ -131,6 +131,21 @@ int mxmoe_moe_gate_ex(const void* hidden, const void* w_gate, const void* w_shar
                       float routed_scale, int32_t* topk_ids, float* topk_weights, float* shared_w, float* logits,
                       float* scores, void* stream);
 
+/* mxmoe_moe_gate_ex with a bias on the logits (gpt-oss's router: F.linear(hidden, w, bias) -> top-k on the
+ * logits -> softmax over the chosen ones, i.e. scoring = MXMOE_GATE_SOFTMAX, renormalize = 1, logit_bias).
+ * Replaces: nothing in the reference (no router kernel); the semantics are GptOssTopKRouter's public code.
+ *   logit_bias f32 [E] or NULL (4-byte aligned): x[e] = acc[e] + logit_bias[e], one f32 add after the MFMA
+ *            reduction and before everything else. The `logits` output, the selection, the softmax / sigmoid
+ *            scores and the group stage all see the biased x. The shared-gate column gets no bias.
+ *   Every other argument, rule and limit: mxmoe_moe_gate_ex's. With logit_bias == NULL the call IS
+ *   mxmoe_moe_gate_ex (the same kernels), bit for bit; a non-NULL bias runs builds of their own, so
+ *   mxmoe_moe_gate's and mxmoe_moe_gate_ex's kernels are untouched by it.
+ * e_bias (sigmoid scoring's selection bias on the scores) and logit_bias are independent and may be combined. */
+int mxmoe_moe_gate_ex2(const void* hidden, const void* w_gate, const void* w_shared_gate, int64_t T, int H, int E, int topk,
+                       int renormalize, int scoring, const float* e_bias, int n_group, int topk_group, int group_top,
+                       float routed_scale, const float* logit_bias, int32_t* topk_ids, float* topk_weights, float* shared_w,
+                       float* logits, float* scores, void* stream);
+
 /* Stable counting sort of the T*topk expert ids (int32, row-major [T][topk], values in [0, E)):
  *   sorted_expert[s] = expert of slot s (non-decreasing), perm_token[s] = source token of slot s,
  *   inv_slot[t*topk + k] = slot of (token t, choice k), counts[e] = tokens routed to expert e.
@@ -221,6 +236,46 @@ int mxmoe_moe_quant_slots(const void* routed_in, const void* shared_in, int64_t 
 int mxmoe_moe_act_quant(int mode, const void* routed_in, const void* shared_in, int64_t T, int topk, int N, int N_shared,
                         const int32_t* sorted_expert, const int32_t* perm_token, const mxmoe_moe_seg* segs, int nseg,
                         uint32_t tag_mask, void* out, void* scales, void* stream);
+
+/* The activation pass of a layer whose gate_up projection has a bias and / or whose gated activation is not
+ * SiLU (gpt-oss): mxmoe_moe_silu_mul_quant's inputs, segments, outputs and limits (mode 1: [gate | up] columns),
+ * tag_mask as in mxmoe_moe_act_quant (every tag, MXFP4 and MXFP8 with their bits).
+ * Replaces: nothing in the reference; the clamped activation is GptOssExperts._apply_gate's public code.
+ * For slot s of expert e = sorted_expert[s] (the shared segment: bias_shared) and column n, all in f32:
+ *   g = f32(in[s][n]) + f32(bg[e][n]),  u = f32(in[s][N + n]) + f32(bu[e][n])   (one IEEE add each; a NULL bias:
+ *                                                                                no add), bias row = [bg | bu]
+ *   MXMOE_GLU_SILU:         a = g * rcp(1 + exp2(g * -log2 e)) * u              (mxmoe_moe_silu_mul_quant's expression)
+ *   MXMOE_GLU_SWIGLU_CLAMP: gc = min(g, limit), uc = min(max(u, -limit), limit), c = -(alpha * 1.4426950408889634f)
+ *                           (computed once on the host in f32), a = (gc * rcp(1 + exp2(gc * c))) * (uc + 1.0f)
+ *   act = fp16_rn(a), then quantised by the segment's tag as mxmoe_moe_quant_act does. NaN inputs: unspecified.
+ * With act = SILU and both biases NULL the outputs are mxmoe_moe_silu_mul_quant's byte for byte. A routed slot
+ * whose id is no routed expert's gets no bias (and, as everywhere, is never written).
+ * Limits: mxmoe_moe_silu_mul_quant's; bias pointers 16-byte aligned; SWIGLU_CLAMP: alpha finite, limit finite and
+ * > 0 (gpt-oss: 1.702, 7.0; both ignored by SILU). An unknown act, a bad limit or a misaligned bias:
+ * MXMOE_GG_ERR_INVALID; an unknown tag bit: MXMOE_GG_ERR_UNSUPPORTED (both checked before any HIP call). */
+enum { MXMOE_GLU_SILU = 0, MXMOE_GLU_SWIGLU_CLAMP = 1 };
+typedef struct mxmoe_moe_glu {
+  int32_t act;              /* MXMOE_GLU_*                                                 */
+  float alpha, limit;       /* SWIGLU_CLAMP only (gpt-oss: 1.702, 7.0); limit > 0, finite  */
+  const void* bias_routed;  /* fp16 [E][2N]  ([gate | up] columns, as routed_in) or NULL   */
+  const void* bias_shared;  /* fp16 [2 N_shared] or NULL                                   */
+} mxmoe_moe_glu;
+int mxmoe_moe_glu_quant(const mxmoe_moe_glu* glu, const void* routed_in, const void* shared_in, int64_t T, int topk, int N,
+                        int N_shared, const int32_t* sorted_expert, const mxmoe_moe_seg* segs, int nseg, uint32_t tag_mask,
+                        void* out, void* scales, void* stream);
+
+/* mxmoe_moe_combine for a down projection with a bias per expert: out[t][h] = fp16_rn(acc), acc = +0 then, for
+ * k = 0..topk-1 in order, slot = inv_slot[t*topk + k], e = sorted_expert[slot],
+ *   acc = fma(weights[t][k], f32(y[slot][h]) + f32(bias[e][h]), acc)      (the inner add: one IEEE f32 add),
+ * then, if shared != NULL, acc = fma(shared_w ? shared_w[t] : 1, f32(shared[t][h]) + f32(shared_bias[h]), acc).
+ * bias fp16 [E][H] or NULL, shared_bias fp16 [H] or NULL (NULL: no add; shared_bias needs shared); both 16-byte
+ * aligned. An e outside [0, E) adds no bias (stale slots of an invalid id in a graph forward): bias is never
+ * indexed with an unchecked id. sorted_expert: mxmoe_moe_route's (required with a bias). Other arguments and
+ * limits: mxmoe_moe_combine's, and E >= 1. With both biases NULL the output is mxmoe_moe_combine's bit for bit.
+ * (No reference counterpart: gg_unpermute_out is an empty stub.) */
+int mxmoe_moe_combine_bias(const void* y, const int32_t* inv_slot, const int32_t* sorted_expert, const float* weights,
+                           const void* bias, const void* shared, const float* shared_w, const void* shared_bias, int64_t T,
+                           int topk, int E, int H, void* out, void* stream);
 
 /* out[t][h] = fp16_rn(acc), acc = +0 then, for k = 0..topk-1 in order,
  *   acc = fma(weights[t][k], f32(y[inv_slot[t*topk + k]][h]), acc),

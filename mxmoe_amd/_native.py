@@ -99,7 +99,12 @@ EXPORTED_SYMBOLS = (
     "mxmoe_moe_route", "mxmoe_moe_quant_act", "mxmoe_moe_silu_mul_quant", "mxmoe_moe_silu_mul_quant_il", "mxmoe_moe_quant_slots", "mxmoe_moe_combine",
     "mxmoe_moe_act_quant",
     "mxmoe_moe_gate", "mxmoe_moe_gate_ex",
+    # gpt-oss layers: router logit bias, biased / clamped gated activation, combine with a down bias
+    "mxmoe_moe_gate_ex2", "mxmoe_moe_glu_quant", "mxmoe_moe_combine_bias",
 )
+# added to ABI 7 without a version bump (additive): a product library without them is a stale build
+GPTOSS_SYMBOLS = ("mxmoe_moe_gate_ex2", "mxmoe_moe_glu_quant", "mxmoe_moe_combine_bias")
+GLU_SILU, GLU_SWIGLU_CLAMP = 0, 1  # MXMOE_GLU_* (include/mxmoe_moe.h)
 
 
 class MoeSegC(ctypes.Structure):
@@ -127,6 +132,13 @@ class MoeSegTableC(ctypes.Structure):
 
     _fields_ = [("qtags", ctypes.c_void_p), ("width", ctypes.c_int32), ("width_shared", ctypes.c_int32),
                 ("ldc", ctypes.c_int64), ("segs", ctypes.c_void_p), ("dyn", ctypes.c_void_p)]
+
+
+class MoeGluC(ctypes.Structure):
+    """mxmoe_moe_glu (include/mxmoe_moe.h): the gated activation and the gate_up biases of mxmoe_moe_glu_quant."""
+
+    _fields_ = [("act", ctypes.c_int32), ("alpha", ctypes.c_float), ("limit", ctypes.c_float),
+                ("bias_routed", ctypes.c_void_p), ("bias_shared", ctypes.c_void_p)]
 
 
 # mxmoe_gg_dynamic_status bits (MXMOE_GG_DYN_*) and mxmoe_moe_segments' (MXMOE_MOE_SEG_COUNT_MISMATCH)
@@ -235,6 +247,15 @@ def _declare(lib: ctypes.CDLL) -> None:
                                           c.c_int, c.c_float, P, P, P, P, P, P]
     lib.mxmoe_moe_combine.restype = c.c_int
     lib.mxmoe_moe_combine.argtypes = [P, P, P, P, P, c.c_int64, c.c_int, c.c_int, P, P]
+    if all(hasattr(lib, fn) for fn in GPTOSS_SYMBOLS):  # (builds before the gpt-oss layers lack them: A/B tools)
+        lib.mxmoe_moe_gate_ex2.restype = c.c_int
+        lib.mxmoe_moe_gate_ex2.argtypes = [P, P, P, c.c_int64, c.c_int, c.c_int, c.c_int, c.c_int, c.c_int, P, c.c_int,
+                                           c.c_int, c.c_int, c.c_float, P, P, P, P, P, P, P]
+        lib.mxmoe_moe_glu_quant.restype = c.c_int
+        lib.mxmoe_moe_glu_quant.argtypes = [c.POINTER(MoeGluC), P, P, c.c_int64, c.c_int, c.c_int, c.c_int, P, P, c.c_int,
+                                            c.c_uint32, P, P, P]
+        lib.mxmoe_moe_combine_bias.restype = c.c_int
+        lib.mxmoe_moe_combine_bias.argtypes = [P, P, P, P, P, P, P, P, c.c_int64, c.c_int, c.c_int, c.c_int, P, P]
 
 
 def lib() -> ctypes.CDLL:
@@ -251,6 +272,7 @@ def lib() -> ctypes.CDLL:
         except OSError as e:  # pragma: no cover - environment dependent
             raise NativeLibraryError(f"failed to load {path}: {e}") from e
         _check_abi(handle, path)
+        _check_symbols(handle, path)
         _declare(handle)
         _lib = handle
         atexit.register(_release_shim)
@@ -272,6 +294,24 @@ def _check_abi(handle: ctypes.CDLL, path: Path) -> None:
         return
     raise NativeLibraryError(f"{path} has ABI version {got}, this binding needs {ABI_VERSION}: rebuild it with "
                              "`python -c 'import __graft_entry__ as g; g.build()'`")
+
+
+def _check_symbols(handle: ctypes.CDLL, path: Path) -> None:
+    """The entry points added to ABI 7 after its first release (GPTOSS_SYMBOLS) must be in the product library: one
+    built before them carries the right version number and would fail with an AttributeError at the first call. A
+    library named by MXMOE_GG_LIB may lack them (``symbol`` then refuses the call)."""
+    missing = [fn for fn in GPTOSS_SYMBOLS if not hasattr(handle, fn)]
+    if missing and "MXMOE_GG_LIB" not in os.environ:
+        raise NativeLibraryError(f"{path} lacks {', '.join(missing)}: a stale build, rebuild it with "
+                                 "`python -c 'import __graft_entry__ as g; g.build()'`")
+
+
+def symbol(name: str):
+    """An entry point of the loaded library, NativeLibraryError (not AttributeError) where the build lacks it."""
+    handle = lib()
+    if not hasattr(handle, name):
+        raise NativeLibraryError(f"the loaded library exports no {name}: it was built before that entry point")
+    return getattr(handle, name)
 
 
 def _release_shim() -> None:

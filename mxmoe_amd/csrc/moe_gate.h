@@ -70,6 +70,15 @@ struct GateModeArgs {
   float routed_scale;
 };
 
+// mxmoe_moe_gate_ex2: a bias on the logits themselves (gpt-oss: F.linear(hidden, w, bias)), added once after
+// the split-K reduction; everything after it (the logits output, selection, scoring, groups) sees the sum
+struct GateBiasArgs {
+  GateModeArgs m;
+  const float* logit_bias;  // [E]
+};
+inline const GateArgs& gate_args_of(const GateModeArgs& m) { return m.g; }
+inline const GateArgs& gate_args_of(const GateBiasArgs& b) { return b.m.g; }
+
 // what a kernel is compiled for: mxmoe_moe_gate's rule (gate_kernel, which gets no GateModeArgs), or
 // mxmoe_moe_gate_ex's with softmax / sigmoid scoring (gate_modes_kernel)
 enum GateMode { kGatePlain = 0, kGateSoftmaxEx = 1, kGateSigmoidEx = 2 };
@@ -196,6 +205,8 @@ template <int NB, int MR, int NW, int U>
 __global__ __launch_bounds__(64 * NW) void gate_kernel(GateArgs a) {
   constexpr int MODE = kGatePlain;
   const GateModeArgs* const ex = nullptr;
+  constexpr bool LB = false;
+  const float* const lbias = nullptr;
 #include "moe_gate_body.inc"
 }
 template <int NB, int MR, int NW, int U, int MODE>
@@ -203,6 +214,19 @@ __global__ __launch_bounds__(64 * NW) void gate_modes_kernel(GateModeArgs mm) {
   static_assert(MODE == kGateSoftmaxEx || MODE == kGateSigmoidEx, "an mxmoe_moe_gate_ex mode");
   const GateArgs& a = mm.g;
   const GateModeArgs* const ex = &mm;
+  constexpr bool LB = false;
+  const float* const lbias = nullptr;
+#include "moe_gate_body.inc"
+}
+// gate_modes_kernel with the logit bias (mxmoe_moe_gate_ex2 with a non-NULL logit_bias): builds of their own, so
+// the two kernels above keep their code and registers
+template <int NB, int MR, int NW, int U, int MODE>
+__global__ __launch_bounds__(64 * NW) void gate_bias_kernel(GateBiasArgs bb) {
+  static_assert(MODE == kGateSoftmaxEx || MODE == kGateSigmoidEx, "an mxmoe_moe_gate_ex mode");
+  const GateArgs& a = bb.m.g;
+  const GateModeArgs* const ex = &bb.m;
+  constexpr bool LB = true;
+  const float* const lbias = bb.logit_bias;
 #include "moe_gate_body.inc"
 }
 
@@ -278,13 +302,19 @@ inline void gate_modes_launch_one(const GateModeArgs& m, bool sigmoid, hipStream
   if (sigmoid) hipLaunchKernelGGL((gate_modes_kernel<NB, MR, NW, U, kGateSigmoidEx>), blocks, threads, 0, st, m);
   else hipLaunchKernelGGL((gate_modes_kernel<NB, MR, NW, U, kGateSoftmaxEx>), blocks, threads, 0, st, m);
 }
+template <int NB, int MR, int NW, int U>
+inline void gate_modes_launch_one(const GateBiasArgs& b, bool sigmoid, hipStream_t st) {
+  const dim3 blocks((unsigned)((b.m.g.T + 16 * MR - 1) / (16 * MR))), threads(64 * NW);
+  if (sigmoid) hipLaunchKernelGGL((gate_bias_kernel<NB, MR, NW, U, kGateSigmoidEx>), blocks, threads, 0, st, b);
+  else hipLaunchKernelGGL((gate_bias_kernel<NB, MR, NW, U, kGateSoftmaxEx>), blocks, threads, 0, st, b);
+}
 // (16 blocks would fit 8 waves - 64 KiB of partial sums, 241 VGPRs - and ran no faster than 4 at
 // H = 7168: DESIGN.md §4 "Router: the other routing rules")
-template <int NB>
-inline void gate_modes_launch_nb(const GateModeArgs& m, bool sigmoid, hipStream_t st) {
+template <int NB, class ARGS>
+inline void gate_modes_launch_nb(const ARGS& m, bool sigmoid, hipStream_t st) {
   constexpr int NW = NB <= 12 ? MXMOE_GATE_NW : 4;
   constexpr int MAXMR = NB <= 4 ? 4 : NB <= 8 ? 2 : 1;
-  const int mr = gate_rows_per_wg(m.g.T, MAXMR);
+  const int mr = gate_rows_per_wg(gate_args_of(m).T, MAXMR);
   if constexpr (MAXMR >= 4) {
     if (mr == 4) return gate_modes_launch_one<NB, 4, NW, gate_group_steps(NB, 4)>(m, sigmoid, st);
   }
@@ -293,9 +323,10 @@ inline void gate_modes_launch_nb(const GateModeArgs& m, bool sigmoid, hipStream_
   }
   gate_modes_launch_one<NB, 1, NW, gate_group_steps(NB, 1)>(m, sigmoid, st);
 }
-// one launch; the caller has validated the arguments (T > 0)
-inline void gate_modes_launch(const GateModeArgs& m, bool sigmoid, hipStream_t st) {
-  const int nb = (m.g.E + (m.g.w_shared ? 1 : 0) + 15) / 16;
+// one launch; the caller has validated the arguments (T > 0). ARGS: GateModeArgs, or GateBiasArgs (gate_bias_kernel)
+template <class ARGS>
+inline void gate_modes_launch(const ARGS& m, bool sigmoid, hipStream_t st) {
+  const int nb = (gate_args_of(m).E + (gate_args_of(m).w_shared ? 1 : 0) + 15) / 16;
   if (nb <= 1) gate_modes_launch_nb<1>(m, sigmoid, st);
   else if (nb <= 2) gate_modes_launch_nb<2>(m, sigmoid, st);
   else if (nb <= 4) gate_modes_launch_nb<4>(m, sigmoid, st);

@@ -1,6 +1,7 @@
 // moe_gate_body.inc — the body of gate_kernel and gate_modes_kernel (moe_gate.h, which says why it is
 // shared as text). In scope: NB, MR, NW, U, MODE (GateMode), `a` (GateArgs) and `ex` (const
-// GateModeArgs*, NULL for kGatePlain).
+// GateModeArgs*, NULL for kGatePlain), LB (constexpr bool: the build adds a logit bias) and `lbias` (const float*,
+// [E]; read only when LB).
   constexpr int kSlots = NW == 8 ? 4 : 3;  // partial-sum tiles in LDS at a time, per (token block, column block)
   static_assert(NW == 4 || NW == 8, "4 or 8 waves");
   static_assert(MR >= 1 && MR <= 4 && MR * kSlots * NB * 1024 <= 64 * 1024, "partial sums must fit 64 KiB of LDS");
@@ -118,6 +119,15 @@
       if (i == wave) x[j] = acc[i][j];
 #pragma unroll
     for (int sl = 0; sl < 3; ++sl) x[j] += red[((wave * 3 + sl) * NB + j) * 64 + lane];
+    if constexpr (LB) {  // x[e] += logit_bias[e], e < E: one add, before everything that reads x (not the shared column)
+      // (branch-free: a column past E reads the last bias and adds nothing)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int e = 16 * j + 4 * (lane >> 4) + r;
+        const float b = lbias[e < E ? e : E - 1];
+        x[j][r] = e < E ? x[j][r] + b : x[j][r];
+      }
+    }
   }
 
   // this lane: token t, experts 16 j + 4 g + r

@@ -12,6 +12,9 @@
 // All four kernels are HBM-bound byte movers: one workgroup per row (token or slot), 16-B
 // coalesced loads of 8 fp16 per lane, reductions in registers / lane shuffles, stores of the packed
 // codes as one 4-B (int4) / 8-B (int8) / 16-B (fp16) word per lane — no LDS tiling, no MFMA.
+// gpt-oss layers: the activation pass also comes with a bias row per expert and the clamped SwiGLU
+// (mxmoe_moe_glu_quant: the GLU builds of act_quant_kernel), the combine with a bias row per expert
+// (mxmoe_moe_combine_bias), the router with a bias on its logits (mxmoe_moe_gate_ex2); no reference counterpart.
 // The router in front of them (mxmoe_moe_gate: logits on the MFMA, top-k, softmax; mxmoe_moe_gate_ex:
 // sigmoid scores, selection bias, group-limited top-k) is moe_gate.h.
 #include <hip/hip_runtime.h>
@@ -155,6 +158,16 @@ struct ActArgs {
   int64_t blk_shared;          // parts > 1: first workgroup of the shared rows (one row per workgroup)
   int parts;                   // 1, or 4: a shared row is split over the 4 waves of its workgroup
 };
+// mxmoe_moe_glu_quant (GLU builds of act_quant_kernel): the biases of the gate_up output and the gated activation
+struct GluArgs : ActArgs {
+  const _Float16* bias_routed;  // [nexp][2N] ([gate | up] columns) or NULL
+  const _Float16* bias_shared;  // [2Ns] or NULL
+  int nexp;                     // routed experts (rows of bias_routed)
+  float c, limit;               // SWIGLU_CLAMP: -(alpha log2 e), the clamp
+};
+enum { kGluNone = 0, kGluSilu = 1, kGluSwigluClamp = 2 };
+template <int GLU> struct ActArgsOf { typedef GluArgs type; };
+template <> struct ActArgsOf<kGluNone> { typedef ActArgs type; };
 
 // quant_weight arithmetic (quantize.cuh:218-279): scale = fp16(amax / qmax), 0 -> 1;
 // q = rint_even(clamp(fp16(x / scale), -qmax, qmax))
@@ -230,9 +243,13 @@ __device__ __forceinline__ float amax8(const h8_t& x) {
 // the fused epilogue, run through the plain epilogue: small-batch calls on wo3)
 // MX: the build that also carries the MXMOE_ACT_MXFP4 and MXMOE_ACT_MXFP8 tags (launched only for calls whose segments hold
 // one, mxmoe_moe_act_quant: the other tags' builds stay as they are without it)
-template <int MODE, int MAXC, bool MX = false>
-__global__ __launch_bounds__(kThreads) void act_quant_kernel(ActArgs a) {
+// GLU (MODE 1 only; mxmoe_moe_glu_quant): kGluSilu / kGluSwigluClamp builds take GluArgs, add the expert's bias
+// row to the gate and up values as they are read (one f32 add each; a NULL bias: no add) and apply the named
+// gated activation. kGluNone: none of that code exists and the builds are the ones above.
+template <int MODE, int MAXC, bool MX = false, int GLU = kGluNone>
+__global__ __launch_bounds__(kThreads) void act_quant_kernel(typename ActArgsOf<GLU>::type a) {
   constexpr bool SILU = MODE == 1 || MODE == 3;
+  static_assert(GLU == kGluNone || MODE == 1, "the GLU builds read [gate | up] columns");
   __shared__ float wave_amax[kThreads / 64];
   const int lane = threadIdx.x & 63;
   const bool split_row = a.parts > 1 && (int64_t)blockIdx.x >= a.blk_shared;  // workgroup-uniform
@@ -284,7 +301,46 @@ __global__ __launch_bounds__(kThreads) void act_quant_kernel(ActArgs a) {
       u[c] = __builtin_bit_cast(h8_t, in ? uv : z);
     }
   }
-  if constexpr (SILU) {
+  if constexpr (GLU != kGluNone) {
+    // the bias row of this slot's expert ([gate | up], the input row's layout; split rows: from col0), loaded
+    // like the row itself; a routed id that is no routed expert's (inconsistent table) gets no bias
+    const _Float16* brow = s >= a.ntk ? a.bias_shared
+                           : (a.bias_routed && e < a.nexp) ? a.bias_routed + (int64_t)e * 2 * a.N : nullptr;
+    const bool has_b = brow != nullptr;  // wave-uniform
+    const _Float16* const bbase = has_b ? (width > 0 ? brow + col0 : brow) : row_src;  // (always a valid address)
+    h8_t bg[MAXC], bu[MAXC];
+#pragma unroll
+    for (int c = 0; c < MAXC; ++c) {
+      const int idx = c * 512 + lane * 8;
+      const bool in = has_b && idx < width;
+      const int li = in ? idx : 0;
+      const uint4 gv = *reinterpret_cast<const uint4*>(bbase + li);
+      const uint4 uv = *reinterpret_cast<const uint4*>(bbase + (has_b ? upoff : 0) + li);
+      const uint4 z = {0, 0, 0, 0};
+      bg[c] = __builtin_bit_cast(h8_t, in ? gv : z);
+      bu[c] = __builtin_bit_cast(h8_t, in ? uv : z);
+    }
+#pragma unroll
+    for (int c = 0; c < MAXC; ++c) {  // (zeros past the row: both activations give 0 * ... = 0)
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        float g = (float)x[c][j], v = (float)u[c][j];
+        if (has_b) {
+          g = g + (float)bg[c][j];
+          v = v + (float)bu[c][j];
+        }
+        if constexpr (GLU == kGluSilu) {  // the SiLU pass's own expression
+          const float sg = g * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(g * -1.4426950408889634f));
+          x[c][j] = (_Float16)(sg * v);
+        } else {  // (u + 1) * g * sigmoid(alpha g) on g clamped from above, u from both sides
+          const float gc = fminf(g, a.limit);
+          const float uc = fminf(fmaxf(v, -a.limit), a.limit);
+          const float sg = gc * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(gc * a.c));
+          x[c][j] = (_Float16)(sg * (uc + 1.0f));
+        }
+      }
+    }
+  } else if constexpr (SILU) {
 #pragma unroll
     for (int c = 0; c < MAXC; ++c) {  // (zeros past the row: silu(0) * 0 = 0)
 #pragma unroll
@@ -480,6 +536,52 @@ __global__ __launch_bounds__(kThreads) void combine_kernel(const _Float16* __res
   }
 }
 
+// combine with a bias row per expert on the down output (mxmoe_moe_combine_bias): the term of choice k is
+// f32(y) + f32(bias[e]) (one add), e = sorted[slot] — an id outside [0, E) (a stale slot) adds nothing — and the
+// shared term f32(shared) + f32(shared_bias)
+__global__ __launch_bounds__(kThreads) void combine_bias_kernel(const _Float16* __restrict__ y, const int32_t* __restrict__ inv,
+                                                                const int32_t* __restrict__ sorted, const float* __restrict__ w,
+                                                                const _Float16* __restrict__ bias,
+                                                                const _Float16* __restrict__ shared,
+                                                                const float* __restrict__ shared_w,
+                                                                const _Float16* __restrict__ shared_bias, int topk, int E, int H,
+                                                                _Float16* __restrict__ out) {
+  const int64_t t = blockIdx.x;
+  for (int idx = threadIdx.x * 8; idx < H; idx += kChunk) {
+    float acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    for (int k = 0; k < topk; ++k) {
+      const int64_t slot = inv[t * topk + k];
+      const float wk = w[t * topk + k];
+      const h8_t v = *reinterpret_cast<const h8_t*>(y + slot * H + idx);
+      const int e = bias ? sorted[slot] : -1;
+      if (e >= 0 && e < E) {  // workgroup-uniform
+        const h8_t b = *reinterpret_cast<const h8_t*>(bias + (int64_t)e * H + idx);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) acc[j] = fmaf(wk, (float)v[j] + (float)b[j], acc[j]);
+      } else {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) acc[j] = fmaf(wk, (float)v[j], acc[j]);
+      }
+    }
+    if (shared) {
+      const float ws = shared_w ? shared_w[t] : 1.0f;
+      const h8_t v = *reinterpret_cast<const h8_t*>(shared + t * H + idx);
+      if (shared_bias) {
+        const h8_t b = *reinterpret_cast<const h8_t*>(shared_bias + idx);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) acc[j] = fmaf(ws, (float)v[j] + (float)b[j], acc[j]);
+      } else {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) acc[j] = fmaf(ws, (float)v[j], acc[j]);
+      }
+    }
+    h8_t r;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) r[j] = (_Float16)acc[j];
+    *reinterpret_cast<h8_t*>(out + t * H + idx) = r;
+  }
+}
+
 bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 // ---------------------------------------------------------------------------------------------
@@ -567,39 +669,50 @@ int segments_check(const int32_t* counts, int E, int64_t T, int topk, const mxmo
 using namespace mxmoe;
 
 // registers sized to the widest row of the launch, in 512-element chunks (1408 -> 3, 2048 -> 4)
-template <int MODE, bool MX>
-static void launch_act_w(const ActArgs& a, int maxw, hipStream_t st) {
+template <int MODE, bool MX, int GLU = kGluNone>
+static void launch_act_w(const typename ActArgsOf<GLU>::type& a, int maxw, hipStream_t st) {
   const int64_t blocks = a.parts > 1 ? a.blk_shared + (a.nslots - a.ntk)
                                      : (a.nslots - a.s0 + kThreads / 64 - 1) / (kThreads / 64);
   const dim3 grid((unsigned)blocks), block(kThreads);
   const int nc = (maxw + 511) / 512;
-  if (nc <= 1) hipLaunchKernelGGL((act_quant_kernel<MODE, 1, MX>), grid, block, 0, st, a);
-  else if (nc <= 2) hipLaunchKernelGGL((act_quant_kernel<MODE, 2, MX>), grid, block, 0, st, a);
-  else if (nc <= 3) hipLaunchKernelGGL((act_quant_kernel<MODE, 3, MX>), grid, block, 0, st, a);
-  else if (nc <= 4) hipLaunchKernelGGL((act_quant_kernel<MODE, 4, MX>), grid, block, 0, st, a);
-  else if (nc <= 6) hipLaunchKernelGGL((act_quant_kernel<MODE, 6, MX>), grid, block, 0, st, a);
-  else if (nc <= 8) hipLaunchKernelGGL((act_quant_kernel<MODE, 8, MX>), grid, block, 0, st, a);
-  else if (nc <= 12) hipLaunchKernelGGL((act_quant_kernel<MODE, 12, MX>), grid, block, 0, st, a);
-  else if (nc <= 16) hipLaunchKernelGGL((act_quant_kernel<MODE, 16, MX>), grid, block, 0, st, a);
-  else hipLaunchKernelGGL((act_quant_kernel<MODE, 32, MX>), grid, block, 0, st, a);
+  if (nc <= 1) hipLaunchKernelGGL((act_quant_kernel<MODE, 1, MX, GLU>), grid, block, 0, st, a);
+  else if (nc <= 2) hipLaunchKernelGGL((act_quant_kernel<MODE, 2, MX, GLU>), grid, block, 0, st, a);
+  else if (nc <= 3) hipLaunchKernelGGL((act_quant_kernel<MODE, 3, MX, GLU>), grid, block, 0, st, a);
+  else if (nc <= 4) hipLaunchKernelGGL((act_quant_kernel<MODE, 4, MX, GLU>), grid, block, 0, st, a);
+  else if (nc <= 6) hipLaunchKernelGGL((act_quant_kernel<MODE, 6, MX, GLU>), grid, block, 0, st, a);
+  else if (nc <= 8) hipLaunchKernelGGL((act_quant_kernel<MODE, 8, MX, GLU>), grid, block, 0, st, a);
+  else if (nc <= 12) hipLaunchKernelGGL((act_quant_kernel<MODE, 12, MX, GLU>), grid, block, 0, st, a);
+  else if (nc <= 16) hipLaunchKernelGGL((act_quant_kernel<MODE, 16, MX, GLU>), grid, block, 0, st, a);
+  else hipLaunchKernelGGL((act_quant_kernel<MODE, 32, MX, GLU>), grid, block, 0, st, a);
 }
 
-// slots [0, nslots): one launch; rows of different widths (routed [0, ntk), shared [ntk, nslots)):
-// one launch with each shared row split over a workgroup's 4 waves when a quarter of the shared row
-// fits the routed rows' register width, else two launches, each with the register row of its width
 template <int MODE>
 static void launch_act_m(const ActArgs& a, int maxw, bool mx, hipStream_t st) {
   if (mx) launch_act_w<MODE, true>(a, maxw, st);
   else launch_act_w<MODE, false>(a, maxw, st);
 }
+// (mode, mx): which build of the kernel; ActArgs: the four passes, GluArgs: mxmoe_moe_glu_quant's (mode = MXMOE_GLU_*)
 static void launch_act_any(int mode, const ActArgs& a, int maxw, bool mx, hipStream_t st) {
   if (mode == 1) launch_act_m<1>(a, maxw, mx, st);
   else if (mode == 2) launch_act_m<2>(a, maxw, mx, st);
   else if (mode == 3) launch_act_m<3>(a, maxw, mx, st);
   else launch_act_m<0>(a, maxw, mx, st);
 }
+static void launch_act_any(int act, const GluArgs& a, int maxw, bool mx, hipStream_t st) {
+  if (act == MXMOE_GLU_SWIGLU_CLAMP) {
+    if (mx) launch_act_w<1, true, kGluSwigluClamp>(a, maxw, st);
+    else launch_act_w<1, false, kGluSwigluClamp>(a, maxw, st);
+  } else {
+    if (mx) launch_act_w<1, true, kGluSilu>(a, maxw, st);
+    else launch_act_w<1, false, kGluSilu>(a, maxw, st);
+  }
+}
+// slots [0, nslots): one launch; rows of different widths (routed [0, ntk), shared [ntk, nslots)):
+// one launch with each shared row split over a workgroup's 4 waves when a quarter of the shared row
+// fits the routed rows' register width, else two launches, each with the register row of its width
 // mx: a segment of the call carries MXMOE_ACT_MXFP4 or MXMOE_ACT_MXFP8 (the MX builds of the kernel)
-static int launch_act(int mode, ActArgs a, int64_t nslots, int w_routed, int w_shared, void* stream, bool mx = false) {
+template <class ARGS>
+static int launch_act(int mode, ARGS a, int64_t nslots, int w_routed, int w_shared, void* stream, bool mx = false) {
   if (nslots == 0) return MXMOE_GG_OK;
   a.parts = 1;
   a.blk_shared = 0;
@@ -641,9 +754,8 @@ static int quant_act_impl(const char* fn, const void* hidden, int64_t T, int K, 
                   sorted_expert, perm_token, segs, nseg, static_cast<uint8_t*>(out), static_cast<_Float16*>(scales)};
   return launch_act(0, a, T * topk + (with_shared ? T : 0), K, K, stream, mx);
 }
-static int slots_impl(const char* fn, int mode, const void* routed_in, const void* shared_in, int64_t T, int topk, int N,
-                      int N_shared, const int32_t* sorted_expert, const mxmoe_moe_seg* segs, int nseg, void* out,
-                      void* scales, void* stream, bool mx) {
+static int slots_check(const char* fn, const void* routed_in, const void* shared_in, int64_t T, int topk, int N,
+                       int N_shared, const int32_t* sorted_expert, const mxmoe_moe_seg* segs, int nseg, void* out) {
   if (T < 0 || topk <= 0 || nseg <= 0 || N <= 0 || N % 128 || N > kMaxWidth ||
       (shared_in && (N_shared <= 0 || N_shared % 128 || N_shared > kMaxWidth)))
     return fail(MXMOE_GG_ERR_INVALID, "%s: widths must be multiples of 128 and <= %d (N=%d, N_shared=%d)", fn, kMaxWidth,
@@ -651,6 +763,12 @@ static int slots_impl(const char* fn, int mode, const void* routed_in, const voi
   if (T > 0 && (!routed_in || !sorted_expert || !segs || !out || !aligned16(routed_in) || !aligned16(out) ||
                 (shared_in && !aligned16(shared_in))))
     return fail(MXMOE_GG_ERR_INVALID, "%s: NULL or misaligned pointer (16 B)", fn);
+  return MXMOE_GG_OK;
+}
+static int slots_impl(const char* fn, int mode, const void* routed_in, const void* shared_in, int64_t T, int topk, int N,
+                      int N_shared, const int32_t* sorted_expert, const mxmoe_moe_seg* segs, int nseg, void* out,
+                      void* scales, void* stream, bool mx) {
+  if (int st = slots_check(fn, routed_in, shared_in, T, topk, N, N_shared, sorted_expert, segs, nseg, out)) return st;
   const ActArgs a{static_cast<const _Float16*>(routed_in), static_cast<const _Float16*>(shared_in), T * topk, 0, 0, 0,
                   N, N_shared, sorted_expert, nullptr, segs, nseg, static_cast<uint8_t*>(out),
                   static_cast<_Float16*>(scales)};
@@ -669,6 +787,38 @@ static int gate_check(const char* fn, const void* hidden, const void* w_gate, co
   if (!aligned16(hidden) || !aligned16(w_gate) || !aligned16(w_shared_gate))
     return fail(MXMOE_GG_ERR_INVALID, "%s: misaligned pointer (hidden / w_gate / w_shared_gate need 16 B)", fn);
   if (T > 0 && (!hidden || !w_gate || !topk_ids || !topk_weights)) return fail(MXMOE_GG_ERR_INVALID, "%s: NULL pointer", fn);
+  return MXMOE_GG_OK;
+}
+
+static int gate_ex_impl(const char* fn, const void* hidden, const void* w_gate, const void* w_shared_gate, int64_t T, int H,
+                        int E, int topk, int renormalize, int scoring, const float* e_bias, int n_group, int topk_group,
+                        int group_top, float routed_scale, const float* logit_bias, int32_t* topk_ids, float* topk_weights,
+                        float* shared_w, float* logits, float* scores, void* stream) {
+  if (scoring != MXMOE_GATE_SOFTMAX && scoring != MXMOE_GATE_SIGMOID)
+    return fail(MXMOE_GG_ERR_INVALID, "%s: scoring must be MXMOE_GATE_SOFTMAX or MXMOE_GATE_SIGMOID (got %d)", fn, scoring);
+  const int st = gate_check(fn, hidden, w_gate, w_shared_gate, T, H, E, topk, topk_ids, topk_weights, shared_w);
+  if (st != MXMOE_GG_OK) return st;
+  if (n_group < 1 || n_group > 8 || E % n_group || (E / n_group) % 4 || topk_group < 1 || topk_group > n_group ||
+      (int64_t)topk > (int64_t)topk_group * (E / n_group))
+    return fail(MXMOE_GG_ERR_INVALID, "%s: need 1 <= n_group <= 8, E %% n_group == 0, (E / n_group) %% 4 == 0, "
+                "1 <= topk_group <= n_group (1 without groups), topk <= topk_group * E / n_group "
+                "(E=%d topk=%d n_group=%d topk_group=%d)", fn, E, topk, n_group, topk_group);
+  if (group_top < 1 || group_top > 2 || group_top > E / n_group)
+    return fail(MXMOE_GG_ERR_INVALID, "%s: group_top must be 1 or 2 and at most E / n_group (got %d)", fn, group_top);
+  if (scoring == MXMOE_GATE_SOFTMAX && (e_bias || scores || group_top != 1))
+    return fail(MXMOE_GG_ERR_INVALID, "%s: softmax scoring takes no e_bias, no scores output and group_top == 1", fn);
+  if (!std::isfinite(routed_scale)) return fail(MXMOE_GG_ERR_INVALID, "%s: routed_scale must be finite", fn);
+  if (((uintptr_t)e_bias | (uintptr_t)scores | (uintptr_t)logit_bias) & 3)
+    return fail(MXMOE_GG_ERR_INVALID, "%s: misaligned pointer (e_bias / scores / logit_bias need 4 B)", fn);
+  if (T == 0) return MXMOE_GG_OK;
+  const gate::GateModeArgs m{{static_cast<const _Float16*>(hidden), static_cast<const _Float16*>(w_gate),
+                              static_cast<const _Float16*>(w_shared_gate), T, H, E, topk, renormalize != 0, topk_ids,
+                              topk_weights, shared_w, logits},
+                             e_bias, scores, n_group, topk_group, group_top, routed_scale};
+  if (logit_bias) gate::gate_modes_launch(gate::GateBiasArgs{m, logit_bias}, scoring == MXMOE_GATE_SIGMOID, (hipStream_t)stream);
+  else gate::gate_modes_launch(m, scoring == MXMOE_GATE_SIGMOID, (hipStream_t)stream);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(MXMOE_GG_ERR_HIP, "gate_modes_kernel launch failed: %s", hipGetErrorString(e));
   return MXMOE_GG_OK;
 }
 
@@ -692,32 +842,17 @@ int mxmoe_moe_gate_ex(const void* hidden, const void* w_gate, const void* w_shar
                       int renormalize, int scoring, const float* e_bias, int n_group, int topk_group, int group_top,
                       float routed_scale, int32_t* topk_ids, float* topk_weights, float* shared_w, float* logits,
                       float* scores, void* stream) {
-  const char* fn = "mxmoe_moe_gate_ex";
-  if (scoring != MXMOE_GATE_SOFTMAX && scoring != MXMOE_GATE_SIGMOID)
-    return fail(MXMOE_GG_ERR_INVALID, "%s: scoring must be MXMOE_GATE_SOFTMAX or MXMOE_GATE_SIGMOID (got %d)", fn, scoring);
-  const int st = gate_check(fn, hidden, w_gate, w_shared_gate, T, H, E, topk, topk_ids, topk_weights, shared_w);
-  if (st != MXMOE_GG_OK) return st;
-  if (n_group < 1 || n_group > 8 || E % n_group || (E / n_group) % 4 || topk_group < 1 || topk_group > n_group ||
-      (int64_t)topk > (int64_t)topk_group * (E / n_group))
-    return fail(MXMOE_GG_ERR_INVALID, "%s: need 1 <= n_group <= 8, E %% n_group == 0, (E / n_group) %% 4 == 0, "
-                "1 <= topk_group <= n_group (1 without groups), topk <= topk_group * E / n_group "
-                "(E=%d topk=%d n_group=%d topk_group=%d)", fn, E, topk, n_group, topk_group);
-  if (group_top < 1 || group_top > 2 || group_top > E / n_group)
-    return fail(MXMOE_GG_ERR_INVALID, "%s: group_top must be 1 or 2 and at most E / n_group (got %d)", fn, group_top);
-  if (scoring == MXMOE_GATE_SOFTMAX && (e_bias || scores || group_top != 1))
-    return fail(MXMOE_GG_ERR_INVALID, "%s: softmax scoring takes no e_bias, no scores output and group_top == 1", fn);
-  if (!std::isfinite(routed_scale)) return fail(MXMOE_GG_ERR_INVALID, "%s: routed_scale must be finite", fn);
-  if (((uintptr_t)e_bias | (uintptr_t)scores) & 3)
-    return fail(MXMOE_GG_ERR_INVALID, "%s: misaligned pointer (e_bias / scores need 4 B)", fn);
-  if (T == 0) return MXMOE_GG_OK;
-  const gate::GateModeArgs m{{static_cast<const _Float16*>(hidden), static_cast<const _Float16*>(w_gate),
-                              static_cast<const _Float16*>(w_shared_gate), T, H, E, topk, renormalize != 0, topk_ids,
-                              topk_weights, shared_w, logits},
-                             e_bias, scores, n_group, topk_group, group_top, routed_scale};
-  gate::gate_modes_launch(m, scoring == MXMOE_GATE_SIGMOID, (hipStream_t)stream);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(MXMOE_GG_ERR_HIP, "gate_modes_kernel launch failed: %s", hipGetErrorString(e));
-  return MXMOE_GG_OK;
+  return gate_ex_impl("mxmoe_moe_gate_ex", hidden, w_gate, w_shared_gate, T, H, E, topk, renormalize, scoring, e_bias, n_group,
+                      topk_group, group_top, routed_scale, nullptr, topk_ids, topk_weights, shared_w, logits, scores, stream);
+}
+
+int mxmoe_moe_gate_ex2(const void* hidden, const void* w_gate, const void* w_shared_gate, int64_t T, int H, int E, int topk,
+                       int renormalize, int scoring, const float* e_bias, int n_group, int topk_group, int group_top,
+                       float routed_scale, const float* logit_bias, int32_t* topk_ids, float* topk_weights, float* shared_w,
+                       float* logits, float* scores, void* stream) {
+  return gate_ex_impl("mxmoe_moe_gate_ex2", hidden, w_gate, w_shared_gate, T, H, E, topk, renormalize, scoring, e_bias,
+                      n_group, topk_group, group_top, routed_scale, logit_bias, topk_ids, topk_weights, shared_w, logits,
+                      scores, stream);
 }
 
 int mxmoe_moe_route(const int32_t* topk_ids, int64_t T, int topk, int E, int32_t* sorted_expert,
@@ -799,6 +934,54 @@ int mxmoe_moe_act_quant(int mode, const void* routed_in, const void* shared_in, 
                           segs, nseg, out, scales, stream, mx);
   return slots_impl("mxmoe_moe_act_quant", mode, routed_in, shared_in, T, topk, N, N_shared, sorted_expert, segs, nseg, out,
                     scales, stream, mx);
+}
+
+int mxmoe_moe_glu_quant(const mxmoe_moe_glu* glu, const void* routed_in, const void* shared_in, int64_t T, int topk, int N,
+                        int N_shared, const int32_t* sorted_expert, const mxmoe_moe_seg* segs, int nseg, uint32_t tag_mask,
+                        void* out, void* scales, void* stream) {
+  const char* fn = "mxmoe_moe_glu_quant";
+  if (!glu || (glu->act != MXMOE_GLU_SILU && glu->act != MXMOE_GLU_SWIGLU_CLAMP))
+    return fail(MXMOE_GG_ERR_INVALID, "%s: glu->act must be MXMOE_GLU_SILU or MXMOE_GLU_SWIGLU_CLAMP (got %d)", fn,
+                glu ? glu->act : -1);
+  if (glu->act == MXMOE_GLU_SWIGLU_CLAMP && (!std::isfinite(glu->alpha) || !std::isfinite(glu->limit) || !(glu->limit > 0.0f)))
+    return fail(MXMOE_GG_ERR_INVALID, "%s: SWIGLU_CLAMP needs a finite alpha and a finite limit > 0 (alpha=%g limit=%g)", fn,
+                (double)glu->alpha, (double)glu->limit);
+  if (!aligned16(glu->bias_routed) || !aligned16(glu->bias_shared))
+    return fail(MXMOE_GG_ERR_INVALID, "%s: misaligned bias pointer (16 B)", fn);
+  if (tag_mask & ~((2u << MXMOE_ACT_MXFP4) - 1u | 1u << MXMOE_ACT_MXFP8))  // (tag 5 is not assigned)
+    return fail(MXMOE_GG_ERR_UNSUPPORTED, "%s: unknown activation tag in mask %#x", fn, tag_mask);
+  if (int st = slots_check(fn, routed_in, shared_in, T, topk, N, N_shared, sorted_expert, segs, nseg, out)) return st;
+  const bool mx = ((tag_mask >> MXMOE_ACT_MXFP4) & 1) || ((tag_mask >> MXMOE_ACT_MXFP8) & 1);
+  GluArgs a{};
+  static_cast<ActArgs&>(a) = ActArgs{static_cast<const _Float16*>(routed_in), static_cast<const _Float16*>(shared_in),
+                                     T * topk, 0, 0, 0, N, N_shared, sorted_expert, nullptr, segs, nseg,
+                                     static_cast<uint8_t*>(out), static_cast<_Float16*>(scales)};
+  a.bias_routed = static_cast<const _Float16*>(glu->bias_routed);
+  a.bias_shared = static_cast<const _Float16*>(glu->bias_shared);
+  a.nexp = nseg - (shared_in ? 1 : 0);
+  a.c = -(glu->alpha * 1.4426950408889634f);
+  a.limit = glu->limit;
+  return launch_act(glu->act, a, T * topk + (shared_in ? T : 0), N, shared_in ? N_shared : N, stream, mx);
+}
+
+int mxmoe_moe_combine_bias(const void* y, const int32_t* inv_slot, const int32_t* sorted_expert, const float* weights,
+                           const void* bias, const void* shared, const float* shared_w, const void* shared_bias, int64_t T,
+                           int topk, int E, int H, void* out, void* stream) {
+  if (T < 0 || topk <= 0 || H <= 0 || H % 8 || E < 1)
+    return fail(MXMOE_GG_ERR_INVALID, "mxmoe_moe_combine_bias: need H %% 8 == 0, topk > 0, E >= 1 (H=%d E=%d)", H, E);
+  if (!aligned16(bias) || !aligned16(shared_bias) || (shared_bias && !shared))
+    return fail(MXMOE_GG_ERR_INVALID, "mxmoe_moe_combine_bias: misaligned bias pointer (16 B), or a shared_bias without shared");
+  if (T == 0) return MXMOE_GG_OK;
+  if (!y || !inv_slot || !weights || !out || (bias && !sorted_expert) || !aligned16(y) || !aligned16(out) ||
+      (shared && !aligned16(shared)))
+    return fail(MXMOE_GG_ERR_INVALID, "mxmoe_moe_combine_bias: NULL or misaligned pointer (16 B)");
+  hipLaunchKernelGGL(combine_bias_kernel, dim3((unsigned)T), dim3(kThreads), 0, (hipStream_t)stream,
+                     static_cast<const _Float16*>(y), inv_slot, sorted_expert, weights, static_cast<const _Float16*>(bias),
+                     static_cast<const _Float16*>(shared), shared_w, static_cast<const _Float16*>(shared_bias), topk, E, H,
+                     static_cast<_Float16*>(out));
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(MXMOE_GG_ERR_HIP, "combine_bias_kernel launch failed: %s", hipGetErrorString(e));
+  return MXMOE_GG_OK;
 }
 
 int mxmoe_moe_combine(const void* y, const int32_t* inv_slot, const float* weights, const void* shared,

@@ -130,11 +130,21 @@ def gate_routing_args(E: int, topk: int, scoring: str = "softmax", e_bias: Optio
     return group_top, plain
 
 
+def _check_logit_bias(logit_bias: Optional[torch.Tensor], E: int, device=None) -> None:
+    if logit_bias is None:
+        return
+    if logit_bias.dtype != torch.float32 or not logit_bias.is_contiguous() or tuple(logit_bias.shape) != (E,):
+        raise ValueError(f"logit_bias must be a contiguous f32 [{E}] tensor")
+    if device is not None and logit_bias.device != device:
+        raise ValueError("logit_bias must be on hidden's device")
+
+
 def gate(hidden: torch.Tensor, w_gate: torch.Tensor, topk: int, *, renormalize: bool = False,
          w_shared_gate: Optional[torch.Tensor] = None, return_logits: bool = False,
          stream: Optional[torch.cuda.Stream] = None, out=None, scoring: str = "softmax",
          e_bias: Optional[torch.Tensor] = None, n_group: int = 1, topk_group: int = 1,
-         group_top: Optional[int] = None, routed_scaling_factor: float = 1.0, return_scores: bool = False):
+         group_top: Optional[int] = None, routed_scaling_factor: float = 1.0, return_scores: bool = False,
+         logit_bias: Optional[torch.Tensor] = None):
     """The router (mxmoe_moe_gate / mxmoe_moe_gate_ex, one launch): hidden fp16 [T, H], w_gate fp16 [E, H] ->
     (topk_ids int32 [T, topk], topk_weights f32 [T, topk], shared_w f32 [T] or None), and the f32
     [T, E] logits as a fourth item with ``return_logits``. Selection on the logits (ties: lower index),
@@ -150,7 +160,11 @@ def gate(hidden: torch.Tensor, w_gate: torch.Tensor, topk: int, *, renormalize: 
     ``routed_scaling_factor`` multiplies the weights; ``return_scores`` appends the f32 [T, E] sigmoid
     scores after the logits, if any. DeepSeek-V3: scoring="sigmoid", e_bias, n_group=8, topk_group=4,
     renormalize=True, routed_scaling_factor=2.5. With all of these at their defaults the call is
-    mxmoe_moe_gate's."""
+    mxmoe_moe_gate's.
+
+    ``logit_bias`` (f32 [E]; mxmoe_moe_gate_ex2): added to the logits before everything else — the returned
+    logits, the selection and the weights all see the sum (the shared gate does not). gpt-oss:
+    ``renormalize=True, logit_bias=router.bias`` (top-k on the biased logits, softmax over the chosen ones)."""
     if hidden.dim() != 2 or hidden.dtype != torch.float16 or not hidden.is_contiguous():
         raise ValueError("hidden must be a contiguous fp16 [T, H] tensor")
     T, H = hidden.shape
@@ -165,6 +179,7 @@ def gate(hidden: torch.Tensor, w_gate: torch.Tensor, topk: int, *, renormalize: 
     dev = hidden.device
     if e_bias is not None and e_bias.device != dev:
         raise ValueError("e_bias must be on hidden's device")
+    _check_logit_bias(logit_bias, E, dev)
     want = [((T, topk), torch.int32), ((T, topk), torch.float32), ((T,), torch.float32) if sg is not None else None]
     want += [((T, E), torch.float32)] * (int(bool(return_logits)) + int(bool(return_scores)))
     if out is None:
@@ -180,7 +195,12 @@ def gate(hidden: torch.Tensor, w_gate: torch.Tensor, topk: int, *, renormalize: 
     ids, wts, sw = out[:3]
     logits = out[3] if return_logits else None
     scores = out[-1] if return_scores else None
-    if plain:
+    if logit_bias is not None:
+        nat.check(nat.symbol("mxmoe_moe_gate_ex2")(
+            _ptr(hidden), _ptr(w_gate), _ptr(sg), T, H, E, topk, int(bool(renormalize)), GATE_SCORING[scoring], _ptr(e_bias),
+            int(n_group), int(topk_group), group_top, float(routed_scaling_factor), _ptr(logit_bias), _ptr(ids), _ptr(wts),
+            _ptr(sw), _ptr(logits), _ptr(scores), _stream(stream)))
+    elif plain:
         nat.check(nat.lib().mxmoe_moe_gate(_ptr(hidden), _ptr(w_gate), _ptr(sg), T, H, E, topk, int(bool(renormalize)),
                                            _ptr(ids), _ptr(wts), _ptr(sw), _ptr(logits), _stream(stream)))
     else:
@@ -363,6 +383,97 @@ def combine_into(out: torch.Tensor, y: torch.Tensor, inv_slot: torch.Tensor, wei
                                           _ptr(out), _stream(stream)))
 
 
+@dataclasses.dataclass(frozen=True)
+class SwigluClamp:
+    """gpt-oss's gated activation (GptOssExperts._apply_gate; MXMOE_GLU_SWIGLU_CLAMP of include/mxmoe_moe.h):
+    act = (clamp(up, -limit, limit) + 1) * g * sigmoid(alpha * g), g = min(gate, limit)."""
+
+    alpha: float = 1.702
+    limit: float = 7.0
+
+    def __post_init__(self):
+        if not math.isfinite(self.alpha) or not math.isfinite(self.limit) or not self.limit > 0:
+            raise ValueError(f"SwigluClamp needs a finite alpha and a finite limit > 0, got {self.alpha}, {self.limit}")
+
+
+def _check_activation(activation) -> None:
+    if activation != "silu" and not isinstance(activation, SwigluClamp):
+        raise ValueError(f"activation must be 'silu' or a SwigluClamp, got {activation!r}")
+
+
+def _glu_struct(activation, bias_routed: Optional[torch.Tensor], bias_shared: Optional[torch.Tensor]) -> "nat.MoeGluC":
+    clamp = isinstance(activation, SwigluClamp)
+    return nat.MoeGluC(nat.GLU_SWIGLU_CLAMP if clamp else nat.GLU_SILU, activation.alpha if clamp else 0.0,
+                       activation.limit if clamp else 0.0, None if bias_routed is None else bias_routed.data_ptr(),
+                       None if bias_shared is None else bias_shared.data_ptr())
+
+
+def _check_bias(b: Optional[torch.Tensor], shape: tuple, what: str, device) -> None:
+    if b is not None and (b.dtype != torch.float16 or not b.is_contiguous() or tuple(b.shape) != shape or b.device != device):
+        raise ValueError(f"{what} must be a contiguous fp16 {list(shape)} tensor on the activations' device")
+
+
+def glu_quant(routed: torch.Tensor, shared: Optional[torch.Tensor], r: Routing, qtags: Sequence[int],
+              activation="silu", bias_routed: Optional[torch.Tensor] = None, bias_shared: Optional[torch.Tensor] = None,
+              stream: Optional[torch.cuda.Stream] = None) -> ActBatch:
+    """``silu_mul_quant`` (plain [gate | up] inputs) for a gate_up projection with a bias and / or another gated
+    activation (mxmoe_moe_glu_quant): the expert's bias row (bias_routed fp16 [E, 2N], bias_shared fp16 [2Ns], each
+    [gate | up]) is added to the gate_up output as it is read, then ``activation`` ("silu" or a ``SwigluClamp``)
+    and the quantisation by tag. With "silu" and no bias: silu_mul_quant's output byte for byte."""
+    _check_activation(activation)
+    N = routed.shape[1] // 2
+    Ns = shared.shape[1] // 2 if shared is not None else 0
+    nseg = r.E + (1 if shared is not None else 0)
+    if len(qtags) != nseg:
+        raise ValueError(f"need {nseg} quant tags, got {len(qtags)}")
+    _check_bias(bias_routed, (r.E, 2 * N), "bias_routed", routed.device)
+    _check_bias(bias_shared, (2 * Ns,), "bias_shared", routed.device)
+    if bias_shared is not None and shared is None:
+        raise ValueError("bias_shared given without a shared input")
+    rows = list(r.counts) + ([r.T] if shared is not None else [])
+    first = r.first_slot + ([r.T * r.topk] if shared is not None else [])
+    widths = [N] * r.E + ([Ns] if shared is not None else [])
+    segs, dsegs, out, scales = _make_segments(rows, first, widths, qtags, routed.device)
+    glu = _glu_struct(activation, bias_routed, bias_shared)
+    fn = nat.symbol("mxmoe_moe_glu_quant")
+
+    def launch(st=stream):
+        nat.check(fn(ctypes.byref(glu), _ptr(routed), _ptr(shared), r.T, r.topk, N, Ns, _ptr(r.sorted_expert), _ptr(dsegs),
+                     nseg, _tag_mask(qtags), _ptr(out), _ptr(scales), _stream(st)))
+
+    launch()
+    b = ActBatch(out, scales, segs, list(qtags))
+    b.relaunch = launch  # (keeps routed, the biases and dsegs alive)
+    return b
+
+
+def combine_bias_into(out: torch.Tensor, y: torch.Tensor, inv_slot: torch.Tensor, sorted_expert: torch.Tensor,
+                      weights: torch.Tensor, bias: Optional[torch.Tensor], shared: Optional[torch.Tensor],
+                      shared_w: Optional[torch.Tensor], shared_bias: Optional[torch.Tensor], topk: int, E: int,
+                      stream: Optional[torch.cuda.Stream] = None) -> None:
+    """mxmoe_moe_combine_bias on preallocated device buffers (no allocation, one launch: graph-capturable): as
+    ``combine_into`` with the down projection's bias (fp16 [E, H], the expert of a slot from sorted_expert; the shared
+    expert's fp16 [H]) added to each down output before its weight."""
+    T, H = out.shape
+    _check_bias(bias, (E, H), "bias", out.device)
+    _check_bias(shared_bias, (H,), "shared_bias", out.device)
+    nat.check(nat.symbol("mxmoe_moe_combine_bias")(_ptr(y), _ptr(inv_slot), _ptr(sorted_expert), _ptr(weights), _ptr(bias),
+                                                   _ptr(shared), _ptr(shared_w), _ptr(shared_bias), T, topk, E, H, _ptr(out),
+                                                   _stream(stream)))
+
+
+def combine_bias(y: torch.Tensor, r: Routing, weights: torch.Tensor, bias: Optional[torch.Tensor],
+                 shared: Optional[torch.Tensor] = None, shared_w: Optional[torch.Tensor] = None,
+                 shared_bias: Optional[torch.Tensor] = None, stream: Optional[torch.cuda.Stream] = None) -> torch.Tensor:
+    """``combine`` for a down projection with a bias per expert: out[t] = sum_k weights[t,k] * (y[slot(t,k)] +
+    bias[expert(t,k)]) (+ shared_w[t] * (shared[t] + shared_bias)), f32 fma chain, fp16 out."""
+    w = weights.to(torch.float32).contiguous()
+    sw = None if shared_w is None else shared_w.to(torch.float32).contiguous()
+    out = torch.empty(r.T, y.shape[1], dtype=torch.float16, device=y.device)
+    combine_bias_into(out, y, r.inv_slot, r.sorted_expert, w, bias, shared, sw, shared_bias, r.topk, r.E, stream)
+    return out
+
+
 # ------------------------------------------------------------------ reference-named entry points
 
 def _qtags(qparams_per_exp, n: int) -> list[int]:
@@ -535,6 +646,7 @@ class ExpertWeights:
     q: QParams
     N: int
     K: int
+    scale_out_of_range: int = 0  # prepare_weight_mx: scale bytes outside [104, 140] (include/mxmoe_gg.h)
 
 
 def prepare_weight(w: torch.Tensor, q: QParams, interleave: bool = False) -> ExpertWeights:
@@ -560,6 +672,71 @@ def prepare_weight(w: torch.Tensor, q: QParams, interleave: bool = False) -> Exp
     return ExpertWeights(pack_wxax(qw, q.w_bits), sw, q, N, K)
 
 
+MX_QCFGS = ("w4a4_g32_sym_MXFP4", "w4a16_g32_sym_MXFP4", "w4a8_g32_sym_MXFP8")
+MX_EXACT_SCALE_RANGE = (104, 140)  # scale bytes for which every dequantised weight is an exact fp16 (include/mxmoe_gg.h)
+
+
+def prepare_weight_mx(codes: torch.Tensor, scales: torch.Tensor, q: QParams, warn: bool = True) -> ExpertWeights:
+    """Weights that already are MXFP4 (a checkpoint's ``blocks`` / ``scales``) -> the GroupGEMM's B operand for any of
+    the three MX qcfgs, with no requantisation: codes uint8 [N, K/2] (low nibble = element 2i, e2m1) are used as they
+    are (no copy when contiguous: the three qcfgs' operands share the tensor), scales uint8 [N, K/32] (e8m0) are put
+    into the device layout (``pack_mxfp4_scales``). ``scale_out_of_range`` of the result counts the scale bytes
+    outside [104, 140], the range in which the weight-only type's fp16 dequantisation is exact (outside it the
+    result is recorded, not specified: include/mxmoe_gg.h); a non-zero count warns unless ``warn`` is False."""
+    from .quantize import MXFP4_BLOCK, pack_mxfp4_scales
+
+    if q.qcfg not in MX_QCFGS:
+        raise ValueError(f"prepare_weight_mx: qcfg must be one of {MX_QCFGS}, got {q.qcfg}")
+    if codes.dtype != torch.uint8 or scales.dtype != torch.uint8 or codes.dim() != 2 or scales.dim() != 2:
+        raise ValueError("prepare_weight_mx: codes uint8 [N, K/2] and scales uint8 [N, K/32]")
+    N, K = codes.shape[0], 2 * codes.shape[1]
+    if K % MXFP4_BLOCK or tuple(scales.shape) != (N, K // MXFP4_BLOCK):
+        raise ValueError(f"prepare_weight_mx: K = {K} must be a multiple of 32 and scales [{N}, K/32], got "
+                         f"{tuple(scales.shape)}")
+    lo, hi = MX_EXACT_SCALE_RANGE
+    bad = int(((scales < lo) | (scales > hi)).sum())
+    if bad and warn:
+        import warnings
+
+        warnings.warn(f"prepare_weight_mx: {bad} of {scales.numel()} scale bytes lie outside [{lo}, {hi}]: with fp16 "
+                      "activations their blocks' weights are not exact fp16 values (include/mxmoe_gg.h)", stacklevel=2)
+    return ExpertWeights(codes.contiguous(), pack_mxfp4_scales(scales), q, N, K, bad)
+
+
+def pad_cols(t: torch.Tensor, width: int) -> torch.Tensor:
+    """``t`` [..., C] zero-padded along its last dimension to ``width`` columns (hidden states and w_gate of a layer
+    whose widths ``gptoss_layer`` padded; slice the layer's output back with ``out[:, :C]``)."""
+    C = t.shape[-1]
+    if C > width:
+        raise ValueError(f"pad_cols: {C} columns do not fit {width}")
+    if C == width:
+        return t.contiguous()
+    out = torch.zeros(*t.shape[:-1], width, dtype=t.dtype, device=t.device)
+    out[..., :C] = t
+    return out
+
+
+def _stack_bias(bias, n: int, width: int, shared_width: int, what: str):
+    """Per-expert bias rows (a sequence of n [width] tensors, the shared expert's [shared_width] last if the layer
+    has one, or a stacked [n, width] tensor) -> (fp16 [E, width] of the routed experts, fp16 [shared_width] or None)."""
+    if bias is None:
+        return None, None
+    rows = list(bias)
+    if len(rows) != n:
+        raise ValueError(f"{what}: need one row per expert ({n}), got {len(rows)}")
+    E = n - (1 if shared_width else 0)
+    for i, b in enumerate(rows):
+        w = shared_width if i == E and shared_width else width
+        if b.dim() != 1 or b.shape[0] != w:
+            raise ValueError(f"{what}[{i}] must hold {w} elements, got {tuple(b.shape)}")
+    routed = torch.stack([b.to(torch.float16) for b in rows[:E]]).contiguous()
+    shared = rows[E].to(torch.float16).contiguous() if shared_width else None
+    for t in (routed, shared):
+        if t is not None and not torch.isfinite(t).all():
+            raise ValueError(f"{what} must be finite as fp16")
+    return routed, shared
+
+
 class MoEFFN:
     """A quantised MoE FFN layer (routed experts + optional shared expert) on the fused GroupGEMM.
 
@@ -573,8 +750,18 @@ class MoEFFN:
     FUSE_WEIGHT_ONLY = True
 
     def __init__(self, gate_up: Sequence[torch.Tensor], down: Sequence[torch.Tensor],
-                 qcfg: Sequence[tuple[QParams, QParams]], num_routed: int, fuse_silu: Optional[bool] = None):
-        """fuse_silu: the gate_up GroupGEMM writes act = silu(gate) * up straight from its epilogue
+                 qcfg: Sequence[tuple[QParams, QParams]], num_routed: int, fuse_silu: Optional[bool] = None,
+                 gate_up_bias=None, down_bias=None, activation="silu"):
+        """gate_up / down may also be ``ExpertWeights`` (``prepare_weight_mx``: weights that already are MXFP4), used
+        as they are (plain layout: no fuse_silu).
+
+        gate_up_bias[e]: [2N] in [gate; up] order, down_bias[e]: [H] (one row per expert, the shared one last; kept as
+        fp16, which must leave them finite); activation: "silu" or ``SwigluClamp`` (gpt-oss). The gate_up bias is added
+        where the activation pass reads the gate_up output (mxmoe_moe_glu_quant), the down bias where the combine
+        reads the down output (mxmoe_moe_combine_bias): no GroupGEMM kernel knows about either, so a layer with a
+        bias or another activation runs the plain gate_up layout — fuse_silu defaults to False and True raises.
+
+        fuse_silu: the gate_up GroupGEMM writes act = silu(gate) * up straight from its epilogue
         (MXMOE_GG_EPI_SILU_MUL; gate_up weights stored with gate / up rows interleaved in 16-row
         blocks) and only the quantisation runs after it — bit-identical outputs, half the gate_up C
         bytes and no separate SiLU pass (qwen2_moe layer step -6 %). Needs every gate_up qcfg in
@@ -583,21 +770,57 @@ class MoEFFN:
         the interleaved weights and the interleaved-input SiLU pass instead — same outputs. (Before
         round 6 that was every small-batch call: the wo3 kernel's fp16 / w8a8 / w4a4 bodies now carry
         the epilogue too.)"""
+        def dims(w):
+            return (w.N, w.K) if isinstance(w, ExpertWeights) else tuple(w.shape)
+
+        prepared = any(isinstance(w, ExpertWeights) for w in list(gate_up) + list(down))
         self.E = num_routed
         self.has_shared = len(gate_up) == num_routed + 1
-        self.H = gate_up[0].shape[1]
-        self.N = gate_up[0].shape[0] // 2
-        self.Ns = gate_up[-1].shape[0] // 2 if self.has_shared else 0
+        self.H = dims(gate_up[0])[1]
+        self.N = dims(gate_up[0])[0] // 2
+        self.Ns = dims(gate_up[-1])[0] // 2 if self.has_shared else 0
         self.qcfg = list(qcfg)
+        _check_activation(activation)
+        self.activation = activation
+        self.b1, self.b1s = _stack_bias(gate_up_bias, len(gate_up), 2 * self.N, 2 * self.Ns, "gate_up_bias")
+        self.b2, self.b2s = _stack_bias(down_bias, len(gate_up), self.H, self.H if self.has_shared else 0, "down_bias")
         eligible = all(q[0].qcfg in self.FUSE_QCFGS or (self.FUSE_WEIGHT_ONLY and q[0].is_weight_only) for q in qcfg)
         if fuse_silu and not eligible:
             raise ValueError(f"fuse_silu needs every gate_up qcfg in {self.FUSE_QCFGS} or weight-only")
-        self.fuse_silu = eligible if fuse_silu is None else fuse_silu
-        self.w1 = [prepare_weight(w, q[0], interleave=self.fuse_silu) for w, q in zip(gate_up, qcfg)]
-        self.w2 = [prepare_weight(w, q[1]) for w, q in zip(down, qcfg)]
+        if fuse_silu and (self.biased_or_gated or prepared):
+            raise ValueError("fuse_silu: a layer with a bias, an activation other than 'silu' or prepared weights runs "
+                             "the plain gate_up layout (the SiLU epilogue knows neither)")
+        self.fuse_silu = (eligible and not self.biased_or_gated and not prepared) if fuse_silu is None else fuse_silu
+
+        def prep(w, q, interleave=False):
+            if isinstance(w, ExpertWeights):
+                if w.q != q:
+                    raise ValueError(f"prepared weights carry qcfg {w.q.qcfg}, the layer's says {q.qcfg}")
+                return w
+            return prepare_weight(w, q, interleave=interleave)
+
+        self.w1 = [prep(w, q[0], self.fuse_silu) for w, q in zip(gate_up, qcfg)]
+        self.w2 = [prep(w, q[1]) for w, q in zip(down, qcfg)]
         self.tag1 = [qtag_of(q[0].a_bits, q[0].gsize) for q in qcfg]
         self.tag2 = [qtag_of(q[1].a_bits, q[1].gsize) for q in qcfg]
         self.gate_up_mode: Optional[str] = None  # None: the library decides; "interleaved": A/B override
+
+    @property
+    def biased_or_gated(self) -> bool:
+        """The layer has a gate_up or down bias or an activation other than SiLU: its activation pass and combine
+        are mxmoe_moe_glu_quant and mxmoe_moe_combine_bias (otherwise exactly the calls of a layer without)."""
+        return (self.activation != "silu" or any(b is not None for b in (self.b1, self.b1s, self.b2, self.b2s)))
+
+    def _carry_glu(self, v: "MoEFFN") -> None:
+        v.activation, v.b1, v.b1s, v.b2, v.b2s = self.activation, self.b1, self.b1s, self.b2, self.b2s
+
+    def act_quant(self, h1: torch.Tensor, h1s: Optional[torch.Tensor], r: Routing, mode: str) -> ActBatch:
+        """The activation pass behind the gate_up GroupGEMM for its output layout ``mode`` (``gate_up_call``)."""
+        if self.biased_or_gated:
+            if mode != "plain":
+                raise ValueError(f"a layer with a bias or another activation needs the plain gate_up layout, got {mode!r}")
+            return glu_quant(h1, h1s, r, self.tag2, self.activation, self.b1, self.b1s)
+        return silu_mul_quant(h1, h1s, r, self.tag2, activated=mode == "fused", interleaved=mode == "interleaved")
 
     def a16_view(self) -> "MoEFFN":
         """This layer (every qcfg w4a4_g32_sym_MXFP4) with fp16 activations: a layer whose qcfgs are
@@ -618,6 +841,7 @@ class MoEFFN:
         v.tag1 = [ACT_FP16] * len(self.qcfg)
         v.tag2 = [ACT_FP16] * len(self.qcfg)
         v.gate_up_mode = None
+        self._carry_glu(v)
         return v
 
     def a8_view(self) -> "MoEFFN":
@@ -640,6 +864,7 @@ class MoEFFN:
         v.tag1 = [ACT_MXFP8] * len(self.qcfg)
         v.tag2 = [ACT_MXFP8] * len(self.qcfg)
         v.gate_up_mode = None
+        self._carry_glu(v)
         return v
 
     def gate_up_call(self, a1: ActBatch, T: int, topk: int, dev):
@@ -697,7 +922,7 @@ class MoEFFN:
         a1 = quant_act(hidden, r, self.tag1, self.has_shared)
         g1, h1, h1s, mode = self.gate_up_call(a1, T, topk, dev)
         g1.launch()
-        a2 = silu_mul_quant(h1, h1s, r, self.tag2, activated=mode == "fused", interleaved=mode == "interleaved")
+        a2 = self.act_quant(h1, h1s, r, mode)
         y = torch.empty(T * topk, self.H, dtype=torch.float16, device=dev)
         ys = torch.empty(T, self.H, dtype=torch.float16, device=dev) if self.has_shared else None
         probs = []
@@ -709,10 +934,78 @@ class MoEFFN:
             probs.append(Problem(A=a2.A(e), B=w.B, C=C, M=s.rows, N=w.N, K=w.K, q=w.q, scale_a=a2.scale(e),
                                  scale_b=w.scale_b))
         GroupGemm(probs, device=dev).launch()
-        out = combine(y, r, topk_weights, ys, shared_w)
+        if self.biased_or_gated:
+            out = combine_bias(y, r, topk_weights, self.b2, ys, shared_w, self.b2s)
+        else:
+            out = combine(y, r, topk_weights, ys, shared_w)
         if return_intermediates:
             return out, dict(routing=r, a1=a1, h1=h1, h1s=h1s, a2=a2, y=y, ys=ys)
         return out
+
+
+def gptoss_layer(blocks_gate_up: torch.Tensor, scales_gate_up: torch.Tensor, bias_gate_up: torch.Tensor,
+                 blocks_down: torch.Tensor, scales_down: torch.Tensor, bias_down: torch.Tensor, *, act_bits: int = 16,
+                 pad_to: int = 128, alpha: float = 1.702, limit: float = 7.0) -> MoEFFN:
+    """A gpt-oss MoE layer's experts from the checkpoint's tensors, with no requantisation: ``*_blocks`` uint8
+    [E, rows, K/32, 16] (16 bytes = 32 e2m1 codes, low nibble first: the canonical format of include/mxmoe_gg.h),
+    ``*_scales`` uint8 [E, rows, K/32] (e8m0), biases [E, rows]; gate_up has rows = 2N with gate / up interleaved
+    (rows 0::2 / 1::2) and K = H, down has rows = H and K = N.
+
+    The rows are de-interleaved into [gate; up] (codes, scales and bias alike) and N and H are zero-padded up to
+    multiples of ``pad_to`` (the plumbing needs widths that are multiples of 128: 2880 -> 2944): padded codes 0,
+    padded scale bytes 127 (2^0), padded biases 0. The padding is neutral — a padded intermediate column has
+    g = u = 0 and act = (0 + 1) * 0 * sigmoid(0) = 0, a padded output column is exactly 0 — so the caller feeds
+    ``pad_cols(hidden, layer.H)`` (and ``pad_cols(w_gate, layer.H)`` to the router) and slices the output.
+    act_bits: 16 (w4a16_g32_sym_MXFP4), 8 (w4a8_g32_sym_MXFP8) or 4 (w4a4_g32_sym_MXFP4); ``a16_view`` / ``a8_view``
+    give the others on the same tensors. ``scale_out_of_range`` of the layer: the checkpoint's scale bytes outside
+    [104, 140] (``prepare_weight_mx``; one warning for the layer)."""
+    from .groupgemm import W4A4_MXFP4, W4A8_MXFP8, W4A16_MXFP4
+
+    if act_bits not in (16, 8, 4):
+        raise ValueError(f"act_bits must be 16, 8 or 4, got {act_bits}")
+    q = {16: W4A16_MXFP4, 8: W4A8_MXFP8, 4: W4A4_MXFP4}[act_bits]
+    if pad_to < 128 or pad_to % 128:
+        raise ValueError(f"pad_to must be a positive multiple of 128, got {pad_to}")
+    for name, blk, sc, bias in (("gate_up", blocks_gate_up, scales_gate_up, bias_gate_up),
+                                ("down", blocks_down, scales_down, bias_down)):
+        if blk.dtype != torch.uint8 or sc.dtype != torch.uint8 or blk.dim() != 4 or blk.shape[3] != 16 or \
+                tuple(sc.shape) != tuple(blk.shape[:3]) or tuple(bias.shape) != tuple(blk.shape[:2]):
+            raise ValueError(f"{name}: need blocks uint8 [E, rows, K/32, 16], scales uint8 [E, rows, K/32], bias [E, rows]")
+    E, N2, H = blocks_gate_up.shape[0], blocks_gate_up.shape[1], 32 * blocks_gate_up.shape[2]
+    N = N2 // 2
+    if N2 % 2 or tuple(blocks_down.shape[:3]) != (E, H, N // 32) or N % 32:
+        raise ValueError(f"down blocks must be [E = {E}, H = {H}, N / 32 = {N // 32}, 16] for gate_up's 2N = {N2} rows")
+    up = lambda v: (v + pad_to - 1) // pad_to * pad_to
+    Hp, Np = up(H), up(N)
+
+    def padded(blk, sc, rows, rows_p, K, Kp):
+        """one expert's [rows, K] weight -> canonical codes [rows_p, Kp / 2] and scales [rows_p, Kp / 32]"""
+        codes = torch.zeros(rows_p, Kp // 2, dtype=torch.uint8, device=blk.device)
+        scales = torch.full((rows_p, Kp // 32), 127, dtype=torch.uint8, device=blk.device)
+        codes[:rows, :K // 2] = blk.reshape(rows, K // 2)
+        scales[:rows, :K // 32] = sc
+        return codes, scales
+
+    w1, w2, b1, b2 = [], [], [], []
+    for e in range(E):
+        parts = [padded(blocks_gate_up[e, h::2], scales_gate_up[e, h::2], N, Np, H, Hp) for h in (0, 1)]  # gate, up
+        w1.append(prepare_weight_mx(torch.cat([p[0] for p in parts]), torch.cat([p[1] for p in parts]), q, warn=False))
+        w2.append(prepare_weight_mx(*padded(blocks_down[e], scales_down[e], H, Hp, N, Np), q, warn=False))
+        bgu = torch.zeros(2 * Np, dtype=torch.float16, device=bias_gate_up.device)
+        bgu[:N] = bias_gate_up[e, 0::2].to(torch.float16)
+        bgu[Np:Np + N] = bias_gate_up[e, 1::2].to(torch.float16)
+        b1.append(bgu)
+        b2.append(pad_cols(bias_down[e].to(torch.float16), Hp))
+    layer = MoEFFN(w1, w2, [(q, q)] * E, num_routed=E, gate_up_bias=b1, down_bias=b2,
+                   activation=SwigluClamp(alpha, limit))
+    layer.scale_out_of_range = sum(w.scale_out_of_range for w in w1 + w2)
+    if layer.scale_out_of_range:
+        import warnings
+
+        lo, hi = MX_EXACT_SCALE_RANGE
+        warnings.warn(f"gptoss_layer: {layer.scale_out_of_range} scale bytes lie outside [{lo}, {hi}]: with fp16 activations "
+                      "their blocks' weights are not exact fp16 values (include/mxmoe_gg.h)", stacklevel=2)
+    return layer
 
 
 class MoEBlock:
@@ -721,12 +1014,14 @@ class MoEBlock:
     w_gate: fp16 [E, H]; topk / renormalize: the model's routing (qwen2_moe: 4, DeepSeek-V2-Lite: 6,
     both without renormalisation; Mixtral: 2 with); w_shared_gate: fp16 [H], qwen2_moe's
     shared_expert_gate (only for a layer with a shared expert); scoring, e_bias, n_group, topk_group,
-    group_top, routed_scaling_factor: ``gate``'s (DeepSeek-V3 / V2, GLM-4.5)."""
+    group_top, routed_scaling_factor: ``gate``'s (DeepSeek-V3 / V2, GLM-4.5); logit_bias: f32 [E], ``gate``'s
+    (gpt-oss: with renormalize=True)."""
 
     def __init__(self, ffn: MoEFFN, w_gate: torch.Tensor, topk: int, renormalize: bool = False,
                  w_shared_gate: Optional[torch.Tensor] = None, scoring: str = "softmax",
                  e_bias: Optional[torch.Tensor] = None, n_group: int = 1, topk_group: int = 1,
-                 group_top: Optional[int] = None, routed_scaling_factor: float = 1.0):
+                 group_top: Optional[int] = None, routed_scaling_factor: float = 1.0,
+                 logit_bias: Optional[torch.Tensor] = None):
         if tuple(w_gate.shape) != (ffn.E, ffn.H):
             raise ValueError(f"w_gate must be [{ffn.E}, {ffn.H}], got {tuple(w_gate.shape)}")
         if w_shared_gate is not None and not ffn.has_shared:
@@ -734,9 +1029,12 @@ class MoEBlock:
         if w_shared_gate is not None and w_shared_gate.numel() != ffn.H:
             raise ValueError(f"w_shared_gate must hold {ffn.H} elements")
         gate_routing_args(ffn.E, topk, scoring, e_bias, n_group, topk_group, group_top, routed_scaling_factor)
+        _check_logit_bias(logit_bias, ffn.E)
         self.ffn, self.topk, self.renormalize = ffn, topk, renormalize
         self.routing = dict(scoring=scoring, e_bias=None if e_bias is None else e_bias.contiguous(), n_group=n_group,
                             topk_group=topk_group, group_top=group_top, routed_scaling_factor=routed_scaling_factor)
+        if logit_bias is not None:  # (a key of its own only when given: the routing of every other block is unchanged)
+            self.routing["logit_bias"] = logit_bias
         self.w_gate = w_gate.contiguous()
         self.w_shared_gate = None if w_shared_gate is None else w_shared_gate.contiguous()
 
@@ -764,8 +1062,7 @@ class PlannedForward:
         topk = r.topk
         self.a1 = quant_act(hidden, r, layer.tag1, layer.has_shared)
         self.g1, self.h1, self.h1s, self.mode = layer.gate_up_call(self.a1, T, topk, dev)
-        self.a2 = silu_mul_quant(self.h1, self.h1s, r, layer.tag2, activated=self.mode == "fused",
-                                 interleaved=self.mode == "interleaved")
+        self.a2 = layer.act_quant(self.h1, self.h1s, r, self.mode)
         self.y = torch.empty(T * topk, layer.H, dtype=torch.float16, device=dev)
         self.ys = torch.empty(T, layer.H, dtype=torch.float16, device=dev) if layer.has_shared else None
         p2 = []
@@ -778,9 +1075,13 @@ class PlannedForward:
         self.g2 = GroupGemm(p2, device=dev)
         self.out = torch.empty(T, layer.H, dtype=torch.float16, device=dev)
         self.w = topk_weights.to(torch.float32).contiguous()
+        if layer.biased_or_gated:
+            comb = lambda: combine_bias_into(self.out, self.y, r.inv_slot, r.sorted_expert, self.w, layer.b2, self.ys, None,
+                                             layer.b2s, topk, layer.E)
+        else:
+            comb = lambda: combine_into(self.out, self.y, r.inv_slot, self.w, self.ys, topk)
         self.stages = {"quant_act": self.a1.relaunch, "gate_up": self.g1.launch, "act_quant": self.a2.relaunch,
-                       "down": self.g2.launch,
-                       "combine": lambda: combine_into(self.out, self.y, r.inv_slot, self.w, self.ys, topk)}
+                       "down": self.g2.launch, "combine": comb}
 
     def __call__(self) -> torch.Tensor:
         for fn in self.stages.values():
@@ -863,6 +1164,9 @@ class GraphForward:
         if ffn.gate_up_mode not in (None, "interleaved"):
             raise ValueError(f"gate_up_mode must be None or 'interleaved', got {ffn.gate_up_mode!r}")
         self.mode = "plain" if not ffn.fuse_silu else "interleaved" if ffn.gate_up_mode == "interleaved" else "fused"
+        if ffn.biased_or_gated and self.mode != "plain":
+            raise ValueError("a layer with a bias or another activation needs the plain gate_up layout")
+        self._glu = _glu_struct(ffn.activation, ffn.b1, ffn.b1s) if ffn.biased_or_gated else None
         while True:
             f = 1 if self.mode == "fused" else 2
             self.h1 = torch.zeros(n, f * N, dtype=torch.float16, device=dev)
@@ -920,7 +1224,11 @@ class GraphForward:
                                               _ptr(self.segs[0]), self.nseg, _ptr(self.a1), _ptr(self.s1), st))
         self.g1.launch(self.dyn[0], stream)
         mode = {"plain": 1, "fused": 2, "interleaved": 3}[self.mode]
-        if any(t in _MX_TAGS for t in ffn.tag2):
+        if self._glu is not None:
+            nat.check(nat.symbol("mxmoe_moe_glu_quant")(ctypes.byref(self._glu), _ptr(self.h1), _ptr(self.h1s), T, topk, ffn.N,
+                                                        ffn.Ns, _ptr(sorted_e), _ptr(self.segs[1]), self.nseg, self.mask2,
+                                                        _ptr(self.a2), _ptr(self.s2), st))
+        elif any(t in _MX_TAGS for t in ffn.tag2):
             nat.check(lib.mxmoe_moe_act_quant(mode, _ptr(self.h1), _ptr(self.h1s), T, topk, ffn.N, ffn.Ns, _ptr(sorted_e),
                                               None, _ptr(self.segs[1]), self.nseg, self.mask2, _ptr(self.a2),
                                               _ptr(self.s2), st))
@@ -929,8 +1237,12 @@ class GraphForward:
             nat.check(fn(_ptr(self.h1), _ptr(self.h1s), T, topk, ffn.N, ffn.Ns, _ptr(sorted_e), _ptr(self.segs[1]),
                          self.nseg, _ptr(self.a2), _ptr(self.s2), st))
         self.g2.launch(self.dyn[1], stream)
-        nat.check(lib.mxmoe_moe_combine(_ptr(self.y), _ptr(inv), _ptr(topk_weights), _ptr(self.ys), _ptr(shared_w), T, topk,
-                                        ffn.H, _ptr(self.out), st))
+        if self._glu is not None:
+            combine_bias_into(self.out, self.y, inv, sorted_e, topk_weights, ffn.b2, self.ys, shared_w, ffn.b2s, topk, ffn.E,
+                              stream)
+        else:
+            nat.check(lib.mxmoe_moe_combine(_ptr(self.y), _ptr(inv), _ptr(topk_weights), _ptr(self.ys), _ptr(shared_w), T,
+                                            topk, ffn.H, _ptr(self.out), st))
         return self.out
 
     __call__ = launch
@@ -1117,6 +1429,123 @@ def graph_forward_bench(batches: Sequence[int] = (128,), model: str = "qwen2_moe
         out["graph_wall_over_eager_wall"] = round(m("graph_wall") / m("eager_wall"), 4)
         out["graph_device_over_planned_device"] = round(m("graph_device") / m("planned_device"), 4)
         out["bit_identical_to_eager"], out["bit_identical_to_planned"] = same, same_planned
+        out["status"] = gf.status()
+        return out
+
+    for bs in batches:  # (a generator: a caller can print each size as it completes)
+        yield one(bs)
+
+
+def gptoss_bench(batches: Sequence[int] = (1, 16, 128, 512, 2048), act_bits: int = 16, rounds: int = 4, iters: int = 20,
+                 E: int = 32, topk: int = 4, H: int = 2944, N: int = 2944):
+    """One gpt-oss-20b-shaped MoE block (E = 32 experts, top-4, H = N = 2880 padded to 2944, MXFP4 weights with random
+    codes, biases, the clamped SwiGLU, the router with its logit bias) at every batch size of ``batches`` (yields one
+    dict each), three ways in one process with the sides alternating over rounds, as ``graph_forward_bench``: eager
+    ``MoEBlock.forward`` (wall, a synchronise per call), ``PlannedForward`` (device), ``GraphForward`` replayed from a
+    captured graph (wall and device); and the two new plumbing kernels against the ones they stand in for at the
+    same shape: the biased clamped activation pass against the SiLU pass, combine_bias against combine, with the
+    extra bias bytes each reads. Per side the median of the rounds' medians with min / max (µs). act_bits: 16 or 8."""
+    import time
+
+    from .groupgemm import W4A8_MXFP8, W4A16_MXFP4
+    from .harness import time_launches
+
+    dev = "cuda"
+    q = {16: W4A16_MXFP4, 8: W4A8_MXFP8}[act_bits]
+    g = torch.Generator(device=dev).manual_seed(0)
+
+    def weight(rows, K):  # random e2m1 codes, scales 2^-6 .. 2^-4 (|w| <= 0.375)
+        codes = torch.randint(0, 256, (rows, K // 2), generator=g, device=dev, dtype=torch.uint8)
+        scales = torch.randint(121, 124, (rows, K // 32), generator=g, device=dev, dtype=torch.uint8)
+        return prepare_weight_mx(codes, scales, q)
+
+    rnd = lambda *shape: torch.rand(*shape, generator=g, device=dev) * 2 - 1
+    ffn = MoEFFN([weight(2 * N, H) for _ in range(E)], [weight(H, N) for _ in range(E)], [(q, q)] * E, num_routed=E,
+                 gate_up_bias=list(rnd(E, 2 * N) * 0.5), down_bias=list(rnd(E, H) * 0.5), activation=SwigluClamp())
+    block = MoEBlock(ffn, (torch.randn(E, H, generator=g, device=dev) * H ** -0.5).half(), topk, renormalize=True,
+                     logit_bias=torch.randn(E, generator=g, device=dev))
+
+    def one(bs: int) -> dict:
+        hidden = (torch.randn(bs, H, generator=g, device=dev) * 0.5).half()
+        want, mid = block.forward(hidden, return_intermediates=True)
+        ids, wts, r = mid["topk_ids"], mid["topk_weights"], mid["routing"]
+        pf = PlannedForward(ffn, hidden, ids, wts)
+        gf = GraphForward(block, bs)
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            gf.launch(hidden)
+        side.synchronize()
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph, stream=side):
+            gf.launch(hidden)
+        torch.cuda.current_stream().wait_stream(side)
+        graph.replay()
+        pf()
+        torch.cuda.synchronize()
+        same = bool(torch.equal(gf.out.view(torch.int16), want.view(torch.int16)))
+        same_planned = bool(torch.equal(pf.out.view(torch.int16), want.view(torch.int16)))
+        # the plumbing kernels alone, old against new, on the planned step's buffers
+        silu = silu_mul_quant(pf.h1, None, r, ffn.tag2)
+        out2 = torch.empty_like(pf.out)
+        w32 = wts.to(torch.float32).contiguous()
+
+        def wall(fn):
+            ts = []
+            for i in range(iters + 3):
+                t0 = time.perf_counter()
+                fn()
+                torch.cuda.synchronize()
+                if i >= 3:
+                    ts.append((time.perf_counter() - t0) * 1e6)
+            return sorted(ts)[len(ts) // 2]
+
+        def device(fn):
+            return time_launches(fn, 3, iters)["median_ms"] * 1e3
+
+        sides = {
+            "eager_wall": lambda: wall(lambda: block.forward(hidden)),
+            "planned_device": lambda: device(pf),
+            "graph_wall": lambda: wall(graph.replay),
+            "graph_device": lambda: device(graph.replay),
+            "act_silu": lambda: device(silu.relaunch),
+            "act_glu_bias": lambda: device(pf.a2.relaunch),
+            "combine": lambda: device(lambda: combine_into(out2, pf.y, r.inv_slot, w32, None, topk)),
+            "combine_bias": lambda: device(pf.stages["combine"]),
+        }
+        res = {k: [] for k in sides}
+        for _ in range(rounds):
+            for k, fn in sides.items():
+                res[k].append(fn())
+
+        def stat(v):
+            med = sorted(v)[len(v) // 2]
+            return {"median_us": round(med, 1), "min_us": round(min(v), 1), "max_us": round(max(v), 1),
+                    "spread": round((max(v) - min(v)) / med, 4)}
+
+        out = {"model": "gpt-oss-20b layer", "act_bits": act_bits, "bs": bs, "E": E, "topk": topk, "H": H, "N": N}
+        out.update({k: stat(v) for k, v in res.items()})
+        m = lambda k: out[k]["median_us"]
+        n = bs * topk
+        abits = _BITS[ffn.tag2[0]]
+        out["act_bytes"] = {"silu": n * 2 * N * 2 + n * N * abits // 8, "extra_bias_read": n * 2 * N * 2,
+                            "distinct_bias": E * 2 * N * 2}
+        out["combine_bytes"] = {"combine": n * H * 2 + bs * H * 2, "extra_bias_read": n * H * 2 + n * 4,
+                                "distinct_bias": E * H * 2}
+        out["act_glu_bias_over_silu"] = round(m("act_glu_bias") / m("act_silu"), 4)
+        out["combine_bias_over_combine"] = round(m("combine_bias") / m("combine"), 4)
+        out["graph_wall_over_eager_wall"] = round(m("graph_wall") / m("eager_wall"), 4)
+        out["graph_device_over_planned_device"] = round(m("graph_device") / m("planned_device"), 4)
+        names = [ln.split()[1] for ln in nat.list_variants()]
+        out["variants"] = {"planned": [names[pf.g1.variant], names[pf.g2.variant]],
+                           "graph": [names[gf.g1.variant], names[gf.g2.variant]]}
+        # the host plans (eager, planned) may split K, the device-planned graph never does: with float accumulation
+        # (fp16 or MXFP8 activations) the two then differ in summation order, so bit identity is expected only
+        # where no host plan split K
+        out["host_splitk_slabs"] = [int(pf.g1.info.splitk_slabs), int(pf.g2.info.splitk_slabs)]
+        out["graph_max_abs_diff_to_eager"] = float((gf.out.float() - want.float()).abs().max())
+        out["eager_max_abs"] = float(want.float().abs().max())
+        out["bit_identical_to_eager"], out["planned_bit_identical_to_eager"] = same, same_planned
         out["status"] = gf.status()
         return out
 
