@@ -716,26 +716,23 @@ static int launch_act(int mode, ARGS a, int64_t nslots, int w_routed, int w_shar
   if (nslots == 0) return MXMOE_GG_OK;
   a.parts = 1;
   a.blk_shared = 0;
+  a.s0 = 0;
   const int qw = (w_shared / 4 + 127) & ~127;
   if (nslots > a.ntk && a.ntk > 0 && w_shared > w_routed && qw <= w_routed) {
     a.parts = 4;
     a.blk_shared = (a.ntk + kThreads / 64 - 1) / (kThreads / 64);
-    a.s0 = 0;
     a.nslots = nslots;
     launch_act_any(mode, a, w_routed, mx, (hipStream_t)stream);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(MXMOE_GG_ERR_HIP, "act_quant_kernel launch failed: %s", hipGetErrorString(e));
-    return MXMOE_GG_OK;
-  }
-  const bool split = nslots > a.ntk && w_routed != w_shared && a.ntk > 0;
-  a.s0 = 0;
-  a.nslots = split ? a.ntk : nslots;
-  const int w0 = split ? w_routed : (nslots > a.ntk ? (w_routed > w_shared ? w_routed : w_shared) : w_routed);
-  launch_act_any(mode, a, w0, mx, (hipStream_t)stream);
-  if (split) {
-    a.s0 = a.ntk;
-    a.nslots = nslots;
-    launch_act_any(mode, a, w_shared, mx, (hipStream_t)stream);
+  } else {
+    const bool split = nslots > a.ntk && w_routed != w_shared && a.ntk > 0;
+    a.nslots = split ? a.ntk : nslots;
+    const int w0 = split ? w_routed : (nslots > a.ntk ? (w_routed > w_shared ? w_routed : w_shared) : w_routed);
+    launch_act_any(mode, a, w0, mx, (hipStream_t)stream);
+    if (split) {
+      a.s0 = a.ntk;
+      a.nslots = nslots;
+      launch_act_any(mode, a, w_shared, mx, (hipStream_t)stream);
+    }
   }
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail(MXMOE_GG_ERR_HIP, "act_quant_kernel launch failed: %s", hipGetErrorString(e));
@@ -765,14 +762,34 @@ static int slots_check(const char* fn, const void* routed_in, const void* shared
     return fail(MXMOE_GG_ERR_INVALID, "%s: NULL or misaligned pointer (16 B)", fn);
   return MXMOE_GG_OK;
 }
+// the kernel arguments of a pass over slot-ordered inputs (modes 1..3 and mxmoe_moe_glu_quant)
+static ActArgs slot_args(const void* routed_in, const void* shared_in, int64_t T, int topk, int N, int N_shared,
+                         const int32_t* sorted_expert, const mxmoe_moe_seg* segs, int nseg, void* out, void* scales) {
+  return ActArgs{static_cast<const _Float16*>(routed_in), static_cast<const _Float16*>(shared_in), T * topk, 0, 0, 0,
+                 N, N_shared, sorted_expert, nullptr, segs, nseg, static_cast<uint8_t*>(out),
+                 static_cast<_Float16*>(scales)};
+}
 static int slots_impl(const char* fn, int mode, const void* routed_in, const void* shared_in, int64_t T, int topk, int N,
                       int N_shared, const int32_t* sorted_expert, const mxmoe_moe_seg* segs, int nseg, void* out,
                       void* scales, void* stream, bool mx) {
   if (int st = slots_check(fn, routed_in, shared_in, T, topk, N, N_shared, sorted_expert, segs, nseg, out)) return st;
-  const ActArgs a{static_cast<const _Float16*>(routed_in), static_cast<const _Float16*>(shared_in), T * topk, 0, 0, 0,
-                  N, N_shared, sorted_expert, nullptr, segs, nseg, static_cast<uint8_t*>(out),
-                  static_cast<_Float16*>(scales)};
+  const ActArgs a = slot_args(routed_in, shared_in, T, topk, N, N_shared, sorted_expert, segs, nseg, out, scales);
   return launch_act(mode, a, T * topk + (shared_in ? T : 0), N, shared_in ? N_shared : N, stream, mx);
+}
+// a tag_mask's check (MXMOE_GG_OK or the failure, under the entry point's name) and whether it names an MX tag
+static int tag_mask_mx(const char* fn, uint32_t tag_mask, bool* mx) {
+  if (tag_mask & ~((2u << MXMOE_ACT_MXFP4) - 1u | 1u << MXMOE_ACT_MXFP8))  // (tag 5 is not assigned)
+    return fail(MXMOE_GG_ERR_UNSUPPORTED, "%s: unknown activation tag in mask %#x", fn, tag_mask);
+  *mx = ((tag_mask >> MXMOE_ACT_MXFP4) & 1) || ((tag_mask >> MXMOE_ACT_MXFP8) & 1);
+  return MXMOE_GG_OK;
+}
+// what mxmoe_moe_combine and mxmoe_moe_combine_bias check alike once T > 0
+// (missing: an entry point's own required pointer is NULL)
+static int combine_check(const char* fn, const void* y, const int32_t* inv_slot, const float* weights, const void* shared,
+                         const void* out, bool missing = false) {
+  if (!y || !inv_slot || !weights || !out || missing || !aligned16(y) || !aligned16(out) || (shared && !aligned16(shared)))
+    return fail(MXMOE_GG_ERR_INVALID, "%s: NULL or misaligned pointer (16 B)", fn);
+  return MXMOE_GG_OK;
 }
 
 // what mxmoe_moe_gate and mxmoe_moe_gate_ex check alike, before any HIP call
@@ -926,9 +943,8 @@ int mxmoe_moe_act_quant(int mode, const void* routed_in, const void* shared_in, 
                         const int32_t* sorted_expert, const int32_t* perm_token, const mxmoe_moe_seg* segs, int nseg,
                         uint32_t tag_mask, void* out, void* scales, void* stream) {
   if (mode < 0 || mode > 3) return fail(MXMOE_GG_ERR_INVALID, "mxmoe_moe_act_quant: mode must be 0..3 (mode=%d)", mode);
-  if (tag_mask & ~((2u << MXMOE_ACT_MXFP4) - 1u | 1u << MXMOE_ACT_MXFP8))  // (tag 5 is not assigned)
-    return fail(MXMOE_GG_ERR_UNSUPPORTED, "mxmoe_moe_act_quant: unknown activation tag in mask %#x", tag_mask);
-  const bool mx = ((tag_mask >> MXMOE_ACT_MXFP4) & 1) || ((tag_mask >> MXMOE_ACT_MXFP8) & 1);
+  bool mx = false;
+  if (int st = tag_mask_mx("mxmoe_moe_act_quant", tag_mask, &mx)) return st;
   if (mode == 0)
     return quant_act_impl("mxmoe_moe_act_quant", routed_in, T, N, topk, shared_in != nullptr, sorted_expert, perm_token,
                           segs, nseg, out, scales, stream, mx);
@@ -948,14 +964,11 @@ int mxmoe_moe_glu_quant(const mxmoe_moe_glu* glu, const void* routed_in, const v
                 (double)glu->alpha, (double)glu->limit);
   if (!aligned16(glu->bias_routed) || !aligned16(glu->bias_shared))
     return fail(MXMOE_GG_ERR_INVALID, "%s: misaligned bias pointer (16 B)", fn);
-  if (tag_mask & ~((2u << MXMOE_ACT_MXFP4) - 1u | 1u << MXMOE_ACT_MXFP8))  // (tag 5 is not assigned)
-    return fail(MXMOE_GG_ERR_UNSUPPORTED, "%s: unknown activation tag in mask %#x", fn, tag_mask);
+  bool mx = false;
+  if (int st = tag_mask_mx(fn, tag_mask, &mx)) return st;
   if (int st = slots_check(fn, routed_in, shared_in, T, topk, N, N_shared, sorted_expert, segs, nseg, out)) return st;
-  const bool mx = ((tag_mask >> MXMOE_ACT_MXFP4) & 1) || ((tag_mask >> MXMOE_ACT_MXFP8) & 1);
   GluArgs a{};
-  static_cast<ActArgs&>(a) = ActArgs{static_cast<const _Float16*>(routed_in), static_cast<const _Float16*>(shared_in),
-                                     T * topk, 0, 0, 0, N, N_shared, sorted_expert, nullptr, segs, nseg,
-                                     static_cast<uint8_t*>(out), static_cast<_Float16*>(scales)};
+  static_cast<ActArgs&>(a) = slot_args(routed_in, shared_in, T, topk, N, N_shared, sorted_expert, segs, nseg, out, scales);
   a.bias_routed = static_cast<const _Float16*>(glu->bias_routed);
   a.bias_shared = static_cast<const _Float16*>(glu->bias_shared);
   a.nexp = nseg - (shared_in ? 1 : 0);
@@ -972,9 +985,7 @@ int mxmoe_moe_combine_bias(const void* y, const int32_t* inv_slot, const int32_t
   if (!aligned16(bias) || !aligned16(shared_bias) || (shared_bias && !shared))
     return fail(MXMOE_GG_ERR_INVALID, "mxmoe_moe_combine_bias: misaligned bias pointer (16 B), or a shared_bias without shared");
   if (T == 0) return MXMOE_GG_OK;
-  if (!y || !inv_slot || !weights || !out || (bias && !sorted_expert) || !aligned16(y) || !aligned16(out) ||
-      (shared && !aligned16(shared)))
-    return fail(MXMOE_GG_ERR_INVALID, "mxmoe_moe_combine_bias: NULL or misaligned pointer (16 B)");
+  if (int st = combine_check("mxmoe_moe_combine_bias", y, inv_slot, weights, shared, out, bias && !sorted_expert)) return st;
   hipLaunchKernelGGL(combine_bias_kernel, dim3((unsigned)T), dim3(kThreads), 0, (hipStream_t)stream,
                      static_cast<const _Float16*>(y), inv_slot, sorted_expert, weights, static_cast<const _Float16*>(bias),
                      static_cast<const _Float16*>(shared), shared_w, static_cast<const _Float16*>(shared_bias), topk, E, H,
@@ -989,8 +1000,7 @@ int mxmoe_moe_combine(const void* y, const int32_t* inv_slot, const float* weigh
   if (T < 0 || topk <= 0 || H <= 0 || H % 8)
     return fail(MXMOE_GG_ERR_INVALID, "mxmoe_moe_combine: need H %% 8 == 0, topk > 0 (H=%d)", H);
   if (T == 0) return MXMOE_GG_OK;
-  if (!y || !inv_slot || !weights || !out || !aligned16(y) || !aligned16(out) || (shared && !aligned16(shared)))
-    return fail(MXMOE_GG_ERR_INVALID, "mxmoe_moe_combine: NULL or misaligned pointer (16 B)");
+  if (int st = combine_check("mxmoe_moe_combine", y, inv_slot, weights, shared, out)) return st;
   hipLaunchKernelGGL(combine_kernel, dim3((unsigned)T), dim3(kThreads), 0, (hipStream_t)stream,
                      static_cast<const _Float16*>(y), inv_slot, weights, static_cast<const _Float16*>(shared), shared_w,
                      topk, H, static_cast<_Float16*>(out));

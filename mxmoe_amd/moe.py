@@ -24,6 +24,7 @@ from __future__ import annotations
 
 import ctypes
 import dataclasses
+import functools
 import math
 from typing import Optional, Sequence
 
@@ -291,33 +292,89 @@ def _make_segments(rows: Sequence[int], first: Sequence[int], widths: Sequence[i
     return segs, dev_segs, out, scales
 
 
+# The activation pass's input layouts (mxmoe_moe_act_quant's mode numbers, include/mxmoe_moe.h) and the entry point
+# each had before the tagged one: "gather" reads hidden rows through perm_token, the others the gate_up output in
+# slot order — "plain" [gate | up] columns, "fused" the activations themselves (the GroupGEMM's SiLU epilogue ran),
+# "interleaved" gate / up alternating in 16-column blocks.
+_ACT_MODES = {"gather": 0, "plain": 1, "fused": 2, "interleaved": 3}
+_LEGACY_ENTRY = {"gather": "mxmoe_moe_quant_act", "plain": "mxmoe_moe_silu_mul_quant", "fused": "mxmoe_moe_quant_slots",
+                 "interleaved": "mxmoe_moe_silu_mul_quant_il"}
+_MX_MASK = _tag_mask(_MX_TAGS)
+
+
+def _act_entry(mode: str, has_mx_tag: bool, glu: bool) -> str:
+    """The C entry point of an activation pass: a gate_up bias or another activation (``glu``) needs
+    mxmoe_moe_glu_quant, which reads the plain layout only; any MX tag needs the tagged entry (the builds of the
+    kernel that carry those tags); everything else keeps the mode's own entry, which a library loaded through
+    MXMOE_GG_LIB that predates the tagged one still has."""
+    if mode not in _ACT_MODES:
+        raise ValueError(f"activation-pass mode must be one of {list(_ACT_MODES)}, got {mode!r}")
+    if glu:
+        if mode != "plain":
+            raise ValueError(f"a layer with a bias or another activation needs the plain gate_up layout, got {mode!r}")
+        return "mxmoe_moe_glu_quant"
+    return "mxmoe_moe_act_quant" if has_mx_tag else _LEGACY_ENTRY[mode]
+
+
+def _launch_act(mode: str, glu: Optional["nat.MoeGluC"], src: torch.Tensor, src_shared: Optional[torch.Tensor], T: int,
+                topk: int, width: int, width_shared: int, sorted_expert: torch.Tensor, perm: Optional[torch.Tensor],
+                dsegs: torch.Tensor, nseg: int, mask: int, out: torch.Tensor, scales: torch.Tensor,
+                stream: Optional[torch.cuda.Stream]) -> None:
+    """One activation pass on preallocated buffers: exactly one native call, nothing allocated or converted.
+    src / src_shared: hidden (and hidden again for a shared expert) with ``perm`` in "gather" mode, else the
+    gate_up outputs; dsegs / nseg: the device segment table; mask: ``_tag_mask`` of the segments' tags."""
+    entry = _act_entry(mode, bool(mask & _MX_MASK), glu is not None)
+    fn = nat.symbol(entry)  # (a library from before the entry refuses here)
+    slots = (_ptr(src), _ptr(src_shared), T, topk, width, width_shared, _ptr(sorted_expert))
+    segs = (_ptr(dsegs), nseg)
+    stores = (_ptr(out), _ptr(scales), _stream(stream))
+    if entry == "mxmoe_moe_quant_act":
+        st = fn(_ptr(src), T, width, topk, int(src_shared is not None), _ptr(sorted_expert), _ptr(perm), *segs, *stores)
+    elif entry == "mxmoe_moe_act_quant":
+        st = fn(_ACT_MODES[mode], *slots, _ptr(perm), *segs, mask, *stores)
+    elif entry == "mxmoe_moe_glu_quant":
+        st = fn(ctypes.byref(glu), *slots, *segs, mask, *stores)
+    else:
+        st = fn(*slots, *segs, *stores)
+    nat.check(st)
+
+
+def _segments_of(r: Routing, qtags: Sequence[int], width: int, width_shared: int, has_shared: bool, device):
+    """``_make_segments`` for a routing: one segment per expert in slot order (rows = its count) and, with
+    ``has_shared``, the shared expert's T rows behind them (len(qtags) == E, or E + 1 with the shared expert last)."""
+    nseg = r.E + (1 if has_shared else 0)
+    if len(qtags) != nseg:
+        raise ValueError(f"need {nseg} quant tags, got {len(qtags)}")
+    rows = list(r.counts) + ([r.T] if has_shared else [])
+    first = r.first_slot + ([r.T * r.topk] if has_shared else [])
+    widths = [width] * r.E + ([width_shared] if has_shared else [])
+    return _make_segments(rows, first, widths, qtags, device)
+
+
+def _act_pass(mode: str, glu, src: torch.Tensor, src_shared: Optional[torch.Tensor], r: Routing, qtags: Sequence[int],
+              width: int, width_shared: int, stream: Optional[torch.cuda.Stream]) -> ActBatch:
+    """Segments and stores for this routing, the pass launched once, and the launch kept as ``relaunch``."""
+    segs, dsegs, out, scales = _segments_of(r, qtags, width, width_shared, src_shared is not None, src.device)
+    mask = _tag_mask(qtags)
+    perm = r.perm_token if mode == "gather" else None
+
+    def launch(st=stream):
+        _launch_act(mode, glu, src, src_shared, r.T, r.topk, width, width_shared, r.sorted_expert, perm, dsegs, len(segs),
+                    mask, out, scales, st)
+
+    launch()
+    b = ActBatch(out, scales, segs, list(qtags))
+    b.relaunch = launch  # same buffers, kernel only (timing / graph capture); keeps the inputs and dsegs alive
+    return b
+
+
 def quant_act(hidden: torch.Tensor, r: Routing, qtags: Sequence[int], with_shared: bool,
               stream: Optional[torch.cuda.Stream] = None) -> ActBatch:
     """Gather hidden rows into expert order and quantise each expert's rows by its tag
     (len(qtags) == E, or E + 1 with the shared expert last)."""
-    T, K = hidden.shape
-    nseg = r.E + (1 if with_shared else 0)
-    if len(qtags) != nseg:
-        raise ValueError(f"need {nseg} quant tags, got {len(qtags)}")
-    rows = list(r.counts) + ([T] if with_shared else [])
-    first = r.first_slot + ([T * r.topk] if with_shared else [])
-    segs, dsegs, out, scales = _make_segments(rows, first, [K] * nseg, qtags, hidden.device)
+    K = hidden.shape[1]
     h = hidden.contiguous()
-
-    def launch(st=stream):
-        if any(t in _MX_TAGS for t in qtags):  # the builds that carry the MX tags (mxmoe_moe_act_quant, mode 0)
-            nat.check(nat.lib().mxmoe_moe_act_quant(0, _ptr(h), _ptr(h) if with_shared else None, T, r.topk, K, K,
-                                                    _ptr(r.sorted_expert), _ptr(r.perm_token), _ptr(dsegs), nseg,
-                                                    _tag_mask(qtags), _ptr(out), _ptr(scales), _stream(st)))
-            return
-        nat.check(nat.lib().mxmoe_moe_quant_act(_ptr(h), T, K, r.topk, int(with_shared), _ptr(r.sorted_expert),
-                                                _ptr(r.perm_token), _ptr(dsegs), nseg, _ptr(out), _ptr(scales),
-                                                _stream(st)))
-
-    launch()
-    b = ActBatch(out, scales, segs, list(qtags))
-    b.relaunch = launch  # same buffers, kernel only (timing / graph capture); keeps h and dsegs alive
-    return b
+    return _act_pass("gather", None, h, h if with_shared else None, r, qtags, K, K, stream)
 
 
 def silu_mul_quant(routed: torch.Tensor, shared: Optional[torch.Tensor], r: Routing, qtags: Sequence[int],
@@ -330,57 +387,52 @@ def silu_mul_quant(routed: torch.Tensor, shared: Optional[torch.Tensor], r: Rout
     output's gate / up columns alternate in 16-column blocks (the fused layout's weights through the
     plain epilogue; mxmoe_moe_silu_mul_quant_il)."""
     div = 1 if activated else 2
-    N = routed.shape[1] // div
     Ns = shared.shape[1] // div if shared is not None else 0
-    nseg = r.E + (1 if shared is not None else 0)
-    if len(qtags) != nseg:
-        raise ValueError(f"need {nseg} quant tags, got {len(qtags)}")
-    rows = list(r.counts) + ([r.T] if shared is not None else [])
-    first = r.first_slot + ([r.T * r.topk] if shared is not None else [])
-    widths = [N] * r.E + ([Ns] if shared is not None else [])
-    segs, dsegs, out, scales = _make_segments(rows, first, widths, qtags, routed.device)
-    fn = (nat.lib().mxmoe_moe_quant_slots if activated else
-          nat.lib().mxmoe_moe_silu_mul_quant_il if interleaved else nat.lib().mxmoe_moe_silu_mul_quant)
+    mode = "fused" if activated else "interleaved" if interleaved else "plain"
+    return _act_pass(mode, None, routed, shared, r, qtags, routed.shape[1] // div, Ns, stream)
 
-    mode = 2 if activated else 3 if interleaved else 1
 
-    def launch(st=stream):
-        if any(t in _MX_TAGS for t in qtags):  # the builds that carry the MX tags
-            nat.check(nat.lib().mxmoe_moe_act_quant(mode, _ptr(routed), _ptr(shared), r.T, r.topk, N, Ns,
-                                                    _ptr(r.sorted_expert), None, _ptr(dsegs), nseg, _tag_mask(qtags),
-                                                    _ptr(out), _ptr(scales), _stream(st)))
-            return
-        nat.check(fn(_ptr(routed), _ptr(shared), r.T, r.topk, N, Ns, _ptr(r.sorted_expert), _ptr(dsegs), nseg,
-                     _ptr(out), _ptr(scales), _stream(st)))
+def _f32(t: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
+    return None if t is None else t.to(torch.float32).contiguous()
 
-    launch()
-    b = ActBatch(out, scales, segs, list(qtags))
-    b.relaunch = launch
-    return b
+
+def _launch_combine(out: torch.Tensor, y: torch.Tensor, inv_slot: torch.Tensor, sorted_expert: Optional[torch.Tensor],
+                    weights: torch.Tensor, shared: Optional[torch.Tensor], shared_w: Optional[torch.Tensor], topk: int,
+                    stream: Optional[torch.cuda.Stream] = None, down_bias: Optional[tuple] = None) -> None:
+    """The combine on preallocated device buffers (no allocation, one launch: graph-capturable): out [T, H] fp16,
+    y [R, H] fp16 rows, inv_slot int32 [T*topk] rows of y, weights f32 [T, topk], shared fp16 [T, H] and shared_w
+    f32 [T] or None. ``down_bias`` = (E, bias, shared_bias): mxmoe_moe_combine_bias, with the down projection's
+    bias (fp16 [E, H], the expert of a slot from sorted_expert; the shared expert's fp16 [H]; either may be None)
+    added to each down output before its weight (``MoEFFN.down_bias``: which layers run that kernel)."""
+    T, H = out.shape
+    if down_bias is not None:
+        E, bias, shared_bias = down_bias
+        _check_bias(bias, (E, H), "bias", out.device)
+        _check_bias(shared_bias, (H,), "shared_bias", out.device)
+        st = nat.symbol("mxmoe_moe_combine_bias")(_ptr(y), _ptr(inv_slot), _ptr(sorted_expert), _ptr(weights), _ptr(bias),
+                                                  _ptr(shared), _ptr(shared_w), _ptr(shared_bias), T, topk, E, H, _ptr(out),
+                                                  _stream(stream))
+    else:
+        st = nat.lib().mxmoe_moe_combine(_ptr(y), _ptr(inv_slot), _ptr(weights), _ptr(shared), _ptr(shared_w), T, topk, H,
+                                         _ptr(out), _stream(stream))
+    nat.check(st)
 
 
 def combine(y: torch.Tensor, r: Routing, weights: torch.Tensor, shared: Optional[torch.Tensor] = None,
             shared_w: Optional[torch.Tensor] = None, stream: Optional[torch.cuda.Stream] = None) -> torch.Tensor:
     """out[t] = sum_k weights[t,k] * y[slot(t,k)] (+ shared_w[t] * shared[t]), f32 fma chain, fp16 out."""
-    H = y.shape[1]
-    w = weights.to(torch.float32).contiguous()
-    sw = None if shared_w is None else shared_w.to(torch.float32).contiguous()
-    out = torch.empty(r.T, H, dtype=torch.float16, device=y.device)
-    nat.check(nat.lib().mxmoe_moe_combine(_ptr(y), _ptr(r.inv_slot), _ptr(w), _ptr(shared), _ptr(sw), r.T, r.topk, H,
-                                          _ptr(out), _stream(stream)))
+    out = torch.empty(r.T, y.shape[1], dtype=torch.float16, device=y.device)
+    _launch_combine(out, y, r.inv_slot, None, _f32(weights), shared, _f32(shared_w), r.topk, stream)
     return out
 
 
 def combine_into(out: torch.Tensor, y: torch.Tensor, inv_slot: torch.Tensor, weights: torch.Tensor,
                  shared: Optional[torch.Tensor], topk: int, stream: Optional[torch.cuda.Stream] = None) -> None:
-    """combine() on preallocated device buffers (no allocation, one launch: graph-capturable):
-    out [T, H] fp16, y [R, H] fp16 rows, inv_slot int32 [T*topk] rows of y, weights f32 [T, topk],
-    shared fp16 [T, H] or None. dist.CombineExchange's token-owner combine."""
-    T, H = out.shape
-    if T == 0:
+    """combine() on preallocated device buffers (``_launch_combine`` without shared_w). dist.CombineExchange's
+    token-owner combine."""
+    if out.shape[0] == 0:
         return
-    nat.check(nat.lib().mxmoe_moe_combine(_ptr(y), _ptr(inv_slot), _ptr(weights), _ptr(shared), None, T, topk, H,
-                                          _ptr(out), _stream(stream)))
+    _launch_combine(out, y, inv_slot, None, weights, shared, None, topk, stream)
 
 
 @dataclasses.dataclass(frozen=True)
@@ -423,27 +475,12 @@ def glu_quant(routed: torch.Tensor, shared: Optional[torch.Tensor], r: Routing, 
     _check_activation(activation)
     N = routed.shape[1] // 2
     Ns = shared.shape[1] // 2 if shared is not None else 0
-    nseg = r.E + (1 if shared is not None else 0)
-    if len(qtags) != nseg:
-        raise ValueError(f"need {nseg} quant tags, got {len(qtags)}")
     _check_bias(bias_routed, (r.E, 2 * N), "bias_routed", routed.device)
     _check_bias(bias_shared, (2 * Ns,), "bias_shared", routed.device)
     if bias_shared is not None and shared is None:
         raise ValueError("bias_shared given without a shared input")
-    rows = list(r.counts) + ([r.T] if shared is not None else [])
-    first = r.first_slot + ([r.T * r.topk] if shared is not None else [])
-    widths = [N] * r.E + ([Ns] if shared is not None else [])
-    segs, dsegs, out, scales = _make_segments(rows, first, widths, qtags, routed.device)
-    glu = _glu_struct(activation, bias_routed, bias_shared)
-    fn = nat.symbol("mxmoe_moe_glu_quant")
-
-    def launch(st=stream):
-        nat.check(fn(ctypes.byref(glu), _ptr(routed), _ptr(shared), r.T, r.topk, N, Ns, _ptr(r.sorted_expert), _ptr(dsegs),
-                     nseg, _tag_mask(qtags), _ptr(out), _ptr(scales), _stream(st)))
-
-    launch()
-    b = ActBatch(out, scales, segs, list(qtags))
-    b.relaunch = launch  # (keeps routed, the biases and dsegs alive)
+    b = _act_pass("plain", _glu_struct(activation, bias_routed, bias_shared), routed, shared, r, qtags, N, Ns, stream)
+    b.biases = (bias_routed, bias_shared)  # the struct holds their addresses only: alive as long as relaunch is
     return b
 
 
@@ -451,15 +488,8 @@ def combine_bias_into(out: torch.Tensor, y: torch.Tensor, inv_slot: torch.Tensor
                       weights: torch.Tensor, bias: Optional[torch.Tensor], shared: Optional[torch.Tensor],
                       shared_w: Optional[torch.Tensor], shared_bias: Optional[torch.Tensor], topk: int, E: int,
                       stream: Optional[torch.cuda.Stream] = None) -> None:
-    """mxmoe_moe_combine_bias on preallocated device buffers (no allocation, one launch: graph-capturable): as
-    ``combine_into`` with the down projection's bias (fp16 [E, H], the expert of a slot from sorted_expert; the shared
-    expert's fp16 [H]) added to each down output before its weight."""
-    T, H = out.shape
-    _check_bias(bias, (E, H), "bias", out.device)
-    _check_bias(shared_bias, (H,), "shared_bias", out.device)
-    nat.check(nat.symbol("mxmoe_moe_combine_bias")(_ptr(y), _ptr(inv_slot), _ptr(sorted_expert), _ptr(weights), _ptr(bias),
-                                                   _ptr(shared), _ptr(shared_w), _ptr(shared_bias), T, topk, E, H, _ptr(out),
-                                                   _stream(stream)))
+    """mxmoe_moe_combine_bias on preallocated device buffers (``_launch_combine`` with a down bias)."""
+    _launch_combine(out, y, inv_slot, sorted_expert, weights, shared, shared_w, topk, stream, (E, bias, shared_bias))
 
 
 def combine_bias(y: torch.Tensor, r: Routing, weights: torch.Tensor, bias: Optional[torch.Tensor],
@@ -467,10 +497,9 @@ def combine_bias(y: torch.Tensor, r: Routing, weights: torch.Tensor, bias: Optio
                  shared_bias: Optional[torch.Tensor] = None, stream: Optional[torch.cuda.Stream] = None) -> torch.Tensor:
     """``combine`` for a down projection with a bias per expert: out[t] = sum_k weights[t,k] * (y[slot(t,k)] +
     bias[expert(t,k)]) (+ shared_w[t] * (shared[t] + shared_bias)), f32 fma chain, fp16 out."""
-    w = weights.to(torch.float32).contiguous()
-    sw = None if shared_w is None else shared_w.to(torch.float32).contiguous()
     out = torch.empty(r.T, y.shape[1], dtype=torch.float16, device=y.device)
-    combine_bias_into(out, y, r.inv_slot, r.sorted_expert, w, bias, shared, sw, shared_bias, r.topk, r.E, stream)
+    combine_bias_into(out, y, r.inv_slot, r.sorted_expert, _f32(weights), bias, shared, _f32(shared_w), shared_bias, r.topk,
+                      r.E, stream)
     return out
 
 
@@ -478,6 +507,23 @@ def combine_bias(y: torch.Tensor, r: Routing, weights: torch.Tensor, bias: Optio
 
 def _qtags(qparams_per_exp, n: int) -> list[int]:
     return [qtag_of(int(q[0]), int(q[2])) for q in list(qparams_per_exp)[:n]]
+
+
+def _problem_lists(b: ActBatch, out_store: torch.Tensor, ld_of):
+    """The reference's per-PROBLEM lists (non-empty segments in order): (inp_list, inp_scale_list, out_list), a
+    segment's output its rows x ld_of(e) slice of out_store, packed one behind the other; no scale: an empty tensor."""
+    inp_list, scale_list, out_list = [], [], []
+    off = 0
+    for e, s in enumerate(b.segs):
+        if s.rows == 0:
+            continue
+        ld = ld_of(e)
+        inp_list.append(b.A(e))
+        sc = b.scale(e)
+        scale_list.append(sc if sc is not None else torch.empty(0, dtype=torch.float16, device=out_store.device))
+        out_list.append(out_store[off:off + s.rows * ld].view(s.rows, ld))
+        off += s.rows * ld
+    return inp_list, scale_list, out_list
 
 
 def gg_permute_inp(hidden: torch.Tensor, topk_ids: torch.Tensor, E: int):
@@ -501,23 +547,11 @@ def quant_inp_act(hidden: torch.Tensor, topk_ids: torch.Tensor, num_experts: int
     tags = _qtags(qparams_per_exp, num_experts + (1 if has_shared else 0))
     b = quant_act(hidden, r, tags, has_shared)
     out_store = torch.empty((num_shared_experts + r.topk) * T * N * 2, dtype=torch.float16, device=hidden.device)
-    inp_list, scale_list, out_list = [], [], []
-    off = 0
-    for e, s in enumerate(b.segs):
-        ld = 2 * N * (num_shared_experts if e == num_experts else 1)
-        if s.rows == 0:
-            continue
-        inp_list.append(b.A(e))
-        sc = b.scale(e)
-        scale_list.append(sc if sc is not None else torch.empty(0, dtype=torch.float16, device=hidden.device))
-        out_list.append(out_store[off:off + s.rows * ld].view(s.rows, ld))
-        off += s.rows * ld
+    lists = _problem_lists(b, out_store, lambda e: 2 * N * (num_shared_experts if e == num_experts else 1))
     if verbose:
         print([(e, s.rows, s.qtag) for e, s in enumerate(b.segs)])
     counts = torch.tensor(r.counts, dtype=torch.int64)
-    res = (inp_list, scale_list, out_list, b.out, b.scales, out_store, counts, r.perm_token.to(torch.int64),
-           r.sorted_expert)
-    return res
+    return (*lists, b.out, b.scales, out_store, counts, r.perm_token.to(torch.int64), r.sorted_expert)
 
 
 def silu_mul_then_quant(inp: torch.Tensor, num_problems: int, num_experts: int, K: int, N: int,
@@ -534,17 +568,7 @@ def silu_mul_then_quant(inp: torch.Tensor, num_problems: int, num_experts: int, 
     tags = _qtags(qparams_per_exp, num_experts + (1 if S > 0 else 0))
     b = silu_mul_quant(routed, shared, r, tags)
     out_store = torch.empty((1 + topk) * T * K, dtype=torch.float16, device=inp.device)
-    inp_list, scale_list, out_list = [], [], []
-    off = 0
-    for e, s in enumerate(b.segs):
-        if s.rows == 0:
-            continue
-        inp_list.append(b.A(e))
-        sc = b.scale(e)
-        scale_list.append(sc if sc is not None else torch.empty(0, dtype=torch.float16, device=inp.device))
-        out_list.append(out_store[off:off + s.rows * K].view(s.rows, K))
-        off += s.rows * K
-    return inp_list, scale_list, out_list, b.out, b.scales, out_store
+    return (*_problem_lists(b, out_store, lambda e: K), b.out, b.scales, out_store)
 
 
 _SHARE_FUSED_PLANS: dict = {}
@@ -737,6 +761,13 @@ def _stack_bias(bias, n: int, width: int, shared_width: int, what: str):
     return routed, shared
 
 
+def _problems(a: ActBatch, ws: Sequence[ExpertWeights], C_of, silu: bool = False) -> list[Problem]:
+    """The GroupGEMM problems of an activation batch on the experts' weights ``ws``: one per non-empty segment, its
+    output C_of(e, segment); silu: the SiLU epilogue (fused-layout gate_up weights)."""
+    return [Problem(A=a.A(e), B=w.B, C=C_of(e, sg), M=sg.rows, N=w.N, K=w.K, q=w.q, scale_a=a.scale(e),
+                    scale_b=w.scale_b, silu=silu) for e, (sg, w) in enumerate(zip(a.segs, ws)) if sg.rows]
+
+
 class MoEFFN:
     """A quantised MoE FFN layer (routed experts + optional shared expert) on the fused GroupGEMM.
 
@@ -809,10 +840,8 @@ class MoEFFN:
     def biased_or_gated(self) -> bool:
         """The layer has a gate_up or down bias or an activation other than SiLU: its activation pass and combine
         are mxmoe_moe_glu_quant and mxmoe_moe_combine_bias (otherwise exactly the calls of a layer without)."""
-        return (self.activation != "silu" or any(b is not None for b in (self.b1, self.b1s, self.b2, self.b2s)))
-
-    def _carry_glu(self, v: "MoEFFN") -> None:
-        v.activation, v.b1, v.b1s, v.b2, v.b2s = self.activation, self.b1, self.b1s, self.b2, self.b2s
+        return (self.activation != "silu" or self.b1 is not None or self.b1s is not None or self.b2 is not None or
+                self.b2s is not None)
 
     def act_quant(self, h1: torch.Tensor, h1s: Optional[torch.Tensor], r: Routing, mode: str) -> ActBatch:
         """The activation pass behind the gate_up GroupGEMM for its output layout ``mode`` (``gate_up_call``)."""
@@ -821,6 +850,27 @@ class MoEFFN:
                 raise ValueError(f"a layer with a bias or another activation needs the plain gate_up layout, got {mode!r}")
             return glu_quant(h1, h1s, r, self.tag2, self.activation, self.b1, self.b1s)
         return silu_mul_quant(h1, h1s, r, self.tag2, activated=mode == "fused", interleaved=mode == "interleaved")
+
+    @property
+    def down_bias(self) -> Optional[tuple]:
+        """``_launch_combine``'s down_bias of this layer: the bias kernel exactly when the layer is
+        ``biased_or_gated`` (then also with no down bias at all), the plain combine (None) otherwise."""
+        return (self.E, self.b2, self.b2s) if self.biased_or_gated else None
+
+    def _view(self, q: QParams, tag: int, fuse_silu: bool) -> "MoEFFN":
+        """This layer with every qcfg replaced by ``q`` (activation tag ``tag``) on the SAME weight tensors: the
+        shapes, the biases and the activation carry over, the A/B override does not."""
+        v = object.__new__(MoEFFN)
+        for name in ("E", "has_shared", "H", "N", "Ns", "activation", "b1", "b1s", "b2", "b2s"):
+            setattr(v, name, getattr(self, name))
+        v.qcfg = [(q, q) for _ in self.qcfg]
+        v.fuse_silu = fuse_silu
+        v.w1 = [dataclasses.replace(w, q=q) for w in self.w1]
+        v.w2 = [dataclasses.replace(w, q=q) for w in self.w2]
+        v.tag1 = [tag] * len(self.qcfg)
+        v.tag2 = [tag] * len(self.qcfg)
+        v.gate_up_mode = None
+        return v
 
     def a16_view(self) -> "MoEFFN":
         """This layer (every qcfg w4a4_g32_sym_MXFP4) with fp16 activations: a layer whose qcfgs are
@@ -832,17 +882,7 @@ class MoEFFN:
 
         if any(q.qcfg != "w4a4_g32_sym_MXFP4" for pair in self.qcfg for q in pair):
             raise ValueError("a16_view needs every qcfg of the layer to be w4a4_g32_sym_MXFP4")
-        v = object.__new__(MoEFFN)
-        v.E, v.has_shared, v.H, v.N, v.Ns = self.E, self.has_shared, self.H, self.N, self.Ns
-        v.qcfg = [(W4A16_MXFP4, W4A16_MXFP4) for _ in self.qcfg]
-        v.fuse_silu = False
-        v.w1 = [dataclasses.replace(w, q=W4A16_MXFP4) for w in self.w1]
-        v.w2 = [dataclasses.replace(w, q=W4A16_MXFP4) for w in self.w2]
-        v.tag1 = [ACT_FP16] * len(self.qcfg)
-        v.tag2 = [ACT_FP16] * len(self.qcfg)
-        v.gate_up_mode = None
-        self._carry_glu(v)
-        return v
+        return self._view(W4A16_MXFP4, ACT_FP16, False)
 
     def a8_view(self) -> "MoEFFN":
         """This layer (every qcfg w4a4_g32_sym_MXFP4, or every one w4a16_g32_sym_MXFP4) with MXFP8
@@ -855,17 +895,23 @@ class MoEFFN:
         if names not in ({"w4a4_g32_sym_MXFP4"}, {"w4a16_g32_sym_MXFP4"}):
             raise ValueError("a8_view needs every qcfg of the layer to be w4a4_g32_sym_MXFP4, or every one "
                              "w4a16_g32_sym_MXFP4")
-        v = object.__new__(MoEFFN)
-        v.E, v.has_shared, v.H, v.N, v.Ns = self.E, self.has_shared, self.H, self.N, self.Ns
-        v.qcfg = [(W4A8_MXFP8, W4A8_MXFP8) for _ in self.qcfg]
-        v.fuse_silu = self.fuse_silu
-        v.w1 = [dataclasses.replace(w, q=W4A8_MXFP8) for w in self.w1]
-        v.w2 = [dataclasses.replace(w, q=W4A8_MXFP8) for w in self.w2]
-        v.tag1 = [ACT_MXFP8] * len(self.qcfg)
-        v.tag2 = [ACT_MXFP8] * len(self.qcfg)
-        v.gate_up_mode = None
-        self._carry_glu(v)
-        return v
+        return self._view(W4A8_MXFP8, ACT_MXFP8, self.fuse_silu)
+
+    def gate_up_layout(self) -> str:
+        """The gate_up output layout the layer asks for: "plain", or for fused-layout weights "fused" (where the
+        call's kernel has the SiLU epilogue: ``gate_up_call``, ``GraphForward``) or, forced, "interleaved"."""
+        if self.gate_up_mode not in (None, "interleaved"):
+            raise ValueError(f"gate_up_mode must be None or 'interleaved', got {self.gate_up_mode!r}")
+        return "plain" if not self.fuse_silu else "interleaved" if self.gate_up_mode == "interleaved" else "fused"
+
+    def _planned(self, a: ActBatch, ws: Sequence[ExpertWeights], T: int, topk: int, width: int, width_shared: int,
+                 silu: bool, dev):
+        """A GroupGEMM over the non-empty segments of ``a`` and its fresh outputs: (GroupGemm, routed
+        [T*topk, width] in slot order, shared [T, width_shared] or None)."""
+        y = torch.empty(T * topk, width, dtype=torch.float16, device=dev)
+        ys = torch.empty(T, width_shared, dtype=torch.float16, device=dev) if self.has_shared else None
+        ps = _problems(a, ws, lambda e, sg: ys if e == self.E else y[sg.first_slot:sg.first_slot + sg.rows], silu)
+        return GroupGemm(ps, device=dev), y, ys
 
     def gate_up_call(self, a1: ActBatch, T: int, topk: int, dev):
         """The planned gate_up GroupGEMM of one call and its output buffers: (GroupGemm, h1, h1s, mode),
@@ -874,44 +920,25 @@ class MoEFFN:
         pass, for calls whose kernel has no SiLU epilogue). The library decides: the variant AUTO
         resolves the call's shapes to is asked for MXMOE_GG_CAP_SILU_MUL (mxmoe_gg_variant_caps), and
         a fused plan the library still refuses (GGError UNSUPPORTED) falls back to "interleaved"."""
-        def problems(C_of, silu):
-            ps = []
-            for e, sg in enumerate(a1.segs):
-                if sg.rows:
-                    w = self.w1[e]
-                    ps.append(Problem(A=a1.A(e), B=w.B, C=C_of(e, sg), M=sg.rows, N=w.N, K=w.K, q=w.q,
-                                      scale_a=a1.scale(e), scale_b=w.scale_b, silu=silu))
-            return ps
-
-        def buffers(mode):
-            f = 1 if mode == "fused" else 2
-            h1 = torch.empty(T * topk, f * self.N, dtype=torch.float16, device=dev)
-            h1s = torch.empty(T, f * self.Ns, dtype=torch.float16, device=dev) if self.has_shared else None
-            ps = problems(lambda e, sg: h1s if e == self.E else h1[sg.first_slot:sg.first_slot + sg.rows],
-                          mode == "fused")
-            return ps, h1, h1s
-
-        if self.gate_up_mode not in (None, "interleaved"):
-            raise ValueError(f"gate_up_mode must be None or 'interleaved', got {self.gate_up_mode!r}")
-        mode = "plain"
-        if self.fuse_silu and self.gate_up_mode == "interleaved":
-            mode = "interleaved"
-        elif self.fuse_silu:
+        mode = self.gate_up_layout()
+        if mode == "fused":
             ph = torch.empty(0, dtype=torch.float16, device=dev)
-            probe = problems(lambda e, sg: ph, False)  # shapes only: AUTO's choice for the plain epilogue
+            probe = _problems(a1, self.w1, lambda e, sg: ph)  # shapes only: AUTO's choice for the plain epilogue
             arr = (nat.GGProblemC * max(len(probe), 1))(*[p.to_c() for p in probe])
             v = nat.resolve_variant(arr, len(probe))
             mode = "fused" if nat.variant_caps(v) & nat.CAP_SILU_MUL else "interleaved"
         if mode == "fused":
-            ps, h1, h1s = buffers(mode)
             try:
-                return GroupGemm(ps, device=dev), h1, h1s, mode
+                return *self._planned(a1, self.w1, T, topk, self.N, self.Ns, True, dev), mode
             except nat.GGError as e:
                 if e.status != nat.MXMOE_GG_ERR_UNSUPPORTED:
                     raise
                 mode = "interleaved"
-        ps, h1, h1s = buffers(mode)
-        return GroupGemm(ps, device=dev), h1, h1s, mode
+        return *self._planned(a1, self.w1, T, topk, 2 * self.N, 2 * self.Ns, False, dev), mode
+
+    def down_call(self, a2: ActBatch, T: int, topk: int, dev):
+        """The planned down GroupGEMM of one call and its output buffers: (GroupGemm, y, ys)."""
+        return self._planned(a2, self.w2, T, topk, self.H, self.H, False, dev)
 
     def forward(self, hidden: torch.Tensor, topk_ids: torch.Tensor, topk_weights: torch.Tensor,
                 shared_w: Optional[torch.Tensor] = None, return_intermediates: bool = False):
@@ -923,21 +950,11 @@ class MoEFFN:
         g1, h1, h1s, mode = self.gate_up_call(a1, T, topk, dev)
         g1.launch()
         a2 = self.act_quant(h1, h1s, r, mode)
-        y = torch.empty(T * topk, self.H, dtype=torch.float16, device=dev)
-        ys = torch.empty(T, self.H, dtype=torch.float16, device=dev) if self.has_shared else None
-        probs = []
-        for e, s in enumerate(a2.segs):
-            if s.rows == 0:
-                continue
-            w = self.w2[e]
-            C = ys if e == self.E else y[s.first_slot:s.first_slot + s.rows]
-            probs.append(Problem(A=a2.A(e), B=w.B, C=C, M=s.rows, N=w.N, K=w.K, q=w.q, scale_a=a2.scale(e),
-                                 scale_b=w.scale_b))
-        GroupGemm(probs, device=dev).launch()
-        if self.biased_or_gated:
-            out = combine_bias(y, r, topk_weights, self.b2, ys, shared_w, self.b2s)
-        else:
-            out = combine(y, r, topk_weights, ys, shared_w)
+        g2, y, ys = self.down_call(a2, T, topk, dev)
+        g2.launch()
+        out = torch.empty(T, self.H, dtype=torch.float16, device=dev)
+        _launch_combine(out, y, r.inv_slot, r.sorted_expert, _f32(topk_weights), ys, _f32(shared_w), topk, None,
+                        self.down_bias)
         if return_intermediates:
             return out, dict(routing=r, a1=a1, h1=h1, h1s=h1s, a2=a2, y=y, ys=ys)
         return out
@@ -1063,23 +1080,11 @@ class PlannedForward:
         self.a1 = quant_act(hidden, r, layer.tag1, layer.has_shared)
         self.g1, self.h1, self.h1s, self.mode = layer.gate_up_call(self.a1, T, topk, dev)
         self.a2 = layer.act_quant(self.h1, self.h1s, r, self.mode)
-        self.y = torch.empty(T * topk, layer.H, dtype=torch.float16, device=dev)
-        self.ys = torch.empty(T, layer.H, dtype=torch.float16, device=dev) if layer.has_shared else None
-        p2 = []
-        for e, sg in enumerate(self.a2.segs):
-            if sg.rows:
-                w = layer.w2[e]
-                C = self.ys if e == layer.E else self.y[sg.first_slot:sg.first_slot + sg.rows]
-                p2.append(Problem(A=self.a2.A(e), B=w.B, C=C, M=sg.rows, N=w.N, K=w.K, q=w.q, scale_a=self.a2.scale(e),
-                                  scale_b=w.scale_b))
-        self.g2 = GroupGemm(p2, device=dev)
+        self.g2, self.y, self.ys = layer.down_call(self.a2, T, topk, dev)
         self.out = torch.empty(T, layer.H, dtype=torch.float16, device=dev)
-        self.w = topk_weights.to(torch.float32).contiguous()
-        if layer.biased_or_gated:
-            comb = lambda: combine_bias_into(self.out, self.y, r.inv_slot, r.sorted_expert, self.w, layer.b2, self.ys, None,
-                                             layer.b2s, topk, layer.E)
-        else:
-            comb = lambda: combine_into(self.out, self.y, r.inv_slot, self.w, self.ys, topk)
+        self.w = _f32(topk_weights)
+        comb = functools.partial(_launch_combine, self.out, self.y, r.inv_slot, r.sorted_expert, self.w, self.ys, None, topk,
+                                 None, layer.down_bias)
         self.stages = {"quant_act": self.a1.relaunch, "gate_up": self.g1.launch, "act_quant": self.a2.relaunch,
                        "down": self.g2.launch, "combine": comb}
 
@@ -1161,9 +1166,7 @@ class GraphForward:
                                   q=w.q, scale_a=sa, scale_b=w.scale_b, silu=silu))
             return DynamicGroupGemm(ps, joint=range(E), rows_total=n, device=dev)
 
-        if ffn.gate_up_mode not in (None, "interleaved"):
-            raise ValueError(f"gate_up_mode must be None or 'interleaved', got {ffn.gate_up_mode!r}")
-        self.mode = "plain" if not ffn.fuse_silu else "interleaved" if ffn.gate_up_mode == "interleaved" else "fused"
+        self.mode = ffn.gate_up_layout()
         if ffn.biased_or_gated and self.mode != "plain":
             raise ValueError("a layer with a bias or another activation needs the plain gate_up layout")
         self._glu = _glu_struct(ffn.activation, ffn.b1, ffn.b1s) if ffn.biased_or_gated else None
@@ -1192,7 +1195,7 @@ class GraphForward:
                stream: Optional[torch.cuda.Stream] = None) -> torch.Tensor:
         """Launches only; returns ``self.out`` (fp16 [T, H]). A MoEFFN takes int32 ids and f32 weights [T, topk]
         (contiguous, as nothing may be converted here) and the optional f32 shared_w [T]; a MoEBlock routes itself."""
-        ffn, T, topk, lib = self.ffn, self.T, self.topk, nat.lib()
+        ffn, T, topk = self.ffn, self.T, self.topk
         if tuple(hidden.shape) != (T, ffn.H) or hidden.dtype != torch.float16 or not hidden.is_contiguous():
             raise ValueError(f"hidden must be a contiguous fp16 [{T}, {ffn.H}] tensor")
         if self.block is not None:
@@ -1210,39 +1213,17 @@ class GraphForward:
                     continue
                 if t is None or t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous():
                     raise ValueError(f"{what} must be a contiguous {dt} {list(shape)} tensor")
-        st = _stream(stream)
         sorted_e, perm, inv, counts = route_device(topk_ids, ffn.E, stream, out=self.route_bufs)
         shared = ffn.has_shared
-        nat.check(lib.mxmoe_moe_segments(_ptr(counts), ffn.E, T, topk, int(shared), self._tables, 2,
-                                         _ptr(self.seg_status), st))
-        if any(t in _MX_TAGS for t in ffn.tag1):
-            nat.check(lib.mxmoe_moe_act_quant(0, _ptr(hidden), _ptr(hidden) if shared else None, T, topk, ffn.H, ffn.H,
-                                              _ptr(sorted_e), _ptr(perm), _ptr(self.segs[0]), self.nseg, self.mask1,
-                                              _ptr(self.a1), _ptr(self.s1), st))
-        else:
-            nat.check(lib.mxmoe_moe_quant_act(_ptr(hidden), T, ffn.H, topk, int(shared), _ptr(sorted_e), _ptr(perm),
-                                              _ptr(self.segs[0]), self.nseg, _ptr(self.a1), _ptr(self.s1), st))
+        nat.check(nat.lib().mxmoe_moe_segments(_ptr(counts), ffn.E, T, topk, int(shared), self._tables, 2,
+                                               _ptr(self.seg_status), _stream(stream)))
+        _launch_act("gather", None, hidden, hidden if shared else None, T, topk, ffn.H, ffn.H, sorted_e, perm, self.segs[0],
+                    self.nseg, self.mask1, self.a1, self.s1, stream)
         self.g1.launch(self.dyn[0], stream)
-        mode = {"plain": 1, "fused": 2, "interleaved": 3}[self.mode]
-        if self._glu is not None:
-            nat.check(nat.symbol("mxmoe_moe_glu_quant")(ctypes.byref(self._glu), _ptr(self.h1), _ptr(self.h1s), T, topk, ffn.N,
-                                                        ffn.Ns, _ptr(sorted_e), _ptr(self.segs[1]), self.nseg, self.mask2,
-                                                        _ptr(self.a2), _ptr(self.s2), st))
-        elif any(t in _MX_TAGS for t in ffn.tag2):
-            nat.check(lib.mxmoe_moe_act_quant(mode, _ptr(self.h1), _ptr(self.h1s), T, topk, ffn.N, ffn.Ns, _ptr(sorted_e),
-                                              None, _ptr(self.segs[1]), self.nseg, self.mask2, _ptr(self.a2),
-                                              _ptr(self.s2), st))
-        else:
-            fn = (lib.mxmoe_moe_silu_mul_quant, lib.mxmoe_moe_quant_slots, lib.mxmoe_moe_silu_mul_quant_il)[mode - 1]
-            nat.check(fn(_ptr(self.h1), _ptr(self.h1s), T, topk, ffn.N, ffn.Ns, _ptr(sorted_e), _ptr(self.segs[1]),
-                         self.nseg, _ptr(self.a2), _ptr(self.s2), st))
+        _launch_act(self.mode, self._glu, self.h1, self.h1s, T, topk, ffn.N, ffn.Ns, sorted_e, None, self.segs[1],
+                    self.nseg, self.mask2, self.a2, self.s2, stream)
         self.g2.launch(self.dyn[1], stream)
-        if self._glu is not None:
-            combine_bias_into(self.out, self.y, inv, sorted_e, topk_weights, ffn.b2, self.ys, shared_w, ffn.b2s, topk, ffn.E,
-                              stream)
-        else:
-            nat.check(lib.mxmoe_moe_combine(_ptr(self.y), _ptr(inv), _ptr(topk_weights), _ptr(self.ys), _ptr(shared_w), T,
-                                            topk, ffn.H, _ptr(self.out), st))
+        _launch_combine(self.out, self.y, inv, sorted_e, topk_weights, self.ys, shared_w, topk, stream, ffn.down_bias)
         return self.out
 
     __call__ = launch

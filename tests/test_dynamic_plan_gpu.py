@@ -199,16 +199,28 @@ def test_layer_under_a_graph_float_experts():
     _replay_against_eager(block, hiddens, T_, exact=False)
 
 
-@pytest.mark.parametrize("T_", [1, 7])
-def test_ffn_with_caller_routing_at_decode_sizes(T_):
-    """GraphForward on a plain MoEFFN with the caller's ids and weights (most experts empty)."""
+# the gate_up layouts: (MoEFFN's fuse_silu, its gate_up_mode override, the modes GraphForward may end in)
+LAYOUTS = {"default": (None, None, ("fused", "interleaved")), "plain": (False, None, ("plain",)),
+           "interleaved": (None, "interleaved", ("interleaved",))}
+
+
+@pytest.mark.parametrize("T_, layout", [pytest.param(1, "default", id="1"), pytest.param(7, "default", id="7"),
+                                        pytest.param(7, "plain", id="7-plain"),
+                                        pytest.param(7, "interleaved", id="7-interleaved")])
+def test_ffn_with_caller_routing_at_decode_sizes(T_, layout):
+    """GraphForward on a plain MoEFFN with the caller's ids and weights (most experts empty), for every gate_up
+    layout: the three forwards (eager, planned, graph) give the same bits. The routed rows (N = 128) and the shared
+    rows (Ns = 256) differ in width, so the activation pass takes its routed / shared split."""
     topk, E_, H, N, Ns = 2, 4, 256, 128, 256
+    fuse, override, modes = LAYOUTS[layout]
     g = torch.Generator().manual_seed(300 + T_)
     mk = lambda n, k: ((torch.rand(n, k, generator=g) * 2 - 1) * 0.2).half().to(DEV)
     qcfg = [(W8A8, W8A8), (W4A4, W4A4), (W8A8, W8A8), (W4A4, W4A4), (W8A8, W8A8)]
     ffn = moe.MoEFFN([mk(2 * N, H) for _ in range(E_)] + [mk(2 * Ns, H)], [mk(H, N) for _ in range(E_)] + [mk(H, Ns)],
-                     qcfg, num_routed=E_)
+                     qcfg, num_routed=E_, fuse_silu=fuse)
+    ffn.gate_up_mode = override
     gf = moe.GraphForward(ffn, T_, topk)
+    assert gf.mode in modes
     for _ in range(2):  # two routings through the same plan
         ids = torch.stack([torch.randperm(E_, generator=g)[:topk] for _ in range(T_)]).to(torch.int32).to(DEV)
         wts = torch.softmax(torch.rand(T_, topk, generator=g), dim=1).to(DEV)
@@ -218,6 +230,15 @@ def test_ffn_with_caller_routing_at_decode_sizes(T_):
         want = ffn.forward(h, ids, wts, sw)
         torch.cuda.synchronize()
         assert torch.equal(got.view(torch.int16), want.view(torch.int16))
+        # a PlannedForward takes no shared_w (the shared expert at weight 1): the three forwards without it
+        pf = moe.PlannedForward(ffn, h, ids, wts)
+        assert pf.mode in modes
+        planned = pf().clone()
+        got = gf.launch(h, ids, wts).clone()
+        want = ffn.forward(h, ids, wts)
+        torch.cuda.synchronize()
+        assert torch.equal(got.view(torch.int16), want.view(torch.int16))
+        assert torch.equal(planned.view(torch.int16), want.view(torch.int16))
     assert gf.status() == 0
     with pytest.raises(ValueError):
         gf.launch(h, ids.long(), wts, sw)  # nothing may be converted under capture: the dtypes are the caller's

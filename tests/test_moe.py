@@ -51,6 +51,30 @@ def test_qtag_mapping_follows_reference():
         moe.qtag_of(8, 128)
 
 
+def test_activation_pass_entry_point_rule():
+    """The one rule every forward (eager, planned, graph) picks its activation-pass entry point by, as a table over
+    every (mode, has_mx_tag, glu): a glu struct needs mxmoe_moe_glu_quant and the plain layout, any MX tag the
+    tagged entry, everything else the mode's own entry (libraries from before the tagged one still have those)."""
+    modes = ["gather", "plain", "fused", "interleaved"]
+    assert [moe._ACT_MODES[m] for m in modes] == [0, 1, 2, 3]  # mxmoe_moe_act_quant's mode numbers (mxmoe_moe.h)
+    legacy = ["mxmoe_moe_quant_act", "mxmoe_moe_silu_mul_quant", "mxmoe_moe_quant_slots", "mxmoe_moe_silu_mul_quant_il"]
+    for mode, name in zip(modes, legacy):
+        assert moe._act_entry(mode, False, False) == name
+        assert moe._act_entry(mode, True, False) == "mxmoe_moe_act_quant"
+        for has_mx in (False, True):
+            if mode == "plain":
+                assert moe._act_entry(mode, has_mx, True) == "mxmoe_moe_glu_quant"
+            else:
+                with pytest.raises(ValueError, match="plain gate_up layout"):
+                    moe._act_entry(mode, has_mx, True)
+    for glu in (False, True):
+        with pytest.raises(ValueError):
+            moe._act_entry("scatter", False, glu)
+    # has_mx_tag as the launcher derives it from a tag mask
+    assert moe._MX_MASK == moe._tag_mask([moe.ACT_MXFP4, moe.ACT_MXFP8])
+    assert not moe._tag_mask([moe.ACT_FP16, moe.ACT_INT8, moe.ACT_INT4, moe.ACT_INT4_G128]) & moe._MX_MASK
+
+
 def test_abi_validation_without_gpu():
     lib = nat.lib()
     assert lib.mxmoe_moe_quant_act(None, 4, 100, 2, 0, None, None, None, 1, None, None, None) == nat.MXMOE_GG_ERR_INVALID
