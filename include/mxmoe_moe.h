@@ -124,7 +124,7 @@ int mxmoe_moe_gate(const void* hidden, const void* w_gate, const void* w_shared_
  * Limits: mxmoe_moe_gate's, and 1 <= n_group <= 8, E % n_group == 0, gs % 4 == 0 (gs = 20 works),
  * 1 <= topk_group <= n_group (so 1 when n_group is 1), topk <= topk_group * gs, group_top 1 or 2 and
  * <= gs, routed_scale finite, e_bias and scores 4-byte aligned. Anything else: MXMOE_GG_ERR_INVALID
- * (checked before any HIP call). E > 256 is out of scope. */
+ * (checked before any HIP call). E > 256: mxmoe_moe_gate_wide (without groups). */
 enum { MXMOE_GATE_SOFTMAX = 0, MXMOE_GATE_SIGMOID = 1 };
 int mxmoe_moe_gate_ex(const void* hidden, const void* w_gate, const void* w_shared_gate, int64_t T, int H, int E, int topk,
                       int renormalize, int scoring, const float* e_bias, int n_group, int topk_group, int group_top,
@@ -145,6 +145,29 @@ int mxmoe_moe_gate_ex2(const void* hidden, const void* w_gate, const void* w_sha
                        int renormalize, int scoring, const float* e_bias, int n_group, int topk_group, int group_top,
                        float routed_scale, const float* logit_bias, int32_t* topk_ids, float* topk_weights, float* shared_w,
                        float* logits, float* scores, void* stream);
+
+/* mxmoe_moe_gate_ex2 for layers with up to 512 experts (Kimi-K2: 384 experts, top-8, sigmoid scores + e_bias,
+ * renormalize, routed_scale; Qwen3-Next: 512 experts, top-10, softmax over the chosen ones, a shared-expert gate,
+ * i.e. 513 columns). One launch, no workspace, no allocation, no synchronisation; graph-capturable like the others.
+ * Replaces: nothing in the reference (no router kernel); the semantics are the models' public routing code.
+ *   Every argument and rule: mxmoe_moe_gate_ex2's — logits by fp16 MFMA with f32 accumulation, logit_bias, e_bias, the
+ *   scores and logits outputs, the shared-gate column outside the softmax and the selection, renormalize,
+ *   routed_scale. Selection: descending value over the whole row, ties (-0 == +0) to the lower expert index over the
+ *   whole row; a row of NaN or +-Inf still gets topk distinct ids in [0, E); rows past T are never written.
+ *   E <= 256: the call IS mxmoe_moe_gate_ex2 (the same kernels, byte-identical outputs; groups allowed).
+ *   E > 256: a kernel of another form (mxmoe_amd/csrc/moe_gate_wide.h): the columns are split into slices that
+ *   different waves finish, and the slices' sorted candidates are merged by (value descending, index ascending).
+ *   The f32 sum of the softmax over all E experts (renormalize == 0) adds per-slice sums in slice order, so weights
+ *   may differ from a single-slice sum in the last bits (never from run to run).
+ * Limits: mxmoe_moe_gate_ex2's with 1 <= E <= 512. For E > 256, n_group, topk_group and group_top must all be 1:
+ * group-limited routing across column slices is deliberately left out (no known model with more than 256 experts
+ * routes group-limited); E need then be no multiple of 4 (that rule serves the group stage). E > 512, topk > 16 and bf16 hidden states are out of scope. Anything else:
+ * MXMOE_GG_ERR_INVALID under this entry point's name (checked before any HIP call). T == 0: OK, no launch.
+ * mxmoe_moe_gate, mxmoe_moe_gate_ex and mxmoe_moe_gate_ex2 keep their E <= 256 limit and their kernels. */
+int mxmoe_moe_gate_wide(const void* hidden, const void* w_gate, const void* w_shared_gate, int64_t T, int H, int E, int topk,
+                        int renormalize, int scoring, const float* e_bias, int n_group, int topk_group, int group_top,
+                        float routed_scale, const float* logit_bias, int32_t* topk_ids, float* topk_weights, float* shared_w,
+                        float* logits, float* scores, void* stream);
 
 /* Stable counting sort of the T*topk expert ids (int32, row-major [T][topk], values in [0, E)):
  *   sorted_expert[s] = expert of slot s (non-decreasing), perm_token[s] = source token of slot s,

@@ -101,9 +101,13 @@ EXPORTED_SYMBOLS = (
     "mxmoe_moe_gate", "mxmoe_moe_gate_ex",
     # gpt-oss layers: router logit bias, biased / clamped gated activation, combine with a down bias
     "mxmoe_moe_gate_ex2", "mxmoe_moe_glu_quant", "mxmoe_moe_combine_bias",
+    # the router for 257 .. 512 experts
+    "mxmoe_moe_gate_wide",
 )
 # added to ABI 7 without a version bump (additive): a product library without them is a stale build
 GPTOSS_SYMBOLS = ("mxmoe_moe_gate_ex2", "mxmoe_moe_glu_quant", "mxmoe_moe_combine_bias")
+# added the same way after them: bound where present, ``symbol`` refuses the call where a build lacks it
+WIDE_GATE_SYMBOLS = ("mxmoe_moe_gate_wide",)
 GLU_SILU, GLU_SWIGLU_CLAMP = 0, 1  # MXMOE_GLU_* (include/mxmoe_moe.h)
 
 
@@ -256,6 +260,10 @@ def _declare(lib: ctypes.CDLL) -> None:
                                             c.c_uint32, P, P, P]
         lib.mxmoe_moe_combine_bias.restype = c.c_int
         lib.mxmoe_moe_combine_bias.argtypes = [P, P, P, P, P, P, P, P, c.c_int64, c.c_int, c.c_int, c.c_int, P, P]
+    if all(hasattr(lib, fn) for fn in WIDE_GATE_SYMBOLS):  # (builds before the wide router lack it: A/B tools)
+        lib.mxmoe_moe_gate_wide.restype = c.c_int
+        lib.mxmoe_moe_gate_wide.argtypes = [P, P, P, c.c_int64, c.c_int, c.c_int, c.c_int, c.c_int, c.c_int, P, c.c_int,
+                                            c.c_int, c.c_int, c.c_float, P, P, P, P, P, P, P]
 
 
 def lib() -> ctypes.CDLL:

@@ -16,7 +16,8 @@
 // (mxmoe_moe_glu_quant: the GLU builds of act_quant_kernel), the combine with a bias row per expert
 // (mxmoe_moe_combine_bias), the router with a bias on its logits (mxmoe_moe_gate_ex2); no reference counterpart.
 // The router in front of them (mxmoe_moe_gate: logits on the MFMA, top-k, softmax; mxmoe_moe_gate_ex:
-// sigmoid scores, selection bias, group-limited top-k) is moe_gate.h.
+// sigmoid scores, selection bias, group-limited top-k) is moe_gate.h; beyond 256 experts (mxmoe_moe_gate_wide),
+// moe_gate_wide.h.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -27,6 +28,7 @@
 #include "../../include/mxmoe_gg.h"
 #include "../../include/mxmoe_moe.h"
 #include "moe_gate.h"
+#include "moe_gate_wide.h"
 #define MXMOE_DYN_KERNEL  // gg_dyn.h: the GroupGEMM's device tile planner kernel is compiled here
 #include "gg_dyn.h"
 
@@ -794,11 +796,12 @@ static int combine_check(const char* fn, const void* y, const int32_t* inv_slot,
 
 // what mxmoe_moe_gate and mxmoe_moe_gate_ex check alike, before any HIP call
 static int gate_check(const char* fn, const void* hidden, const void* w_gate, const void* w_shared_gate, int64_t T, int H,
-                      int E, int topk, const int32_t* topk_ids, const float* topk_weights, const float* shared_w) {
-  if (T < 0 || E < 1 || E > 256 || topk < 1 || topk > 16 || topk > E || H <= 0 || H % 32 ||
+                      int E, int topk, const int32_t* topk_ids, const float* topk_weights, const float* shared_w,
+                      int max_e = 256) {
+  if (T < 0 || E < 1 || E > max_e || topk < 1 || topk > 16 || topk > E || H <= 0 || H % 32 ||
       T * topk > (int64_t)1 << 30)
-    return fail(MXMOE_GG_ERR_INVALID, "%s: need T >= 0, 1 <= E <= 256, 1 <= topk <= min(E, 16), H %% 32 == 0, "
-                "T * topk <= 2^30 (T=%lld H=%d E=%d topk=%d)", fn, (long long)T, H, E, topk);
+    return fail(MXMOE_GG_ERR_INVALID, "%s: need T >= 0, 1 <= E <= %d, 1 <= topk <= min(E, 16), H %% 32 == 0, "
+                "T * topk <= 2^30 (T=%lld H=%d E=%d topk=%d)", fn, max_e, (long long)T, H, E, topk);
   if ((w_shared_gate != nullptr) != (shared_w != nullptr))
     return fail(MXMOE_GG_ERR_INVALID, "%s: w_shared_gate and shared_w must be given together", fn);
   if (!aligned16(hidden) || !aligned16(w_gate) || !aligned16(w_shared_gate))
@@ -810,13 +813,17 @@ static int gate_check(const char* fn, const void* hidden, const void* w_gate, co
 static int gate_ex_impl(const char* fn, const void* hidden, const void* w_gate, const void* w_shared_gate, int64_t T, int H,
                         int E, int topk, int renormalize, int scoring, const float* e_bias, int n_group, int topk_group,
                         int group_top, float routed_scale, const float* logit_bias, int32_t* topk_ids, float* topk_weights,
-                        float* shared_w, float* logits, float* scores, void* stream) {
+                        float* shared_w, float* logits, float* scores, void* stream, int max_e = 256) {
   if (scoring != MXMOE_GATE_SOFTMAX && scoring != MXMOE_GATE_SIGMOID)
     return fail(MXMOE_GG_ERR_INVALID, "%s: scoring must be MXMOE_GATE_SOFTMAX or MXMOE_GATE_SIGMOID (got %d)", fn, scoring);
-  const int st = gate_check(fn, hidden, w_gate, w_shared_gate, T, H, E, topk, topk_ids, topk_weights, shared_w);
+  const int st = gate_check(fn, hidden, w_gate, w_shared_gate, T, H, E, topk, topk_ids, topk_weights, shared_w, max_e);
   if (st != MXMOE_GG_OK) return st;
-  if (n_group < 1 || n_group > 8 || E % n_group || (E / n_group) % 4 || topk_group < 1 || topk_group > n_group ||
-      (int64_t)topk > (int64_t)topk_group * (E / n_group))
+  if (E > 256 && (n_group != 1 || topk_group != 1 || group_top != 1))  // (mxmoe_moe_gate_wide only: max_e)
+    return fail(MXMOE_GG_ERR_INVALID, "%s: E > 256 routes without groups: n_group, topk_group and group_top must be 1 "
+                "(E=%d n_group=%d topk_group=%d group_top=%d)", fn, E, n_group, topk_group, group_top);
+  // ((E / n_group) % 4 serves the group stage's register layout; the kernel for E > 256 has none and takes any E)
+  if (n_group < 1 || n_group > 8 || E % n_group || (E <= 256 && (E / n_group) % 4) || topk_group < 1 ||
+      topk_group > n_group || (int64_t)topk > (int64_t)topk_group * (E / n_group))
     return fail(MXMOE_GG_ERR_INVALID, "%s: need 1 <= n_group <= 8, E %% n_group == 0, (E / n_group) %% 4 == 0, "
                 "1 <= topk_group <= n_group (1 without groups), topk <= topk_group * E / n_group "
                 "(E=%d topk=%d n_group=%d topk_group=%d)", fn, E, topk, n_group, topk_group);
@@ -832,10 +839,12 @@ static int gate_ex_impl(const char* fn, const void* hidden, const void* w_gate, 
                               static_cast<const _Float16*>(w_shared_gate), T, H, E, topk, renormalize != 0, topk_ids,
                               topk_weights, shared_w, logits},
                              e_bias, scores, n_group, topk_group, group_top, routed_scale};
-  if (logit_bias) gate::gate_modes_launch(gate::GateBiasArgs{m, logit_bias}, scoring == MXMOE_GATE_SIGMOID, (hipStream_t)stream);
+  if (E > 256) gate::gate_wide_launch(gate::GateBiasArgs{m, logit_bias}, scoring == MXMOE_GATE_SIGMOID, (hipStream_t)stream);
+  else if (logit_bias) gate::gate_modes_launch(gate::GateBiasArgs{m, logit_bias}, scoring == MXMOE_GATE_SIGMOID, (hipStream_t)stream);
   else gate::gate_modes_launch(m, scoring == MXMOE_GATE_SIGMOID, (hipStream_t)stream);
   const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(MXMOE_GG_ERR_HIP, "gate_modes_kernel launch failed: %s", hipGetErrorString(e));
+  if (e != hipSuccess)
+    return fail(MXMOE_GG_ERR_HIP, "%s launch failed: %s", E > 256 ? "gate_wide_kernel" : "gate_modes_kernel", hipGetErrorString(e));
   return MXMOE_GG_OK;
 }
 
@@ -870,6 +879,16 @@ int mxmoe_moe_gate_ex2(const void* hidden, const void* w_gate, const void* w_sha
   return gate_ex_impl("mxmoe_moe_gate_ex2", hidden, w_gate, w_shared_gate, T, H, E, topk, renormalize, scoring, e_bias,
                       n_group, topk_group, group_top, routed_scale, logit_bias, topk_ids, topk_weights, shared_w, logits,
                       scores, stream);
+}
+
+int mxmoe_moe_gate_wide(const void* hidden, const void* w_gate, const void* w_shared_gate, int64_t T, int H, int E, int topk,
+                        int renormalize, int scoring, const float* e_bias, int n_group, int topk_group, int group_top,
+                        float routed_scale, const float* logit_bias, int32_t* topk_ids, float* topk_weights, float* shared_w,
+                        float* logits, float* scores, void* stream) {
+  // E <= 256: mxmoe_moe_gate_ex2's path and kernels; beyond, gate_wide_kernel (moe_gate_wide.h)
+  return gate_ex_impl("mxmoe_moe_gate_wide", hidden, w_gate, w_shared_gate, T, H, E, topk, renormalize, scoring, e_bias,
+                      n_group, topk_group, group_top, routed_scale, logit_bias, topk_ids, topk_weights, shared_w, logits,
+                      scores, stream, gate::kGateWideMaxExperts);
 }
 
 int mxmoe_moe_route(const int32_t* topk_ids, int64_t T, int topk, int E, int32_t* sorted_expert,

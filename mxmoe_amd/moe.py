@@ -100,6 +100,8 @@ class Routing:
 
 
 GATE_SCORING = {"softmax": 0, "sigmoid": 1}  # MXMOE_GATE_SOFTMAX / MXMOE_GATE_SIGMOID (include/mxmoe_moe.h)
+# beyond GATE_GROUPS_MAX_E experts the router is mxmoe_moe_gate_wide's kernel: up to GATE_MAX_E, one group
+GATE_GROUPS_MAX_E, GATE_MAX_E = 256, 512
 
 
 def gate_routing_args(E: int, topk: int, scoring: str = "softmax", e_bias: Optional[torch.Tensor] = None,
@@ -110,7 +112,13 @@ def gate_routing_args(E: int, topk: int, scoring: str = "softmax", e_bias: Optio
     if scoring not in GATE_SCORING:
         raise ValueError(f"scoring must be 'softmax' or 'sigmoid', got {scoring!r}")
     n_group, topk_group = int(n_group), int(topk_group)
-    if not 1 <= n_group <= 8 or E % n_group or (E // n_group) % 4:
+    if E > GATE_MAX_E:
+        raise ValueError(f"the router takes at most {GATE_MAX_E} experts, got E = {E}")
+    if E > GATE_GROUPS_MAX_E and n_group > 1:
+        raise ValueError(f"group-limited routing needs E <= {GATE_GROUPS_MAX_E} (mxmoe_moe_gate_wide routes without "
+                         f"groups), got E = {E}, n_group = {n_group}")
+    # (a multiple of 4 experts per group: the group stage's layout, which the kernel for E > 256 does not have)
+    if not 1 <= n_group <= 8 or E % n_group or (E <= GATE_GROUPS_MAX_E and (E // n_group) % 4):
         raise ValueError(f"n_group must be in [1, 8] and split E = {E} into groups of a multiple of 4 experts, got {n_group}")
     gs = E // n_group
     if not 1 <= topk_group <= n_group:
@@ -119,8 +127,9 @@ def gate_routing_args(E: int, topk: int, scoring: str = "softmax", e_bias: Optio
         raise ValueError(f"topk = {topk} exceeds the {topk_group * gs} experts of {topk_group} kept groups")
     if group_top is None:
         group_top = 2 if scoring == "sigmoid" and n_group > 1 else 1
-    if group_top not in (1, 2) or group_top > gs:
-        raise ValueError(f"group_top must be 1 or 2 and at most the group size {gs}, got {group_top}")
+    if group_top not in (1, 2) or group_top > gs or (E > GATE_GROUPS_MAX_E and group_top != 1):
+        raise ValueError(f"group_top must be 1 or 2 and at most the group size {gs} (1 for E > {GATE_GROUPS_MAX_E}), "
+                         f"got {group_top}")
     if scoring == "softmax" and (e_bias is not None or group_top != 1 or return_scores):
         raise ValueError("softmax scoring takes no e_bias, no return_scores and group_top = 1")
     if e_bias is not None and (e_bias.dtype != torch.float32 or not e_bias.is_contiguous() or tuple(e_bias.shape) != (E,)):
@@ -165,7 +174,11 @@ def gate(hidden: torch.Tensor, w_gate: torch.Tensor, topk: int, *, renormalize: 
 
     ``logit_bias`` (f32 [E]; mxmoe_moe_gate_ex2): added to the logits before everything else — the returned
     logits, the selection and the weights all see the sum (the shared gate does not). gpt-oss:
-    ``renormalize=True, logit_bias=router.bias`` (top-k on the biased logits, softmax over the chosen ones)."""
+    ``renormalize=True, logit_bias=router.bias`` (top-k on the biased logits, softmax over the chosen ones).
+
+    More than 256 experts (up to 512; mxmoe_moe_gate_wide, still one launch): every rule above except the groups
+    (``n_group`` must be 1). Kimi-K2: E 384, ``scoring="sigmoid", e_bias, renormalize=True,
+    routed_scaling_factor=2.827``; Qwen3-Next: E 512, ``renormalize=True, w_shared_gate``."""
     if hidden.dim() != 2 or hidden.dtype != torch.float16 or not hidden.is_contiguous():
         raise ValueError("hidden must be a contiguous fp16 [T, H] tensor")
     T, H = hidden.shape
@@ -196,8 +209,9 @@ def gate(hidden: torch.Tensor, w_gate: torch.Tensor, topk: int, *, renormalize: 
     ids, wts, sw = out[:3]
     logits = out[3] if return_logits else None
     scores = out[-1] if return_scores else None
-    if logit_bias is not None:
-        nat.check(nat.symbol("mxmoe_moe_gate_ex2")(
+    if E > GATE_GROUPS_MAX_E or logit_bias is not None:
+        fn = "mxmoe_moe_gate_wide" if E > GATE_GROUPS_MAX_E else "mxmoe_moe_gate_ex2"
+        nat.check(nat.symbol(fn)(
             _ptr(hidden), _ptr(w_gate), _ptr(sg), T, H, E, topk, int(bool(renormalize)), GATE_SCORING[scoring], _ptr(e_bias),
             int(n_group), int(topk_group), group_top, float(routed_scaling_factor), _ptr(logit_bias), _ptr(ids), _ptr(wts),
             _ptr(sw), _ptr(logits), _ptr(scores), _stream(stream)))
@@ -1541,7 +1555,13 @@ GATE_MODELS = {"qwen2_moe": dict(H=2048, E=60, topk=4, shared_gate=True),
                            routing=dict(scoring="sigmoid", n_group=8, topk_group=4, routed_scaling_factor=2.5)),
                "ds2_full": dict(H=5120, E=160, topk=6, shared_gate=False,
                                 routing=dict(scoring="softmax", n_group=8, topk_group=3, group_top=1,
-                                             routed_scaling_factor=16.0))}
+                                             routed_scaling_factor=16.0)),
+               # more than 256 experts (mxmoe_moe_gate_wide): Kimi-K2 (sigmoid + bias, one group) and Qwen3-Next
+               # (softmax over the chosen ones, shared-expert gate: 513 columns)
+               "kimi_k2": dict(H=7168, E=384, topk=8, shared_gate=False, renormalize=True, bias=True,
+                               routing=dict(scoring="sigmoid", routed_scaling_factor=2.827)),
+               "qwen3_next": dict(H=2048, E=512, topk=10, shared_gate=True, renormalize=True,
+                                  routing=dict(scoring="softmax"))}
 HBM_ROOF_BYTES_PER_S = 8e12  # MI355X
 
 
@@ -1591,7 +1611,9 @@ def gate_bench(bs: int = 8192, model: str = "qwen2_moe", rounds: int = 4, iters:
     spread (max - min) / median; the kernel's algorithmic bytes and fraction of the HBM roof.
     model: "qwen2_moe" (H 2048, E 60, top-4, shared gate), "ds2" (DeepSeek-V2-Lite: E 64, top-6),
     "ds3" (DeepSeek-V3: H 7168, E 256, top-8, 8 groups / 4 kept, sigmoid + bias, renormalised, factor
-    2.5) or "ds2_full" (DeepSeek-V2: H 5120, E 160, top-6, 8 groups / 3 kept, softmax, factor 16)."""
+    2.5), "ds2_full" (DeepSeek-V2: H 5120, E 160, top-6, 8 groups / 3 kept, softmax, factor 16), "kimi_k2"
+    (H 7168, E 384, top-8, sigmoid + bias, renormalised, factor 2.827) or "qwen3_next" (H 2048, E 512, top-10,
+    softmax renormalised, shared gate)."""
     from .harness import time_launches
 
     m = GATE_MODELS[model]

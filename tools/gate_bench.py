@@ -1,5 +1,5 @@
 """Print mxmoe_amd.moe.gate_bench (the router kernel against the torch composite) as JSON lines:
-    python tools/gate_bench.py [--bs 8192 128] [--models qwen2_moe ds2 ds3 ds2_full] [--out FILE]"""
+    python tools/gate_bench.py [--bs 8192 128] [--models qwen2_moe ds2 ds3 ds2_full kimi_k2 qwen3_next] [--out FILE]"""
 from __future__ import annotations
 
 import argparse
@@ -15,7 +15,8 @@ from mxmoe_amd.moe import gate_bench  # noqa: E402
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--bs", type=int, nargs="+", default=[8192, 128])
-    ap.add_argument("--models", nargs="+", default=["qwen2_moe", "ds2"])
+    ap.add_argument("--models", nargs="+", default=["qwen2_moe", "ds2"],
+                    help="qwen2_moe ds2 ds3 ds2_full kimi_k2 qwen3_next (mxmoe_amd.moe.GATE_MODELS)")
     ap.add_argument("--rounds", type=int, default=4)
     ap.add_argument("--iters", type=int, default=30)
     ap.add_argument("--out", default=None, help="also write the list of results to this JSON file")
