@@ -161,13 +161,36 @@ int mxmoe_moe_gate_ex2(const void* hidden, const void* w_gate, const void* w_sha
  *   may differ from a single-slice sum in the last bits (never from run to run).
  * Limits: mxmoe_moe_gate_ex2's with 1 <= E <= 512. For E > 256, n_group, topk_group and group_top must all be 1:
  * group-limited routing across column slices is deliberately left out (no known model with more than 256 experts
- * routes group-limited); E need then be no multiple of 4 (that rule serves the group stage). E > 512, topk > 16 and bf16 hidden states are out of scope. Anything else:
+ * routes group-limited); E need then be no multiple of 4 (that rule serves the group stage). E > 512 and topk > 16 are out
+ * of scope; bf16 operands: mxmoe_moe_gate_dt. Anything else:
  * MXMOE_GG_ERR_INVALID under this entry point's name (checked before any HIP call). T == 0: OK, no launch.
  * mxmoe_moe_gate, mxmoe_moe_gate_ex and mxmoe_moe_gate_ex2 keep their E <= 256 limit and their kernels. */
 int mxmoe_moe_gate_wide(const void* hidden, const void* w_gate, const void* w_shared_gate, int64_t T, int H, int E, int topk,
                         int renormalize, int scoring, const float* e_bias, int n_group, int topk_group, int group_top,
                         float routed_scale, const float* logit_bias, int32_t* topk_ids, float* topk_weights, float* shared_w,
                         float* logits, float* scores, void* stream);
+
+/* Element types of the entry points that take one (the *_dt / gather entries below). Every other entry is fp16. */
+enum { MXMOE_DT_FP16 = 0, MXMOE_DT_BF16 = 1 };
+
+/* mxmoe_moe_gate_wide with the operands' element type as an argument: the router of a bf16 model, with no cast pass.
+ * Replaces: nothing in the reference (no router kernel, fp16 only).
+ *   dtype    MXMOE_DT_FP16: the call IS mxmoe_moe_gate_wide (the same kernels, byte-identical outputs).
+ *            MXMOE_DT_BF16: hidden, w_gate and w_shared_gate are bf16 (all three: one dtype per call). The logits are
+ *            x[e] = sum_h f32(hidden[t][h]) * f32(w_gate[e][h]) on v_mfma_f32_16x16x32_bf16: every product of two bf16
+ *            values is exact in f32, the accumulation is f32 in the kernel's own order. The operands are NOT converted
+ *            to fp16 on the way: a weight below 2^-14 or a hidden value above 65504 keeps its value. Everything after
+ *            the logits — logit_bias, selection, softmax / sigmoid, groups, e_bias, renormalize, routed_scale, the
+ *            shared-expert gate, the logits / scores outputs — is the fp16 kernels' code, unchanged; so are the launch
+ *            forms (rows per workgroup, K split, column slices beyond 256 experts).
+ *   Every other argument, rule and limit: mxmoe_moe_gate_wide's (1 <= E <= 512; groups up to 256 experts), checked
+ *   before any HIP call and reported under this entry point's name; an unknown dtype: MXMOE_GG_ERR_INVALID.
+ * A call with every rule at its default (mxmoe_moe_gate's) runs the softmax build of mxmoe_moe_gate_ex's kernel with
+ * routed_scale 1.0: there is no bf16 build of mxmoe_moe_gate's own kernel. */
+int mxmoe_moe_gate_dt(int dtype, const void* hidden, const void* w_gate, const void* w_shared_gate, int64_t T, int H, int E,
+                      int topk, int renormalize, int scoring, const float* e_bias, int n_group, int topk_group, int group_top,
+                      float routed_scale, const float* logit_bias, int32_t* topk_ids, float* topk_weights, float* shared_w,
+                      float* logits, float* scores, void* stream);
 
 /* Stable counting sort of the T*topk expert ids (int32, row-major [T][topk], values in [0, E)):
  *   sorted_expert[s] = expert of slot s (non-decreasing), perm_token[s] = source token of slot s,
@@ -218,6 +241,22 @@ int mxmoe_moe_segments_host(const int32_t* counts, int E, int64_t T, int topk, i
 int mxmoe_moe_quant_act(const void* hidden, int64_t T, int K, int topk, int with_shared,
                         const int32_t* sorted_expert, const int32_t* perm_token, const mxmoe_moe_seg* segs, int nseg,
                         void* out, void* scales, void* stream);
+
+/* mxmoe_moe_quant_act with the element type of hidden as an argument and mxmoe_moe_act_quant's tag_mask (bits 4 / 6
+ * select the builds that carry MXMOE_ACT_MXFP4 / MXMOE_ACT_MXFP8; an unknown bit: MXMOE_GG_ERR_UNSUPPORTED).
+ * Replaces: nothing in the reference (fp16 only).
+ *   dtype    MXMOE_DT_FP16: mxmoe_moe_quant_act's (mxmoe_moe_act_quant mode 0's) kernels and bytes.
+ *            MXMOE_DT_BF16: hidden is bf16 [T][K]. Each element is converted to fp16 as it is loaded — widened to f32
+ *            (exact), then rounded once to fp16 to nearest even; beyond fp16's range +-Inf; the fp16-subnormal range
+ *            is rounded, not flushed: the value hidden.to(torch.float16) holds — and from there the pass is the fp16
+ *            one for every tag: out and scales equal, byte for byte, what the fp16 pass writes for the converted
+ *            hidden. The experts therefore still compute on fp16 values: bf16's range is not kept past this pass.
+ *            NaN payloads are unspecified.
+ * Only the gather reads bf16: the gate_up output the other activation passes read stays fp16.
+ * Other arguments and limits: mxmoe_moe_quant_act's; an unknown dtype: MXMOE_GG_ERR_INVALID. */
+int mxmoe_moe_gather_quant(int dtype, const void* hidden, int64_t T, int K, int topk, int with_shared,
+                           const int32_t* sorted_expert, const int32_t* perm_token, const mxmoe_moe_seg* segs, int nseg,
+                           uint32_t tag_mask, void* out, void* scales, void* stream);
 
 /* act = fp16_rn(silu(f32 g) * f32 u) of the gate_up output (silu(g) = g * rcp(1 + exp2(-g log2 e)) with
  * the hardware exp2 / reciprocal), then quantised as mxmoe_moe_quant_act.
@@ -299,6 +338,16 @@ int mxmoe_moe_glu_quant(const mxmoe_moe_glu* glu, const void* routed_in, const v
 int mxmoe_moe_combine_bias(const void* y, const int32_t* inv_slot, const int32_t* sorted_expert, const float* weights,
                            const void* bias, const void* shared, const float* shared_w, const void* shared_bias, int64_t T,
                            int topk, int E, int H, void* out, void* stream);
+
+/* mxmoe_moe_combine_bias with the output's element type as an argument: the f32 accumulator of the same fma chain
+ * (y, bias, shared and shared_bias stay fp16) is rounded once to out_dtype, to nearest even — MXMOE_DT_BF16: out is
+ * bf16 [T][H] (v_cvt_pk_bf16_f32); MXMOE_DT_FP16: mxmoe_moe_combine_bias's output bit for bit.
+ * sorted_expert, bias and shared_bias may be NULL (sorted_expert is required with a bias); with bias and shared_bias
+ * both NULL the arithmetic is mxmoe_moe_combine's (and its kernel runs). Other arguments and limits:
+ * mxmoe_moe_combine_bias's; an unknown out_dtype: MXMOE_GG_ERR_INVALID. (No reference counterpart.) */
+int mxmoe_moe_combine_dt(int out_dtype, const void* y, const int32_t* inv_slot, const int32_t* sorted_expert,
+                         const float* weights, const void* bias, const void* shared, const float* shared_w,
+                         const void* shared_bias, int64_t T, int topk, int E, int H, void* out, void* stream);
 
 /* out[t][h] = fp16_rn(acc), acc = +0 then, for k = 0..topk-1 in order,
  *   acc = fma(weights[t][k], f32(y[inv_slot[t*topk + k]][h]), acc),

@@ -103,11 +103,15 @@ EXPORTED_SYMBOLS = (
     "mxmoe_moe_gate_ex2", "mxmoe_moe_glu_quant", "mxmoe_moe_combine_bias",
     # the router for 257 .. 512 experts
     "mxmoe_moe_gate_wide",
+    # bf16 layers: the router, the gather and the combine with the element type as an argument
+    "mxmoe_moe_gate_dt", "mxmoe_moe_gather_quant", "mxmoe_moe_combine_dt",
 )
 # added to ABI 7 without a version bump (additive): a product library without them is a stale build
 GPTOSS_SYMBOLS = ("mxmoe_moe_gate_ex2", "mxmoe_moe_glu_quant", "mxmoe_moe_combine_bias")
 # added the same way after them: bound where present, ``symbol`` refuses the call where a build lacks it
 WIDE_GATE_SYMBOLS = ("mxmoe_moe_gate_wide",)
+DT_SYMBOLS = ("mxmoe_moe_gate_dt", "mxmoe_moe_gather_quant", "mxmoe_moe_combine_dt")  # (likewise: the bf16 layers)
+DT_FP16, DT_BF16 = 0, 1  # MXMOE_DT_* (include/mxmoe_moe.h)
 GLU_SILU, GLU_SWIGLU_CLAMP = 0, 1  # MXMOE_GLU_* (include/mxmoe_moe.h)
 
 
@@ -264,6 +268,14 @@ def _declare(lib: ctypes.CDLL) -> None:
         lib.mxmoe_moe_gate_wide.restype = c.c_int
         lib.mxmoe_moe_gate_wide.argtypes = [P, P, P, c.c_int64, c.c_int, c.c_int, c.c_int, c.c_int, c.c_int, P, c.c_int,
                                             c.c_int, c.c_int, c.c_float, P, P, P, P, P, P, P]
+    if all(hasattr(lib, fn) for fn in DT_SYMBOLS):  # (builds before the bf16 layers lack them: A/B tools)
+        lib.mxmoe_moe_gate_dt.restype = c.c_int
+        lib.mxmoe_moe_gate_dt.argtypes = [c.c_int] + lib.mxmoe_moe_gate_wide.argtypes
+        lib.mxmoe_moe_gather_quant.restype = c.c_int
+        lib.mxmoe_moe_gather_quant.argtypes = [c.c_int, P, c.c_int64, c.c_int, c.c_int, c.c_int, P, P, P, c.c_int, c.c_uint32,
+                                               P, P, P]
+        lib.mxmoe_moe_combine_dt.restype = c.c_int
+        lib.mxmoe_moe_combine_dt.argtypes = [c.c_int] + lib.mxmoe_moe_combine_bias.argtypes
 
 
 def lib() -> ctypes.CDLL:

@@ -31,9 +31,15 @@ namespace gate {
 
 typedef _Float16 gh8_t __attribute__((ext_vector_type(8)));
 typedef float gf4_t __attribute__((ext_vector_type(4)));
+typedef __bf16 gb8_t __attribute__((ext_vector_type(8)));
+
+// The bf16 builds (BF, mxmoe_moe_gate_dt): the 16 bytes of each fragment are 8 bf16 values — the builds keep the
+// fp16-typed pointers and fragment registers, so their loads and address arithmetic are the fp16 builds' own — and go
+// to v_mfma_f32_16x16x32_bf16, whose operand and accumulator layout is the f16 form's. A product of two bf16 values
+// (8-bit significands) is exact in f32; the accumulation is the MFMA's f32.
 
 struct GateArgs {
-  const _Float16* hidden;    // [T][H]
+  const _Float16* hidden;    // [T][H]   (the bf16 builds: bf16 bit patterns, all three operands alike)
   const _Float16* w_gate;    // [E][H]
   const _Float16* w_shared;  // [H] or NULL
   int64_t T;
@@ -206,10 +212,12 @@ __global__ __launch_bounds__(64 * NW) void gate_kernel(GateArgs a) {
   constexpr int MODE = kGatePlain;
   const GateModeArgs* const ex = nullptr;
   constexpr bool LB = false;
+  constexpr bool BF = false;  // (a bf16 call with every rule at its default runs gate_modes_kernel: mxmoe_moe_gate_dt)
   const float* const lbias = nullptr;
 #include "moe_gate_body.inc"
 }
-template <int NB, int MR, int NW, int U, int MODE>
+// BF (here and in gate_bias_kernel): the bf16 builds (mxmoe_moe_gate_dt); BF = false is the fp16 kernel as it was
+template <int NB, int MR, int NW, int U, int MODE, bool BF = false>
 __global__ __launch_bounds__(64 * NW) void gate_modes_kernel(GateModeArgs mm) {
   static_assert(MODE == kGateSoftmaxEx || MODE == kGateSigmoidEx, "an mxmoe_moe_gate_ex mode");
   const GateArgs& a = mm.g;
@@ -220,7 +228,7 @@ __global__ __launch_bounds__(64 * NW) void gate_modes_kernel(GateModeArgs mm) {
 }
 // gate_modes_kernel with the logit bias (mxmoe_moe_gate_ex2 with a non-NULL logit_bias): builds of their own, so
 // the two kernels above keep their code and registers
-template <int NB, int MR, int NW, int U, int MODE>
+template <int NB, int MR, int NW, int U, int MODE, bool BF = false>
 __global__ __launch_bounds__(64 * NW) void gate_bias_kernel(GateBiasArgs bb) {
   static_assert(MODE == kGateSoftmaxEx || MODE == kGateSigmoidEx, "an mxmoe_moe_gate_ex mode");
   const GateArgs& a = bb.m.g;
@@ -296,45 +304,46 @@ inline void gate_launch(const GateArgs& a, hipStream_t st) {
 
 // gate_modes_kernel: gate_kernel's forms (the same NW, U and rows per workgroup by T), and a 16-block
 // form for 256 experts without a shared gate
-template <int NB, int MR, int NW, int U>
+template <int NB, int MR, int NW, int U, bool BF>
 inline void gate_modes_launch_one(const GateModeArgs& m, bool sigmoid, hipStream_t st) {
   const dim3 blocks((unsigned)((m.g.T + 16 * MR - 1) / (16 * MR))), threads(64 * NW);
-  if (sigmoid) hipLaunchKernelGGL((gate_modes_kernel<NB, MR, NW, U, kGateSigmoidEx>), blocks, threads, 0, st, m);
-  else hipLaunchKernelGGL((gate_modes_kernel<NB, MR, NW, U, kGateSoftmaxEx>), blocks, threads, 0, st, m);
+  if (sigmoid) hipLaunchKernelGGL((gate_modes_kernel<NB, MR, NW, U, kGateSigmoidEx, BF>), blocks, threads, 0, st, m);
+  else hipLaunchKernelGGL((gate_modes_kernel<NB, MR, NW, U, kGateSoftmaxEx, BF>), blocks, threads, 0, st, m);
 }
-template <int NB, int MR, int NW, int U>
+template <int NB, int MR, int NW, int U, bool BF>
 inline void gate_modes_launch_one(const GateBiasArgs& b, bool sigmoid, hipStream_t st) {
   const dim3 blocks((unsigned)((b.m.g.T + 16 * MR - 1) / (16 * MR))), threads(64 * NW);
-  if (sigmoid) hipLaunchKernelGGL((gate_bias_kernel<NB, MR, NW, U, kGateSigmoidEx>), blocks, threads, 0, st, b);
-  else hipLaunchKernelGGL((gate_bias_kernel<NB, MR, NW, U, kGateSoftmaxEx>), blocks, threads, 0, st, b);
+  if (sigmoid) hipLaunchKernelGGL((gate_bias_kernel<NB, MR, NW, U, kGateSigmoidEx, BF>), blocks, threads, 0, st, b);
+  else hipLaunchKernelGGL((gate_bias_kernel<NB, MR, NW, U, kGateSoftmaxEx, BF>), blocks, threads, 0, st, b);
 }
 // (16 blocks would fit 8 waves - 64 KiB of partial sums, 241 VGPRs - and ran no faster than 4 at
 // H = 7168: DESIGN.md §4 "Router: the other routing rules")
-template <int NB, class ARGS>
+template <int NB, bool BF, class ARGS>
 inline void gate_modes_launch_nb(const ARGS& m, bool sigmoid, hipStream_t st) {
   constexpr int NW = NB <= 12 ? MXMOE_GATE_NW : 4;
   constexpr int MAXMR = NB <= 4 ? 4 : NB <= 8 ? 2 : 1;
   const int mr = gate_rows_per_wg(gate_args_of(m).T, MAXMR);
   if constexpr (MAXMR >= 4) {
-    if (mr == 4) return gate_modes_launch_one<NB, 4, NW, gate_group_steps(NB, 4)>(m, sigmoid, st);
+    if (mr == 4) return gate_modes_launch_one<NB, 4, NW, gate_group_steps(NB, 4), BF>(m, sigmoid, st);
   }
   if constexpr (MAXMR >= 2) {
-    if (mr == 2) return gate_modes_launch_one<NB, 2, NW, gate_group_steps(NB, 2)>(m, sigmoid, st);
+    if (mr == 2) return gate_modes_launch_one<NB, 2, NW, gate_group_steps(NB, 2), BF>(m, sigmoid, st);
   }
-  gate_modes_launch_one<NB, 1, NW, gate_group_steps(NB, 1)>(m, sigmoid, st);
+  gate_modes_launch_one<NB, 1, NW, gate_group_steps(NB, 1), BF>(m, sigmoid, st);
 }
-// one launch; the caller has validated the arguments (T > 0). ARGS: GateModeArgs, or GateBiasArgs (gate_bias_kernel)
-template <class ARGS>
+// one launch; the caller has validated the arguments (T > 0). ARGS: GateModeArgs, or GateBiasArgs (gate_bias_kernel);
+// BF: the bf16 builds
+template <bool BF = false, class ARGS>
 inline void gate_modes_launch(const ARGS& m, bool sigmoid, hipStream_t st) {
   const int nb = (gate_args_of(m).E + (gate_args_of(m).w_shared ? 1 : 0) + 15) / 16;
-  if (nb <= 1) gate_modes_launch_nb<1>(m, sigmoid, st);
-  else if (nb <= 2) gate_modes_launch_nb<2>(m, sigmoid, st);
-  else if (nb <= 4) gate_modes_launch_nb<4>(m, sigmoid, st);
-  else if (nb <= 5) gate_modes_launch_nb<5>(m, sigmoid, st);
-  else if (nb <= 8) gate_modes_launch_nb<8>(m, sigmoid, st);
-  else if (nb <= 12) gate_modes_launch_nb<12>(m, sigmoid, st);
-  else if (nb <= 16) gate_modes_launch_nb<16>(m, sigmoid, st);
-  else gate_modes_launch_nb<kGateMaxBlocks>(m, sigmoid, st);
+  if (nb <= 1) gate_modes_launch_nb<1, BF>(m, sigmoid, st);
+  else if (nb <= 2) gate_modes_launch_nb<2, BF>(m, sigmoid, st);
+  else if (nb <= 4) gate_modes_launch_nb<4, BF>(m, sigmoid, st);
+  else if (nb <= 5) gate_modes_launch_nb<5, BF>(m, sigmoid, st);
+  else if (nb <= 8) gate_modes_launch_nb<8, BF>(m, sigmoid, st);
+  else if (nb <= 12) gate_modes_launch_nb<12, BF>(m, sigmoid, st);
+  else if (nb <= 16) gate_modes_launch_nb<16, BF>(m, sigmoid, st);
+  else gate_modes_launch_nb<kGateMaxBlocks, BF>(m, sigmoid, st);
 }
 
 }  // namespace gate

@@ -1,7 +1,8 @@
 // moe_gate_body.inc — the body of gate_kernel and gate_modes_kernel (moe_gate.h, which says why it is
 // shared as text). In scope: NB, MR, NW, U, MODE (GateMode), `a` (GateArgs) and `ex` (const
 // GateModeArgs*, NULL for kGatePlain), LB (constexpr bool: the build adds a logit bias) and `lbias` (const float*,
-// [E]; read only when LB).
+// [E]; read only when LB), BF (constexpr bool: the operands are bf16 bit patterns behind the fp16-typed pointers,
+// multiplied on v_mfma_f32_16x16x32_bf16 — the same operand and accumulator layout; nothing else differs).
   constexpr int kSlots = NW == 8 ? 4 : 3;  // partial-sum tiles in LDS at a time, per (token block, column block)
   static_assert(NW == 4 || NW == 8, "4 or 8 waves");
   static_assert(MR >= 1 && MR <= 4 && MR * kSlots * NB * 1024 <= 64 * 1024, "partial sums must fit 64 KiB of LDS");
@@ -56,7 +57,11 @@
         for (int i = 0; i < MR; ++i)
 #pragma unroll
           for (int j = 0; j < NB; ++j)
-            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(w[u][j], h[u][i], acc[i][j], 0, 0, 0);
+            if constexpr (BF)  // (in place, not through a helper: moe_gate.h, above gate_kernel)
+              acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(gb8_t, w[u][j]),
+                                                                  __builtin_bit_cast(gb8_t, h[u][i]), acc[i][j], 0, 0, 0);
+            else
+              acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(w[u][j], h[u][i], acc[i][j], 0, 0, 0);
       }
     }
   };

@@ -41,8 +41,8 @@ constexpr int gate_wide_group_steps(int sb, int mr) { return sb <= 8 && mr == 1 
 
 // CS slices of SB column blocks, K split KS, 16 MR token rows (MR = 2 with KS = 2 only: part ks finishes token
 // block ks); SIGMOID: mxmoe_moe_gate_ex's sigmoid scoring (else softmax on the logits).
-// The logit bias is a run-time pointer (one wave-uniform branch per workgroup)
-template <int CS, int SB, int KS, int MR, int U, bool SIGMOID>
+// The logit bias is a run-time pointer (one wave-uniform branch per workgroup). BF: the bf16 builds (the `if constexpr` in mma below)
+template <int CS, int SB, int KS, int MR, int U, bool SIGMOID, bool BF = false>
 __global__ __launch_bounds__(64 * CS * KS) void gate_wide_kernel(GateBiasArgs bb) {
   static_assert(MR == 1 || (MR == 2 && KS == 2), "32 rows: one token block per K part");
   static_assert(CS >= 2 && CS <= 4 && SB <= 9 && CS * SB >= 17 && CS * SB <= 36, "17 .. 33 blocks in <= 4 slices of <= 9");
@@ -108,7 +108,11 @@ __global__ __launch_bounds__(64 * CS * KS) void gate_wide_kernel(GateBiasArgs bb
         for (int i = 0; i < MR; ++i)
 #pragma unroll
           for (int j = 0; j < SB; ++j)
-            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(w[u][j], h[u][i], acc[i][j], 0, 0, 0);
+            if constexpr (BF)  // (in place, not through a helper: moe_gate.h, above gate_kernel)
+              acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(gb8_t, w[u][j]),
+                                                                  __builtin_bit_cast(gb8_t, h[u][i]), acc[i][j], 0, 0, 0);
+            else
+              acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(w[u][j], h[u][i], acc[i][j], 0, 0, 0);
       }
     }
   };
@@ -388,33 +392,34 @@ __global__ __launch_bounds__(64 * CS * KS) void gate_wide_kernel(GateBiasArgs bb
   }
 }
 
-template <int CS, int SB, int KS, int MR>
+template <int CS, int SB, int KS, int MR, bool BF>
 inline void gate_wide_launch_mr(const GateBiasArgs& b, bool sigmoid, hipStream_t st) {
   constexpr int U = gate_wide_group_steps(SB, MR);
   const dim3 blocks((unsigned)((b.m.g.T + 16 * MR - 1) / (16 * MR))), threads(64 * CS * KS);
-  if (sigmoid) hipLaunchKernelGGL((gate_wide_kernel<CS, SB, KS, MR, U, true>), blocks, threads, 0, st, b);
-  else hipLaunchKernelGGL((gate_wide_kernel<CS, SB, KS, MR, U, false>), blocks, threads, 0, st, b);
+  if (sigmoid) hipLaunchKernelGGL((gate_wide_kernel<CS, SB, KS, MR, U, true, BF>), blocks, threads, 0, st, b);
+  else hipLaunchKernelGGL((gate_wide_kernel<CS, SB, KS, MR, U, false, BF>), blocks, threads, 0, st, b);
 }
 // 32 rows per workgroup (half the w_gate re-reads per token) once the grid still has a workgroup per CU
 // (gate_rows_per_wg of moe_gate.h); the K split of 4 keeps 16
-template <int CS, int SB, int KS>
+template <int CS, int SB, int KS, bool BF>
 inline void gate_wide_launch_one(const GateBiasArgs& b, bool sigmoid, hipStream_t st) {
   if constexpr (KS == 2) {
-    if (gate_rows_per_wg(b.m.g.T, 2) == 2) return gate_wide_launch_mr<CS, SB, KS, 2>(b, sigmoid, st);
+    if (gate_rows_per_wg(b.m.g.T, 2) == 2) return gate_wide_launch_mr<CS, SB, KS, 2, BF>(b, sigmoid, st);
   }
-  gate_wide_launch_mr<CS, SB, KS, 1>(b, sigmoid, st);
+  gate_wide_launch_mr<CS, SB, KS, 1, BF>(b, sigmoid, st);
 }
 // one launch; the caller has validated the arguments (T > 0, 256 < E <= 512, no groups). The fewest slices of at most
 // 9 blocks, then the fewest blocks per slice; 8 waves (6 for three slices)
+template <bool BF = false>
 inline void gate_wide_launch(const GateBiasArgs& b, bool sigmoid, hipStream_t st) {
   const int nb = (b.m.g.E + (b.m.g.w_shared ? 1 : 0) + 15) / 16;  // 17 .. 33
-  if (nb <= 18) gate_wide_launch_one<2, 9, 4>(b, sigmoid, st);
-  else if (nb <= 21) gate_wide_launch_one<3, 7, 2>(b, sigmoid, st);
-  else if (nb <= 24) gate_wide_launch_one<3, 8, 2>(b, sigmoid, st);
-  else if (nb <= 27) gate_wide_launch_one<3, 9, 2>(b, sigmoid, st);
-  else if (nb <= 28) gate_wide_launch_one<4, 7, 2>(b, sigmoid, st);
-  else if (nb <= 32) gate_wide_launch_one<4, 8, 2>(b, sigmoid, st);
-  else gate_wide_launch_one<4, 9, 2>(b, sigmoid, st);
+  if (nb <= 18) gate_wide_launch_one<2, 9, 4, BF>(b, sigmoid, st);
+  else if (nb <= 21) gate_wide_launch_one<3, 7, 2, BF>(b, sigmoid, st);
+  else if (nb <= 24) gate_wide_launch_one<3, 8, 2, BF>(b, sigmoid, st);
+  else if (nb <= 27) gate_wide_launch_one<3, 9, 2, BF>(b, sigmoid, st);
+  else if (nb <= 28) gate_wide_launch_one<4, 7, 2, BF>(b, sigmoid, st);
+  else if (nb <= 32) gate_wide_launch_one<4, 8, 2, BF>(b, sigmoid, st);
+  else gate_wide_launch_one<4, 9, 2, BF>(b, sigmoid, st);
 }
 
 }  // namespace gate

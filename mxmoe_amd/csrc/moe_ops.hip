@@ -18,6 +18,9 @@
 // The router in front of them (mxmoe_moe_gate: logits on the MFMA, top-k, softmax; mxmoe_moe_gate_ex:
 // sigmoid scores, selection bias, group-limited top-k) is moe_gate.h; beyond 256 experts (mxmoe_moe_gate_wide),
 // moe_gate_wide.h.
+// bf16 layers (mxmoe_moe_gate_dt, mxmoe_moe_gather_quant, mxmoe_moe_combine_dt): the element type of the router's
+// operands, of the gather's source rows and of the combine's output is a template parameter of the kernels above;
+// the fp16 instantiations are the kernels as they were. No reference counterpart (the reference is fp16 only).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -229,6 +232,20 @@ __device__ __forceinline__ float amax8(const h8_t& x) {
   return fmaxf((float)c[0], (float)c[1]);
 }
 
+// 8 bf16 (one 16-B load) -> 8 fp16: each element widened to f32 (its bits << 16, exact) and rounded once to fp16 by
+// v_cvt_f16_f32 — to nearest even, overflow to +-Inf, the fp16-subnormal range rounded and not flushed (the fp16
+// denormal mode of these kernels is IEEE): the value hidden.to(torch.float16) holds.
+__device__ __forceinline__ h8_t bf16x8_to_f16(const uint4& v) {
+  const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+  h8_t r;
+#pragma unroll
+  for (int p = 0; p < 4; ++p) {
+    r[2 * p] = (_Float16)__builtin_bit_cast(float, w[p] << 16);
+    r[2 * p + 1] = (_Float16)__builtin_bit_cast(float, w[p] & 0xFFFF0000u);
+  }
+  return r;
+}
+
 // One WAVE per slot row (4 rows per 256-thread workgroup): lane l holds elements c*512 + 8l .. +7
 // of chunk c in registers (MAXC chunks: rows up to MAXC*512 elements, MAXC = the launch's widest
 // row in 512-element chunks), so every lane has MAXC independent 16-B loads in flight, the
@@ -248,10 +265,13 @@ __device__ __forceinline__ float amax8(const h8_t& x) {
 // GLU (MODE 1 only; mxmoe_moe_glu_quant): kGluSilu / kGluSwigluClamp builds take GluArgs, add the expert's bias
 // row to the gate and up values as they are read (one f32 add each; a NULL bias: no add) and apply the named
 // gated activation. kGluNone: none of that code exists and the builds are the ones above.
-template <int MODE, int MAXC, bool MX = false, int GLU = kGluNone>
+// SRCBF (MODE 0 only; mxmoe_moe_gather_quant): hidden holds bf16; every 16-B load is converted to fp16 as it arrives
+// (bf16x8_to_f16) and nothing after the loads differs. SRCBF = false: the builds above, as they were.
+template <int MODE, int MAXC, bool MX = false, int GLU = kGluNone, bool SRCBF = false>
 __global__ __launch_bounds__(kThreads) void act_quant_kernel(typename ActArgsOf<GLU>::type a) {
   constexpr bool SILU = MODE == 1 || MODE == 3;
   static_assert(GLU == kGluNone || MODE == 1, "the GLU builds read [gate | up] columns");
+  static_assert(!SRCBF || MODE == 0, "only the gather reads bf16 rows: the gate_up output stays fp16");
   __shared__ float wave_amax[kThreads / 64];
   const int lane = threadIdx.x & 63;
   const bool split_row = a.parts > 1 && (int64_t)blockIdx.x >= a.blk_shared;  // workgroup-uniform
@@ -297,7 +317,8 @@ __global__ __launch_bounds__(kThreads) void act_quant_kernel(typename ActArgsOf<
     const int gi = MODE == 3 ? 2 * (li & ~15) + (li & 15) : li;
     const uint4 xv = *reinterpret_cast<const uint4*>(base + gi);
     const uint4 z = {0, 0, 0, 0};
-    x[c] = __builtin_bit_cast(h8_t, in ? xv : z);
+    if constexpr (SRCBF) x[c] = bf16x8_to_f16(in ? xv : z);
+    else x[c] = __builtin_bit_cast(h8_t, in ? xv : z);
     if constexpr (SILU) {
       const uint4 uv = *reinterpret_cast<const uint4*>(base + (MODE == 3 ? gi + 16 : upoff + li));
       u[c] = __builtin_bit_cast(h8_t, in ? uv : z);
@@ -510,11 +531,14 @@ __global__ __launch_bounds__(kThreads) void act_quant_kernel(typename ActArgsOf<
 }
 
 // ---------------------------------------------------------------------------------------------
-// combine: one workgroup per token, 8 fp16 columns per lane and pass
+// combine: one workgroup per token, 8 fp16 columns per lane and pass. OT: the output element, _Float16 (the kernel
+// as it was) or __bf16 (mxmoe_moe_combine_dt: the f32 accumulator rounded to bf16 to nearest even, v_cvt_pk_bf16_f32)
+template <class OT>
 __global__ __launch_bounds__(kThreads) void combine_kernel(const _Float16* __restrict__ y, const int32_t* __restrict__ inv,
                                                            const float* __restrict__ w, const _Float16* __restrict__ shared,
                                                            const float* __restrict__ shared_w, int topk, int H,
-                                                           _Float16* __restrict__ out) {
+                                                           OT* __restrict__ out) {
+  typedef OT o8_t __attribute__((ext_vector_type(8)));
   const int64_t t = blockIdx.x;
   for (int idx = threadIdx.x * 8; idx < H; idx += kChunk) {
     float acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -531,23 +555,25 @@ __global__ __launch_bounds__(kThreads) void combine_kernel(const _Float16* __res
 #pragma unroll
       for (int j = 0; j < 8; ++j) acc[j] = fmaf(ws, (float)v[j], acc[j]);
     }
-    h8_t r;
+    o8_t r;
 #pragma unroll
-    for (int j = 0; j < 8; ++j) r[j] = (_Float16)acc[j];
-    *reinterpret_cast<h8_t*>(out + t * H + idx) = r;
+    for (int j = 0; j < 8; ++j) r[j] = (OT)acc[j];
+    *reinterpret_cast<o8_t*>(out + t * H + idx) = r;
   }
 }
 
 // combine with a bias row per expert on the down output (mxmoe_moe_combine_bias): the term of choice k is
 // f32(y) + f32(bias[e]) (one add), e = sorted[slot] — an id outside [0, E) (a stale slot) adds nothing — and the
-// shared term f32(shared) + f32(shared_bias)
+// shared term f32(shared) + f32(shared_bias). OT: as combine_kernel's
+template <class OT>
 __global__ __launch_bounds__(kThreads) void combine_bias_kernel(const _Float16* __restrict__ y, const int32_t* __restrict__ inv,
                                                                 const int32_t* __restrict__ sorted, const float* __restrict__ w,
                                                                 const _Float16* __restrict__ bias,
                                                                 const _Float16* __restrict__ shared,
                                                                 const float* __restrict__ shared_w,
                                                                 const _Float16* __restrict__ shared_bias, int topk, int E, int H,
-                                                                _Float16* __restrict__ out) {
+                                                                OT* __restrict__ out) {
+  typedef OT o8_t __attribute__((ext_vector_type(8)));
   const int64_t t = blockIdx.x;
   for (int idx = threadIdx.x * 8; idx < H; idx += kChunk) {
     float acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -577,10 +603,10 @@ __global__ __launch_bounds__(kThreads) void combine_bias_kernel(const _Float16* 
         for (int j = 0; j < 8; ++j) acc[j] = fmaf(ws, (float)v[j], acc[j]);
       }
     }
-    h8_t r;
+    o8_t r;
 #pragma unroll
-    for (int j = 0; j < 8; ++j) r[j] = (_Float16)acc[j];
-    *reinterpret_cast<h8_t*>(out + t * H + idx) = r;
+    for (int j = 0; j < 8; ++j) r[j] = (OT)acc[j];
+    *reinterpret_cast<o8_t*>(out + t * H + idx) = r;
   }
 }
 
@@ -671,33 +697,35 @@ int segments_check(const int32_t* counts, int E, int64_t T, int topk, const mxmo
 using namespace mxmoe;
 
 // registers sized to the widest row of the launch, in 512-element chunks (1408 -> 3, 2048 -> 4)
-template <int MODE, bool MX, int GLU = kGluNone>
+template <int MODE, bool MX, int GLU = kGluNone, bool SRCBF = false>
 static void launch_act_w(const typename ActArgsOf<GLU>::type& a, int maxw, hipStream_t st) {
   const int64_t blocks = a.parts > 1 ? a.blk_shared + (a.nslots - a.ntk)
                                      : (a.nslots - a.s0 + kThreads / 64 - 1) / (kThreads / 64);
   const dim3 grid((unsigned)blocks), block(kThreads);
   const int nc = (maxw + 511) / 512;
-  if (nc <= 1) hipLaunchKernelGGL((act_quant_kernel<MODE, 1, MX, GLU>), grid, block, 0, st, a);
-  else if (nc <= 2) hipLaunchKernelGGL((act_quant_kernel<MODE, 2, MX, GLU>), grid, block, 0, st, a);
-  else if (nc <= 3) hipLaunchKernelGGL((act_quant_kernel<MODE, 3, MX, GLU>), grid, block, 0, st, a);
-  else if (nc <= 4) hipLaunchKernelGGL((act_quant_kernel<MODE, 4, MX, GLU>), grid, block, 0, st, a);
-  else if (nc <= 6) hipLaunchKernelGGL((act_quant_kernel<MODE, 6, MX, GLU>), grid, block, 0, st, a);
-  else if (nc <= 8) hipLaunchKernelGGL((act_quant_kernel<MODE, 8, MX, GLU>), grid, block, 0, st, a);
-  else if (nc <= 12) hipLaunchKernelGGL((act_quant_kernel<MODE, 12, MX, GLU>), grid, block, 0, st, a);
-  else if (nc <= 16) hipLaunchKernelGGL((act_quant_kernel<MODE, 16, MX, GLU>), grid, block, 0, st, a);
-  else hipLaunchKernelGGL((act_quant_kernel<MODE, 32, MX, GLU>), grid, block, 0, st, a);
+  if (nc <= 1) hipLaunchKernelGGL((act_quant_kernel<MODE, 1, MX, GLU, SRCBF>), grid, block, 0, st, a);
+  else if (nc <= 2) hipLaunchKernelGGL((act_quant_kernel<MODE, 2, MX, GLU, SRCBF>), grid, block, 0, st, a);
+  else if (nc <= 3) hipLaunchKernelGGL((act_quant_kernel<MODE, 3, MX, GLU, SRCBF>), grid, block, 0, st, a);
+  else if (nc <= 4) hipLaunchKernelGGL((act_quant_kernel<MODE, 4, MX, GLU, SRCBF>), grid, block, 0, st, a);
+  else if (nc <= 6) hipLaunchKernelGGL((act_quant_kernel<MODE, 6, MX, GLU, SRCBF>), grid, block, 0, st, a);
+  else if (nc <= 8) hipLaunchKernelGGL((act_quant_kernel<MODE, 8, MX, GLU, SRCBF>), grid, block, 0, st, a);
+  else if (nc <= 12) hipLaunchKernelGGL((act_quant_kernel<MODE, 12, MX, GLU, SRCBF>), grid, block, 0, st, a);
+  else if (nc <= 16) hipLaunchKernelGGL((act_quant_kernel<MODE, 16, MX, GLU, SRCBF>), grid, block, 0, st, a);
+  else hipLaunchKernelGGL((act_quant_kernel<MODE, 32, MX, GLU, SRCBF>), grid, block, 0, st, a);
 }
 
-template <int MODE>
+template <int MODE, bool SRCBF = false>
 static void launch_act_m(const ActArgs& a, int maxw, bool mx, hipStream_t st) {
-  if (mx) launch_act_w<MODE, true>(a, maxw, st);
-  else launch_act_w<MODE, false>(a, maxw, st);
+  if (mx) launch_act_w<MODE, true, kGluNone, SRCBF>(a, maxw, st);
+  else launch_act_w<MODE, false, kGluNone, SRCBF>(a, maxw, st);
 }
+constexpr int kModeGatherBf16 = 4;  // launch_act_any's number for mode 0 on bf16 rows (no mode of the C interface)
 // (mode, mx): which build of the kernel; ActArgs: the four passes, GluArgs: mxmoe_moe_glu_quant's (mode = MXMOE_GLU_*)
 static void launch_act_any(int mode, const ActArgs& a, int maxw, bool mx, hipStream_t st) {
   if (mode == 1) launch_act_m<1>(a, maxw, mx, st);
   else if (mode == 2) launch_act_m<2>(a, maxw, mx, st);
   else if (mode == 3) launch_act_m<3>(a, maxw, mx, st);
+  else if (mode == kModeGatherBf16) launch_act_m<0, true>(a, maxw, mx, st);
   else launch_act_m<0>(a, maxw, mx, st);
 }
 static void launch_act_any(int act, const GluArgs& a, int maxw, bool mx, hipStream_t st) {
@@ -744,14 +772,14 @@ static int launch_act(int mode, ARGS a, int64_t nslots, int w_routed, int w_shar
 // the activation entry points' bodies; mx: the call's segments may carry MXMOE_ACT_MXFP4
 static int quant_act_impl(const char* fn, const void* hidden, int64_t T, int K, int topk, int with_shared,
                           const int32_t* sorted_expert, const int32_t* perm_token, const mxmoe_moe_seg* segs, int nseg,
-                          void* out, void* scales, void* stream, bool mx) {
+                          void* out, void* scales, void* stream, bool mx, bool src_bf16 = false) {
   if (T < 0 || topk <= 0 || nseg <= 0 || K <= 0 || K % 128 || K > kMaxWidth)
     return fail(MXMOE_GG_ERR_INVALID, "%s: need K %% 128 == 0, K <= %d, topk > 0, nseg > 0 (K=%d)", fn, kMaxWidth, K);
   if (T > 0 && (!hidden || !sorted_expert || !perm_token || !segs || !out || !aligned16(hidden) || !aligned16(out)))
     return fail(MXMOE_GG_ERR_INVALID, "%s: NULL or misaligned pointer (hidden / out need 16 B)", fn);
   const ActArgs a{static_cast<const _Float16*>(hidden), static_cast<const _Float16*>(hidden), T * topk, 0, 0, K, 0, 0,
                   sorted_expert, perm_token, segs, nseg, static_cast<uint8_t*>(out), static_cast<_Float16*>(scales)};
-  return launch_act(0, a, T * topk + (with_shared ? T : 0), K, K, stream, mx);
+  return launch_act(src_bf16 ? kModeGatherBf16 : 0, a, T * topk + (with_shared ? T : 0), K, K, stream, mx);
 }
 static int slots_check(const char* fn, const void* routed_in, const void* shared_in, int64_t T, int topk, int N,
                        int N_shared, const int32_t* sorted_expert, const mxmoe_moe_seg* segs, int nseg, void* out) {
@@ -794,6 +822,48 @@ static int combine_check(const char* fn, const void* y, const int32_t* inv_slot,
   return MXMOE_GG_OK;
 }
 
+// mxmoe_moe_combine_bias and mxmoe_moe_combine_dt: the checks, then combine_kernel without any bias (the arithmetic of
+// mxmoe_moe_combine) or combine_bias_kernel, on the output type OT
+template <class OT>
+static void launch_combine(const void* y, const int32_t* inv_slot, const int32_t* sorted_expert, const float* weights,
+                           const void* bias, const void* shared, const float* shared_w, const void* shared_bias, int64_t T,
+                           int topk, int E, int H, void* out, bool plain, void* stream) {
+  if (plain)
+    hipLaunchKernelGGL(combine_kernel<OT>, dim3((unsigned)T), dim3(kThreads), 0, (hipStream_t)stream,
+                       static_cast<const _Float16*>(y), inv_slot, weights, static_cast<const _Float16*>(shared), shared_w,
+                       topk, H, static_cast<OT*>(out));
+  else
+    hipLaunchKernelGGL(combine_bias_kernel<OT>, dim3((unsigned)T), dim3(kThreads), 0, (hipStream_t)stream,
+                       static_cast<const _Float16*>(y), inv_slot, sorted_expert, weights, static_cast<const _Float16*>(bias),
+                       static_cast<const _Float16*>(shared), shared_w, static_cast<const _Float16*>(shared_bias), topk, E, H,
+                       static_cast<OT*>(out));
+}
+// dt_entry: mxmoe_moe_combine_dt (a call without any bias runs combine_kernel; mxmoe_moe_combine_bias always its own)
+static int combine_bias_impl(const char* fn, bool dt_entry, int out_dtype, const void* y, const int32_t* inv_slot,
+                             const int32_t* sorted_expert, const float* weights, const void* bias, const void* shared,
+                             const float* shared_w, const void* shared_bias, int64_t T, int topk, int E, int H, void* out,
+                             void* stream) {
+  if (out_dtype != MXMOE_DT_FP16 && out_dtype != MXMOE_DT_BF16)
+    return fail(MXMOE_GG_ERR_INVALID, "%s: out_dtype must be MXMOE_DT_FP16 or MXMOE_DT_BF16 (got %d)", fn, out_dtype);
+  if (T < 0 || topk <= 0 || H <= 0 || H % 8 || E < 1)
+    return fail(MXMOE_GG_ERR_INVALID, "%s: need H %% 8 == 0, topk > 0, E >= 1 (H=%d E=%d)", fn, H, E);
+  if (!aligned16(bias) || !aligned16(shared_bias) || (shared_bias && !shared))
+    return fail(MXMOE_GG_ERR_INVALID, "%s: misaligned bias pointer (16 B), or a shared_bias without shared", fn);
+  if (T == 0) return MXMOE_GG_OK;
+  if (int st = combine_check(fn, y, inv_slot, weights, shared, out, bias && !sorted_expert)) return st;
+  const bool plain = dt_entry && !bias && !shared_bias;
+  if (out_dtype == MXMOE_DT_BF16)
+    launch_combine<__bf16>(y, inv_slot, sorted_expert, weights, bias, shared, shared_w, shared_bias, T, topk, E, H, out, plain,
+                           stream);
+  else
+    launch_combine<_Float16>(y, inv_slot, sorted_expert, weights, bias, shared, shared_w, shared_bias, T, topk, E, H, out,
+                             plain, stream);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess)
+    return fail(MXMOE_GG_ERR_HIP, "%s launch failed: %s", plain ? "combine_kernel" : "combine_bias_kernel", hipGetErrorString(e));
+  return MXMOE_GG_OK;
+}
+
 // what mxmoe_moe_gate and mxmoe_moe_gate_ex check alike, before any HIP call
 static int gate_check(const char* fn, const void* hidden, const void* w_gate, const void* w_shared_gate, int64_t T, int H,
                       int E, int topk, const int32_t* topk_ids, const float* topk_weights, const float* shared_w,
@@ -813,7 +883,10 @@ static int gate_check(const char* fn, const void* hidden, const void* w_gate, co
 static int gate_ex_impl(const char* fn, const void* hidden, const void* w_gate, const void* w_shared_gate, int64_t T, int H,
                         int E, int topk, int renormalize, int scoring, const float* e_bias, int n_group, int topk_group,
                         int group_top, float routed_scale, const float* logit_bias, int32_t* topk_ids, float* topk_weights,
-                        float* shared_w, float* logits, float* scores, void* stream, int max_e = 256) {
+                        float* shared_w, float* logits, float* scores, void* stream, int max_e = 256,
+                        int dtype = MXMOE_DT_FP16) {
+  if (dtype != MXMOE_DT_FP16 && dtype != MXMOE_DT_BF16)
+    return fail(MXMOE_GG_ERR_INVALID, "%s: dtype must be MXMOE_DT_FP16 or MXMOE_DT_BF16 (got %d)", fn, dtype);
   if (scoring != MXMOE_GATE_SOFTMAX && scoring != MXMOE_GATE_SIGMOID)
     return fail(MXMOE_GG_ERR_INVALID, "%s: scoring must be MXMOE_GATE_SOFTMAX or MXMOE_GATE_SIGMOID (got %d)", fn, scoring);
   const int st = gate_check(fn, hidden, w_gate, w_shared_gate, T, H, E, topk, topk_ids, topk_weights, shared_w, max_e);
@@ -839,9 +912,15 @@ static int gate_ex_impl(const char* fn, const void* hidden, const void* w_gate, 
                               static_cast<const _Float16*>(w_shared_gate), T, H, E, topk, renormalize != 0, topk_ids,
                               topk_weights, shared_w, logits},
                              e_bias, scores, n_group, topk_group, group_top, routed_scale};
-  if (E > 256) gate::gate_wide_launch(gate::GateBiasArgs{m, logit_bias}, scoring == MXMOE_GATE_SIGMOID, (hipStream_t)stream);
-  else if (logit_bias) gate::gate_modes_launch(gate::GateBiasArgs{m, logit_bias}, scoring == MXMOE_GATE_SIGMOID, (hipStream_t)stream);
-  else gate::gate_modes_launch(m, scoring == MXMOE_GATE_SIGMOID, (hipStream_t)stream);
+  const bool sigmoid = scoring == MXMOE_GATE_SIGMOID;
+  hipStream_t const hs = (hipStream_t)stream;
+  if (dtype == MXMOE_DT_BF16) {  // the same launch forms on the bf16 builds (the pointers carry bf16 bit patterns)
+    if (E > 256) gate::gate_wide_launch<true>(gate::GateBiasArgs{m, logit_bias}, sigmoid, hs);
+    else if (logit_bias) gate::gate_modes_launch<true>(gate::GateBiasArgs{m, logit_bias}, sigmoid, hs);
+    else gate::gate_modes_launch<true>(m, sigmoid, hs);
+  } else if (E > 256) gate::gate_wide_launch(gate::GateBiasArgs{m, logit_bias}, sigmoid, hs);
+  else if (logit_bias) gate::gate_modes_launch(gate::GateBiasArgs{m, logit_bias}, sigmoid, hs);
+  else gate::gate_modes_launch(m, sigmoid, hs);
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess)
     return fail(MXMOE_GG_ERR_HIP, "%s launch failed: %s", E > 256 ? "gate_wide_kernel" : "gate_modes_kernel", hipGetErrorString(e));
@@ -891,6 +970,16 @@ int mxmoe_moe_gate_wide(const void* hidden, const void* w_gate, const void* w_sh
                       scores, stream, gate::kGateWideMaxExperts);
 }
 
+int mxmoe_moe_gate_dt(int dtype, const void* hidden, const void* w_gate, const void* w_shared_gate, int64_t T, int H, int E,
+                      int topk, int renormalize, int scoring, const float* e_bias, int n_group, int topk_group, int group_top,
+                      float routed_scale, const float* logit_bias, int32_t* topk_ids, float* topk_weights, float* shared_w,
+                      float* logits, float* scores, void* stream) {
+  // MXMOE_DT_FP16: mxmoe_moe_gate_wide's call; MXMOE_DT_BF16: the same launch forms on the kernels' bf16 builds
+  return gate_ex_impl("mxmoe_moe_gate_dt", hidden, w_gate, w_shared_gate, T, H, E, topk, renormalize, scoring, e_bias,
+                      n_group, topk_group, group_top, routed_scale, logit_bias, topk_ids, topk_weights, shared_w, logits,
+                      scores, stream, gate::kGateWideMaxExperts, dtype);
+}
+
 int mxmoe_moe_route(const int32_t* topk_ids, int64_t T, int topk, int E, int32_t* sorted_expert,
                     int32_t* perm_token, int32_t* inv_slot, int32_t* counts, void* stream) {
   if (T < 0 || topk <= 0 || E <= 0 || E > 4096 || T * topk > (int64_t)1 << 30)
@@ -935,6 +1024,18 @@ int mxmoe_moe_quant_act(const void* hidden, int64_t T, int K, int topk, int with
                         void* out, void* scales, void* stream) {
   return quant_act_impl("mxmoe_moe_quant_act", hidden, T, K, topk, with_shared, sorted_expert, perm_token, segs, nseg, out,
                         scales, stream, false);
+}
+
+int mxmoe_moe_gather_quant(int dtype, const void* hidden, int64_t T, int K, int topk, int with_shared,
+                           const int32_t* sorted_expert, const int32_t* perm_token, const mxmoe_moe_seg* segs, int nseg,
+                           uint32_t tag_mask, void* out, void* scales, void* stream) {
+  const char* fn = "mxmoe_moe_gather_quant";
+  if (dtype != MXMOE_DT_FP16 && dtype != MXMOE_DT_BF16)
+    return fail(MXMOE_GG_ERR_INVALID, "%s: dtype must be MXMOE_DT_FP16 or MXMOE_DT_BF16 (got %d)", fn, dtype);
+  bool mx = false;
+  if (int st = tag_mask_mx(fn, tag_mask, &mx)) return st;
+  return quant_act_impl(fn, hidden, T, K, topk, with_shared, sorted_expert, perm_token, segs, nseg, out, scales, stream, mx,
+                        dtype == MXMOE_DT_BF16);
 }
 
 int mxmoe_moe_silu_mul_quant(const void* routed_in, const void* shared_in, int64_t T, int topk, int N, int N_shared,
@@ -999,19 +1100,15 @@ int mxmoe_moe_glu_quant(const mxmoe_moe_glu* glu, const void* routed_in, const v
 int mxmoe_moe_combine_bias(const void* y, const int32_t* inv_slot, const int32_t* sorted_expert, const float* weights,
                            const void* bias, const void* shared, const float* shared_w, const void* shared_bias, int64_t T,
                            int topk, int E, int H, void* out, void* stream) {
-  if (T < 0 || topk <= 0 || H <= 0 || H % 8 || E < 1)
-    return fail(MXMOE_GG_ERR_INVALID, "mxmoe_moe_combine_bias: need H %% 8 == 0, topk > 0, E >= 1 (H=%d E=%d)", H, E);
-  if (!aligned16(bias) || !aligned16(shared_bias) || (shared_bias && !shared))
-    return fail(MXMOE_GG_ERR_INVALID, "mxmoe_moe_combine_bias: misaligned bias pointer (16 B), or a shared_bias without shared");
-  if (T == 0) return MXMOE_GG_OK;
-  if (int st = combine_check("mxmoe_moe_combine_bias", y, inv_slot, weights, shared, out, bias && !sorted_expert)) return st;
-  hipLaunchKernelGGL(combine_bias_kernel, dim3((unsigned)T), dim3(kThreads), 0, (hipStream_t)stream,
-                     static_cast<const _Float16*>(y), inv_slot, sorted_expert, weights, static_cast<const _Float16*>(bias),
-                     static_cast<const _Float16*>(shared), shared_w, static_cast<const _Float16*>(shared_bias), topk, E, H,
-                     static_cast<_Float16*>(out));
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(MXMOE_GG_ERR_HIP, "combine_bias_kernel launch failed: %s", hipGetErrorString(e));
-  return MXMOE_GG_OK;
+  return combine_bias_impl("mxmoe_moe_combine_bias", false, MXMOE_DT_FP16, y, inv_slot, sorted_expert, weights, bias, shared,
+                           shared_w, shared_bias, T, topk, E, H, out, stream);
+}
+
+int mxmoe_moe_combine_dt(int out_dtype, const void* y, const int32_t* inv_slot, const int32_t* sorted_expert,
+                         const float* weights, const void* bias, const void* shared, const float* shared_w,
+                         const void* shared_bias, int64_t T, int topk, int E, int H, void* out, void* stream) {
+  return combine_bias_impl("mxmoe_moe_combine_dt", true, out_dtype, y, inv_slot, sorted_expert, weights, bias, shared,
+                           shared_w, shared_bias, T, topk, E, H, out, stream);
 }
 
 int mxmoe_moe_combine(const void* y, const int32_t* inv_slot, const float* weights, const void* shared,
@@ -1020,7 +1117,7 @@ int mxmoe_moe_combine(const void* y, const int32_t* inv_slot, const float* weigh
     return fail(MXMOE_GG_ERR_INVALID, "mxmoe_moe_combine: need H %% 8 == 0, topk > 0 (H=%d)", H);
   if (T == 0) return MXMOE_GG_OK;
   if (int st = combine_check("mxmoe_moe_combine", y, inv_slot, weights, shared, out)) return st;
-  hipLaunchKernelGGL(combine_kernel, dim3((unsigned)T), dim3(kThreads), 0, (hipStream_t)stream,
+  hipLaunchKernelGGL(combine_kernel<_Float16>, dim3((unsigned)T), dim3(kThreads), 0, (hipStream_t)stream,
                      static_cast<const _Float16*>(y), inv_slot, weights, static_cast<const _Float16*>(shared), shared_w,
                      topk, H, static_cast<_Float16*>(out));
   const hipError_t e = hipGetLastError();

@@ -99,6 +99,16 @@ class Routing:
         return out
 
 
+# The element types of a layer's two ends (hidden, the router's weights, out): MXMOE_DT_* of include/mxmoe_moe.h.
+# Everything between them (activation stores, h1, y, biases) is fp16 whatever the ends are.
+_DT = {torch.float16: nat.DT_FP16, torch.bfloat16: nat.DT_BF16}
+
+
+def _check_io_dtype(dtype, what: str) -> None:
+    if dtype not in _DT:
+        raise ValueError(f"{what} must be fp16 or bf16, got {dtype}")
+
+
 GATE_SCORING = {"softmax": 0, "sigmoid": 1}  # MXMOE_GATE_SOFTMAX / MXMOE_GATE_SIGMOID (include/mxmoe_moe.h)
 # beyond GATE_GROUPS_MAX_E experts the router is mxmoe_moe_gate_wide's kernel: up to GATE_MAX_E, one group
 GATE_GROUPS_MAX_E, GATE_MAX_E = 256, 512
@@ -178,16 +188,23 @@ def gate(hidden: torch.Tensor, w_gate: torch.Tensor, topk: int, *, renormalize: 
 
     More than 256 experts (up to 512; mxmoe_moe_gate_wide, still one launch): every rule above except the groups
     (``n_group`` must be 1). Kimi-K2: E 384, ``scoring="sigmoid", e_bias, renormalize=True,
-    routed_scaling_factor=2.827``; Qwen3-Next: E 512, ``renormalize=True, w_shared_gate``."""
-    if hidden.dim() != 2 or hidden.dtype != torch.float16 or not hidden.is_contiguous():
-        raise ValueError("hidden must be a contiguous fp16 [T, H] tensor")
+    routed_scaling_factor=2.827``; Qwen3-Next: E 512, ``renormalize=True, w_shared_gate``.
+
+    bf16: ``hidden``, ``w_gate`` and ``w_shared_gate`` may all be bf16 instead (one dtype per call; a mix raises).
+    The logits are then bf16 x bf16 products — each exact in f32 — accumulated in f32 on the bf16 MFMA
+    (mxmoe_moe_gate_dt, whatever E and the rules are): nothing is rounded to fp16 on the way, and everything after
+    the logits is the same code."""
+    if hidden.dim() != 2 or hidden.dtype not in _DT or not hidden.is_contiguous():
+        raise ValueError("hidden must be a contiguous fp16 or bf16 [T, H] tensor")
     T, H = hidden.shape
-    if w_gate.dim() != 2 or w_gate.dtype != torch.float16 or not w_gate.is_contiguous() or w_gate.shape[1] != H:
-        raise ValueError(f"w_gate must be a contiguous fp16 [E, {H}] tensor")
+    dt = hidden.dtype
+    if w_gate.dim() != 2 or w_gate.dtype != dt or not w_gate.is_contiguous() or w_gate.shape[1] != H:
+        raise ValueError(f"w_gate must be a contiguous [E, {H}] tensor of hidden's dtype ({dt}), got {w_gate.dtype} "
+                         f"{list(w_gate.shape)}")
     E = w_gate.shape[0]
     sg = w_shared_gate
-    if sg is not None and (sg.dtype != torch.float16 or not sg.is_contiguous() or sg.numel() != H):
-        raise ValueError(f"w_shared_gate must be a contiguous fp16 tensor of {H} elements")
+    if sg is not None and (sg.dtype != dt or not sg.is_contiguous() or sg.numel() != H):
+        raise ValueError(f"w_shared_gate must be a contiguous tensor of {H} elements of hidden's dtype ({dt})")
     group_top, plain = gate_routing_args(E, topk, scoring, e_bias, n_group, topk_group, group_top,
                                          routed_scaling_factor, return_scores)
     dev = hidden.device
@@ -209,7 +226,12 @@ def gate(hidden: torch.Tensor, w_gate: torch.Tensor, topk: int, *, renormalize: 
     ids, wts, sw = out[:3]
     logits = out[3] if return_logits else None
     scores = out[-1] if return_scores else None
-    if E > GATE_GROUPS_MAX_E or logit_bias is not None:
+    if dt != torch.float16:  # one entry for every E and rule (the fp16 call keeps the entries and kernels it had)
+        nat.check(nat.symbol("mxmoe_moe_gate_dt")(
+            _DT[dt], _ptr(hidden), _ptr(w_gate), _ptr(sg), T, H, E, topk, int(bool(renormalize)), GATE_SCORING[scoring],
+            _ptr(e_bias), int(n_group), int(topk_group), group_top, float(routed_scaling_factor), _ptr(logit_bias), _ptr(ids),
+            _ptr(wts), _ptr(sw), _ptr(logits), _ptr(scores), _stream(stream)))
+    elif E > GATE_GROUPS_MAX_E or logit_bias is not None:
         fn = "mxmoe_moe_gate_wide" if E > GATE_GROUPS_MAX_E else "mxmoe_moe_gate_ex2"
         nat.check(nat.symbol(fn)(
             _ptr(hidden), _ptr(w_gate), _ptr(sg), T, H, E, topk, int(bool(renormalize)), GATE_SCORING[scoring], _ptr(e_bias),
@@ -338,11 +360,19 @@ def _launch_act(mode: str, glu: Optional["nat.MoeGluC"], src: torch.Tensor, src_
     src / src_shared: hidden (and hidden again for a shared expert) with ``perm`` in "gather" mode, else the
     gate_up outputs; dsegs / nseg: the device segment table; mask: ``_tag_mask`` of the segments' tags."""
     entry = _act_entry(mode, bool(mask & _MX_MASK), glu is not None)
+    if src.dtype != torch.float16:  # only the gather reads another element type (bf16 rows: mxmoe_moe_gather_quant)
+        if mode != "gather" or src.dtype not in _DT:
+            raise ValueError(f"the activation pass reads fp16 (the gather: fp16 or bf16 hidden states), got {src.dtype} "
+                             f"in mode {mode!r}")
+        entry = "mxmoe_moe_gather_quant"
     fn = nat.symbol(entry)  # (a library from before the entry refuses here)
     slots = (_ptr(src), _ptr(src_shared), T, topk, width, width_shared, _ptr(sorted_expert))
     segs = (_ptr(dsegs), nseg)
     stores = (_ptr(out), _ptr(scales), _stream(stream))
-    if entry == "mxmoe_moe_quant_act":
+    if entry == "mxmoe_moe_gather_quant":
+        st = fn(_DT[src.dtype], _ptr(src), T, width, topk, int(src_shared is not None), _ptr(sorted_expert), _ptr(perm), *segs,
+                mask, *stores)
+    elif entry == "mxmoe_moe_quant_act":
         st = fn(_ptr(src), T, width, topk, int(src_shared is not None), _ptr(sorted_expert), _ptr(perm), *segs, *stores)
     elif entry == "mxmoe_moe_act_quant":
         st = fn(_ACT_MODES[mode], *slots, _ptr(perm), *segs, mask, *stores)
@@ -385,7 +415,13 @@ def _act_pass(mode: str, glu, src: torch.Tensor, src_shared: Optional[torch.Tens
 def quant_act(hidden: torch.Tensor, r: Routing, qtags: Sequence[int], with_shared: bool,
               stream: Optional[torch.cuda.Stream] = None) -> ActBatch:
     """Gather hidden rows into expert order and quantise each expert's rows by its tag
-    (len(qtags) == E, or E + 1 with the shared expert last)."""
+    (len(qtags) == E, or E + 1 with the shared expert last). hidden: fp16, or bf16 (mxmoe_moe_gather_quant): each
+    element is then rounded to fp16 as it is loaded (to nearest even, +-Inf beyond fp16's range, fp16 subnormals kept)
+    and the stores are byte for byte those of ``quant_act(hidden.to(torch.float16), ...)`` — the experts compute on
+    fp16 values either way. Any other dtype raises."""
+    if hidden.dim() != 2:
+        raise ValueError("hidden must be [T, K]")
+    _check_io_dtype(hidden.dtype, "hidden")
     K = hidden.shape[1]
     h = hidden.contiguous()
     return _act_pass("gather", None, h, h if with_shared else None, r, qtags, K, K, stream)
@@ -413,16 +449,24 @@ def _f32(t: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
 def _launch_combine(out: torch.Tensor, y: torch.Tensor, inv_slot: torch.Tensor, sorted_expert: Optional[torch.Tensor],
                     weights: torch.Tensor, shared: Optional[torch.Tensor], shared_w: Optional[torch.Tensor], topk: int,
                     stream: Optional[torch.cuda.Stream] = None, down_bias: Optional[tuple] = None) -> None:
-    """The combine on preallocated device buffers (no allocation, one launch: graph-capturable): out [T, H] fp16,
+    """The combine on preallocated device buffers (no allocation, one launch: graph-capturable): out [T, H] fp16
+    (or bf16: mxmoe_moe_combine_dt rounds the same f32 accumulator to bf16; every input stays fp16),
     y [R, H] fp16 rows, inv_slot int32 [T*topk] rows of y, weights f32 [T, topk], shared fp16 [T, H] and shared_w
     f32 [T] or None. ``down_bias`` = (E, bias, shared_bias): mxmoe_moe_combine_bias, with the down projection's
     bias (fp16 [E, H], the expert of a slot from sorted_expert; the shared expert's fp16 [H]; either may be None)
     added to each down output before its weight (``MoEFFN.down_bias``: which layers run that kernel)."""
     T, H = out.shape
+    _check_io_dtype(out.dtype, "out")
     if down_bias is not None:
         E, bias, shared_bias = down_bias
         _check_bias(bias, (E, H), "bias", out.device)
         _check_bias(shared_bias, (H,), "shared_bias", out.device)
+    if out.dtype != torch.float16:  # (a layer without a down bias: no bias pointers, mxmoe_moe_combine's arithmetic)
+        E, bias, shared_bias = down_bias if down_bias is not None else (1, None, None)
+        st = nat.symbol("mxmoe_moe_combine_dt")(_DT[out.dtype], _ptr(y), _ptr(inv_slot), _ptr(sorted_expert), _ptr(weights),
+                                                _ptr(bias), _ptr(shared), _ptr(shared_w), _ptr(shared_bias), T, topk, E, H,
+                                                _ptr(out), _stream(stream))
+    elif down_bias is not None:
         st = nat.symbol("mxmoe_moe_combine_bias")(_ptr(y), _ptr(inv_slot), _ptr(sorted_expert), _ptr(weights), _ptr(bias),
                                                   _ptr(shared), _ptr(shared_w), _ptr(shared_bias), T, topk, E, H, _ptr(out),
                                                   _stream(stream))
@@ -433,9 +477,12 @@ def _launch_combine(out: torch.Tensor, y: torch.Tensor, inv_slot: torch.Tensor, 
 
 
 def combine(y: torch.Tensor, r: Routing, weights: torch.Tensor, shared: Optional[torch.Tensor] = None,
-            shared_w: Optional[torch.Tensor] = None, stream: Optional[torch.cuda.Stream] = None) -> torch.Tensor:
-    """out[t] = sum_k weights[t,k] * y[slot(t,k)] (+ shared_w[t] * shared[t]), f32 fma chain, fp16 out."""
-    out = torch.empty(r.T, y.shape[1], dtype=torch.float16, device=y.device)
+            shared_w: Optional[torch.Tensor] = None, stream: Optional[torch.cuda.Stream] = None,
+            out_dtype: torch.dtype = torch.float16) -> torch.Tensor:
+    """out[t] = sum_k weights[t,k] * y[slot(t,k)] (+ shared_w[t] * shared[t]), f32 fma chain, fp16 out
+    (``out_dtype=torch.bfloat16``: the same chain rounded to bf16)."""
+    _check_io_dtype(out_dtype, "out_dtype")
+    out = torch.empty(r.T, y.shape[1], dtype=out_dtype, device=y.device)
     _launch_combine(out, y, r.inv_slot, None, _f32(weights), shared, _f32(shared_w), r.topk, stream)
     return out
 
@@ -508,10 +555,12 @@ def combine_bias_into(out: torch.Tensor, y: torch.Tensor, inv_slot: torch.Tensor
 
 def combine_bias(y: torch.Tensor, r: Routing, weights: torch.Tensor, bias: Optional[torch.Tensor],
                  shared: Optional[torch.Tensor] = None, shared_w: Optional[torch.Tensor] = None,
-                 shared_bias: Optional[torch.Tensor] = None, stream: Optional[torch.cuda.Stream] = None) -> torch.Tensor:
+                 shared_bias: Optional[torch.Tensor] = None, stream: Optional[torch.cuda.Stream] = None,
+                 out_dtype: torch.dtype = torch.float16) -> torch.Tensor:
     """``combine`` for a down projection with a bias per expert: out[t] = sum_k weights[t,k] * (y[slot(t,k)] +
-    bias[expert(t,k)]) (+ shared_w[t] * (shared[t] + shared_bias)), f32 fma chain, fp16 out."""
-    out = torch.empty(r.T, y.shape[1], dtype=torch.float16, device=y.device)
+    bias[expert(t,k)]) (+ shared_w[t] * (shared[t] + shared_bias)), f32 fma chain, fp16 out (or ``out_dtype`` bf16)."""
+    _check_io_dtype(out_dtype, "out_dtype")
+    out = torch.empty(r.T, y.shape[1], dtype=out_dtype, device=y.device)
     combine_bias_into(out, y, r.inv_slot, r.sorted_expert, _f32(weights), bias, shared, _f32(shared_w), shared_bias, r.topk,
                       r.E, stream)
     return out
@@ -787,7 +836,12 @@ class MoEFFN:
 
     gate_up[e]: fp16 [2N, H] (gate rows then up rows), down[e]: fp16 [H, N]; qcfg[e] = (QParams of
     gate_up, QParams of down) — the activation side (a_bits, gsize) of each QParams sets how the
-    plumbing quantises that expert's input (qtag_of). Expert E (if given) is the shared expert."""
+    plumbing quantises that expert's input (qtag_of). Expert E (if given) is the shared expert.
+
+    hidden may be fp16 or bf16, and ``out`` has its dtype. A bf16 layer has no cast pass: the gather rounds each
+    hidden element to fp16 as it loads it (``quant_act``) and the combine rounds its f32 sums to bf16. The experts
+    themselves compute on fp16 values (a hidden value beyond fp16's range is +-Inf to them), h1 / y / the biases
+    stay fp16, and y is bit for bit the fp16 layer's on ``hidden.to(torch.float16)``."""
 
     # gate_up qcfgs with the SiLU epilogue: fp16 / w8a8 / w4a4 on every product kernel, weight-only
     # on the small-batch kernel (wo3; a large call of those falls back to the interleaved form)
@@ -966,7 +1020,7 @@ class MoEFFN:
         a2 = self.act_quant(h1, h1s, r, mode)
         g2, y, ys = self.down_call(a2, T, topk, dev)
         g2.launch()
-        out = torch.empty(T, self.H, dtype=torch.float16, device=dev)
+        out = torch.empty(T, self.H, dtype=hidden.dtype, device=dev)
         _launch_combine(out, y, r.inv_slot, r.sorted_expert, _f32(topk_weights), ys, _f32(shared_w), topk, None,
                         self.down_bias)
         if return_intermediates:
@@ -989,7 +1043,10 @@ def gptoss_layer(blocks_gate_up: torch.Tensor, scales_gate_up: torch.Tensor, bia
     ``pad_cols(hidden, layer.H)`` (and ``pad_cols(w_gate, layer.H)`` to the router) and slices the output.
     act_bits: 16 (w4a16_g32_sym_MXFP4), 8 (w4a8_g32_sym_MXFP8) or 4 (w4a4_g32_sym_MXFP4); ``a16_view`` / ``a8_view``
     give the others on the same tensors. ``scale_out_of_range`` of the layer: the checkpoint's scale bytes outside
-    [104, 140] (``prepare_weight_mx``; one warning for the layer)."""
+    [104, 140] (``prepare_weight_mx``; one warning for the layer).
+
+    bf16 hidden states: the layer takes them as every ``MoEFFN`` does (bf16 in, bf16 out, a bf16 ``w_gate`` in its
+    ``MoEBlock``); nothing here changes for them, and the biases stay fp16."""
     from .groupgemm import W4A4_MXFP4, W4A8_MXFP8, W4A16_MXFP4
 
     if act_bits not in (16, 8, 4):
@@ -1042,7 +1099,8 @@ def gptoss_layer(blocks_gate_up: torch.Tensor, scales_gate_up: torch.Tensor, bia
 class MoEBlock:
     """A MoE layer from hidden states: the router (``gate``) in front of a ``MoEFFN``.
 
-    w_gate: fp16 [E, H]; topk / renormalize: the model's routing (qwen2_moe: 4, DeepSeek-V2-Lite: 6,
+    w_gate: fp16 or bf16 [E, H] (w_shared_gate of the same dtype; ``forward`` takes hidden of that dtype and
+    returns it); topk / renormalize: the model's routing (qwen2_moe: 4, DeepSeek-V2-Lite: 6,
     both without renormalisation; Mixtral: 2 with); w_shared_gate: fp16 [H], qwen2_moe's
     shared_expert_gate (only for a layer with a shared expert); scoring, e_bias, n_group, topk_group,
     group_top, routed_scaling_factor: ``gate``'s (DeepSeek-V3 / V2, GLM-4.5); logit_bias: f32 [E], ``gate``'s
@@ -1059,6 +1117,9 @@ class MoEBlock:
             raise ValueError("w_shared_gate given for a layer without a shared expert")
         if w_shared_gate is not None and w_shared_gate.numel() != ffn.H:
             raise ValueError(f"w_shared_gate must hold {ffn.H} elements")
+        _check_io_dtype(w_gate.dtype, "w_gate")
+        if w_shared_gate is not None and w_shared_gate.dtype != w_gate.dtype:
+            raise ValueError(f"w_shared_gate must have w_gate's dtype ({w_gate.dtype}), got {w_shared_gate.dtype}")
         gate_routing_args(ffn.E, topk, scoring, e_bias, n_group, topk_group, group_top, routed_scaling_factor)
         _check_logit_bias(logit_bias, ffn.E)
         self.ffn, self.topk, self.renormalize = ffn, topk, renormalize
@@ -1070,6 +1131,8 @@ class MoEBlock:
         self.w_shared_gate = None if w_shared_gate is None else w_shared_gate.contiguous()
 
     def forward(self, hidden: torch.Tensor, return_intermediates: bool = False):
+        if hidden.dtype != self.w_gate.dtype:
+            raise ValueError(f"hidden must have the router's dtype ({self.w_gate.dtype}), got {hidden.dtype}")
         ids, wts, sw = gate(hidden, self.w_gate, self.topk, renormalize=self.renormalize,
                             w_shared_gate=self.w_shared_gate, **self.routing)
         res = self.ffn.forward(hidden, ids, wts, sw, return_intermediates=return_intermediates)
@@ -1095,7 +1158,7 @@ class PlannedForward:
         self.g1, self.h1, self.h1s, self.mode = layer.gate_up_call(self.a1, T, topk, dev)
         self.a2 = layer.act_quant(self.h1, self.h1s, r, self.mode)
         self.g2, self.y, self.ys = layer.down_call(self.a2, T, topk, dev)
-        self.out = torch.empty(T, layer.H, dtype=torch.float16, device=dev)
+        self.out = torch.empty(T, layer.H, dtype=hidden.dtype, device=dev)
         self.w = _f32(topk_weights)
         comb = functools.partial(_launch_combine, self.out, self.y, r.inv_slot, r.sorted_expert, self.w, self.ys, None, topk,
                                  None, layer.down_bias)
@@ -1125,9 +1188,17 @@ class GraphForward:
 
     SEG_STATUS_SHIFT = 4
 
-    def __init__(self, layer, T: int, topk: Optional[int] = None, device=None):
+    def __init__(self, layer, T: int, topk: Optional[int] = None, device=None, dtype: Optional[torch.dtype] = None):
+        """dtype: the element type of ``hidden`` and ``out`` (fp16 or bf16); default: the block's ``w_gate.dtype``
+        (which it must equal), fp16 for a bare ``MoEFFN``. Every buffer between the two ends is fp16."""
         self.block = layer if isinstance(layer, MoEBlock) else None
         self.ffn = ffn = layer.ffn if self.block is not None else layer
+        if dtype is None:
+            dtype = self.block.w_gate.dtype if self.block is not None else torch.float16
+        _check_io_dtype(dtype, "dtype")
+        if self.block is not None and dtype != self.block.w_gate.dtype:
+            raise ValueError(f"dtype = {dtype} differs from the block's router ({self.block.w_gate.dtype})")
+        self.dtype = dtype
         if self.block is not None:
             if topk is not None and topk != self.block.topk:
                 raise ValueError(f"topk = {topk} differs from the block's {self.block.topk}")
@@ -1198,7 +1269,7 @@ class GraphForward:
         self.y = torch.zeros(n, H, dtype=torch.float16, device=dev)
         self.ys = torch.zeros(T, H, dtype=torch.float16, device=dev) if shared else None
         self.g2 = plan(ffn.w2, self.a2, self.s2, ffn.tag2, self.y, self.ys, False)
-        self.out = torch.zeros(T, H, dtype=torch.float16, device=dev)
+        self.out = torch.zeros(T, H, dtype=dtype, device=dev)
         self._tables = (nat.MoeSegTableC * 2)(
             nat.MoeSegTableC(self.tags[0].data_ptr(), H, H if shared else 0, self.h1.shape[1], self.segs[0].data_ptr(),
                              self.dyn[0].data_ptr()),
@@ -1207,11 +1278,12 @@ class GraphForward:
     def launch(self, hidden: torch.Tensor, topk_ids: Optional[torch.Tensor] = None,
                topk_weights: Optional[torch.Tensor] = None, shared_w: Optional[torch.Tensor] = None,
                stream: Optional[torch.cuda.Stream] = None) -> torch.Tensor:
-        """Launches only; returns ``self.out`` (fp16 [T, H]). A MoEFFN takes int32 ids and f32 weights [T, topk]
+        """Launches only; returns ``self.out`` ([T, H] of ``self.dtype``, which hidden must have). A MoEFFN takes int32 ids and f32 weights [T, topk]
         (contiguous, as nothing may be converted here) and the optional f32 shared_w [T]; a MoEBlock routes itself."""
         ffn, T, topk = self.ffn, self.T, self.topk
-        if tuple(hidden.shape) != (T, ffn.H) or hidden.dtype != torch.float16 or not hidden.is_contiguous():
-            raise ValueError(f"hidden must be a contiguous fp16 [{T}, {ffn.H}] tensor")
+        if tuple(hidden.shape) != (T, ffn.H) or hidden.dtype != self.dtype or not hidden.is_contiguous():
+            raise ValueError(f"hidden must be a contiguous {self.dtype} [{T}, {ffn.H}] tensor, got {hidden.dtype} "
+                             f"{list(hidden.shape)}")
         if self.block is not None:
             if topk_ids is not None or topk_weights is not None or shared_w is not None:
                 raise ValueError("a MoEBlock routes itself: launch(hidden)")
@@ -1603,7 +1675,7 @@ def gate_composite(logits: torch.Tensor, topk: int, renormalize: bool = False, e
     return ids.to(torch.int32), wts
 
 
-def gate_bench(bs: int = 8192, model: str = "qwen2_moe", rounds: int = 4, iters: int = 30) -> dict:
+def gate_bench(bs: int = 8192, model: str = "qwen2_moe", rounds: int = 4, iters: int = 30, dtype: str = "fp16") -> dict:
     """The router kernel against the torch composite it replaces (fp16 matmul -> f32 softmax -> topk
     -> int32 ids, + sigmoid(hidden @ w_sg) for qwen2_moe; for ds3 / ds2_full the public group-limited
     routing code, ``gate_composite``), same process, interleaved round by round:
@@ -1613,18 +1685,22 @@ def gate_bench(bs: int = 8192, model: str = "qwen2_moe", rounds: int = 4, iters:
     "ds3" (DeepSeek-V3: H 7168, E 256, top-8, 8 groups / 4 kept, sigmoid + bias, renormalised, factor
     2.5), "ds2_full" (DeepSeek-V2: H 5120, E 160, top-6, 8 groups / 3 kept, softmax, factor 16), "kimi_k2"
     (H 7168, E 384, top-8, sigmoid + bias, renormalised, factor 2.827) or "qwen3_next" (H 2048, E 512, top-10,
-    softmax renormalised, shared gate)."""
+    softmax renormalised, shared gate). dtype: "fp16" or "bf16" — the operands of the kernel and of the composite's
+    matmul (the same random values rounded to that format)."""
     from .harness import time_launches
 
+    if dtype not in ("fp16", "bf16"):
+        raise ValueError(f"dtype must be 'fp16' or 'bf16', got {dtype!r}")
+    dt = torch.bfloat16 if dtype == "bf16" else torch.float16
     m = GATE_MODELS[model]
     H, E, topk = m["H"], m["E"], m["topk"]
     routing = dict(m.get("routing", {}))
     renorm = bool(m.get("renormalize", False))
     dev = "cuda"
     g = torch.Generator().manual_seed(0)
-    hidden = torch.randn(bs, H, generator=g).half().to(dev)
-    w_gate = (torch.randn(E, H, generator=g) * H ** -0.5).half().to(dev)
-    w_sg = (torch.randn(H, generator=g) * H ** -0.5).half().to(dev) if m["shared_gate"] else None
+    hidden = torch.randn(bs, H, generator=g).to(dt).to(dev)
+    w_gate = (torch.randn(E, H, generator=g) * H ** -0.5).to(dt).to(dev)
+    w_sg = (torch.randn(H, generator=g) * H ** -0.5).to(dt).to(dev) if m["shared_gate"] else None
     if m.get("bias"):
         routing["e_bias"] = (torch.randint(-64, 65, (E,), generator=g).float() / 256).to(dev)
     bufs = gate(hidden, w_gate, topk, renormalize=renorm, w_shared_gate=w_sg, **routing)
@@ -1655,7 +1731,7 @@ def gate_bench(bs: int = 8192, model: str = "qwen2_moe", rounds: int = 4, iters:
         return {"median_us": round(med, 2), "min_us": round(min(v), 2), "max_us": round(max(v), 2),
                 "spread": round((max(v) - min(v)) / med, 4)}
 
-    out = {"model": model, "bs": bs, "H": H, "E": E, "topk": topk, "shared_gate": w_sg is not None,
+    out = {"model": model, "bs": bs, "H": H, "E": E, "topk": topk, "dtype": dtype, "shared_gate": w_sg is not None,
            "kernel": side(res["kernel"]), "torch": side(res["torch"])}
     nbytes = bs * H * 2 + (E + 1) * H * 2 + bs * topk * 8 + (bs * 4 if w_sg is not None else 0)
     if routing:
