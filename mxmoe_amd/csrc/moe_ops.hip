@@ -14,19 +14,24 @@
 // codes as one 4-B (int4) / 8-B (int8) / 16-B (fp16) word per lane — no LDS tiling, no MFMA.
 // gpt-oss layers: the activation pass also comes with a bias row per expert and the clamped SwiGLU
 // (mxmoe_moe_glu_quant: the GLU builds of act_quant_kernel), the combine with a bias row per expert
-// (mxmoe_moe_combine_bias), the router with a bias on its logits (mxmoe_moe_gate_ex2); no reference counterpart.
+// (mxmoe_moe_combine_bias: combine_bias_kernel, the BIAS build of the combine's one loop), the router with a bias on
+// its logits (mxmoe_moe_gate_ex2); no reference counterpart.
 // The router in front of them (mxmoe_moe_gate: logits on the MFMA, top-k, softmax; mxmoe_moe_gate_ex:
 // sigmoid scores, selection bias, group-limited top-k) is moe_gate.h; beyond 256 experts (mxmoe_moe_gate_wide),
 // moe_gate_wide.h.
 // bf16 layers (mxmoe_moe_gate_dt, mxmoe_moe_gather_quant, mxmoe_moe_combine_dt): the element type of the router's
 // operands, of the gather's source rows and of the combine's output is a template parameter of the kernels above;
 // the fp16 instantiations are the kernels as they were. No reference counterpart (the reference is fp16 only).
+// What builds share exists once: the two block-scaled tags' amax, exponent and scale store (mx_block_amax, mx_exponent,
+// mx_store_scale), the two combine kernels' loop (combine_row), the choice of an activation build (launch_act_any) and
+// the entry points' post-launch and element-type checks (launched, dtype_check).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <string>
+#include <type_traits>
 
 #include "../../include/mxmoe_gg.h"
 #include "../../include/mxmoe_moe.h"
@@ -55,6 +60,18 @@ int fail(int code, const char* fmt, ...) {
   vsnprintf(buf, sizeof(buf), fmt, ap);
   va_end(ap);
   return detail::set_error(code, buf);
+}
+// after a launch: the runtime's verdict on it, under the kernel's name
+int launched(const char* kernel) {
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(MXMOE_GG_ERR_HIP, "%s launch failed: %s", kernel, hipGetErrorString(e));
+  return MXMOE_GG_OK;
+}
+// an element-type argument (what: its name in the entry point fn) must be one of the two MXMOE_DT_*
+int dtype_check(const char* fn, const char* what, int dtype) {
+  if (dtype != MXMOE_DT_FP16 && dtype != MXMOE_DT_BF16)
+    return fail(MXMOE_GG_ERR_INVALID, "%s: %s must be MXMOE_DT_FP16 or MXMOE_DT_BF16 (got %d)", fn, what, dtype);
+  return MXMOE_GG_OK;
 }
 
 constexpr int kThreads = 256;
@@ -246,6 +263,40 @@ __device__ __forceinline__ h8_t bf16x8_to_f16(const uint4& v) {
   return r;
 }
 
+// The block-scaled tags (OCP MXFP4 / MXFP8, include/mxmoe_gg.h): what the two share. A 32-element block is 4 adjacent
+// lanes of one chunk.
+// mx_block_amax: the block amax on the sign-cleared fp16 bit patterns as integers (their order is the values', with
+// Inf / NaN on top: a result >= 0x7C00 means an Inf or a NaN in the block)
+__device__ __forceinline__ uint32_t mx_block_amax(const h8_t& x) {
+  const uint4 w = __builtin_bit_cast(uint4, x);
+  const uint32_t cm = 0x7FFF7FFFu;
+  uint32_t m2 = max(max((w.x & cm) & 0xFFFFu, (w.x & cm) >> 16), max((w.y & cm) & 0xFFFFu, (w.y & cm) >> 16));
+  m2 = max(m2, max(max((w.z & cm) & 0xFFFFu, (w.z & cm) >> 16), max((w.w & cm) & 0xFFFFu, (w.w & cm) >> 16)));
+  m2 = max(m2, (uint32_t)__shfl_xor((int)m2, 1, 64));
+  m2 = max(m2, (uint32_t)__shfl_xor((int)m2, 2, 64));
+  return m2;
+}
+// mx_exponent: e = floor(log2 amax) - EOFF from the exponent field of f32(amax) (the conversion normalises fp16
+// subnormals; EOFF: the exponent of the element format's largest binade, 2 for e2m1 and 8 for e4m3), -127 for a
+// zero block, and inv = 2^-e (e in [-127, 15 - EOFF]), by which the elements are scaled exactly
+template <int EOFF>
+__device__ __forceinline__ int mx_exponent(uint32_t m2, float& inv) {
+  const float am = (float)__builtin_bit_cast(_Float16, (uint16_t)m2);
+  const int e = m2 == 0 ? -127 : (int)((__builtin_bit_cast(uint32_t, am) >> 23) & 0xFF) - 127 - EOFF;
+  inv = __builtin_bit_cast(float, (uint32_t)(127 - e) << 23);
+  return e;
+}
+// mx_store_scale (the block's first lane): the e8m0 byte of block blk of a row of nblk blocks whose scale bytes start
+// at so, at its permuted place in the row's 16-byte group (device layout); bad: a NaN scale
+__device__ __forceinline__ void mx_store_scale(uint8_t* so, int blk, int nblk, bool bad, int e) {
+  const int c16 = blk & 15;
+  so[(blk & ~15) + 4 * (c16 & 3) + (c16 >> 2)] = bad ? (uint8_t)255 : (uint8_t)(e + 127);
+  if (blk == nblk - 1) {  // the row's last block: the pads of its 16-byte group are 2^0
+#pragma clang loop unroll(disable) vectorize(disable)
+    for (int pc = c16 + 1; pc < 16; ++pc) so[(blk & ~15) + 4 * (pc & 3) + (pc >> 2)] = 127;
+  }
+}
+
 // One WAVE per slot row (4 rows per 256-thread workgroup): lane l holds elements c*512 + 8l .. +7
 // of chunk c in registers (MAXC chunks: rows up to MAXC*512 elements, MAXC = the launch's widest
 // row in 512-element chunks), so every lane has MAXC independent 16-B loads in flight, the
@@ -387,10 +438,8 @@ __global__ __launch_bounds__(kThreads) void act_quant_kernel(typename ActArgsOf<
     return;
   }
   if constexpr (MX) if (sg.qtag == MXMOE_ACT_MXFP4) {
-    // OCP MXFP4 (include/mxmoe_gg.h): a 32-element block is 4 adjacent lanes. Block amax on the
-    // sign-cleared fp16 bit patterns as integers (their order is the values', with Inf / NaN on top),
-    // e = floor(log2 amax) - 2 from the exponent field of f32(amax) (the conversion normalises fp16
-    // subnormals), elements scaled by 2^-e exactly and rounded to the e2m1 grid with v_rndne (an even
+    // OCP MXFP4 (include/mxmoe_gg.h): block amax, e = floor(log2 amax) - 2 and scale bytes by the mx_* helpers
+    // above, elements scaled by 2^-e exactly and rounded to the e2m1 grid with v_rndne (an even
     // multiple of the grid step is an even code in each of the three segments).
     const int srow = ((sg.width / 32 + 15) >> 4) << 4;  // scale bytes per row (device layout)
     uint8_t* const o4 = a.out + sg.out_off + (row * (int64_t)sg.width + col0) / 2;
@@ -400,17 +449,11 @@ __global__ __launch_bounds__(kThreads) void act_quant_kernel(typename ActArgsOf<
     for (int c = 0; c < MAXC; ++c) {
       if (c * 512 >= width) break;  // uniform
       const int idx = c * 512 + lane * 8;
-      const uint4 w = __builtin_bit_cast(uint4, x[c]);
-      const uint32_t cm = 0x7FFF7FFFu;
-      uint32_t m2 = max(max((w.x & cm) & 0xFFFFu, (w.x & cm) >> 16), max((w.y & cm) & 0xFFFFu, (w.y & cm) >> 16));
-      m2 = max(m2, max(max((w.z & cm) & 0xFFFFu, (w.z & cm) >> 16), max((w.w & cm) & 0xFFFFu, (w.w & cm) >> 16)));
-      m2 = max(m2, (uint32_t)__shfl_xor((int)m2, 1, 64));
-      m2 = max(m2, (uint32_t)__shfl_xor((int)m2, 2, 64));
+      const uint32_t m2 = mx_block_amax(x[c]);
       if (idx >= width) continue;
       const bool bad = m2 >= 0x7C00u;  // an Inf or a NaN in the block: NaN scale, zero codes
-      const float am = (float)__builtin_bit_cast(_Float16, (uint16_t)m2);
-      const int e = m2 == 0 ? -127 : (int)((__builtin_bit_cast(uint32_t, am) >> 23) & 0xFF) - 127 - 2;
-      const float inv = __builtin_bit_cast(float, (uint32_t)(127 - e) << 23);  // 2^-e (e in [-127, 13])
+      float inv;
+      const int e = mx_exponent<2>(m2, inv);
       uint32_t q = 0;
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
@@ -422,20 +465,13 @@ __global__ __launch_bounds__(kThreads) void act_quant_kernel(typename ActArgsOf<
         q |= nib << (4 * j);
       }
       *reinterpret_cast<uint32_t*>(o4 + idx / 2) = bad ? 0u : q;
-      if ((lane & 3) == 0) {
-        const int blk = (col0 + idx) >> 5, c16 = blk & 15;
-        so[(blk & ~15) + 4 * (c16 & 3) + (c16 >> 2)] = bad ? (uint8_t)255 : (uint8_t)(e + 127);
-        if (blk == nblk - 1) {  // the row's last block: the pads of its 16-byte group are 2^0
-#pragma clang loop unroll(disable) vectorize(disable)
-          for (int pc = c16 + 1; pc < 16; ++pc) so[(blk & ~15) + 4 * (pc & 3) + (pc >> 2)] = 127;
-        }
-      }
+      if ((lane & 3) == 0) mx_store_scale(so, (col0 + idx) >> 5, nblk, bad, e);
     }
     return;
   }
   if constexpr (MX) if (sg.qtag == MXMOE_ACT_MXFP8) {
     // OCP MXFP8, e4m3 elements (include/mxmoe_gg.h, w4a8_g32_sym_MXFP8): blocks, amax and scale bytes
-    // as the MXFP4 tag above with e = floor(log2 amax) - 8 (e4m3's largest binade); elements scaled by
+    // as the MXFP4 tag's with e = floor(log2 amax) - 8 (e4m3's largest binade); elements scaled by
     // 2^-e exactly, clamped to +-448 (v_med3_f32 keeps the sign of -0) and rounded ONCE to e4m3, to
     // nearest even, by the hardware convert (OCP e4m3 on gfx950). One code byte per element.
     const int srow = ((sg.width / 32 + 15) >> 4) << 4;  // scale bytes per row (device layout)
@@ -446,17 +482,11 @@ __global__ __launch_bounds__(kThreads) void act_quant_kernel(typename ActArgsOf<
     for (int c = 0; c < MAXC; ++c) {
       if (c * 512 >= width) break;  // uniform
       const int idx = c * 512 + lane * 8;
-      const uint4 w = __builtin_bit_cast(uint4, x[c]);
-      const uint32_t cm = 0x7FFF7FFFu;
-      uint32_t m2 = max(max((w.x & cm) & 0xFFFFu, (w.x & cm) >> 16), max((w.y & cm) & 0xFFFFu, (w.y & cm) >> 16));
-      m2 = max(m2, max(max((w.z & cm) & 0xFFFFu, (w.z & cm) >> 16), max((w.w & cm) & 0xFFFFu, (w.w & cm) >> 16)));
-      m2 = max(m2, (uint32_t)__shfl_xor((int)m2, 1, 64));
-      m2 = max(m2, (uint32_t)__shfl_xor((int)m2, 2, 64));
+      const uint32_t m2 = mx_block_amax(x[c]);
       if (idx >= width) continue;
       const bool bad = m2 >= 0x7C00u;  // an Inf or a NaN in the block: NaN scale, zero codes
-      const float am = (float)__builtin_bit_cast(_Float16, (uint16_t)m2);
-      const int e = m2 == 0 ? -127 : (int)((__builtin_bit_cast(uint32_t, am) >> 23) & 0xFF) - 127 - 8;
-      const float inv = __builtin_bit_cast(float, (uint32_t)(127 - e) << 23);  // 2^-e (e in [-127, 7])
+      float inv;
+      const int e = mx_exponent<8>(m2, inv);
       float y[8];
 #pragma unroll
       for (int j = 0; j < 8; ++j) y[j] = __builtin_amdgcn_fmed3f((float)x[c][j] * inv, -448.0f, 448.0f);  // product exact
@@ -466,14 +496,7 @@ __global__ __launch_bounds__(kThreads) void act_quant_kernel(typename ActArgsOf<
       q1 = __builtin_amdgcn_cvt_pk_fp8_f32(y[4], y[5], q1, false);
       q1 = __builtin_amdgcn_cvt_pk_fp8_f32(y[6], y[7], q1, true);
       *reinterpret_cast<uint2*>(o8 + idx) = bad ? uint2{0u, 0u} : uint2{(uint32_t)q0, (uint32_t)q1};
-      if ((lane & 3) == 0) {
-        const int blk = (col0 + idx) >> 5, c16 = blk & 15;
-        so[(blk & ~15) + 4 * (c16 & 3) + (c16 >> 2)] = bad ? (uint8_t)255 : (uint8_t)(e + 127);
-        if (blk == nblk - 1) {  // the row's last block: the pads of its 16-byte group are 2^0
-#pragma clang loop unroll(disable) vectorize(disable)
-          for (int pc = c16 + 1; pc < 16; ++pc) so[(blk & ~15) + 4 * (pc & 3) + (pc >> 2)] = 127;
-        }
-      }
+      if ((lane & 3) == 0) mx_store_scale(so, (col0 + idx) >> 5, nblk, bad, e);
     }
     return;
   }
@@ -532,47 +555,19 @@ __global__ __launch_bounds__(kThreads) void act_quant_kernel(typename ActArgsOf<
 
 // ---------------------------------------------------------------------------------------------
 // combine: one workgroup per token, 8 fp16 columns per lane and pass. OT: the output element, _Float16 (the kernel
-// as it was) or __bf16 (mxmoe_moe_combine_dt: the f32 accumulator rounded to bf16 to nearest even, v_cvt_pk_bf16_f32)
-template <class OT>
-__global__ __launch_bounds__(kThreads) void combine_kernel(const _Float16* __restrict__ y, const int32_t* __restrict__ inv,
-                                                           const float* __restrict__ w, const _Float16* __restrict__ shared,
-                                                           const float* __restrict__ shared_w, int topk, int H,
-                                                           OT* __restrict__ out) {
-  typedef OT o8_t __attribute__((ext_vector_type(8)));
-  const int64_t t = blockIdx.x;
-  for (int idx = threadIdx.x * 8; idx < H; idx += kChunk) {
-    float acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    for (int k = 0; k < topk; ++k) {
-      const int64_t slot = inv[t * topk + k];
-      const float wk = w[t * topk + k];
-      const h8_t v = *reinterpret_cast<const h8_t*>(y + slot * H + idx);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) acc[j] = fmaf(wk, (float)v[j], acc[j]);
-    }
-    if (shared) {
-      const float ws = shared_w ? shared_w[t] : 1.0f;
-      const h8_t v = *reinterpret_cast<const h8_t*>(shared + t * H + idx);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) acc[j] = fmaf(ws, (float)v[j], acc[j]);
-    }
-    o8_t r;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) r[j] = (OT)acc[j];
-    *reinterpret_cast<o8_t*>(out + t * H + idx) = r;
-  }
-}
-
-// combine with a bias row per expert on the down output (mxmoe_moe_combine_bias): the term of choice k is
+// as it was) or __bf16 (mxmoe_moe_combine_dt: the f32 accumulator rounded to bf16 to nearest even, v_cvt_pk_bf16_f32).
+// BIAS: the build with a bias row per expert on the down output (mxmoe_moe_combine_bias): the term of choice k is
 // f32(y) + f32(bias[e]) (one add), e = sorted[slot] — an id outside [0, E) (a stale slot) adds nothing — and the
-// shared term f32(shared) + f32(shared_bias). OT: as combine_kernel's
-template <class OT>
-__global__ __launch_bounds__(kThreads) void combine_bias_kernel(const _Float16* __restrict__ y, const int32_t* __restrict__ inv,
-                                                                const int32_t* __restrict__ sorted, const float* __restrict__ w,
-                                                                const _Float16* __restrict__ bias,
-                                                                const _Float16* __restrict__ shared,
-                                                                const float* __restrict__ shared_w,
-                                                                const _Float16* __restrict__ shared_bias, int topk, int E, int H,
-                                                                OT* __restrict__ out) {
+// shared term f32(shared) + f32(shared_bias); either pointer may be NULL. BIAS = false: none of that code exists and
+// sorted, bias, shared_bias and E are not read.
+// One body under two kernels, each with the arguments its build reads: one argument list for both moved the
+// kernel-argument loads of whichever build did not keep its own layout (profiles/r16/plumbing_dedupe/).
+template <class OT, bool BIAS>
+__device__ __forceinline__ void combine_row(const _Float16* __restrict__ y, const int32_t* __restrict__ inv,
+                                            const int32_t* __restrict__ sorted, const float* __restrict__ w,
+                                            const _Float16* __restrict__ bias, const _Float16* __restrict__ shared,
+                                            const float* __restrict__ shared_w, const _Float16* __restrict__ shared_bias,
+                                            int topk, int E, int H, OT* __restrict__ out) {
   typedef OT o8_t __attribute__((ext_vector_type(8)));
   const int64_t t = blockIdx.x;
   for (int idx = threadIdx.x * 8; idx < H; idx += kChunk) {
@@ -581,7 +576,8 @@ __global__ __launch_bounds__(kThreads) void combine_bias_kernel(const _Float16* 
       const int64_t slot = inv[t * topk + k];
       const float wk = w[t * topk + k];
       const h8_t v = *reinterpret_cast<const h8_t*>(y + slot * H + idx);
-      const int e = bias ? sorted[slot] : -1;
+      int e = -1;  // the expert whose bias row the term takes
+      if constexpr (BIAS) e = bias ? sorted[slot] : -1;
       if (e >= 0 && e < E) {  // workgroup-uniform
         const h8_t b = *reinterpret_cast<const h8_t*>(bias + (int64_t)e * H + idx);
 #pragma unroll
@@ -594,7 +590,9 @@ __global__ __launch_bounds__(kThreads) void combine_bias_kernel(const _Float16* 
     if (shared) {
       const float ws = shared_w ? shared_w[t] : 1.0f;
       const h8_t v = *reinterpret_cast<const h8_t*>(shared + t * H + idx);
-      if (shared_bias) {
+      bool sb = false;
+      if constexpr (BIAS) sb = shared_bias != nullptr;
+      if (sb) {
         const h8_t b = *reinterpret_cast<const h8_t*>(shared_bias + idx);
 #pragma unroll
         for (int j = 0; j < 8; ++j) acc[j] = fmaf(ws, (float)v[j] + (float)b[j], acc[j]);
@@ -608,6 +606,23 @@ __global__ __launch_bounds__(kThreads) void combine_bias_kernel(const _Float16* 
     for (int j = 0; j < 8; ++j) r[j] = (OT)acc[j];
     *reinterpret_cast<o8_t*>(out + t * H + idx) = r;
   }
+}
+template <class OT>
+__global__ __launch_bounds__(kThreads) void combine_kernel(const _Float16* __restrict__ y, const int32_t* __restrict__ inv,
+                                                           const float* __restrict__ w, const _Float16* __restrict__ shared,
+                                                           const float* __restrict__ shared_w, int topk, int H,
+                                                           OT* __restrict__ out) {
+  combine_row<OT, false>(y, inv, nullptr, w, nullptr, shared, shared_w, nullptr, topk, 0, H, out);
+}
+template <class OT>
+__global__ __launch_bounds__(kThreads) void combine_bias_kernel(const _Float16* __restrict__ y, const int32_t* __restrict__ inv,
+                                                                const int32_t* __restrict__ sorted, const float* __restrict__ w,
+                                                                const _Float16* __restrict__ bias,
+                                                                const _Float16* __restrict__ shared,
+                                                                const float* __restrict__ shared_w,
+                                                                const _Float16* __restrict__ shared_bias, int topk, int E, int H,
+                                                                OT* __restrict__ out) {
+  combine_row<OT, true>(y, inv, sorted, w, bias, shared, shared_w, shared_bias, topk, E, H, out);
 }
 
 bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
@@ -714,28 +729,23 @@ static void launch_act_w(const typename ActArgsOf<GLU>::type& a, int maxw, hipSt
   else hipLaunchKernelGGL((act_quant_kernel<MODE, 32, MX, GLU, SRCBF>), grid, block, 0, st, a);
 }
 
-template <int MODE, bool SRCBF = false>
-static void launch_act_m(const ActArgs& a, int maxw, bool mx, hipStream_t st) {
-  if (mx) launch_act_w<MODE, true, kGluNone, SRCBF>(a, maxw, st);
-  else launch_act_w<MODE, false, kGluNone, SRCBF>(a, maxw, st);
-}
 constexpr int kModeGatherBf16 = 4;  // launch_act_any's number for mode 0 on bf16 rows (no mode of the C interface)
 // (mode, mx): which build of the kernel; ActArgs: the four passes, GluArgs: mxmoe_moe_glu_quant's (mode = MXMOE_GLU_*)
-static void launch_act_any(int mode, const ActArgs& a, int maxw, bool mx, hipStream_t st) {
-  if (mode == 1) launch_act_m<1>(a, maxw, mx, st);
-  else if (mode == 2) launch_act_m<2>(a, maxw, mx, st);
-  else if (mode == 3) launch_act_m<3>(a, maxw, mx, st);
-  else if (mode == kModeGatherBf16) launch_act_m<0, true>(a, maxw, mx, st);
-  else launch_act_m<0>(a, maxw, mx, st);
-}
-static void launch_act_any(int act, const GluArgs& a, int maxw, bool mx, hipStream_t st) {
-  if (act == MXMOE_GLU_SWIGLU_CLAMP) {
-    if (mx) launch_act_w<1, true, kGluSwigluClamp>(a, maxw, st);
-    else launch_act_w<1, false, kGluSwigluClamp>(a, maxw, st);
-  } else {
-    if (mx) launch_act_w<1, true, kGluSilu>(a, maxw, st);
-    else launch_act_w<1, false, kGluSilu>(a, maxw, st);
-  }
+template <class ARGS>
+static void launch_act_any(int mode, const ARGS& a, int maxw, bool mx, hipStream_t st) {
+  const auto go = [&](auto mx_build) {
+    constexpr bool MX = decltype(mx_build)::value;
+    if constexpr (std::is_same<ARGS, GluArgs>::value) {
+      if (mode == MXMOE_GLU_SWIGLU_CLAMP) launch_act_w<1, MX, kGluSwigluClamp>(a, maxw, st);
+      else launch_act_w<1, MX, kGluSilu>(a, maxw, st);
+    } else if (mode == 1) launch_act_w<1, MX>(a, maxw, st);
+    else if (mode == 2) launch_act_w<2, MX>(a, maxw, st);
+    else if (mode == 3) launch_act_w<3, MX>(a, maxw, st);
+    else if (mode == kModeGatherBf16) launch_act_w<0, MX, kGluNone, true>(a, maxw, st);
+    else launch_act_w<0, MX>(a, maxw, st);
+  };
+  if (mx) go(std::true_type{});
+  else go(std::false_type{});
 }
 // slots [0, nslots): one launch; rows of different widths (routed [0, ntk), shared [ntk, nslots)):
 // one launch with each shared row split over a workgroup's 4 waves when a quarter of the shared row
@@ -764,9 +774,7 @@ static int launch_act(int mode, ARGS a, int64_t nslots, int w_routed, int w_shar
       launch_act_any(mode, a, w_shared, mx, (hipStream_t)stream);
     }
   }
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(MXMOE_GG_ERR_HIP, "act_quant_kernel launch failed: %s", hipGetErrorString(e));
-  return MXMOE_GG_OK;
+  return launched("act_quant_kernel");
 }
 
 // the activation entry points' bodies; mx: the call's segments may carry MXMOE_ACT_MXFP4
@@ -822,12 +830,12 @@ static int combine_check(const char* fn, const void* y, const int32_t* inv_slot,
   return MXMOE_GG_OK;
 }
 
-// mxmoe_moe_combine_bias and mxmoe_moe_combine_dt: the checks, then combine_kernel without any bias (the arithmetic of
-// mxmoe_moe_combine) or combine_bias_kernel, on the output type OT
+// the combine's launch (T > 0, arguments checked) on the output type OT. plain: combine_kernel, which takes neither
+// sorted_expert nor the bias pointers nor E; else combine_bias_kernel
 template <class OT>
-static void launch_combine(const void* y, const int32_t* inv_slot, const int32_t* sorted_expert, const float* weights,
-                           const void* bias, const void* shared, const float* shared_w, const void* shared_bias, int64_t T,
-                           int topk, int E, int H, void* out, bool plain, void* stream) {
+static int launch_combine(const void* y, const int32_t* inv_slot, const int32_t* sorted_expert, const float* weights,
+                          const void* bias, const void* shared, const float* shared_w, const void* shared_bias, int64_t T,
+                          int topk, int E, int H, void* out, bool plain, void* stream) {
   if (plain)
     hipLaunchKernelGGL(combine_kernel<OT>, dim3((unsigned)T), dim3(kThreads), 0, (hipStream_t)stream,
                        static_cast<const _Float16*>(y), inv_slot, weights, static_cast<const _Float16*>(shared), shared_w,
@@ -837,14 +845,16 @@ static void launch_combine(const void* y, const int32_t* inv_slot, const int32_t
                        static_cast<const _Float16*>(y), inv_slot, sorted_expert, weights, static_cast<const _Float16*>(bias),
                        static_cast<const _Float16*>(shared), shared_w, static_cast<const _Float16*>(shared_bias), topk, E, H,
                        static_cast<OT*>(out));
+  return launched(plain ? "combine_kernel" : "combine_bias_kernel");
 }
-// dt_entry: mxmoe_moe_combine_dt (a call without any bias runs combine_kernel; mxmoe_moe_combine_bias always its own)
+// mxmoe_moe_combine_bias and mxmoe_moe_combine_dt: the checks, then the launch. dt_entry: mxmoe_moe_combine_dt (a call
+// without any bias runs the build without, the arithmetic of mxmoe_moe_combine; mxmoe_moe_combine_bias always the
+// bias build)
 static int combine_bias_impl(const char* fn, bool dt_entry, int out_dtype, const void* y, const int32_t* inv_slot,
                              const int32_t* sorted_expert, const float* weights, const void* bias, const void* shared,
                              const float* shared_w, const void* shared_bias, int64_t T, int topk, int E, int H, void* out,
                              void* stream) {
-  if (out_dtype != MXMOE_DT_FP16 && out_dtype != MXMOE_DT_BF16)
-    return fail(MXMOE_GG_ERR_INVALID, "%s: out_dtype must be MXMOE_DT_FP16 or MXMOE_DT_BF16 (got %d)", fn, out_dtype);
+  if (int st = dtype_check(fn, "out_dtype", out_dtype)) return st;
   if (T < 0 || topk <= 0 || H <= 0 || H % 8 || E < 1)
     return fail(MXMOE_GG_ERR_INVALID, "%s: need H %% 8 == 0, topk > 0, E >= 1 (H=%d E=%d)", fn, H, E);
   if (!aligned16(bias) || !aligned16(shared_bias) || (shared_bias && !shared))
@@ -852,16 +862,8 @@ static int combine_bias_impl(const char* fn, bool dt_entry, int out_dtype, const
   if (T == 0) return MXMOE_GG_OK;
   if (int st = combine_check(fn, y, inv_slot, weights, shared, out, bias && !sorted_expert)) return st;
   const bool plain = dt_entry && !bias && !shared_bias;
-  if (out_dtype == MXMOE_DT_BF16)
-    launch_combine<__bf16>(y, inv_slot, sorted_expert, weights, bias, shared, shared_w, shared_bias, T, topk, E, H, out, plain,
-                           stream);
-  else
-    launch_combine<_Float16>(y, inv_slot, sorted_expert, weights, bias, shared, shared_w, shared_bias, T, topk, E, H, out,
-                             plain, stream);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess)
-    return fail(MXMOE_GG_ERR_HIP, "%s launch failed: %s", plain ? "combine_kernel" : "combine_bias_kernel", hipGetErrorString(e));
-  return MXMOE_GG_OK;
+  const auto launch = out_dtype == MXMOE_DT_BF16 ? launch_combine<__bf16> : launch_combine<_Float16>;
+  return launch(y, inv_slot, sorted_expert, weights, bias, shared, shared_w, shared_bias, T, topk, E, H, out, plain, stream);
 }
 
 // what mxmoe_moe_gate and mxmoe_moe_gate_ex check alike, before any HIP call
@@ -885,8 +887,7 @@ static int gate_ex_impl(const char* fn, const void* hidden, const void* w_gate, 
                         int group_top, float routed_scale, const float* logit_bias, int32_t* topk_ids, float* topk_weights,
                         float* shared_w, float* logits, float* scores, void* stream, int max_e = 256,
                         int dtype = MXMOE_DT_FP16) {
-  if (dtype != MXMOE_DT_FP16 && dtype != MXMOE_DT_BF16)
-    return fail(MXMOE_GG_ERR_INVALID, "%s: dtype must be MXMOE_DT_FP16 or MXMOE_DT_BF16 (got %d)", fn, dtype);
+  if (int st = dtype_check(fn, "dtype", dtype)) return st;
   if (scoring != MXMOE_GATE_SOFTMAX && scoring != MXMOE_GATE_SIGMOID)
     return fail(MXMOE_GG_ERR_INVALID, "%s: scoring must be MXMOE_GATE_SOFTMAX or MXMOE_GATE_SIGMOID (got %d)", fn, scoring);
   const int st = gate_check(fn, hidden, w_gate, w_shared_gate, T, H, E, topk, topk_ids, topk_weights, shared_w, max_e);
@@ -921,10 +922,7 @@ static int gate_ex_impl(const char* fn, const void* hidden, const void* w_gate, 
   } else if (E > 256) gate::gate_wide_launch(gate::GateBiasArgs{m, logit_bias}, sigmoid, hs);
   else if (logit_bias) gate::gate_modes_launch(gate::GateBiasArgs{m, logit_bias}, sigmoid, hs);
   else gate::gate_modes_launch(m, sigmoid, hs);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess)
-    return fail(MXMOE_GG_ERR_HIP, "%s launch failed: %s", E > 256 ? "gate_wide_kernel" : "gate_modes_kernel", hipGetErrorString(e));
-  return MXMOE_GG_OK;
+  return launched(E > 256 ? "gate_wide_kernel" : "gate_modes_kernel");
 }
 
 extern "C" {
@@ -938,9 +936,7 @@ int mxmoe_moe_gate(const void* hidden, const void* w_gate, const void* w_shared_
                          static_cast<const _Float16*>(w_shared_gate), T, H, E, topk, renormalize != 0, topk_ids,
                          topk_weights, shared_w, logits};
   gate::gate_launch(a, (hipStream_t)stream);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(MXMOE_GG_ERR_HIP, "gate_kernel launch failed: %s", hipGetErrorString(e));
-  return MXMOE_GG_OK;
+  return launched("gate_kernel");
 }
 
 int mxmoe_moe_gate_ex(const void* hidden, const void* w_gate, const void* w_shared_gate, int64_t T, int H, int E, int topk,
@@ -989,9 +985,7 @@ int mxmoe_moe_route(const int32_t* topk_ids, int64_t T, int topk, int E, int32_t
   if (!counts) return fail(MXMOE_GG_ERR_INVALID, "mxmoe_moe_route: NULL counts");
   hipLaunchKernelGGL(route_kernel, dim3(E), dim3(kRouteThreads), 0, (hipStream_t)stream, topk_ids, (int)(T * topk), topk,
                      sorted_expert, perm_token, inv_slot, counts);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(MXMOE_GG_ERR_HIP, "route_kernel launch failed: %s", hipGetErrorString(e));
-  return MXMOE_GG_OK;
+  return launched("route_kernel");
 }
 
 int mxmoe_moe_segments(const int32_t* counts, int E, int64_t T, int topk, int with_shared,
@@ -1004,9 +998,7 @@ int mxmoe_moe_segments(const int32_t* counts, int E, int64_t T, int topk, int wi
     a.tables[t] = tables[t];
   }
   hipLaunchKernelGGL(segments_kernel, dim3(1), dim3(kThreads), 0, (hipStream_t)stream, a);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(MXMOE_GG_ERR_HIP, "segments_kernel launch failed: %s", hipGetErrorString(e));
-  return MXMOE_GG_OK;
+  return launched("segments_kernel");
 }
 
 int mxmoe_moe_segments_host(const int32_t* counts, int E, int64_t T, int topk, int with_shared,
@@ -1030,8 +1022,7 @@ int mxmoe_moe_gather_quant(int dtype, const void* hidden, int64_t T, int K, int 
                            const int32_t* sorted_expert, const int32_t* perm_token, const mxmoe_moe_seg* segs, int nseg,
                            uint32_t tag_mask, void* out, void* scales, void* stream) {
   const char* fn = "mxmoe_moe_gather_quant";
-  if (dtype != MXMOE_DT_FP16 && dtype != MXMOE_DT_BF16)
-    return fail(MXMOE_GG_ERR_INVALID, "%s: dtype must be MXMOE_DT_FP16 or MXMOE_DT_BF16 (got %d)", fn, dtype);
+  if (int st = dtype_check(fn, "dtype", dtype)) return st;
   bool mx = false;
   if (int st = tag_mask_mx(fn, tag_mask, &mx)) return st;
   return quant_act_impl(fn, hidden, T, K, topk, with_shared, sorted_expert, perm_token, segs, nseg, out, scales, stream, mx,
@@ -1117,12 +1108,8 @@ int mxmoe_moe_combine(const void* y, const int32_t* inv_slot, const float* weigh
     return fail(MXMOE_GG_ERR_INVALID, "mxmoe_moe_combine: need H %% 8 == 0, topk > 0 (H=%d)", H);
   if (T == 0) return MXMOE_GG_OK;
   if (int st = combine_check("mxmoe_moe_combine", y, inv_slot, weights, shared, out)) return st;
-  hipLaunchKernelGGL(combine_kernel<_Float16>, dim3((unsigned)T), dim3(kThreads), 0, (hipStream_t)stream,
-                     static_cast<const _Float16*>(y), inv_slot, weights, static_cast<const _Float16*>(shared), shared_w,
-                     topk, H, static_cast<_Float16*>(out));
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(MXMOE_GG_ERR_HIP, "combine_kernel launch failed: %s", hipGetErrorString(e));
-  return MXMOE_GG_OK;
+  return launch_combine<_Float16>(y, inv_slot, nullptr, weights, nullptr, shared, shared_w, nullptr, T, topk, 0, H, out, true,
+                                  stream);
 }
 
 }  // extern "C"

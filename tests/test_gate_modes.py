@@ -13,6 +13,7 @@ import torch
 
 from mxmoe_amd import _native as nat
 from mxmoe_amd import moe
+from mxmoe_amd.moe_bench import GATE_MODELS, gate_composite
 from tests import _gate_modes_ref as mref
 from tests import _gate_ref as ref
 
@@ -93,8 +94,8 @@ def test_reference_matches_deepseek_v2():
 
 @pytest.mark.parametrize("model", ["ds3", "ds2_full"])
 def test_bench_composite_routes_as_the_reference(model):
-    """moe.gate_composite (gate_bench's yardstick for the two new models) on the CPU, small T."""
-    m = moe.GATE_MODELS[model]
+    """moe_bench.gate_composite (gate_bench's yardstick for the two new models) on the CPU, small T."""
+    m = GATE_MODELS[model]
     E, k, routing = m["E"], m["topk"], dict(m["routing"])
     hidden, w = ref.random_data(32, 128, E, seed=14)
     x = ref.logits_f64(hidden, w)
@@ -102,7 +103,7 @@ def test_bench_composite_routes_as_the_reference(model):
     renorm = bool(m.get("renormalize", False))
     scale = routing.pop("routed_scaling_factor")
     ids, wts, _, _ = mref.gate(hidden, w, k, e_bias=bias, renormalize=renorm, routed_scale=scale, **routing)
-    ti, tw = moe.gate_composite(torch.from_numpy(x), k, renorm, None if bias is None else torch.from_numpy(bias).double(),
+    ti, tw = gate_composite(torch.from_numpy(x), k, renorm, None if bias is None else torch.from_numpy(bias).double(),
                                 routed_scaling_factor=scale, **routing)
     assert ti.dtype == torch.int32 and (ids == ti.numpy()).all()
     assert np.abs(wts - tw.numpy()).max() <= 1e-12 * scale

@@ -11,6 +11,7 @@ import torch
 
 from mxmoe_amd import _native as nat
 from mxmoe_amd import moe
+from mxmoe_amd.moe_bench import GATE_MODELS, gate_composite
 from tests import _gate_modes_ref as mref
 from tests import _gate_ref as ref
 from tests import _gate_wide_ref as wref
@@ -110,9 +111,9 @@ def test_by_construction_inputs_keep_their_margins(case):
 
 @pytest.mark.parametrize("model", ["kimi_k2", "qwen3_next"])
 def test_bench_composite_routes_as_the_reference(model):
-    """moe.gate_composite (gate_bench's yardstick) on the two models with more than 256 experts, on the CPU at small
+    """moe_bench.gate_composite (gate_bench's yardstick) on the two models with more than 256 experts, on the CPU at small
     T, on the rows whose f64 margins exceed what f64 rounding in either implementation can move."""
-    m = moe.GATE_MODELS[model]
+    m = GATE_MODELS[model]
     E, k, routing = m["E"], m["topk"], dict(m["routing"])
     assert E > 256 and routing.get("n_group", 1) == 1
     moe.gate_routing_args(E, k, **{kk: v for kk, v in routing.items()})
@@ -126,7 +127,7 @@ def test_bench_composite_routes_as_the_reference(model):
     em, _ = mref.decision_margins(v, k)
     ok = em > 1e-9
     assert ok.sum() >= 0.9 * len(ok)
-    ti, tw = moe.gate_composite(torch.from_numpy(x), k, renorm, None if bias is None else torch.from_numpy(bias).double(),
+    ti, tw = gate_composite(torch.from_numpy(x), k, renorm, None if bias is None else torch.from_numpy(bias).double(),
                                 routed_scaling_factor=scale, **routing)
     assert ti.dtype == torch.int32 and (ids[ok] == ti.numpy()[ok]).all()
     assert np.abs(wts[ok] - tw.numpy()[ok]).max() <= 1e-12 * scale

@@ -1,4 +1,4 @@
-"""Print mxmoe_amd.moe.gate_bench (the router kernel against the torch composite) as JSON lines:
+"""Print mxmoe_amd.moe_bench.gate_bench (the router kernel against the torch composite) as JSON lines:
     python tools/gate_bench.py [--bs 8192 128] [--models qwen2_moe ds2 ds3 ds2_full kimi_k2 qwen3_next]
                                [--dtype fp16 bf16] [--out FILE]"""
 from __future__ import annotations
@@ -10,14 +10,14 @@ import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-from mxmoe_amd.moe import gate_bench  # noqa: E402
+from mxmoe_amd.moe_bench import gate_bench  # noqa: E402
 
 
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--bs", type=int, nargs="+", default=[8192, 128])
     ap.add_argument("--models", nargs="+", default=["qwen2_moe", "ds2"],
-                    help="qwen2_moe ds2 ds3 ds2_full kimi_k2 qwen3_next (mxmoe_amd.moe.GATE_MODELS)")
+                    help="qwen2_moe ds2 ds3 ds2_full kimi_k2 qwen3_next (mxmoe_amd.moe_bench.GATE_MODELS)")
     ap.add_argument("--dtype", nargs="+", default=["fp16"], choices=["fp16", "bf16"],
                     help="the operands' element type; both: each shape with the two dtypes back to back")
     ap.add_argument("--rounds", type=int, default=4)

@@ -4,7 +4,7 @@ router logit bias) at bs 1 / 16 / 128 / 512 / 2048, with fp16 (a16) and MXFP8 (a
   (b) PlannedForward — device time of the host-planned step;
   (c) GraphForward replayed from a captured graph — wall and device time;
 and the biased clamped activation pass against the SiLU pass, combine_bias against combine, at the same shape, in one
-process with the sides alternating over rounds (moe.gptoss_bench). One JSON line per (act_bits, bs); --out also writes
+process with the sides alternating over rounds (moe_bench.gptoss_bench). One JSON line per (act_bits, bs); --out also writes
 the list to a file (profiles/<round>/gptoss/bench.json).
 
 python tools/gptoss_bench.py [--rounds 4] [--iters 20] [--batches 1,16,128,512,2048] [--act-bits 16,8] [--out FILE]
@@ -18,7 +18,7 @@ import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-from mxmoe_amd import moe  # noqa: E402
+from mxmoe_amd import moe_bench  # noqa: E402
 
 
 def main():
@@ -32,7 +32,7 @@ def main():
     results = []
     batches = [int(b) for b in args.batches.split(",") if b]
     for bits in [int(b) for b in args.act_bits.split(",") if b]:
-        for r in moe.gptoss_bench(batches, bits, args.rounds, args.iters):
+        for r in moe_bench.gptoss_bench(batches, bits, args.rounds, args.iters):
             print(json.dumps(r), flush=True)
             results.append(r)
     if args.out:
@@ -40,7 +40,7 @@ def main():
         with open(args.out, "w") as f:
             json.dump(results, f, indent=1)
             f.write("\n")
-    # (the graph replay is bit-identical to the eager call only where no host plan split K: moe.gptoss_bench)
+    # (the graph replay is bit-identical to the eager call only where no host plan split K: moe_bench.gptoss_bench)
     if not all(r["planned_bit_identical_to_eager"] and r["status"] == 0 and
                (r["bit_identical_to_eager"] or max(r["host_splitk_slabs"]) > 0) for r in results):
         sys.exit(1)

@@ -3,7 +3,7 @@ w4a4 + w8a8) at bs 1 / 16 / 128 / 512 / 2048 and the DeepSeek-V2-Lite mixed laye
   (a) eager MoEFFN.forward — wall time per call, one synchronise per call;
   (b) PlannedForward — device time of the host-planned step (the lower bound: XCD packing, split-K);
   (c) GraphForward replayed from a captured graph — wall and device time,
-in one process with the sides alternating over rounds (moe.graph_forward_bench). One JSON line per (model, bs);
+in one process with the sides alternating over rounds (moe_bench.graph_forward_bench). One JSON line per (model, bs);
 --out also writes the list to a file (profiles/<round>/graph_forward/bench.json).
 
 python tools/graph_bench.py [--rounds 4] [--iters 20] [--batches 1,16,128,512,2048] [--ds2 128] [--out FILE]
@@ -17,7 +17,7 @@ import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-from mxmoe_amd import moe  # noqa: E402
+from mxmoe_amd import moe_bench  # noqa: E402
 
 
 def main():
@@ -33,7 +33,7 @@ def main():
         batches = [int(b) for b in spec.split(",") if b]
         if not batches:
             continue
-        for r in moe.graph_forward_bench(batches, model, args.rounds, args.iters):
+        for r in moe_bench.graph_forward_bench(batches, model, args.rounds, args.iters):
             print(json.dumps(r), flush=True)
             results.append(r)
     if args.out:

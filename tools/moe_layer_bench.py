@@ -1,6 +1,6 @@
 """One qwen2_moe layer-11 MoE FFN step at bs=8192 (LP-1 mixed w4a4 + w8a8 qconfig, routed histogram of
 the committed workload, random weights) on the device, unfused (silu_mul_quant) against the fused
-SiLU epilogue (MXMOE_GG_EPI_SILU_MUL + quant_slots): moe.qwen2_layer_bench — per-stage and step
+SiLU epilogue (MXMOE_GG_EPI_SILU_MUL + quant_slots): moe_bench.qwen2_layer_bench — per-stage and step
 times, outputs checked bit-identical.
 
 python tools/moe_layer_bench.py [--rounds 4] [--iters 30] > gpurun_out/moe_layer.json
@@ -20,7 +20,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 import torch  # noqa: E402
 
-from mxmoe_amd import moe  # noqa: E402
+from mxmoe_amd import moe_bench  # noqa: E402
 
 
 def bf16_layer_bench(batches=(128, 8192), rounds: int = 4, iters: int = 20):
@@ -33,11 +33,9 @@ def bf16_layer_bench(batches=(128, 8192), rounds: int = 4, iters: int = 20):
     Each as eager ``GraphForward.launch`` calls and as a captured-graph replay: device time (events around ``iters``
     back-to-back runs) and wall time per run with a synchronise. Per side the median of the rounds' medians with
     min / max (us), and native / wrap ratios."""
-    import time
-
     from mxmoe_amd.groupgemm import QParams
-    from mxmoe_amd.harness import time_launches
     from mxmoe_amd.moe import GraphForward, MoEBlock, MoEFFN
+    from mxmoe_amd.moe_bench import _captured, _device, _rounds, _stat, _wall
     from mxmoe_amd.workload import load_workload, mixed_qconfig_lp1, qwen2_layer11_workload
 
     shapes, topk = load_workload(qwen2_layer11_workload(8192, qconfig=mixed_qconfig_lp1()))["layer-11"], 4
@@ -56,18 +54,6 @@ def bf16_layer_bench(batches=(128, 8192), rounds: int = 4, iters: int = 20):
     blk_b = MoEBlock(ffn, w_gate, topk, w_shared_gate=w_sg)
     blk_h = MoEBlock(ffn, w_gate.half(), topk, w_shared_gate=w_sg.half())
 
-    def captured(fn):
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            fn()
-        side.synchronize()
-        graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph, stream=side):
-            fn()
-        torch.cuda.current_stream().wait_stream(side)
-        return graph
-
     def one(bs: int) -> dict:
         hidden = torch.randn(bs, H, generator=g).to(torch.bfloat16).to(dev)
         gf_b, gf_h = GraphForward(blk_b, bs), GraphForward(blk_h, bs)
@@ -82,38 +68,16 @@ def bf16_layer_bench(batches=(128, 8192), rounds: int = 4, iters: int = 20):
             gf_h.launch(h16)
             out_b.copy_(gf_h.out)
 
-        g_native, g_wrap = captured(native), captured(wrap)
+        g_native, g_wrap = _captured(native), _captured(wrap)
         torch.cuda.synchronize()
 
-        def wall(fn):
-            ts = []
-            for i in range(iters + 3):
-                t0 = time.perf_counter()
-                fn()
-                torch.cuda.synchronize()
-                if i >= 3:
-                    ts.append((time.perf_counter() - t0) * 1e6)
-            return sorted(ts)[len(ts) // 2]
-
-        def device(fn):
-            return time_launches(fn, 3, iters)["median_ms"] * 1e3
-
+        wall, device = (lambda fn: _wall(fn, iters)), (lambda fn: _device(fn, iters))
         sides = {"native_eager_device": lambda: device(native), "wrap_eager_device": lambda: device(wrap),
                  "native_graph_device": lambda: device(g_native.replay), "wrap_graph_device": lambda: device(g_wrap.replay),
                  "native_eager_wall": lambda: wall(native), "wrap_eager_wall": lambda: wall(wrap),
                  "native_graph_wall": lambda: wall(g_native.replay), "wrap_graph_wall": lambda: wall(g_wrap.replay)}
-        res = {k: [] for k in sides}
-        for _ in range(rounds):
-            for k, fn in sides.items():
-                res[k].append(fn())
-
-        def stat(v):
-            med = sorted(v)[len(v) // 2]
-            return {"median_us": round(med, 1), "min_us": round(min(v), 1), "max_us": round(max(v), 1),
-                    "spread": round((max(v) - min(v)) / med, 4)}
-
         out = {"model": "qwen2_moe layer 11, bf16 ends", "bs": bs, "E": E, "topk": topk, "H": H}
-        out.update({k: stat(v) for k, v in res.items()})
+        out.update({k: _stat(v) for k, v in _rounds(sides, rounds).items()})
         m = lambda k: out[k]["median_us"]
         for form in ("eager_device", "graph_device", "eager_wall", "graph_wall"):
             out[f"native_over_wrap_{form}"] = round(m(f"native_{form}") / m(f"wrap_{form}"), 4)
@@ -141,7 +105,7 @@ def main():
             if r["status"]:
                 sys.exit(1)
         return
-    r = moe.qwen2_layer_bench(args.rounds, args.iters, model=args.model)
+    r = moe_bench.qwen2_layer_bench(args.rounds, args.iters, model=args.model)
     r["model"] = args.model
     print(json.dumps(r), flush=True)
     if not r["bit_identical"]:
