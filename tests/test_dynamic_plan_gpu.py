@@ -9,6 +9,8 @@ quant-type mixes keep both sides on the same kernel build.
 """
 from __future__ import annotations
 
+import types
+
 import numpy as np
 import pytest
 import torch
@@ -16,8 +18,8 @@ import torch
 from mxmoe_amd import _native as nat
 from mxmoe_amd import moe
 from mxmoe_amd import quantize as qz
-from mxmoe_amd.groupgemm import (FP16, W4A4, W4A4_MXFP4, W4A8_MXFP8, W4A16_MXFP4, W8A8, DynamicGroupGemm, GroupGemm,
-                                 Problem, QParams)
+from mxmoe_amd.groupgemm import (BF16, FP16, W4A4, W4A4_MXFP4, W4A8_MXFP8, W4A16_MXFP4, W8A8, W8A8_E4M3, DynamicGroupGemm,
+                                 GroupGemm, Problem, QParams)
 from tests._util import assert_f16_close
 
 pytestmark = pytest.mark.gpu
@@ -42,9 +44,20 @@ class Operands:
         a = ((torch.rand(cap, K, generator=g) * 2 - 1)).half()
         w = ((torch.rand(N, K, generator=g) * 2 - 1) * 0.2).half()
         self.q, self.cap, self.N, self.K, self.silu = q, cap, N, K, silu
-        self.w = moe.prepare_weight(w.to(DEV), q, interleave=silu)
         self.sa = None
-        if q.fmt == "MXFP4" and not q.is_weight_only:
+        if q.is_fp8:  # (moe.prepare_weight has neither E4M3 nor bf16: B and scale_b built here; no SiLU epilogue)
+            qb, sb = qz.quant_e4m3(w)
+            self.w = types.SimpleNamespace(B=qz.pack_e4m3(qb).to(DEV), scale_b=sb.to(DEV))
+        elif q.fmt == "bf16":
+            self.w = types.SimpleNamespace(B=w.bfloat16().to(DEV), scale_b=None)
+        else:
+            self.w = moe.prepare_weight(w.to(DEV), q, interleave=silu)
+        if q.is_fp8:
+            qa, sa = qz.quant_e4m3(a)
+            self.A, self.sa = qz.pack_e4m3(qa).to(DEV), sa.to(DEV)
+        elif q.fmt == "bf16":
+            self.A = a.bfloat16().to(DEV)
+        elif q.fmt == "MXFP4" and not q.is_weight_only:
             codes, sc = qz.quant_mxfp4(a)
             self.A, self.sa = codes.to(DEV), qz.pack_mxfp4_scales(sc).to(DEV)
         elif q.fmt == "MXFP8":
@@ -75,6 +88,8 @@ GG_CASES = {
     "v3_w4a4": (V3, [W4A4] * 4, W4A4, 256, False),
     "wo3_silu": (WO3, [W8A8, FP16, W4A4, W8A8], FP16, 256, True),
     "v2x_silu": (V2X, [W8A8, FP16, W8A8, FP16], W8A8, 256, True),
+    "v2x_e4m3_w8a8": (V2X, [W8A8_E4M3, W8A8, W8A8_E4M3, W8A8], W8A8_E4M3, 256, False),
+    "v2x_bf16_fp16": (V2X, [BF16, FP16, BF16, FP16], BF16, 256, False),
 }
 # rows of the 4 routed experts (sum <= R = 600) and of the shared expert (<= T = 513): tile-boundary values, one
 # expert holding all of R, two experts empty
