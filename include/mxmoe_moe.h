@@ -356,6 +356,68 @@ int mxmoe_moe_combine_dt(int out_dtype, const void* y, const int32_t* inv_slot, 
 int mxmoe_moe_combine(const void* y, const int32_t* inv_slot, const float* weights, const void* shared,
                       const float* shared_w, int64_t T, int topk, int H, void* out, void* stream);
 
+/* The decode forward: a layer call of 1..16 tokens as two weight-streaming launches, with no sort, no segment table,
+ * no tile table and no planner — every workgroup reads the T * topk ids and finds the rows of its own expert
+ * (mxmoe_amd/csrc/moe_decode.h). mxmoe_moe_decode_gate_up writes the activations, mxmoe_moe_decode_down the down
+ * projections, both in PAIR order (row p = t * topk + k, no permutation); mxmoe_moe_combine / mxmoe_moe_combine_dt
+ * with inv_slot[p] = p then give the layer's output.
+ * Replaces: nothing in the reference (which plans a GroupGEMM whatever the batch). The arithmetic is the one the
+ * entries above and the GroupGEMM (include/mxmoe_gg.h) compute, so for the integer kinds act, y and out equal the
+ * planned layer's bit for bit.
+ *   experts  DEVICE array of E records (E + 1 with_shared: the shared expert last). Per linear a kind:
+ *            MXMOE_DECODE_FP16 (B fp16 [rows][K], no scale), MXMOE_DECODE_W8A8 (w8a8_g-1_sym: B pack_wxax int8
+ *            [rows][K], scale_b fp16 [rows]), MXMOE_DECODE_W4A4 (w4a4_g-1_sym: B pack_wxax int4 [rows][K / 2], scale_b
+ *            fp16 [rows]); the kinds may differ per expert and between an expert's two linears. b1: the gate_up weight,
+ *            2N rows (2 N_shared for the shared expert), K = H; b2: the down weight, H rows, K = N (N_shared).
+ *   kind_mask bit k set when some record carries kind k on the call's linear (kind1 for gate_up, kind2 for down): it
+ *            sizes the workgroups' LDS rows. A bit of a kind that does not exist: MXMOE_GG_ERR_UNSUPPORTED. A record
+ *            whose kind is not in the mask sets MXMOE_DECODE_BAD_KIND in *status and its rows are not written.
+ *   layout   of every gate_up weight: MXMOE_DECODE_GU_PLAIN (gate rows [0, N), up rows [N, 2N)) or
+ *            MXMOE_DECODE_GU_INTERLEAVED (16-row blocks alternating gate, up — MXMOE_GG_EPI_SILU_MUL's layout: gate
+ *            row n at 32 (n / 16) + n % 16, its up row 16 further); scale_b follows its rows. The layout changes only
+ *            the row index.
+ * mxmoe_moe_decode_gate_up, for every pair p = t * topk + k with e = topk_ids[t][k] in [0, E) (and, with_shared, for
+ * every token t on the shared expert), with the expert's kind1:
+ *   x        hidden[t], fp16; dtype MXMOE_DT_BF16: each bf16 element converted to fp16 as mxmoe_moe_gather_quant does
+ *            (to nearest even, +-Inf beyond fp16's range, subnormals rounded).
+ *   A row    FP16: x. W8A8 / W4A4 (qmax 127 / 7): mxmoe_moe_quant_act's rule over the whole row,
+ *            scale_a = fp16(amax / qmax), 0 -> 1; q = rint_even(clamp(fp16(x / scale_a), +-qmax)).
+ *   dot      row r of B against the A row: integers exactly in int32 (v_dot4_i32_i8 / v_dot8_i32_i4; int4 codes are
+ *            two's-complement nibbles; A and B share pack_wxax's K permutation), fp16 in f32 (fma, the kernel's order).
+ *   v(r)     FP16: fp16_rn(acc); W8A8 / W4A4: fp16_rn(0 + f32(acc) * f32(fp16_rn(scale_a * scale_b[r]))), the f32
+ *            product rounded on its own — the GroupGEMM's epilogue.
+ *   act      column n: g = v(gate row of n), u = v(up row of n), act[p][n] = fp16_rn(silu(f32 g) * f32 u),
+ *            silu(g) = g * rcp(1 + exp2(g * -log2 e)) on the hardware exp2 / rcp (mxmoe_moe_silu_mul_quant's).
+ *            act fp16 [T * topk][N]; act_shared fp16 [T][N_shared] (row t).
+ * mxmoe_moe_decode_down, for the same pairs and tokens, with the expert's kind2: the A row is act[p] (act_shared[t])
+ *   quantised by the same rule (amax over the whole row of N / N_shared elements; every workgroup re-derives the rows
+ *   it needs), dot and v(r) as above on b2 / sb2: y[p][h] = v(h), fp16 [T * topk][H]; ys[t][h], fp16 [T][H].
+ * Safety: nothing is indexed by an id. An id outside [0, E) is matched by no workgroup: its pair's act / y rows keep
+ * what they held, and MXMOE_DECODE_BAD_ID is OR-ed into *status (DEVICE int32, optional). Rows past T are never
+ * written. NaN inputs: unspecified.
+ * Limits: 1 <= T <= MXMOE_DECODE_MAX_T (T == 0: OK, no launch), E >= 1, 1 <= topk <= min(E, 16); H, N and (with_shared)
+ * N_shared multiples of 128 and <= 16384; hidden, act, act_shared, y, ys and every B 16-byte aligned, topk_ids 4-byte;
+ * layout and dtype known. Anything else: MXMOE_GG_ERR_INVALID (an unknown kind bit: MXMOE_GG_ERR_UNSUPPORTED), checked
+ * before any HIP call and reported under the entry point's name. Each entry is one launch on `stream`, no allocation,
+ * no synchronisation: graph-capturable. */
+enum { MXMOE_DECODE_MAX_T = 16 };
+enum { MXMOE_DECODE_FP16 = 0, MXMOE_DECODE_W8A8 = 1, MXMOE_DECODE_W4A4 = 2 }; /* per linear */
+enum { MXMOE_DECODE_GU_PLAIN = 0, MXMOE_DECODE_GU_INTERLEAVED = 1 };
+enum { MXMOE_DECODE_BAD_ID = 1, MXMOE_DECODE_BAD_KIND = 2 };                   /* bits of *status */
+typedef struct mxmoe_moe_decode_expert {
+  const void* b1;  /* gate_up B [2N][K bits / 8]           */
+  const void* sb1; /* its fp16 scale_b [2N] (FP16: NULL)   */
+  const void* b2;  /* down B [H][N bits / 8]               */
+  const void* sb2; /* its fp16 scale_b [H] (FP16: NULL)    */
+  int32_t kind1, kind2;
+} mxmoe_moe_decode_expert;
+int mxmoe_moe_decode_gate_up(int dtype, const void* hidden, int64_t T, int topk, int E, int with_shared,
+                             const int32_t* topk_ids, const mxmoe_moe_decode_expert* experts, uint32_t kind_mask, int H,
+                             int N, int N_shared, int layout, void* act, void* act_shared, int32_t* status, void* stream);
+int mxmoe_moe_decode_down(int64_t T, int topk, int E, int with_shared, const int32_t* topk_ids,
+                          const mxmoe_moe_decode_expert* experts, uint32_t kind_mask, int H, int N, int N_shared,
+                          const void* act, const void* act_shared, void* y, void* ys, int32_t* status, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

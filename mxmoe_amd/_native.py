@@ -105,13 +105,21 @@ EXPORTED_SYMBOLS = (
     "mxmoe_moe_gate_wide",
     # bf16 layers: the router, the gather and the combine with the element type as an argument
     "mxmoe_moe_gate_dt", "mxmoe_moe_gather_quant", "mxmoe_moe_combine_dt",
+    # the decode forward (1..16 tokens, no planner)
+    "mxmoe_moe_decode_gate_up", "mxmoe_moe_decode_down",
 )
 # added to ABI 7 without a version bump (additive): a product library without them is a stale build
 GPTOSS_SYMBOLS = ("mxmoe_moe_gate_ex2", "mxmoe_moe_glu_quant", "mxmoe_moe_combine_bias")
 # added the same way after them: bound where present, ``symbol`` refuses the call where a build lacks it
 WIDE_GATE_SYMBOLS = ("mxmoe_moe_gate_wide",)
 DT_SYMBOLS = ("mxmoe_moe_gate_dt", "mxmoe_moe_gather_quant", "mxmoe_moe_combine_dt")  # (likewise: the bf16 layers)
+DECODE_SYMBOLS = ("mxmoe_moe_decode_gate_up", "mxmoe_moe_decode_down")  # (likewise: the decode forward)
 DT_FP16, DT_BF16 = 0, 1  # MXMOE_DT_* (include/mxmoe_moe.h)
+# MXMOE_DECODE_* (include/mxmoe_moe.h): the token limit, the kinds per linear, the gate_up layouts, the status bits
+DECODE_MAX_T = 16
+DECODE_FP16, DECODE_W8A8, DECODE_W4A4 = 0, 1, 2
+DECODE_GU_PLAIN, DECODE_GU_INTERLEAVED = 0, 1
+DECODE_BAD_ID, DECODE_BAD_KIND = 1, 2
 GLU_SILU, GLU_SWIGLU_CLAMP = 0, 1  # MXMOE_GLU_* (include/mxmoe_moe.h)
 
 
@@ -147,6 +155,13 @@ class MoeGluC(ctypes.Structure):
 
     _fields_ = [("act", ctypes.c_int32), ("alpha", ctypes.c_float), ("limit", ctypes.c_float),
                 ("bias_routed", ctypes.c_void_p), ("bias_shared", ctypes.c_void_p)]
+
+
+class MoeDecodeExpertC(ctypes.Structure):
+    """mxmoe_moe_decode_expert (include/mxmoe_moe.h): one expert's two weights and their kinds for the decode forward."""
+
+    _fields_ = [("b1", ctypes.c_void_p), ("sb1", ctypes.c_void_p), ("b2", ctypes.c_void_p), ("sb2", ctypes.c_void_p),
+                ("kind1", ctypes.c_int32), ("kind2", ctypes.c_int32)]
 
 
 # mxmoe_gg_dynamic_status bits (MXMOE_GG_DYN_*) and mxmoe_moe_segments' (MXMOE_MOE_SEG_COUNT_MISMATCH)
@@ -276,6 +291,13 @@ def _declare(lib: ctypes.CDLL) -> None:
                                                P, P, P]
         lib.mxmoe_moe_combine_dt.restype = c.c_int
         lib.mxmoe_moe_combine_dt.argtypes = [c.c_int] + lib.mxmoe_moe_combine_bias.argtypes
+    if all(hasattr(lib, fn) for fn in DECODE_SYMBOLS):  # (builds before the decode forward lack them: A/B tools)
+        lib.mxmoe_moe_decode_gate_up.restype = c.c_int
+        lib.mxmoe_moe_decode_gate_up.argtypes = [c.c_int, P, c.c_int64, c.c_int, c.c_int, c.c_int, P, P, c.c_uint32, c.c_int,
+                                                 c.c_int, c.c_int, c.c_int, P, P, P, P]
+        lib.mxmoe_moe_decode_down.restype = c.c_int
+        lib.mxmoe_moe_decode_down.argtypes = [c.c_int64, c.c_int, c.c_int, c.c_int, P, P, c.c_uint32, c.c_int, c.c_int,
+                                              c.c_int, P, P, P, P, P, P]
 
 
 def lib() -> ctypes.CDLL:

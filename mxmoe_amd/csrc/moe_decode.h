@@ -1,0 +1,395 @@
+// moe_decode.h — the decode forward's two kernels (mxmoe_moe_decode_gate_up, mxmoe_moe_decode_down of
+// include/mxmoe_moe.h), gfx950. Included by moe_ops.hip after its quantiser helpers, which the kernels call as they
+// are (rtn_scale, div_f16_operands, codes_i8, codes_i4, amax8, bf16x8_to_f16): the quantised rows are byte for byte
+// what act_quant_kernel writes.
+//
+// A forward of 1..16 tokens has at most a few hundred (token, choice) pairs, so no tile table is planned: every
+// workgroup reads all T * topk ids and finds the rows of its own expert. Both kernels are weight streamers — no MFMA,
+// the integer dot products on v_dot4_i32_i8 / v_dot8_i32_i4, fp16 on v_fma_mix_f32.
+//
+// Mapping. One workgroup (256 threads) per (expert, tile of `ct` output columns); the shared expert's tiles come
+// first in the grid (its rows are the most: all T). A workgroup whose expert has no row returns after the id scan.
+//   rows      thread i < T * topk holds id i; the pairs whose id is the workgroup's expert are listed in pair order
+//             (ballot + prefix over the 4 waves). The shared expert's rows are the tokens 0..T-1.
+//   A rows    wave w quantises rows w, w + 4, ... of the batch into LDS by the tag of the expert's kind (one pass for
+//             the row's amax, one for the codes; fp16: a copy), in pack_wxax order, the K permutation of the weight
+//             rows: packed 32-bit words of A and B multiply element by element. A batch is `rb` rows (16, or what
+//             fits the LDS budget for very wide rows; more rows than a batch — only with repeated ids — re-read the
+//             weights).
+//   dot       a quarter-wave (16 lanes) owns two weight rows at a time (gate_up: gate and up row of one output column;
+//             down: output columns n and n + 16): lane l holds bytes [256 s + 16 l, + 16) of step s of both rows, four
+//             steps (8 loads of 16 B) in flight, and multiplies them with the same bytes of every A row of the batch
+//             (LDS, a broadcast across the 4 quarters of a wave). The 16 partial sums of a row are added with four
+//             DPP steps inside the 16-lane row (integers: exact; fp16 experts: f32 in that order).
+//   epilogue  lane r of the quarter finishes row r: the GroupGEMM's scale arithmetic, gate_up: the SiLU, then a 2-byte
+//             store to row `pair` of the output (pair order: no permutation).
+// Nothing is indexed by an id: an id outside [0, E) matches no workgroup, its pair's rows stay as they were, and the
+// first routed workgroup sets MXMOE_DECODE_BAD_ID in the status word. The expert record is indexed by the workgroup's
+// own expert number. A kind outside the call's kind_mask (which sized the LDS rows) sets MXMOE_DECODE_BAD_KIND and the
+// workgroup writes nothing.
+#pragma once
+
+namespace mxmoe {
+namespace {
+namespace decode {
+
+constexpr int kThreadsD = 256;
+constexpr int kMaxPairs = MXMOE_DECODE_MAX_T * 16;  // T <= 16, topk <= 16
+constexpr int kBatchRows = 16;                      // A rows per batch: the accumulators a lane keeps per weight row
+constexpr int kLdsBudget = 60 * 1024;               // dynamic LDS of a workgroup (the A rows of one batch)
+constexpr int kMaxWidthD = 16384;
+
+struct Args {
+  const void* src;         // gate_up: hidden [T][K] (fp16 or bf16); down: act [T * topk][K]
+  const void* src_shared;  // gate_up: hidden; down: act_shared [T][K_shared]
+  const int32_t* ids;      // [T][topk]
+  const mxmoe_moe_decode_expert* experts;
+  _Float16* out;           // gate_up: act [T * topk][C]; down: y [T * topk][C]
+  _Float16* out_shared;    // [T][C_shared]
+  int32_t* status;
+  int T, topk, E, with_shared;
+  int K, K_shared;          // elements per A row (routed / shared expert)
+  int C, C_shared;          // output columns
+  int tiles, tiles_shared;  // column tiles per routed expert / of the shared expert
+  int ct;                   // output columns per tile (32, 64 or 128)
+  int rb;                   // A rows per batch
+  int lds_row;              // bytes per A row in LDS (the widest row of the kinds in kind_mask, up to 1024)
+  int layout, src_bf16;
+  uint32_t kind_mask;
+};
+
+__host__ __device__ inline int row_bytes(int kind, int K) {
+  return kind == MXMOE_DECODE_FP16 ? 2 * K : kind == MXMOE_DECODE_W8A8 ? K : K / 2;
+}
+
+// sum over the 16 lanes of a DPP row (quad_perm [1,0,3,2], [2,3,0,1], row_half_mirror, row_mirror): every lane
+// of the row ends with the total
+template <class T>
+__device__ __forceinline__ T row16_sum(T v) {
+#define MXMOE_DEC_STEP(ctrl)                                                                              \
+  {                                                                                                       \
+    const int o = __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), ctrl, 0xF, 0xF, false);      \
+    v = v + __builtin_bit_cast(T, o);                                                                     \
+  }
+  MXMOE_DEC_STEP(0xB1) MXMOE_DEC_STEP(0x4E) MXMOE_DEC_STEP(0x141) MXMOE_DEC_STEP(0x140)
+#undef MXMOE_DEC_STEP
+  return v;
+}
+
+// One kind's dequant-and-dot: acc += dot of 16 packed bytes of a weight row with the same 16 bytes of an A row.
+template <int KIND> struct Dot;
+template <> struct Dot<MXMOE_DECODE_FP16> {
+  typedef float acc_t;
+  static __device__ __forceinline__ float dot(const uint4& w, const uint4& a, float acc) {
+    const h8_t wv = __builtin_bit_cast(h8_t, w), av = __builtin_bit_cast(h8_t, a);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) acc = fmaf((float)wv[j], (float)av[j], acc);
+    return acc;
+  }
+  // fp16_rn(acc)
+  static __device__ __forceinline__ _Float16 finish(float acc, _Float16, _Float16) { return (_Float16)acc; }
+};
+// the GroupGEMM's scaled epilogue: fp16_rn(0 + f32(acc) * f32(fp16_rn(sa * sb))), the f32 product rounded on its own
+// (the empty asm keeps the multiply and the conversion from fusing into one rounding)
+__device__ __forceinline__ _Float16 scaled_out(int acc, _Float16 sa, _Float16 sb) {
+  const _Float16 s16 = sa * sb;
+  float prod = (float)acc * (float)s16;
+  asm volatile("" : "+v"(prod));
+  return (_Float16)(0.0f + prod);
+}
+template <> struct Dot<MXMOE_DECODE_W8A8> {
+  typedef int acc_t;
+  static __device__ __forceinline__ int dot(const uint4& w, const uint4& a, int acc) {
+    acc = __builtin_amdgcn_sdot4((int)w.x, (int)a.x, acc, false);
+    acc = __builtin_amdgcn_sdot4((int)w.y, (int)a.y, acc, false);
+    acc = __builtin_amdgcn_sdot4((int)w.z, (int)a.z, acc, false);
+    return __builtin_amdgcn_sdot4((int)w.w, (int)a.w, acc, false);
+  }
+  static __device__ __forceinline__ _Float16 finish(int acc, _Float16 sa, _Float16 sb) { return scaled_out(acc, sa, sb); }
+};
+template <> struct Dot<MXMOE_DECODE_W4A4> {
+  typedef int acc_t;
+  static __device__ __forceinline__ int dot(const uint4& w, const uint4& a, int acc) {
+    acc = __builtin_amdgcn_sdot8((int)w.x, (int)a.x, acc, false);
+    acc = __builtin_amdgcn_sdot8((int)w.y, (int)a.y, acc, false);
+    acc = __builtin_amdgcn_sdot8((int)w.z, (int)a.z, acc, false);
+    return __builtin_amdgcn_sdot8((int)w.w, (int)a.w, acc, false);
+  }
+  static __device__ __forceinline__ _Float16 finish(int acc, _Float16 sa, _Float16 sb) { return scaled_out(acc, sa, sb); }
+};
+
+// act = fp16_rn(silu(f32 g) * f32 u): act_quant_kernel's expression. The product is rounded to f32 and then to fp16, as
+// there and in the GroupGEMM's SiLU epilogue (the empty asm keeps hipcc from fusing the multiply and the conversion
+// into one v_fma_mixlo_f16: a single rounding, and +0 where the product is -0)
+__device__ __forceinline__ _Float16 silu_mul(_Float16 g16, _Float16 u16) {
+  const float g = (float)g16;
+  const float sg = g * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(g * -1.4426950408889634f));
+  float p = sg * (float)u16;
+  asm volatile("" : "+v"(p));
+  return (_Float16)p;
+}
+
+// Row `src` (K fp16, or bf16 converted as mxmoe_moe_gather_quant does) quantised by kind's tag into `row` (LDS,
+// pack_wxax order) by one wave, zeros behind it up to a multiple of 1024 bytes (the dot loop's group of four 256-byte
+// steps reads the pad); its scale to *scale. The arithmetic and the helpers are act_quant_kernel's.
+__device__ __forceinline__ void quant_row(const uint8_t* __restrict__ src, int K, int kind, bool bf, uint8_t* row,
+                                          _Float16* scale) {
+  const int lane = threadIdx.x & 63;
+  const int KB = row_bytes(kind, K);
+  for (int o = KB + lane * 16; o < ((KB + 1023) & ~1023); o += 1024) *reinterpret_cast<uint4*>(row + o) = uint4{0, 0, 0, 0};
+  auto ld = [&](int idx) -> h8_t {
+    const uint4 v = *reinterpret_cast<const uint4*>(src + 2 * idx);
+    return bf ? bf16x8_to_f16(v) : __builtin_bit_cast(h8_t, v);
+  };
+  if (kind == MXMOE_DECODE_FP16) {
+#pragma unroll 4
+    for (int idx = lane * 8; idx < K; idx += 512) *reinterpret_cast<h8_t*>(row + 2 * idx) = ld(idx);
+    return;
+  }
+  float m = 0.0f;
+#pragma unroll 4
+  for (int idx = lane * 8; idx < K; idx += 512) m = fmaxf(m, amax8(ld(idx)));
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) m = fmaxf(m, __shfl_xor(m, d, 64));
+  const float qmax = kind == MXMOE_DECODE_W8A8 ? 127.0f : 7.0f;
+  const h2_t lim = {(_Float16)qmax, (_Float16)qmax};
+  const _Float16 sc = rtn_scale(m, qmax);
+  const float rs = __builtin_amdgcn_rcpf((float)sc);
+  if (lane == 0) *scale = sc;
+  if (kind == MXMOE_DECODE_W8A8) {
+#pragma unroll 4
+    for (int idx = lane * 8; idx < K; idx += 512) *reinterpret_cast<uint2*>(row + idx) = codes_i8(ld(idx), (float)sc, rs, lim);
+  } else {
+#pragma unroll 4
+    for (int idx = lane * 8; idx < K; idx += 512)
+      *reinterpret_cast<uint32_t*>(row + idx / 2) = codes_i4(ld(idx), (float)sc, rs, lim);
+  }
+}
+
+// The two weight rows w0, w1 (KB bytes each) of a quarter-wave against the nr A rows of the batch, and the rows'
+// results: lane r (< nr) of the quarter returns row r's two outputs in *o0, *o1 (other lanes: unspecified).
+template <int KIND>
+__device__ __forceinline__ void dot_rows(const uint8_t* __restrict__ w0, const uint8_t* __restrict__ w1,
+                                         const _Float16* __restrict__ SB, int sb0, int sb1, int KB,
+                                         const uint8_t* A, int lds_row, const _Float16* s_scale, int nr, int l16,
+                                         _Float16* o0, _Float16* o1) {
+  typedef typename Dot<KIND>::acc_t acc_t;
+  acc_t acc0[kBatchRows], acc1[kBatchRows];
+#pragma unroll
+  for (int r = 0; r < kBatchRows; ++r) acc0[r] = acc1[r] = 0;
+  const int S = (KB + 255) >> 8;
+  for (int s0 = 0; s0 < S; s0 += 4) {
+    uint4 wa[4], wb[4];
+    int off[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {  // 8 loads of 16 B in flight; past the row: the row's first bytes (zeroed below)
+      off[u] = ((s0 + u) * 16 + l16) * 16;
+      const int wo = off[u] < KB ? off[u] : 0;
+      wa[u] = *reinterpret_cast<const uint4*>(w0 + wo);
+      wb[u] = *reinterpret_cast<const uint4*>(w1 + wo);
+    }
+    if ((s0 + 4) * 256 > KB) {  // (uniform) the row ends inside this group: zero weights past it; the A rows' pad is zero
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const uint32_t mk = off[u] < KB ? ~0u : 0u;
+        wa[u].x &= mk, wa[u].y &= mk, wa[u].z &= mk, wa[u].w &= mk;
+        wb[u].x &= mk, wb[u].y &= mk, wb[u].z &= mk, wb[u].w &= mk;
+      }
+    }
+    int nrs = nr, ldr = lds_row;
+    asm volatile("" : "+s"(nrs), "+s"(ldr));  // the 16 row tests and row offsets are made here, not kept in SGPRs
+#pragma unroll
+    for (int r = 0; r < kBatchRows; ++r) {
+      if (r < nrs) {  // workgroup-uniform
+        const uint8_t* ar = A + r * ldr;
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          const uint4 av = *reinterpret_cast<const uint4*>(ar + off[u]);  // (off < lds_row: a multiple of 1024)
+          acc0[r] = Dot<KIND>::dot(wa[u], av, acc0[r]);
+          acc1[r] = Dot<KIND>::dot(wb[u], av, acc1[r]);
+        }
+      }
+    }
+  }
+  acc_t v0 = 0, v1 = 0;
+  int lsel = l16, nrs = nr;
+  asm volatile("" : "+v"(lsel), "+s"(nrs));  // the 16 lane masks and row tests below are formed here, not kept in SGPRs
+#pragma unroll
+  for (int r = 0; r < kBatchRows; ++r) {
+    if (r < nrs) {
+      const acc_t t0 = row16_sum(acc0[r]), t1 = row16_sum(acc1[r]);
+      if (lsel == r) {
+        v0 = t0;
+        v1 = t1;
+      }
+    }
+  }
+  _Float16 sa = (_Float16)0, b0 = (_Float16)0, b1 = (_Float16)0;
+  if constexpr (KIND != MXMOE_DECODE_FP16) {
+    sa = s_scale[l16 < nr ? l16 : 0];
+    b0 = SB[sb0];
+    b1 = SB[sb1];
+  }
+  *o0 = Dot<KIND>::finish(v0, sa, b0);
+  *o1 = Dot<KIND>::finish(v1, sa, b1);
+}
+
+// One workgroup's work on an expert of kind KIND: per batch of rows, the A rows into LDS, then the tile's columns.
+template <bool DOWN, int KIND>
+__device__ __forceinline__ void expert_tile(const Args& a, const mxmoe_moe_decode_expert& ex, bool shared, int tile,
+                                            int nrows, uint8_t* s_a, const int* s_rows, _Float16* s_scale) {
+  const int tid = threadIdx.x, wave = tid >> 6;
+  const int K = shared ? a.K_shared : a.K, C = shared ? a.C_shared : a.C;
+  const int KB = row_bytes(KIND, K);  // <= lds_row: the kind is in the mask
+  const uint8_t* const B = static_cast<const uint8_t*>(DOWN ? ex.b2 : ex.b1);
+  const _Float16* const SB = static_cast<const _Float16*>(DOWN ? ex.sb2 : ex.sb1);
+  const uint8_t* const src = static_cast<const uint8_t*>(shared ? a.src_shared : a.src);
+  _Float16* const out = shared ? a.out_shared : a.out;
+  const int n0 = tile * a.ct;
+  const int q = tid >> 4, l16 = tid & 15;
+
+  for (int r0 = 0; r0 < nrows; r0 += a.rb) {
+    const int nr = min(a.rb, nrows - r0);
+    __syncthreads();  // s_rows is complete; the previous batch's A rows are no longer read
+    for (int r = wave; r < nr; r += kThreadsD / 64) {
+      const int p = shared ? r0 + r : s_rows[r0 + r];      // token (shared) or pair
+      const int srow = (shared || DOWN) ? p : p / a.topk;  // gate_up reads the pair's token
+      quant_row(src + (int64_t)srow * K * 2, K, KIND, !DOWN && a.src_bf16, s_a + r * a.lds_row, s_scale + r);
+    }
+    __syncthreads();
+    const int orow = l16 < nr ? (shared ? r0 + l16 : s_rows[r0 + l16]) : 0;
+    for (int c = q; c < a.ct; c += DOWN ? 32 : 16) {
+      // gate_up: column n, weight rows gate(n), up(n); down: columns n and n + 16, weight rows n, n + 16
+      const int n = n0 + c;
+      if (n + (DOWN ? 16 : 0) >= C) continue;
+      int wr0, wr1;
+      if constexpr (DOWN) {
+        wr0 = n;
+        wr1 = n + 16;
+      } else if (a.layout == MXMOE_DECODE_GU_INTERLEAVED) {
+        wr0 = 32 * (n >> 4) + (n & 15);
+        wr1 = wr0 + 16;
+      } else {
+        wr0 = n;
+        wr1 = C + n;
+      }
+      _Float16 o0, o1;
+      dot_rows<KIND>(B + (int64_t)wr0 * KB, B + (int64_t)wr1 * KB, SB, wr0, wr1, KB, s_a, a.lds_row, s_scale, nr, l16, &o0,
+                     &o1);
+      if (l16 < nr) {
+        _Float16* const orp = out + (int64_t)orow * C;
+        if constexpr (DOWN) {
+          orp[n] = o0;
+          orp[n + 16] = o1;
+        } else {
+          orp[n] = silu_mul(o0, o1);
+        }
+      }
+    }
+  }
+}
+
+// DOWN = false: decode_gate_up; true: decode_down
+template <bool DOWN>
+__global__ __launch_bounds__(kThreadsD) void decode_kernel(Args a) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t s_a[];  // [rb][lds_row]
+  __shared__ int s_rows[kMaxPairs];
+  __shared__ int s_cnt[kThreadsD / 64];
+  __shared__ _Float16 s_scale[kBatchRows];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int nsh = a.with_shared ? a.tiles_shared : 0;
+  const int b = blockIdx.x;
+  const bool shared = b < nsh;
+  const int e = shared ? a.E : (b - nsh) / a.tiles;  // in [0, E] by the grid's size
+  const int tile = shared ? b : (b - nsh) % a.tiles;
+  const int npairs = a.T * a.topk;
+
+  int nrows = a.T;
+  if (!shared) {
+    const int id = tid < npairs ? a.ids[tid] : -1;
+    const bool hit = id == e;
+    const uint64_t m = __builtin_amdgcn_ballot_w64(hit);
+    if (lane == 0) s_cnt[wave] = __popcll(m);
+    if (b == nsh && a.status) {  // one workgroup reports the ids that no workgroup matches
+      const bool bad = tid < npairs && (id < 0 || id >= a.E);
+      if (__builtin_amdgcn_ballot_w64(bad) != 0 && lane == 0) atomicOr(a.status, MXMOE_DECODE_BAD_ID);
+    }
+    __syncthreads();
+    int base = 0;
+    nrows = 0;
+#pragma unroll
+    for (int w = 0; w < kThreadsD / 64; ++w) {
+      base += w < wave ? s_cnt[w] : 0;
+      nrows += s_cnt[w];
+    }
+    if (nrows == 0) return;  // no token chose this expert
+    if (hit) s_rows[base + __popcll(m & (((uint64_t)1 << lane) - 1))] = tid;
+  }
+
+  const mxmoe_moe_decode_expert ex = a.experts[e];
+  const int kind = DOWN ? ex.kind2 : ex.kind1;
+  if (kind < 0 || kind > 31 || !((a.kind_mask >> kind) & 1u)) {  // (the mask holds existing kinds only: the entry's check)
+    if (tid == 0 && a.status) atomicOr(a.status, MXMOE_DECODE_BAD_KIND);
+    return;
+  }
+  // the kind is chosen once, outside the loops: one dequant-and-dot body per kind, one switch
+  if (kind == MXMOE_DECODE_FP16) expert_tile<DOWN, MXMOE_DECODE_FP16>(a, ex, shared, tile, nrows, s_a, s_rows, s_scale);
+  else if (kind == MXMOE_DECODE_W8A8) expert_tile<DOWN, MXMOE_DECODE_W8A8>(a, ex, shared, tile, nrows, s_a, s_rows, s_scale);
+  else expert_tile<DOWN, MXMOE_DECODE_W4A4>(a, ex, shared, tile, nrows, s_a, s_rows, s_scale);
+}
+
+// ---------------------------------------------------------------------------------------------
+// host side: the entries' checks (before any HIP call) and the launch geometry
+
+inline int kind_mask_check(const char* fn, uint32_t kind_mask) {
+  const uint32_t known = 1u << MXMOE_DECODE_FP16 | 1u << MXMOE_DECODE_W8A8 | 1u << MXMOE_DECODE_W4A4;
+  if (kind_mask & ~known)
+    return fail(MXMOE_GG_ERR_UNSUPPORTED, "%s: unknown expert kind in kind_mask %#x (fp16, w8a8_g-1_sym and "
+                "w4a4_g-1_sym only)", fn, kind_mask);
+  if (!kind_mask) return fail(MXMOE_GG_ERR_INVALID, "%s: kind_mask names no kind", fn);
+  return MXMOE_GG_OK;
+}
+inline bool width_ok(int w) { return w > 0 && w % 128 == 0 && w <= kMaxWidthD; }
+
+inline int sizes_check(const char* fn, int64_t T, int topk, int E, int with_shared, int H, int N, int N_shared) {
+  if (T < 0 || T > MXMOE_DECODE_MAX_T || E < 1 || topk < 1 || topk > 16 || topk > E)
+    return fail(MXMOE_GG_ERR_INVALID, "%s: need 0 <= T <= %d, E >= 1, 1 <= topk <= min(E, 16) (T=%lld E=%d topk=%d)", fn,
+                (int)MXMOE_DECODE_MAX_T, (long long)T, E, topk);
+  if (!width_ok(H) || !width_ok(N) || (with_shared && !width_ok(N_shared)))
+    return fail(MXMOE_GG_ERR_INVALID, "%s: H, N and N_shared must be multiples of 128 and <= %d (H=%d N=%d N_shared=%d)",
+                fn, kMaxWidthD, H, N, N_shared);
+  return MXMOE_GG_OK;
+}
+
+// tiles, batch rows and LDS bytes of a launch whose other fields are set; returns the dynamic LDS bytes
+inline int geometry(Args& a) {
+  int kb = 0;
+  const int kmax = a.with_shared && a.K_shared > a.K ? a.K_shared : a.K;
+  for (int k = 0; k < 3; ++k)
+    if ((a.kind_mask >> k) & 1u) kb = row_bytes(k, kmax) > kb ? row_bytes(k, kmax) : kb;
+  a.lds_row = kb = (kb + 1023) & ~1023;  // (rows are zero-padded to the dot loop's group of four 256-byte steps)
+  int rb = kLdsBudget / kb;
+  rb = rb < 1 ? 1 : rb > kBatchRows ? kBatchRows : rb;
+  a.rb = rb > a.T ? a.T : rb;
+  // columns of the experts that can have rows; tiles of 128 columns, halved while the grid would not fill the CUs
+  const int npairs = a.T * a.topk;
+  const int64_t cols = (int64_t)(a.E < npairs ? a.E : npairs) * a.C + (a.with_shared ? a.C_shared : 0);
+  int ct = 128;
+  while (ct > 32 && cols / ct < 1024) ct >>= 1;
+  a.ct = ct;
+  a.tiles = a.C / ct;
+  a.tiles_shared = a.with_shared ? a.C_shared / ct : 0;
+  return a.rb * a.lds_row;
+}
+
+template <bool DOWN>
+inline int launch(Args a, void* stream) {
+  const int lds = geometry(a);
+  const int64_t blocks = (int64_t)a.tiles_shared + (int64_t)a.E * a.tiles;
+  hipLaunchKernelGGL(decode_kernel<DOWN>, dim3((unsigned)blocks), dim3(kThreadsD), lds, (hipStream_t)stream, a);
+  return launched(DOWN ? "decode_down_kernel" : "decode_gate_up_kernel");
+}
+
+}  // namespace decode
+}  // namespace
+}  // namespace mxmoe

@@ -18,7 +18,8 @@
 // its logits (mxmoe_moe_gate_ex2); no reference counterpart.
 // The router in front of them (mxmoe_moe_gate: logits on the MFMA, top-k, softmax; mxmoe_moe_gate_ex:
 // sigmoid scores, selection bias, group-limited top-k) is moe_gate.h; beyond 256 experts (mxmoe_moe_gate_wide),
-// moe_gate_wide.h.
+// moe_gate_wide.h. The decode forward (mxmoe_moe_decode_gate_up, mxmoe_moe_decode_down: a layer call of up to 16 tokens
+// as two weight-streaming launches with no planner) is moe_decode.h.
 // bf16 layers (mxmoe_moe_gate_dt, mxmoe_moe_gather_quant, mxmoe_moe_combine_dt): the element type of the router's
 // operands, of the gather's source rows and of the combine's output is a template parameter of the kernels above;
 // the fp16 instantiations are the kernels as they were. No reference counterpart (the reference is fp16 only).
@@ -709,6 +710,8 @@ int segments_check(const int32_t* counts, int E, int64_t T, int topk, const mxmo
 }  // namespace
 }  // namespace mxmoe
 
+#include "moe_decode.h"  // the decode forward's kernels (after the quantiser helpers above, which they call)
+
 using namespace mxmoe;
 
 // registers sized to the widest row of the launch, in 512-element chunks (1408 -> 3, 2048 -> 4)
@@ -1110,6 +1113,63 @@ int mxmoe_moe_combine(const void* y, const int32_t* inv_slot, const float* weigh
   if (int st = combine_check("mxmoe_moe_combine", y, inv_slot, weights, shared, out)) return st;
   return launch_combine<_Float16>(y, inv_slot, nullptr, weights, nullptr, shared, shared_w, nullptr, T, topk, 0, H, out, true,
                                   stream);
+}
+
+int mxmoe_moe_decode_gate_up(int dtype, const void* hidden, int64_t T, int topk, int E, int with_shared,
+                             const int32_t* topk_ids, const mxmoe_moe_decode_expert* experts, uint32_t kind_mask, int H,
+                             int N, int N_shared, int layout, void* act, void* act_shared, int32_t* status, void* stream) {
+  const char* fn = "mxmoe_moe_decode_gate_up";
+  if (int st = dtype_check(fn, "dtype", dtype)) return st;
+  if (int st = decode::kind_mask_check(fn, kind_mask)) return st;
+  if (int st = decode::sizes_check(fn, T, topk, E, with_shared, H, N, N_shared)) return st;
+  if (layout != MXMOE_DECODE_GU_PLAIN && layout != MXMOE_DECODE_GU_INTERLEAVED)
+    return fail(MXMOE_GG_ERR_INVALID, "%s: layout must be MXMOE_DECODE_GU_PLAIN or MXMOE_DECODE_GU_INTERLEAVED (got %d)", fn,
+                layout);
+  if (!aligned16(hidden) || !aligned16(act) || !aligned16(act_shared) || ((uintptr_t)topk_ids & 3) ||
+      ((uintptr_t)experts & 7) || ((uintptr_t)status & 3))
+    return fail(MXMOE_GG_ERR_INVALID, "%s: misaligned pointer (hidden / act / act_shared need 16 B)", fn);
+  if (T == 0) return MXMOE_GG_OK;
+  if (!hidden || !topk_ids || !experts || !act || (with_shared && !act_shared))
+    return fail(MXMOE_GG_ERR_INVALID, "%s: NULL pointer", fn);
+  decode::Args a{};
+  a.src = a.src_shared = hidden;
+  a.ids = topk_ids;
+  a.experts = experts;
+  a.out = static_cast<_Float16*>(act);
+  a.out_shared = static_cast<_Float16*>(act_shared);
+  a.status = status;
+  a.T = (int)T, a.topk = topk, a.E = E, a.with_shared = with_shared != 0;
+  a.K = a.K_shared = H;
+  a.C = N, a.C_shared = with_shared ? N_shared : 0;
+  a.layout = layout, a.src_bf16 = dtype == MXMOE_DT_BF16, a.kind_mask = kind_mask;
+  return decode::launch<false>(a, stream);
+}
+
+int mxmoe_moe_decode_down(int64_t T, int topk, int E, int with_shared, const int32_t* topk_ids,
+                          const mxmoe_moe_decode_expert* experts, uint32_t kind_mask, int H, int N, int N_shared,
+                          const void* act, const void* act_shared, void* y, void* ys, int32_t* status, void* stream) {
+  const char* fn = "mxmoe_moe_decode_down";
+  if (int st = decode::kind_mask_check(fn, kind_mask)) return st;
+  if (int st = decode::sizes_check(fn, T, topk, E, with_shared, H, N, N_shared)) return st;
+  if (!aligned16(act) || !aligned16(act_shared) || !aligned16(y) || !aligned16(ys) || ((uintptr_t)topk_ids & 3) ||
+      ((uintptr_t)experts & 7) || ((uintptr_t)status & 3))
+    return fail(MXMOE_GG_ERR_INVALID, "%s: misaligned pointer (act / act_shared / y / ys need 16 B)", fn);
+  if (T == 0) return MXMOE_GG_OK;
+  if (!act || !topk_ids || !experts || !y || (with_shared && (!act_shared || !ys)))
+    return fail(MXMOE_GG_ERR_INVALID, "%s: NULL pointer", fn);
+  decode::Args a{};
+  a.src = act;
+  a.src_shared = act_shared;
+  a.ids = topk_ids;
+  a.experts = experts;
+  a.out = static_cast<_Float16*>(y);
+  a.out_shared = static_cast<_Float16*>(ys);
+  a.status = status;
+  a.T = (int)T, a.topk = topk, a.E = E, a.with_shared = with_shared != 0;
+  a.K = N, a.K_shared = with_shared ? N_shared : N;
+  a.C = a.C_shared = H;
+  a.kind_mask = kind_mask;
+  return decode::launch<true>(a, stream);
 }
 
 }  // extern "C"

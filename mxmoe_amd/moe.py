@@ -1322,6 +1322,135 @@ class GraphForward:
         return self.g1.status(reset) | self.g2.status(reset) | (seg << self.SEG_STATUS_SHIFT)
 
 
+class DecodeForward:
+    """A MoE layer (``MoEFFN``, or a ``MoEBlock`` with its router) for calls of 1 to ``DECODE_MAX_T`` (16) tokens, with
+    no planner: gate (block only) -> decode_gate_up -> decode_down -> combine, three launches (four with the router),
+    nothing copied to the host, so ``launch`` can be captured with ``torch.cuda.graph`` like ``GraphForward``'s
+    (DESIGN.md §4 "Decode forward"). There is no sort, no segment table and no tile table: the two kernels
+    (mxmoe_moe_decode_gate_up / mxmoe_moe_decode_down, include/mxmoe_moe.h) stream the weights of the experts the ids
+    name and write ``act`` and ``y`` in pair order (row t * topk + k), which the existing combine reads through an
+    identity slot table. The arithmetic is ``MoEFFN.forward``'s: for w8a8 / w4a4 experts ``out`` equals it bit for
+    bit, for fp16 experts within the f32 summation order.
+
+    Experts may be fp16, w8a8_g-1_sym or w4a4_g-1_sym, mixed freely per expert and per linear; the weights are the
+    layer's own tensors (no copy). Anything else — the MX and weight-only types, g128, a layer with a bias or
+    another activation — raises ValueError here. An id outside [0, E) leaves its pair's rows as they were and sets
+    ``DECODE_BAD_ID`` in ``status()``; every access stays inside the buffers."""
+
+    MAX_T = nat.DECODE_MAX_T
+    KINDS = {"fp16": nat.DECODE_FP16, "w8a8_g-1_sym": nat.DECODE_W8A8, "w4a4_g-1_sym": nat.DECODE_W4A4}
+
+    def __init__(self, layer, T: int, topk: Optional[int] = None, device=None, dtype: Optional[torch.dtype] = None):
+        """T: the capacity in tokens (1..16; an uncaptured call may bring fewer rows). dtype: the element type of
+        ``hidden`` and ``out`` (fp16 or bf16); default: the block's ``w_gate.dtype`` (which it must equal), fp16 for
+        a bare ``MoEFFN``."""
+        self.block = layer if isinstance(layer, MoEBlock) else None
+        self.ffn = ffn = layer.ffn if self.block is not None else layer
+        if dtype is None:
+            dtype = self.block.w_gate.dtype if self.block is not None else torch.float16
+        _check_io_dtype(dtype, "dtype")
+        if self.block is not None and dtype != self.block.w_gate.dtype:
+            raise ValueError(f"dtype = {dtype} differs from the block's router ({self.block.w_gate.dtype})")
+        self.dtype = dtype
+        if self.block is not None:
+            if topk is not None and topk != self.block.topk:
+                raise ValueError(f"topk = {topk} differs from the block's {self.block.topk}")
+            topk = self.block.topk
+        if topk is None or topk < 1 or topk > min(ffn.E, 16):
+            raise ValueError(f"DecodeForward needs 1 <= topk <= min(E, 16), got {topk}")
+        if T < 1 or T > self.MAX_T:
+            raise ValueError(f"DecodeForward takes 1 <= T <= {self.MAX_T} tokens, got T = {T}: larger batches are "
+                             "GraphForward's")
+        if ffn.biased_or_gated:
+            raise ValueError("DecodeForward: a layer with a bias or an activation other than 'silu' (gpt-oss) is not "
+                             "supported")
+        for w in list(ffn.w1) + list(ffn.w2):
+            if w.q.qcfg not in self.KINDS:
+                raise ValueError(f"DecodeForward: qcfg {w.q.qcfg} is not supported (experts must be one of "
+                                 f"{tuple(self.KINDS)})")
+        for what, v in (("H", ffn.H), ("N", ffn.N)) + ((("N_shared", ffn.Ns),) if ffn.has_shared else ()):
+            if v <= 0 or v % 128 or v > 16384:
+                raise ValueError(f"DecodeForward: {what} = {v} must be a multiple of 128 and <= 16384")
+        dev = torch.device(device) if device is not None else ffn.w1[0].B.device
+        self.T, self.topk, self.device = T, topk, dev
+        n, H = T * topk, ffn.H
+        self.layout = nat.DECODE_GU_INTERLEAVED if ffn.fuse_silu else nat.DECODE_GU_PLAIN
+        kinds1 = [self.KINDS[w.q.qcfg] for w in ffn.w1]
+        kinds2 = [self.KINDS[w.q.qcfg] for w in ffn.w2]
+        self.mask1, self.mask2 = _tag_mask(kinds1), _tag_mask(kinds2)
+        table = (nat.MoeDecodeExpertC * len(ffn.w1))()
+        for rec, w1, w2, k1, k2 in zip(table, ffn.w1, ffn.w2, kinds1, kinds2):
+            for w in (w1, w2):
+                if w.B.device != dev or not w.B.is_contiguous() or w.B.data_ptr() % 16:
+                    raise ValueError("DecodeForward: every weight must be a contiguous, 16-byte aligned tensor on the "
+                                     "layer's device")
+            rec.b1, rec.sb1 = w1.B.data_ptr(), 0 if w1.scale_b is None else w1.scale_b.data_ptr()
+            rec.b2, rec.sb2 = w2.B.data_ptr(), 0 if w2.scale_b is None else w2.scale_b.data_ptr()
+            rec.kind1, rec.kind2 = k1, k2
+        self.experts = torch.frombuffer(bytearray(bytes(table)), dtype=torch.uint8).to(dev)
+        f16 = dict(dtype=torch.float16, device=dev)
+        self.act = torch.zeros(n, ffn.N, **f16)
+        self.act_shared = torch.zeros(T, ffn.Ns, **f16) if ffn.has_shared else None
+        self.y = torch.zeros(n, H, **f16)
+        self.ys = torch.zeros(T, H, **f16) if ffn.has_shared else None
+        self.out = torch.zeros(T, H, dtype=dtype, device=dev)
+        self.inv_slot = torch.arange(n, dtype=torch.int32, device=dev)  # pair order: the combine's identity table
+        self.dev_status = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.gate_out = None
+        if self.block is not None:
+            i32 = dict(dtype=torch.int32, device=dev)
+            self.gate_out = (torch.zeros(T, topk, **i32), torch.zeros(T, topk, dtype=torch.float32, device=dev),
+                             torch.zeros(T, dtype=torch.float32, device=dev) if self.block.w_shared_gate is not None else None)
+
+    def launch(self, hidden: torch.Tensor, topk_ids: Optional[torch.Tensor] = None,
+               topk_weights: Optional[torch.Tensor] = None, shared_w: Optional[torch.Tensor] = None,
+               stream: Optional[torch.cuda.Stream] = None) -> torch.Tensor:
+        """Launches only; returns ``self.out`` (its first rows for a call with fewer than ``T`` rows). A MoEFFN takes
+        int32 ids and f32 weights [rows, topk] (contiguous, as nothing may be converted here) and the optional f32
+        shared_w [rows]; a MoEBlock routes itself."""
+        ffn, topk = self.ffn, self.topk
+        T = hidden.shape[0] if hidden.dim() == 2 else -1
+        if not 1 <= T <= self.T or hidden.shape[1] != ffn.H or hidden.dtype != self.dtype or not hidden.is_contiguous():
+            raise ValueError(f"hidden must be a contiguous {self.dtype} [1..{self.T}, {ffn.H}] tensor, got {hidden.dtype} "
+                             f"{list(hidden.shape)}")
+        if self.block is not None:
+            if topk_ids is not None or topk_weights is not None or shared_w is not None:
+                raise ValueError("a MoEBlock routes itself: launch(hidden)")
+            b = self.block
+            out = tuple(None if t is None else t[:T] for t in self.gate_out)
+            topk_ids, topk_weights, shared_w = gate(hidden, b.w_gate, topk, renormalize=b.renormalize,
+                                                    w_shared_gate=b.w_shared_gate, stream=stream, out=out, **b.routing)
+        else:
+            for t, dt, shape, what in ((topk_ids, torch.int32, (T, topk), "topk_ids"),
+                                       (topk_weights, torch.float32, (T, topk), "topk_weights"),
+                                       (shared_w, torch.float32, (T,), "shared_w")):
+                if t is None and what == "shared_w":
+                    continue
+                if t is None or t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous():
+                    raise ValueError(f"{what} must be a contiguous {dt} {list(shape)} tensor")
+        shared = int(ffn.has_shared)
+        st = _stream(stream)
+        nat.check(nat.symbol("mxmoe_moe_decode_gate_up")(
+            _DT[self.dtype], _ptr(hidden), T, topk, ffn.E, shared, _ptr(topk_ids), _ptr(self.experts), self.mask1, ffn.H,
+            ffn.N, ffn.Ns, self.layout, _ptr(self.act), _ptr(self.act_shared), _ptr(self.dev_status), st))
+        nat.check(nat.symbol("mxmoe_moe_decode_down")(
+            T, topk, ffn.E, shared, _ptr(topk_ids), _ptr(self.experts), self.mask2, ffn.H, ffn.N, ffn.Ns, _ptr(self.act),
+            _ptr(self.act_shared), _ptr(self.y), _ptr(self.ys), _ptr(self.dev_status), st))
+        out = self.out[:T]
+        _launch_combine(out, self.y, self.inv_slot, None, topk_weights, self.ys, shared_w, topk, stream, None)
+        return out
+
+    __call__ = launch
+
+    def status(self, reset: bool = False) -> int:
+        """0 for a clean history (bits ``_native.DECODE_BAD_ID`` / ``DECODE_BAD_KIND``); synchronises (not for use
+        under capture)."""
+        st = int(self.dev_status.item())
+        if reset:
+            self.dev_status.zero_()
+        return st
+
+
 def qwen2_layer_bench(*args, **kwargs) -> dict:
     """``moe_bench.qwen2_layer_bench`` under the name bench.py imports (the benchmarks live in mxmoe_amd/moe_bench.py)."""
     from .moe_bench import qwen2_layer_bench as bench

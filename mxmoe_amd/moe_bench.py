@@ -12,7 +12,7 @@ import torch
 from . import _native as nat
 from .groupgemm import W4A8_MXFP8, W4A16_MXFP4, QParams
 from .harness import time_launches
-from .moe import (_BITS, GraphForward, MoEBlock, MoEFFN, PlannedForward, SwigluClamp, _ptr, _stream, combine_into, gate,
+from .moe import (_BITS, DecodeForward, GraphForward, MoEBlock, MoEFFN, PlannedForward, SwigluClamp, _ptr, _stream, combine_into, gate,
                   prepare_weight_mx, silu_mul_quant)
 from .workload import (ds2_mixed_qconfig, ds2_workload, load_workload, mixed_qconfig_lp1, qwen2_layer11_workload,
                        w4a16_w8a8_qconfig)
@@ -203,6 +203,71 @@ def graph_forward_bench(batches: Sequence[int] = (128,), model: str = "qwen2_moe
         return out
 
     for bs in batches:  # (a generator: a caller can print each size as it completes)
+        yield one(bs)
+
+
+def decode_forward_bench(batches: Sequence[int] = (1, 4, 16), rounds: int = 4, iters: int = 30):
+    """qwen2_moe layer 11 (LP-1 mixed w4a4 + w8a8, random weights, routing drawn from the committed histogram) at
+    decode sizes, ``DecodeForward`` against ``GraphForward``, both replayed from captured graphs in one process with
+    the sides alternating over rounds (yields one dict per batch size): device and wall time of each graph, the two
+    decode kernels alone, the plain-layout DecodeForward (the same kernels on [gate; up] rows), and the combine. Per
+    side the median of the rounds' medians with min / max (µs). ``faster``: the bar — DecodeForward's device median,
+    max over rounds, below GraphForward's min over rounds."""
+    shapes, topk = load_workload(qwen2_layer11_workload(8192, qconfig=mixed_qconfig_lp1()))["layer-11"], 4
+    E = len(shapes["gate_up"]) - 1
+    H = shapes["gate_up"][0].K
+    N, Ns = shapes["down"][0].K, shapes["down"][-1].K
+    qcfg = [(QParams(a.a_bits, a.w_bits, a.gsize, a.sym), QParams(b.a_bits, b.w_bits, b.gsize, b.sym))
+            for a, b in zip(shapes["gate_up"], shapes["down"])]
+    dev = "cuda"
+    g = torch.Generator().manual_seed(0)
+    hist = torch.tensor([max(s.M, 1) for s in shapes["gate_up"][:E]], dtype=torch.float64)
+    mk = lambda n, k: ((torch.rand(n, k, generator=g) * 2 - 1) * 0.05).half().to(dev)
+    gate_up, down = [mk(2 * N, H) for _ in range(E)] + [mk(2 * Ns, H)], [mk(H, N) for _ in range(E)] + [mk(H, Ns)]
+    layer = MoEFFN(gate_up, down, qcfg, num_routed=E)
+    plain = MoEFFN(gate_up, down, qcfg, num_routed=E, fuse_silu=False)
+    del gate_up, down
+    weight_bytes = lambda ws, es: sum(ws[e].B.numel() * ws[e].B.element_size() for e in es)
+
+    def one(bs: int) -> dict:
+        ids = torch.multinomial((hist / hist.sum()).expand(bs, E), topk, replacement=False, generator=g).to(torch.int32).to(dev)
+        hidden = ((torch.rand(bs, H, generator=g) * 2 - 1)).half().to(dev)
+        wts = torch.softmax(torch.rand(bs, topk, generator=g), dim=1).to(dev)
+        want = layer.forward(hidden, ids, wts)
+        gf, df, dp = GraphForward(layer, bs, topk), DecodeForward(layer, bs, topk), DecodeForward(plain, bs, topk)
+        graphs = {"graph": _captured(lambda: gf.launch(hidden, ids, wts)), "decode": _captured(lambda: df.launch(hidden, ids, wts)),
+                  "decode_plain": _captured(lambda: dp.launch(hidden, ids, wts))}
+        for gr in graphs.values():
+            gr.replay()
+        torch.cuda.synchronize()
+        same = {k: bool(torch.equal(o.out.view(torch.int16), want.view(torch.int16)))
+                for k, o in (("graph", gf), ("decode", df), ("decode_plain", dp))}
+        wall, device = (lambda fn: _wall(fn, iters)), (lambda fn: _device(fn, iters))
+        lib, st = nat.lib(), _stream(None)
+        f = df.ffn
+        gate_up_k = lambda: nat.check(lib.mxmoe_moe_decode_gate_up(
+            nat.DT_FP16, _ptr(hidden), bs, topk, E, 1, _ptr(ids), _ptr(df.experts), df.mask1, f.H, f.N, f.Ns, df.layout,
+            _ptr(df.act), _ptr(df.act_shared), _ptr(df.dev_status), st))
+        down_k = lambda: nat.check(lib.mxmoe_moe_decode_down(
+            bs, topk, E, 1, _ptr(ids), _ptr(df.experts), df.mask2, f.H, f.N, f.Ns, _ptr(df.act), _ptr(df.act_shared),
+            _ptr(df.y), _ptr(df.ys), _ptr(df.dev_status), st))
+        sides = {"graph_device": lambda: device(graphs["graph"].replay), "decode_device": lambda: device(graphs["decode"].replay),
+                 "decode_plain_device": lambda: device(graphs["decode_plain"].replay),
+                 "graph_wall": lambda: wall(graphs["graph"].replay), "decode_wall": lambda: wall(graphs["decode"].replay),
+                 "decode_gate_up": lambda: device(gate_up_k), "decode_down": lambda: device(down_k),
+                 "combine": lambda: device(lambda: combine_into(df.out, df.y, df.inv_slot, wts, df.ys, topk))}
+        out = {"model": "qwen2_moe", "bs": bs, "E": E, "topk": topk, "H": H, "N": N, "N_shared": Ns,
+               "graph_gate_up_mode": gf.mode}
+        out.update({k: _stat(v) for k, v in _rounds(sides, rounds).items()})
+        used = sorted(set(ids.flatten().tolist())) + [E]
+        out["weight_mb"] = {"gate_up": round(weight_bytes(layer.w1, used) / 1e6, 2), "down": round(weight_bytes(layer.w2, used) / 1e6, 2)}
+        out["decode_over_graph_device"] = round(out["decode_device"]["median_us"] / out["graph_device"]["median_us"], 4)
+        out["faster"] = bool(out["decode_device"]["max_us"] < out["graph_device"]["min_us"])
+        out["bit_identical_to_eager"] = same
+        out["status"] = {"graph": gf.status(), "decode": df.status() | dp.status()}
+        return out
+
+    for bs in batches:
         yield one(bs)
 
 

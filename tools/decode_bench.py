@@ -1,0 +1,42 @@
+"""The decode forward against the graph forward: qwen2_moe layer 11 (LP-1 mixed w4a4 + w8a8) at T = 1 / 4 / 16, run as
+  (a) GraphForward replayed from a captured graph (route, segments, device planner, two GroupGEMMs, ...);
+  (b) DecodeForward replayed from a captured graph (decode_gate_up, decode_down, combine; no planner),
+in one process with the sides alternating over rounds (moe_bench.decode_forward_bench): device and wall time of both,
+the two decode kernels alone, the plain-layout variant and the combine. One JSON line per T; --out also writes the
+list to a file (profiles/<round>/decode/bench.json). Exits 1 when an output is not bit-identical to the eager layer.
+
+python tools/decode_bench.py [--rounds 4] [--iters 30] [--batches 1,4,16] [--out FILE]
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+from mxmoe_amd import moe_bench  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rounds", type=int, default=4)
+    ap.add_argument("--iters", type=int, default=30)
+    ap.add_argument("--batches", default="1,4,16")
+    ap.add_argument("--out", default="")
+    args = ap.parse_args()
+    results = []
+    for r in moe_bench.decode_forward_bench([int(b) for b in args.batches.split(",") if b], args.rounds, args.iters):
+        print(json.dumps(r), flush=True)
+        results.append(r)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            json.dump(results, f, indent=1)
+    if not all(all(r["bit_identical_to_eager"].values()) and not any(r["status"].values()) for r in results):
+        sys.exit(1)
+
+
+if __name__ == "__main__":
+    main()
