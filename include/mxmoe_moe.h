@@ -401,14 +401,15 @@ int mxmoe_moe_combine(const void* y, const int32_t* inv_slot, const float* weigh
  * before any HIP call and reported under the entry point's name. Each entry is one launch on `stream`, no allocation,
  * no synchronisation: graph-capturable. */
 enum { MXMOE_DECODE_MAX_T = 16 };
-enum { MXMOE_DECODE_FP16 = 0, MXMOE_DECODE_W8A8 = 1, MXMOE_DECODE_W4A4 = 2 }; /* per linear */
+enum { MXMOE_DECODE_FP16 = 0, MXMOE_DECODE_W8A8 = 1, MXMOE_DECODE_W4A4 = 2,
+       MXMOE_DECODE_W4A16_MX = 3 /* the _ex entries only */ };                 /* per linear */
 enum { MXMOE_DECODE_GU_PLAIN = 0, MXMOE_DECODE_GU_INTERLEAVED = 1 };
 enum { MXMOE_DECODE_BAD_ID = 1, MXMOE_DECODE_BAD_KIND = 2 };                   /* bits of *status */
 typedef struct mxmoe_moe_decode_expert {
   const void* b1;  /* gate_up B [2N][K bits / 8]           */
-  const void* sb1; /* its fp16 scale_b [2N] (FP16: NULL)   */
+  const void* sb1; /* its fp16 scale_b [2N] (FP16: NULL; W4A16_MX: the e8m0 rows, uint8 [2N][16 ceil(K / 512)]) */
   const void* b2;  /* down B [H][N bits / 8]               */
-  const void* sb2; /* its fp16 scale_b [H] (FP16: NULL)    */
+  const void* sb2; /* its fp16 scale_b [H] (FP16: NULL; W4A16_MX: the e8m0 rows, uint8 [H][16 ceil(N / 512)])    */
   int32_t kind1, kind2;
 } mxmoe_moe_decode_expert;
 int mxmoe_moe_decode_gate_up(int dtype, const void* hidden, int64_t T, int topk, int E, int with_shared,
@@ -417,6 +418,43 @@ int mxmoe_moe_decode_gate_up(int dtype, const void* hidden, int64_t T, int topk,
 int mxmoe_moe_decode_down(int64_t T, int topk, int E, int with_shared, const int32_t* topk_ids,
                           const mxmoe_moe_decode_expert* experts, uint32_t kind_mask, int H, int N, int N_shared,
                           const void* act, const void* act_shared, void* y, void* ys, int32_t* status, void* stream);
+
+/* The decode forward for gpt-oss layers (added to ABI 7 without a version bump): the two entries above with one more
+ * kind and, in gate_up, the biases and the gated activation of an mxmoe_moe_glu. Arguments, pair order, safety and
+ * limits are those of mxmoe_moe_decode_gate_up / mxmoe_moe_decode_down; the expert record is unchanged. The first two
+ * entries keep their kernels and refuse kind bit 3; these run kernels of their own.
+ *   MXMOE_DECODE_W4A16_MX (w4a16_g32_sym_MXFP4): B the canonical e2m1 codes, uint8 [rows][K / 2] (element 2i the low
+ *            nibble of byte i); sb1 / sb2 the e8m0 scale bytes in the device layout of include/mxmoe_gg.h, uint8
+ *            [rows][16 ceil(K / 512)], pads 127 — byte for byte the GroupGEMM's operands of that type, used in place.
+ *            K % 64 == 0 (the widths' multiple of 128 gives it).
+ *   A row    x (gate_up: hidden[t], bf16 converted as above; down: act[p]) as fp16: not quantised.
+ *   b[r][k]  = fp16(e2m1(code) * 2^(byte - 127)) by v_cvt_scalef32_pk_f16_fp4 on the f32 byte << 23, the GroupGEMM's
+ *            convert: the same fp16 value as there for every scale byte (exact for bytes 104..140, include/mxmoe_gg.h).
+ *   v(r)     = fp16_rn(sum_k f32(x[k]) * f32(b[r][k])), accumulated in f32 (fma; the order of the sum is the
+ *            kernel's) — the contract of the GroupGEMM's w4a16_g32_sym_MXFP4 tile.
+ * mxmoe_moe_decode_gate_up_ex, every kind: with g = v(gate row of n), u = v(up row of n) (fp16), expert e of the pair
+ *   (the shared expert: bias_shared) and bias rows [bg | bu] = glu->bias_routed[e] (fp16 [E][2N], indexed by column
+ *   whatever the weight layout), mxmoe_moe_glu_quant's arithmetic in f32:
+ *     g' = f32 g + f32 bg[n], u' = f32 u + f32 bu[n]  (one IEEE add each; a NULL bias: no add),
+ *     MXMOE_GLU_SILU: a = g' * rcp(1 + exp2(g' * -log2 e)) * u';  MXMOE_GLU_SWIGLU_CLAMP: gc = min(g', limit),
+ *     uc = min(max(u', -limit), limit), a = (gc * rcp(1 + exp2(gc * c))) * (uc + 1.0f), c = -(alpha * 1.4426950408889634f)
+ *     computed once on the host in f32;  act[p][n] = fp16_rn(a), the f32 product rounded on its own.
+ *   The bias row is that of the workgroup's own expert, never indexed by an id. glu == NULL, or SILU with both biases
+ *   NULL: mxmoe_moe_decode_gate_up's output byte for byte.
+ * mxmoe_moe_decode_down_ex: y[p][h] = v(h) with kind2 on b2 / sb2. A down bias is not added here: it stays in the
+ *   combine (mxmoe_moe_combine_bias / _dt with inv_slot[p] = p and sorted_expert[p] = topk_ids[p]: an id outside
+ *   [0, E) gets no bias there).
+ * Refusals, before any HIP call and under the entry's name: everything the first two entries check; glu's checks
+ * as in mxmoe_moe_glu_quant (an unknown act, a non-finite alpha, a limit that is not finite and > 0, a bias that is
+ * not 16-byte aligned) and bias_shared without with_shared: MXMOE_GG_ERR_INVALID; a kind bit >= 4:
+ * MXMOE_GG_ERR_UNSUPPORTED. One launch each, no allocation, no synchronisation: graph-capturable. */
+int mxmoe_moe_decode_gate_up_ex(const mxmoe_moe_glu* glu, int dtype, const void* hidden, int64_t T, int topk, int E,
+                                int with_shared, const int32_t* topk_ids, const mxmoe_moe_decode_expert* experts,
+                                uint32_t kind_mask, int H, int N, int N_shared, int layout, void* act, void* act_shared,
+                                int32_t* status, void* stream);
+int mxmoe_moe_decode_down_ex(int64_t T, int topk, int E, int with_shared, const int32_t* topk_ids,
+                             const mxmoe_moe_decode_expert* experts, uint32_t kind_mask, int H, int N, int N_shared,
+                             const void* act, const void* act_shared, void* y, void* ys, int32_t* status, void* stream);
 
 #ifdef __cplusplus
 }

@@ -107,6 +107,8 @@ EXPORTED_SYMBOLS = (
     "mxmoe_moe_gate_dt", "mxmoe_moe_gather_quant", "mxmoe_moe_combine_dt",
     # the decode forward (1..16 tokens, no planner)
     "mxmoe_moe_decode_gate_up", "mxmoe_moe_decode_down",
+    # the decode forward for gpt-oss layers: MXFP4 weights, gate_up biases, the clamped SwiGLU
+    "mxmoe_moe_decode_gate_up_ex", "mxmoe_moe_decode_down_ex",
 )
 # added to ABI 7 without a version bump (additive): a product library without them is a stale build
 GPTOSS_SYMBOLS = ("mxmoe_moe_gate_ex2", "mxmoe_moe_glu_quant", "mxmoe_moe_combine_bias")
@@ -114,10 +116,12 @@ GPTOSS_SYMBOLS = ("mxmoe_moe_gate_ex2", "mxmoe_moe_glu_quant", "mxmoe_moe_combin
 WIDE_GATE_SYMBOLS = ("mxmoe_moe_gate_wide",)
 DT_SYMBOLS = ("mxmoe_moe_gate_dt", "mxmoe_moe_gather_quant", "mxmoe_moe_combine_dt")  # (likewise: the bf16 layers)
 DECODE_SYMBOLS = ("mxmoe_moe_decode_gate_up", "mxmoe_moe_decode_down")  # (likewise: the decode forward)
+DECODE_EX_SYMBOLS = ("mxmoe_moe_decode_gate_up_ex", "mxmoe_moe_decode_down_ex")  # (likewise: gpt-oss layers)
 DT_FP16, DT_BF16 = 0, 1  # MXMOE_DT_* (include/mxmoe_moe.h)
 # MXMOE_DECODE_* (include/mxmoe_moe.h): the token limit, the kinds per linear, the gate_up layouts, the status bits
 DECODE_MAX_T = 16
 DECODE_FP16, DECODE_W8A8, DECODE_W4A4 = 0, 1, 2
+DECODE_W4A16_MX = 3  # (the _ex entries only)
 DECODE_GU_PLAIN, DECODE_GU_INTERLEAVED = 0, 1
 DECODE_BAD_ID, DECODE_BAD_KIND = 1, 2
 GLU_SILU, GLU_SWIGLU_CLAMP = 0, 1  # MXMOE_GLU_* (include/mxmoe_moe.h)
@@ -298,6 +302,13 @@ def _declare(lib: ctypes.CDLL) -> None:
         lib.mxmoe_moe_decode_down.restype = c.c_int
         lib.mxmoe_moe_decode_down.argtypes = [c.c_int64, c.c_int, c.c_int, c.c_int, P, P, c.c_uint32, c.c_int, c.c_int,
                                               c.c_int, P, P, P, P, P, P]
+    if all(hasattr(lib, fn) for fn in DECODE_EX_SYMBOLS):  # (builds before the gpt-oss decode forward lack them)
+        lib.mxmoe_moe_decode_gate_up_ex.restype = c.c_int
+        lib.mxmoe_moe_decode_gate_up_ex.argtypes = [c.POINTER(MoeGluC), c.c_int, P, c.c_int64, c.c_int, c.c_int, c.c_int, P, P,
+                                                    c.c_uint32, c.c_int, c.c_int, c.c_int, c.c_int, P, P, P, P]
+        lib.mxmoe_moe_decode_down_ex.restype = c.c_int
+        lib.mxmoe_moe_decode_down_ex.argtypes = [c.c_int64, c.c_int, c.c_int, c.c_int, P, P, c.c_uint32, c.c_int, c.c_int,
+                                                 c.c_int, P, P, P, P, P, P]
 
 
 def lib() -> ctypes.CDLL:

@@ -27,6 +27,17 @@
 // first routed workgroup sets MXMOE_DECODE_BAD_ID in the status word. The expert record is indexed by the workgroup's
 // own expert number. A kind outside the call's kind_mask (which sized the LDS rows) sets MXMOE_DECODE_BAD_KIND and the
 // workgroup writes nothing.
+//
+// The _ex entries (mxmoe_moe_decode_gate_up_ex, mxmoe_moe_decode_down_ex: gpt-oss layers) run kernels of their own,
+// decode_ex_kernel<DOWN>, which begin with the same statements (moe_decode_body.inc) and instantiate expert_tile with
+// EX, a template parameter; without it none of the following exists:
+//   W4A16_MX  w4a16_g32_sym_MXFP4: the A row stays fp16 (4 LDS bytes per weight byte), stored permuted inside every
+//             1024 bytes so that a lane's four 16-byte reads of its MX block are the other kinds' conflict-free pattern
+//             (quant_row); lane l at step s owns block 16 s + l, reads one e8m0 byte of the device scale layout,
+//             dequantises a dword of codes at a time with the GroupGEMM's convert and reuses it for every A row of the
+//             batch, accumulating in f32 (dot_rows_mx).
+//   epilogue  gate_up: the bias row of the workgroup's own expert and the gated activation of an mxmoe_moe_glu, by the
+//             activation pass's own helper (glu_value of moe_ops.hip); glu_out.
 #pragma once
 
 namespace mxmoe {
@@ -58,8 +69,23 @@ struct Args {
   uint32_t kind_mask;
 };
 
-__host__ __device__ inline int row_bytes(int kind, int K) {
+// the _ex entries' arguments: the gate_up biases and the gated activation of an mxmoe_moe_glu, as GluArgs carries them
+struct ArgsEx : Args {
+  const _Float16* bias_routed;  // gate_up: [E][2 C] ([gate | up] columns) or NULL
+  const _Float16* bias_shared;  // gate_up: [2 C_shared] or NULL
+  int glu;                      // gate_up: kGluSilu / kGluSwigluClamp
+  float c, limit;               // SWIGLU_CLAMP: -(alpha log2 e), the clamp
+};
+template <bool EX> struct ArgsOf { typedef Args type; };
+template <> struct ArgsOf<true> { typedef ArgsEx type; };
+
+// bytes of a weight row in global memory, and of an A row in LDS: the integer kinds quantise A to the weights' width,
+// W4A16_MX keeps the fp16 row (four times its weight row)
+__host__ __device__ inline int b_row_bytes(int kind, int K) {
   return kind == MXMOE_DECODE_FP16 ? 2 * K : kind == MXMOE_DECODE_W8A8 ? K : K / 2;
+}
+__host__ __device__ inline int a_row_bytes(int kind, int K) {
+  return kind == MXMOE_DECODE_W4A16_MX ? 2 * K : b_row_bytes(kind, K);
 }
 
 // sum over the 16 lanes of a DPP row (quad_perm [1,0,3,2], [2,3,0,1], row_half_mirror, row_mirror): every lane
@@ -129,18 +155,73 @@ __device__ __forceinline__ _Float16 silu_mul(_Float16 g16, _Float16 u16) {
   return (_Float16)p;
 }
 
+// The _ex gate_up epilogue: mxmoe_moe_glu_quant's arithmetic on the fp16 g, u (the GLU builds of act_quant_kernel:
+// one f32 add per bias, then glu_value — that pass's own helper), the f32 product rounded on its own as in silu_mul.
+// has_b false and kGluSilu: silu_mul's value bit for bit.
+template <int GLU>
+__device__ __forceinline__ _Float16 glu_out(_Float16 g16, _Float16 u16, bool has_b, _Float16 bg, _Float16 bu, float limit,
+                                            float c) {
+  float g = (float)g16, v = (float)u16;
+  if (has_b) {
+    g = g + (float)bg;
+    v = v + (float)bu;
+  }
+  float p = glu_value<GLU>(g, v, limit, c);
+  asm volatile("" : "+v"(p));
+  return (_Float16)p;
+}
+
+// W4A16_MX: the 32 e2m1 codes of one MX block (16 bytes, element 2i the low nibble of byte i) times 2^(byte - 127) as
+// fp16, by the GroupGEMM's convert (wo_dequant_mx of gg_device.h: v_cvt_scalef32_pk_f16_fp4 on the f32 byte << 23), so
+// b[n][k] is the GroupGEMM's fp16 value for every scale byte. Dword j of the block's 16 bytes: elements 8 j .. 8 j + 7.
+__device__ __forceinline__ h8_t dequant_mx(uint32_t w, uint32_t scale_bits) {
+  const float sc = __builtin_bit_cast(float, scale_bits);
+  const h2_t p0 = __builtin_amdgcn_cvt_scalef32_pk_f16_fp4(w, sc, 0);
+  const h2_t p1 = __builtin_amdgcn_cvt_scalef32_pk_f16_fp4(w, sc, 1);
+  const h2_t p2 = __builtin_amdgcn_cvt_scalef32_pk_f16_fp4(w, sc, 2);
+  const h2_t p3 = __builtin_amdgcn_cvt_scalef32_pk_f16_fp4(w, sc, 3);
+  return h8_t{p0[0], p0[1], p1[0], p1[1], p2[0], p2[1], p3[0], p3[1]};
+}
+// its dot: 8 dequantised weights against the same 8 fp16 elements of an A row, accumulated in f32
+// (acc += f32(b) * f32(a), v_fma_mix_f32 as the fp16 kind); a row's sum is rounded once, fp16_rn(acc)
+template <> struct Dot<MXMOE_DECODE_W4A16_MX> {
+  typedef float acc_t;
+  static __device__ __forceinline__ float dot(const h8_t& w, const uint4& a, float acc) {
+    const h8_t av = __builtin_bit_cast(h8_t, a);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) acc = fmaf((float)w[j], (float)av[j], acc);
+    return acc;
+  }
+  static __device__ __forceinline__ _Float16 finish(float acc, _Float16, _Float16) { return (_Float16)acc; }
+};
+
 // Row `src` (K fp16, or bf16 converted as mxmoe_moe_gather_quant does) quantised by kind's tag into `row` (LDS,
 // pack_wxax order) by one wave, zeros behind it up to a multiple of 1024 bytes (the dot loop's group of four 256-byte
 // steps reads the pad); its scale to *scale. The arithmetic and the helpers are act_quant_kernel's.
 __device__ __forceinline__ void quant_row(const uint8_t* __restrict__ src, int K, int kind, bool bf, uint8_t* row,
                                           _Float16* scale) {
   const int lane = threadIdx.x & 63;
-  const int KB = row_bytes(kind, K);
-  for (int o = KB + lane * 16; o < ((KB + 1023) & ~1023); o += 1024) *reinterpret_cast<uint4*>(row + o) = uint4{0, 0, 0, 0};
+  const int KB = a_row_bytes(kind, K);
   auto ld = [&](int idx) -> h8_t {
     const uint4 v = *reinterpret_cast<const uint4*>(src + 2 * idx);
     return bf ? bf16x8_to_f16(v) : __builtin_bit_cast(h8_t, v);
   };
+  if (kind == MXMOE_DECODE_W4A16_MX) {
+    // The fp16 row, permuted inside every 1024 bytes (a step: 16 MX blocks of 64 bytes): piece j (16 bytes) of block l
+    // goes to byte 256 j + 16 l, so that the dot loop's j-th read of lane l is the plain kinds' conflict-free pattern
+    // (16 lanes, 16 consecutive 16-byte slots: all 64 banks once). Lane 16 j + l copies that piece, so the stores are
+    // the plain copy's (consecutive lanes, consecutive slots) and only the global address is permuted. Pieces past the
+    // row are zeros up to the step's end.
+    const int src_piece = 4 * (lane & 15) + (lane >> 4);
+    for (int o = 0; o < ((KB + 1023) & ~1023); o += 1024) {
+      const int idx = (o >> 1) + 8 * src_piece;
+      h8_t v = {0, 0, 0, 0, 0, 0, 0, 0};
+      if (idx < K) v = ld(idx);
+      *reinterpret_cast<h8_t*>(row + o + lane * 16) = v;
+    }
+    return;
+  }
+  for (int o = KB + lane * 16; o < ((KB + 1023) & ~1023); o += 1024) *reinterpret_cast<uint4*>(row + o) = uint4{0, 0, 0, 0};
   if (kind == MXMOE_DECODE_FP16) {
 #pragma unroll 4
     for (int idx = lane * 8; idx < K; idx += 512) *reinterpret_cast<h8_t*>(row + 2 * idx) = ld(idx);
@@ -234,13 +315,89 @@ __device__ __forceinline__ void dot_rows(const uint8_t* __restrict__ w0, const u
   *o1 = Dot<KIND>::finish(v1, sa, b1);
 }
 
+// dot_rows for W4A16_MX. A step is 256 bytes of codes = 16 MX blocks: lane l holds block 16 s + l of both weight rows
+// and its scale byte — device byte 16 s + 4 (l & 3) + (l >> 2) of the row's scales (include/mxmoe_gg.h:
+// dev[16 t + 4 g + i] = canon[16 t + 4 i + g]; a row has 16 bytes per step, pads 127). The block is dequantised once
+// (a quarter at a time) and multiplied with the 64 bytes of the block in every A row of the batch (quant_row's
+// permuted copy: four 16-byte reads at 1024 s + 256 j + 16 l). SB0 / SB1: the two rows' scale bytes. A lane past the row's end (only inside its
+// last step) loads the row's first bytes, codes and scale alike, and both are zeroed: +0 weights on the A rows' zero
+// pad. Whole steps past the end are loaded the same way (the four steps in flight) but not multiplied: the A rows end
+// with the last step.
+__device__ __forceinline__ void dot_rows_mx(const uint8_t* __restrict__ w0, const uint8_t* __restrict__ w1,
+                                            const uint8_t* __restrict__ SB0, const uint8_t* __restrict__ SB1, int KB,
+                                            const uint8_t* A, int lds_row, int nr, int l16, _Float16* o0, _Float16* o1) {
+  typedef Dot<MXMOE_DECODE_W4A16_MX> D;
+  float acc0[kBatchRows], acc1[kBatchRows];
+#pragma unroll
+  for (int r = 0; r < kBatchRows; ++r) acc0[r] = acc1[r] = 0;
+  const int S = (KB + 255) >> 8;
+  const int sl = 4 * (l16 & 3) + (l16 >> 2);
+  for (int s0 = 0; s0 < S; s0 += 4) {
+    uint4 wa[4], wb[4];
+    uint32_t sa[4], sb[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {  // 8 loads of 16 B and 8 scale bytes in flight
+      const bool in = ((s0 + u) * 16 + l16) * 16 < KB;
+      const int wo = in ? ((s0 + u) * 16 + l16) * 16 : 0;
+      const int so = in ? (s0 + u) * 16 + sl : 0;
+      wa[u] = *reinterpret_cast<const uint4*>(w0 + wo);
+      wb[u] = *reinterpret_cast<const uint4*>(w1 + wo);
+      sa[u] = (uint32_t)SB0[so] << 23;
+      sb[u] = (uint32_t)SB1[so] << 23;
+      if (!in) {
+        wa[u] = wb[u] = uint4{0, 0, 0, 0};
+        sa[u] = sb[u] = 0;
+      }
+    }
+    int nrs = nr, ldr = lds_row;
+    asm volatile("" : "+s"(nrs), "+s"(ldr));  // (as in dot_rows)
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      if (s0 + u < S) {  // workgroup-uniform
+        const uint32_t da[4] = {wa[u].x, wa[u].y, wa[u].z, wa[u].w}, db[4] = {wb[u].x, wb[u].y, wb[u].z, wb[u].w};
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {  // a quarter of the block at a time: 8 weights of each row live, not 32
+          const h8_t x0 = dequant_mx(da[j], sa[u]), x1 = dequant_mx(db[j], sb[u]);
+          const uint8_t* const aj = A + (s0 + u) * 1024 + 256 * j + l16 * 16;  // (< lds_row: whole steps of the padded row)
+#pragma unroll
+          for (int r = 0; r < kBatchRows; ++r) {
+            if (r < nrs) {  // workgroup-uniform
+              const uint4 av = *reinterpret_cast<const uint4*>(aj + r * ldr);
+              acc0[r] = D::dot(x0, av, acc0[r]);
+              acc1[r] = D::dot(x1, av, acc1[r]);
+            }
+          }
+        }
+      }
+    }
+  }
+  float v0 = 0, v1 = 0;
+  int lsel = l16, nrs = nr;
+  asm volatile("" : "+v"(lsel), "+s"(nrs));
+#pragma unroll
+  for (int r = 0; r < kBatchRows; ++r) {
+    if (r < nrs) {
+      const float t0 = row16_sum(acc0[r]), t1 = row16_sum(acc1[r]);
+      if (lsel == r) {
+        v0 = t0;
+        v1 = t1;
+      }
+    }
+  }
+  *o0 = D::finish(v0, (_Float16)0, (_Float16)0);
+  *o1 = D::finish(v1, (_Float16)0, (_Float16)0);
+}
+
 // One workgroup's work on an expert of kind KIND: per batch of rows, the A rows into LDS, then the tile's columns.
-template <bool DOWN, int KIND>
-__device__ __forceinline__ void expert_tile(const Args& a, const mxmoe_moe_decode_expert& ex, bool shared, int tile,
-                                            int nrows, uint8_t* s_a, const int* s_rows, _Float16* s_scale) {
+// EX: the _ex entries' build — `brow`, the bias row of the workgroup's expert ([gate | up], or NULL), and the gated
+// activation of ArgsEx in the gate_up epilogue. Without EX none of that code exists.
+template <bool DOWN, int KIND, bool EX = false>
+__device__ __forceinline__ void expert_tile(const typename ArgsOf<EX>::type& a, const mxmoe_moe_decode_expert& ex,
+                                            bool shared, int tile, int nrows, uint8_t* s_a, const int* s_rows,
+                                            _Float16* s_scale, const _Float16* brow = nullptr) {
   const int tid = threadIdx.x, wave = tid >> 6;
   const int K = shared ? a.K_shared : a.K, C = shared ? a.C_shared : a.C;
-  const int KB = row_bytes(KIND, K);  // <= lds_row: the kind is in the mask
+  const int KB = b_row_bytes(KIND, K);  // of a weight row (the A row's bytes are <= lds_row: the kind is in the mask)
   const uint8_t* const B = static_cast<const uint8_t*>(DOWN ? ex.b2 : ex.b1);
   const _Float16* const SB = static_cast<const _Float16*>(DOWN ? ex.sb2 : ex.sb1);
   const uint8_t* const src = static_cast<const uint8_t*>(shared ? a.src_shared : a.src);
@@ -274,13 +431,26 @@ __device__ __forceinline__ void expert_tile(const Args& a, const mxmoe_moe_decod
         wr1 = C + n;
       }
       _Float16 o0, o1;
-      dot_rows<KIND>(B + (int64_t)wr0 * KB, B + (int64_t)wr1 * KB, SB, wr0, wr1, KB, s_a, a.lds_row, s_scale, nr, l16, &o0,
-                     &o1);
+      if constexpr (KIND == MXMOE_DECODE_W4A16_MX) {
+        const uint8_t* const SB8 = reinterpret_cast<const uint8_t*>(SB);  // e8m0 rows of 16 bytes per step
+        const int sr = ((KB + 255) >> 8) * 16;
+        dot_rows_mx(B + (int64_t)wr0 * KB, B + (int64_t)wr1 * KB, SB8 + (int64_t)wr0 * sr, SB8 + (int64_t)wr1 * sr, KB, s_a,
+                    a.lds_row, nr, l16, &o0, &o1);
+      } else {
+        dot_rows<KIND>(B + (int64_t)wr0 * KB, B + (int64_t)wr1 * KB, SB, wr0, wr1, KB, s_a, a.lds_row, s_scale, nr, l16, &o0,
+                       &o1);
+      }
       if (l16 < nr) {
         _Float16* const orp = out + (int64_t)orow * C;
         if constexpr (DOWN) {
           orp[n] = o0;
           orp[n + 16] = o1;
+        } else if constexpr (EX) {
+          // the bias by column, whatever the weight layout: bg[n], bu[C + n] of the workgroup's own expert
+          const bool has_b = brow != nullptr;  // workgroup-uniform
+          const _Float16 bg = has_b ? brow[n] : (_Float16)0, bu = has_b ? brow[C + n] : (_Float16)0;
+          orp[n] = a.glu == kGluSwigluClamp ? glu_out<kGluSwigluClamp>(o0, o1, has_b, bg, bu, a.limit, a.c)
+                                            : glu_out<kGluSilu>(o0, o1, has_b, bg, bu, a.limit, a.c);
         } else {
           orp[n] = silu_mul(o0, o1);
         }
@@ -289,63 +459,43 @@ __device__ __forceinline__ void expert_tile(const Args& a, const mxmoe_moe_decod
   }
 }
 
-// DOWN = false: decode_gate_up; true: decode_down
+// The kernels. DOWN = false: decode_gate_up; true: decode_down. Both begin with the statements of
+// moe_decode_body.inc; decode_ex_kernel (the _ex entries) also carries the W4A16_MX kind and (gate_up) the biases and the
+// gated activation, through expert_tile's EX parameter: without it that code does not exist.
 template <bool DOWN>
 __global__ __launch_bounds__(kThreadsD) void decode_kernel(Args a) {
-  extern __shared__ __attribute__((aligned(16))) uint8_t s_a[];  // [rb][lds_row]
-  __shared__ int s_rows[kMaxPairs];
-  __shared__ int s_cnt[kThreadsD / 64];
-  __shared__ _Float16 s_scale[kBatchRows];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int nsh = a.with_shared ? a.tiles_shared : 0;
-  const int b = blockIdx.x;
-  const bool shared = b < nsh;
-  const int e = shared ? a.E : (b - nsh) / a.tiles;  // in [0, E] by the grid's size
-  const int tile = shared ? b : (b - nsh) % a.tiles;
-  const int npairs = a.T * a.topk;
-
-  int nrows = a.T;
-  if (!shared) {
-    const int id = tid < npairs ? a.ids[tid] : -1;
-    const bool hit = id == e;
-    const uint64_t m = __builtin_amdgcn_ballot_w64(hit);
-    if (lane == 0) s_cnt[wave] = __popcll(m);
-    if (b == nsh && a.status) {  // one workgroup reports the ids that no workgroup matches
-      const bool bad = tid < npairs && (id < 0 || id >= a.E);
-      if (__builtin_amdgcn_ballot_w64(bad) != 0 && lane == 0) atomicOr(a.status, MXMOE_DECODE_BAD_ID);
-    }
-    __syncthreads();
-    int base = 0;
-    nrows = 0;
-#pragma unroll
-    for (int w = 0; w < kThreadsD / 64; ++w) {
-      base += w < wave ? s_cnt[w] : 0;
-      nrows += s_cnt[w];
-    }
-    if (nrows == 0) return;  // no token chose this expert
-    if (hit) s_rows[base + __popcll(m & (((uint64_t)1 << lane) - 1))] = tid;
-  }
-
-  const mxmoe_moe_decode_expert ex = a.experts[e];
-  const int kind = DOWN ? ex.kind2 : ex.kind1;
-  if (kind < 0 || kind > 31 || !((a.kind_mask >> kind) & 1u)) {  // (the mask holds existing kinds only: the entry's check)
-    if (tid == 0 && a.status) atomicOr(a.status, MXMOE_DECODE_BAD_KIND);
-    return;
-  }
+#include "moe_decode_body.inc"
   // the kind is chosen once, outside the loops: one dequant-and-dot body per kind, one switch
   if (kind == MXMOE_DECODE_FP16) expert_tile<DOWN, MXMOE_DECODE_FP16>(a, ex, shared, tile, nrows, s_a, s_rows, s_scale);
   else if (kind == MXMOE_DECODE_W8A8) expert_tile<DOWN, MXMOE_DECODE_W8A8>(a, ex, shared, tile, nrows, s_a, s_rows, s_scale);
   else expert_tile<DOWN, MXMOE_DECODE_W4A4>(a, ex, shared, tile, nrows, s_a, s_rows, s_scale);
 }
+template <bool DOWN>
+__global__ __launch_bounds__(kThreadsD) void decode_ex_kernel(ArgsEx a) {
+#include "moe_decode_body.inc"
+  // the bias row of the workgroup's own expert (e < E by the grid's size): never indexed by an id
+  const _Float16* brow = nullptr;
+  if constexpr (!DOWN) brow = shared ? a.bias_shared : a.bias_routed ? a.bias_routed + (int64_t)e * 2 * a.C : nullptr;
+  if (kind == MXMOE_DECODE_FP16)
+    expert_tile<DOWN, MXMOE_DECODE_FP16, true>(a, ex, shared, tile, nrows, s_a, s_rows, s_scale, brow);
+  else if (kind == MXMOE_DECODE_W8A8)
+    expert_tile<DOWN, MXMOE_DECODE_W8A8, true>(a, ex, shared, tile, nrows, s_a, s_rows, s_scale, brow);
+  else if (kind == MXMOE_DECODE_W4A4)
+    expert_tile<DOWN, MXMOE_DECODE_W4A4, true>(a, ex, shared, tile, nrows, s_a, s_rows, s_scale, brow);
+  else
+    expert_tile<DOWN, MXMOE_DECODE_W4A16_MX, true>(a, ex, shared, tile, nrows, s_a, s_rows, s_scale, brow);
+}
 
 // ---------------------------------------------------------------------------------------------
 // host side: the entries' checks (before any HIP call) and the launch geometry
 
-inline int kind_mask_check(const char* fn, uint32_t kind_mask) {
-  const uint32_t known = 1u << MXMOE_DECODE_FP16 | 1u << MXMOE_DECODE_W8A8 | 1u << MXMOE_DECODE_W4A4;
+// ex: the _ex entries, which also take W4A16_MX
+inline int kind_mask_check(const char* fn, uint32_t kind_mask, bool ex = false) {
+  const uint32_t known = 1u << MXMOE_DECODE_FP16 | 1u << MXMOE_DECODE_W8A8 | 1u << MXMOE_DECODE_W4A4 |
+                         (ex ? 1u << MXMOE_DECODE_W4A16_MX : 0u);
   if (kind_mask & ~known)
-    return fail(MXMOE_GG_ERR_UNSUPPORTED, "%s: unknown expert kind in kind_mask %#x (fp16, w8a8_g-1_sym and "
-                "w4a4_g-1_sym only)", fn, kind_mask);
+    return fail(MXMOE_GG_ERR_UNSUPPORTED, "%s: unknown expert kind in kind_mask %#x (fp16, w8a8_g-1_sym%s w4a4_g-1_sym%s "
+                "only)", fn, kind_mask, ex ? "," : " and", ex ? " and w4a16_g32_sym_MXFP4" : "");
   if (!kind_mask) return fail(MXMOE_GG_ERR_INVALID, "%s: kind_mask names no kind", fn);
   return MXMOE_GG_OK;
 }
@@ -365,8 +515,8 @@ inline int sizes_check(const char* fn, int64_t T, int topk, int E, int with_shar
 inline int geometry(Args& a) {
   int kb = 0;
   const int kmax = a.with_shared && a.K_shared > a.K ? a.K_shared : a.K;
-  for (int k = 0; k < 3; ++k)
-    if ((a.kind_mask >> k) & 1u) kb = row_bytes(k, kmax) > kb ? row_bytes(k, kmax) : kb;
+  for (int k = 0; k <= MXMOE_DECODE_W4A16_MX; ++k)
+    if ((a.kind_mask >> k) & 1u) kb = a_row_bytes(k, kmax) > kb ? a_row_bytes(k, kmax) : kb;
   a.lds_row = kb = (kb + 1023) & ~1023;  // (rows are zero-padded to the dot loop's group of four 256-byte steps)
   int rb = kLdsBudget / kb;
   rb = rb < 1 ? 1 : rb > kBatchRows ? kBatchRows : rb;
@@ -382,12 +532,18 @@ inline int geometry(Args& a) {
   return a.rb * a.lds_row;
 }
 
-template <bool DOWN>
-inline int launch(Args a, void* stream) {
+// ArgsEx: the _ex kernels; Args: the kernels of the first two entries
+template <bool DOWN, class ARGS>
+inline int launch(ARGS a, void* stream) {
   const int lds = geometry(a);
   const int64_t blocks = (int64_t)a.tiles_shared + (int64_t)a.E * a.tiles;
-  hipLaunchKernelGGL(decode_kernel<DOWN>, dim3((unsigned)blocks), dim3(kThreadsD), lds, (hipStream_t)stream, a);
-  return launched(DOWN ? "decode_down_kernel" : "decode_gate_up_kernel");
+  if constexpr (std::is_same<ARGS, ArgsEx>::value) {
+    hipLaunchKernelGGL(decode_ex_kernel<DOWN>, dim3((unsigned)blocks), dim3(kThreadsD), lds, (hipStream_t)stream, a);
+    return launched(DOWN ? "decode_down_ex_kernel" : "decode_gate_up_ex_kernel");
+  } else {
+    hipLaunchKernelGGL(decode_kernel<DOWN>, dim3((unsigned)blocks), dim3(kThreadsD), lds, (hipStream_t)stream, a);
+    return launched(DOWN ? "decode_down_kernel" : "decode_gate_up_kernel");
+  }
 }
 
 }  // namespace decode

@@ -19,7 +19,8 @@
 // The router in front of them (mxmoe_moe_gate: logits on the MFMA, top-k, softmax; mxmoe_moe_gate_ex:
 // sigmoid scores, selection bias, group-limited top-k) is moe_gate.h; beyond 256 experts (mxmoe_moe_gate_wide),
 // moe_gate_wide.h. The decode forward (mxmoe_moe_decode_gate_up, mxmoe_moe_decode_down: a layer call of up to 16 tokens
-// as two weight-streaming launches with no planner) is moe_decode.h.
+// as two weight-streaming launches with no planner; their _ex forms for gpt-oss layers: MXFP4 weights, gate_up biases,
+// the clamped SwiGLU) is moe_decode.h.
 // bf16 layers (mxmoe_moe_gate_dt, mxmoe_moe_gather_quant, mxmoe_moe_combine_dt): the element type of the router's
 // operands, of the gather's source rows and of the combine's output is a template parameter of the kernels above;
 // the fp16 instantiations are the kernels as they were. No reference counterpart (the reference is fp16 only).
@@ -191,6 +192,22 @@ struct GluArgs : ActArgs {
 enum { kGluNone = 0, kGluSilu = 1, kGluSwigluClamp = 2 };
 template <int GLU> struct ActArgsOf { typedef GluArgs type; };
 template <> struct ActArgsOf<kGluNone> { typedef ActArgs type; };
+// The gated activation of mxmoe_moe_glu (include/mxmoe_moe.h) on the f32 gate and up values, biases added: the f32
+// value `a` that its caller rounds to fp16. One definition for the GLU builds of act_quant_kernel and the decode
+// forward's _ex gate_up epilogue (moe_decode.h).
+template <int GLU>
+__device__ __forceinline__ float glu_value(float g, float v, float limit, float c) {
+  static_assert(GLU == kGluSilu || GLU == kGluSwigluClamp, "a gated activation");
+  if constexpr (GLU == kGluSilu) {  // the SiLU pass's own expression
+    const float sg = g * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(g * -1.4426950408889634f));
+    return sg * v;
+  } else {  // (u + 1) * g * sigmoid(alpha g) on g clamped from above, u from both sides
+    const float gc = fminf(g, limit);
+    const float uc = fminf(fmaxf(v, -limit), limit);
+    const float sg = gc * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(gc * c));
+    return sg * (uc + 1.0f);
+  }
+}
 
 // quant_weight arithmetic (quantize.cuh:218-279): scale = fp16(amax / qmax), 0 -> 1;
 // q = rint_even(clamp(fp16(x / scale), -qmax, qmax))
@@ -404,15 +421,7 @@ __global__ __launch_bounds__(kThreads) void act_quant_kernel(typename ActArgsOf<
           g = g + (float)bg[c][j];
           v = v + (float)bu[c][j];
         }
-        if constexpr (GLU == kGluSilu) {  // the SiLU pass's own expression
-          const float sg = g * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(g * -1.4426950408889634f));
-          x[c][j] = (_Float16)(sg * v);
-        } else {  // (u + 1) * g * sigmoid(alpha g) on g clamped from above, u from both sides
-          const float gc = fminf(g, a.limit);
-          const float uc = fminf(fmaxf(v, -a.limit), a.limit);
-          const float sg = gc * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(gc * a.c));
-          x[c][j] = (_Float16)(sg * (uc + 1.0f));
-        }
+        x[c][j] = (_Float16)glu_value<GLU>(g, v, a.limit, a.c);
       }
     }
   } else if constexpr (SILU) {
@@ -928,6 +937,91 @@ static int gate_ex_impl(const char* fn, const void* hidden, const void* w_gate, 
   return launched(E > 256 ? "gate_wide_kernel" : "gate_modes_kernel");
 }
 
+// the checks of an mxmoe_moe_glu (mxmoe_moe_glu_quant and the decode forward's _ex gate_up), under the entry's name
+static int glu_check(const char* fn, const mxmoe_moe_glu* glu) {
+  if (!glu || (glu->act != MXMOE_GLU_SILU && glu->act != MXMOE_GLU_SWIGLU_CLAMP))
+    return fail(MXMOE_GG_ERR_INVALID, "%s: glu->act must be MXMOE_GLU_SILU or MXMOE_GLU_SWIGLU_CLAMP (got %d)", fn,
+                glu ? glu->act : -1);
+  if (glu->act == MXMOE_GLU_SWIGLU_CLAMP && (!std::isfinite(glu->alpha) || !std::isfinite(glu->limit) || !(glu->limit > 0.0f)))
+    return fail(MXMOE_GG_ERR_INVALID, "%s: SWIGLU_CLAMP needs a finite alpha and a finite limit > 0 (alpha=%g limit=%g)", fn,
+                (double)glu->alpha, (double)glu->limit);
+  if (!aligned16(glu->bias_routed) || !aligned16(glu->bias_shared))
+    return fail(MXMOE_GG_ERR_INVALID, "%s: misaligned bias pointer (16 B)", fn);
+  return MXMOE_GG_OK;
+}
+
+// The two decode entries and their _ex forms: one body of checks and one launcher each. ex: the _ex entry (kind bit 3,
+// the _ex kernels; glu may be NULL: SiLU and no bias); otherwise glu is NULL and the first entries' kernels run.
+static int decode_gate_up_impl(const char* fn, bool ex, const mxmoe_moe_glu* glu, int dtype, const void* hidden, int64_t T,
+                               int topk, int E, int with_shared, const int32_t* topk_ids,
+                               const mxmoe_moe_decode_expert* experts, uint32_t kind_mask, int H, int N, int N_shared,
+                               int layout, void* act, void* act_shared, int32_t* status, void* stream) {
+  if (int st = dtype_check(fn, "dtype", dtype)) return st;
+  if (int st = decode::kind_mask_check(fn, kind_mask, ex)) return st;
+  if (int st = decode::sizes_check(fn, T, topk, E, with_shared, H, N, N_shared)) return st;
+  if (layout != MXMOE_DECODE_GU_PLAIN && layout != MXMOE_DECODE_GU_INTERLEAVED)
+    return fail(MXMOE_GG_ERR_INVALID, "%s: layout must be MXMOE_DECODE_GU_PLAIN or MXMOE_DECODE_GU_INTERLEAVED (got %d)", fn,
+                layout);
+  if (glu) {
+    if (int st = glu_check(fn, glu)) return st;
+    if (glu->bias_shared && !with_shared)
+      return fail(MXMOE_GG_ERR_INVALID, "%s: glu->bias_shared given without a shared expert", fn);
+  }
+  if (!aligned16(hidden) || !aligned16(act) || !aligned16(act_shared) || ((uintptr_t)topk_ids & 3) ||
+      ((uintptr_t)experts & 7) || ((uintptr_t)status & 3))
+    return fail(MXMOE_GG_ERR_INVALID, "%s: misaligned pointer (hidden / act / act_shared need 16 B)", fn);
+  if (T == 0) return MXMOE_GG_OK;
+  if (!hidden || !topk_ids || !experts || !act || (with_shared && !act_shared))
+    return fail(MXMOE_GG_ERR_INVALID, "%s: NULL pointer", fn);
+  decode::ArgsEx a{};
+  a.src = a.src_shared = hidden;
+  a.ids = topk_ids;
+  a.experts = experts;
+  a.out = static_cast<_Float16*>(act);
+  a.out_shared = static_cast<_Float16*>(act_shared);
+  a.status = status;
+  a.T = (int)T, a.topk = topk, a.E = E, a.with_shared = with_shared != 0;
+  a.K = a.K_shared = H;
+  a.C = N, a.C_shared = with_shared ? N_shared : 0;
+  a.layout = layout, a.src_bf16 = dtype == MXMOE_DT_BF16, a.kind_mask = kind_mask;
+  if (!ex) return decode::launch<false>(static_cast<const decode::Args&>(a), stream);
+  a.glu = glu && glu->act == MXMOE_GLU_SWIGLU_CLAMP ? kGluSwigluClamp : kGluSilu;
+  if (glu) {
+    a.bias_routed = static_cast<const _Float16*>(glu->bias_routed);
+    a.bias_shared = static_cast<const _Float16*>(glu->bias_shared);
+    a.c = -(glu->alpha * 1.4426950408889634f);
+    a.limit = glu->limit;
+  }
+  return decode::launch<false>(a, stream);
+}
+
+static int decode_down_impl(const char* fn, bool ex, int64_t T, int topk, int E, int with_shared, const int32_t* topk_ids,
+                            const mxmoe_moe_decode_expert* experts, uint32_t kind_mask, int H, int N, int N_shared,
+                            const void* act, const void* act_shared, void* y, void* ys, int32_t* status, void* stream) {
+  if (int st = decode::kind_mask_check(fn, kind_mask, ex)) return st;
+  if (int st = decode::sizes_check(fn, T, topk, E, with_shared, H, N, N_shared)) return st;
+  if (!aligned16(act) || !aligned16(act_shared) || !aligned16(y) || !aligned16(ys) || ((uintptr_t)topk_ids & 3) ||
+      ((uintptr_t)experts & 7) || ((uintptr_t)status & 3))
+    return fail(MXMOE_GG_ERR_INVALID, "%s: misaligned pointer (act / act_shared / y / ys need 16 B)", fn);
+  if (T == 0) return MXMOE_GG_OK;
+  if (!act || !topk_ids || !experts || !y || (with_shared && (!act_shared || !ys)))
+    return fail(MXMOE_GG_ERR_INVALID, "%s: NULL pointer", fn);
+  decode::ArgsEx a{};
+  a.src = act;
+  a.src_shared = act_shared;
+  a.ids = topk_ids;
+  a.experts = experts;
+  a.out = static_cast<_Float16*>(y);
+  a.out_shared = static_cast<_Float16*>(ys);
+  a.status = status;
+  a.T = (int)T, a.topk = topk, a.E = E, a.with_shared = with_shared != 0;
+  a.K = N, a.K_shared = with_shared ? N_shared : N;
+  a.C = a.C_shared = H;
+  a.kind_mask = kind_mask;
+  if (!ex) return decode::launch<true>(static_cast<const decode::Args&>(a), stream);
+  return decode::launch<true>(a, stream);
+}
+
 extern "C" {
 
 int mxmoe_moe_gate(const void* hidden, const void* w_gate, const void* w_shared_gate, int64_t T, int H, int E, int topk,
@@ -1070,14 +1164,7 @@ int mxmoe_moe_glu_quant(const mxmoe_moe_glu* glu, const void* routed_in, const v
                         int N_shared, const int32_t* sorted_expert, const mxmoe_moe_seg* segs, int nseg, uint32_t tag_mask,
                         void* out, void* scales, void* stream) {
   const char* fn = "mxmoe_moe_glu_quant";
-  if (!glu || (glu->act != MXMOE_GLU_SILU && glu->act != MXMOE_GLU_SWIGLU_CLAMP))
-    return fail(MXMOE_GG_ERR_INVALID, "%s: glu->act must be MXMOE_GLU_SILU or MXMOE_GLU_SWIGLU_CLAMP (got %d)", fn,
-                glu ? glu->act : -1);
-  if (glu->act == MXMOE_GLU_SWIGLU_CLAMP && (!std::isfinite(glu->alpha) || !std::isfinite(glu->limit) || !(glu->limit > 0.0f)))
-    return fail(MXMOE_GG_ERR_INVALID, "%s: SWIGLU_CLAMP needs a finite alpha and a finite limit > 0 (alpha=%g limit=%g)", fn,
-                (double)glu->alpha, (double)glu->limit);
-  if (!aligned16(glu->bias_routed) || !aligned16(glu->bias_shared))
-    return fail(MXMOE_GG_ERR_INVALID, "%s: misaligned bias pointer (16 B)", fn);
+  if (int st = glu_check(fn, glu)) return st;
   bool mx = false;
   if (int st = tag_mask_mx(fn, tag_mask, &mx)) return st;
   if (int st = slots_check(fn, routed_in, shared_in, T, topk, N, N_shared, sorted_expert, segs, nseg, out)) return st;
@@ -1118,58 +1205,30 @@ int mxmoe_moe_combine(const void* y, const int32_t* inv_slot, const float* weigh
 int mxmoe_moe_decode_gate_up(int dtype, const void* hidden, int64_t T, int topk, int E, int with_shared,
                              const int32_t* topk_ids, const mxmoe_moe_decode_expert* experts, uint32_t kind_mask, int H,
                              int N, int N_shared, int layout, void* act, void* act_shared, int32_t* status, void* stream) {
-  const char* fn = "mxmoe_moe_decode_gate_up";
-  if (int st = dtype_check(fn, "dtype", dtype)) return st;
-  if (int st = decode::kind_mask_check(fn, kind_mask)) return st;
-  if (int st = decode::sizes_check(fn, T, topk, E, with_shared, H, N, N_shared)) return st;
-  if (layout != MXMOE_DECODE_GU_PLAIN && layout != MXMOE_DECODE_GU_INTERLEAVED)
-    return fail(MXMOE_GG_ERR_INVALID, "%s: layout must be MXMOE_DECODE_GU_PLAIN or MXMOE_DECODE_GU_INTERLEAVED (got %d)", fn,
-                layout);
-  if (!aligned16(hidden) || !aligned16(act) || !aligned16(act_shared) || ((uintptr_t)topk_ids & 3) ||
-      ((uintptr_t)experts & 7) || ((uintptr_t)status & 3))
-    return fail(MXMOE_GG_ERR_INVALID, "%s: misaligned pointer (hidden / act / act_shared need 16 B)", fn);
-  if (T == 0) return MXMOE_GG_OK;
-  if (!hidden || !topk_ids || !experts || !act || (with_shared && !act_shared))
-    return fail(MXMOE_GG_ERR_INVALID, "%s: NULL pointer", fn);
-  decode::Args a{};
-  a.src = a.src_shared = hidden;
-  a.ids = topk_ids;
-  a.experts = experts;
-  a.out = static_cast<_Float16*>(act);
-  a.out_shared = static_cast<_Float16*>(act_shared);
-  a.status = status;
-  a.T = (int)T, a.topk = topk, a.E = E, a.with_shared = with_shared != 0;
-  a.K = a.K_shared = H;
-  a.C = N, a.C_shared = with_shared ? N_shared : 0;
-  a.layout = layout, a.src_bf16 = dtype == MXMOE_DT_BF16, a.kind_mask = kind_mask;
-  return decode::launch<false>(a, stream);
+  return decode_gate_up_impl("mxmoe_moe_decode_gate_up", false, nullptr, dtype, hidden, T, topk, E, with_shared, topk_ids,
+                             experts, kind_mask, H, N, N_shared, layout, act, act_shared, status, stream);
 }
 
 int mxmoe_moe_decode_down(int64_t T, int topk, int E, int with_shared, const int32_t* topk_ids,
                           const mxmoe_moe_decode_expert* experts, uint32_t kind_mask, int H, int N, int N_shared,
                           const void* act, const void* act_shared, void* y, void* ys, int32_t* status, void* stream) {
-  const char* fn = "mxmoe_moe_decode_down";
-  if (int st = decode::kind_mask_check(fn, kind_mask)) return st;
-  if (int st = decode::sizes_check(fn, T, topk, E, with_shared, H, N, N_shared)) return st;
-  if (!aligned16(act) || !aligned16(act_shared) || !aligned16(y) || !aligned16(ys) || ((uintptr_t)topk_ids & 3) ||
-      ((uintptr_t)experts & 7) || ((uintptr_t)status & 3))
-    return fail(MXMOE_GG_ERR_INVALID, "%s: misaligned pointer (act / act_shared / y / ys need 16 B)", fn);
-  if (T == 0) return MXMOE_GG_OK;
-  if (!act || !topk_ids || !experts || !y || (with_shared && (!act_shared || !ys)))
-    return fail(MXMOE_GG_ERR_INVALID, "%s: NULL pointer", fn);
-  decode::Args a{};
-  a.src = act;
-  a.src_shared = act_shared;
-  a.ids = topk_ids;
-  a.experts = experts;
-  a.out = static_cast<_Float16*>(y);
-  a.out_shared = static_cast<_Float16*>(ys);
-  a.status = status;
-  a.T = (int)T, a.topk = topk, a.E = E, a.with_shared = with_shared != 0;
-  a.K = N, a.K_shared = with_shared ? N_shared : N;
-  a.C = a.C_shared = H;
-  a.kind_mask = kind_mask;
-  return decode::launch<true>(a, stream);
+  return decode_down_impl("mxmoe_moe_decode_down", false, T, topk, E, with_shared, topk_ids, experts, kind_mask, H, N,
+                          N_shared, act, act_shared, y, ys, status, stream);
+}
+
+int mxmoe_moe_decode_gate_up_ex(const mxmoe_moe_glu* glu, int dtype, const void* hidden, int64_t T, int topk, int E,
+                                int with_shared, const int32_t* topk_ids, const mxmoe_moe_decode_expert* experts,
+                                uint32_t kind_mask, int H, int N, int N_shared, int layout, void* act, void* act_shared,
+                                int32_t* status, void* stream) {
+  return decode_gate_up_impl("mxmoe_moe_decode_gate_up_ex", true, glu, dtype, hidden, T, topk, E, with_shared, topk_ids,
+                             experts, kind_mask, H, N, N_shared, layout, act, act_shared, status, stream);
+}
+
+int mxmoe_moe_decode_down_ex(int64_t T, int topk, int E, int with_shared, const int32_t* topk_ids,
+                             const mxmoe_moe_decode_expert* experts, uint32_t kind_mask, int H, int N, int N_shared,
+                             const void* act, const void* act_shared, void* y, void* ys, int32_t* status, void* stream) {
+  return decode_down_impl("mxmoe_moe_decode_down_ex", true, T, topk, E, with_shared, topk_ids, experts, kind_mask, H, N,
+                          N_shared, act, act_shared, y, ys, status, stream);
 }
 
 }  // extern "C"

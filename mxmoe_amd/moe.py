@@ -1322,28 +1322,25 @@ class GraphForward:
         return self.g1.status(reset) | self.g2.status(reset) | (seg << self.SEG_STATUS_SHIFT)
 
 
-class DecodeForward:
-    """A MoE layer (``MoEFFN``, or a ``MoEBlock`` with its router) for calls of 1 to ``DECODE_MAX_T`` (16) tokens, with
-    no planner: gate (block only) -> decode_gate_up -> decode_down -> combine, three launches (four with the router),
-    nothing copied to the host, so ``launch`` can be captured with ``torch.cuda.graph`` like ``GraphForward``'s
-    (DESIGN.md §4 "Decode forward"). There is no sort, no segment table and no tile table: the two kernels
-    (mxmoe_moe_decode_gate_up / mxmoe_moe_decode_down, include/mxmoe_moe.h) stream the weights of the experts the ids
-    name and write ``act`` and ``y`` in pair order (row t * topk + k), which the existing combine reads through an
-    identity slot table. The arithmetic is ``MoEFFN.forward``'s: for w8a8 / w4a4 experts ``out`` equals it bit for
-    bit, for fp16 experts within the f32 summation order.
-
-    Experts may be fp16, w8a8_g-1_sym or w4a4_g-1_sym, mixed freely per expert and per linear; the weights are the
-    layer's own tensors (no copy). Anything else — the MX and weight-only types, g128, a layer with a bias or
-    another activation — raises ValueError here. An id outside [0, E) leaves its pair's rows as they were and sets
-    ``DECODE_BAD_ID`` in ``status()``; every access stays inside the buffers."""
+class _DecodeBase:
+    """What ``DecodeForward`` and ``DecodeForwardEx`` share: the constructor, ``launch`` and ``status``. A subclass names
+    its kinds (``KINDS``: qcfg -> MXMOE_DECODE_*), its two entries (``ENTRIES``), whether the gate_up entry takes an
+    mxmoe_moe_glu (``TAKES_GLU``) and what it refuses about a layer (``_check_layer``)."""
 
     MAX_T = nat.DECODE_MAX_T
-    KINDS = {"fp16": nat.DECODE_FP16, "w8a8_g-1_sym": nat.DECODE_W8A8, "w4a4_g-1_sym": nat.DECODE_W4A4}
+    KINDS: dict = {}
+    ENTRIES: tuple = ()
+    TAKES_GLU = False
+    TAKES_MX = False  # e8m0 scale rows are read by row and byte offset: they are checked like the weights
+
+    def _check_layer(self, ffn: "MoEFFN") -> None:
+        """What the class refuses about a layer beyond the experts' types."""
 
     def __init__(self, layer, T: int, topk: Optional[int] = None, device=None, dtype: Optional[torch.dtype] = None):
         """T: the capacity in tokens (1..16; an uncaptured call may bring fewer rows). dtype: the element type of
         ``hidden`` and ``out`` (fp16 or bf16); default: the block's ``w_gate.dtype`` (which it must equal), fp16 for
         a bare ``MoEFFN``."""
+        name = type(self).__name__
         self.block = layer if isinstance(layer, MoEBlock) else None
         self.ffn = ffn = layer.ffn if self.block is not None else layer
         if dtype is None:
@@ -1357,20 +1354,18 @@ class DecodeForward:
                 raise ValueError(f"topk = {topk} differs from the block's {self.block.topk}")
             topk = self.block.topk
         if topk is None or topk < 1 or topk > min(ffn.E, 16):
-            raise ValueError(f"DecodeForward needs 1 <= topk <= min(E, 16), got {topk}")
+            raise ValueError(f"{name} needs 1 <= topk <= min(E, 16), got {topk}")
         if T < 1 or T > self.MAX_T:
-            raise ValueError(f"DecodeForward takes 1 <= T <= {self.MAX_T} tokens, got T = {T}: larger batches are "
+            raise ValueError(f"{name} takes 1 <= T <= {self.MAX_T} tokens, got T = {T}: larger batches are "
                              "GraphForward's")
-        if ffn.biased_or_gated:
-            raise ValueError("DecodeForward: a layer with a bias or an activation other than 'silu' (gpt-oss) is not "
-                             "supported")
+        self._check_layer(ffn)
         for w in list(ffn.w1) + list(ffn.w2):
             if w.q.qcfg not in self.KINDS:
-                raise ValueError(f"DecodeForward: qcfg {w.q.qcfg} is not supported (experts must be one of "
+                raise ValueError(f"{name}: qcfg {w.q.qcfg} is not supported (experts must be one of "
                                  f"{tuple(self.KINDS)})")
         for what, v in (("H", ffn.H), ("N", ffn.N)) + ((("N_shared", ffn.Ns),) if ffn.has_shared else ()):
             if v <= 0 or v % 128 or v > 16384:
-                raise ValueError(f"DecodeForward: {what} = {v} must be a multiple of 128 and <= 16384")
+                raise ValueError(f"{name}: {what} = {v} must be a multiple of 128 and <= 16384")
         dev = torch.device(device) if device is not None else ffn.w1[0].B.device
         self.T, self.topk, self.device = T, topk, dev
         n, H = T * topk, ffn.H
@@ -1382,12 +1377,21 @@ class DecodeForward:
         for rec, w1, w2, k1, k2 in zip(table, ffn.w1, ffn.w2, kinds1, kinds2):
             for w in (w1, w2):
                 if w.B.device != dev or not w.B.is_contiguous() or w.B.data_ptr() % 16:
-                    raise ValueError("DecodeForward: every weight must be a contiguous, 16-byte aligned tensor on the "
+                    raise ValueError(f"{name}: every weight must be a contiguous, 16-byte aligned tensor on the "
                                      "layer's device")
+                if self.TAKES_MX and w.scale_b is not None and (w.scale_b.device != dev or not w.scale_b.is_contiguous()):
+                    raise ValueError(f"{name}: every scale_b must be a contiguous tensor on the layer's device")
             rec.b1, rec.sb1 = w1.B.data_ptr(), 0 if w1.scale_b is None else w1.scale_b.data_ptr()
             rec.b2, rec.sb2 = w2.B.data_ptr(), 0 if w2.scale_b is None else w2.scale_b.data_ptr()
             rec.kind1, rec.kind2 = k1, k2
         self.experts = torch.frombuffer(bytearray(bytes(table)), dtype=torch.uint8).to(dev)
+        # a layer with a bias or another activation (the _ex entries only): the gate_up entry's mxmoe_moe_glu, and the
+        # combine with the down bias (``MoEFFN.down_bias``) — the eager layer's own choice of calls
+        self._glu = None
+        if self.TAKES_GLU and ffn.biased_or_gated:
+            _check_bias(ffn.b1, (ffn.E, 2 * ffn.N), "gate_up_bias", dev)
+            _check_bias(ffn.b1s, (2 * ffn.Ns,), "gate_up_bias (shared)", dev)
+            self._glu = _glu_struct(ffn.activation, ffn.b1, ffn.b1s)
         f16 = dict(dtype=torch.float16, device=dev)
         self.act = torch.zeros(n, ffn.N, **f16)
         self.act_shared = torch.zeros(T, ffn.Ns, **f16) if ffn.has_shared else None
@@ -1430,14 +1434,20 @@ class DecodeForward:
                     raise ValueError(f"{what} must be a contiguous {dt} {list(shape)} tensor")
         shared = int(ffn.has_shared)
         st = _stream(stream)
-        nat.check(nat.symbol("mxmoe_moe_decode_gate_up")(
-            _DT[self.dtype], _ptr(hidden), T, topk, ffn.E, shared, _ptr(topk_ids), _ptr(self.experts), self.mask1, ffn.H,
+        gate_up, down = self.ENTRIES
+        glu = (self._glu,) if self.TAKES_GLU else ()
+        nat.check(nat.symbol(gate_up)(
+            *glu, _DT[self.dtype], _ptr(hidden), T, topk, ffn.E, shared, _ptr(topk_ids), _ptr(self.experts), self.mask1, ffn.H,
             ffn.N, ffn.Ns, self.layout, _ptr(self.act), _ptr(self.act_shared), _ptr(self.dev_status), st))
-        nat.check(nat.symbol("mxmoe_moe_decode_down")(
+        nat.check(nat.symbol(down)(
             T, topk, ffn.E, shared, _ptr(topk_ids), _ptr(self.experts), self.mask2, ffn.H, ffn.N, ffn.Ns, _ptr(self.act),
             _ptr(self.act_shared), _ptr(self.y), _ptr(self.ys), _ptr(self.dev_status), st))
         out = self.out[:T]
-        _launch_combine(out, self.y, self.inv_slot, None, topk_weights, self.ys, shared_w, topk, stream, None)
+        if self._glu is not None:  # in pair order the expert of slot p is ids[p]; an id outside [0, E) adds no bias
+            _launch_combine(out, self.y, self.inv_slot, topk_ids.view(-1), topk_weights, self.ys, shared_w, topk, stream,
+                            ffn.down_bias)
+        else:
+            _launch_combine(out, self.y, self.inv_slot, None, topk_weights, self.ys, shared_w, topk, stream, None)
         return out
 
     __call__ = launch
@@ -1449,6 +1459,59 @@ class DecodeForward:
         if reset:
             self.dev_status.zero_()
         return st
+
+
+class DecodeForward(_DecodeBase):
+    """A MoE layer (``MoEFFN``, or a ``MoEBlock`` with its router) for calls of 1 to ``DECODE_MAX_T`` (16) tokens, with
+    no planner: gate (block only) -> decode_gate_up -> decode_down -> combine, three launches (four with the router),
+    nothing copied to the host, so ``launch`` can be captured with ``torch.cuda.graph`` like ``GraphForward``'s
+    (DESIGN.md §4 "Decode forward"). There is no sort, no segment table and no tile table: the two kernels
+    (mxmoe_moe_decode_gate_up / mxmoe_moe_decode_down, include/mxmoe_moe.h) stream the weights of the experts the ids
+    name and write ``act`` and ``y`` in pair order (row t * topk + k), which the existing combine reads through an
+    identity slot table. The arithmetic is ``MoEFFN.forward``'s: for w8a8 / w4a4 experts ``out`` equals it bit for
+    bit, for fp16 experts within the f32 summation order.
+
+    Experts may be fp16, w8a8_g-1_sym or w4a4_g-1_sym, mixed freely per expert and per linear; the weights are the
+    layer's own tensors (no copy). Anything else — the MX and weight-only types, g128, a layer with a bias or
+    another activation — raises ValueError here (``DecodeForwardEx`` takes gpt-oss layers). An id outside [0, E)
+    leaves its pair's rows as they were and sets ``DECODE_BAD_ID`` in ``status()``; every access stays inside the
+    buffers."""
+
+    KINDS = {"fp16": nat.DECODE_FP16, "w8a8_g-1_sym": nat.DECODE_W8A8, "w4a4_g-1_sym": nat.DECODE_W4A4}
+    ENTRIES = ("mxmoe_moe_decode_gate_up", "mxmoe_moe_decode_down")
+
+    def _check_layer(self, ffn: "MoEFFN") -> None:
+        if ffn.biased_or_gated:
+            raise ValueError("DecodeForward: a layer with a bias or an activation other than 'silu' (gpt-oss) is not "
+                             "supported")
+
+
+class DecodeForwardEx(_DecodeBase):
+    """``DecodeForward`` for gpt-oss layers (DESIGN.md §4 "Decode forward: gpt-oss layers"): the same constructor,
+    ``launch`` and ``status`` on the _ex entries (mxmoe_moe_decode_gate_up_ex / mxmoe_moe_decode_down_ex,
+    include/mxmoe_moe.h), which also take
+
+    - ``w4a16_g32_sym_MXFP4`` experts (``gptoss_layer``, ``prepare_weight_mx``: the checkpoint's codes and the e8m0
+      scales in the GroupGEMM's device layout, read in place), mixed freely with fp16, w8a8_g-1_sym and w4a4_g-1_sym
+      per expert and per linear;
+    - a layer that is ``biased_or_gated``: any of the four biases, and "silu" or a ``SwigluClamp``. The gate_up
+      biases and the activation are applied in decode_gate_up's epilogue with the activation pass's arithmetic
+      (mxmoe_moe_glu_quant); the down biases stay in the combine, as in ``MoEFFN.forward``, which reads the expert of
+      pair p from ``topk_ids`` (pair order) and adds no bias for an id outside [0, E).
+
+    So a gpt-oss MoE block decodes as router -> decode_gate_up -> decode_down -> combine, launches only, with fp16 or
+    bf16 ends. ``out`` equals ``MoEFFN.forward``'s bit for bit for w8a8 / w4a4 experts and within the f32 summation
+    order for fp16 and MXFP4 experts. Still refused, naming the qcfg: w4a4_g32_sym_MXFP4, w4a8_g32_sym_MXFP8, g128
+    and the integer weight-only types.
+
+    On the gpt-oss layer shape (E = 32, topk = 4, H = N = 2944) this form takes 0.56x / 0.71x of ``GraphForward``'s
+    device time at T = 1 / 4, 0.94x at T = 6 and 1.14x / 1.48x at T = 8 / 16: the crossover is between 6 and 8
+    tokens, so take ``GraphForward`` from 8."""
+
+    KINDS = dict(DecodeForward.KINDS, **{"w4a16_g32_sym_MXFP4": nat.DECODE_W4A16_MX})
+    ENTRIES = nat.DECODE_EX_SYMBOLS
+    TAKES_GLU = True
+    TAKES_MX = True
 
 
 def qwen2_layer_bench(*args, **kwargs) -> dict:

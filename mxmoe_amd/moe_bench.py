@@ -12,8 +12,8 @@ import torch
 from . import _native as nat
 from .groupgemm import W4A8_MXFP8, W4A16_MXFP4, QParams
 from .harness import time_launches
-from .moe import (_BITS, DecodeForward, GraphForward, MoEBlock, MoEFFN, PlannedForward, SwigluClamp, _ptr, _stream, combine_into, gate,
-                  prepare_weight_mx, silu_mul_quant)
+from .moe import (_BITS, DecodeForward, DecodeForwardEx, GraphForward, MoEBlock, MoEFFN, PlannedForward, SwigluClamp, _launch_combine,
+                  _ptr, _stream, combine_into, gate, gptoss_layer, prepare_weight_mx, silu_mul_quant)
 from .workload import (ds2_mixed_qconfig, ds2_workload, load_workload, mixed_qconfig_lp1, qwen2_layer11_workload,
                        w4a16_w8a8_qconfig)
 
@@ -265,6 +265,69 @@ def decode_forward_bench(batches: Sequence[int] = (1, 4, 16), rounds: int = 4, i
         out["faster"] = bool(out["decode_device"]["max_us"] < out["graph_device"]["min_us"])
         out["bit_identical_to_eager"] = same
         out["status"] = {"graph": gf.status(), "decode": df.status() | dp.status()}
+        return out
+
+    for bs in batches:
+        yield one(bs)
+
+
+def decode_forward_gptoss_bench(batches: Sequence[int] = (1, 4, 16), rounds: int = 4, iters: int = 30, E: int = 32,
+                                topk: int = 4, H: int = 2880, N: int = 2880):
+    """A synthetic gpt-oss layer (``gptoss_layer``: E = 32, top-4, H = N = 2880 padded to 2944, random e2m1 codes, scale
+    bytes in [118, 126], biases in +-0.5, the clamped SwiGLU) at decode sizes, ``DecodeForwardEx`` against
+    ``GraphForward`` of the same layer, as ``decode_forward_bench`` measures the qwen2_moe layer: both replayed from
+    captured graphs in one process, the sides alternating over rounds (yields one dict per batch size). Also the two
+    decode kernels and the bias combine alone, the weight bytes (codes and scale bytes of the experts the ids name) and
+    the TB/s they imply. ``faster``: DecodeForwardEx's device median, max over rounds, below GraphForward's min over
+    rounds. MXFP4 sums depend on their order, so the outputs are compared with the eager layer's within the fp16
+    GroupGEMM tolerance (1e-3 |ref| + 1e-3 rms(ref)), not bit for bit."""
+    dev = "cuda"
+    g = torch.Generator(device=dev).manual_seed(0)
+    u8 = lambda *shape, lo=0, hi=256: torch.randint(lo, hi, shape, generator=g, device=dev, dtype=torch.uint8)
+    bias = lambda *shape: torch.rand(*shape, generator=g, device=dev) - 0.5
+    layer = gptoss_layer(u8(E, 2 * N, H // 32, 16), u8(E, 2 * N, H // 32, lo=118, hi=127), bias(E, 2 * N),
+                         u8(E, H, N // 32, 16), u8(E, H, N // 32, lo=118, hi=127), bias(E, H))
+    Hp, Np = layer.H, layer.N
+    weight_bytes = lambda ws, es: sum(ws[e].B.numel() + ws[e].scale_b.numel() for e in es)
+
+    def one(bs: int) -> dict:
+        ids = torch.stack([torch.randperm(E, generator=g, device=dev)[:topk] for _ in range(bs)]).to(torch.int32)
+        hidden = torch.zeros(bs, Hp, dtype=torch.float16, device=dev)
+        hidden[:, :H] = (torch.randn(bs, H, generator=g, device=dev) * 0.5).half()
+        wts = torch.softmax(torch.rand(bs, topk, generator=g, device=dev), dim=1)
+        want = layer.forward(hidden, ids, wts).float()
+        gf, df = GraphForward(layer, bs, topk), DecodeForwardEx(layer, bs, topk)
+        graphs = {"graph": _captured(lambda: gf.launch(hidden, ids, wts)), "decode": _captured(lambda: df.launch(hidden, ids, wts))}
+        for gr in graphs.values():
+            gr.replay()
+        torch.cuda.synchronize()
+        tol = 1e-3 * want.abs() + 1e-3 * want.square().mean().sqrt() + 1e-6
+        close = {k: bool(((o.out.float() - want).abs() <= tol).all()) for k, o in (("graph", gf), ("decode", df))}
+        wall, device = (lambda fn: _wall(fn, iters)), (lambda fn: _device(fn, iters))
+        st = _stream(None)
+        gate_up_k = lambda: nat.check(nat.symbol("mxmoe_moe_decode_gate_up_ex")(
+            df._glu, nat.DT_FP16, _ptr(hidden), bs, topk, E, 0, _ptr(ids), _ptr(df.experts), df.mask1, Hp, Np, 0, df.layout,
+            _ptr(df.act), None, _ptr(df.dev_status), st))
+        down_k = lambda: nat.check(nat.symbol("mxmoe_moe_decode_down_ex")(
+            bs, topk, E, 0, _ptr(ids), _ptr(df.experts), df.mask2, Hp, Np, 0, _ptr(df.act), None, _ptr(df.y), None,
+            _ptr(df.dev_status), st))
+        combine_k = lambda: _launch_combine(df.out, df.y, df.inv_slot, ids.view(-1), wts, None, None, topk, None, layer.down_bias)
+        sides = {"graph_device": lambda: device(graphs["graph"].replay), "decode_device": lambda: device(graphs["decode"].replay),
+                 "graph_wall": lambda: wall(graphs["graph"].replay), "decode_wall": lambda: wall(graphs["decode"].replay),
+                 "decode_gate_up": lambda: device(gate_up_k), "decode_down": lambda: device(down_k),
+                 "combine_bias": lambda: device(combine_k)}
+        out = {"model": "gpt-oss layer (synthetic)", "bs": bs, "E": E, "topk": topk, "H": Hp, "N": Np,
+               "graph_gate_up_mode": gf.mode}
+        out.update({k: _stat(v) for k, v in _rounds(sides, rounds).items()})
+        used = sorted(set(ids.flatten().tolist()))
+        mb = {"gate_up": weight_bytes(layer.w1, used) / 1e6, "down": weight_bytes(layer.w2, used) / 1e6}
+        out["experts_used"] = len(used)
+        out["weight_mb"] = {k: round(v, 2) for k, v in mb.items()}
+        out["implied_tb_s"] = {k: round(mb[k] / out["decode_" + k]["median_us"], 3) for k in mb}  # MB / µs = TB/s
+        out["decode_over_graph_device"] = round(out["decode_device"]["median_us"] / out["graph_device"]["median_us"], 4)
+        out["faster"] = bool(out["decode_device"]["max_us"] < out["graph_device"]["min_us"])
+        out["close_to_eager"] = close
+        out["status"] = {"graph": gf.status(), "decode": df.status()}
         return out
 
     for bs in batches:

@@ -5,7 +5,12 @@ in one process with the sides alternating over rounds (moe_bench.decode_forward_
 the two decode kernels alone, the plain-layout variant and the combine. One JSON line per T; --out also writes the
 list to a file (profiles/<round>/decode/bench.json). Exits 1 when an output is not bit-identical to the eager layer.
 
-python tools/decode_bench.py [--rounds 4] [--iters 30] [--batches 1,4,16] [--out FILE]
+--model gpt-oss: a synthetic gpt-oss layer instead (moe_bench.decode_forward_gptoss_bench: gptoss_layer of E = 32,
+topk = 4, H = N = 2880, random codes, scale bytes in [118, 126]), DecodeForwardEx against GraphForward of the same layer,
+with the two _ex kernels and the bias combine alone, the weight bytes read and the TB/s they imply. Exits 1 when an
+output is not within the fp16 tolerance of the eager layer (MXFP4 sums depend on their order).
+
+python tools/decode_bench.py [--model qwen2_moe|gpt-oss] [--rounds 4] [--iters 30] [--batches 1,4,16] [--out FILE]
 """
 from __future__ import annotations
 
@@ -25,16 +30,19 @@ def main():
     ap.add_argument("--iters", type=int, default=30)
     ap.add_argument("--batches", default="1,4,16")
     ap.add_argument("--out", default="")
+    ap.add_argument("--model", default="qwen2_moe", choices=["qwen2_moe", "gpt-oss"])
     args = ap.parse_args()
     results = []
-    for r in moe_bench.decode_forward_bench([int(b) for b in args.batches.split(",") if b], args.rounds, args.iters):
+    bench = moe_bench.decode_forward_gptoss_bench if args.model == "gpt-oss" else moe_bench.decode_forward_bench
+    for r in bench([int(b) for b in args.batches.split(",") if b], args.rounds, args.iters):
         print(json.dumps(r), flush=True)
         results.append(r)
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         with open(args.out, "w") as f:
             json.dump(results, f, indent=1)
-    if not all(all(r["bit_identical_to_eager"].values()) and not any(r["status"].values()) for r in results):
+    same = "close_to_eager" if args.model == "gpt-oss" else "bit_identical_to_eager"
+    if not all(all(r[same].values()) and not any(r["status"].values()) for r in results):
         sys.exit(1)
 
 
