@@ -16,37 +16,57 @@ LAB_LIB = PKG / "lib" / "libmxmoe_gg_lab.so"
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = os.environ.get("MXMOE_OFFLOAD_ARCH", "gfx950")
 
-SOURCES = [CSRC / "gg_api.hip", CSRC / "moe_ops.hip"]
-DEPS = SOURCES + [CSRC / "gg_device.h", CSRC / "gg_dyn.h", CSRC / "gg_v2q.h", CSRC / "moe_gate.h", CSRC / "moe_gate_body.inc", CSRC / "moe_gate_wide.h", CSRC / "moe_decode.h", CSRC / "moe_decode_body.inc", ROOT / "include" / "mxmoe_gg.h", ROOT / "include" / "mxmoe_moe.h"]
+# gg_api.hip stays first (tests/test_codegen.py compiles SOURCES[0] for the device ISA); gg_plan.cpp is the
+# host-only tile planner, compiled by the same hipcc and flags as the rest
+SOURCES = [CSRC / "gg_api.hip", CSRC / "moe_ops.hip", CSRC / "gg_plan.cpp"]
 
 FLAGS = ["-O3", "-std=c++17", "-fPIC", "-shared", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-function",
          "-I", str(ROOT / "include")]
 
 
-# the lab build also compiles the lab-only kernels' headers
-LAB_DEPS = DEPS + [CSRC / "gg_f6.h"]
+def _deps() -> list[Path]:
+    """What every object, and so every library, is built from: all of csrc/ and the public headers."""
+    return sorted(p for p in CSRC.iterdir() if p.is_file()) + sorted((ROOT / "include").glob("*.h"))
+
+
+def _newer(deps: list[Path], target: Path) -> bool:
+    return not target.exists() or any(p.stat().st_mtime > target.stat().st_mtime for p in deps)
 
 
 def needs_build(lib: Path = LIB) -> bool:
     """True when `lib` is missing or older than any source it is built from (the lab library's
     tests skip on a stale lab build: a binary HEAD does not produce must not pass for HEAD's)."""
-    if not lib.exists():
-        return True
-    t = lib.stat().st_mtime
-    return any(p.stat().st_mtime > t for p in (LAB_DEPS if lib == LAB_LIB else DEPS))
+    return _newer(_deps(), lib)
 
 
 def build(force: bool = False, verbose: bool = False, extra: list[str] | None = None, lab: bool = False,
           lab_fast: bool = False) -> Path:
-    """lab_fast: the lab library with only the experiments under test (-DMXMOE_LAB_FAST; gg_api.hip)."""
+    """Compile each source to an object of its own (lib/obj/<product|lab|lab_fast>/, all at once, one hipcc
+    per source; an object is kept while it is newer than its source and every header), then link.
+    lab_fast: the lab library with only the experiments under test (-DMXMOE_LAB_FAST; gg_api.hip)."""
     lab = lab or lab_fast
     out = LAB_LIB if lab else LIB
     if not force and not needs_build(out):
         return out
-    out.parent.mkdir(parents=True, exist_ok=True)
-    tmp = out.with_suffix(".so.tmp")
+    objdir = out.parent / "obj" / ("lab_fast" if lab_fast else "lab" if lab else "product")
+    objdir.mkdir(parents=True, exist_ok=True)
+    objs = [objdir / (src.stem + ".o") for src in SOURCES]
     defs = (["-DMXMOE_LAB"] if lab else []) + (["-DMXMOE_LAB_FAST"] if lab_fast else [])
-    cmd = [HIPCC, *FLAGS, *defs, *(extra or []), "-o", str(tmp), *map(str, SOURCES)]
+    compile_flags = [f for f in FLAGS if f != "-shared"] + defs + list(extra or [])
+    headers = [p for p in _deps() if p not in SOURCES]
+    running = []
+    for src, obj in zip(SOURCES, objs):
+        if not force and not _newer([src, *headers], obj):
+            continue
+        cmd = [HIPCC, *compile_flags, "-c", "-o", str(obj), str(src)]
+        if verbose:
+            print(" ".join(cmd), file=sys.stderr)
+        running.append((cmd, subprocess.Popen(cmd)))
+    failed = [cmd for cmd, proc in running if proc.wait() != 0]  # (every compile is waited for before any error)
+    if failed:
+        raise subprocess.CalledProcessError(1, failed[0])
+    tmp = out.with_suffix(".so.tmp")
+    cmd = [HIPCC, *FLAGS, *defs, *(extra or []), "-o", str(tmp), *map(str, objs)]
     if verbose:
         print(" ".join(cmd), file=sys.stderr)
     subprocess.run(cmd, check=True)

@@ -60,7 +60,7 @@ struct DynGeom {
 };
 static_assert(sizeof(DynGeom) == 128, "DynGeom must stay 128 bytes");
 
-// THE TILE RULE (the host planner's m_tiles, gg_api.hip): with `rem` rows left at m0, the tile is the
+// THE TILE RULE (the host planner's m_tiles, gg_plan.cpp): with `rem` rows left at m0, the tile is the
 // 64-row class if the type takes it and rem fits, else the 128-row tail class if rem fits, else a main
 // tile. Returns the class; every tile but a problem's last is a main tile, and m-tile i starts at i * bm.
 MXMOE_HD inline int dyn_tile_class(const DynGeom& g, int rem) {
@@ -194,6 +194,11 @@ MXMOE_HD inline void dyn_tile_at(const DynGeom* g, const int32_t* order, int P, 
   td[4] = 0, td[5] = q.nst, td[6] = -1, td[7] = -1;
 }
 
+// workgroups of the planner kernel: at most kDynMaxBlocks, each taking kDynSlotsPerBlock tile slots (the host
+// sizes the per-workgroup scratch of the workspace by the former: gg_plan.cpp's dyn_layout)
+constexpr int kDynMaxBlocks = 16;
+constexpr int kDynSlotsPerBlock = 2048;
+
 }  // namespace mxmoe
 
 #if defined(__HIPCC__)
@@ -223,8 +228,6 @@ struct DynArgs {
   const int64_t* rows_total;  // the joint bound (static plan data in the workspace)
   int32_t P, tile_slots;
 };
-constexpr int kDynMaxBlocks = 16;
-constexpr int kDynSlotsPerBlock = 2048;
 namespace detail {
 // launches dyn_plan_kernel (moe_ops.hip) on min(kDynMaxBlocks, cdiv(tile_slots, kDynSlotsPerBlock)) workgroups
 void launch_dyn_plan(const DynArgs& a, hipStream_t stream);

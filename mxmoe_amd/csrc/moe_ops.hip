@@ -30,13 +30,13 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
-#include <cstdarg>
 #include <cstdio>
 #include <string>
 #include <type_traits>
 
 #include "../../include/mxmoe_gg.h"
 #include "../../include/mxmoe_moe.h"
+#include "gg_error.h"  // fail(): the library's error channel (mxmoe_gg_last_error)
 #include "moe_gate.h"
 #include "moe_gate_wide.h"
 #define MXMOE_DYN_KERNEL  // gg_dyn.h: the GroupGEMM's device tile planner kernel is compiled here
@@ -44,8 +44,6 @@
 
 namespace mxmoe {
 namespace detail {
-int set_error(int code, const std::string& msg);  // gg_api.hip (thread-local mxmoe_gg_last_error)
-
 void launch_dyn_plan(const DynArgs& a, hipStream_t stream) {
   const int want = (a.tile_slots + kDynSlotsPerBlock - 1) / kDynSlotsPerBlock;
   const int blocks = want < 1 ? 1 : want > kDynMaxBlocks ? kDynMaxBlocks : want;
@@ -55,14 +53,6 @@ void launch_dyn_plan(const DynArgs& a, hipStream_t stream) {
 
 namespace {
 
-int fail(int code, const char* fmt, ...) {
-  char buf[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof(buf), fmt, ap);
-  va_end(ap);
-  return detail::set_error(code, buf);
-}
 // after a launch: the runtime's verdict on it, under the kernel's name
 int launched(const char* kernel) {
   const hipError_t e = hipGetLastError();

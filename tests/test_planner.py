@@ -1,9 +1,11 @@
-"""CPU tests of the host tile planner (gg_api.hip:plan_host) through mxmoe_gg_plan_tiles: every
+"""CPU tests of the host tile planner (gg_plan.cpp:plan_host) through mxmoe_gg_plan_tiles: every
 output tile of every problem is planned exactly once (split-K slices partition its K stages), and
 the placement rules hold — the shared expert of a bs=8192 layer is cut into one rectangle per XCD at
 the end (or, switched, the head) of that XCD's queue, and routed experts are not split across XCDs by chunk boundaries.
 (The reference's TileScheduler, tile_scheduler.cuh:5-50, walks problems in order on the device; the
 placement is ours and affects speed and HBM traffic only, never results.)
+The planner is a host-only unit: tests/cpp/plan_host_check.cpp runs it without the library, under the host
+compiler's sanitizers (test_host_planner_under_host_sanitizers).
 """
 from __future__ import annotations
 
@@ -119,7 +121,7 @@ def _queue_parts(shapes):
 @pytest.mark.parametrize("cfg", ["fp16", "w8a8", "mixed"])
 @pytest.mark.parametrize("gg", ["gate_up", "down"])
 def test_xcd_packing_shared_pieces(cfg, gg):
-    """XCD packing (gg_api.hip plan_host): the shared expert's tiles are cut into
+    """XCD packing (gg_plan.cpp plan_host): the shared expert's tiles are cut into
     8 consecutive pieces of its rectangle order, one per XCD queue — at the queue HEAD when its tiles
     are the long ones (down: 4x the routed K) or the call is 16-bit (fp16: low arithmetic intensity),
     at the TAIL otherwise — each piece a compact block of the tile grid (panel reuse in one L2), and the
@@ -262,3 +264,32 @@ def test_lab_planner_knobs_plan_the_small_batch_kernel():
         r = subprocess.run([sys.executable, "-c", code], cwd=str(build.ROOT),
                            env=env, capture_output=True, text=True, timeout=300)
         assert r.returncode == 0 and "ok" in r.stdout, (knob, r.returncode, r.stderr[-800:])
+
+
+def test_host_planner_under_host_sanitizers(tmp_path):
+    """tests/cpp/plan_host_check.cpp: the host planner (gg_plan.cpp) with the product's three variants, built
+    with the host compiler alone and -fsanitize=address,undefined, run as a program of its own: the coverage
+    check_coverage asserts, on the Plan itself, over the tile classes, split-K, XCD regions, the packed MoE call
+    shape and every validation error."""
+    import shutil
+    import subprocess
+
+    from mxmoe_amd import build
+
+    cxx = shutil.which("g++") or shutil.which("c++")
+    if cxx is None:
+        pytest.skip("no host C++ compiler")
+    flags = ["-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"]
+    probe = tmp_path / "probe.cpp"
+    probe.write_text("int main() { return 0; }\n")
+    if subprocess.run([cxx, *flags, "-o", str(tmp_path / "probe"), str(probe)], capture_output=True).returncode != 0 or \
+            subprocess.run([str(tmp_path / "probe")], capture_output=True).returncode != 0:
+        pytest.skip("the host compiler has no address / undefined-behaviour sanitizer runtime")
+    exe = tmp_path / "plan_host_check"
+    r = subprocess.run([cxx, *flags, "-Wall", "-Wextra", "-Werror", "-o", str(exe),
+                        str(build.ROOT / "tests" / "cpp" / "plan_host_check.cpp"), str(build.CSRC / "gg_plan.cpp")],
+                       capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr
+    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert r.stdout.startswith("plan_host_check ok")

@@ -19,7 +19,7 @@ sys.path.insert(0, ROOT)
 
 
 def stage_time(s, cls: int, geom=(256, 256, 128), tail=(128, 64)) -> float:
-    """gg_api.hip stage_time for the fp16 / int8 / int4 bodies of the v2 kernels."""
+    """gg_plan.cpp stage_time for the fp16 / int8 / int4 bodies of the v2 kernels."""
     rows = geom[0] if cls == 0 else tail[cls - 1]
     cols, bkb = geom[1], geom[2]
     fp = s.a_bits == 16
