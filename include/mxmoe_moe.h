@@ -402,7 +402,11 @@ int mxmoe_moe_combine(const void* y, const int32_t* inv_slot, const float* weigh
  * no synchronisation: graph-capturable. */
 enum { MXMOE_DECODE_MAX_T = 16 };
 enum { MXMOE_DECODE_FP16 = 0, MXMOE_DECODE_W8A8 = 1, MXMOE_DECODE_W4A4 = 2,
-       MXMOE_DECODE_W4A16_MX = 3 /* the _ex entries only */ };                 /* per linear */
+       MXMOE_DECODE_W4A16_MX = 3 /* the _ex and _wo entries only */,
+       /* the _wo entries only: kind = 4 + (w_bits == 8) + 2 * (gsize == 128) + 4 * asym */
+       MXMOE_DECODE_W4A16 = 4, MXMOE_DECODE_W8A16 = 5, MXMOE_DECODE_W4A16_G128 = 6, MXMOE_DECODE_W8A16_G128 = 7,
+       MXMOE_DECODE_W4A16_ASYM = 8, MXMOE_DECODE_W8A16_ASYM = 9, MXMOE_DECODE_W4A16_G128_ASYM = 10,
+       MXMOE_DECODE_W8A16_G128_ASYM = 11 };                                    /* per linear */
 enum { MXMOE_DECODE_GU_PLAIN = 0, MXMOE_DECODE_GU_INTERLEAVED = 1 };
 enum { MXMOE_DECODE_BAD_ID = 1, MXMOE_DECODE_BAD_KIND = 2 };                   /* bits of *status */
 typedef struct mxmoe_moe_decode_expert {
@@ -453,6 +457,39 @@ int mxmoe_moe_decode_gate_up_ex(const mxmoe_moe_glu* glu, int dtype, const void*
                                 uint32_t kind_mask, int H, int N, int N_shared, int layout, void* act, void* act_shared,
                                 int32_t* status, void* stream);
 int mxmoe_moe_decode_down_ex(int64_t T, int topk, int E, int with_shared, const int32_t* topk_ids,
+                             const mxmoe_moe_decode_expert* experts, uint32_t kind_mask, int H, int N, int N_shared,
+                             const void* act, const void* act_shared, void* y, void* ys, int32_t* status, void* stream);
+
+/* The decode forward with integer weight-only experts (added to ABI 7 without a version bump): the two _ex entries
+ * with eight more kinds, w4a16 and w8a16, per-channel or g128, sym or asym — the reference's small-batch scheme
+ * w4a16 + w8a8 among them. Arguments (glu included), pair order, safety, limits and refusals are those of
+ * mxmoe_moe_decode_gate_up_ex / mxmoe_moe_decode_down_ex; the expert record is unchanged (40 bytes). The four entries
+ * above keep their kernels and their mask checks; these run kernels of their own and take kinds 0 to 11.
+ *   kinds    the record has no room for a group size or a symmetry flag, so the kind carries them:
+ *            kind = 4 + (w_bits == 8) + 2 * (gsize == 128) + 4 * asym, MXMOE_DECODE_W4A16 .. _W8A16_G128_ASYM (4..11).
+ *   b1 / b2  mxmoe_gg_repack_weightonly's layout (include/mxmoe_gg.h), uint8 [rows][K bits / 8], used in place: per
+ *            64-K segment, K value 32 kc + 8 g + e at element position 16 g + 8 kc + e; 4-bit: one 32-bit word per
+ *            (g, kc), codes 2q, 2q + 1 at bits 4q and 16 + 4q. Sym codes are stored with the offset 2^(bits-1) - 1.
+ *   sb1 / sb2 the fp16 scale buffer in the reference's permute_scale layout, used in place: sym [G][rows], asym
+ *            [G][rows][2] (scale, zp); G = 1 per-channel, K / 128 for g128; rows the weight's own row count (2N, or
+ *            2 N_shared, for gate_up; H for down). 2-byte aligned. With MXMOE_DECODE_GU_INTERLEAVED the scales follow
+ *            their rows.
+ *   A row    x (gate_up: hidden[t], bf16 converted as mxmoe_moe_gather_quant does; down: act[p]) as fp16: not quantised.
+ *   b[r][k]  = fp16(fma(u - off, scale, zp)), one fp16 rounding (v_pk_fma_f16), scale / zp those of row r and of group
+ *            k / 128 (g128); off = 2^(bits-1) - 1 for sym codes, 0 for asym; zp = +0 for sym; u - off exact (0x6400 | u
+ *            as fp16, then an exact v_pk_add_f16): the GroupGEMM's weight-only value (DESIGN.md §4 "Weight-only WxA16").
+ *   v(r)     = fp16_rn(sum_k f32(x[k]) * f32(b[r][k])), accumulated in f32 (v_fma_mix_f32; the order of the sum is the
+ *            kernel's), as the FP16 and W4A16_MX kinds.
+ *   The gate_up epilogue (SiLU, or glu's biases and clamp) and everything behind it are the _ex entries'. On kinds 0..3
+ *   the outputs are those entries' byte for byte.
+ * Refusals, before any HIP call and under these entries' names: everything the _ex entries check; a kind bit >= 12:
+ * MXMOE_GG_ERR_UNSUPPORTED. A record whose kind is outside the mask: MXMOE_DECODE_BAD_KIND and nothing written. Scale
+ * and zp values that are not finite: unspecified. One launch each, no allocation, no synchronisation: graph-capturable. */
+int mxmoe_moe_decode_gate_up_wo(const mxmoe_moe_glu* glu, int dtype, const void* hidden, int64_t T, int topk, int E,
+                                int with_shared, const int32_t* topk_ids, const mxmoe_moe_decode_expert* experts,
+                                uint32_t kind_mask, int H, int N, int N_shared, int layout, void* act, void* act_shared,
+                                int32_t* status, void* stream);
+int mxmoe_moe_decode_down_wo(int64_t T, int topk, int E, int with_shared, const int32_t* topk_ids,
                              const mxmoe_moe_decode_expert* experts, uint32_t kind_mask, int H, int N, int N_shared,
                              const void* act, const void* act_shared, void* y, void* ys, int32_t* status, void* stream);
 

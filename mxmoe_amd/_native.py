@@ -109,6 +109,8 @@ EXPORTED_SYMBOLS = (
     "mxmoe_moe_decode_gate_up", "mxmoe_moe_decode_down",
     # the decode forward for gpt-oss layers: MXFP4 weights, gate_up biases, the clamped SwiGLU
     "mxmoe_moe_decode_gate_up_ex", "mxmoe_moe_decode_down_ex",
+    # the decode forward with the integer weight-only kinds (w4a16 / w8a16, per-channel or g128, sym or asym)
+    "mxmoe_moe_decode_gate_up_wo", "mxmoe_moe_decode_down_wo",
 )
 # added to ABI 7 without a version bump (additive): a product library without them is a stale build
 GPTOSS_SYMBOLS = ("mxmoe_moe_gate_ex2", "mxmoe_moe_glu_quant", "mxmoe_moe_combine_bias")
@@ -117,11 +119,24 @@ WIDE_GATE_SYMBOLS = ("mxmoe_moe_gate_wide",)
 DT_SYMBOLS = ("mxmoe_moe_gate_dt", "mxmoe_moe_gather_quant", "mxmoe_moe_combine_dt")  # (likewise: the bf16 layers)
 DECODE_SYMBOLS = ("mxmoe_moe_decode_gate_up", "mxmoe_moe_decode_down")  # (likewise: the decode forward)
 DECODE_EX_SYMBOLS = ("mxmoe_moe_decode_gate_up_ex", "mxmoe_moe_decode_down_ex")  # (likewise: gpt-oss layers)
+DECODE_WO_SYMBOLS = ("mxmoe_moe_decode_gate_up_wo", "mxmoe_moe_decode_down_wo")  # (likewise: weight-only experts)
 DT_FP16, DT_BF16 = 0, 1  # MXMOE_DT_* (include/mxmoe_moe.h)
 # MXMOE_DECODE_* (include/mxmoe_moe.h): the token limit, the kinds per linear, the gate_up layouts, the status bits
 DECODE_MAX_T = 16
 DECODE_FP16, DECODE_W8A8, DECODE_W4A4 = 0, 1, 2
-DECODE_W4A16_MX = 3  # (the _ex entries only)
+DECODE_W4A16_MX = 3  # (the _ex and _wo entries only)
+# the _wo entries only: kind = 4 + (w_bits == 8) + 2 * (gsize == 128) + 4 * asym
+DECODE_W4A16, DECODE_W8A16, DECODE_W4A16_G128, DECODE_W8A16_G128 = 4, 5, 6, 7
+DECODE_W4A16_ASYM, DECODE_W8A16_ASYM, DECODE_W4A16_G128_ASYM, DECODE_W8A16_G128_ASYM = 8, 9, 10, 11
+
+
+def decode_wo_kind(w_bits: int, gsize: int, sym: bool) -> int:
+    """MXMOE_DECODE_* of an integer weight-only type (w_bits 4 or 8, gsize -1 or 128)."""
+    if w_bits not in (4, 8) or gsize not in (-1, 128):
+        raise ValueError(f"no decode kind for w{w_bits}a16_g{gsize}: 4 or 8 bits, per-channel or g128")
+    return DECODE_W4A16 + (w_bits == 8) + 2 * (gsize == 128) + 4 * (not sym)
+
+
 DECODE_GU_PLAIN, DECODE_GU_INTERLEAVED = 0, 1
 DECODE_BAD_ID, DECODE_BAD_KIND = 1, 2
 GLU_SILU, GLU_SWIGLU_CLAMP = 0, 1  # MXMOE_GLU_* (include/mxmoe_moe.h)
@@ -309,6 +324,11 @@ def _declare(lib: ctypes.CDLL) -> None:
         lib.mxmoe_moe_decode_down_ex.restype = c.c_int
         lib.mxmoe_moe_decode_down_ex.argtypes = [c.c_int64, c.c_int, c.c_int, c.c_int, P, P, c.c_uint32, c.c_int, c.c_int,
                                                  c.c_int, P, P, P, P, P, P]
+    if all(hasattr(lib, fn) for fn in DECODE_WO_SYMBOLS):  # (builds before the weight-only decode forward lack them)
+        lib.mxmoe_moe_decode_gate_up_wo.restype = c.c_int
+        lib.mxmoe_moe_decode_gate_up_wo.argtypes = list(lib.mxmoe_moe_decode_gate_up_ex.argtypes)
+        lib.mxmoe_moe_decode_down_wo.restype = c.c_int
+        lib.mxmoe_moe_decode_down_wo.argtypes = list(lib.mxmoe_moe_decode_down_ex.argtypes)
 
 
 def lib() -> ctypes.CDLL:

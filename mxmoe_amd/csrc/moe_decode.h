@@ -38,6 +38,24 @@
 //             batch, accumulating in f32 (dot_rows_mx).
 //   epilogue  gate_up: the bias row of the workgroup's own expert and the gated activation of an mxmoe_moe_glu, by the
 //             activation pass's own helper (glu_value of moe_ops.hip); glu_out.
+//
+// The _wo entries (mxmoe_moe_decode_gate_up_wo, mxmoe_moe_decode_down_wo) run a third pair, decode_wo_kernel<DOWN>: the
+// _ex kernels' four kinds and epilogue, and the integer weight-only kinds 4..11 (w4a16 / w8a16, per-channel or g128,
+// sym or asym) on mxmoe_gg_repack_weightonly's codes and the [G][rows] / [G][rows][2] fp16 scale buffer. One body per
+// code width (expert_tile_wo<DOWN, 4 or 8>); the group size and the symmetry come from the record's kind as
+// workgroup-uniform values.
+//   codes     a lane's 16 bytes of step s are whole K runs of 8 (one dword of 4-bit, two dwords of 8-bit codes):
+//             4-bit  run j (0..3) of lane l: K = 512 s + 64 (l >> 1) + 32 (j & 1) + 8 (2 (l & 1) + (j >> 1)) + 0..7
+//             8-bit  run j (0..1) of lane l: K = 256 s + 64 (l >> 2) + 32 j + 8 (l & 3) + 0..7
+//   A rows    fp16, not quantised, permuted inside every step (4-bit: 512 K = 1024 bytes; 8-bit: 256 K = 512 bytes) so
+//             that the 8 elements of run j of lane l lie at LDS byte
+//               4-bit: 1024 s + 256 j + 16 l        8-bit: 512 s + 256 j + 16 l
+//             of the row: a lane's j-th ds_read_b128 of a step is the other kinds' conflict-free pattern (quant_row_wo).
+//   dequant   a run at a time, b = fp16(fma(u - off, scale, zp)) by the GroupGEMM's steps (wo_dequant of gg_device.h:
+//             0x6400 | u, an exact packed add, one packed fma), reused for every A row of the batch; f32 accumulation
+//             as the MX kind (dot_rows_wo).
+//   scales    per-channel: the two rows' (scale, zp), loaded once per weight row; g128: one pair per lane, step and
+//             row — group 4 s + (l >> 2) (4-bit) or 2 s + (l >> 3) (8-bit) — loaded with the step's codes.
 #pragma once
 
 namespace mxmoe {
@@ -81,6 +99,12 @@ template <> struct ArgsOf<true> { typedef ArgsEx type; };
 
 // bytes of a weight row in global memory, and of an A row in LDS: the integer kinds quantise A to the weights' width,
 // W4A16_MX keeps the fp16 row (four times its weight row)
+// the weight-only kinds (the _wo entries): kind = 4 + (w_bits == 8) + 2 * (gsize == 128) + 4 * asym
+__host__ __device__ inline bool wo_kind(int kind) { return kind >= MXMOE_DECODE_W4A16; }
+__host__ __device__ inline int wo_bits(int kind) { return ((kind - MXMOE_DECODE_W4A16) & 1) ? 8 : 4; }
+__host__ __device__ inline bool wo_g128(int kind) { return ((kind - MXMOE_DECODE_W4A16) & 2) != 0; }
+__host__ __device__ inline bool wo_asym(int kind) { return ((kind - MXMOE_DECODE_W4A16) & 4) != 0; }
+
 __host__ __device__ inline int b_row_bytes(int kind, int K) {
   return kind == MXMOE_DECODE_FP16 ? 2 * K : kind == MXMOE_DECODE_W8A8 ? K : K / 2;
 }
@@ -195,6 +219,25 @@ template <> struct Dot<MXMOE_DECODE_W4A16_MX> {
   static __device__ __forceinline__ _Float16 finish(float acc, _Float16, _Float16) { return (_Float16)acc; }
 };
 
+// The weight-only kinds: 8 codes (K ascending: one dword of 4-bit codes, 2q and 2q + 1 at bits 4q and 16 + 4q, or two
+// dwords of bytes) to b = fp16(fma(u - off, scale, zp)), the GroupGEMM's steps (wo_dequant of gg_device.h): 0x6400 | u
+// is the fp16 1024 + u, moff = -(1024 + off) makes u - off exactly (v_pk_add_f16), then one v_pk_fma_f16: one rounding.
+template <int BITS>
+__device__ __forceinline__ h8_t dequant_wo(uint32_t w0, uint32_t w1, h2_t moff, h2_t s2, h2_t z2) {
+  h8_t out;
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    uint32_t d;
+    if constexpr (BITS == 4) d = ((w0 >> (4 * q)) & 0x000F000Fu) | 0x64006400u;
+    else d = __builtin_amdgcn_perm(0x64646464u, q < 2 ? w0 : w1, (q & 1) ? 0x04030402u : 0x04010400u);
+    h2_t x = __builtin_bit_cast(h2_t, d) + moff;
+    x = __builtin_elementwise_fma(x, s2, z2);
+    out[2 * q] = x[0];
+    out[2 * q + 1] = x[1];
+  }
+  return out;
+}
+
 // Row `src` (K fp16, or bf16 converted as mxmoe_moe_gather_quant does) quantised by kind's tag into `row` (LDS,
 // pack_wxax order) by one wave, zeros behind it up to a multiple of 1024 bytes (the dot loop's group of four 256-byte
 // steps reads the pad); its scale to *scale. The arithmetic and the helpers are act_quant_kernel's.
@@ -244,6 +287,27 @@ __device__ __forceinline__ void quant_row(const uint8_t* __restrict__ src, int K
 #pragma unroll 4
     for (int idx = lane * 8; idx < K; idx += 512)
       *reinterpret_cast<uint32_t*>(row + idx / 2) = codes_i4(ld(idx), (float)sc, rs, lim);
+  }
+}
+
+// quant_row for the weight-only kinds (bits: the code width): the fp16 row (or bf16 converted), not quantised, as the
+// permuted copy the MX kind makes, with these kinds' source element (the K map at the head of this file). 4-bit: slot
+// 16 j + l of a step's 1024 bytes holds run j of lane l. 8-bit: two steps of 512 bytes per pass of 1024, slot
+// 32 s' + 16 j + l holds run j of lane l of step 2 (o / 1024) + s'. Lane 16 j' + l of the copying wave stores slot
+// 16 j' + l: consecutive lanes, consecutive slots. Pieces past the row are zeros up to a multiple of 1024 bytes.
+__device__ __forceinline__ void quant_row_wo(const uint8_t* __restrict__ src, int K, int bits, bool bf, uint8_t* row) {
+  const int lane = threadIdx.x & 63;
+  const int l = lane & 15, j = lane >> 4;
+  const int src_el = bits == 4 ? 64 * (l >> 1) + 32 * (j & 1) + 8 * (2 * (l & 1) + (j >> 1))
+                               : 256 * (j >> 1) + 64 * (l >> 2) + 32 * (j & 1) + 8 * (l & 3);
+  for (int o = 0; o < ((2 * K + 1023) & ~1023); o += 1024) {
+    const int idx = (o >> 1) + src_el;
+    h8_t v = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (idx < K) {
+      const uint4 x = *reinterpret_cast<const uint4*>(src + 2 * idx);
+      v = bf ? bf16x8_to_f16(x) : __builtin_bit_cast(h8_t, x);
+    }
+    *reinterpret_cast<h8_t*>(row + o + lane * 16) = v;
   }
 }
 
@@ -388,10 +452,111 @@ __device__ __forceinline__ void dot_rows_mx(const uint8_t* __restrict__ w0, cons
   *o1 = D::finish(v1, (_Float16)0, (_Float16)0);
 }
 
+// dot_rows for the weight-only kinds (BITS: the code width; g128, asym: of the expert's kind, workgroup-uniform). SB:
+// the weight's scale buffer, fp16 [G][rows] or (asym) [G][rows][2] (scale, zp); sr0 / sr1: the two weight rows. Lane l
+// holds 16 bytes of codes of step s of both rows: 4 (4-bit) or 2 (8-bit) runs of 8 K, each dequantised once and
+// multiplied with the run's 16 bytes of every A row of the batch (quant_row_wo's permuted copy). Per-channel scales are
+// loaded once here; g128 scales with the step's codes, one pair per lane and row. A lane past the row's end (only
+// inside its last step) loads the row's first bytes and group 0's scales, and codes, scale and zp are zeroed: b = +0
+// on the A rows' zero pad. Whole steps past the end are loaded the same way but not multiplied.
+template <int BITS>
+__device__ __forceinline__ void dot_rows_wo(const uint8_t* __restrict__ w0, const uint8_t* __restrict__ w1,
+                                            const _Float16* __restrict__ SB, int sr0, int sr1, int rows, bool g128,
+                                            bool asym, int KB, const uint8_t* A, int lds_row, int nr, int l16,
+                                            _Float16* o0, _Float16* o1) {
+  typedef Dot<MXMOE_DECODE_W4A16_MX> D;  // (the fp16-times-fp16 f32 dot of 8 elements)
+  constexpr int kRuns = BITS == 4 ? 4 : 2;           // K runs of 8 in a lane's 16 bytes
+  constexpr int kStepLds = BITS == 4 ? 1024 : 512;   // LDS bytes of an A row per step
+  constexpr int kStepGroups = BITS == 4 ? 4 : 2;     // 128-K groups per step
+  float acc0[kBatchRows], acc1[kBatchRows];
+#pragma unroll
+  for (int r = 0; r < kBatchRows; ++r) acc0[r] = acc1[r] = 0;
+  const int S = (KB + 255) >> 8;
+  const int gl = BITS == 4 ? l16 >> 2 : l16 >> 3;
+  const int sh = asym ? 1 : 0;  // element (g * rows + r) << sh: the scale; + 1 (asym): the zp
+  const _Float16 off = (_Float16)(asym ? -1024.0f : BITS == 4 ? -1031.0f : -1151.0f);  // -(1024 + 2^(BITS-1) - 1), sym
+  const h2_t moff = {off, off};
+  // (scale, zp) of a row's group as one register
+  auto pair = [&](int row, int g) -> h2_t {
+    const int i = (g * rows + row) << sh;
+    return h2_t{SB[i], asym ? SB[i + 1] : (_Float16)0};
+  };
+  h2_t pc0 = {0, 0}, pc1 = {0, 0};
+  if (!g128) {
+    pc0 = pair(sr0, 0);
+    pc1 = pair(sr1, 0);
+  }
+  for (int s0 = 0; s0 < S; s0 += 4) {
+    uint4 wa[4], wb[4];
+    h2_t sa[4], sb[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {  // 8 loads of 16 B (and, g128, the 2 or 4 scale halves of each) in flight
+      const bool in = ((s0 + u) * 16 + l16) * 16 < KB;
+      const int wo = in ? ((s0 + u) * 16 + l16) * 16 : 0;
+      wa[u] = *reinterpret_cast<const uint4*>(w0 + wo);
+      wb[u] = *reinterpret_cast<const uint4*>(w1 + wo);
+      if (g128) {
+        const int g = in ? (s0 + u) * kStepGroups + gl : 0;
+        sa[u] = pair(sr0, g);
+        sb[u] = pair(sr1, g);
+      } else {
+        sa[u] = pc0;
+        sb[u] = pc1;
+      }
+      if (!in) {
+        wa[u] = wb[u] = uint4{0, 0, 0, 0};
+        sa[u] = sb[u] = h2_t{0, 0};
+      }
+    }
+    int nrs = nr, ldr = lds_row;
+    asm volatile("" : "+s"(nrs), "+s"(ldr));  // (as in dot_rows)
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      if (s0 + u < S) {  // workgroup-uniform
+        const uint32_t da[4] = {wa[u].x, wa[u].y, wa[u].z, wa[u].w}, db[4] = {wb[u].x, wb[u].y, wb[u].z, wb[u].w};
+        const h2_t as2 = {sa[u][0], sa[u][0]}, az2 = {sa[u][1], sa[u][1]};
+        const h2_t bs2 = {sb[u][0], sb[u][0]}, bz2 = {sb[u][1], sb[u][1]};
+#pragma unroll
+        for (int j = 0; j < kRuns; ++j) {  // a run at a time: 8 weights of each row live
+          const int d = BITS == 4 ? j : 2 * j;
+          const h8_t x0 = dequant_wo<BITS>(da[d], da[(d + 1) & 3], moff, as2, az2);
+          const h8_t x1 = dequant_wo<BITS>(db[d], db[(d + 1) & 3], moff, bs2, bz2);
+          const uint8_t* const aj = A + (s0 + u) * kStepLds + 256 * j + l16 * 16;  // (< lds_row: whole steps of the row)
+#pragma unroll
+          for (int r = 0; r < kBatchRows; ++r) {
+            if (r < nrs) {  // workgroup-uniform
+              const uint4 av = *reinterpret_cast<const uint4*>(aj + r * ldr);
+              acc0[r] = D::dot(x0, av, acc0[r]);
+              acc1[r] = D::dot(x1, av, acc1[r]);
+            }
+          }
+        }
+      }
+    }
+  }
+  float v0 = 0, v1 = 0;
+  int lsel = l16, nrs = nr;
+  asm volatile("" : "+v"(lsel), "+s"(nrs));
+#pragma unroll
+  for (int r = 0; r < kBatchRows; ++r) {
+    if (r < nrs) {
+      const float t0 = row16_sum(acc0[r]), t1 = row16_sum(acc1[r]);
+      if (lsel == r) {
+        v0 = t0;
+        v1 = t1;
+      }
+    }
+  }
+  *o0 = D::finish(v0, (_Float16)0, (_Float16)0);
+  *o1 = D::finish(v1, (_Float16)0, (_Float16)0);
+}
+
 // One workgroup's work on an expert of kind KIND: per batch of rows, the A rows into LDS, then the tile's columns.
 // EX: the _ex entries' build — `brow`, the bias row of the workgroup's expert ([gate | up], or NULL), and the gated
-// activation of ArgsEx in the gate_up epilogue. Without EX none of that code exists.
-template <bool DOWN, int KIND, bool EX = false>
+// activation of ArgsEx in the gate_up epilogue. Without EX none of that code exists. WO: a tag that changes no code and
+// gives the _wo kernels instantiations of their own — when they shared the _ex kernels', those kernels' register
+// allocation changed (DESIGN.md §4 "Decode forward: weight-only experts").
+template <bool DOWN, int KIND, bool EX = false, int WO = 0>
 __device__ __forceinline__ void expert_tile(const typename ArgsOf<EX>::type& a, const mxmoe_moe_decode_expert& ex,
                                             bool shared, int tile, int nrows, uint8_t* s_a, const int* s_rows,
                                             _Float16* s_scale, const _Float16* brow = nullptr) {
@@ -459,6 +624,68 @@ __device__ __forceinline__ void expert_tile(const typename ArgsOf<EX>::type& a, 
   }
 }
 
+// expert_tile for the weight-only kinds 4..11 (the _wo kernels; BITS: the code width, `kind`: the record's own, which
+// gives the group size and the symmetry as workgroup-uniform values): the same batches, columns, weight rows and
+// gate_up epilogue, with the fp16 A rows of quant_row_wo and the dot of dot_rows_wo.
+template <bool DOWN, int BITS>
+__device__ __forceinline__ void expert_tile_wo(const ArgsEx& a, const mxmoe_moe_decode_expert& ex, int kind, bool shared,
+                                               int tile, int nrows, uint8_t* s_a, const int* s_rows,
+                                               const _Float16* brow) {
+  const int tid = threadIdx.x, wave = tid >> 6;
+  const int K = shared ? a.K_shared : a.K, C = shared ? a.C_shared : a.C;
+  const int KB = K * BITS / 8;  // of a weight row (the fp16 A row's 2 K bytes are <= lds_row: the kind is in the mask)
+  const uint8_t* const B = static_cast<const uint8_t*>(DOWN ? ex.b2 : ex.b1);
+  const _Float16* const SB = static_cast<const _Float16*>(DOWN ? ex.sb2 : ex.sb1);
+  const uint8_t* const src = static_cast<const uint8_t*>(shared ? a.src_shared : a.src);
+  _Float16* const out = shared ? a.out_shared : a.out;
+  const int n0 = tile * a.ct;
+  const int q = tid >> 4, l16 = tid & 15;
+  const int rows = DOWN ? C : 2 * C;  // of the weight: the scale buffer is [G][rows] or [G][rows][2]
+  const bool g128 = wo_g128(kind), asym = wo_asym(kind);
+
+  for (int r0 = 0; r0 < nrows; r0 += a.rb) {
+    const int nr = min(a.rb, nrows - r0);
+    __syncthreads();  // s_rows is complete; the previous batch's A rows are no longer read
+    for (int r = wave; r < nr; r += kThreadsD / 64) {
+      const int p = shared ? r0 + r : s_rows[r0 + r];      // token (shared) or pair
+      const int srow = (shared || DOWN) ? p : p / a.topk;  // gate_up reads the pair's token
+      quant_row_wo(src + (int64_t)srow * K * 2, K, BITS, !DOWN && a.src_bf16, s_a + r * a.lds_row);
+    }
+    __syncthreads();
+    const int orow = l16 < nr ? (shared ? r0 + l16 : s_rows[r0 + l16]) : 0;
+    for (int c = q; c < a.ct; c += DOWN ? 32 : 16) {
+      const int n = n0 + c;
+      if (n + (DOWN ? 16 : 0) >= C) continue;
+      int wr0, wr1;  // (as in expert_tile)
+      if constexpr (DOWN) {
+        wr0 = n;
+        wr1 = n + 16;
+      } else if (a.layout == MXMOE_DECODE_GU_INTERLEAVED) {
+        wr0 = 32 * (n >> 4) + (n & 15);
+        wr1 = wr0 + 16;
+      } else {
+        wr0 = n;
+        wr1 = C + n;
+      }
+      _Float16 o0, o1;
+      dot_rows_wo<BITS>(B + (int64_t)wr0 * KB, B + (int64_t)wr1 * KB, SB, wr0, wr1, rows, g128, asym, KB, s_a, a.lds_row,
+                        nr, l16, &o0, &o1);
+      if (l16 < nr) {
+        _Float16* const orp = out + (int64_t)orow * C;
+        if constexpr (DOWN) {
+          orp[n] = o0;
+          orp[n + 16] = o1;
+        } else {
+          const bool has_b = brow != nullptr;  // workgroup-uniform
+          const _Float16 bg = has_b ? brow[n] : (_Float16)0, bu = has_b ? brow[C + n] : (_Float16)0;
+          orp[n] = a.glu == kGluSwigluClamp ? glu_out<kGluSwigluClamp>(o0, o1, has_b, bg, bu, a.limit, a.c)
+                                            : glu_out<kGluSilu>(o0, o1, has_b, bg, bu, a.limit, a.c);
+        }
+      }
+    }
+  }
+}
+
 // The kernels. DOWN = false: decode_gate_up; true: decode_down. Both begin with the statements of
 // moe_decode_body.inc; decode_ex_kernel (the _ex entries) also carries the W4A16_MX kind and (gate_up) the biases and the
 // gated activation, through expert_tile's EX parameter: without it that code does not exist.
@@ -486,16 +713,45 @@ __global__ __launch_bounds__(kThreadsD) void decode_ex_kernel(ArgsEx a) {
     expert_tile<DOWN, MXMOE_DECODE_W4A16_MX, true>(a, ex, shared, tile, nrows, s_a, s_rows, s_scale, brow);
 }
 
+// the _wo entries: the _ex kernel's kinds and, per code width, one body for the weight-only kinds 4..11
+struct ArgsWo : ArgsEx {};
+template <bool DOWN>
+__global__ __launch_bounds__(kThreadsD) void decode_wo_kernel(ArgsWo a) {
+#include "moe_decode_body.inc"
+  const _Float16* brow = nullptr;
+  if constexpr (!DOWN) brow = shared ? a.bias_shared : a.bias_routed ? a.bias_routed + (int64_t)e * 2 * a.C : nullptr;
+  if (kind == MXMOE_DECODE_FP16)
+    expert_tile<DOWN, MXMOE_DECODE_FP16, true, 1>(a, ex, shared, tile, nrows, s_a, s_rows, s_scale, brow);
+  else if (kind == MXMOE_DECODE_W8A8)
+    expert_tile<DOWN, MXMOE_DECODE_W8A8, true, 1>(a, ex, shared, tile, nrows, s_a, s_rows, s_scale, brow);
+  else if (kind == MXMOE_DECODE_W4A4)
+    expert_tile<DOWN, MXMOE_DECODE_W4A4, true, 1>(a, ex, shared, tile, nrows, s_a, s_rows, s_scale, brow);
+  else if (kind == MXMOE_DECODE_W4A16_MX)
+    expert_tile<DOWN, MXMOE_DECODE_W4A16_MX, true, 1>(a, ex, shared, tile, nrows, s_a, s_rows, s_scale, brow);
+  else if (wo_bits(kind) == 4)  // (kind <= 11: it is in the mask, which the entry checked)
+    expert_tile_wo<DOWN, 4>(a, ex, kind, shared, tile, nrows, s_a, s_rows, brow);
+  else
+    expert_tile_wo<DOWN, 8>(a, ex, kind, shared, tile, nrows, s_a, s_rows, brow);
+}
+
 // ---------------------------------------------------------------------------------------------
 // host side: the entries' checks (before any HIP call) and the launch geometry
 
-// ex: the _ex entries, which also take W4A16_MX
-inline int kind_mask_check(const char* fn, uint32_t kind_mask, bool ex = false) {
-  const uint32_t known = 1u << MXMOE_DECODE_FP16 | 1u << MXMOE_DECODE_W8A8 | 1u << MXMOE_DECODE_W4A4 |
-                         (ex ? 1u << MXMOE_DECODE_W4A16_MX : 0u);
-  if (kind_mask & ~known)
-    return fail(MXMOE_GG_ERR_UNSUPPORTED, "%s: unknown expert kind in kind_mask %#x (fp16, w8a8_g-1_sym%s w4a4_g-1_sym%s "
-                "only)", fn, kind_mask, ex ? "," : " and", ex ? " and w4a16_g32_sym_MXFP4" : "");
+// level: which entries — kFirst, kEx (also W4A16_MX) or kWo (also the weight-only kinds 4..11)
+enum { kFirst = 0, kEx = 1, kWo = 2 };
+inline int kind_mask_check(const char* fn, uint32_t kind_mask, int level = kFirst) {
+  if (level == kWo) {
+    if (kind_mask >> (MXMOE_DECODE_W8A16_G128_ASYM + 1))
+      return fail(MXMOE_GG_ERR_UNSUPPORTED, "%s: unknown expert kind in kind_mask %#x (kinds 0 to %d only)", fn, kind_mask,
+                  (int)MXMOE_DECODE_W8A16_G128_ASYM);
+  } else {
+    const bool ex = level == kEx;
+    const uint32_t known = 1u << MXMOE_DECODE_FP16 | 1u << MXMOE_DECODE_W8A8 | 1u << MXMOE_DECODE_W4A4 |
+                           (ex ? 1u << MXMOE_DECODE_W4A16_MX : 0u);
+    if (kind_mask & ~known)
+      return fail(MXMOE_GG_ERR_UNSUPPORTED, "%s: unknown expert kind in kind_mask %#x (fp16, w8a8_g-1_sym%s w4a4_g-1_sym%s "
+                  "only)", fn, kind_mask, ex ? "," : " and", ex ? " and w4a16_g32_sym_MXFP4" : "");
+  }
   if (!kind_mask) return fail(MXMOE_GG_ERR_INVALID, "%s: kind_mask names no kind", fn);
   return MXMOE_GG_OK;
 }
@@ -515,8 +771,11 @@ inline int sizes_check(const char* fn, int64_t T, int topk, int E, int with_shar
 inline int geometry(Args& a) {
   int kb = 0;
   const int kmax = a.with_shared && a.K_shared > a.K ? a.K_shared : a.K;
-  for (int k = 0; k <= MXMOE_DECODE_W4A16_MX; ++k)
-    if ((a.kind_mask >> k) & 1u) kb = a_row_bytes(k, kmax) > kb ? a_row_bytes(k, kmax) : kb;
+  for (int k = 0; k <= MXMOE_DECODE_W8A16_G128_ASYM; ++k)
+    if ((a.kind_mask >> k) & 1u) {
+      const int ab = wo_kind(k) ? 2 * kmax : a_row_bytes(k, kmax);  // (the weight-only kinds keep the fp16 row)
+      kb = ab > kb ? ab : kb;
+    }
   a.lds_row = kb = (kb + 1023) & ~1023;  // (rows are zero-padded to the dot loop's group of four 256-byte steps)
   int rb = kLdsBudget / kb;
   rb = rb < 1 ? 1 : rb > kBatchRows ? kBatchRows : rb;
@@ -532,12 +791,15 @@ inline int geometry(Args& a) {
   return a.rb * a.lds_row;
 }
 
-// ArgsEx: the _ex kernels; Args: the kernels of the first two entries
+// ArgsWo: the _wo kernels; ArgsEx: the _ex kernels; Args: the kernels of the first two entries
 template <bool DOWN, class ARGS>
 inline int launch(ARGS a, void* stream) {
   const int lds = geometry(a);
   const int64_t blocks = (int64_t)a.tiles_shared + (int64_t)a.E * a.tiles;
-  if constexpr (std::is_same<ARGS, ArgsEx>::value) {
+  if constexpr (std::is_same<ARGS, ArgsWo>::value) {
+    hipLaunchKernelGGL(decode_wo_kernel<DOWN>, dim3((unsigned)blocks), dim3(kThreadsD), lds, (hipStream_t)stream, a);
+    return launched(DOWN ? "decode_down_wo_kernel" : "decode_gate_up_wo_kernel");
+  } else if constexpr (std::is_same<ARGS, ArgsEx>::value) {
     hipLaunchKernelGGL(decode_ex_kernel<DOWN>, dim3((unsigned)blocks), dim3(kThreadsD), lds, (hipStream_t)stream, a);
     return launched(DOWN ? "decode_down_ex_kernel" : "decode_gate_up_ex_kernel");
   } else {

@@ -1,5 +1,5 @@
-// moe_decode_body.inc — the statements with which both decode kernels of moe_decode.h begin (decode_kernel<DOWN>,
-// decode_ex_kernel<DOWN>; `a`: the kernel's Args or ArgsEx): the workgroup's expert and column tile, the rows of that
+// moe_decode_body.inc — the statements with which the three decode kernels of moe_decode.h begin (decode_kernel<DOWN>,
+// decode_ex_kernel<DOWN>, decode_wo_kernel<DOWN>; `a`: the kernel's Args, ArgsEx or ArgsWo): the workgroup's expert and column tile, the rows of that
 // expert among the call's ids (in pair order, into s_rows), the report of ids that no workgroup matches, and the
 // expert's record and kind. Leaves s_a, s_rows, s_scale, shared, e, tile, nrows, ex and kind to the kernel; a
 // workgroup without rows, or with a kind outside the call's mask, returns here. Included as text, not called: the

@@ -940,9 +940,10 @@ static int glu_check(const char* fn, const mxmoe_moe_glu* glu) {
   return MXMOE_GG_OK;
 }
 
-// The two decode entries and their _ex forms: one body of checks and one launcher each. ex: the _ex entry (kind bit 3,
-// the _ex kernels; glu may be NULL: SiLU and no bias); otherwise glu is NULL and the first entries' kernels run.
-static int decode_gate_up_impl(const char* fn, bool ex, const mxmoe_moe_glu* glu, int dtype, const void* hidden, int64_t T,
+// The two decode entries and their _ex and _wo forms: one body of checks and one launcher each. ex: decode::kEx, the
+// _ex entry (kind bit 3, the _ex kernels; glu may be NULL: SiLU and no bias), decode::kWo, the _wo entry (kind bits up
+// to 11, the _wo kernels, glu likewise); otherwise glu is NULL and the first entries' kernels run.
+static int decode_gate_up_impl(const char* fn, int ex, const mxmoe_moe_glu* glu, int dtype, const void* hidden, int64_t T,
                                int topk, int E, int with_shared, const int32_t* topk_ids,
                                const mxmoe_moe_decode_expert* experts, uint32_t kind_mask, int H, int N, int N_shared,
                                int layout, void* act, void* act_shared, int32_t* status, void* stream) {
@@ -963,7 +964,7 @@ static int decode_gate_up_impl(const char* fn, bool ex, const mxmoe_moe_glu* glu
   if (T == 0) return MXMOE_GG_OK;
   if (!hidden || !topk_ids || !experts || !act || (with_shared && !act_shared))
     return fail(MXMOE_GG_ERR_INVALID, "%s: NULL pointer", fn);
-  decode::ArgsEx a{};
+  decode::ArgsWo a{};
   a.src = a.src_shared = hidden;
   a.ids = topk_ids;
   a.experts = experts;
@@ -982,10 +983,11 @@ static int decode_gate_up_impl(const char* fn, bool ex, const mxmoe_moe_glu* glu
     a.c = -(glu->alpha * 1.4426950408889634f);
     a.limit = glu->limit;
   }
-  return decode::launch<false>(a, stream);
+  if (ex == decode::kWo) return decode::launch<false>(static_cast<const decode::ArgsWo&>(a), stream);
+  return decode::launch<false>(static_cast<const decode::ArgsEx&>(a), stream);
 }
 
-static int decode_down_impl(const char* fn, bool ex, int64_t T, int topk, int E, int with_shared, const int32_t* topk_ids,
+static int decode_down_impl(const char* fn, int ex, int64_t T, int topk, int E, int with_shared, const int32_t* topk_ids,
                             const mxmoe_moe_decode_expert* experts, uint32_t kind_mask, int H, int N, int N_shared,
                             const void* act, const void* act_shared, void* y, void* ys, int32_t* status, void* stream) {
   if (int st = decode::kind_mask_check(fn, kind_mask, ex)) return st;
@@ -996,7 +998,7 @@ static int decode_down_impl(const char* fn, bool ex, int64_t T, int topk, int E,
   if (T == 0) return MXMOE_GG_OK;
   if (!act || !topk_ids || !experts || !y || (with_shared && (!act_shared || !ys)))
     return fail(MXMOE_GG_ERR_INVALID, "%s: NULL pointer", fn);
-  decode::ArgsEx a{};
+  decode::ArgsWo a{};
   a.src = act;
   a.src_shared = act_shared;
   a.ids = topk_ids;
@@ -1009,7 +1011,8 @@ static int decode_down_impl(const char* fn, bool ex, int64_t T, int topk, int E,
   a.C = a.C_shared = H;
   a.kind_mask = kind_mask;
   if (!ex) return decode::launch<true>(static_cast<const decode::Args&>(a), stream);
-  return decode::launch<true>(a, stream);
+  if (ex == decode::kWo) return decode::launch<true>(static_cast<const decode::ArgsWo&>(a), stream);
+  return decode::launch<true>(static_cast<const decode::ArgsEx&>(a), stream);
 }
 
 extern "C" {
@@ -1195,14 +1198,14 @@ int mxmoe_moe_combine(const void* y, const int32_t* inv_slot, const float* weigh
 int mxmoe_moe_decode_gate_up(int dtype, const void* hidden, int64_t T, int topk, int E, int with_shared,
                              const int32_t* topk_ids, const mxmoe_moe_decode_expert* experts, uint32_t kind_mask, int H,
                              int N, int N_shared, int layout, void* act, void* act_shared, int32_t* status, void* stream) {
-  return decode_gate_up_impl("mxmoe_moe_decode_gate_up", false, nullptr, dtype, hidden, T, topk, E, with_shared, topk_ids,
+  return decode_gate_up_impl("mxmoe_moe_decode_gate_up", decode::kFirst, nullptr, dtype, hidden, T, topk, E, with_shared, topk_ids,
                              experts, kind_mask, H, N, N_shared, layout, act, act_shared, status, stream);
 }
 
 int mxmoe_moe_decode_down(int64_t T, int topk, int E, int with_shared, const int32_t* topk_ids,
                           const mxmoe_moe_decode_expert* experts, uint32_t kind_mask, int H, int N, int N_shared,
                           const void* act, const void* act_shared, void* y, void* ys, int32_t* status, void* stream) {
-  return decode_down_impl("mxmoe_moe_decode_down", false, T, topk, E, with_shared, topk_ids, experts, kind_mask, H, N,
+  return decode_down_impl("mxmoe_moe_decode_down", decode::kFirst, T, topk, E, with_shared, topk_ids, experts, kind_mask, H, N,
                           N_shared, act, act_shared, y, ys, status, stream);
 }
 
@@ -1210,15 +1213,30 @@ int mxmoe_moe_decode_gate_up_ex(const mxmoe_moe_glu* glu, int dtype, const void*
                                 int with_shared, const int32_t* topk_ids, const mxmoe_moe_decode_expert* experts,
                                 uint32_t kind_mask, int H, int N, int N_shared, int layout, void* act, void* act_shared,
                                 int32_t* status, void* stream) {
-  return decode_gate_up_impl("mxmoe_moe_decode_gate_up_ex", true, glu, dtype, hidden, T, topk, E, with_shared, topk_ids,
+  return decode_gate_up_impl("mxmoe_moe_decode_gate_up_ex", decode::kEx, glu, dtype, hidden, T, topk, E, with_shared, topk_ids,
                              experts, kind_mask, H, N, N_shared, layout, act, act_shared, status, stream);
 }
 
 int mxmoe_moe_decode_down_ex(int64_t T, int topk, int E, int with_shared, const int32_t* topk_ids,
                              const mxmoe_moe_decode_expert* experts, uint32_t kind_mask, int H, int N, int N_shared,
                              const void* act, const void* act_shared, void* y, void* ys, int32_t* status, void* stream) {
-  return decode_down_impl("mxmoe_moe_decode_down_ex", true, T, topk, E, with_shared, topk_ids, experts, kind_mask, H, N,
+  return decode_down_impl("mxmoe_moe_decode_down_ex", decode::kEx, T, topk, E, with_shared, topk_ids, experts, kind_mask, H, N,
                           N_shared, act, act_shared, y, ys, status, stream);
+}
+
+int mxmoe_moe_decode_gate_up_wo(const mxmoe_moe_glu* glu, int dtype, const void* hidden, int64_t T, int topk, int E,
+                                int with_shared, const int32_t* topk_ids, const mxmoe_moe_decode_expert* experts,
+                                uint32_t kind_mask, int H, int N, int N_shared, int layout, void* act, void* act_shared,
+                                int32_t* status, void* stream) {
+  return decode_gate_up_impl("mxmoe_moe_decode_gate_up_wo", decode::kWo, glu, dtype, hidden, T, topk, E, with_shared,
+                             topk_ids, experts, kind_mask, H, N, N_shared, layout, act, act_shared, status, stream);
+}
+
+int mxmoe_moe_decode_down_wo(int64_t T, int topk, int E, int with_shared, const int32_t* topk_ids,
+                             const mxmoe_moe_decode_expert* experts, uint32_t kind_mask, int H, int N, int N_shared,
+                             const void* act, const void* act_shared, void* y, void* ys, int32_t* status, void* stream) {
+  return decode_down_impl("mxmoe_moe_decode_down_wo", decode::kWo, T, topk, E, with_shared, topk_ids, experts, kind_mask,
+                          H, N, N_shared, act, act_shared, y, ys, status, stream);
 }
 
 }  // extern "C"

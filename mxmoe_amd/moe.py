@@ -1336,6 +1336,9 @@ class _DecodeBase:
     def _check_layer(self, ffn: "MoEFFN") -> None:
         """What the class refuses about a layer beyond the experts' types."""
 
+    def _check_scale(self, w: "ExpertWeights", dev) -> None:
+        """What the class refuses about a weight's scale buffer (a kind whose kernel indexes it by more than the row)."""
+
     def __init__(self, layer, T: int, topk: Optional[int] = None, device=None, dtype: Optional[torch.dtype] = None):
         """T: the capacity in tokens (1..16; an uncaptured call may bring fewer rows). dtype: the element type of
         ``hidden`` and ``out`` (fp16 or bf16); default: the block's ``w_gate.dtype`` (which it must equal), fp16 for
@@ -1381,6 +1384,7 @@ class _DecodeBase:
                                      "layer's device")
                 if self.TAKES_MX and w.scale_b is not None and (w.scale_b.device != dev or not w.scale_b.is_contiguous()):
                     raise ValueError(f"{name}: every scale_b must be a contiguous tensor on the layer's device")
+                self._check_scale(w, dev)
             rec.b1, rec.sb1 = w1.B.data_ptr(), 0 if w1.scale_b is None else w1.scale_b.data_ptr()
             rec.b2, rec.sb2 = w2.B.data_ptr(), 0 if w2.scale_b is None else w2.scale_b.data_ptr()
             rec.kind1, rec.kind2 = k1, k2
@@ -1473,7 +1477,8 @@ class DecodeForward(_DecodeBase):
 
     Experts may be fp16, w8a8_g-1_sym or w4a4_g-1_sym, mixed freely per expert and per linear; the weights are the
     layer's own tensors (no copy). Anything else — the MX and weight-only types, g128, a layer with a bias or
-    another activation — raises ValueError here (``DecodeForwardEx`` takes gpt-oss layers). An id outside [0, E)
+    another activation — raises ValueError here (``DecodeForwardEx`` takes gpt-oss layers, ``DecodeForwardWo`` the
+    integer weight-only types). An id outside [0, E)
     leaves its pair's rows as they were and sets ``DECODE_BAD_ID`` in ``status()``; every access stays inside the
     buffers."""
 
@@ -1502,7 +1507,7 @@ class DecodeForwardEx(_DecodeBase):
     So a gpt-oss MoE block decodes as router -> decode_gate_up -> decode_down -> combine, launches only, with fp16 or
     bf16 ends. ``out`` equals ``MoEFFN.forward``'s bit for bit for w8a8 / w4a4 experts and within the f32 summation
     order for fp16 and MXFP4 experts. Still refused, naming the qcfg: w4a4_g32_sym_MXFP4, w4a8_g32_sym_MXFP8, g128
-    and the integer weight-only types.
+    and the integer weight-only types (``DecodeForwardWo`` takes those).
 
     On the gpt-oss layer shape (E = 32, topk = 4, H = N = 2944) this form takes 0.56x / 0.71x of ``GraphForward``'s
     device time at T = 1 / 4, 0.94x at T = 6 and 1.14x / 1.48x at T = 8 / 16: the crossover is between 6 and 8
@@ -1512,6 +1517,46 @@ class DecodeForwardEx(_DecodeBase):
     ENTRIES = nat.DECODE_EX_SYMBOLS
     TAKES_GLU = True
     TAKES_MX = True
+
+
+class DecodeForwardWo(_DecodeBase):
+    """``DecodeForwardEx`` for layers with integer weight-only experts (DESIGN.md §4 "Decode forward: weight-only
+    experts"): the same constructor, ``launch`` and ``status`` on the _wo entries (mxmoe_moe_decode_gate_up_wo /
+    mxmoe_moe_decode_down_wo, include/mxmoe_moe.h), which take everything the _ex entries take and also
+
+    - ``w4a16`` and ``w8a16`` experts, per-channel (``g-1``) or ``g128``, ``sym`` or ``asym``: ``prepare_weight``'s
+      repacked codes and its [G][rows] / [G][rows][2] fp16 scale buffer, read in place, mixed freely with the other
+      kinds per expert and per linear. The A row stays fp16; a weight is fp16(fma(u - off, scale, zp)), the
+      GroupGEMM's value, and a row's sum is accumulated in f32 in the kernel's order: ``out`` is within the f32
+      summation order of ``MoEFFN.forward``'s.
+
+    Which class takes which layer: ``DecodeForward`` fp16 / w8a8 / w4a4 experts with SiLU and no bias;
+    ``DecodeForwardEx`` those plus w4a16_g32_sym_MXFP4, biases and ``SwigluClamp`` (gpt-oss); ``DecodeForwardWo``
+    all of that plus the eight integer weight-only types — the reference's small-batch scheme w4a16 + w8a8
+    (``workload.w4a16_w8a8_qconfig``) is a layer for this class. Still refused, naming the qcfg: w2a16, group sizes
+    other than -1 and 128, w4a4_g32_sym_MXFP4, w4a8_g32_sym_MXFP8, w4a4_g128, E4M3 and bf16 experts.
+
+    On qwen2_moe layer 11 with the w4a16 + w8a8 scheme (E = 60, topk = 4, the shared expert included) this form takes
+    0.37x / 0.51x / 0.66x of ``GraphForward``'s device time at T = 1 / 4 / 6, 0.99x at T = 8 and 1.32x / 1.68x at
+    T = 12 / 16: take ``GraphForward`` from T = 8."""
+
+    KINDS = dict(DecodeForwardEx.KINDS, **{f"w{b}a16_g{g}_{'sym' if s else 'asym'}": nat.decode_wo_kind(b, g, s)
+                                           for b in (4, 8) for g in (-1, 128) for s in (True, False)})
+    ENTRIES = nat.DECODE_WO_SYMBOLS
+    TAKES_GLU = True
+    TAKES_MX = True
+
+    def _check_scale(self, w: "ExpertWeights", dev) -> None:
+        """The weight-only kernel reads scale_b by group and row: the buffer is checked like the weights."""
+        q = w.q
+        if not q.is_weight_only or q.fmt:  # (the MX kind's e8m0 rows: TAKES_MX's check)
+            return
+        want = (1 if q.gsize == -1 else w.K // q.gsize) * w.N * (1 if q.sym else 2)
+        sb = w.scale_b
+        if (sb is None or sb.device != dev or sb.dtype != torch.float16 or not sb.is_contiguous() or sb.data_ptr() % 2 or
+                sb.numel() != want):
+            raise ValueError(f"DecodeForwardWo: the scale buffer of a {q.qcfg} weight [{w.N}, {w.K}] must be a contiguous "
+                             f"fp16 tensor of {want} elements on the layer's device")
 
 
 def qwen2_layer_bench(*args, **kwargs) -> dict:

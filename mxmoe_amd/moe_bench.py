@@ -12,7 +12,7 @@ import torch
 from . import _native as nat
 from .groupgemm import W4A8_MXFP8, W4A16_MXFP4, QParams
 from .harness import time_launches
-from .moe import (_BITS, DecodeForward, DecodeForwardEx, GraphForward, MoEBlock, MoEFFN, PlannedForward, SwigluClamp, _launch_combine,
+from .moe import (_BITS, DecodeForward, DecodeForwardEx, DecodeForwardWo, GraphForward, MoEBlock, MoEFFN, PlannedForward, SwigluClamp, _launch_combine,
                   _ptr, _stream, combine_into, gate, gptoss_layer, prepare_weight_mx, silu_mul_quant)
 from .workload import (ds2_mixed_qconfig, ds2_workload, load_workload, mixed_qconfig_lp1, qwen2_layer11_workload,
                        w4a16_w8a8_qconfig)
@@ -265,6 +265,74 @@ def decode_forward_bench(batches: Sequence[int] = (1, 4, 16), rounds: int = 4, i
         out["faster"] = bool(out["decode_device"]["max_us"] < out["graph_device"]["min_us"])
         out["bit_identical_to_eager"] = same
         out["status"] = {"graph": gf.status(), "decode": df.status() | dp.status()}
+        return out
+
+    for bs in batches:
+        yield one(bs)
+
+
+def decode_forward_wo_bench(batches: Sequence[int] = (1, 4, 16), rounds: int = 4, iters: int = 30):
+    """qwen2_moe layer 11 with the reference's small-batch scheme (``w4a16_w8a8_qconfig``: w4a16_g-1_asym + w8a8 per
+    linear, the shared expert included; random weights, routing drawn from the committed histogram) at decode sizes,
+    ``DecodeForwardWo`` against ``GraphForward`` of the same layer, as ``decode_forward_bench`` measures the LP-1 layer:
+    both replayed from captured graphs in one process, the sides alternating over rounds (yields one dict per batch
+    size). Also the two _wo kernels and the combine alone, the weight bytes (codes and scale buffers of the experts the
+    ids name, and the shared expert's) and the TB/s they imply. ``faster``: DecodeForwardWo's device median, max over
+    rounds, below GraphForward's min over rounds. Weight-only sums depend on their order, so the outputs are compared
+    with the eager layer's within the fp16 GroupGEMM tolerance (1e-3 |ref| + 1e-3 rms(ref)), not bit for bit."""
+    shapes, topk = load_workload(qwen2_layer11_workload(8192, qconfig=w4a16_w8a8_qconfig()))["layer-11"], 4
+    E = len(shapes["gate_up"]) - 1
+    H = shapes["gate_up"][0].K
+    N, Ns = shapes["down"][0].K, shapes["down"][-1].K
+    qcfg = [(QParams(a.a_bits, a.w_bits, a.gsize, a.sym), QParams(b.a_bits, b.w_bits, b.gsize, b.sym))
+            for a, b in zip(shapes["gate_up"], shapes["down"])]
+    dev = "cuda"
+    g = torch.Generator().manual_seed(0)
+    hist = torch.tensor([max(s.M, 1) for s in shapes["gate_up"][:E]], dtype=torch.float64)
+    mk = lambda n, k: ((torch.rand(n, k, generator=g) * 2 - 1) * 0.05).half().to(dev)
+    layer = MoEFFN([mk(2 * N, H) for _ in range(E)] + [mk(2 * Ns, H)], [mk(H, N) for _ in range(E)] + [mk(H, Ns)], qcfg,
+                   num_routed=E)
+    weight_bytes = lambda ws, es: sum(ws[e].B.numel() * ws[e].B.element_size() +
+                                      ws[e].scale_b.numel() * ws[e].scale_b.element_size() for e in es)
+
+    def one(bs: int) -> dict:
+        ids = torch.multinomial((hist / hist.sum()).expand(bs, E), topk, replacement=False, generator=g).to(torch.int32).to(dev)
+        hidden = ((torch.rand(bs, H, generator=g) * 2 - 1)).half().to(dev)
+        wts = torch.softmax(torch.rand(bs, topk, generator=g), dim=1).to(dev)
+        want = layer.forward(hidden, ids, wts).float()
+        gf, df = GraphForward(layer, bs, topk), DecodeForwardWo(layer, bs, topk)
+        graphs = {"graph": _captured(lambda: gf.launch(hidden, ids, wts)), "decode": _captured(lambda: df.launch(hidden, ids, wts))}
+        for gr in graphs.values():
+            gr.replay()
+        torch.cuda.synchronize()
+        tol = 1e-3 * want.abs() + 1e-3 * want.square().mean().sqrt() + 1e-6
+        close = {k: bool(((o.out.float() - want).abs() <= tol).all()) for k, o in (("graph", gf), ("decode", df))}
+        wall, device = (lambda fn: _wall(fn, iters)), (lambda fn: _device(fn, iters))
+        st = _stream(None)
+        f = df.ffn
+        gate_up_k = lambda: nat.check(nat.symbol("mxmoe_moe_decode_gate_up_wo")(
+            df._glu, nat.DT_FP16, _ptr(hidden), bs, topk, E, 1, _ptr(ids), _ptr(df.experts), df.mask1, f.H, f.N, f.Ns,
+            df.layout, _ptr(df.act), _ptr(df.act_shared), _ptr(df.dev_status), st))
+        down_k = lambda: nat.check(nat.symbol("mxmoe_moe_decode_down_wo")(
+            bs, topk, E, 1, _ptr(ids), _ptr(df.experts), df.mask2, f.H, f.N, f.Ns, _ptr(df.act), _ptr(df.act_shared),
+            _ptr(df.y), _ptr(df.ys), _ptr(df.dev_status), st))
+        sides = {"graph_device": lambda: device(graphs["graph"].replay), "decode_device": lambda: device(graphs["decode"].replay),
+                 "graph_wall": lambda: wall(graphs["graph"].replay), "decode_wall": lambda: wall(graphs["decode"].replay),
+                 "decode_gate_up": lambda: device(gate_up_k), "decode_down": lambda: device(down_k),
+                 "combine": lambda: device(lambda: combine_into(df.out, df.y, df.inv_slot, wts, df.ys, topk))}
+        out = {"model": "qwen2_moe", "scheme": "w4a16_w8a8", "bs": bs, "E": E, "topk": topk, "H": H, "N": N, "N_shared": Ns,
+               "graph_gate_up_mode": gf.mode}
+        out.update({k: _stat(v) for k, v in _rounds(sides, rounds).items()})
+        used = sorted(set(ids.flatten().tolist())) + [E]
+        mb = {"gate_up": weight_bytes(layer.w1, used) / 1e6, "down": weight_bytes(layer.w2, used) / 1e6}
+        out["experts_used"] = len(used) - 1
+        out["kinds"] = {"gate_up": sorted({layer.w1[e].q.qcfg for e in used}), "down": sorted({layer.w2[e].q.qcfg for e in used})}
+        out["weight_mb"] = {k: round(v, 2) for k, v in mb.items()}
+        out["implied_tb_s"] = {k: round(mb[k] / out["decode_" + k]["median_us"], 3) for k in mb}  # MB / µs = TB/s
+        out["decode_over_graph_device"] = round(out["decode_device"]["median_us"] / out["graph_device"]["median_us"], 4)
+        out["faster"] = bool(out["decode_device"]["max_us"] < out["graph_device"]["min_us"])
+        out["close_to_eager"] = close
+        out["status"] = {"graph": gf.status(), "decode": df.status()}
         return out
 
     for bs in batches:

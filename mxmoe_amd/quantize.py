@@ -207,7 +207,20 @@ def dequant_weightonly(codes: torch.Tensor, sz: torch.Tensor, bits: int, gsize: 
         s, z = t[..., 0], t[..., 1]
     off = (1 << (bits - 1)) - 1 if sym else 0
     u = codes.to(torch.float64).reshape(N, G, g) - off
-    return (u * s[..., None] + z[..., None]).reshape(N, K).half()  # exact in f64, then one rounding
+    return _f64_to_f16((u * s[..., None] + z[..., None]).reshape(N, K))  # exact in f64, then one rounding
+
+
+def _f64_to_f16(v: torch.Tensor) -> torch.Tensor:
+    """float64 -> fp16 with ONE rounding to nearest even. ``v.half()`` goes through float32 and rounds twice: a value
+    of more than 24 bits (8-bit code x scale + zp) that the first rounding puts on an fp16 tie ends one ulp off.
+    Here the float32 step rounds to odd (truncate, then set the last bit where inexact), which keeps the sticky
+    information, so the second rounding is the correct one."""
+    f = v.float()
+    over = f.double().abs() > v.abs()  # rounded away from zero: step back towards it
+    f = torch.where(over, torch.nextafter(f, torch.zeros_like(f)), f)
+    inexact = f.double() != v
+    f = torch.where(inexact, (f.view(torch.int32) | 1).view(torch.float32), f)
+    return f.half()
 
 
 # ---- OCP MXFP4 (w4a4_g32_sym_MXFP4): e2m1 codes, one e8m0 scale per 32-element block ------------------

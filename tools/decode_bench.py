@@ -10,7 +10,14 @@ topk = 4, H = N = 2880, random codes, scale bytes in [118, 126]), DecodeForwardE
 with the two _ex kernels and the bias combine alone, the weight bytes read and the TB/s they imply. Exits 1 when an
 output is not within the fp16 tolerance of the eager layer (MXFP4 sums depend on their order).
 
-python tools/decode_bench.py [--model qwen2_moe|gpt-oss] [--rounds 4] [--iters 30] [--batches 1,4,16] [--out FILE]
+--model qwen2_moe --scheme w4a16_w8a8: layer 11 with the reference's small-batch scheme instead of LP-1
+(workload.w4a16_w8a8_qconfig: w4a16_g-1_asym + w8a8 per linear, the shared expert included;
+moe_bench.decode_forward_wo_bench), DecodeForwardWo against GraphForward of the same layer, with the two _wo kernels and
+the combine alone, the weight bytes read and the TB/s they imply. Exits 1 when an output is not within the fp16
+tolerance of the eager layer (weight-only sums depend on their order).
+
+python tools/decode_bench.py [--model qwen2_moe|gpt-oss] [--scheme lp1|w4a16_w8a8] [--rounds 4] [--iters 30]
+                             [--batches 1,4,16] [--out FILE]
 """
 from __future__ import annotations
 
@@ -31,9 +38,14 @@ def main():
     ap.add_argument("--batches", default="1,4,16")
     ap.add_argument("--out", default="")
     ap.add_argument("--model", default="qwen2_moe", choices=["qwen2_moe", "gpt-oss"])
+    ap.add_argument("--scheme", default="lp1", choices=["lp1", "w4a16_w8a8"], help="qwen2_moe: the layer's qconfig")
     args = ap.parse_args()
+    if args.model == "gpt-oss" and args.scheme != "lp1":
+        ap.error("--scheme belongs to --model qwen2_moe")
     results = []
-    bench = moe_bench.decode_forward_gptoss_bench if args.model == "gpt-oss" else moe_bench.decode_forward_bench
+    wo = args.scheme == "w4a16_w8a8"
+    bench = moe_bench.decode_forward_gptoss_bench if args.model == "gpt-oss" else \
+        moe_bench.decode_forward_wo_bench if wo else moe_bench.decode_forward_bench
     for r in bench([int(b) for b in args.batches.split(",") if b], args.rounds, args.iters):
         print(json.dumps(r), flush=True)
         results.append(r)
@@ -41,7 +53,7 @@ def main():
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         with open(args.out, "w") as f:
             json.dump(results, f, indent=1)
-    same = "close_to_eager" if args.model == "gpt-oss" else "bit_identical_to_eager"
+    same = "close_to_eager" if args.model == "gpt-oss" or wo else "bit_identical_to_eager"
     if not all(all(r[same].values()) and not any(r["status"].values()) for r in results):
         sys.exit(1)
 

@@ -5,7 +5,7 @@ hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -I include --cuda-device-only -
 
 A kernel is matched by its mangled name, a template's cut behind its template arguments. Per kernel: the .amdhsa_*
 resource lines below, the histogram of all mnemonics, and the instruction text without comments, labels and directives
-(the function number of a branch target removed). Exit status 1 when a kernel has no partner or differs in resources
+(the function number of a branch target and the file-wide counter of a long branch's .Lpost_getpc label removed). Exit status 1 when a kernel has no partner or differs in resources
 or histogram.
 """
 import collections
@@ -21,7 +21,7 @@ def kernels(path):
     for m in re.finditer(r"^\s*\.amdhsa_kernel (\S+)\n(.*?)\.end_amdhsa_kernel", src, flags=re.M | re.S):
         sym, desc = m.group(1), m.group(2)
         start = src.index(f"\n{sym}:") + len(sym) + 2
-        lines = [re.sub(r"\.LBB\d+_", ".LBB_", ln.split(";")[0].strip()) for ln in
+        lines = [re.sub(r"\.Lpost_getpc\d+", ".Lpost_getpc", re.sub(r"\.LBB\d+_", ".LBB_", ln.split(";")[0].strip())) for ln in
                  src[start:src.index(".Lfunc_end", start)].split("\n")]
         lines = [ln for ln in lines if ln and not ln.startswith(".") and not ln.endswith(":")]
         res = tuple(re.search(rf"\.amdhsa_{r} (\S+)", desc).group(1) for r in RESOURCES)
