@@ -940,15 +940,15 @@ static int glu_check(const char* fn, const mxmoe_moe_glu* glu) {
   return MXMOE_GG_OK;
 }
 
-// The two decode entries and their _ex and _wo forms: one body of checks and one launcher each. ex: decode::kEx, the
+// The two decode entries and their _ex and _wo forms: one body of checks and one launcher each. level: decode::kEx, the
 // _ex entry (kind bit 3, the _ex kernels; glu may be NULL: SiLU and no bias), decode::kWo, the _wo entry (kind bits up
-// to 11, the _wo kernels, glu likewise); otherwise glu is NULL and the first entries' kernels run.
-static int decode_gate_up_impl(const char* fn, int ex, const mxmoe_moe_glu* glu, int dtype, const void* hidden, int64_t T,
+// to 11, the _wo kernels, glu likewise); decode::kFirst: glu is NULL and the first entries' kernels run.
+static int decode_gate_up_impl(const char* fn, int level, const mxmoe_moe_glu* glu, int dtype, const void* hidden, int64_t T,
                                int topk, int E, int with_shared, const int32_t* topk_ids,
                                const mxmoe_moe_decode_expert* experts, uint32_t kind_mask, int H, int N, int N_shared,
                                int layout, void* act, void* act_shared, int32_t* status, void* stream) {
   if (int st = dtype_check(fn, "dtype", dtype)) return st;
-  if (int st = decode::kind_mask_check(fn, kind_mask, ex)) return st;
+  if (int st = decode::kind_mask_check(fn, kind_mask, level)) return st;
   if (int st = decode::sizes_check(fn, T, topk, E, with_shared, H, N, N_shared)) return st;
   if (layout != MXMOE_DECODE_GU_PLAIN && layout != MXMOE_DECODE_GU_INTERLEAVED)
     return fail(MXMOE_GG_ERR_INVALID, "%s: layout must be MXMOE_DECODE_GU_PLAIN or MXMOE_DECODE_GU_INTERLEAVED (got %d)", fn,
@@ -964,7 +964,7 @@ static int decode_gate_up_impl(const char* fn, int ex, const mxmoe_moe_glu* glu,
   if (T == 0) return MXMOE_GG_OK;
   if (!hidden || !topk_ids || !experts || !act || (with_shared && !act_shared))
     return fail(MXMOE_GG_ERR_INVALID, "%s: NULL pointer", fn);
-  decode::ArgsWo a{};
+  decode::Args a{};
   a.src = a.src_shared = hidden;
   a.ids = topk_ids;
   a.experts = experts;
@@ -975,7 +975,6 @@ static int decode_gate_up_impl(const char* fn, int ex, const mxmoe_moe_glu* glu,
   a.K = a.K_shared = H;
   a.C = N, a.C_shared = with_shared ? N_shared : 0;
   a.layout = layout, a.src_bf16 = dtype == MXMOE_DT_BF16, a.kind_mask = kind_mask;
-  if (!ex) return decode::launch<false>(static_cast<const decode::Args&>(a), stream);
   a.glu = glu && glu->act == MXMOE_GLU_SWIGLU_CLAMP ? kGluSwigluClamp : kGluSilu;
   if (glu) {
     a.bias_routed = static_cast<const _Float16*>(glu->bias_routed);
@@ -983,14 +982,13 @@ static int decode_gate_up_impl(const char* fn, int ex, const mxmoe_moe_glu* glu,
     a.c = -(glu->alpha * 1.4426950408889634f);
     a.limit = glu->limit;
   }
-  if (ex == decode::kWo) return decode::launch<false>(static_cast<const decode::ArgsWo&>(a), stream);
-  return decode::launch<false>(static_cast<const decode::ArgsEx&>(a), stream);
+  return decode::launch<false>(a, level, stream);
 }
 
-static int decode_down_impl(const char* fn, int ex, int64_t T, int topk, int E, int with_shared, const int32_t* topk_ids,
+static int decode_down_impl(const char* fn, int level, int64_t T, int topk, int E, int with_shared, const int32_t* topk_ids,
                             const mxmoe_moe_decode_expert* experts, uint32_t kind_mask, int H, int N, int N_shared,
                             const void* act, const void* act_shared, void* y, void* ys, int32_t* status, void* stream) {
-  if (int st = decode::kind_mask_check(fn, kind_mask, ex)) return st;
+  if (int st = decode::kind_mask_check(fn, kind_mask, level)) return st;
   if (int st = decode::sizes_check(fn, T, topk, E, with_shared, H, N, N_shared)) return st;
   if (!aligned16(act) || !aligned16(act_shared) || !aligned16(y) || !aligned16(ys) || ((uintptr_t)topk_ids & 3) ||
       ((uintptr_t)experts & 7) || ((uintptr_t)status & 3))
@@ -998,7 +996,7 @@ static int decode_down_impl(const char* fn, int ex, int64_t T, int topk, int E, 
   if (T == 0) return MXMOE_GG_OK;
   if (!act || !topk_ids || !experts || !y || (with_shared && (!act_shared || !ys)))
     return fail(MXMOE_GG_ERR_INVALID, "%s: NULL pointer", fn);
-  decode::ArgsWo a{};
+  decode::Args a{};
   a.src = act;
   a.src_shared = act_shared;
   a.ids = topk_ids;
@@ -1010,9 +1008,7 @@ static int decode_down_impl(const char* fn, int ex, int64_t T, int topk, int E, 
   a.K = N, a.K_shared = with_shared ? N_shared : N;
   a.C = a.C_shared = H;
   a.kind_mask = kind_mask;
-  if (!ex) return decode::launch<true>(static_cast<const decode::Args&>(a), stream);
-  if (ex == decode::kWo) return decode::launch<true>(static_cast<const decode::ArgsWo&>(a), stream);
-  return decode::launch<true>(static_cast<const decode::ArgsEx&>(a), stream);
+  return decode::launch<true>(a, level, stream);
 }
 
 extern "C" {

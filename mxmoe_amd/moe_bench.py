@@ -206,6 +206,87 @@ def graph_forward_bench(batches: Sequence[int] = (128,), model: str = "qwen2_moe
         yield one(bs)
 
 
+def _decode_bench(layer: MoEFFN, cls, call, rounds: int, iters: int, head: dict, compare: str, weight_bytes,
+                  plain: Optional[MoEFFN] = None, report_used: bool = True) -> dict:
+    """One batch size of a decode bench: ``cls(layer)`` against ``GraphForward(layer)`` on ``call`` = (hidden, ids,
+    wts), both captured and replayed, the sides alternating over rounds. Compared with the eager layer bit for bit
+    (``compare`` = "bit_identical_to_eager") or within the fp16 GroupGEMM tolerance 1e-3 |ref| + 1e-3 rms(ref)
+    ("close_to_eager": sums that depend on their order). Timed: device and wall time of each graph, the class's two
+    entries alone and its combine; ``plain``: the same layer in the plain gate_up layout as a third side (LP-1).
+    Reported: ``weight_bytes(weights, experts)`` of the experts the ids name (and the shared one), with ``report_used``
+    also their number and the TB/s the two entries imply; ``faster`` — the decode graph's device median, max over
+    rounds, below GraphForward's min over rounds — and the status words."""
+    hidden, ids, wts = call
+    bs, topk = ids.shape
+    E, shared = layer.E, int(layer.has_shared)
+    want = layer.forward(hidden, ids, wts)
+    objs = {"graph": GraphForward(layer, bs, topk), "decode": cls(layer, bs, topk)}
+    if plain is not None:
+        objs["decode_plain"] = cls(plain, bs, topk)
+    gf, df = objs["graph"], objs["decode"]
+    graphs = {k: _captured(lambda o=o: o.launch(hidden, ids, wts)) for k, o in objs.items()}
+    for gr in graphs.values():
+        gr.replay()
+    torch.cuda.synchronize()
+    if compare == "bit_identical_to_eager":
+        same = {k: bool(torch.equal(o.out.view(torch.int16), want.view(torch.int16))) for k, o in objs.items()}
+    else:
+        want = want.float()
+        tol = 1e-3 * want.abs() + 1e-3 * want.square().mean().sqrt() + 1e-6
+        same = {k: bool(((o.out.float() - want).abs() <= tol).all()) for k, o in objs.items()}
+    wall, device = (lambda fn: _wall(fn, iters)), (lambda fn: _device(fn, iters))
+    st, glu = _stream(None), ((df._glu,) if df.TAKES_GLU else ())
+    gate_up_k = lambda: nat.check(nat.symbol(df.ENTRIES[0])(
+        *glu, nat.DT_FP16, _ptr(hidden), bs, topk, E, shared, _ptr(ids), _ptr(df.experts), df.mask1, layer.H, layer.N,
+        layer.Ns, df.layout, _ptr(df.act), _ptr(df.act_shared), _ptr(df.dev_status), st))
+    down_k = lambda: nat.check(nat.symbol(df.ENTRIES[1])(
+        bs, topk, E, shared, _ptr(ids), _ptr(df.experts), df.mask2, layer.H, layer.N, layer.Ns, _ptr(df.act),
+        _ptr(df.act_shared), _ptr(df.y), _ptr(df.ys), _ptr(df.dev_status), st))
+    if df._glu is not None:  # the bias combine, as DecodeForwardEx.launch calls it
+        combine = {"combine_bias": lambda: device(lambda: _launch_combine(df.out, df.y, df.inv_slot, ids.view(-1), wts, None, None,
+                                                                          topk, None, layer.down_bias))}
+    else:
+        combine = {"combine": lambda: device(lambda: combine_into(df.out, df.y, df.inv_slot, wts, df.ys, topk))}
+    sides = {k + "_device": (lambda gr=gr: device(gr.replay)) for k, gr in graphs.items()}
+    sides.update({"graph_wall": lambda: wall(graphs["graph"].replay), "decode_wall": lambda: wall(graphs["decode"].replay),
+                  "decode_gate_up": lambda: device(gate_up_k), "decode_down": lambda: device(down_k)}, **combine)
+    out = dict(head, graph_gate_up_mode=gf.mode)
+    out.update({k: _stat(v) for k, v in _rounds(sides, rounds).items()})
+    used = sorted(set(ids.flatten().tolist())) + ([E] if shared else [])
+    mb = {"gate_up": weight_bytes(layer.w1, used) / 1e6, "down": weight_bytes(layer.w2, used) / 1e6}
+    if report_used:
+        out["experts_used"] = len(used) - shared
+    out["weight_mb"] = {k: round(v, 2) for k, v in mb.items()}
+    if report_used:
+        out["implied_tb_s"] = {k: round(mb[k] / out["decode_" + k]["median_us"], 3) for k in mb}  # MB / µs = TB/s
+    out["decode_over_graph_device"] = round(out["decode_device"]["median_us"] / out["graph_device"]["median_us"], 4)
+    out["faster"] = bool(out["decode_device"]["max_us"] < out["graph_device"]["min_us"])
+    out[compare] = same
+    out["status"] = {"graph": gf.status(), "decode": df.status() | (objs["decode_plain"].status() if plain is not None else 0)}
+    return out
+
+
+def _qwen2_decode_layer(qconfig, g, dev: str):
+    """qwen2_moe layer 11 under ``qconfig`` with random weights: (gate_up, down, qcfg, routing histogram, E, H, N, Ns)"""
+    shapes = load_workload(qwen2_layer11_workload(8192, qconfig=qconfig))["layer-11"]
+    E = len(shapes["gate_up"]) - 1
+    H = shapes["gate_up"][0].K
+    N, Ns = shapes["down"][0].K, shapes["down"][-1].K
+    qcfg = [(QParams(a.a_bits, a.w_bits, a.gsize, a.sym), QParams(b.a_bits, b.w_bits, b.gsize, b.sym))
+            for a, b in zip(shapes["gate_up"], shapes["down"])]
+    hist = torch.tensor([max(s.M, 1) for s in shapes["gate_up"][:E]], dtype=torch.float64)
+    mk = lambda n, k: ((torch.rand(n, k, generator=g) * 2 - 1) * 0.05).half().to(dev)
+    gate_up, down = [mk(2 * N, H) for _ in range(E)] + [mk(2 * Ns, H)], [mk(H, N) for _ in range(E)] + [mk(H, Ns)]
+    return gate_up, down, qcfg, hist, E, H, N, Ns
+
+
+def _qwen2_decode_call(g, hist, bs: int, E: int, topk: int, H: int, dev: str):
+    ids = torch.multinomial((hist / hist.sum()).expand(bs, E), topk, replacement=False, generator=g).to(torch.int32).to(dev)
+    hidden = ((torch.rand(bs, H, generator=g) * 2 - 1)).half().to(dev)
+    wts = torch.softmax(torch.rand(bs, topk, generator=g), dim=1).to(dev)
+    return hidden, ids, wts
+
+
 def decode_forward_bench(batches: Sequence[int] = (1, 4, 16), rounds: int = 4, iters: int = 30):
     """qwen2_moe layer 11 (LP-1 mixed w4a4 + w8a8, random weights, routing drawn from the committed histogram) at
     decode sizes, ``DecodeForward`` against ``GraphForward``, both replayed from captured graphs in one process with
@@ -213,193 +294,62 @@ def decode_forward_bench(batches: Sequence[int] = (1, 4, 16), rounds: int = 4, i
     decode kernels alone, the plain-layout DecodeForward (the same kernels on [gate; up] rows), and the combine. Per
     side the median of the rounds' medians with min / max (µs). ``faster``: the bar — DecodeForward's device median,
     max over rounds, below GraphForward's min over rounds."""
-    shapes, topk = load_workload(qwen2_layer11_workload(8192, qconfig=mixed_qconfig_lp1()))["layer-11"], 4
-    E = len(shapes["gate_up"]) - 1
-    H = shapes["gate_up"][0].K
-    N, Ns = shapes["down"][0].K, shapes["down"][-1].K
-    qcfg = [(QParams(a.a_bits, a.w_bits, a.gsize, a.sym), QParams(b.a_bits, b.w_bits, b.gsize, b.sym))
-            for a, b in zip(shapes["gate_up"], shapes["down"])]
-    dev = "cuda"
-    g = torch.Generator().manual_seed(0)
-    hist = torch.tensor([max(s.M, 1) for s in shapes["gate_up"][:E]], dtype=torch.float64)
-    mk = lambda n, k: ((torch.rand(n, k, generator=g) * 2 - 1) * 0.05).half().to(dev)
-    gate_up, down = [mk(2 * N, H) for _ in range(E)] + [mk(2 * Ns, H)], [mk(H, N) for _ in range(E)] + [mk(H, Ns)]
+    dev, topk, g = "cuda", 4, torch.Generator().manual_seed(0)
+    gate_up, down, qcfg, hist, E, H, N, Ns = _qwen2_decode_layer(mixed_qconfig_lp1(), g, dev)
     layer = MoEFFN(gate_up, down, qcfg, num_routed=E)
     plain = MoEFFN(gate_up, down, qcfg, num_routed=E, fuse_silu=False)
     del gate_up, down
     weight_bytes = lambda ws, es: sum(ws[e].B.numel() * ws[e].B.element_size() for e in es)
-
-    def one(bs: int) -> dict:
-        ids = torch.multinomial((hist / hist.sum()).expand(bs, E), topk, replacement=False, generator=g).to(torch.int32).to(dev)
-        hidden = ((torch.rand(bs, H, generator=g) * 2 - 1)).half().to(dev)
-        wts = torch.softmax(torch.rand(bs, topk, generator=g), dim=1).to(dev)
-        want = layer.forward(hidden, ids, wts)
-        gf, df, dp = GraphForward(layer, bs, topk), DecodeForward(layer, bs, topk), DecodeForward(plain, bs, topk)
-        graphs = {"graph": _captured(lambda: gf.launch(hidden, ids, wts)), "decode": _captured(lambda: df.launch(hidden, ids, wts)),
-                  "decode_plain": _captured(lambda: dp.launch(hidden, ids, wts))}
-        for gr in graphs.values():
-            gr.replay()
-        torch.cuda.synchronize()
-        same = {k: bool(torch.equal(o.out.view(torch.int16), want.view(torch.int16)))
-                for k, o in (("graph", gf), ("decode", df), ("decode_plain", dp))}
-        wall, device = (lambda fn: _wall(fn, iters)), (lambda fn: _device(fn, iters))
-        lib, st = nat.lib(), _stream(None)
-        f = df.ffn
-        gate_up_k = lambda: nat.check(lib.mxmoe_moe_decode_gate_up(
-            nat.DT_FP16, _ptr(hidden), bs, topk, E, 1, _ptr(ids), _ptr(df.experts), df.mask1, f.H, f.N, f.Ns, df.layout,
-            _ptr(df.act), _ptr(df.act_shared), _ptr(df.dev_status), st))
-        down_k = lambda: nat.check(lib.mxmoe_moe_decode_down(
-            bs, topk, E, 1, _ptr(ids), _ptr(df.experts), df.mask2, f.H, f.N, f.Ns, _ptr(df.act), _ptr(df.act_shared),
-            _ptr(df.y), _ptr(df.ys), _ptr(df.dev_status), st))
-        sides = {"graph_device": lambda: device(graphs["graph"].replay), "decode_device": lambda: device(graphs["decode"].replay),
-                 "decode_plain_device": lambda: device(graphs["decode_plain"].replay),
-                 "graph_wall": lambda: wall(graphs["graph"].replay), "decode_wall": lambda: wall(graphs["decode"].replay),
-                 "decode_gate_up": lambda: device(gate_up_k), "decode_down": lambda: device(down_k),
-                 "combine": lambda: device(lambda: combine_into(df.out, df.y, df.inv_slot, wts, df.ys, topk))}
-        out = {"model": "qwen2_moe", "bs": bs, "E": E, "topk": topk, "H": H, "N": N, "N_shared": Ns,
-               "graph_gate_up_mode": gf.mode}
-        out.update({k: _stat(v) for k, v in _rounds(sides, rounds).items()})
-        used = sorted(set(ids.flatten().tolist())) + [E]
-        out["weight_mb"] = {"gate_up": round(weight_bytes(layer.w1, used) / 1e6, 2), "down": round(weight_bytes(layer.w2, used) / 1e6, 2)}
-        out["decode_over_graph_device"] = round(out["decode_device"]["median_us"] / out["graph_device"]["median_us"], 4)
-        out["faster"] = bool(out["decode_device"]["max_us"] < out["graph_device"]["min_us"])
-        out["bit_identical_to_eager"] = same
-        out["status"] = {"graph": gf.status(), "decode": df.status() | dp.status()}
-        return out
-
-    for bs in batches:
-        yield one(bs)
+    for bs in batches:  # (a generator: a caller can print each size as it completes)
+        head = {"model": "qwen2_moe", "bs": bs, "E": E, "topk": topk, "H": H, "N": N, "N_shared": Ns}
+        yield _decode_bench(layer, DecodeForward, _qwen2_decode_call(g, hist, bs, E, topk, H, dev), rounds, iters, head,
+                            "bit_identical_to_eager", weight_bytes, plain=plain, report_used=False)
 
 
 def decode_forward_wo_bench(batches: Sequence[int] = (1, 4, 16), rounds: int = 4, iters: int = 30):
     """qwen2_moe layer 11 with the reference's small-batch scheme (``w4a16_w8a8_qconfig``: w4a16_g-1_asym + w8a8 per
     linear, the shared expert included; random weights, routing drawn from the committed histogram) at decode sizes,
-    ``DecodeForwardWo`` against ``GraphForward`` of the same layer, as ``decode_forward_bench`` measures the LP-1 layer:
-    both replayed from captured graphs in one process, the sides alternating over rounds (yields one dict per batch
-    size). Also the two _wo kernels and the combine alone, the weight bytes (codes and scale buffers of the experts the
-    ids name, and the shared expert's) and the TB/s they imply. ``faster``: DecodeForwardWo's device median, max over
-    rounds, below GraphForward's min over rounds. Weight-only sums depend on their order, so the outputs are compared
-    with the eager layer's within the fp16 GroupGEMM tolerance (1e-3 |ref| + 1e-3 rms(ref)), not bit for bit."""
-    shapes, topk = load_workload(qwen2_layer11_workload(8192, qconfig=w4a16_w8a8_qconfig()))["layer-11"], 4
-    E = len(shapes["gate_up"]) - 1
-    H = shapes["gate_up"][0].K
-    N, Ns = shapes["down"][0].K, shapes["down"][-1].K
-    qcfg = [(QParams(a.a_bits, a.w_bits, a.gsize, a.sym), QParams(b.a_bits, b.w_bits, b.gsize, b.sym))
-            for a, b in zip(shapes["gate_up"], shapes["down"])]
-    dev = "cuda"
-    g = torch.Generator().manual_seed(0)
-    hist = torch.tensor([max(s.M, 1) for s in shapes["gate_up"][:E]], dtype=torch.float64)
-    mk = lambda n, k: ((torch.rand(n, k, generator=g) * 2 - 1) * 0.05).half().to(dev)
-    layer = MoEFFN([mk(2 * N, H) for _ in range(E)] + [mk(2 * Ns, H)], [mk(H, N) for _ in range(E)] + [mk(H, Ns)], qcfg,
-                   num_routed=E)
+    ``DecodeForwardWo`` against ``GraphForward`` of the same layer, as ``decode_forward_bench`` measures the LP-1 layer
+    (yields one dict per batch size). Also the weight bytes (codes and scale buffers of the experts the ids name, and
+    the shared expert's), the TB/s they imply and the kinds among them. Weight-only sums depend on their order, so the
+    outputs are compared with the eager layer's within the fp16 GroupGEMM tolerance, not bit for bit."""
+    dev, topk, g = "cuda", 4, torch.Generator().manual_seed(0)
+    gate_up, down, qcfg, hist, E, H, N, Ns = _qwen2_decode_layer(w4a16_w8a8_qconfig(), g, dev)
+    layer = MoEFFN(gate_up, down, qcfg, num_routed=E)
+    del gate_up, down
     weight_bytes = lambda ws, es: sum(ws[e].B.numel() * ws[e].B.element_size() +
                                       ws[e].scale_b.numel() * ws[e].scale_b.element_size() for e in es)
-
-    def one(bs: int) -> dict:
-        ids = torch.multinomial((hist / hist.sum()).expand(bs, E), topk, replacement=False, generator=g).to(torch.int32).to(dev)
-        hidden = ((torch.rand(bs, H, generator=g) * 2 - 1)).half().to(dev)
-        wts = torch.softmax(torch.rand(bs, topk, generator=g), dim=1).to(dev)
-        want = layer.forward(hidden, ids, wts).float()
-        gf, df = GraphForward(layer, bs, topk), DecodeForwardWo(layer, bs, topk)
-        graphs = {"graph": _captured(lambda: gf.launch(hidden, ids, wts)), "decode": _captured(lambda: df.launch(hidden, ids, wts))}
-        for gr in graphs.values():
-            gr.replay()
-        torch.cuda.synchronize()
-        tol = 1e-3 * want.abs() + 1e-3 * want.square().mean().sqrt() + 1e-6
-        close = {k: bool(((o.out.float() - want).abs() <= tol).all()) for k, o in (("graph", gf), ("decode", df))}
-        wall, device = (lambda fn: _wall(fn, iters)), (lambda fn: _device(fn, iters))
-        st = _stream(None)
-        f = df.ffn
-        gate_up_k = lambda: nat.check(nat.symbol("mxmoe_moe_decode_gate_up_wo")(
-            df._glu, nat.DT_FP16, _ptr(hidden), bs, topk, E, 1, _ptr(ids), _ptr(df.experts), df.mask1, f.H, f.N, f.Ns,
-            df.layout, _ptr(df.act), _ptr(df.act_shared), _ptr(df.dev_status), st))
-        down_k = lambda: nat.check(nat.symbol("mxmoe_moe_decode_down_wo")(
-            bs, topk, E, 1, _ptr(ids), _ptr(df.experts), df.mask2, f.H, f.N, f.Ns, _ptr(df.act), _ptr(df.act_shared),
-            _ptr(df.y), _ptr(df.ys), _ptr(df.dev_status), st))
-        sides = {"graph_device": lambda: device(graphs["graph"].replay), "decode_device": lambda: device(graphs["decode"].replay),
-                 "graph_wall": lambda: wall(graphs["graph"].replay), "decode_wall": lambda: wall(graphs["decode"].replay),
-                 "decode_gate_up": lambda: device(gate_up_k), "decode_down": lambda: device(down_k),
-                 "combine": lambda: device(lambda: combine_into(df.out, df.y, df.inv_slot, wts, df.ys, topk))}
-        out = {"model": "qwen2_moe", "scheme": "w4a16_w8a8", "bs": bs, "E": E, "topk": topk, "H": H, "N": N, "N_shared": Ns,
-               "graph_gate_up_mode": gf.mode}
-        out.update({k: _stat(v) for k, v in _rounds(sides, rounds).items()})
-        used = sorted(set(ids.flatten().tolist())) + [E]
-        mb = {"gate_up": weight_bytes(layer.w1, used) / 1e6, "down": weight_bytes(layer.w2, used) / 1e6}
-        out["experts_used"] = len(used) - 1
-        out["kinds"] = {"gate_up": sorted({layer.w1[e].q.qcfg for e in used}), "down": sorted({layer.w2[e].q.qcfg for e in used})}
-        out["weight_mb"] = {k: round(v, 2) for k, v in mb.items()}
-        out["implied_tb_s"] = {k: round(mb[k] / out["decode_" + k]["median_us"], 3) for k in mb}  # MB / µs = TB/s
-        out["decode_over_graph_device"] = round(out["decode_device"]["median_us"] / out["graph_device"]["median_us"], 4)
-        out["faster"] = bool(out["decode_device"]["max_us"] < out["graph_device"]["min_us"])
-        out["close_to_eager"] = close
-        out["status"] = {"graph": gf.status(), "decode": df.status()}
-        return out
-
     for bs in batches:
-        yield one(bs)
+        head = {"model": "qwen2_moe", "scheme": "w4a16_w8a8", "bs": bs, "E": E, "topk": topk, "H": H, "N": N, "N_shared": Ns}
+        call = _qwen2_decode_call(g, hist, bs, E, topk, H, dev)
+        out = _decode_bench(layer, DecodeForwardWo, call, rounds, iters, head, "close_to_eager", weight_bytes)
+        used = sorted(set(call[1].flatten().tolist())) + [E]
+        out["kinds"] = {"gate_up": sorted({layer.w1[e].q.qcfg for e in used}), "down": sorted({layer.w2[e].q.qcfg for e in used})}
+        yield out
 
 
 def decode_forward_gptoss_bench(batches: Sequence[int] = (1, 4, 16), rounds: int = 4, iters: int = 30, E: int = 32,
                                 topk: int = 4, H: int = 2880, N: int = 2880):
     """A synthetic gpt-oss layer (``gptoss_layer``: E = 32, top-4, H = N = 2880 padded to 2944, random e2m1 codes, scale
     bytes in [118, 126], biases in +-0.5, the clamped SwiGLU) at decode sizes, ``DecodeForwardEx`` against
-    ``GraphForward`` of the same layer, as ``decode_forward_bench`` measures the qwen2_moe layer: both replayed from
-    captured graphs in one process, the sides alternating over rounds (yields one dict per batch size). Also the two
-    decode kernels and the bias combine alone, the weight bytes (codes and scale bytes of the experts the ids name) and
-    the TB/s they imply. ``faster``: DecodeForwardEx's device median, max over rounds, below GraphForward's min over
-    rounds. MXFP4 sums depend on their order, so the outputs are compared with the eager layer's within the fp16
-    GroupGEMM tolerance (1e-3 |ref| + 1e-3 rms(ref)), not bit for bit."""
+    ``GraphForward`` of the same layer, as ``decode_forward_bench`` measures the qwen2_moe layer (yields one dict per
+    batch size), with the bias combine alone. Also the weight bytes (codes and scale bytes of the experts the ids
+    name) and the TB/s they imply. MXFP4 sums depend on their order, so the outputs are compared with the eager
+    layer's within the fp16 GroupGEMM tolerance, not bit for bit."""
     dev = "cuda"
     g = torch.Generator(device=dev).manual_seed(0)
     u8 = lambda *shape, lo=0, hi=256: torch.randint(lo, hi, shape, generator=g, device=dev, dtype=torch.uint8)
     bias = lambda *shape: torch.rand(*shape, generator=g, device=dev) - 0.5
     layer = gptoss_layer(u8(E, 2 * N, H // 32, 16), u8(E, 2 * N, H // 32, lo=118, hi=127), bias(E, 2 * N),
                          u8(E, H, N // 32, 16), u8(E, H, N // 32, lo=118, hi=127), bias(E, H))
-    Hp, Np = layer.H, layer.N
     weight_bytes = lambda ws, es: sum(ws[e].B.numel() + ws[e].scale_b.numel() for e in es)
-
-    def one(bs: int) -> dict:
+    for bs in batches:
         ids = torch.stack([torch.randperm(E, generator=g, device=dev)[:topk] for _ in range(bs)]).to(torch.int32)
-        hidden = torch.zeros(bs, Hp, dtype=torch.float16, device=dev)
+        hidden = torch.zeros(bs, layer.H, dtype=torch.float16, device=dev)
         hidden[:, :H] = (torch.randn(bs, H, generator=g, device=dev) * 0.5).half()
         wts = torch.softmax(torch.rand(bs, topk, generator=g, device=dev), dim=1)
-        want = layer.forward(hidden, ids, wts).float()
-        gf, df = GraphForward(layer, bs, topk), DecodeForwardEx(layer, bs, topk)
-        graphs = {"graph": _captured(lambda: gf.launch(hidden, ids, wts)), "decode": _captured(lambda: df.launch(hidden, ids, wts))}
-        for gr in graphs.values():
-            gr.replay()
-        torch.cuda.synchronize()
-        tol = 1e-3 * want.abs() + 1e-3 * want.square().mean().sqrt() + 1e-6
-        close = {k: bool(((o.out.float() - want).abs() <= tol).all()) for k, o in (("graph", gf), ("decode", df))}
-        wall, device = (lambda fn: _wall(fn, iters)), (lambda fn: _device(fn, iters))
-        st = _stream(None)
-        gate_up_k = lambda: nat.check(nat.symbol("mxmoe_moe_decode_gate_up_ex")(
-            df._glu, nat.DT_FP16, _ptr(hidden), bs, topk, E, 0, _ptr(ids), _ptr(df.experts), df.mask1, Hp, Np, 0, df.layout,
-            _ptr(df.act), None, _ptr(df.dev_status), st))
-        down_k = lambda: nat.check(nat.symbol("mxmoe_moe_decode_down_ex")(
-            bs, topk, E, 0, _ptr(ids), _ptr(df.experts), df.mask2, Hp, Np, 0, _ptr(df.act), None, _ptr(df.y), None,
-            _ptr(df.dev_status), st))
-        combine_k = lambda: _launch_combine(df.out, df.y, df.inv_slot, ids.view(-1), wts, None, None, topk, None, layer.down_bias)
-        sides = {"graph_device": lambda: device(graphs["graph"].replay), "decode_device": lambda: device(graphs["decode"].replay),
-                 "graph_wall": lambda: wall(graphs["graph"].replay), "decode_wall": lambda: wall(graphs["decode"].replay),
-                 "decode_gate_up": lambda: device(gate_up_k), "decode_down": lambda: device(down_k),
-                 "combine_bias": lambda: device(combine_k)}
-        out = {"model": "gpt-oss layer (synthetic)", "bs": bs, "E": E, "topk": topk, "H": Hp, "N": Np,
-               "graph_gate_up_mode": gf.mode}
-        out.update({k: _stat(v) for k, v in _rounds(sides, rounds).items()})
-        used = sorted(set(ids.flatten().tolist()))
-        mb = {"gate_up": weight_bytes(layer.w1, used) / 1e6, "down": weight_bytes(layer.w2, used) / 1e6}
-        out["experts_used"] = len(used)
-        out["weight_mb"] = {k: round(v, 2) for k, v in mb.items()}
-        out["implied_tb_s"] = {k: round(mb[k] / out["decode_" + k]["median_us"], 3) for k in mb}  # MB / µs = TB/s
-        out["decode_over_graph_device"] = round(out["decode_device"]["median_us"] / out["graph_device"]["median_us"], 4)
-        out["faster"] = bool(out["decode_device"]["max_us"] < out["graph_device"]["min_us"])
-        out["close_to_eager"] = close
-        out["status"] = {"graph": gf.status(), "decode": df.status()}
-        return out
-
-    for bs in batches:
-        yield one(bs)
+        head = {"model": "gpt-oss layer (synthetic)", "bs": bs, "E": E, "topk": topk, "H": layer.H, "N": layer.N}
+        yield _decode_bench(layer, DecodeForwardEx, (hidden, ids, wts), rounds, iters, head, "close_to_eager", weight_bytes)
 
 
 def gptoss_bench(batches: Sequence[int] = (1, 16, 128, 512, 2048), act_bits: int = 16, rounds: int = 4, iters: int = 20,

@@ -11,25 +11,18 @@ import torch
 from mxmoe_amd import _native as nat
 from mxmoe_amd import moe
 from mxmoe_amd.groupgemm import FP16, W4A4, W4A4_G128, W4A4_MXFP4, W8A8
+from tests._decode_util import cpu_ffn, entry_down, entry_gate_up, err
 
 INVALID, UNSUPPORTED, OK = nat.MXMOE_GG_ERR_INVALID, nat.MXMOE_GG_ERR_UNSUPPORTED, nat.MXMOE_GG_OK
 ALL_KINDS = 0b111
 
 
-def _err():
-    return nat.lib().mxmoe_gg_last_error()
+def _gate_up(**kw):
+    return entry_gate_up("first", **dict(dict(mask=ALL_KINDS), **kw))
 
 
-def _gate_up(dtype=nat.DT_FP16, hidden=16, T=4, topk=2, E=4, with_shared=1, ids=16, experts=16, mask=ALL_KINDS, H=256, N=128,
-             Ns=256, layout=nat.DECODE_GU_PLAIN, act=16, act_shared=16, status=None):
-    return nat.symbol("mxmoe_moe_decode_gate_up")(dtype, hidden, T, topk, E, with_shared, ids, experts, mask, H, N, Ns, layout,
-                                                 act, act_shared, status, None)
-
-
-def _down(T=4, topk=2, E=4, with_shared=1, ids=16, experts=16, mask=ALL_KINDS, H=256, N=128, Ns=256, act=16, act_shared=16,
-          y=16, ys=16, status=None):
-    return nat.symbol("mxmoe_moe_decode_down")(T, topk, E, with_shared, ids, experts, mask, H, N, Ns, act, act_shared, y, ys,
-                                              status, None)
+def _down(**kw):
+    return entry_down("first", **dict(dict(mask=ALL_KINDS), **kw))
 
 
 ENTRIES = [(_gate_up, b"mxmoe_moe_decode_gate_up"), (_down, b"mxmoe_moe_decode_down")]
@@ -55,7 +48,7 @@ def test_limits_are_refused_before_any_hip_call(call, name):
                dict(ids=2), dict(experts=4), dict(status=2), dict(mask=0), dict(ids=None), dict(experts=None),
                dict(act=None), dict(act_shared=None)):
         assert call(**kw) == INVALID, kw
-        assert name in _err(), kw
+        assert name in err(), kw
     assert call(T=0) == OK  # no launch
     assert call(T=0, with_shared=0, Ns=0, act_shared=None) == OK  # N_shared is not looked at without a shared expert
     assert call(T=0, H=16384, N=16384, Ns=16384, topk=16, E=16) == OK
@@ -67,7 +60,7 @@ def test_unknown_kind_is_unsupported(call, name):
     empty batch."""
     for mask in (1 << 3, ALL_KINDS | 1 << 4, 1 << 31):
         assert call(mask=mask) == UNSUPPORTED, mask
-        assert name in _err() and b"kind" in _err()
+        assert name in err() and b"kind" in err()
         assert call(mask=mask, T=0) == UNSUPPORTED
     for mask in (1, 2, 4, 3, 6, 7):
         assert call(mask=mask, T=0) == OK
@@ -77,26 +70,19 @@ def test_entry_specific_refusals():
     """★ gate_up: an unknown dtype, an unknown layout, a misaligned hidden; down: a misaligned or missing y / ys."""
     for kw in (dict(dtype=2), dict(dtype=-1), dict(layout=2), dict(layout=-1), dict(hidden=8), dict(hidden=None)):
         assert _gate_up(**kw) == INVALID, kw
-        assert b"mxmoe_moe_decode_gate_up" in _err(), kw
+        assert b"mxmoe_moe_decode_gate_up" in err(), kw
     assert _gate_up(dtype=2, T=0) == INVALID  # (before the empty-batch return)
     assert _gate_up(dtype=nat.DT_BF16, layout=nat.DECODE_GU_INTERLEAVED, T=0) == OK
     for kw in (dict(y=8), dict(ys=4), dict(y=None), dict(ys=None)):
         assert _down(**kw) == INVALID, kw
-        assert b"mxmoe_moe_decode_down" in _err(), kw
+        assert b"mxmoe_moe_decode_down" in err(), kw
     assert _down(with_shared=0, ys=None, act_shared=None, T=0) == OK
-
-
-def _ffn(qcfg, E=2, H=256, N=128, Ns=128, **kw):
-    g = torch.Generator().manual_seed(5)
-    mk = lambda n, k: ((torch.rand(n, k, generator=g) * 2 - 1) * 0.2).half()
-    return moe.MoEFFN([mk(2 * N, H) for _ in range(E)] + [mk(2 * Ns, H)], [mk(H, N) for _ in range(E)] + [mk(H, Ns)], qcfg,
-                      num_routed=E, **kw)
 
 
 def test_decode_forward_value_errors():
     """★ DecodeForward refuses, naming the reason: T = 17 (and 0), an MX qcfg, g128, a layer with a bias, a topk beyond
     the experts, a dtype that is neither fp16 nor bf16."""
-    ok = _ffn([(W8A8, W4A4), (FP16, W8A8), (W4A4, FP16)])
+    ok = cpu_ffn([(W8A8, W4A4), (FP16, W8A8), (W4A4, FP16)])
     with pytest.raises(ValueError, match="T = 17"):
         moe.DecodeForward(ok, 17, 2)
     with pytest.raises(ValueError, match="T = 0"):
@@ -108,13 +94,13 @@ def test_decode_forward_value_errors():
     with pytest.raises(ValueError, match="dtype"):
         moe.DecodeForward(ok, 4, 2, dtype=torch.float32)
     with pytest.raises(ValueError, match="w4a4_g32_sym_MXFP4"):
-        moe.DecodeForward(_ffn([(W8A8, W8A8), (W4A4_MXFP4, W4A4_MXFP4), (W8A8, W8A8)]), 4, 2)
+        moe.DecodeForward(cpu_ffn([(W8A8, W8A8), (W4A4_MXFP4, W4A4_MXFP4), (W8A8, W8A8)]), 4, 2)
     with pytest.raises(ValueError, match="w4a4_g128_sym"):
-        moe.DecodeForward(_ffn([(W8A8, W8A8), (W8A8, W4A4_G128), (W8A8, W8A8)]), 4, 2)
-    biased = _ffn([(W8A8, W8A8)] * 3, down_bias=[torch.zeros(256) for _ in range(3)])
+        moe.DecodeForward(cpu_ffn([(W8A8, W8A8), (W8A8, W4A4_G128), (W8A8, W8A8)]), 4, 2)
+    biased = cpu_ffn([(W8A8, W8A8)] * 3, down_bias=[torch.zeros(256) for _ in range(3)])
     assert biased.biased_or_gated
     with pytest.raises(ValueError, match="bias"):
         moe.DecodeForward(biased, 4, 2)
-    gated = _ffn([(FP16, FP16)] * 3, activation=moe.SwigluClamp())
+    gated = cpu_ffn([(FP16, FP16)] * 3, activation=moe.SwigluClamp())
     with pytest.raises(ValueError, match="activation"):
         moe.DecodeForward(gated, 4, 2)

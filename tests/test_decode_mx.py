@@ -15,30 +15,23 @@ import torch
 from mxmoe_amd import _native as nat
 from mxmoe_amd import moe, quantize
 from mxmoe_amd.groupgemm import FP16, W4A4_G128, W4A4_MXFP4, W4A8_MXFP8, W4A16_MXFP4, W8A8
+from tests._decode_util import cpu_ffn, entry_down, entry_gate_up, err
 
 INVALID, UNSUPPORTED, OK = nat.MXMOE_GG_ERR_INVALID, nat.MXMOE_GG_ERR_UNSUPPORTED, nat.MXMOE_GG_OK
 ALL_KINDS = 0b1111
 ROOT = Path(__file__).resolve().parent.parent
 
 
-def _err():
-    return nat.lib().mxmoe_gg_last_error()
-
-
 def _glu(act=nat.GLU_SWIGLU_CLAMP, alpha=1.702, limit=7.0, bias_routed=32, bias_shared=64):
     return nat.MoeGluC(act, alpha, limit, bias_routed, bias_shared)
 
 
-def _gate_up(glu=None, dtype=nat.DT_FP16, hidden=16, T=4, topk=2, E=4, with_shared=1, ids=16, experts=16, mask=ALL_KINDS,
-             H=256, N=128, Ns=256, layout=nat.DECODE_GU_PLAIN, act=16, act_shared=16, status=None):
-    return nat.symbol("mxmoe_moe_decode_gate_up_ex")(glu, dtype, hidden, T, topk, E, with_shared, ids, experts, mask, H, N,
-                                                    Ns, layout, act, act_shared, status, None)
+def _gate_up(**kw):
+    return entry_gate_up("ex", **dict(dict(mask=ALL_KINDS), **kw))
 
 
-def _down(T=4, topk=2, E=4, with_shared=1, ids=16, experts=16, mask=ALL_KINDS, H=256, N=128, Ns=256, act=16, act_shared=16,
-          y=16, ys=16, status=None):
-    return nat.symbol("mxmoe_moe_decode_down_ex")(T, topk, E, with_shared, ids, experts, mask, H, N, Ns, act, act_shared, y,
-                                                 ys, status, None)
+def _down(**kw):
+    return entry_down("ex", **dict(dict(mask=ALL_KINDS), **kw))
 
 
 ENTRIES = [(_gate_up, b"mxmoe_moe_decode_gate_up_ex"), (_down, b"mxmoe_moe_decode_down_ex")]
@@ -69,7 +62,7 @@ def test_limits_are_refused_before_any_hip_call(call, name):
                dict(ids=2), dict(experts=4), dict(status=2), dict(mask=0), dict(ids=None), dict(experts=None),
                dict(act=None), dict(act_shared=None)):
         assert call(**kw) == INVALID, kw
-        assert name in _err(), kw
+        assert name in err(), kw
     assert call(T=0) == OK
     assert call(T=0, with_shared=0, Ns=0, act_shared=None) == OK
     assert call(T=0, H=16384, N=16384, Ns=16384, topk=16, E=16) == OK
@@ -82,7 +75,7 @@ def test_kind_bits(call, name):
         assert call(mask=mask, T=0) == OK, mask
     for mask in (1 << 4, ALL_KINDS | 1 << 4, 1 << 31):
         assert call(mask=mask) == UNSUPPORTED, mask
-        assert name in _err() and b"kind" in _err()
+        assert name in err() and b"kind" in err()
         assert call(mask=mask, T=0) == UNSUPPORTED
 
 
@@ -91,29 +84,22 @@ def test_entry_specific_refusals():
     name = b"mxmoe_moe_decode_gate_up_ex"
     for kw in (dict(dtype=2), dict(dtype=-1), dict(layout=2), dict(layout=-1), dict(hidden=8), dict(hidden=None)):
         assert _gate_up(**kw) == INVALID, kw
-        assert name in _err(), kw
+        assert name in err(), kw
     for glu in (_glu(act=2), _glu(act=-1), _glu(alpha=math.inf), _glu(alpha=math.nan), _glu(limit=0.0), _glu(limit=-1.0),
                 _glu(limit=math.inf), _glu(limit=math.nan), _glu(bias_routed=8), _glu(bias_shared=24)):
         assert _gate_up(glu=glu) == INVALID, (glu.act, glu.alpha, glu.limit, glu.bias_routed, glu.bias_shared)
-        assert name in _err()
+        assert name in err()
         assert _gate_up(glu=glu, T=0) == INVALID  # (before the empty-batch return)
     assert _gate_up(glu=_glu(), with_shared=0, act_shared=None) == INVALID  # bias_shared without a shared expert
-    assert name in _err() and b"bias_shared" in _err()
+    assert name in err() and b"bias_shared" in err()
     assert _gate_up(glu=_glu(), T=0) == OK
     assert _gate_up(glu=_glu(bias_shared=None), with_shared=0, act_shared=None, T=0) == OK
     assert _gate_up(glu=_glu(act=nat.GLU_SILU, alpha=math.nan, limit=-1.0, bias_routed=None, bias_shared=None), T=0) == OK
     assert _gate_up(glu=None, dtype=nat.DT_BF16, layout=nat.DECODE_GU_INTERLEAVED, T=0) == OK
     for kw in (dict(y=8), dict(ys=4), dict(y=None), dict(ys=None)):
         assert _down(**kw) == INVALID, kw
-        assert b"mxmoe_moe_decode_down_ex" in _err(), kw
+        assert b"mxmoe_moe_decode_down_ex" in err(), kw
     assert _down(with_shared=0, ys=None, act_shared=None, T=0) == OK
-
-
-def _ffn(qcfg, E=2, H=256, N=128, Ns=128, **kw):
-    g = torch.Generator().manual_seed(5)
-    mk = lambda n, k: ((torch.rand(n, k, generator=g) * 2 - 1) * 0.2).half()
-    return moe.MoEFFN([mk(2 * N, H) for _ in range(E)] + [mk(2 * Ns, H)], [mk(H, N) for _ in range(E)] + [mk(H, Ns)], qcfg,
-                      num_routed=E, **kw)
 
 
 def _gptoss(E=4, H=256, N=128, act_bits=16, seed=3):
@@ -127,8 +113,8 @@ def _gptoss(E=4, H=256, N=128, act_bits=16, seed=3):
 def test_decode_forward_ex_on_cpu_built_layers():
     """★ 2. DecodeForwardEx constructs for a biased w8a8 layer, an fp16 SwigluClamp layer and a gptoss_layer (which
     DecodeForward still refuses), and refuses the a4 / a8 MX forms and g128 naming the qcfg."""
-    biased = _ffn([(W8A8, W8A8)] * 3, down_bias=[torch.zeros(256) for _ in range(3)])
-    gated = _ffn([(FP16, FP16)] * 3, activation=moe.SwigluClamp())
+    biased = cpu_ffn([(W8A8, W8A8)] * 3, down_bias=[torch.zeros(256) for _ in range(3)])
+    gated = cpu_ffn([(FP16, FP16)] * 3, activation=moe.SwigluClamp())
     oss = _gptoss()
     assert biased.biased_or_gated and gated.biased_or_gated and oss.biased_or_gated
     for layer, E in ((biased, 2), (gated, 2), (oss, 4)):
@@ -141,9 +127,9 @@ def test_decode_forward_ex_on_cpu_built_layers():
     assert (rec.b1, rec.sb1, rec.kind1) == (oss.w1[1].B.data_ptr(), oss.w1[1].scale_b.data_ptr(), 3)
     assert (rec.b2, rec.sb2, rec.kind2) == (oss.w2[1].B.data_ptr(), oss.w2[1].scale_b.data_ptr(), 3)
     assert df._glu.act == nat.GLU_SWIGLU_CLAMP and df._glu.bias_routed == oss.b1.data_ptr()
-    mixed = moe.DecodeForwardEx(_ffn([(W4A16_MXFP4, W8A8), (FP16, W4A16_MXFP4), (W8A8, W8A8)]), 4, 2)
+    mixed = moe.DecodeForwardEx(cpu_ffn([(W4A16_MXFP4, W8A8), (FP16, W4A16_MXFP4), (W8A8, W8A8)]), 4, 2)
     assert mixed.mask1 == 0b1011 and mixed.mask2 == 0b1010 and mixed._glu is None
-    plain = moe.DecodeForwardEx(_ffn([(W8A8, W8A8)] * 3), 4, 2)  # a layer DecodeForward takes: its layout and no glu
+    plain = moe.DecodeForwardEx(cpu_ffn([(W8A8, W8A8)] * 3), 4, 2)  # a layer DecodeForward takes: its layout and no glu
     assert plain._glu is None and plain.layout == nat.DECODE_GU_INTERLEAVED
     with pytest.raises(ValueError, match="bias"):
         moe.DecodeForward(biased, 4, 2)
@@ -152,15 +138,15 @@ def test_decode_forward_ex_on_cpu_built_layers():
     with pytest.raises(ValueError):
         moe.DecodeForward(oss, 4, 2)
     with pytest.raises(ValueError, match="w4a4_g32_sym_MXFP4"):
-        moe.DecodeForwardEx(_ffn([(W8A8, W8A8), (W4A4_MXFP4, W4A4_MXFP4), (W8A8, W8A8)]), 4, 2)
+        moe.DecodeForwardEx(cpu_ffn([(W8A8, W8A8), (W4A4_MXFP4, W4A4_MXFP4), (W8A8, W8A8)]), 4, 2)
     with pytest.raises(ValueError, match="w4a4_g32_sym_MXFP4"):
         moe.DecodeForwardEx(_gptoss(act_bits=4), 4, 2)
     with pytest.raises(ValueError, match="w4a8_g32_sym_MXFP8"):
         moe.DecodeForwardEx(_gptoss(act_bits=8), 4, 2)
     with pytest.raises(ValueError, match="w4a8_g32_sym_MXFP8"):
-        moe.DecodeForwardEx(_ffn([(W8A8, W8A8), (W8A8, W4A8_MXFP8), (W8A8, W8A8)]), 4, 2)
+        moe.DecodeForwardEx(cpu_ffn([(W8A8, W8A8), (W8A8, W4A8_MXFP8), (W8A8, W8A8)]), 4, 2)
     with pytest.raises(ValueError, match="w4a4_g128_sym"):
-        moe.DecodeForwardEx(_ffn([(W8A8, W8A8), (W8A8, W4A4_G128), (W8A8, W8A8)]), 4, 2)
+        moe.DecodeForwardEx(cpu_ffn([(W8A8, W8A8), (W8A8, W4A4_G128), (W8A8, W8A8)]), 4, 2)
     with pytest.raises(ValueError, match="T = 17"):
         moe.DecodeForwardEx(oss, 17, 2)
 

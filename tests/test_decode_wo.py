@@ -15,6 +15,7 @@ from mxmoe_amd import _native as nat
 from mxmoe_amd import moe, quantize
 from mxmoe_amd.groupgemm import (FP16, W2A16_G128_ASYM, W4A4, W4A4_G128, W4A4_MXFP4, W4A8_MXFP8, W4A16_ASYM,
                                  W4A16_G128_SYM, W8A8, W8A16_ASYM, QParams)
+from tests._decode_util import cpu_ffn, entry_down, entry_gate_up, err
 
 INVALID, UNSUPPORTED, OK = nat.MXMOE_GG_ERR_INVALID, nat.MXMOE_GG_ERR_UNSUPPORTED, nat.MXMOE_GG_OK
 ALL_KINDS = (1 << 12) - 1
@@ -23,20 +24,12 @@ NAMES = {4: "W4A16", 5: "W8A16", 6: "W4A16_G128", 7: "W8A16_G128", 8: "W4A16_ASY
          10: "W4A16_G128_ASYM", 11: "W8A16_G128_ASYM"}
 
 
-def _err():
-    return nat.lib().mxmoe_gg_last_error()
+def _gate_up(**kw):
+    return entry_gate_up("wo", **dict(dict(mask=ALL_KINDS), **kw))
 
 
-def _gate_up(glu=None, dtype=nat.DT_FP16, hidden=16, T=4, topk=2, E=4, with_shared=1, ids=16, experts=16, mask=ALL_KINDS,
-             H=256, N=128, Ns=256, layout=nat.DECODE_GU_PLAIN, act=16, act_shared=16, status=None):
-    return nat.symbol("mxmoe_moe_decode_gate_up_wo")(glu, dtype, hidden, T, topk, E, with_shared, ids, experts, mask, H, N,
-                                                    Ns, layout, act, act_shared, status, None)
-
-
-def _down(T=4, topk=2, E=4, with_shared=1, ids=16, experts=16, mask=ALL_KINDS, H=256, N=128, Ns=256, act=16, act_shared=16,
-          y=16, ys=16, status=None):
-    return nat.symbol("mxmoe_moe_decode_down_wo")(T, topk, E, with_shared, ids, experts, mask, H, N, Ns, act, act_shared, y,
-                                                 ys, status, None)
+def _down(**kw):
+    return entry_down("wo", **dict(dict(mask=ALL_KINDS), **kw))
 
 
 ENTRIES = [(_gate_up, b"mxmoe_moe_decode_gate_up_wo"), (_down, b"mxmoe_moe_decode_down_wo")]
@@ -84,7 +77,7 @@ def test_limits_are_refused_before_any_hip_call(call, name):
                dict(ids=2), dict(experts=4), dict(status=2), dict(mask=0), dict(ids=None), dict(experts=None),
                dict(act=None), dict(act_shared=None)):
         assert call(**kw) == INVALID, kw
-        assert name in _err(), kw
+        assert name in err(), kw
     assert call(T=0) == OK
     assert call(T=0, with_shared=0, Ns=0, act_shared=None) == OK
     assert call(T=0, H=16384, N=16384, Ns=16384, topk=16, E=16) == OK
@@ -98,9 +91,9 @@ def test_kind_bits(call, name):
         assert call(mask=mask, T=0) == OK, mask
     for mask in (1 << 12, ALL_KINDS | 1 << 12, 1 << 31):
         assert call(mask=mask) == UNSUPPORTED, mask
-        assert name in _err() and b"kind" in _err()
+        assert name in err() and b"kind" in err()
         assert call(mask=mask, T=0) == UNSUPPORTED
-    assert call(mask=0, T=0) == INVALID and name in _err()
+    assert call(mask=0, T=0) == INVALID and name in err()
     ex = nat.symbol("mxmoe_moe_decode_down_ex")
     first = nat.symbol("mxmoe_moe_decode_down")
     args = (0, 2, 4, 1, 16, 16)
@@ -118,27 +111,20 @@ def test_entry_specific_refusals():
         nat.MoeGluC(act, alpha, limit, bias_routed, bias_shared)
     for kw in (dict(dtype=2), dict(dtype=-1), dict(layout=2), dict(layout=-1), dict(hidden=8), dict(hidden=None)):
         assert _gate_up(**kw) == INVALID, kw
-        assert name in _err(), kw
+        assert name in err(), kw
     for g in (glu(act=2), glu(act=-1), glu(alpha=math.inf), glu(alpha=math.nan), glu(limit=0.0), glu(limit=-1.0),
               glu(limit=math.inf), glu(limit=math.nan), glu(bias_routed=8), glu(bias_shared=24)):
         assert _gate_up(glu=g) == INVALID
-        assert name in _err()
+        assert name in err()
         assert _gate_up(glu=g, T=0) == INVALID  # (before the empty-batch return)
     assert _gate_up(glu=glu(), with_shared=0, act_shared=None) == INVALID  # bias_shared without a shared expert
-    assert name in _err() and b"bias_shared" in _err()
+    assert name in err() and b"bias_shared" in err()
     assert _gate_up(glu=glu(), T=0) == OK
     assert _gate_up(glu=None, dtype=nat.DT_BF16, layout=nat.DECODE_GU_INTERLEAVED, T=0) == OK
     for kw in (dict(y=8), dict(ys=4), dict(y=None), dict(ys=None)):
         assert _down(**kw) == INVALID, kw
-        assert b"mxmoe_moe_decode_down_wo" in _err(), kw
+        assert b"mxmoe_moe_decode_down_wo" in err(), kw
     assert _down(with_shared=0, ys=None, act_shared=None, T=0) == OK
-
-
-def _ffn(qcfg, E=2, H=256, N=128, Ns=128, **kw):
-    g = torch.Generator().manual_seed(5)
-    mk = lambda n, k: ((torch.rand(n, k, generator=g) * 2 - 1) * 0.2).half()
-    return moe.MoEFFN([mk(2 * N, H) for _ in range(E)] + [mk(2 * Ns, H)], [mk(H, N) for _ in range(E)] + [mk(H, Ns)], qcfg,
-                      num_routed=E, **kw)
 
 
 def _record(df, e):
@@ -148,7 +134,7 @@ def _record(df, e):
 def test_decode_forward_wo_on_cpu_built_layers():
     """DecodeForwardWo constructs for the w4a16_asym + w8a8 scheme (masks, the layer's own tensors in the records, the
     interleaved layout), a g128 sym layer and a biased w8a16 layer; the other two classes refuse those layers."""
-    scheme = _ffn([(W4A16_ASYM, W8A8), (W8A8, W4A16_ASYM), (W4A16_ASYM, W4A16_ASYM)])
+    scheme = cpu_ffn([(W4A16_ASYM, W8A8), (W8A8, W4A16_ASYM), (W4A16_ASYM, W4A16_ASYM)])
     df = moe.DecodeForwardWo(scheme, 4, 2)
     both = 1 << nat.DECODE_W8A8 | 1 << nat.DECODE_W4A16_ASYM
     assert df.mask1 == both == df.mask2 and df._glu is None
@@ -160,15 +146,15 @@ def test_decode_forward_wo_on_cpu_built_layers():
         assert (rec.b1, rec.sb1, rec.kind1) == (w1.B.data_ptr(), w1.scale_b.data_ptr(), k1)
         assert (rec.b2, rec.sb2, rec.kind2) == (w2.B.data_ptr(), w2.scale_b.data_ptr(), k2)
     assert scheme.w1[0].scale_b.numel() == 256 * 2 and scheme.w2[1].scale_b.numel() == 256 * 2  # [1][rows][2]
-    g128 = _ffn([(W4A16_G128_SYM, W4A16_G128_SYM)] * 3)
+    g128 = cpu_ffn([(W4A16_G128_SYM, W4A16_G128_SYM)] * 3)
     df = moe.DecodeForwardWo(g128, 16, 2)
     assert df.mask1 == df.mask2 == 1 << nat.DECODE_W4A16_G128
     assert g128.w1[0].scale_b.numel() == 2 * 256 and g128.w2[0].scale_b.numel() == 1 * 256  # [K / 128][rows]
-    biased = _ffn([(W8A16_ASYM, W8A16_ASYM)] * 3, down_bias=[torch.zeros(256) for _ in range(3)])
+    biased = cpu_ffn([(W8A16_ASYM, W8A16_ASYM)] * 3, down_bias=[torch.zeros(256) for _ in range(3)])
     df = moe.DecodeForwardWo(biased, 4, 2)
     assert df._glu is not None and df.layout == nat.DECODE_GU_PLAIN
     assert df.mask1 == df.mask2 == 1 << nat.DECODE_W8A16_ASYM
-    plain = moe.DecodeForwardWo(_ffn([(W8A8, W4A4), (FP16, W8A8), (W4A4, FP16)]), 4, 2)  # a layer DecodeForward takes
+    plain = moe.DecodeForwardWo(cpu_ffn([(W8A8, W4A4), (FP16, W8A8), (W4A4, FP16)]), 4, 2)  # a layer DecodeForward takes
     assert plain.mask1 == 0b111 == plain.mask2 and plain._glu is None
     for cls in (moe.DecodeForward, moe.DecodeForwardEx):
         with pytest.raises(ValueError, match="w4a16_g-1_asym"):
@@ -182,10 +168,10 @@ def test_decode_forward_wo_refusals():
     for q, name in ((W2A16_G128_ASYM, "w2a16_g128_asym"), (W4A4_G128, "w4a4_g128_sym"), (W4A4_MXFP4, "w4a4_g32_sym_MXFP4"),
                     (W4A8_MXFP8, "w4a8_g32_sym_MXFP8")):
         with pytest.raises(ValueError, match=name):
-            moe.DecodeForwardWo(_ffn([(W8A8, W8A8), (W8A8, q), (W8A8, W8A8)]), 4, 2)
+            moe.DecodeForwardWo(cpu_ffn([(W8A8, W8A8), (W8A8, q), (W8A8, W8A8)]), 4, 2)
     with pytest.raises(ValueError, match="w4a16_g64_sym"):
-        moe.DecodeForwardWo(_ffn([(QParams(16, 4, 64, True), W8A8)] * 3), 4, 2)
-    ok = _ffn([(W4A16_ASYM, W4A16_G128_SYM)] * 3)
+        moe.DecodeForwardWo(cpu_ffn([(QParams(16, 4, 64, True), W8A8)] * 3), 4, 2)
+    ok = cpu_ffn([(W4A16_ASYM, W4A16_G128_SYM)] * 3)
     with pytest.raises(ValueError, match="T = 17"):
         moe.DecodeForwardWo(ok, 17, 2)
     moe.DecodeForwardWo(ok, 16, 2)
@@ -194,7 +180,7 @@ def test_decode_forward_wo_refusals():
         moe.DecodeForwardWo(ok, 16, 2)
 
 
-# ---- the kernel's maps, in plain Python (mxmoe_amd/csrc/moe_decode.h, "codes" and "A rows") -------------------------
+# ---- the kernel's maps, in plain Python (mxmoe_amd/csrc/moe_decode.h, "WeightOnly" and "fp16 A") -------------------------
 def run_k(bits, s, lane, j):
     """first K of run j of lane `lane` (of a quarter-wave) at step s"""
     if bits == 4:
@@ -220,7 +206,7 @@ def run_codes(bits, row_bytes, s, lane, j):
 
 
 def quant_row_source(bits, piece, copy_lane):
-    """quant_row: first K of the 8 elements that lane `copy_lane` (of 64) stores at LDS byte 1024 piece + 16 copy_lane"""
+    """stage_f16: first K of the 8 elements that lane `copy_lane` (of 64) stores at LDS byte 1024 piece + 16 copy_lane"""
     lane, j = copy_lane & 15, copy_lane >> 4
     if bits == 4:
         return 512 * piece + 64 * (lane >> 1) + 32 * (j & 1) + 8 * (2 * (lane & 1) + (j >> 1))
@@ -265,7 +251,7 @@ def test_k_maps(bits, K):
                 assert k // 128 == (4 * s + (lane >> 2) if bits == 4 else 2 * s + (lane >> 3))
     assert (hits == 1).all()
     assert sorted(lds_of_k) == list(range(0, steps * step_lds, 16))  # every 16-byte slot of the steps, once
-    # quant_row's copy: passes of 1024 bytes, lane c stores slot c
+    # stage_f16's copy: passes of 1024 bytes, lane c stores slot c
     for piece in range(-(-2 * K // 1024)):
         for c in range(64):
             byte, k = 1024 * piece + 16 * c, quant_row_source(bits, piece, c)

@@ -8,19 +8,17 @@ exact, within the project's fp16 tolerance on random data. The eager intermediat
 expert), the decode buffers in pair order: row p of ``act`` / ``y`` is row inv_slot[p] of the eager one."""
 from __future__ import annotations
 
-import ctypes
-
 import pytest
 import torch
 
 from mxmoe_amd import _native as nat
 from mxmoe_amd import moe, quantize
 from mxmoe_amd.groupgemm import FP16, W4A4, W4A16_ASYM, W4A16_G128_SYM, W8A8, W8A16_ASYM, QParams
+from tests._decode_util import DEV, GUARD, biases, bits, check_stages, down_raw, f16_weights, guard, routing
+from tests._decode_util import hidden as _hidden
 from tests._util import assert_f16_close
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
-GUARD = 0x7B7B
 W8A16_G128_ASYM = QParams(16, 8, 128, False)
 EXACT_KINDS = {"w4a16_g-1_asym": W4A16_ASYM, "w4a16_g128_sym": W4A16_G128_SYM, "w8a16_g-1_asym": W8A16_ASYM,
                "w8a16_g128_asym": W8A16_G128_ASYM}
@@ -28,84 +26,9 @@ SCHEME = [(W4A16_ASYM, W8A8), (W8A8, W8A8), (W8A8, W4A16_ASYM), (W4A16_ASYM, W4A
           (W4A16_ASYM, W4A16_ASYM)]  # E = 5 and the shared expert
 
 
-def _bits(t):
-    return t.view(torch.int16)
-
-
-def _guard(df):
-    bufs = [t for t in (df.act, df.act_shared, df.y, df.ys, df.out) if t is not None]
-    for t in bufs:
-        _bits(t).fill_(GUARD)
-    return bufs
-
-
-def _hidden(g, T, H, grid=False, dtype=torch.float16):
-    if grid:  # multiples of 1/4 in [-1, 1] (exact in bf16 too)
-        return (torch.randint(-4, 5, (T, H), generator=g).float() / 4).to(dtype).to(DEV)
-    return torch.randn(T, H, generator=g).to(dtype).to(DEV)
-
-
-def _routing(g, T, E, topk):
-    ids = torch.stack([torch.randperm(E, generator=g)[:topk] for _ in range(T)]).to(torch.int32).to(DEV)
-    wts = torch.softmax(torch.rand(T, topk, generator=g), dim=1).to(DEV)
-    sw = torch.rand(T, generator=g).to(DEV)
-    return ids, wts, sw
-
-
-def _f16_weights(g, E, H, N, Ns):
-    mk = lambda n, k: ((torch.rand(n, k, generator=g) * 2 - 1) * 0.2).half().to(DEV)
-    return [mk(2 * N, H) for _ in range(E)] + ([mk(2 * Ns, H)] if Ns else []), \
-        [mk(H, N) for _ in range(E)] + ([mk(H, Ns)] if Ns else [])
-
-
-def _biases(g, E, H, N, Ns):
-    mk = lambda n: (torch.rand(n, generator=g) - 0.5).half().to(DEV)
-    return [mk(2 * N) for _ in range(E)] + ([mk(2 * Ns)] if Ns else []), [mk(H) for _ in range(E + (1 if Ns else 0))]
-
-
-def _eager_act(ffn, mid):
-    """The eager layer's fp16 activation rows (routed in slot order, shared): its own activation pass run with fp16
-    tags on its gate_up output."""
-    r, tags = mid["routing"], [moe.ACT_FP16] * (ffn.E + (1 if ffn.has_shared else 0))
-    if mid["h1"].shape[1] == ffn.N:  # the SiLU epilogue ran: h1 is act
-        return mid["h1"], mid["h1s"]
-    if ffn.biased_or_gated:
-        a = moe.glu_quant(mid["h1"], mid["h1s"], r, tags, ffn.activation, ffn.b1, ffn.b1s)
-    else:
-        a = moe.silu_mul_quant(mid["h1"], mid["h1s"], r, tags, interleaved=ffn.gate_up_layout() != "plain")
-    torch.cuda.synchronize()
-    return torch.cat([a.A(e) for e in range(ffn.E)]), a.A(ffn.E) if ffn.has_shared else None
-
-
-def _check_stages(df, ffn, h, ids, wts, sw, stages=("act", "y", "out")):
-    """One call through ``df`` against the eager layer: the stages "act", "y", "out" bit for bit, "close": out within the
-    project's fp16 tolerance."""
-    T, topk = ids.shape
-    n = T * topk
-    got = df.launch(h, ids, wts, sw).clone()
-    want, mid = ffn.forward(h, ids, wts, sw, return_intermediates=True)
-    torch.cuda.synchronize()
-    inv = mid["routing"].inv_slot.long()
-    if "act" in stages:
-        act, act_s = _eager_act(ffn, mid)
-        assert torch.equal(_bits(df.act[:n]), _bits(act[inv])), "gate_up (routed act)"
-        if ffn.has_shared:
-            assert torch.equal(_bits(df.act_shared[:T]), _bits(act_s)), "gate_up (shared act)"
-    if "y" in stages:
-        assert torch.equal(_bits(df.y[:n]), _bits(mid["y"][inv])), "down (routed y)"
-        if ffn.has_shared:
-            assert torch.equal(_bits(df.ys[:T]), _bits(mid["ys"])), "down (shared ys)"
-    if "out" in stages:
-        assert torch.equal(_bits(got), _bits(want)), "combine"
-    if "close" in stages:
-        assert_f16_close(got.float().cpu().numpy(), want.float().cpu().numpy(), ffn.H)
-    return mid
-
-
-def _down_wo(T, topk, E, shared, ids, experts, mask, H, N, Ns, act, act_shared, y, ys, status):
-    p = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())
-    nat.check(nat.symbol("mxmoe_moe_decode_down_wo")(T, topk, E, shared, p(ids), p(experts), mask, H, N, Ns, p(act),
-                                                    p(act_shared), p(y), p(ys), p(status), None))
+def hidden(g, T, H, grid=False, dtype=torch.float16):
+    """randn, or (grid) multiples of 1/4 in [-1, 1] (exact in bf16 too)"""
+    return _hidden(g, T, H, grid, dtype, step=4, bound=1)
 
 
 # ---- 1. the dequantised weights, read back bit for bit ------------------------------------------------------------
@@ -125,13 +48,13 @@ def test_dequant_readback(kind):
     group and both row ends (192 bytes: less than a step; 384: one and a half). Codes cover every value; scales and
     zps are arbitrary finite fp16 values (|scale| < 64, |zp| < 1024, so every weight is finite), negative, subnormal
     and zero ones among them."""
-    bits, gsize, sym = (8 if (kind - 4) & 1 else 4), (128 if (kind - 4) & 2 else -1), not (kind - 4) & 4
-    assert nat.decode_wo_kind(bits, gsize, sym) == kind
+    w_bits, gsize, sym = (8 if (kind - 4) & 1 else 4), (128 if (kind - 4) & 2 else -1), not (kind - 4) & 4
+    assert nat.decode_wo_kind(w_bits, gsize, sym) == kind
     T, H, N = 16, 384, 384
     g = torch.Generator().manual_seed(700 + kind)
     G = 1 if gsize == -1 else N // gsize
-    codes = torch.randint(0, 1 << bits, (H, N), generator=g, dtype=torch.uint8)
-    codes[0, :1 << bits] = torch.arange(1 << bits, dtype=torch.uint8)[:N]  # every value, whatever the draw
+    codes = torch.randint(0, 1 << w_bits, (H, N), generator=g, dtype=torch.uint8)
+    codes[0, :1 << w_bits] = torch.arange(1 << w_bits, dtype=torch.uint8)[:N]  # every value, whatever the draw
     scale = _finite_f16(g, (G, H), 20)
     scale[:, 3], scale[:, 5], scale[:, 6] = 0.0, -(2.0 ** -20), 2.0 ** -24  # a zero and two subnormal scales, in any draw
     if sym:
@@ -140,10 +63,10 @@ def test_dequant_readback(kind):
         zp = _finite_f16(g, (G, H), 24)
         zp[:, ::7] = 0
         sz = torch.stack([scale, zp], dim=-1).reshape(-1)
-    want = quantize.dequant_weightonly(codes, sz, bits, gsize, sym)
+    want = quantize.dequant_weightonly(codes, sz, w_bits, gsize, sym)
     assert torch.isfinite(want).all() and (sz == 0).any() and ((sz != 0) & (sz.abs() < 2.0 ** -14)).any() and (sz < 0).any()
     want = (want.float() + 0.0).half()  # -0 -> +0
-    B, SZ = quantize.pack_weightonly_mi355x(codes, bits).to(DEV), sz.to(DEV)
+    B, SZ = quantize.pack_weightonly_mi355x(codes, w_bits).to(DEV), sz.to(DEV)
     rec = (nat.MoeDecodeExpertC * 1)()
     rec[0].b1, rec[0].sb1, rec[0].kind1 = B.data_ptr(), SZ.data_ptr(), kind
     rec[0].b2, rec[0].sb2, rec[0].kind2 = B.data_ptr(), SZ.data_ptr(), kind
@@ -155,12 +78,12 @@ def test_dequant_readback(kind):
         act = torch.zeros(T, N, dtype=torch.float16, device=DEV)
         act[torch.arange(T), 16 * c + torch.arange(T)] = 1.0
         y = torch.empty(T, H, dtype=torch.float16, device=DEV)
-        _bits(y).fill_(GUARD)
-        _down_wo(T, 1, 1, 0, ids, experts, 1 << kind, H, N, 0, act, None, y, None, status)
+        bits(y).fill_(GUARD)
+        down_raw("wo", T, 1, 1, 0, ids, experts, 1 << kind, H, N, 0, act, None, y, None, status)
         ys.append(y)
     torch.cuda.synchronize()
     got = torch.cat(ys).cpu()  # row 16 c + t = K position: [N][H]
-    assert torch.equal(_bits(got), _bits(want.t().contiguous()))
+    assert torch.equal(bits(got), bits(want.t().contiguous()))
     assert int(status.item()) == 0
 
 
@@ -189,7 +112,7 @@ def _exact_layer(g, q, E, H, N, Ns, variant):
         bmax = max(bmax, b)
     kw = dict(fuse_silu=variant == "interleaved")
     if variant == "bias_clamp":
-        b1, b2 = _biases(g, E, H, N, Ns)
+        b1, b2 = biases(g, E, H, N, Ns)
         kw = dict(gate_up_bias=b1, down_bias=b2, activation=moe.SwigluClamp())
     ffn = moe.MoEFFN(ws[:E + 1], ws[E + 1:], [(q, q)] * (E + 1), num_routed=E, **kw)
     return ffn, bmax
@@ -224,25 +147,25 @@ def test_exact_gate_up_and_down(name, variant, shape, T):
     kind = nat.decode_wo_kind(q.w_bits, q.gsize, q.sym)
     assert df.mask1 == df.mask2 == 1 << kind and (df._glu is not None) == (variant == "bias_clamp")
     assert df.layout == (nat.DECODE_GU_INTERLEAVED if variant == "interleaved" else nat.DECODE_GU_PLAIN)
-    bufs = _guard(df)
-    ids, wts, sw = _routing(g, T, E, topk)
-    mid = _check_stages(df, ffn, _hidden(g, T, H, grid=True), ids, wts, sw, stages=("act",))
+    bufs = guard(df)
+    ids, wts, sw = routing(g, T, E, topk)
+    mid = check_stages(df, ffn, hidden(g, T, H, grid=True), ids, wts, sw, stages=("act",))
     for t in bufs:
-        assert not (_bits(t) == GUARD).all(dim=1).any()
+        assert not (bits(t) == GUARD).all(dim=1).any()
     # down, on grid activations in pair order
     n, r = T * topk, mid["routing"]
     inv = r.inv_slot.long()
-    act, act_s = _hidden(g, n, N, grid=True), _hidden(g, T, Ns, grid=True)
+    act, act_s = hidden(g, n, N, grid=True), hidden(g, T, Ns, grid=True)
     slots = torch.empty_like(act)
     slots[inv] = act
     a2 = moe.silu_mul_quant(slots, act_s, r, ffn.tag2, activated=True)
     g2, y, ys = ffn.down_call(a2, T, topk, torch.device(DEV))
     g2.launch()
-    _bits(df.y).fill_(GUARD), _bits(df.ys).fill_(GUARD)
-    _down_wo(T, topk, E, 1, ids, df.experts, df.mask2, H, N, Ns, act, act_s, df.y, df.ys, df.dev_status)
+    bits(df.y).fill_(GUARD), bits(df.ys).fill_(GUARD)
+    down_raw("wo", T, topk, E, 1, ids, df.experts, df.mask2, H, N, Ns, act, act_s, df.y, df.ys, df.dev_status)
     torch.cuda.synchronize()
-    assert torch.equal(_bits(df.y[:n]), _bits(y[inv])), "down (routed y)"
-    assert torch.equal(_bits(df.ys[:T]), _bits(ys)), "down (shared ys)"
+    assert torch.equal(bits(df.y[:n]), bits(y[inv])), "down (routed y)"
+    assert torch.equal(bits(df.ys[:T]), bits(ys)), "down (shared ys)"
     assert df.status() == 0
 
 
@@ -251,7 +174,7 @@ def test_exact_gate_up_and_down(name, variant, shape, T):
 @pytest.fixture(scope="module")
 def scheme_layer():
     g = torch.Generator().manual_seed(720)
-    gate_up, down = _f16_weights(g, 5, 384, 256, 640)
+    gate_up, down = f16_weights(g, 5, 384, 256, 640)
     return moe.MoEFFN(gate_up, down, SCHEME, num_routed=5)
 
 
@@ -265,13 +188,13 @@ def test_scheme_random_data(scheme_layer, T):
     df = moe.DecodeForwardWo(ffn, T, topk)
     assert df.mask1 == df.mask2 == 1 << nat.DECODE_W8A8 | 1 << nat.DECODE_W4A16_ASYM
     assert df.layout == nat.DECODE_GU_INTERLEAVED
-    _guard(df)
+    guard(df)
     for _ in range(2):
-        ids, wts, sw = _routing(g, T, ffn.E, topk)
-        mid = _check_stages(df, ffn, _hidden(g, T, ffn.H), ids, wts, sw, stages=("close",))
+        ids, wts, sw = routing(g, T, ffn.E, topk)
+        mid = check_stages(df, ffn, hidden(g, T, ffn.H), ids, wts, sw, stages=("close",))
         inv = mid["routing"].inv_slot.long()
         w8 = torch.tensor([e in (1, 4) for e in ids.view(-1).tolist()])
-        assert torch.equal(_bits(df.y[:T * topk])[w8], _bits(mid["y"][inv])[w8])
+        assert torch.equal(bits(df.y[:T * topk])[w8], bits(mid["y"][inv])[w8])
     assert df.status() == 0
 
 
@@ -279,10 +202,10 @@ def test_older_kinds_give_decode_forwards_bytes():
     """On an fp16 / w8a8 / w4a4 layer the _wo entries give DecodeForward's bytes, in both gate_up layouts."""
     T, topk, E, H, N, Ns = 16, 2, 4, 256, 128, 256
     g = torch.Generator().manual_seed(730)
-    gate_up, down = _f16_weights(g, E, H, N, Ns)
+    gate_up, down = f16_weights(g, E, H, N, Ns)
     qcfg = [(W8A8, W4A4), (W4A4, FP16), (FP16, W8A8), (W4A4, W4A4), (W8A8, W8A8)]
-    ids, wts, sw = _routing(g, T, E, topk)
-    h = _hidden(g, T, H)
+    ids, wts, sw = routing(g, T, E, topk)
+    h = hidden(g, T, H)
     for fuse in (None, False):
         layer = moe.MoEFFN(gate_up, down, qcfg, num_routed=E, fuse_silu=fuse)
         new, old = moe.DecodeForwardWo(layer, T, topk), moe.DecodeForward(layer, T, topk)
@@ -290,7 +213,7 @@ def test_older_kinds_give_decode_forwards_bytes():
         new.launch(h, ids, wts, sw), old.launch(h, ids, wts, sw)
         torch.cuda.synchronize()
         for a, b in ((new.act, old.act), (new.act_shared, old.act_shared), (new.y, old.y), (new.ys, old.ys), (new.out, old.out)):
-            assert torch.equal(_bits(a), _bits(b))
+            assert torch.equal(bits(a), bits(b))
         assert new.status() == 0 == old.status()
 
 
@@ -302,13 +225,13 @@ def test_wide_rows_reread_the_weights(q):
     and every id = 1: 16 rows on one expert, so gate_up's second batch re-reads the weights."""
     T, E, topk, H, N = 16, 2, 1, 2176, 256
     g = torch.Generator().manual_seed(740)
-    gate_up, down = _f16_weights(g, E, H, N, 0)
+    gate_up, down = f16_weights(g, E, H, N, 0)
     ffn = moe.MoEFFN(gate_up, down, [(q, q)] * E, num_routed=E)
     df = moe.DecodeForwardWo(ffn, T, topk)
-    _guard(df)
-    ids, wts, _ = _routing(g, T, E, topk)
+    guard(df)
+    ids, wts, _ = routing(g, T, E, topk)
     ids.fill_(1)
-    mid = _check_stages(df, ffn, _hidden(g, T, H), ids, wts, None, stages=("close",))
+    mid = check_stages(df, ffn, hidden(g, T, H), ids, wts, None, stages=("close",))
     assert mid["routing"].counts == [0, 16]
     assert df.status() == 0
 
@@ -321,9 +244,9 @@ def test_bf16_ends():
     bit, and y equals the fp16 layer's y on hidden.to(torch.float16) — the row is converted as it is loaded."""
     T, topk, E, H, N, Ns = 16, 2, 4, 384, 384, 640
     g = torch.Generator().manual_seed(750)
-    _, down = _f16_weights(g, E, H, N, Ns)
+    _, down = f16_weights(g, E, H, N, Ns)
     gate_up = [_grid_weight(g, 2 * n, H, W4A16_ASYM)[0] for n in [N] * E + [Ns]]
-    b1, b2 = _biases(g, E, H, N, Ns)
+    b1, b2 = biases(g, E, H, N, Ns)
     ffn = moe.MoEFFN(gate_up, down, [(W4A16_ASYM, W8A8)] * (E + 1), num_routed=E, gate_up_bias=b1, down_bias=b2,
                      activation=moe.SwigluClamp())
     bf = torch.bfloat16
@@ -332,17 +255,17 @@ def test_bf16_ends():
     block = moe.MoEBlock(ffn, w_gate, topk, renormalize=True, w_shared_gate=w_sg)
     df = moe.DecodeForwardWo(block, T, dtype=bf)
     assert df.out.dtype == bf
-    h = _hidden(g, T, H, grid=True, dtype=bf)
+    h = hidden(g, T, H, grid=True, dtype=bf)
     got = df.launch(h).clone()
     want, mid = block.forward(h, return_intermediates=True)
     torch.cuda.synchronize()
     assert torch.equal(df.gate_out[0], mid["topk_ids"])
-    assert got.dtype == bf and torch.equal(_bits(got), _bits(want))
+    assert got.dtype == bf and torch.equal(bits(got), bits(want))
     df16 = moe.DecodeForwardWo(ffn, T, topk)
     df16.launch(h.to(torch.float16), mid["topk_ids"], mid["topk_weights"], mid["shared_w"])
     torch.cuda.synchronize()
-    assert torch.equal(_bits(df.y), _bits(df16.y)) and torch.equal(_bits(df.ys), _bits(df16.ys))
-    assert torch.equal(_bits(df.y), _bits(mid["y"][mid["routing"].inv_slot.long()]))
+    assert torch.equal(bits(df.y), bits(df16.y)) and torch.equal(bits(df.ys), bits(df16.ys))
+    assert torch.equal(bits(df.y), bits(mid["y"][mid["routing"].inv_slot.long()]))
     assert df.status() == 0
     with pytest.raises(ValueError):
         df.launch(h.to(torch.float16))
@@ -353,13 +276,13 @@ def test_block_under_a_graph():
     combine — and replayed on two hidden states: each replay equals the uncaptured launch bit for bit."""
     T, E, topk, H, N, Ns = 7, 8, 2, 384, 256, 640
     g = torch.Generator().manual_seed(760)
-    gate_up, down = _f16_weights(g, E, H, N, Ns)
+    gate_up, down = f16_weights(g, E, H, N, Ns)
     qcfg = [SCHEME[e % 5] for e in range(E)] + [SCHEME[5]]
     ffn = moe.MoEFFN(gate_up, down, qcfg, num_routed=E)
     w_gate = (torch.randn(E, H, generator=g) * H ** -0.5).half().to(DEV)
     block = moe.MoEBlock(ffn, w_gate, topk, renormalize=True)
     df, ref = moe.DecodeForwardWo(block, T), moe.DecodeForwardWo(block, T)
-    hiddens = [_hidden(g, T, H) for _ in range(2)]
+    hiddens = [hidden(g, T, H) for _ in range(2)]
     static_hidden = hiddens[0].clone()
     side = torch.cuda.Stream()
     side.wait_stream(torch.cuda.current_stream())
@@ -379,7 +302,7 @@ def test_block_under_a_graph():
         torch.cuda.synchronize()
         assert torch.equal(df.gate_out[0], ref.gate_out[0])
         for a, b in ((df.act, ref.act), (df.y, ref.y), (df.out, want)):
-            assert torch.equal(_bits(a), _bits(b))
+            assert torch.equal(bits(a), bits(b))
         seen.append(df.gate_out[0].clone())
     assert not torch.equal(seen[0], seen[1])  # two routings
     eager = block.forward(hiddens[1])
@@ -395,19 +318,19 @@ def test_bad_ids_and_short_calls_keep_their_guard(scheme_layer):
     ffn, cap, T, topk = scheme_layer, 16, 7, 2
     g = torch.Generator().manual_seed(770)
     df = moe.DecodeForwardWo(ffn, cap, topk)
-    _guard(df)
-    ids, wts, sw = _routing(g, T, ffn.E, topk)
+    guard(df)
+    ids, wts, sw = routing(g, T, ffn.E, topk)
     ids[2, 0], ids[5, 1] = ffn.E, -1
     bad = [2 * topk + 0, 5 * topk + 1]
-    out = df.launch(_hidden(g, T, ffn.H), ids, wts, sw)
+    out = df.launch(hidden(g, T, ffn.H), ids, wts, sw)
     torch.cuda.synchronize()
     good = [p for p in range(T * topk) if p not in bad]
     for t in (df.act, df.y):
-        assert (_bits(t[bad]) == GUARD).all() and (_bits(t[T * topk:]) == GUARD).all()
-        assert not (_bits(t[good]) == GUARD).all(dim=1).any()
+        assert (bits(t[bad]) == GUARD).all() and (bits(t[T * topk:]) == GUARD).all()
+        assert not (bits(t[good]) == GUARD).all(dim=1).any()
     for t in (df.act_shared, df.ys):
-        assert (_bits(t[T:]) == GUARD).all() and not (_bits(t[:T]) == GUARD).all(dim=1).any()
-    assert (_bits(df.out[T:]) == GUARD).all() and out.shape[0] == T
+        assert (bits(t[T:]) == GUARD).all() and not (bits(t[:T]) == GUARD).all(dim=1).any()
+    assert (bits(df.out[T:]) == GUARD).all() and out.shape[0] == T
     assert torch.isfinite(out[[t for t in range(T) if t not in (2, 5)]].float()).all()
     assert df.status(reset=True) == nat.DECODE_BAD_ID and df.status() == 0
 
@@ -419,14 +342,14 @@ def test_kind_outside_the_mask_writes_nothing(scheme_layer):
     g = torch.Generator().manual_seed(780)
     df = moe.DecodeForwardWo(ffn, T, topk)
     df.mask1 = df.mask2 = 1 << nat.DECODE_W8A8
-    _guard(df)
-    ids, wts, sw = _routing(g, T, ffn.E, topk)
-    df.launch(_hidden(g, T, ffn.H), ids, wts, sw)
+    guard(df)
+    ids, wts, sw = routing(g, T, ffn.E, topk)
+    df.launch(hidden(g, T, ffn.H), ids, wts, sw)
     torch.cuda.synchronize()
     flat = ids.view(-1).tolist()
     for buf, lin in ((df.act, 0), (df.y, 1)):
         for p, e in enumerate(flat):
-            written = not (_bits(buf[p]) == GUARD).all()
+            written = not (bits(buf[p]) == GUARD).all()
             assert written == (SCHEME[e][lin] is W8A8), (p, e, lin)
-    assert (_bits(df.act_shared) == GUARD).all() and (_bits(df.ys) == GUARD).all()
+    assert (bits(df.act_shared) == GUARD).all() and (bits(df.ys) == GUARD).all()
     assert df.status(reset=True) == nat.DECODE_BAD_KIND
