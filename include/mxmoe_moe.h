@@ -40,7 +40,7 @@ enum {
                           * canonical nibble order, scale bytes in the GroupGEMM's device layout;
                           * through mxmoe_moe_act_quant with bit 4 of tag_mask only               */
   /* 5 is NOT assigned: a tag_mask with bit 5 stays "unknown activation tag" */
-  MXMOE_ACT_MXFP8 = 6    /* OCP MXFP8, e4m3 elements (w4a8_g32_sym_MXFP8): one code byte per element
+  MXMOE_ACT_MXFP8 = 6,   /* OCP MXFP8, e4m3 elements (w4a8_g32_sym_MXFP8): one code byte per element
                           * (torch.float8_e4m3fn's bit patterns), one e8m0 scale per (token, 32-element
                           * block) in the device layout, as MXFP4's. Per block: e = floor(log2 amax) - 8
                           * clamped to [-127, 127], scale code e + 127; an all-zero block: scale code 0
@@ -48,6 +48,21 @@ enum {
                           * element is multiplied by 2^-e exactly, saturated at +-448 and rounded to
                           * e4m3 once, to nearest even (-0 keeps its sign). quantize.quant_mxfp8 is
                           * the same rule. Through mxmoe_moe_act_quant with bit 6 of tag_mask only  */
+  /* 7 is NOT assigned: a tag_mask with bit 7 stays "unknown activation tag" */
+  MXMOE_ACT_E4M3 = 8     /* per-token OCP e4m3 (w8a8_g-1_sym_E4M3): one code byte per element (torch.float8_e4m3fn's
+                          * bit patterns) in MXMOE_ACT_INT8's byte order (pack_wxax 8-bit: element 2j in the high byte
+                          * of its 16-bit word), one fp16 scale per row at scales[scale_off + row]: the A operand of
+                          * the E4M3 GroupGEMM tile as it reads it. A row whose values are all finite: amax = the
+                          * row's largest |x| (the fp16 values as f32); s = fp16_rn(amax / 448), 1.0 for an all-zero
+                          * row, clamped from below to 0x0400 (2^-14: never subnormal); code =
+                          * e4m3_rn_sat(f32(x) / f32(s)) — the correctly rounded f32 quotient, rounded ONCE to e4m3
+                          * to nearest even and saturated at +-448; -0 and values that round to zero keep their
+                          * sign (-0 -> 0x80). quantize.quant_e4m3 and the oracle's oracle_quant_e4m3 are the same
+                          * rule. A row holding +-Inf or NaN (a bf16 hidden value beyond 65504 becomes one in the
+                          * gather): every code 0x00 and the scale fp16 NaN 0x7E00, so the GroupGEMM's outputs of
+                          * that slot are NaN and the fault stays visible (neither the oracle's nor torch's answer
+                          * for such a row is kept). Through mxmoe_moe_act_quant, mxmoe_moe_gather_quant and
+                          * mxmoe_moe_glu_quant with bit 8 of tag_mask only */
 };
 
 /* One expert's segment of a permuted activation buffer. Slots (rows of the permuted batch) are
@@ -59,7 +74,7 @@ typedef struct mxmoe_moe_seg {
   int32_t rows;        /* tokens routed to this expert                                        */
   int32_t width;       /* elements per row of this segment's output (K of the next GEMM)      */
   int64_t out_off;     /* byte offset of the segment's [rows][width * bits / 8] block in `out` */
-  int64_t scale_off;   /* fp16-element offset of its scales: [rows] or [width/128][rows];
+  int64_t scale_off;   /* fp16-element offset of its scales: [rows] (INT8, INT4, E4M3) or [width/128][rows];
                         * MXFP4 / MXFP8: of its [rows][16 ceil(width/32 / 16)] e8m0 bytes (even offset: the
                         * block is 4-byte aligned)                                              */
 } mxmoe_moe_seg;
@@ -208,7 +223,7 @@ int mxmoe_moe_route(const int32_t* topk_ids, int64_t T, int topk, int E, int32_t
  * shared expert), the routed segments' width and the shared one's. Written, per segment in expert order:
  *   segs[e]   {qtag, first_slot = rows before e (shared: T * topk), rows = counts[e] (shared: T), width,
  *              out_off, scale_off}: out_off advances by the segment's bytes rounded up to 16, scale_off by its
- *              scale elements ([rows], g128 [width/128][rows], MXFP4 / MXFP8 rows * 16 ceil(width/32 / 16) / 2
+ *              scale elements ([rows] for INT8 / INT4 / E4M3, g128 [width/128][rows], MXFP4 / MXFP8 rows * 16 ceil(width/32 / 16) / 2
  *              after rounding scale_off up to even, fp16 none);
  *   dyn[e]    (optional, mxmoe_gg_dyn_row of include/mxmoe_gg.h: the row table of the GroupGEMM that reads the
  *              buffer) {rows, a_off = out_off, sa_off = 2 * scale_off, c_off = 2 * first_slot * ldc; shared: 0}.
@@ -242,8 +257,9 @@ int mxmoe_moe_quant_act(const void* hidden, int64_t T, int K, int topk, int with
                         const int32_t* sorted_expert, const int32_t* perm_token, const mxmoe_moe_seg* segs, int nseg,
                         void* out, void* scales, void* stream);
 
-/* mxmoe_moe_quant_act with the element type of hidden as an argument and mxmoe_moe_act_quant's tag_mask (bits 4 / 6
- * select the builds that carry MXMOE_ACT_MXFP4 / MXMOE_ACT_MXFP8; an unknown bit: MXMOE_GG_ERR_UNSUPPORTED).
+/* mxmoe_moe_quant_act with the element type of hidden as an argument and mxmoe_moe_act_quant's tag_mask (bits 4 / 6 / 8
+ * select the builds that carry MXMOE_ACT_MXFP4 / MXMOE_ACT_MXFP8 / MXMOE_ACT_E4M3; an unknown bit:
+ * MXMOE_GG_ERR_UNSUPPORTED).
  * Replaces: nothing in the reference (fp16 only).
  *   dtype    MXMOE_DT_FP16: mxmoe_moe_quant_act's (mxmoe_moe_act_quant mode 0's) kernels and bytes.
  *            MXMOE_DT_BF16: hidden is bf16 [T][K]. Each element is converted to fp16 as it is loaded — widened to f32
@@ -289,7 +305,8 @@ int mxmoe_moe_quant_slots(const void* routed_in, const void* shared_in, int64_t 
  * MXMOE_ACT_MXFP4: the kernel builds with the MXFP4 code run only when bit 4 is set, so the four named
  * entry points (and any call here without the bit) keep the builds they had before the tag existed
  * and must not be given such a segment — they would treat it as int4. MXMOE_ACT_MXFP8 segments
- * likewise need bit 6. A mask with bit 5 or a bit above 6 is MXMOE_GG_ERR_UNSUPPORTED.
+ * likewise need bit 6, MXMOE_ACT_E4M3 segments bit 8 (builds of their own, which carry the MX tags too: a call may
+ * set bit 8 together with bit 4 or 6, a mixed layer). A mask with bit 5, bit 7 or a bit above 8 is MXMOE_GG_ERR_UNSUPPORTED.
  *   mode 0: mxmoe_moe_quant_act      (routed_in = hidden [T][N], N = K; shared_in != NULL <=> with_shared,
  *                                     its value is ignored; perm_token required)
  *   mode 1: mxmoe_moe_silu_mul_quant, 2: mxmoe_moe_quant_slots, 3: mxmoe_moe_silu_mul_quant_il
@@ -301,7 +318,7 @@ int mxmoe_moe_act_quant(int mode, const void* routed_in, const void* shared_in, 
 
 /* The activation pass of a layer whose gate_up projection has a bias and / or whose gated activation is not
  * SiLU (gpt-oss): mxmoe_moe_silu_mul_quant's inputs, segments, outputs and limits (mode 1: [gate | up] columns),
- * tag_mask as in mxmoe_moe_act_quant (every tag, MXFP4 and MXFP8 with their bits).
+ * tag_mask as in mxmoe_moe_act_quant (every tag; MXFP4, MXFP8 and E4M3 with their bits).
  * Replaces: nothing in the reference; the clamped activation is GptOssExperts._apply_gate's public code.
  * For slot s of expert e = sorted_expert[s] (the shared segment: bias_shared) and column n, all in f32:
  *   g = f32(in[s][n]) + f32(bg[e][n]),  u = f32(in[s][N + n]) + f32(bu[e][n])   (one IEEE add each; a NULL bias:

@@ -305,6 +305,44 @@ __device__ __forceinline__ void mx_store_scale(uint8_t* so, int blk, int nblk, b
   }
 }
 
+// The per-token e4m3 tag (MXMOE_ACT_E4M3, include/mxmoe_moe.h).
+// amax8_bits: max |x| over 8 fp16 as the largest sign-cleared bit pattern (v_pk_max_u16; the patterns' order is the
+// values', with Inf / NaN on top: a result >= 0x7C00 means an Inf or a NaN among them)
+typedef uint16_t us2_t __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ uint32_t amax8_bits(const h8_t& x) {
+  const uint4 w = __builtin_bit_cast(uint4, x);
+  const uint32_t m = 0x7FFF7FFFu;
+  const us2_t a = __builtin_elementwise_max(__builtin_bit_cast(us2_t, w.x & m), __builtin_bit_cast(us2_t, w.y & m));
+  const us2_t b = __builtin_elementwise_max(__builtin_bit_cast(us2_t, w.z & m), __builtin_bit_cast(us2_t, w.w & m));
+  const us2_t c = __builtin_elementwise_max(a, b);
+  return max((uint32_t)c[0], (uint32_t)c[1]);
+}
+// codes_e4m3: 8 elements -> 8 code bytes in pack_wxax's 8-bit order (bytes [q1, q0, q3, q2, ...]).
+// The tag's contract is e4m3_rn_sat of the correctly rounded f32 quotient x / s. The IEEE divide sequence costs ~10
+// VALU per element; here r = the correctly rounded 1 / s (once per row), q = x * r and one residual step
+// q' = q + (x - q s) r, which is within 0.5 ulp (+ 2^-46 relative) of x / s in f32. Both q' and the IEEE quotient
+// round to the same code: a point where the e4m3 rounding (or the clamp at 448) changes is a value of at most 5
+// significant bits, x and s have 11, so x / s either IS such a point — then it is an f32 and both sequences return it
+// exactly — or is more than 2^-16 (relative) away from it (x - P s is a non-zero multiple of the finer of x's and
+// P s's grids, P s having at most 16 bits): over a hundred f32 ulps. tests/test_e4m3_layer.py checks this over every
+// pair of fp16 significands. x = -0 leaves q' = +0 (the residual is +0), so the sign is copied from x (s > 0).
+// The clamp at +-448 (v_med3_f32) precedes the hardware convert, which rounds once to OCP e4m3, to nearest even.
+__device__ __forceinline__ uint2 codes_e4m3(const h8_t& x, float s, float r) {
+  float y[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const float xf = (float)x[j];
+    const float q = xf * r;
+    y[j] = __builtin_amdgcn_fmed3f(__builtin_copysignf(fmaf(fmaf(-q, s, xf), r, q), xf), -448.0f, 448.0f);
+  }
+  int q0 = 0, q1 = 0;
+  q0 = __builtin_amdgcn_cvt_pk_fp8_f32(y[1], y[0], q0, false);
+  q0 = __builtin_amdgcn_cvt_pk_fp8_f32(y[3], y[2], q0, true);
+  q1 = __builtin_amdgcn_cvt_pk_fp8_f32(y[5], y[4], q1, false);
+  q1 = __builtin_amdgcn_cvt_pk_fp8_f32(y[7], y[6], q1, true);
+  return uint2{(uint32_t)q0, (uint32_t)q1};
+}
+
 // One WAVE per slot row (4 rows per 256-thread workgroup): lane l holds elements c*512 + 8l .. +7
 // of chunk c in registers (MAXC chunks: rows up to MAXC*512 elements, MAXC = the launch's widest
 // row in 512-element chunks), so every lane has MAXC independent 16-B loads in flight, the
@@ -326,8 +364,18 @@ __device__ __forceinline__ void mx_store_scale(uint8_t* so, int blk, int nblk, b
 // gated activation. kGluNone: none of that code exists and the builds are the ones above.
 // SRCBF (MODE 0 only; mxmoe_moe_gather_quant): hidden holds bf16; every 16-B load is converted to fp16 as it arrives
 // (bf16x8_to_f16) and nothing after the loads differs. SRCBF = false: the builds above, as they were.
-template <int MODE, int MAXC, bool MX = false, int GLU = kGluNone, bool SRCBF = false>
+// kActF8 (a flag on the MODE argument, MODEF = MODE | kActF8): the builds that also carry the MXMOE_ACT_E4M3 tag,
+// launched only for calls whose tag_mask has bit 8. They carry the block-scaled tags too (MX = true), so one family
+// serves an E4M3 layer and a layer that mixes E4M3 with MX experts (a second family without the MX code would be 63
+// more kernels to compile). The flag rides on MODE so that the template's parameter list, and with it the name and
+// the code of every build without the flag, stay what they were before the tag existed: in those none of its code
+// exists.
+constexpr int kActF8 = 8;
+template <int MODEF, int MAXC, bool MX = false, int GLU = kGluNone, bool SRCBF = false>
 __global__ __launch_bounds__(kThreads) void act_quant_kernel(typename ActArgsOf<GLU>::type a) {
+  constexpr int MODE = MODEF & ~kActF8;
+  constexpr bool F8 = (MODEF & kActF8) != 0;
+  static_assert(!F8 || MX, "the E4M3 builds carry the MX tags too");
   constexpr bool SILU = MODE == 1 || MODE == 3;
   static_assert(GLU == kGluNone || MODE == 1, "the GLU builds read [gate | up] columns");
   static_assert(!SRCBF || MODE == 0, "only the gather reads bf16 rows: the gate_up output stays fp16");
@@ -500,6 +548,37 @@ __global__ __launch_bounds__(kThreads) void act_quant_kernel(typename ActArgsOf<
     }
     return;
   }
+  if constexpr (F8) if (sg.qtag == MXMOE_ACT_E4M3) {
+    // per-token e4m3 (include/mxmoe_moe.h): the row amax as a bit pattern (chunks past the row are zeros), across the
+    // wave by a butterfly and, for a split row, across its 4 waves through LDS as the INT8 tag's
+    uint32_t mi = 0;
+#pragma unroll
+    for (int c = 0; c < MAXC; ++c) mi = max(mi, amax8_bits(x[c]));
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) mi = max(mi, (uint32_t)__shfl_xor((int)mi, d, 64));
+    if (split_row) {  // every wave of the workgroup reaches here (its row's checks are uniform)
+      if (lane == 0) wave_amax[part] = __builtin_bit_cast(float, mi);
+      __syncthreads();
+      mi = max(max(__builtin_bit_cast(uint32_t, wave_amax[0]), __builtin_bit_cast(uint32_t, wave_amax[1])),
+               max(__builtin_bit_cast(uint32_t, wave_amax[2]), __builtin_bit_cast(uint32_t, wave_amax[3])));
+    }
+    const bool bad = mi >= 0x7C00u;  // an Inf or a NaN in the row: NaN scale, zero codes
+    // s = fp16_rn(amax / 448) (the f32 quotient correctly rounded), at least 2^-14, 1 for a zero row
+    _Float16 sc = (_Float16)((float)__builtin_bit_cast(_Float16, (uint16_t)mi) / 448.0f);
+    if (__builtin_bit_cast(uint16_t, sc) < 0x0400u) sc = __builtin_bit_cast(_Float16, (uint16_t)0x0400u);
+    if (mi == 0) sc = (_Float16)1;
+    if (bad) sc = __builtin_bit_cast(_Float16, (uint16_t)0x7E00u);
+    if (lane == 0 && part == 0) a.scales[sg.scale_off + row] = sc;
+    const float s = (float)sc, r = 1.0f / s;  // (the IEEE division: once per row)
+    uint8_t* const o8 = a.out + sg.out_off + row * (int64_t)sg.width + col0;
+    uint2 q[MAXC];
+#pragma unroll
+    for (int c = 0; c < MAXC; ++c) q[c] = codes_e4m3(x[c], s, r);
+#pragma unroll
+    for (int c = 0; c < MAXC; ++c)
+      if (c * 512 + lane * 8 < width) *reinterpret_cast<uint2*>(o8 + c * 512 + lane * 8) = bad ? uint2{0u, 0u} : q[c];
+    return;
+  }
   const int bits = sg.qtag == MXMOE_ACT_INT8 ? 8 : 4;
   const float qmax = bits == 8 ? 127.0f : 7.0f;
   const h2_t lim = {(_Float16)qmax, (_Float16)qmax};
@@ -635,7 +714,7 @@ bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 // clamp means the counts are not route's); a clamp or a sum below T * topk (ids outside [0, E)) sets bit 0
 // of the returned status.
 __host__ __device__ inline int act_bits(int tag) {
-  return tag == MXMOE_ACT_INT8 || tag == MXMOE_ACT_MXFP8 ? 8
+  return tag == MXMOE_ACT_INT8 || tag == MXMOE_ACT_MXFP8 || tag == MXMOE_ACT_E4M3 ? 8
          : tag == MXMOE_ACT_INT4 || tag == MXMOE_ACT_INT4_G128 || tag == MXMOE_ACT_MXFP4 ? 4 : 16;
 }
 __host__ __device__ inline int32_t fill_segments(const int32_t* counts, int E, int64_t T, int topk, bool with_shared,
@@ -714,47 +793,59 @@ int segments_check(const int32_t* counts, int E, int64_t T, int topk, const mxmo
 using namespace mxmoe;
 
 // registers sized to the widest row of the launch, in 512-element chunks (1408 -> 3, 2048 -> 4)
-template <int MODE, bool MX, int GLU = kGluNone, bool SRCBF = false>
+// F8: the kActF8 builds (the MXMOE_ACT_E4M3 tag and the MX tags; MX is then not read)
+template <int MODE, bool MX, bool F8, int GLU = kGluNone, bool SRCBF = false>
 static void launch_act_w(const typename ActArgsOf<GLU>::type& a, int maxw, hipStream_t st) {
   const int64_t blocks = a.parts > 1 ? a.blk_shared + (a.nslots - a.ntk)
                                      : (a.nslots - a.s0 + kThreads / 64 - 1) / (kThreads / 64);
   const dim3 grid((unsigned)blocks), block(kThreads);
   const int nc = (maxw + 511) / 512;
-  if (nc <= 1) hipLaunchKernelGGL((act_quant_kernel<MODE, 1, MX, GLU, SRCBF>), grid, block, 0, st, a);
-  else if (nc <= 2) hipLaunchKernelGGL((act_quant_kernel<MODE, 2, MX, GLU, SRCBF>), grid, block, 0, st, a);
-  else if (nc <= 3) hipLaunchKernelGGL((act_quant_kernel<MODE, 3, MX, GLU, SRCBF>), grid, block, 0, st, a);
-  else if (nc <= 4) hipLaunchKernelGGL((act_quant_kernel<MODE, 4, MX, GLU, SRCBF>), grid, block, 0, st, a);
-  else if (nc <= 6) hipLaunchKernelGGL((act_quant_kernel<MODE, 6, MX, GLU, SRCBF>), grid, block, 0, st, a);
-  else if (nc <= 8) hipLaunchKernelGGL((act_quant_kernel<MODE, 8, MX, GLU, SRCBF>), grid, block, 0, st, a);
-  else if (nc <= 12) hipLaunchKernelGGL((act_quant_kernel<MODE, 12, MX, GLU, SRCBF>), grid, block, 0, st, a);
-  else if (nc <= 16) hipLaunchKernelGGL((act_quant_kernel<MODE, 16, MX, GLU, SRCBF>), grid, block, 0, st, a);
-  else hipLaunchKernelGGL((act_quant_kernel<MODE, 32, MX, GLU, SRCBF>), grid, block, 0, st, a);
+  const auto go = [&](auto maxc) {
+    constexpr int C = decltype(maxc)::value;
+    if constexpr (F8) hipLaunchKernelGGL((act_quant_kernel<MODE | kActF8, C, true, GLU, SRCBF>), grid, block, 0, st, a);
+    else hipLaunchKernelGGL((act_quant_kernel<MODE, C, MX, GLU, SRCBF>), grid, block, 0, st, a);
+  };
+  if (nc <= 1) go(std::integral_constant<int, 1>{});
+  else if (nc <= 2) go(std::integral_constant<int, 2>{});
+  else if (nc <= 3) go(std::integral_constant<int, 3>{});
+  else if (nc <= 4) go(std::integral_constant<int, 4>{});
+  else if (nc <= 6) go(std::integral_constant<int, 6>{});
+  else if (nc <= 8) go(std::integral_constant<int, 8>{});
+  else if (nc <= 12) go(std::integral_constant<int, 12>{});
+  else if (nc <= 16) go(std::integral_constant<int, 16>{});
+  else go(std::integral_constant<int, 32>{});
 }
 
 constexpr int kModeGatherBf16 = 4;  // launch_act_any's number for mode 0 on bf16 rows (no mode of the C interface)
-// (mode, mx): which build of the kernel; ActArgs: the four passes, GluArgs: mxmoe_moe_glu_quant's (mode = MXMOE_GLU_*)
+// The tags a call's tag_mask names beyond the integer ones: which builds of the kernel run it
+struct ActTags {
+  bool mx = false;  // MXMOE_ACT_MXFP4 or MXMOE_ACT_MXFP8 (the MX builds)
+  bool f8 = false;  // MXMOE_ACT_E4M3 (the kActF8 builds, which carry the MX tags as well)
+};
+// (mode, tags): which build of the kernel; ActArgs: the four passes, GluArgs: mxmoe_moe_glu_quant's (mode = MXMOE_GLU_*)
 template <class ARGS>
-static void launch_act_any(int mode, const ARGS& a, int maxw, bool mx, hipStream_t st) {
-  const auto go = [&](auto mx_build) {
-    constexpr bool MX = decltype(mx_build)::value;
+static void launch_act_any(int mode, const ARGS& a, int maxw, ActTags tags, hipStream_t st) {
+  const auto go = [&](auto mx_build, auto f8_build) {
+    constexpr bool MX = decltype(mx_build)::value, F8 = decltype(f8_build)::value;
     if constexpr (std::is_same<ARGS, GluArgs>::value) {
-      if (mode == MXMOE_GLU_SWIGLU_CLAMP) launch_act_w<1, MX, kGluSwigluClamp>(a, maxw, st);
-      else launch_act_w<1, MX, kGluSilu>(a, maxw, st);
-    } else if (mode == 1) launch_act_w<1, MX>(a, maxw, st);
-    else if (mode == 2) launch_act_w<2, MX>(a, maxw, st);
-    else if (mode == 3) launch_act_w<3, MX>(a, maxw, st);
-    else if (mode == kModeGatherBf16) launch_act_w<0, MX, kGluNone, true>(a, maxw, st);
-    else launch_act_w<0, MX>(a, maxw, st);
+      if (mode == MXMOE_GLU_SWIGLU_CLAMP) launch_act_w<1, MX, F8, kGluSwigluClamp>(a, maxw, st);
+      else launch_act_w<1, MX, F8, kGluSilu>(a, maxw, st);
+    } else if (mode == 1) launch_act_w<1, MX, F8>(a, maxw, st);
+    else if (mode == 2) launch_act_w<2, MX, F8>(a, maxw, st);
+    else if (mode == 3) launch_act_w<3, MX, F8>(a, maxw, st);
+    else if (mode == kModeGatherBf16) launch_act_w<0, MX, F8, kGluNone, true>(a, maxw, st);
+    else launch_act_w<0, MX, F8>(a, maxw, st);
   };
-  if (mx) go(std::true_type{});
-  else go(std::false_type{});
+  if (tags.f8) go(std::true_type{}, std::true_type{});
+  else if (tags.mx) go(std::true_type{}, std::false_type{});
+  else go(std::false_type{}, std::false_type{});
 }
 // slots [0, nslots): one launch; rows of different widths (routed [0, ntk), shared [ntk, nslots)):
 // one launch with each shared row split over a workgroup's 4 waves when a quarter of the shared row
 // fits the routed rows' register width, else two launches, each with the register row of its width
-// mx: a segment of the call carries MXMOE_ACT_MXFP4 or MXMOE_ACT_MXFP8 (the MX builds of the kernel)
+// tags: the call's segments may carry the MX tags / MXMOE_ACT_E4M3 (the builds of the kernel that hold their code)
 template <class ARGS>
-static int launch_act(int mode, ARGS a, int64_t nslots, int w_routed, int w_shared, void* stream, bool mx = false) {
+static int launch_act(int mode, ARGS a, int64_t nslots, int w_routed, int w_shared, void* stream, ActTags tags = {}) {
   if (nslots == 0) return MXMOE_GG_OK;
   a.parts = 1;
   a.blk_shared = 0;
@@ -764,32 +855,32 @@ static int launch_act(int mode, ARGS a, int64_t nslots, int w_routed, int w_shar
     a.parts = 4;
     a.blk_shared = (a.ntk + kThreads / 64 - 1) / (kThreads / 64);
     a.nslots = nslots;
-    launch_act_any(mode, a, w_routed, mx, (hipStream_t)stream);
+    launch_act_any(mode, a, w_routed, tags, (hipStream_t)stream);
   } else {
     const bool split = nslots > a.ntk && w_routed != w_shared && a.ntk > 0;
     a.nslots = split ? a.ntk : nslots;
     const int w0 = split ? w_routed : (nslots > a.ntk ? (w_routed > w_shared ? w_routed : w_shared) : w_routed);
-    launch_act_any(mode, a, w0, mx, (hipStream_t)stream);
+    launch_act_any(mode, a, w0, tags, (hipStream_t)stream);
     if (split) {
       a.s0 = a.ntk;
       a.nslots = nslots;
-      launch_act_any(mode, a, w_shared, mx, (hipStream_t)stream);
+      launch_act_any(mode, a, w_shared, tags, (hipStream_t)stream);
     }
   }
   return launched("act_quant_kernel");
 }
 
-// the activation entry points' bodies; mx: the call's segments may carry MXMOE_ACT_MXFP4
+// the activation entry points' bodies; tags: what the call's tag_mask names (the four older entries: nothing)
 static int quant_act_impl(const char* fn, const void* hidden, int64_t T, int K, int topk, int with_shared,
                           const int32_t* sorted_expert, const int32_t* perm_token, const mxmoe_moe_seg* segs, int nseg,
-                          void* out, void* scales, void* stream, bool mx, bool src_bf16 = false) {
+                          void* out, void* scales, void* stream, ActTags tags, bool src_bf16 = false) {
   if (T < 0 || topk <= 0 || nseg <= 0 || K <= 0 || K % 128 || K > kMaxWidth)
     return fail(MXMOE_GG_ERR_INVALID, "%s: need K %% 128 == 0, K <= %d, topk > 0, nseg > 0 (K=%d)", fn, kMaxWidth, K);
   if (T > 0 && (!hidden || !sorted_expert || !perm_token || !segs || !out || !aligned16(hidden) || !aligned16(out)))
     return fail(MXMOE_GG_ERR_INVALID, "%s: NULL or misaligned pointer (hidden / out need 16 B)", fn);
   const ActArgs a{static_cast<const _Float16*>(hidden), static_cast<const _Float16*>(hidden), T * topk, 0, 0, K, 0, 0,
                   sorted_expert, perm_token, segs, nseg, static_cast<uint8_t*>(out), static_cast<_Float16*>(scales)};
-  return launch_act(src_bf16 ? kModeGatherBf16 : 0, a, T * topk + (with_shared ? T : 0), K, K, stream, mx);
+  return launch_act(src_bf16 ? kModeGatherBf16 : 0, a, T * topk + (with_shared ? T : 0), K, K, stream, tags);
 }
 static int slots_check(const char* fn, const void* routed_in, const void* shared_in, int64_t T, int topk, int N,
                        int N_shared, const int32_t* sorted_expert, const mxmoe_moe_seg* segs, int nseg, void* out) {
@@ -811,16 +902,18 @@ static ActArgs slot_args(const void* routed_in, const void* shared_in, int64_t T
 }
 static int slots_impl(const char* fn, int mode, const void* routed_in, const void* shared_in, int64_t T, int topk, int N,
                       int N_shared, const int32_t* sorted_expert, const mxmoe_moe_seg* segs, int nseg, void* out,
-                      void* scales, void* stream, bool mx) {
+                      void* scales, void* stream, ActTags tags) {
   if (int st = slots_check(fn, routed_in, shared_in, T, topk, N, N_shared, sorted_expert, segs, nseg, out)) return st;
   const ActArgs a = slot_args(routed_in, shared_in, T, topk, N, N_shared, sorted_expert, segs, nseg, out, scales);
-  return launch_act(mode, a, T * topk + (shared_in ? T : 0), N, shared_in ? N_shared : N, stream, mx);
+  return launch_act(mode, a, T * topk + (shared_in ? T : 0), N, shared_in ? N_shared : N, stream, tags);
 }
-// a tag_mask's check (MXMOE_GG_OK or the failure, under the entry point's name) and whether it names an MX tag
-static int tag_mask_mx(const char* fn, uint32_t tag_mask, bool* mx) {
-  if (tag_mask & ~((2u << MXMOE_ACT_MXFP4) - 1u | 1u << MXMOE_ACT_MXFP8))  // (tag 5 is not assigned)
+// a tag_mask's check (MXMOE_GG_OK or the failure, under the entry point's name) and which builds' tags it names
+static int tag_mask_tags(const char* fn, uint32_t tag_mask, ActTags* tags) {
+  // (tags 5 and 7 are not assigned)
+  if (tag_mask & ~((2u << MXMOE_ACT_MXFP4) - 1u | 1u << MXMOE_ACT_MXFP8 | 1u << MXMOE_ACT_E4M3))
     return fail(MXMOE_GG_ERR_UNSUPPORTED, "%s: unknown activation tag in mask %#x", fn, tag_mask);
-  *mx = ((tag_mask >> MXMOE_ACT_MXFP4) & 1) || ((tag_mask >> MXMOE_ACT_MXFP8) & 1);
+  tags->mx = ((tag_mask >> MXMOE_ACT_MXFP4) & 1) || ((tag_mask >> MXMOE_ACT_MXFP8) & 1);
+  tags->f8 = (tag_mask >> MXMOE_ACT_E4M3) & 1;
   return MXMOE_GG_OK;
 }
 // what mxmoe_moe_combine and mxmoe_moe_combine_bias check alike once T > 0
@@ -1101,7 +1194,7 @@ int mxmoe_moe_quant_act(const void* hidden, int64_t T, int K, int topk, int with
                         const int32_t* sorted_expert, const int32_t* perm_token, const mxmoe_moe_seg* segs, int nseg,
                         void* out, void* scales, void* stream) {
   return quant_act_impl("mxmoe_moe_quant_act", hidden, T, K, topk, with_shared, sorted_expert, perm_token, segs, nseg, out,
-                        scales, stream, false);
+                        scales, stream, ActTags{});
 }
 
 int mxmoe_moe_gather_quant(int dtype, const void* hidden, int64_t T, int K, int topk, int with_shared,
@@ -1109,9 +1202,9 @@ int mxmoe_moe_gather_quant(int dtype, const void* hidden, int64_t T, int K, int 
                            uint32_t tag_mask, void* out, void* scales, void* stream) {
   const char* fn = "mxmoe_moe_gather_quant";
   if (int st = dtype_check(fn, "dtype", dtype)) return st;
-  bool mx = false;
-  if (int st = tag_mask_mx(fn, tag_mask, &mx)) return st;
-  return quant_act_impl(fn, hidden, T, K, topk, with_shared, sorted_expert, perm_token, segs, nseg, out, scales, stream, mx,
+  ActTags tags;
+  if (int st = tag_mask_tags(fn, tag_mask, &tags)) return st;
+  return quant_act_impl(fn, hidden, T, K, topk, with_shared, sorted_expert, perm_token, segs, nseg, out, scales, stream, tags,
                         dtype == MXMOE_DT_BF16);
 }
 
@@ -1119,34 +1212,34 @@ int mxmoe_moe_silu_mul_quant(const void* routed_in, const void* shared_in, int64
                              const int32_t* sorted_expert, const mxmoe_moe_seg* segs, int nseg, void* out,
                              void* scales, void* stream) {
   return slots_impl("mxmoe_moe_silu_mul_quant", 1, routed_in, shared_in, T, topk, N, N_shared, sorted_expert, segs, nseg,
-                    out, scales, stream, false);
+                    out, scales, stream, ActTags{});
 }
 
 int mxmoe_moe_silu_mul_quant_il(const void* routed_in, const void* shared_in, int64_t T, int topk, int N,
                                 int N_shared, const int32_t* sorted_expert, const mxmoe_moe_seg* segs, int nseg,
                                 void* out, void* scales, void* stream) {
   return slots_impl("mxmoe_moe_silu_mul_quant_il", 3, routed_in, shared_in, T, topk, N, N_shared, sorted_expert, segs,
-                    nseg, out, scales, stream, false);
+                    nseg, out, scales, stream, ActTags{});
 }
 
 int mxmoe_moe_quant_slots(const void* routed_in, const void* shared_in, int64_t T, int topk, int N, int N_shared,
                           const int32_t* sorted_expert, const mxmoe_moe_seg* segs, int nseg, void* out, void* scales,
                           void* stream) {
   return slots_impl("mxmoe_moe_quant_slots", 2, routed_in, shared_in, T, topk, N, N_shared, sorted_expert, segs, nseg, out,
-                    scales, stream, false);
+                    scales, stream, ActTags{});
 }
 
 int mxmoe_moe_act_quant(int mode, const void* routed_in, const void* shared_in, int64_t T, int topk, int N, int N_shared,
                         const int32_t* sorted_expert, const int32_t* perm_token, const mxmoe_moe_seg* segs, int nseg,
                         uint32_t tag_mask, void* out, void* scales, void* stream) {
   if (mode < 0 || mode > 3) return fail(MXMOE_GG_ERR_INVALID, "mxmoe_moe_act_quant: mode must be 0..3 (mode=%d)", mode);
-  bool mx = false;
-  if (int st = tag_mask_mx("mxmoe_moe_act_quant", tag_mask, &mx)) return st;
+  ActTags tags;
+  if (int st = tag_mask_tags("mxmoe_moe_act_quant", tag_mask, &tags)) return st;
   if (mode == 0)
     return quant_act_impl("mxmoe_moe_act_quant", routed_in, T, N, topk, shared_in != nullptr, sorted_expert, perm_token,
-                          segs, nseg, out, scales, stream, mx);
+                          segs, nseg, out, scales, stream, tags);
   return slots_impl("mxmoe_moe_act_quant", mode, routed_in, shared_in, T, topk, N, N_shared, sorted_expert, segs, nseg, out,
-                    scales, stream, mx);
+                    scales, stream, tags);
 }
 
 int mxmoe_moe_glu_quant(const mxmoe_moe_glu* glu, const void* routed_in, const void* shared_in, int64_t T, int topk, int N,
@@ -1154,8 +1247,8 @@ int mxmoe_moe_glu_quant(const mxmoe_moe_glu* glu, const void* routed_in, const v
                         void* out, void* scales, void* stream) {
   const char* fn = "mxmoe_moe_glu_quant";
   if (int st = glu_check(fn, glu)) return st;
-  bool mx = false;
-  if (int st = tag_mask_mx(fn, tag_mask, &mx)) return st;
+  ActTags tags;
+  if (int st = tag_mask_tags(fn, tag_mask, &tags)) return st;
   if (int st = slots_check(fn, routed_in, shared_in, T, topk, N, N_shared, sorted_expert, segs, nseg, out)) return st;
   GluArgs a{};
   static_cast<ActArgs&>(a) = slot_args(routed_in, shared_in, T, topk, N, N_shared, sorted_expert, segs, nseg, out, scales);
@@ -1164,7 +1257,7 @@ int mxmoe_moe_glu_quant(const mxmoe_moe_glu* glu, const void* routed_in, const v
   a.nexp = nseg - (shared_in ? 1 : 0);
   a.c = -(glu->alpha * 1.4426950408889634f);
   a.limit = glu->limit;
-  return launch_act(glu->act, a, T * topk + (shared_in ? T : 0), N, shared_in ? N_shared : N, stream, mx);
+  return launch_act(glu->act, a, T * topk + (shared_in ? T : 0), N, shared_in ? N_shared : N, stream, tags);
 }
 
 int mxmoe_moe_combine_bias(const void* y, const int32_t* inv_slot, const int32_t* sorted_expert, const float* weights,

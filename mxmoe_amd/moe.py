@@ -35,7 +35,8 @@ from .groupgemm import DynamicGroupGemm, GroupGemm, Problem, QParams
 
 ACT_FP16, ACT_INT8, ACT_INT4, ACT_INT4_G128, ACT_MXFP4 = 0, 1, 2, 3, 4
 ACT_MXFP8 = 6  # MXMOE_ACT_MXFP8 (w4a8_g32_sym_MXFP8); 5 is not assigned (include/mxmoe_moe.h)
-_BITS = {ACT_FP16: 16, ACT_INT8: 8, ACT_INT4: 4, ACT_INT4_G128: 4, ACT_MXFP4: 4, ACT_MXFP8: 8}
+ACT_E4M3 = 8   # MXMOE_ACT_E4M3 (w8a8_g-1_sym_E4M3: e4m3 codes, one fp16 scale per token); 7 is not assigned either
+_BITS = {ACT_FP16: 16, ACT_INT8: 8, ACT_INT4: 4, ACT_INT4_G128: 4, ACT_MXFP4: 4, ACT_MXFP8: 8, ACT_E4M3: 8}
 _MX_TAGS = (ACT_MXFP4, ACT_MXFP8)  # block-scaled tags: e8m0 scale rows, the MX builds of the activation kernel
 
 
@@ -46,16 +47,20 @@ def _mx_scale_row(width: int) -> int:
 
 def _scale_elems(tag: int, width: int) -> int:
     """fp16 elements of scale store per row of a segment: the MX tags' e8m0 bytes two to an element, one scale per
-    128-element group for g128, none for fp16, else one per row."""
+    128-element group for g128, none for fp16, else (INT8, INT4, E4M3) one per row."""
     if tag in _MX_TAGS:
         return _mx_scale_row(width) // 2
     return width // 128 if tag == ACT_INT4_G128 else 0 if tag == ACT_FP16 else 1
 
 
-def qtag_of(a_bits: int, gsize: int) -> int:
-    """The reference's cvt_qparams_to_tag (ref_bind.cu:467-479); unsupported -> ValueError."""
+def qtag_of(a_bits: int, gsize: int, fmt: str = "") -> int:
+    """The reference's cvt_qparams_to_tag (ref_bind.cu:467-479); unsupported -> ValueError. ``fmt``: the QParams'
+    operand format; it matters for (8, -1) alone, where "E4M3" (w8a8_g-1_sym_E4M3) is a tag of its own and anything
+    else the integer one. A call without it behaves as before the E4M3 tag existed."""
     if a_bits >= 16:
         return ACT_FP16
+    if a_bits == 8 and gsize == -1 and fmt == "E4M3":
+        return ACT_E4M3
     if a_bits == 8 and gsize == -1:
         return ACT_INT8
     if a_bits == 4 and gsize == -1:
@@ -340,12 +345,13 @@ _ACT_MODES = {"gather": 0, "plain": 1, "fused": 2, "interleaved": 3}
 _LEGACY_ENTRY = {"gather": "mxmoe_moe_quant_act", "plain": "mxmoe_moe_silu_mul_quant", "fused": "mxmoe_moe_quant_slots",
                  "interleaved": "mxmoe_moe_silu_mul_quant_il"}
 _MX_MASK = _tag_mask(_MX_TAGS)
+_TAGGED_MASK = _MX_MASK | _tag_mask([ACT_E4M3])  # tags only the entries with a tag_mask carry (builds of their own)
 
 
 def _act_entry(mode: str, has_mx_tag: bool, glu: bool) -> str:
     """The C entry point of an activation pass: a gate_up bias or another activation (``glu``) needs
-    mxmoe_moe_glu_quant, which reads the plain layout only; any MX tag needs the tagged entry (the builds of the
-    kernel that carry those tags); everything else keeps the mode's own entry, which a library loaded through
+    mxmoe_moe_glu_quant, which reads the plain layout only; any MX tag or the E4M3 tag (``has_mx_tag``) needs the
+    tagged entry (the builds of the kernel that carry those tags); everything else keeps the mode's own entry, which a library loaded through
     MXMOE_GG_LIB that predates the tagged one still has."""
     if mode not in _ACT_MODES:
         raise ValueError(f"activation-pass mode must be one of {list(_ACT_MODES)}, got {mode!r}")
@@ -363,7 +369,7 @@ def _launch_act(mode: str, glu: Optional["nat.MoeGluC"], src: torch.Tensor, src_
     """One activation pass on preallocated buffers: exactly one native call, nothing allocated or converted.
     src / src_shared: hidden (and hidden again for a shared expert) with ``perm`` in "gather" mode, else the
     gate_up outputs; dsegs / nseg: the device segment table; mask: ``_tag_mask`` of the segments' tags."""
-    entry = _act_entry(mode, bool(mask & _MX_MASK), glu is not None)
+    entry = _act_entry(mode, bool(mask & _TAGGED_MASK), glu is not None)
     if src.dtype != torch.float16:  # only the gather reads another element type (bf16 rows: mxmoe_moe_gather_quant)
         if mode != "gather" or src.dtype not in _DT:
             raise ValueError(f"the activation pass reads fp16 (the gather: fp16 or bf16 hidden states), got {src.dtype} "
@@ -737,7 +743,8 @@ class ExpertWeights:
     q: QParams
     N: int
     K: int
-    scale_out_of_range: int = 0  # prepare_weight_mx: scale bytes outside [104, 140] (include/mxmoe_gg.h)
+    scale_out_of_range: int = 0  # prepare_weight_mx: scale bytes outside [104, 140] (include/mxmoe_gg.h);
+    #                              prepare_weight_e4m3: f32 scales that fp16 changed or that left its normal range
 
 
 def prepare_weight(w: torch.Tensor, q: QParams, interleave: bool = False) -> ExpertWeights:
@@ -745,8 +752,8 @@ def prepare_weight(w: torch.Tensor, q: QParams, interleave: bool = False) -> Exp
     gate_up weight ([gate; up] rows) reordered for the fused SiLU epilogue (interleave_gate_up; the
     per-row scales follow their rows)."""
     from .groupgemm import interleave_gate_up
-    from .quantize import (pack_mxfp4_scales, pack_weightonly_mi355x, pack_wxax, quant_mxfp4, quant_rtn_sym,
-                           quant_weightonly)
+    from .quantize import (pack_e4m3, pack_mxfp4_scales, pack_weightonly_mi355x, pack_wxax, quant_e4m3, quant_mxfp4,
+                           quant_rtn_sym, quant_weightonly)
 
     N, K = w.shape
     if interleave:
@@ -759,6 +766,9 @@ def prepare_weight(w: torch.Tensor, q: QParams, interleave: bool = False) -> Exp
     if q.is_weight_only:
         codes, sz = quant_weightonly(w, q.w_bits, q.gsize, q.sym)
         return ExpertWeights(pack_weightonly_mi355x(codes, q.w_bits), sz, q, N, K)
+    if q.is_fp8:  # w8a8_g-1_sym_E4M3: e4m3 codes in pack_wxax's 8-bit order, one fp16 scale per output row
+        codes, sc = quant_e4m3(w)
+        return ExpertWeights(pack_e4m3(codes), sc, q, N, K)
     qw, sw = quant_rtn_sym(w, q.w_bits, q.gsize)
     return ExpertWeights(pack_wxax(qw, q.w_bits), sw, q, N, K)
 
@@ -792,6 +802,38 @@ def prepare_weight_mx(codes: torch.Tensor, scales: torch.Tensor, q: QParams, war
         warnings.warn(f"prepare_weight_mx: {bad} of {scales.numel()} scale bytes lie outside [{lo}, {hi}]: with fp16 "
                       "activations their blocks' weights are not exact fp16 values (include/mxmoe_gg.h)", stacklevel=2)
     return ExpertWeights(codes.contiguous(), pack_mxfp4_scales(scales), q, N, K, bad)
+
+
+def prepare_weight_e4m3(codes: torch.Tensor, scales: torch.Tensor, warn: bool = True) -> ExpertWeights:
+    """Weights that already are per-channel FP8 (a checkpoint's ``weight`` / ``weight_scale``) -> the GroupGEMM's B
+    operand for w8a8_g-1_sym_E4M3, with no requantisation: codes ``float8_e4m3fn`` or uint8 [N, K] (OCP e4m3 bit
+    patterns, logical K order; K even) are put into pack_wxax's 8-bit byte order (``pack_e4m3``), scales [N] (or
+    [N, 1]; fp16 or f32, one per output row) are kept as fp16. The kernel multiplies by fp16 scales: an f32 scale is
+    rounded to nearest even, and ``scale_out_of_range`` of the result counts the scales whose value that changed or
+    that are not normal fp16 numbers (zero, subnormal, beyond 65504 or not finite — a weight row scaled by one of
+    those no longer is the checkpoint's); a non-zero count warns unless ``warn`` is False."""
+    from .groupgemm import W8A8_E4M3
+    from .quantize import pack_e4m3
+
+    if codes.dtype == torch.float8_e4m3fn:
+        codes = codes.view(torch.uint8)
+    if codes.dtype != torch.uint8 or codes.dim() != 2 or codes.shape[1] % 2:
+        raise ValueError("prepare_weight_e4m3: codes float8_e4m3fn or uint8 [N, K], K even")
+    N, K = codes.shape
+    if scales.dim() == 2 and scales.shape[1] == 1:
+        scales = scales[:, 0]
+    if scales.dtype not in (torch.float16, torch.float32) or tuple(scales.shape) != (N,):
+        raise ValueError(f"prepare_weight_e4m3: scales fp16 or f32 [{N}] (one per output row), got {scales.dtype} "
+                         f"{tuple(scales.shape)}")
+    sc = scales.to(torch.float16)
+    a = sc.float().abs()
+    bad = int(((sc.float() != scales.float()) | ~torch.isfinite(sc) | (a < 2.0 ** -14)).sum())
+    if bad and warn:
+        import warnings
+
+        warnings.warn(f"prepare_weight_e4m3: {bad} of {N} scales change value as fp16 or are no normal fp16 numbers: "
+                      "their rows are not the checkpoint's weights (include/mxmoe_gg.h: fp16 scale_b)", stacklevel=2)
+    return ExpertWeights(pack_e4m3(codes.contiguous()), sc.contiguous(), W8A8_E4M3, N, K, bad)
 
 
 def pad_cols(t: torch.Tensor, width: int) -> torch.Tensor:
@@ -848,7 +890,8 @@ class MoEFFN:
     stay fp16, and y is bit for bit the fp16 layer's on ``hidden.to(torch.float16)``."""
 
     # gate_up qcfgs with the SiLU epilogue: fp16 / w8a8 / w4a4 on every product kernel, weight-only
-    # on the small-batch kernel (wo3; a large call of those falls back to the interleaved form)
+    # on the small-batch kernel (wo3; a large call of those falls back to the interleaved form).
+    # w8a8_g-1_sym_E4M3 is not among them (its tile has no SiLU epilogue): a layer with an E4M3 gate_up is plain
     FUSE_QCFGS = ("fp16", "w8a8_g-1_sym", "w4a4_g-1_sym", "w4a8_g32_sym_MXFP8")
     FUSE_WEIGHT_ONLY = True
 
@@ -904,8 +947,8 @@ class MoEFFN:
 
         self.w1 = [prep(w, q[0], self.fuse_silu) for w, q in zip(gate_up, qcfg)]
         self.w2 = [prep(w, q[1]) for w, q in zip(down, qcfg)]
-        self.tag1 = [qtag_of(q[0].a_bits, q[0].gsize) for q in qcfg]
-        self.tag2 = [qtag_of(q[1].a_bits, q[1].gsize) for q in qcfg]
+        self.tag1 = [qtag_of(q[0].a_bits, q[0].gsize, q[0].fmt) for q in qcfg]
+        self.tag2 = [qtag_of(q[1].a_bits, q[1].gsize, q[1].fmt) for q in qcfg]
         self.gate_up_mode: Optional[str] = None  # None: the library decides; "interleaved": A/B override
 
     @property

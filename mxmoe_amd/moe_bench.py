@@ -1,5 +1,5 @@
 """Benchmarks of the MoE layer and its plumbing (mxmoe_amd/moe.py), and the torch composite the router is timed
-against: what tools/moe_layer_bench.py, graph_bench.py, gptoss_bench.py and gate_bench.py print, and bench.py's MoE
+against: what tools/moe_layer_bench.py, graph_bench.py, gptoss_bench.py, fp8_layer_bench.py and gate_bench.py print, and bench.py's MoE
 layer extras (through ``moe.qwen2_layer_bench``). Nothing here is on a layer's path."""
 from __future__ import annotations
 
@@ -200,6 +200,67 @@ def graph_forward_bench(batches: Sequence[int] = (128,), model: str = "qwen2_moe
         out["graph_device_over_planned_device"] = round(m("graph_device") / m("planned_device"), 4)
         out["bit_identical_to_eager"], out["bit_identical_to_planned"] = same, same_planned
         out["status"] = gf.status()
+        return out
+
+    for bs in batches:  # (a generator: a caller can print each size as it completes)
+        yield one(bs)
+
+
+def fp8_layer_bench(batches: Sequence[int] = (128, 512, 2048, 8192), rounds: int = 4, iters: int = 30):
+    """FP8 layers: the qwen2_moe layer-11 shape (60 routed experts, top-4, the shared expert; routing drawn from the
+    committed histogram, random weights) at every batch size of ``batches`` (yields one dict each) with every expert
+    w8a8_g-1_sym_E4M3 ("e4m3"), w8a8_g-1_sym ("w8a8") or fp16, each side a ``PlannedForward`` step on the same
+    weights, hidden states and routing, in one process with the sides alternating over rounds. All three run the
+    plain gate_up layout (fuse_silu=False: the E4M3 tile has no SiLU epilogue), so the two activation passes of the
+    e4m3 and w8a8 sides are the same launches on the same bytes but for the tag. Per side and stage the median of the
+    rounds' medians with min / max (us), the gate_up / down variants, and per activation pass whether the e4m3 median
+    lies inside the w8a8 side's own min - max over the rounds ("parity") with the ratio of the medians."""
+    from .groupgemm import FP16, W8A8, W8A8_E4M3
+
+    shapes, topk = load_workload(qwen2_layer11_workload(8192))["layer-11"], 4
+    E = len(shapes["gate_up"]) - 1
+    H = shapes["gate_up"][0].K
+    N, Ns = shapes["down"][0].K, shapes["down"][-1].K
+    dev = "cuda"
+    g = torch.Generator().manual_seed(0)
+    hist = torch.tensor([max(s.M, 1) for s in shapes["gate_up"][:E]], dtype=torch.float64)
+    mk = lambda n, k: ((torch.rand(n, k, generator=g) * 2 - 1) * 0.05).half().to(dev)
+    gate_up = [mk(2 * N, H) for _ in range(E)] + [mk(2 * Ns, H)]
+    down = [mk(H, N) for _ in range(E)] + [mk(H, Ns)]
+    layers = {name: MoEFFN(gate_up, down, [(q, q)] * (E + 1), num_routed=E, fuse_silu=False)
+              for name, q in (("e4m3", W8A8_E4M3), ("w8a8", W8A8), ("fp16", FP16))}
+    names = [ln.split()[1] for ln in nat.list_variants()]
+
+    def one(bs: int) -> dict:
+        ids = torch.multinomial((hist / hist.sum()).expand(bs, E), topk, replacement=False, generator=g).to(torch.int32).to(dev)
+        hidden = ((torch.rand(bs, H, generator=g) * 2 - 1)).half().to(dev)
+        wts = torch.softmax(torch.rand(bs, topk, generator=g), dim=1).to(dev)
+        steps = {n: PlannedForward(layer, hidden, ids, wts) for n, layer in layers.items()}
+        for st in steps.values():
+            st()
+        torch.cuda.synchronize()
+        ref = steps["fp16"].out.float()
+        sides = {}
+        for n, st in steps.items():
+            sides[(n, "step")] = lambda st=st: time_launches(st, 5, iters)["median_ms"] * 1e3
+            for k, fn in st.stages.items():
+                sides[(n, k)] = lambda fn=fn: _device(fn, iters)
+        res = _rounds(sides, rounds)
+        out = {"bs": bs, "E": E, "topk": topk, "H": H, "N": N, "N_shared": Ns}
+        for n, st in steps.items():
+            out[n] = {k: _stat(res[(n, k)]) for k in ["step", *st.stages]}
+            out[n]["gate_up_mode"] = st.mode
+            out[n]["variants"] = {"gate_up": names[st.g1.variant], "down": names[st.g2.variant]}
+            out[n]["splitk_slabs"] = [int(st.g1.info.splitk_slabs), int(st.g2.info.splitk_slabs)]
+            err = (st.out.float() - ref).norm() / ref.norm()
+            out[n]["rel_err_to_fp16"] = round(float(err), 5)
+        out["act_passes_vs_w8a8"] = {}
+        for k in ("quant_act", "act_quant"):
+            e, w = out["e4m3"][k], out["w8a8"][k]
+            out["act_passes_vs_w8a8"][k] = {"parity": bool(w["min_us"] <= e["median_us"] <= w["max_us"]),
+                                            "ratio": round(e["median_us"] / w["median_us"], 4)}
+        for k in ("gate_up", "down", "step"):
+            out["act_passes_vs_w8a8"][k] = {"ratio": round(out["e4m3"][k]["median_us"] / out["w8a8"][k]["median_us"], 4)}
         return out
 
     for bs in batches:  # (a generator: a caller can print each size as it completes)
