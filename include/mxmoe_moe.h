@@ -423,7 +423,9 @@ enum { MXMOE_DECODE_FP16 = 0, MXMOE_DECODE_W8A8 = 1, MXMOE_DECODE_W4A4 = 2,
        /* the _wo entries only: kind = 4 + (w_bits == 8) + 2 * (gsize == 128) + 4 * asym */
        MXMOE_DECODE_W4A16 = 4, MXMOE_DECODE_W8A16 = 5, MXMOE_DECODE_W4A16_G128 = 6, MXMOE_DECODE_W8A16_G128 = 7,
        MXMOE_DECODE_W4A16_ASYM = 8, MXMOE_DECODE_W8A16_ASYM = 9, MXMOE_DECODE_W4A16_G128_ASYM = 10,
-       MXMOE_DECODE_W8A16_G128_ASYM = 11 };                                    /* per linear */
+       MXMOE_DECODE_W8A16_G128_ASYM = 11,
+       /* the _lp entries only: e4m3, MXFP8 and MXFP4 activations */
+       MXMOE_DECODE_W8A8_E4M3 = 12, MXMOE_DECODE_W4A8_MXFP8 = 13, MXMOE_DECODE_W4A4_MXFP4 = 14 }; /* per linear */
 enum { MXMOE_DECODE_GU_PLAIN = 0, MXMOE_DECODE_GU_INTERLEAVED = 1 };
 enum { MXMOE_DECODE_BAD_ID = 1, MXMOE_DECODE_BAD_KIND = 2 };                   /* bits of *status */
 typedef struct mxmoe_moe_decode_expert {
@@ -507,6 +509,34 @@ int mxmoe_moe_decode_gate_up_wo(const mxmoe_moe_glu* glu, int dtype, const void*
                                 uint32_t kind_mask, int H, int N, int N_shared, int layout, void* act, void* act_shared,
                                 int32_t* status, void* stream);
 int mxmoe_moe_decode_down_wo(int64_t T, int topk, int E, int with_shared, const int32_t* topk_ids,
+                             const mxmoe_moe_decode_expert* experts, uint32_t kind_mask, int H, int N, int N_shared,
+                             const void* act, const void* act_shared, void* y, void* ys, int32_t* status, void* stream);
+
+/* The decode forward for experts with low-precision floating-point activations ("lp"; added to ABI 7 without a version
+ * bump): the two _wo entries with three more kinds, computed on v_mfma_scale_f32_16x16x128_f8f6f4 (a batch of up to 16
+ * rows is that instruction's M; mxmoe_amd/csrc/moe_decode_mfma.h). Arguments (glu included), pair order, safety,
+ * limits and refusals are those of mxmoe_moe_decode_gate_up_wo / mxmoe_moe_decode_down_wo; the expert record is
+ * unchanged (40 bytes). The six entries above keep their kernels and their mask checks; these run kernels of their own
+ * and take kinds 0 to 14 (kinds 0..11: the _wo entries' arithmetic and outputs, byte for byte).
+ *   MXMOE_DECODE_W8A8_E4M3 (w8a8_g-1_sym_E4M3): B the e4m3 codes in pack_wxax's 8-bit order, uint8 [rows][K]; sb1 /
+ *            sb2 fp16 [rows]. A row: the MXMOE_ACT_E4M3 tag's codes and row scale (an Inf / NaN row: zero codes, a NaN
+ *            scale). v(r) = fp16_rn(f32 acc * f32(fp16_rn(scale_a * scale_b[r]))), the product rounded on its own.
+ *   MXMOE_DECODE_W4A8_MXFP8 (w4a8_g32_sym_MXFP8) and MXMOE_DECODE_W4A4_MXFP4 (w4a4_g32_sym_MXFP4): B and sb1 / sb2 as
+ *            MXMOE_DECODE_W4A16_MX's (e2m1 codes, the e8m0 rows in the device layout, read in place as dwords: 4-byte
+ *            aligned). A row: the MXMOE_ACT_MXFP8 / MXMOE_ACT_MXFP4 tag's codes and e8m0 bytes (an Inf / NaN block: zero
+ *            codes and byte 255; a zero block: byte 0). v(r) = fp16_rn(acc).
+ *   acc      the block-scaled MFMA's f32 sum over K (both scales applied by the instruction; E4M3: unit scales), K = 128
+ *            per step, steps ascending: within the f32 summation order of the GroupGEMM's tiles of these types.
+ *   The gate_up epilogue (SiLU, or glu's biases and clamp) and everything behind it are the _ex entries'.
+ * Refusals, before any HIP call and under these entries' names: everything the _wo entries check; a kind bit >= 15:
+ * MXMOE_GG_ERR_UNSUPPORTED. The records live in device memory, so the alignment of the pointers in them (16 bytes for
+ * codes, 4 for e8m0 rows) is the caller's to keep. One launch each, no allocation, no synchronisation:
+ * graph-capturable. */
+int mxmoe_moe_decode_gate_up_lp(const mxmoe_moe_glu* glu, int dtype, const void* hidden, int64_t T, int topk, int E,
+                                int with_shared, const int32_t* topk_ids, const mxmoe_moe_decode_expert* experts,
+                                uint32_t kind_mask, int H, int N, int N_shared, int layout, void* act, void* act_shared,
+                                int32_t* status, void* stream);
+int mxmoe_moe_decode_down_lp(int64_t T, int topk, int E, int with_shared, const int32_t* topk_ids,
                              const mxmoe_moe_decode_expert* experts, uint32_t kind_mask, int H, int N, int N_shared,
                              const void* act, const void* act_shared, void* y, void* ys, int32_t* status, void* stream);
 

@@ -111,6 +111,8 @@ EXPORTED_SYMBOLS = (
     "mxmoe_moe_decode_gate_up_ex", "mxmoe_moe_decode_down_ex",
     # the decode forward with the integer weight-only kinds (w4a16 / w8a16, per-channel or g128, sym or asym)
     "mxmoe_moe_decode_gate_up_wo", "mxmoe_moe_decode_down_wo",
+    # the decode forward on MFMA: experts with E4M3, MXFP8 or MXFP4 activations beside all the kinds above
+    "mxmoe_moe_decode_gate_up_lp", "mxmoe_moe_decode_down_lp",
 )
 # added to ABI 7 without a version bump (additive): a product library without them is a stale build
 GPTOSS_SYMBOLS = ("mxmoe_moe_gate_ex2", "mxmoe_moe_glu_quant", "mxmoe_moe_combine_bias")
@@ -120,6 +122,7 @@ DT_SYMBOLS = ("mxmoe_moe_gate_dt", "mxmoe_moe_gather_quant", "mxmoe_moe_combine_
 DECODE_SYMBOLS = ("mxmoe_moe_decode_gate_up", "mxmoe_moe_decode_down")  # (likewise: the decode forward)
 DECODE_EX_SYMBOLS = ("mxmoe_moe_decode_gate_up_ex", "mxmoe_moe_decode_down_ex")  # (likewise: gpt-oss layers)
 DECODE_WO_SYMBOLS = ("mxmoe_moe_decode_gate_up_wo", "mxmoe_moe_decode_down_wo")  # (likewise: weight-only experts)
+DECODE_LP_SYMBOLS = ("mxmoe_moe_decode_gate_up_lp", "mxmoe_moe_decode_down_lp")  # (likewise: low-precision activations)
 DT_FP16, DT_BF16 = 0, 1  # MXMOE_DT_* (include/mxmoe_moe.h)
 # MXMOE_DECODE_* (include/mxmoe_moe.h): the token limit, the kinds per linear, the gate_up layouts, the status bits
 DECODE_MAX_T = 16
@@ -128,6 +131,8 @@ DECODE_W4A16_MX = 3  # (the _ex and _wo entries only)
 # the _wo entries only: kind = 4 + (w_bits == 8) + 2 * (gsize == 128) + 4 * asym
 DECODE_W4A16, DECODE_W8A16, DECODE_W4A16_G128, DECODE_W8A16_G128 = 4, 5, 6, 7
 DECODE_W4A16_ASYM, DECODE_W8A16_ASYM, DECODE_W4A16_G128_ASYM, DECODE_W8A16_G128_ASYM = 8, 9, 10, 11
+# the _lp entries only: e4m3 / MXFP8 / MXFP4 activations (w8a8_g-1_sym_E4M3, w4a8_g32_sym_MXFP8, w4a4_g32_sym_MXFP4)
+DECODE_W8A8_E4M3, DECODE_W4A8_MXFP8, DECODE_W4A4_MXFP4 = 12, 13, 14
 
 
 def decode_wo_kind(w_bits: int, gsize: int, sym: bool) -> int:
@@ -329,6 +334,11 @@ def _declare(lib: ctypes.CDLL) -> None:
         lib.mxmoe_moe_decode_gate_up_wo.argtypes = list(lib.mxmoe_moe_decode_gate_up_ex.argtypes)
         lib.mxmoe_moe_decode_down_wo.restype = c.c_int
         lib.mxmoe_moe_decode_down_wo.argtypes = list(lib.mxmoe_moe_decode_down_ex.argtypes)
+    if all(hasattr(lib, fn) for fn in DECODE_LP_SYMBOLS):  # (builds before the MFMA decode forward lack them)
+        lib.mxmoe_moe_decode_gate_up_lp.restype = c.c_int
+        lib.mxmoe_moe_decode_gate_up_lp.argtypes = list(lib.mxmoe_moe_decode_gate_up_ex.argtypes)
+        lib.mxmoe_moe_decode_down_lp.restype = c.c_int
+        lib.mxmoe_moe_decode_down_lp.argtypes = list(lib.mxmoe_moe_decode_down_ex.argtypes)
 
 
 def lib() -> ctypes.CDLL:

@@ -14,8 +14,9 @@
 //   Mx             W4A16_MX: fp16 A, e2m1 codes dequantised with a block's e8m0 byte
 //   WeightOnly<B>  kinds 4..11 (w4a16 / w8a16): fp16 A, integer codes dequantised with a (scale, zp) pair
 // LEVEL is the entry pair: kFirst (the plain kinds, SiLU), kEx (the _ex entries, gpt-oss layers: also Mx, and in
-// gate_up the biases and the gated activation of an mxmoe_moe_glu) or kWo (the _wo entries: also WeightOnly). A
-// level's kernel contains its own kinds' bodies only.
+// gate_up the biases and the gated activation of an mxmoe_moe_glu), kWo (the _wo entries: also WeightOnly) or kLp (the
+// _lp entries: also the kinds with e4m3 / MXFP8 / MXFP4 activations, which run lp_tile, the MFMA tile of
+// moe_decode_mfma.h, in place of expert_tile). A level's kernel contains its own kinds' bodies only.
 //
 // Mapping. One workgroup (256 threads) per (expert, tile of `ct` output columns); the shared expert's tiles come
 // first in the grid (its rows are the most: all T). A workgroup whose expert has no row returns after the id scan.
@@ -71,8 +72,9 @@ constexpr int kBatchRows = 16;                      // A rows per batch: the acc
 constexpr int kLdsBudget = 60 * 1024;               // dynamic LDS of a workgroup (the A rows of one batch)
 constexpr int kMaxWidthD = 16384;
 
-// level: which entries — kFirst, kEx (also W4A16_MX, biases, the gated activation) or kWo (also the kinds 4..11)
-enum { kFirst = 0, kEx = 1, kWo = 2 };
+// level: which entries — kFirst, kEx (also W4A16_MX, biases, the gated activation), kWo (also the kinds 4..11) or kLp
+// (also the kinds 12..14 on the MFMA tile of moe_decode_mfma.h)
+enum { kFirst = 0, kEx = 1, kWo = 2, kLp = 3 };
 
 struct Args {
   const void* src;         // gate_up: hidden [T][K] (fp16 or bf16); down: act [T * topk][K]
@@ -112,6 +114,36 @@ __host__ __device__ inline int b_row_bytes(int kind, int K) {
 __host__ __device__ inline int a_row_bytes(int kind, int K) {
   return kind == MXMOE_DECODE_W4A16_MX || wo_kind(kind) ? 2 * K : b_row_bytes(kind, K);
 }
+
+// The kinds with low-precision floating-point activations (the _lp entries, moe_decode_mfma.h): bytes of a weight row,
+// of an A row's codes (K bytes of fp8 codes, K / 2 of fp4) and of a row's e8m0 bytes (device layout, both operands)
+__host__ __device__ inline bool lp_kind(int kind) { return kind >= MXMOE_DECODE_W8A8_E4M3 && kind <= MXMOE_DECODE_W4A4_MXFP4; }
+__host__ __device__ inline int lp_b_row_bytes(int kind, int K) { return kind == MXMOE_DECODE_W8A8_E4M3 ? K : K / 2; }
+__host__ __device__ inline int lp_a_row_bytes(int kind, int K) { return kind == MXMOE_DECODE_W4A4_MXFP4 ? K / 2 : K; }
+__host__ __device__ inline int lp_scale_row_bytes(int K) { return ((K / 32 + 15) >> 4) << 4; }
+// Their LDS map, derived from the call's arguments by the host (the launch's LDS bytes) and by every workgroup: a head
+// of kLpHead bytes, rb rows of codes `row` bytes apart, rb rows of e8m0 bytes `srow` bytes apart (moe_decode_mfma.h)
+constexpr int kLpHead = 32;
+struct LpLds {
+  int rb, row, srow;
+};
+__host__ __device__ inline LpLds lp_lds(const Args& a) {
+  const int kmax = a.with_shared && a.K_shared > a.K ? a.K_shared : a.K;
+  int ab = 0;
+  for (int k = MXMOE_DECODE_W8A8_E4M3; k <= MXMOE_DECODE_W4A4_MXFP4; ++k)
+    if ((a.kind_mask >> k) & 1u) ab = lp_a_row_bytes(k, kmax) > ab ? lp_a_row_bytes(k, kmax) : ab;
+  LpLds L;
+  L.row = ab + 16;
+  L.srow = lp_scale_row_bytes(kmax) + 4;
+  int rb = (kLdsBudget - kLpHead) / (L.row + L.srow);
+  rb = rb < 1 ? 1 : rb > kBatchRows ? kBatchRows : rb;
+  L.rb = rb > a.T ? a.T : rb;
+  return L;
+}
+// (moe_decode_mfma.h) one workgroup's work on an expert of an lp kind
+template <bool DOWN, int KIND>
+__device__ __forceinline__ void lp_tile(const Args& a, const mxmoe_moe_decode_expert& ex, bool shared, int tile, int nrows,
+                                        uint8_t* s_a, const int* s_rows, _Float16* s_scale, const _Float16* brow);
 
 // sum over the 16 lanes of a DPP row (quad_perm [1,0,3,2], [2,3,0,1], row_half_mirror, row_mirror): every lane
 // of the row ends with the total
@@ -467,8 +499,10 @@ __device__ __forceinline__ void dot_rows(const P& p, const uint8_t* __restrict__
 
 // One workgroup's work on an expert whose kind has policy P (`kind`: the record's own): per batch of rows, the A rows
 // into LDS, then the tile's columns. EX: the kEx / kWo build — `brow`, the bias row of the workgroup's expert ([gate |
-// up], or NULL), and the gated activation of Args in the gate_up epilogue. Without EX none of that code exists.
-template <bool DOWN, class P, bool EX>
+// up], or NULL), and the gated activation of Args in the gate_up epilogue. Without EX none of that code exists. TAG:
+// kLp's instantiations are its own, so that what the compiler derives for the other levels' from their one caller
+// (and with it their kernels' code) does not depend on the kLp kernel's existence.
+template <bool DOWN, class P, bool EX, int TAG = 0>
 __device__ __forceinline__ void expert_tile(const Args& a, const mxmoe_moe_decode_expert& ex, int kind, bool shared,
                                             int tile, int nrows, uint8_t* s_a, const int* s_rows, _Float16* s_scale,
                                             const _Float16* brow) {
@@ -580,13 +614,21 @@ __global__ __launch_bounds__(kThreadsD) void decode_kernel(Args a) {
   // the bias row of the workgroup's own expert (e < E by the grid's size): never indexed by an id
   const _Float16* brow = nullptr;
   if constexpr (EX && !DOWN) brow = shared ? a.bias_shared : a.bias_routed ? a.bias_routed + (int64_t)e * 2 * a.C : nullptr;
-#define MXMOE_DEC_TILE(...) expert_tile<DOWN, __VA_ARGS__, EX>(a, ex, kind, shared, tile, nrows, s_a, s_rows, s_scale, brow)
+#define MXMOE_DEC_TILE(...) \
+  expert_tile<DOWN, __VA_ARGS__, EX, LEVEL == kLp ? kLp : 0>(a, ex, kind, shared, tile, nrows, s_a, s_rows, s_scale, brow)
   if (kind == MXMOE_DECODE_FP16) return MXMOE_DEC_TILE(Plain<MXMOE_DECODE_FP16>);
   if (kind == MXMOE_DECODE_W8A8) return MXMOE_DEC_TILE(Plain<MXMOE_DECODE_W8A8>);
   if (LEVEL == kFirst || kind == MXMOE_DECODE_W4A4) return MXMOE_DEC_TILE(Plain<MXMOE_DECODE_W4A4>);
   if constexpr (LEVEL >= kEx) {
     if (LEVEL == kEx || kind == MXMOE_DECODE_W4A16_MX) return MXMOE_DEC_TILE(Mx);
-    if constexpr (LEVEL == kWo) {
+    if constexpr (LEVEL >= kWo) {
+      if constexpr (LEVEL == kLp) {
+#define MXMOE_DEC_LP(KIND) lp_tile<DOWN, KIND>(a, ex, shared, tile, nrows, s_a, s_rows, s_scale, brow)
+        if (kind == MXMOE_DECODE_W8A8_E4M3) return MXMOE_DEC_LP(MXMOE_DECODE_W8A8_E4M3);
+        if (kind == MXMOE_DECODE_W4A8_MXFP8) return MXMOE_DEC_LP(MXMOE_DECODE_W4A8_MXFP8);
+        if (kind == MXMOE_DECODE_W4A4_MXFP4) return MXMOE_DEC_LP(MXMOE_DECODE_W4A4_MXFP4);
+#undef MXMOE_DEC_LP
+      }
       if (wo_bits(kind) == 4) return MXMOE_DEC_TILE(WeightOnly<4>);
       return MXMOE_DEC_TILE(WeightOnly<8>);
     }
@@ -598,10 +640,11 @@ __global__ __launch_bounds__(kThreadsD) void decode_kernel(Args a) {
 // host side: the entries' checks (before any HIP call) and the launch geometry
 
 inline int kind_mask_check(const char* fn, uint32_t kind_mask, int level = kFirst) {
-  if (level == kWo) {
-    if (kind_mask >> (MXMOE_DECODE_W8A16_G128_ASYM + 1))
+  if (level >= kWo) {
+    const int last = level == kLp ? MXMOE_DECODE_W4A4_MXFP4 : MXMOE_DECODE_W8A16_G128_ASYM;
+    if (kind_mask >> (last + 1))
       return fail(MXMOE_GG_ERR_UNSUPPORTED, "%s: unknown expert kind in kind_mask %#x (kinds 0 to %d only)", fn, kind_mask,
-                  (int)MXMOE_DECODE_W8A16_G128_ASYM);
+                  last);
   } else {
     const bool ex = level == kEx;
     const uint32_t known = 1u << MXMOE_DECODE_FP16 | 1u << MXMOE_DECODE_W8A8 | 1u << MXMOE_DECODE_W4A4 |
@@ -625,8 +668,10 @@ inline int sizes_check(const char* fn, int64_t T, int topk, int E, int with_shar
   return MXMOE_GG_OK;
 }
 
-// tiles, batch rows and LDS bytes of a launch whose other fields are set; returns the dynamic LDS bytes
-inline int geometry(Args& a) {
+// tiles, batch rows and LDS bytes of a launch whose other fields are set; returns the dynamic LDS bytes. level kLp: the
+// kinds 0..11 of the mask size lds_row and rb as at the other levels (none of them: no such row is staged), the lp
+// kinds their own map (lp_lds), and the launch takes the larger of the two
+inline int geometry(Args& a, int level = kFirst) {
   int kb = 0;
   const int kmax = a.with_shared && a.K_shared > a.K ? a.K_shared : a.K;
   for (int k = 0; k <= MXMOE_DECODE_W8A16_G128_ASYM; ++k)
@@ -635,7 +680,7 @@ inline int geometry(Args& a) {
       kb = ab > kb ? ab : kb;
     }
   a.lds_row = kb = (kb + 1023) & ~1023;  // (rows are zero-padded to the dot loop's group of four 256-byte steps)
-  int rb = kLdsBudget / kb;
+  int rb = kb ? kLdsBudget / kb : kBatchRows;  // (kb == 0: a kLp mask of lp kinds only)
   rb = rb < 1 ? 1 : rb > kBatchRows ? kBatchRows : rb;
   a.rb = rb > a.T ? a.T : rb;
   // columns of the experts that can have rows; tiles of 128 columns, halved while the grid would not fill the CUs
@@ -646,14 +691,23 @@ inline int geometry(Args& a) {
   a.ct = ct;
   a.tiles = a.C / ct;
   a.tiles_shared = a.with_shared ? a.C_shared / ct : 0;
-  return a.rb * a.lds_row;
+  int lds = a.rb * a.lds_row;
+  if (level == kLp && (a.kind_mask >> MXMOE_DECODE_W8A8_E4M3)) {
+    const LpLds L = lp_lds(a);
+    const int lp = kLpHead + L.rb * (L.row + L.srow);
+    lds = lp > lds ? lp : lds;
+  }
+  return lds;
 }
 
 template <bool DOWN>
 inline int launch(Args a, int level, void* stream) {
-  const int lds = geometry(a);
+  const int lds = geometry(a, level);
   const dim3 grid((unsigned)((int64_t)a.tiles_shared + (int64_t)a.E * a.tiles));
   switch (level) {
+    case kLp:
+      hipLaunchKernelGGL((decode_kernel<DOWN, kLp>), grid, dim3(kThreadsD), lds, (hipStream_t)stream, a);
+      return launched(DOWN ? "decode_down_lp_kernel" : "decode_gate_up_lp_kernel");
     case kWo:
       hipLaunchKernelGGL((decode_kernel<DOWN, kWo>), grid, dim3(kThreadsD), lds, (hipStream_t)stream, a);
       return launched(DOWN ? "decode_down_wo_kernel" : "decode_gate_up_wo_kernel");

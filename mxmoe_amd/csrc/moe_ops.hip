@@ -789,6 +789,7 @@ int segments_check(const int32_t* counts, int E, int64_t T, int topk, const mxmo
 }  // namespace mxmoe
 
 #include "moe_decode.h"  // the decode forward's kernels (after the quantiser helpers above, which they call)
+#include "moe_decode_mfma.h"  // its MFMA tile: the kinds with e4m3 / MXFP8 / MXFP4 activations (the _lp entries)
 
 using namespace mxmoe;
 
@@ -1035,7 +1036,8 @@ static int glu_check(const char* fn, const mxmoe_moe_glu* glu) {
 
 // The two decode entries and their _ex and _wo forms: one body of checks and one launcher each. level: decode::kEx, the
 // _ex entry (kind bit 3, the _ex kernels; glu may be NULL: SiLU and no bias), decode::kWo, the _wo entry (kind bits up
-// to 11, the _wo kernels, glu likewise); decode::kFirst: glu is NULL and the first entries' kernels run.
+// to 11, the _wo kernels, glu likewise), decode::kLp, the _lp entry (kind bits up to 14, the _lp kernels, glu likewise);
+// decode::kFirst: glu is NULL and the first entries' kernels run.
 static int decode_gate_up_impl(const char* fn, int level, const mxmoe_moe_glu* glu, int dtype, const void* hidden, int64_t T,
                                int topk, int E, int with_shared, const int32_t* topk_ids,
                                const mxmoe_moe_decode_expert* experts, uint32_t kind_mask, int H, int N, int N_shared,
@@ -1325,6 +1327,21 @@ int mxmoe_moe_decode_down_wo(int64_t T, int topk, int E, int with_shared, const 
                              const mxmoe_moe_decode_expert* experts, uint32_t kind_mask, int H, int N, int N_shared,
                              const void* act, const void* act_shared, void* y, void* ys, int32_t* status, void* stream) {
   return decode_down_impl("mxmoe_moe_decode_down_wo", decode::kWo, T, topk, E, with_shared, topk_ids, experts, kind_mask,
+                          H, N, N_shared, act, act_shared, y, ys, status, stream);
+}
+
+int mxmoe_moe_decode_gate_up_lp(const mxmoe_moe_glu* glu, int dtype, const void* hidden, int64_t T, int topk, int E,
+                                int with_shared, const int32_t* topk_ids, const mxmoe_moe_decode_expert* experts,
+                                uint32_t kind_mask, int H, int N, int N_shared, int layout, void* act, void* act_shared,
+                                int32_t* status, void* stream) {
+  return decode_gate_up_impl("mxmoe_moe_decode_gate_up_lp", decode::kLp, glu, dtype, hidden, T, topk, E, with_shared,
+                             topk_ids, experts, kind_mask, H, N, N_shared, layout, act, act_shared, status, stream);
+}
+
+int mxmoe_moe_decode_down_lp(int64_t T, int topk, int E, int with_shared, const int32_t* topk_ids,
+                             const mxmoe_moe_decode_expert* experts, uint32_t kind_mask, int H, int N, int N_shared,
+                             const void* act, const void* act_shared, void* y, void* ys, int32_t* status, void* stream) {
+  return decode_down_impl("mxmoe_moe_decode_down_lp", decode::kLp, T, topk, E, with_shared, topk_ids, experts, kind_mask,
                           H, N, N_shared, act, act_shared, y, ys, status, stream);
 }
 

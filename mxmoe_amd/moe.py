@@ -1549,8 +1549,8 @@ class DecodeForwardEx(_DecodeBase):
 
     So a gpt-oss MoE block decodes as router -> decode_gate_up -> decode_down -> combine, launches only, with fp16 or
     bf16 ends. ``out`` equals ``MoEFFN.forward``'s bit for bit for w8a8 / w4a4 experts and within the f32 summation
-    order for fp16 and MXFP4 experts. Still refused, naming the qcfg: w4a4_g32_sym_MXFP4, w4a8_g32_sym_MXFP8, g128
-    and the integer weight-only types (``DecodeForwardWo`` takes those).
+    order for fp16 and MXFP4 experts. Still refused, naming the qcfg: w4a4_g32_sym_MXFP4 and w4a8_g32_sym_MXFP8
+    (``DecodeForwardLp`` takes those), g128 and the integer weight-only types (``DecodeForwardWo`` takes those).
 
     On the gpt-oss layer shape (E = 32, topk = 4, H = N = 2944) this form takes 0.56x / 0.71x of ``GraphForward``'s
     device time at T = 1 / 4, 0.94x at T = 6 and 1.14x / 1.48x at T = 8 / 16: the crossover is between 6 and 8
@@ -1577,7 +1577,8 @@ class DecodeForwardWo(_DecodeBase):
     ``DecodeForwardEx`` those plus w4a16_g32_sym_MXFP4, biases and ``SwigluClamp`` (gpt-oss); ``DecodeForwardWo``
     all of that plus the eight integer weight-only types — the reference's small-batch scheme w4a16 + w8a8
     (``workload.w4a16_w8a8_qconfig``) is a layer for this class. Still refused, naming the qcfg: w2a16, group sizes
-    other than -1 and 128, w4a4_g32_sym_MXFP4, w4a8_g32_sym_MXFP8, w4a4_g128, E4M3 and bf16 experts.
+    other than -1 and 128, w4a4_g32_sym_MXFP4, w4a8_g32_sym_MXFP8 and E4M3 (``DecodeForwardLp`` takes these three),
+    w4a4_g128 and bf16 experts.
 
     On qwen2_moe layer 11 with the w4a16 + w8a8 scheme (E = 60, topk = 4, the shared expert included) this form takes
     0.37x / 0.51x / 0.66x of ``GraphForward``'s device time at T = 1 / 4 / 6, 0.99x at T = 8 and 1.32x / 1.68x at
@@ -1600,6 +1601,54 @@ class DecodeForwardWo(_DecodeBase):
                 sb.numel() != want):
             raise ValueError(f"DecodeForwardWo: the scale buffer of a {q.qcfg} weight [{w.N}, {w.K}] must be a contiguous "
                              f"fp16 tensor of {want} elements on the layer's device")
+
+
+class DecodeForwardLp(_DecodeBase):
+    """``DecodeForwardWo`` for layers whose experts take low-precision floating-point activations (DESIGN.md §4 "Decode
+    forward on MFMA"): the same constructor, ``launch`` and ``status`` on the _lp entries (mxmoe_moe_decode_gate_up_lp /
+    mxmoe_moe_decode_down_lp, include/mxmoe_moe.h), which take everything the _wo entries take and also
+
+    - ``w8a8_g-1_sym_E4M3`` (FP8 layers), ``w4a8_g32_sym_MXFP8`` (``MoEFFN.a8_view()``, ``gptoss_layer`` with MXFP8
+      activations) and ``w4a4_g32_sym_MXFP4`` experts, mixed freely with the other twelve kinds per expert and per
+      linear. A workgroup on one of the three quantises its batch of rows into LDS byte for byte as the activation
+      pass does and multiplies them with v_mfma_scale_f32_16x16x128_f8f6f4 (a decode batch is at most 16 rows, that
+      instruction's M); the weights and their e8m0 rows are the layer's own tensors, read in place. ``out`` is within
+      the f32 summation order of ``MoEFFN.forward``'s.
+
+    Which class takes which layer: ``DecodeForward`` fp16 / w8a8 / w4a4 experts with SiLU and no bias;
+    ``DecodeForwardEx`` those plus w4a16_g32_sym_MXFP4, biases and ``SwigluClamp`` (gpt-oss); ``DecodeForwardWo`` all
+    of that plus the eight integer weight-only types; ``DecodeForwardLp`` all of that plus the three types above.
+    Still refused, naming the qcfg: w2a16, group sizes other than -1 and 128, w4a4_g128 and bf16 experts.
+
+    Device time against ``GraphForward`` (tools/decode_bench.py --scheme e4m3 / --model gpt-oss --act-bits 8): on
+    qwen2_moe layer 11 with every expert E4M3 0.30x / 0.35x / 0.36x / 0.37x / 0.48x / 0.50x at T = 1 / 4 / 6 / 8 / 12 /
+    16; on the gpt-oss layer shape with MXFP8 activations 0.41x / 0.48x / 0.57x / 0.59x / 0.54x / 0.54x. No crossover
+    up to 16 tokens: one MFMA serves 16 rows, so the time follows the weight bytes of the experts named, not the rows
+    (DESIGN.md §4)."""
+
+    KINDS = dict(DecodeForwardWo.KINDS, **{"w8a8_g-1_sym_E4M3": nat.DECODE_W8A8_E4M3,
+                                           "w4a8_g32_sym_MXFP8": nat.DECODE_W4A8_MXFP8,
+                                           "w4a4_g32_sym_MXFP4": nat.DECODE_W4A4_MXFP4})
+    ENTRIES = nat.DECODE_LP_SYMBOLS
+    TAKES_GLU = True
+    TAKES_MX = True
+
+    def _check_scale(self, w: "ExpertWeights", dev) -> None:
+        """As ``DecodeForwardWo``'s; the E4M3 weight's fp16 [N] scale is read by row, an MX weight's e8m0 rows as
+        dwords (the entries cannot see the records' pointers: they are checked here)."""
+        q, sb = w.q, w.scale_b
+        if q.is_fp8:
+            if (sb is None or sb.device != dev or sb.dtype != torch.float16 or not sb.is_contiguous() or sb.data_ptr() % 2 or
+                    sb.numel() != w.N):
+                raise ValueError(f"DecodeForwardLp: the scale buffer of a {q.qcfg} weight [{w.N}, {w.K}] must be a contiguous "
+                                 f"fp16 tensor of {w.N} elements on the layer's device")
+        elif q.fmt in ("MXFP4", "MXFP8") and not q.is_weight_only:
+            want = w.N * 16 * ((w.K // 32 + 15) // 16)
+            if sb is None or sb.dtype != torch.uint8 or sb.numel() != want or sb.data_ptr() % 4:
+                raise ValueError(f"DecodeForwardLp: the e8m0 rows of a {q.qcfg} weight [{w.N}, {w.K}] must be a 4-byte "
+                                 f"aligned uint8 tensor of {want} bytes (the device scale layout)")
+        else:
+            DecodeForwardWo._check_scale(self, w, dev)
 
 
 def qwen2_layer_bench(*args, **kwargs) -> dict:

@@ -10,9 +10,9 @@ from typing import Optional, Sequence
 import torch
 
 from . import _native as nat
-from .groupgemm import W4A8_MXFP8, W4A16_MXFP4, QParams
+from .groupgemm import W4A8_MXFP8, W4A16_MXFP4, W8A8_E4M3, QParams
 from .harness import time_launches
-from .moe import (_BITS, DecodeForward, DecodeForwardEx, DecodeForwardWo, GraphForward, MoEBlock, MoEFFN, PlannedForward, SwigluClamp, _launch_combine,
+from .moe import (_BITS, DecodeForward, DecodeForwardEx, DecodeForwardLp, DecodeForwardWo, GraphForward, MoEBlock, MoEFFN, PlannedForward, SwigluClamp, _launch_combine,
                   _ptr, _stream, combine_into, gate, gptoss_layer, prepare_weight_mx, silu_mul_quant)
 from .workload import (ds2_mixed_qconfig, ds2_workload, load_workload, mixed_qconfig_lp1, qwen2_layer11_workload,
                        w4a16_w8a8_qconfig)
@@ -389,28 +389,47 @@ def decode_forward_wo_bench(batches: Sequence[int] = (1, 4, 16), rounds: int = 4
         yield out
 
 
+def decode_forward_e4m3_bench(batches: Sequence[int] = (1, 4, 16), rounds: int = 4, iters: int = 30):
+    """qwen2_moe layer 11 with every expert w8a8_g-1_sym_E4M3 (the shared one included; random weights, routing drawn
+    from the committed histogram) at decode sizes, ``DecodeForwardLp`` against ``GraphForward`` of the same layer, as
+    ``decode_forward_wo_bench`` measures its layer. E4M3 sums depend on their order: compared with the eager layer
+    within the fp16 GroupGEMM tolerance."""
+    dev, topk, g = "cuda", 4, torch.Generator().manual_seed(0)
+    gate_up, down, _, hist, E, H, N, Ns = _qwen2_decode_layer(mixed_qconfig_lp1(), g, dev)
+    layer = MoEFFN(gate_up, down, [(W8A8_E4M3, W8A8_E4M3)] * (E + 1), num_routed=E)
+    del gate_up, down
+    weight_bytes = lambda ws, es: sum(ws[e].B.numel() + 2 * ws[e].scale_b.numel() for e in es)
+    for bs in batches:
+        head = {"model": "qwen2_moe", "scheme": "e4m3", "bs": bs, "E": E, "topk": topk, "H": H, "N": N, "N_shared": Ns}
+        yield _decode_bench(layer, DecodeForwardLp, _qwen2_decode_call(g, hist, bs, E, topk, H, dev), rounds, iters, head,
+                            "close_to_eager", weight_bytes)
+
+
 def decode_forward_gptoss_bench(batches: Sequence[int] = (1, 4, 16), rounds: int = 4, iters: int = 30, E: int = 32,
-                                topk: int = 4, H: int = 2880, N: int = 2880):
+                                topk: int = 4, H: int = 2880, N: int = 2880, act_bits: int = 16):
     """A synthetic gpt-oss layer (``gptoss_layer``: E = 32, top-4, H = N = 2880 padded to 2944, random e2m1 codes, scale
     bytes in [118, 126], biases in +-0.5, the clamped SwiGLU) at decode sizes, ``DecodeForwardEx`` against
     ``GraphForward`` of the same layer, as ``decode_forward_bench`` measures the qwen2_moe layer (yields one dict per
     batch size), with the bias combine alone. Also the weight bytes (codes and scale bytes of the experts the ids
     name) and the TB/s they imply. MXFP4 sums depend on their order, so the outputs are compared with the eager
-    layer's within the fp16 GroupGEMM tolerance, not bit for bit."""
+    layer's within the fp16 GroupGEMM tolerance, not bit for bit. act_bits = 8: the layer with MXFP8 activations
+    (w4a8_g32_sym_MXFP8) and ``DecodeForwardLp``."""
     dev = "cuda"
     g = torch.Generator(device=dev).manual_seed(0)
     u8 = lambda *shape, lo=0, hi=256: torch.randint(lo, hi, shape, generator=g, device=dev, dtype=torch.uint8)
     bias = lambda *shape: torch.rand(*shape, generator=g, device=dev) - 0.5
     layer = gptoss_layer(u8(E, 2 * N, H // 32, 16), u8(E, 2 * N, H // 32, lo=118, hi=127), bias(E, 2 * N),
-                         u8(E, H, N // 32, 16), u8(E, H, N // 32, lo=118, hi=127), bias(E, H))
+                         u8(E, H, N // 32, 16), u8(E, H, N // 32, lo=118, hi=127), bias(E, H), act_bits=act_bits)
+    cls = DecodeForwardEx if act_bits == 16 else DecodeForwardLp
     weight_bytes = lambda ws, es: sum(ws[e].B.numel() + ws[e].scale_b.numel() for e in es)
     for bs in batches:
         ids = torch.stack([torch.randperm(E, generator=g, device=dev)[:topk] for _ in range(bs)]).to(torch.int32)
         hidden = torch.zeros(bs, layer.H, dtype=torch.float16, device=dev)
         hidden[:, :H] = (torch.randn(bs, H, generator=g, device=dev) * 0.5).half()
         wts = torch.softmax(torch.rand(bs, topk, generator=g, device=dev), dim=1)
-        head = {"model": "gpt-oss layer (synthetic)", "bs": bs, "E": E, "topk": topk, "H": layer.H, "N": layer.N}
-        yield _decode_bench(layer, DecodeForwardEx, (hidden, ids, wts), rounds, iters, head, "close_to_eager", weight_bytes)
+        head = {"model": "gpt-oss layer (synthetic)", "act_bits": act_bits, "bs": bs, "E": E, "topk": topk, "H": layer.H,
+                "N": layer.N}
+        yield _decode_bench(layer, cls, (hidden, ids, wts), rounds, iters, head, "close_to_eager", weight_bytes)
 
 
 def gptoss_bench(batches: Sequence[int] = (1, 16, 128, 512, 2048), act_bits: int = 16, rounds: int = 4, iters: int = 20,

@@ -16,8 +16,12 @@ moe_bench.decode_forward_wo_bench), DecodeForwardWo against GraphForward of the 
 the combine alone, the weight bytes read and the TB/s they imply. Exits 1 when an output is not within the fp16
 tolerance of the eager layer (weight-only sums depend on their order).
 
-python tools/decode_bench.py [--model qwen2_moe|gpt-oss] [--scheme lp1|w4a16_w8a8] [--rounds 4] [--iters 30]
-                             [--batches 1,4,16] [--out FILE]
+--model qwen2_moe --scheme e4m3: layer 11 with every expert w8a8_g-1_sym_E4M3 (moe_bench.decode_forward_e4m3_bench),
+and --model gpt-oss --act-bits 8: the gpt-oss layer with MXFP8 activations (w4a8_g32_sym_MXFP8): DecodeForwardLp (the
+MFMA decode kernels) against GraphForward of the same layer, compared within the fp16 tolerance.
+
+python tools/decode_bench.py [--model qwen2_moe|gpt-oss] [--scheme lp1|w4a16_w8a8|e4m3] [--act-bits 16|8] [--rounds 4]
+                             [--iters 30] [--batches 1,4,16] [--out FILE]
 """
 from __future__ import annotations
 
@@ -38,15 +42,20 @@ def main():
     ap.add_argument("--batches", default="1,4,16")
     ap.add_argument("--out", default="")
     ap.add_argument("--model", default="qwen2_moe", choices=["qwen2_moe", "gpt-oss"])
-    ap.add_argument("--scheme", default="lp1", choices=["lp1", "w4a16_w8a8"], help="qwen2_moe: the layer's qconfig")
+    ap.add_argument("--scheme", default="lp1", choices=["lp1", "w4a16_w8a8", "e4m3"], help="qwen2_moe: the layer's qconfig")
+    ap.add_argument("--act-bits", type=int, default=16, choices=[16, 8], help="gpt-oss: fp16 or MXFP8 activations")
     args = ap.parse_args()
     if args.model == "gpt-oss" and args.scheme != "lp1":
         ap.error("--scheme belongs to --model qwen2_moe")
+    if args.model != "gpt-oss" and args.act_bits != 16:
+        ap.error("--act-bits belongs to --model gpt-oss")
     results = []
-    wo = args.scheme == "w4a16_w8a8"
+    wo = args.scheme != "lp1"
+    kw = {"act_bits": args.act_bits} if args.model == "gpt-oss" else {}
     bench = moe_bench.decode_forward_gptoss_bench if args.model == "gpt-oss" else \
-        moe_bench.decode_forward_wo_bench if wo else moe_bench.decode_forward_bench
-    for r in bench([int(b) for b in args.batches.split(",") if b], args.rounds, args.iters):
+        {"lp1": moe_bench.decode_forward_bench, "w4a16_w8a8": moe_bench.decode_forward_wo_bench,
+         "e4m3": moe_bench.decode_forward_e4m3_bench}[args.scheme]
+    for r in bench([int(b) for b in args.batches.split(",") if b], args.rounds, args.iters, **kw):
         print(json.dumps(r), flush=True)
         results.append(r)
     if args.out:
