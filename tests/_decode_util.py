@@ -8,15 +8,17 @@ from __future__ import annotations
 
 import ctypes
 
+import numpy as np
 import torch
 
 from mxmoe_amd import _native as nat
 from mxmoe_amd import moe
+from tests import _gptoss_ref as gref
 from tests._util import assert_f16_close
 
 DEV = "cuda:0"
 GUARD = 0x7B7B
-SUFFIX = {"first": "", "ex": "_ex", "wo": "_wo"}  # the entry levels, by the suffix of their symbols
+SUFFIX = {"first": "", "ex": "_ex", "wo": "_wo", "lp": "_lp"}  # the entry levels, by the suffix of their symbols
 
 # ---- the entries, called as they are (no GPU: the refusals come before any HIP call) ---------------------------------
 
@@ -52,6 +54,13 @@ def down_raw(level, T, topk, E, shared, ids, experts, mask, H, N, Ns, act, act_s
     p = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())
     nat.check(entry_down(level, T, topk, E, shared, p(ids), p(experts), mask, H, N, Ns, p(act), p(act_shared), p(y), p(ys),
                          p(status)))
+
+
+def gate_up_raw(level, glu, dtype, hidden, T, topk, E, shared, ids, experts, mask, H, N, Ns, layout, act, act_shared, status):
+    """The gate_up entry of a level alone, on the caller's own device buffers (glu: the _ex, _wo and _lp levels')."""
+    p = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())
+    nat.check(entry_gate_up(level, glu, dtype, p(hidden), T, topk, E, shared, p(ids), p(experts), mask, H, N, Ns, layout,
+                            p(act), p(act_shared), p(status)))
 
 
 # ---- seeded data ------------------------------------------------------------------------------------------------------
@@ -145,3 +154,26 @@ def check_stages(df, ffn, h, ids, wts, sw, stages=("act", "y", "out")):
     if "close" in stages:
         assert_f16_close(got.float().cpu().numpy(), want.float().cpu().numpy(), ffn.H)
     return mid
+
+
+def assert_act_close(act, gu, b1, act_fn, glu):
+    """act against the gated activation of the reference's fp16 [gate | up] row. assert_f16_close's bound belongs to a
+    GroupGEMM's output, here g and u, which the kernel does not store; the activation multiplies a relative error of g
+    by |1 + g (1 - sigmoid g)| (about |g| for a negative g), so one fp16 ulp of g can move act by more than 1e-3 of
+    itself. The bound is therefore that figure on g and u, t = 1e-3 |x| + 1e-3 rms(row) + 1e-6, carried through the
+    activation: the largest |glu(g +- t, u +- t) - glu(g, u)| over the four corners, plus 2^-10 |act| for the two
+    roundings of act to fp16."""
+    def f(x):
+        x = gref.add_bias(x, b1)
+        N = x.shape[1] // 2
+        return gref.silu_mul_f32(x[:, :N], x[:, N:]) if act_fn == "silu" else gref.swiglu_clamp_f32(x[:, :N], x[:, N:], **glu)
+
+    x = gu.astype(np.float32)
+    N = x.shape[1] // 2
+    t = (1e-3 * np.abs(x) + 1e-3 * np.sqrt(np.mean(x.astype(np.float64) ** 2)) + 1e-6).astype(np.float32)
+    want = f(x).astype(np.float64)
+    sign = lambda dg, du: np.concatenate([np.full((1, N), dg), np.full((1, N), du)], axis=1).astype(np.float32)
+    tol = np.max([np.abs(f(x + sign(dg, du) * t) - want) for dg in (-1, 1) for du in (-1, 1)], axis=0)
+    tol = tol + 2.0 ** -10 * np.abs(want) + 1e-6
+    err = np.abs(act.astype(np.float64) - want)
+    assert np.isfinite(act).all() and (err <= tol).all(), f"{(err > tol).sum()} / {err.size} act values outside the bound"

@@ -19,7 +19,8 @@ from mxmoe_amd import moe
 from mxmoe_amd import quantize as qz
 from mxmoe_amd.groupgemm import W4A4_MXFP4, W4A8_MXFP8, W4A16_ASYM, W8A8, W8A8_E4M3
 from tests import _gptoss_ref as gref
-from tests._decode_util import DEV, GUARD, biases, bits, eager_act, f16_weights, guard, hidden, mx_codes, routing
+from tests._decode_util import DEV, GUARD, assert_act_close as _assert_act_close, biases, bits, eager_act, f16_weights, guard, hidden, \
+    mx_codes, routing
 from tests._util import assert_f16_close
 
 pytestmark = pytest.mark.gpu
@@ -62,29 +63,6 @@ def _linear(x, w):
     if sa is not None:
         c = c * (sa[:, None] * sb[None, :]).double()  # fp16_rn(scale_a * scale_b), as the epilogue forms it
     return c.half()
-
-
-def _assert_act_close(act, gu, b1, act_fn, glu):
-    """act against the gated activation of the reference's fp16 [gate | up] row. assert_f16_close's bound belongs to a
-    GroupGEMM's output, here g and u, which the kernel does not store; the activation multiplies a relative error of g
-    by |1 + g (1 - sigmoid g)| (about |g| for a negative g), so one fp16 ulp of g can move act by more than 1e-3 of
-    itself. The bound is therefore that figure on g and u, t = 1e-3 |x| + 1e-3 rms(row) + 1e-6, carried through the
-    activation: the largest |glu(g +- t, u +- t) - glu(g, u)| over the four corners, plus 2^-10 |act| for the two
-    roundings of act to fp16."""
-    def f(x):
-        x = gref.add_bias(x, b1)
-        N = x.shape[1] // 2
-        return gref.silu_mul_f32(x[:, :N], x[:, N:]) if act_fn == "silu" else gref.swiglu_clamp_f32(x[:, :N], x[:, N:], **glu)
-
-    x = gu.astype(np.float32)
-    N = x.shape[1] // 2
-    t = (1e-3 * np.abs(x) + 1e-3 * np.sqrt(np.mean(x.astype(np.float64) ** 2)) + 1e-6).astype(np.float32)
-    want = f(x).astype(np.float64)
-    sign = lambda dg, du: np.concatenate([np.full((1, N), dg), np.full((1, N), du)], axis=1).astype(np.float32)
-    tol = np.max([np.abs(f(x + sign(dg, du) * t) - want) for dg in (-1, 1) for du in (-1, 1)], axis=0)
-    tol = tol + 2.0 ** -10 * np.abs(want) + 1e-6
-    err = np.abs(act.astype(np.float64) - want)
-    assert np.isfinite(act).all() and (err <= tol).all(), f"{(err > tol).sum()} / {err.size} act values outside the bound"
 
 
 def _check(df, ffn, h, ids, wts, sw, skip=()):
