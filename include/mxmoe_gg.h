@@ -13,6 +13,13 @@
  *   w8a8_g-1_sym_E4M3 (fmt MXMOE_GG_FMT_E4M3): A,B OCP fp8 e4m3 codes (one byte each, pack_wxax
  *          8-bit byte order), per-channel fp16 scales, f32 accumulate (products exact, sum order
  *          unspecified), C = fp16_rn(0.f + acc * f32(fp16_rn(sa[m] * sb[n])))
+ *   w8a8_g128_sym_E4M3 (fmt MXMOE_GG_FMT_E4M3 with gsize 128; block-scaled FP8 checkpoints): A,B e4m3 codes as
+ *          above; scale_a f32, one per row and 128-K group, stored group-major [K/128][M]; scale_b f32, one per
+ *          block of 128 output rows x 128 K (the checkpoints' weight_scale_inv, transposed), stored group-major
+ *          [K/128][ceil(N/128)] — a K stage's scales are contiguous; both 4-byte aligned. K % 128 == 0; the last
+ *          scale block along N may be partial. With out = 0, for g = 0 .. K/128 - 1 in order:
+ *          out = fmaf(acc_g, f32_rn(sa[g][m] * sb[g][n / 128]), out), acc_g the f32 sum of the group's 128
+ *          products (sum order unspecified); C = fp16_rn(out). Never split along K. Large-batch kernel (v2x) only.
  *   bf16 (fmt MXMOE_GG_FMT_BF16): A,B bf16, fp32 accumulate, C = fp16_rn(acc) (C is fp16 for every
  *          type, as the reference's `half** ptr_Cs`)
  *   w4a4_g32_sym_MXFP4 (fmt MXMOE_GG_FMT_MXFP4): A,B OCP MXFP4 (e2m1 codes, e8m0 scale per 32-K block),
@@ -60,7 +67,7 @@ enum {
  * tile_config.py:192, and its MMA_BF16_FP32 / MMA_E4M3_K32 strategies, tile_config.py:87-106). */
 enum {
   MXMOE_GG_FMT_DEFAULT = 0, /* fp16 for 16-bit operands, two's-complement integers otherwise */
-  MXMOE_GG_FMT_E4M3 = 1,    /* w8a8_g-1_sym_E4M3: OCP fp8 e4m3 codes                         */
+  MXMOE_GG_FMT_E4M3 = 1,    /* w8a8_g-1_sym_E4M3, w8a8_g128_sym_E4M3 (gsize 128): OCP fp8 e4m3 codes */
   MXMOE_GG_FMT_BF16 = 2,    /* bf16: 16-bit operands are bfloat16                              */
   /* 3: fp6 images of int4 codes (tools-only lab library) */
   MXMOE_GG_FMT_MXFP4 = 4,   /* w4a4_g32_sym_MXFP4 and w4a16_g32_sym_MXFP4: OCP MXFP4, e2m1 codes + e8m0
@@ -180,7 +187,7 @@ typedef struct mxmoe_gg_plan_info {
   int32_t lds_bytes;
   int32_t qtype_mask;      /* bit q set if a planned problem has quant type q (0 fp16, 1 w8a8, 2 w4a4,
                             * 3 w4a16, 4 w8a16, 5 w4a4_g128, 6 w2a16, 7 w8a8 E4M3, 8 bf16, 10 MXFP4, 11 weight-only MXFP4,
-                            * 12 w4a8 MXFP8); bit 16:
+                            * 12 w4a8 MXFP8, 13 w8a8 g128 E4M3); bit 16:
                             * a weight-only problem carries MXMOE_GG_EPI_SILU_MUL (small-batch kernel);
                             * selects the kernel specialisation at launch */
   int32_t splitk_slabs;    /* 256-KiB partial-sum slabs the plan's split-K tiles use (0: no split) */

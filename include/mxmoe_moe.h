@@ -49,7 +49,7 @@ enum {
                           * e4m3 once, to nearest even (-0 keeps its sign). quantize.quant_mxfp8 is
                           * the same rule. Through mxmoe_moe_act_quant with bit 6 of tag_mask only  */
   /* 7 is NOT assigned: a tag_mask with bit 7 stays "unknown activation tag" */
-  MXMOE_ACT_E4M3 = 8     /* per-token OCP e4m3 (w8a8_g-1_sym_E4M3): one code byte per element (torch.float8_e4m3fn's
+  MXMOE_ACT_E4M3 = 8,    /* per-token OCP e4m3 (w8a8_g-1_sym_E4M3): one code byte per element (torch.float8_e4m3fn's
                           * bit patterns) in MXMOE_ACT_INT8's byte order (pack_wxax 8-bit: element 2j in the high byte
                           * of its 16-bit word), one fp16 scale per row at scales[scale_off + row]: the A operand of
                           * the E4M3 GroupGEMM tile as it reads it. A row whose values are all finite: amax = the
@@ -63,6 +63,18 @@ enum {
                           * that slot are NaN and the fault stays visible (neither the oracle's nor torch's answer
                           * for such a row is kept). Through mxmoe_moe_act_quant, mxmoe_moe_gather_quant and
                           * mxmoe_moe_glu_quant with bit 8 of tag_mask only */
+  /* 9 is NOT assigned */
+  MXMOE_ACT_E4M3_G128 = 10 /* per (token, 128-element group) OCP e4m3 (w8a8_g128_sym_E4M3, block-scaled FP8 checkpoints):
+                          * codes as MXMOE_ACT_E4M3's (one byte per element, pack_wxax 8-bit order), one F32 scale per
+                          * (row, group), group-major: the float at byte 2 * scale_off + 4 * (g * rows + row) of the
+                          * scale store (scale_off even; [width/128][rows], the GroupGEMM's scale_a). Per group, in
+                          * f32: s = f32(amax) / 448, 1 for an all-zero group (no floor: an f32 scale does not
+                          * underflow), code = e4m3_rn(f32(x) / s) saturating at +-448 — the IEEE quotient, one
+                          * rounding to e4m3, to nearest even; the sign of -0 is kept. A group holding +-Inf or NaN:
+                          * every code 0x00 and a NaN scale, as MXMOE_ACT_E4M3 does for a whole row.
+                          * quantize.quant_e4m3_g128 is the same rule. Through the same three entry points with bit
+                          * 10 of tag_mask only (the builds that carry MXMOE_ACT_E4M3). The value 7, left free
+                          * beside it, stays unassigned: masks with bit 7 keep failing as they always have. */
 };
 
 /* One expert's segment of a permuted activation buffer. Slots (rows of the permuted batch) are
@@ -74,7 +86,7 @@ typedef struct mxmoe_moe_seg {
   int32_t rows;        /* tokens routed to this expert                                        */
   int32_t width;       /* elements per row of this segment's output (K of the next GEMM)      */
   int64_t out_off;     /* byte offset of the segment's [rows][width * bits / 8] block in `out` */
-  int64_t scale_off;   /* fp16-element offset of its scales: [rows] (INT8, INT4, E4M3) or [width/128][rows];
+  int64_t scale_off;   /* fp16-element offset of its scales: [rows] (INT8, INT4, E4M3) or [width/128][rows] (E4M3_G128: of f32, two elements each);
                         * MXFP4 / MXFP8: of its [rows][16 ceil(width/32 / 16)] e8m0 bytes (even offset: the
                         * block is 4-byte aligned)                                              */
 } mxmoe_moe_seg;
@@ -306,7 +318,7 @@ int mxmoe_moe_quant_slots(const void* routed_in, const void* shared_in, int64_t 
  * entry points (and any call here without the bit) keep the builds they had before the tag existed
  * and must not be given such a segment — they would treat it as int4. MXMOE_ACT_MXFP8 segments
  * likewise need bit 6, MXMOE_ACT_E4M3 segments bit 8 (builds of their own, which carry the MX tags too: a call may
- * set bit 8 together with bit 4 or 6, a mixed layer). A mask with bit 5, bit 7 or a bit above 8 is MXMOE_GG_ERR_UNSUPPORTED.
+ * set bit 8 together with bit 4 or 6, a mixed layer). MXMOE_ACT_E4M3_G128 segments need bit 10 (the same builds). A mask with bit 5, 7, 9 or a bit above 10 is MXMOE_GG_ERR_UNSUPPORTED.
  *   mode 0: mxmoe_moe_quant_act      (routed_in = hidden [T][N], N = K; shared_in != NULL <=> with_shared,
  *                                     its value is ignored; perm_token required)
  *   mode 1: mxmoe_moe_silu_mul_quant, 2: mxmoe_moe_quant_slots, 3: mxmoe_moe_silu_mul_quant_il

@@ -18,7 +18,9 @@ ARCH = os.environ.get("MXMOE_OFFLOAD_ARCH", "gfx950")
 
 # gg_api.hip stays first (tests/test_codegen.py compiles SOURCES[0] for the device ISA); gg_plan.cpp is the
 # host-only tile planner, compiled by the same hipcc and flags as the rest
-SOURCES = [CSRC / "gg_api.hip", CSRC / "moe_ops.hip", CSRC / "gg_plan.cpp"]
+SOURCES = [CSRC / "gg_api.hip", CSRC / "moe_ops.hip", CSRC / "gg_plan.cpp", CSRC / "gg_f8g128.hip"]
+# per-source device flags: the block-scaled FP8 builds keep their f32 arithmetic unpacked
+SOURCE_FLAGS = {"gg_f8g128.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 
 FLAGS = ["-O3", "-std=c++17", "-fPIC", "-shared", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-function",
          "-I", str(ROOT / "include")]
@@ -58,7 +60,7 @@ def build(force: bool = False, verbose: bool = False, extra: list[str] | None = 
     for src, obj in zip(SOURCES, objs):
         if not force and not _newer([src, *headers], obj):
             continue
-        cmd = [HIPCC, *compile_flags, "-c", "-o", str(obj), str(src)]
+        cmd = [HIPCC, *compile_flags, *SOURCE_FLAGS.get(src.name, []), "-c", "-o", str(obj), str(src)]
         if verbose:
             print(" ".join(cmd), file=sys.stderr)
         running.append((cmd, subprocess.Popen(cmd)))

@@ -12,6 +12,7 @@ depends only on A[rows] and B[cols]), for every quant type the library runs:
     do, fp16(fma(u - off, scale, zp)) (quantize.cuh:146-213), then an f64 GEMM — fp16 tolerance;
   * w8a8 E4M3: e4m3 codes decoded, exact f64 dot products rounded to f32, the wxax epilogue — fp16
     tolerance (the MFMA's f32 summation order is unspecified);
+  * w8a8 E4M3 g128 (block-scaled): codes decoded and scaled per group / block, f64 GEMM — fp16 tolerance;
   * MXFP4 (w4a4_g32_sym_MXFP4): e2m1 codes and e8m0 block scales decoded (dequant_mxfp4), f64 GEMM —
     fp16 tolerance (f32 accumulation in the MFMA, order unspecified);
   * weight-only MXFP4 (w4a16_g32_sym_MXFP4): fp16 A, B decoded as above, f64 GEMM — fp16 tolerance;
@@ -66,6 +67,13 @@ def expected_sample(p, rows: torch.Tensor, cols: torch.Tensor) -> tuple[torch.Te
         Adq = dequant_mxfp8(A, unpack_mxfp4_scales(p.scale_a.index_select(0, rows).cpu(), p.K))
         Bdq = dequant_mxfp4(p.B.index_select(0, cols).cpu(), unpack_mxfp4_scales(p.scale_b.index_select(0, cols).cpu(), p.K))
         return Adq @ Bdq.T, False
+    if q.is_fp8 and q.gsize == 128:  # f32 scales [K/128][M] / [K/128][ceil(N/128)]: decoded f64 GEMM
+        G = p.K // 128
+        dec = lambda t: unpack_wxax(t, 8, p.K).view(torch.float8_e4m3fn).double().reshape(-1, G, 128)  # noqa: E731
+        sa = p.scale_a.cpu().reshape(G, p.M).index_select(1, rows.cpu()).double()
+        sb = p.scale_b.cpu().reshape(G, -1).index_select(1, cols.cpu() // 128).double()
+        a, b = dec(A) * sa.T[..., None], dec(p.B.index_select(0, cols).cpu()) * sb.T[..., None]
+        return a.reshape(len(rows), p.K) @ b.reshape(len(cols), p.K).T, False
     if q.is_fp8:
         def dec(t):
             return unpack_wxax(t, 8, p.K).view(torch.float8_e4m3fn).double()

@@ -25,7 +25,7 @@
 #include <vector>
 
 #include "../../include/mxmoe_gg.h"
-#include "gg_device.h"
+#include "gg_builds.h"  // (gg_device.h, the variant flags, the launchers of gg_f8g128.hip)
 #include "gg_dyn.h"
 #include "gg_error.h"
 #include "gg_plan.h"
@@ -49,10 +49,7 @@ namespace {
 
 // the small-batch weight-only tile's loop options (gg_tile_wo)
 constexpr int kWo3 = WO_SCLATE | WO_ANDOR | WO_MSKIP | WO_SPLIT | WO_NIBPOS;
-// the round-3 AUTO default's mainloop flags (variant v2x_256x256_w8_b3_buf_spread_edma, without the
-// weight-only options)
-constexpr int kV2x = V2_STAGGER | V2_B3 | V2_BUF | V2_EARLYDMA | (4 << V2_SPREAD_SHIFT);
-[[maybe_unused]] constexpr int kV2xProduct = kV2x | WO_PIPE | WO_STAG | V2_I4NOPAIR | V2_I4EDMA;
+// (the v2x flags kV2x / kV2xProduct: gg_builds.h)
 [[maybe_unused]] constexpr int kWo3Product = kWo3 | WO_PCH;
 
 // One compiled kernel of a variant's family: the tile bodies of the quant types in `qmask`.
@@ -110,9 +107,7 @@ Variant variant_of(const PlanVariant& plan, const char* name, int lds_bytes, Bui
 }
 constexpr int pick_only(int) { return 0; }  // (families of one build)
 
-[[maybe_unused]] constexpr int kMx4 = 1 << QT_MXF4;   // w4a4_g32_sym_MXFP4
-[[maybe_unused]] constexpr int kMxW = 1 << QT_MXF4W;  // weight-only MXFP4
-[[maybe_unused]] constexpr int kMx8 = 1 << QT_MXF8A;  // w4a8_g32_sym_MXFP8 (gg_tile_v2's 64 x 128 body)
+// (the type bits kMx4 / kMxW / kMx8 / kF8G and kV2Widest: gg_builds.h)
 // the MX types have tile bodies in the product library's v2 / wo2 build tables only
 #ifdef MXMOE_LAB
 constexpr bool kMxBodies = false;
@@ -147,8 +142,15 @@ constexpr Builds<sizeof...(QM)> v2_rows(bool fallback = false) {
 // room for that (the compiler spilled inside their K loops), so the fallbacks are plain v2 (ABL = 0; the
 // plan info still reports the variant's LDS image); the 2-bit weight-only body only joins when the mix has
 // one (it costs 12 B of prologue spill there, tests/test_codegen.py), the MX bodies likewise — builds apart
-// from the narrower ones, which come out unchanged.
+// from the narrower ones, which come out unchanged. The two builds with the w8a8_g128_sym_E4M3 body (the exact one
+// and one more widest fallback) are compiled in gg_f8g128.hip, for the product variant's flags only.
 // (lab builds: fp16, w8a8, w4a4, w8a8 + w4a4, w4a16, E4M3, bf16 only; fast: fp16, w8a8, w4a16)
+template <int ABL>
+constexpr Builds<1> f8g_row(bool fallback) {
+  static_assert(ABL == kV2xProduct, "gg_f8g128.hip compiles the product variant's builds only");
+  if (fallback) return {{Build{kV2Widest, true, kV2Lds<ABL>, &launch_v2_widest}}};
+  return {{Build{kF8G, false, kV2Lds<ABL>, &launch_v2x_f8g}}};
+}
 template <int ABL>
 constexpr auto kV2Builds =
 #if defined(MXMOE_LAB) && defined(MXMOE_LAB_FAST)
@@ -156,8 +158,8 @@ constexpr auto kV2Builds =
 #elif defined(MXMOE_LAB)
     v2_rows<ABL, kV2Lds<ABL>, 1, 2, 4, 6, 8, 128, 256>();
 #else
-    v2_rows<ABL, kV2Lds<ABL>, 1, 2, 4, 6, 7, 8, 10, 16, 32, 64, 128, 256, kMx4, kMxW, kMx8>() +
-    v2_rows<0, kV2Lds<ABL>, 63, 127, 511, 511 | kMx4, 511 | kMx4 | kMxW, 511 | kMx4 | kMxW | kMx8>(true);
+    v2_rows<ABL, kV2Lds<ABL>, 1, 2, 4, 6, 7, 8, 10, 16, 32, 64, 128, 256, kMx4, kMxW, kMx8>() + f8g_row<ABL>(false) +
+    v2_rows<0, kV2Lds<ABL>, 63, 127, 511, 511 | kMx4, 511 | kMx4 | kMxW, 511 | kMx4 | kMxW | kMx8>(true) + f8g_row<ABL>(true);
 #endif
 // timing ablations: int8 tiles only (kAblMask) / w4a16 tiles only (kWoAblMask), whatever the call holds
 template <int ABL>
@@ -172,9 +174,9 @@ constexpr int pick_v2(int qmask) {
 #ifdef MXMOE_LAB
   return pick_build(v2_builds<ABL>(), qmask & 511);
 #else
-  // (all 13 type bits beside an MX type, the low 9 otherwise: the only other bit is the lab's fp6 type, which no
-  // product variant plans)
-  return pick_build(v2_builds<ABL>(), qmask & ((qmask & (kMx4 | kMxW | kMx8)) ? 8191 : 511));
+  // (all 14 type bits beside an MX type or the block-scaled E4M3 one, the low 9 otherwise: the only other bit is
+  // the lab's fp6 type, which no product variant plans)
+  return pick_build(v2_builds<ABL>(), qmask & ((qmask & (kMx4 | kMxW | kMx8 | kF8G)) ? 16383 : 511));
 #endif
 }
 #ifndef MXMOE_LAB
@@ -187,6 +189,8 @@ static_assert(v2x_picked((1 << QT_I8) | (1 << QT_F8)).qmask == 511 && v2x_picked
 static_assert(v2x_picked(kMx4 | (1 << QT_F16)).qmask == (511 | kMx4) && v2x_picked(kMx4 | kMxW).qmask == (511 | kMx4 | kMxW));
 static_assert(v2x_picked(kMxW | (1 << QT_I8)).qmask == (511 | kMx4 | kMxW));
 static_assert(v2x_picked(kMx8 | (1 << QT_W4A16)).qmask == (511 | kMx4 | kMxW | kMx8) && v2x_picked(kMx8 | kMx4).qmask == v2x_picked(8191).qmask);
+static_assert(v2x_picked(kF8G).launch == &launch_v2x_f8g && v2x_picked(kV2Widest).launch == &launch_v2_widest && v2x_picked(kF8G | kMx4).qmask == kV2Widest);
+static_assert(v2x_picked(kF8G | (1 << QT_F16) | (1 << QT_I8)).qmask == kV2Widest && v2x_picked(8191).qmask == (kV2Widest & ~kF8G));
 #endif
 
 static_assert(V2Cfg<256>::BM == 256 && V2Cfg<256>::BN == 256 && V2Cfg<256>::BKB == 128 && V2Cfg<256>::NT == 512,

@@ -697,12 +697,17 @@ constexpr int kAblMask = ABL_NO_DMA | ABL_NO_LDS | ABL_NO_EPI | ABL_B_NODMA | AB
 // drained), nst << 48 | class << 40 | qtype << 36 | XCC_ID << 32 | HW_ID}, s_memrealtime ticks
 // (100 MHz); read back with mxmoe_gg_debug_trace.
 constexpr int kTraceBlocks = 32768;
-__device__ uint64_t g_gg_trace[kTraceBlocks * 4];
+#ifdef MXMOE_GG_UNIT2  // a further unit of kernels (gg_f8g128.hip), none of them a trace build: local, unused copies
+#define MXMOE_GG_DIAG static
+#else
+#define MXMOE_GG_DIAG
+#endif
+MXMOE_GG_DIAG __device__ uint64_t g_gg_trace[kTraceBlocks * 4];
 #ifdef MXMOE_LAB
 // per-wave stage stamps of the spread mainloop (V2_STAMP builds, lab library only): per (block, wave)
 // {sum of s_memtime cycles in the stage body, in the vmcnt(0) wait, in the barrier, steady stages}
 constexpr int kStampBlocks = 4096;
-__device__ uint64_t g_gg_stamp[kStampBlocks * 8 * 4];
+MXMOE_GG_DIAG __device__ uint64_t g_gg_stamp[kStampBlocks * 8 * 4];
 #endif
 __device__ __forceinline__ void trace_mark(int slot) {
   if (threadIdx.x == 0 && blockIdx.x < kTraceBlocks) g_gg_trace[blockIdx.x * 4 + slot] = __builtin_amdgcn_s_memrealtime();
@@ -1968,6 +1973,178 @@ __device__ __forceinline__ void gg_tile_g128(const GGMeta& mt, const uint8_t* __
   }
 }
 
+// ============================================================================================
+// w8a8_g128_sym_E4M3 (block-scaled FP8 checkpoints: e4m3 B codes with one f32 scale per 128 x 128
+// block, e4m3 A codes with one f32 scale per row and 128-K group): per group the MFMA's f32 sum of
+// the 128 products, folded into an f32 accumulator in group order,
+//     out = fma(acc_g, f32_rn(sa_g[m] * sb_g[n / 128]), out),   C = fp16_rn(out)
+// Scales: f32 [K/128][M] and [K/128][ceil(N/128)] (include/mxmoe_gg.h).
+//
+// Layout: gg_tile_g128's (v2 tiles, 8 waves 2M x 4N, two LDS stages by LDS-DMA, the f32 fold
+// accumulators in registers for the whole tile, group accumulators for two fragment rows at a
+// time). One 128-B stage = 128 e4m3 codes = one group = ONE K = 128 MFMA per 16 x 16 block (the
+// QT_F8 body's chunks g / g + 4, unit e8m0 scales) on a zero C operand. n0 is a multiple of 256
+// and a wave's tile 64 columns wide, so a wave's columns lie in one scale block: sb is one
+// wave-uniform value per stage, sa one value per fragment row and lane, and the fold one v_mul_f32
+// per fragment row and one v_fma_f32 per output. Stage s+1's scales (sa: one dword per thread
+// < BM, sb: two dwords) are loaded before that stage's DMA, parked in a 2-KiB LDS slot after stage
+// s's MFMAs and published by the stage barrier. K is whole groups (the planner checks): no K tail,
+// and no split along K (an f32 partial fold would change the rounding order).
+// ============================================================================================
+template <class Cfg>
+__device__ __forceinline__ void gg_tile_f8g128(const GGMeta& mt, const uint8_t* __restrict__ A,
+                                               const uint8_t* __restrict__ B, const float* __restrict__ SA,
+                                               const float* __restrict__ SB, _Float16* __restrict__ C, int m0, int n0,
+                                               uint8_t* lds) {
+  constexpr int FM = Cfg::FM, FN = Cfg::FN, GA = Cfg::GA, GB = Cfg::GB;
+  static_assert(Cfg::BM <= 256 && Cfg::BN == 256 && Cfg::WTN == 64, "scale slot: 256 rows, two 128-column blocks");
+  constexpr int SCL = 2 * Cfg::STAGE_BYTES;  // LDS scale slots: [buf][sa 256 | sb 2] f32
+  constexpr int SCL_BYTES = 2048;
+  static_assert(SCL + 2 * SCL_BYTES <= V2Cfg<256>::LDS_BYTES + V2_LDS_EXTRA, "scale slots must fit the v2 LDS image");
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int wm = wave / Cfg::WN, wn = wave % Cfg::WN;
+  const int r16 = lane & 15, g = lane >> 4;
+  const int M = mt.M, N = mt.N, ngroups = mt.reserved;  // one 128-B stage per group
+  const int NB = (N + 127) >> 7;                        // scale blocks along N
+  const int64_t lda = mt.lda_b, ldb = mt.ldb_b;
+
+  // buffer-form LDS-DMA: the tile's first row in the resource, a 32-bit lane offset (row strides are below
+  // 8 MiB, the planner checks: 256 rows stay below 2^31), the stage's K bytes in the scalar offset — one
+  // register per piece where a pointer per piece cost the 256-row body spills inside the K loop
+  auto rsrc = [](const uint8_t* base) {
+    return __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(base), (short)0, 0x7fffffff, 0x00020000);
+  };
+  const __amdgpu_buffer_rsrc_t rsA = rsrc(A + (int64_t)m0 * lda), rsB = rsrc(B + (int64_t)n0 * ldb);
+  uint32_t va[GA], vb[GB];
+  {
+    const int rsub = lane >> 3, p = lane & 7;
+#pragma unroll
+    for (int j = 0; j < GA; ++j) {
+      const int row = (wave * GA + j) * 8 + rsub;
+      va[j] = (uint32_t)(min(row, M - 1 - m0) * (int)lda) + ((p ^ ((row >> 1) & 7)) << 4);
+    }
+#pragma unroll
+    for (int j = 0; j < GB; ++j) {
+      const int row = (wave * GB + j) * 8 + rsub;
+      vb[j] = (uint32_t)(min(row, N - 1 - n0) * (int)ldb) + ((p ^ ((row >> 1) & 7)) << 4);
+    }
+  }
+  auto issue = [&](int s, int buf) {
+    uint8_t* As = lds + buf * Cfg::STAGE_BYTES;
+    uint8_t* Bs = As + Cfg::A_BYTES;
+    const int kb = s * Cfg::BKB;
+#pragma unroll
+    for (int j = 0; j < GA; ++j) bdma16(rsA, As + (wave * GA + j) * 1024, va[j], kb);
+#pragma unroll
+    for (int j = 0; j < GB; ++j) bdma16(rsB, Bs + (wave * GB + j) * 1024, vb[j], kb);
+  };
+  // group scales of stage s: threads < BM the sa of tile row tid, threads 256 / 257 the sb of the
+  // tile's two column blocks (rows past M, blocks past N: clamped, their outputs are never stored)
+  float sc = 0.0f;
+  auto load_scales = [&](int s) {
+    if (tid < Cfg::BM) sc = SA[(int64_t)s * M + min(m0 + tid, M - 1)];
+    else if (tid >= 256 && tid < 258) sc = SB[(int64_t)s * NB + min((n0 >> 7) + tid - 256, NB - 1)];
+  };
+  auto stash_scales = [&](int buf) {
+    float* sl = reinterpret_cast<float*>(lds + SCL + buf * SCL_BYTES);
+    if (tid < Cfg::BM || (tid >= 256 && tid < 258)) sl[tid] = sc;
+  };
+
+  v4f out[FM][FN];
+#pragma unroll
+  for (int i = 0; i < FM; ++i)
+#pragma unroll
+    for (int j = 0; j < FN; ++j) out[i][j] = v4f{0, 0, 0, 0};
+
+  const int swz = (r16 >> 1) & 7;
+  const uint32_t a_row = (uint32_t)(wm * Cfg::WTM + r16) * 128u;
+  const uint32_t b_row = (uint32_t)(wn * Cfg::WTN + r16) * 128u;
+  const uint32_t off0 = (uint32_t)((g ^ swz) << 4), off1 = (uint32_t)(((4 + g) ^ swz) << 4);
+  // fold of fragment row i: the scale product rounded once to f32, then one fma per output
+  // The fma is the compiler's own instruction (it places the wait states an MFMA result needs before a VALU
+  // read only for instructions it emitted itself, not for inline assembly); each result then passes an empty
+  // asm, which keeps the four fmas of a fragment scalar: merged into packed f32 forms they cost the body
+  // register pairs it does not have (spills inside the K loop)
+  auto fold = [&](int i, const v4f (&acc)[FN], float sai, float sbw) {
+    const float s = sai * sbw;
+#pragma unroll
+    for (int j = 0; j < FN; ++j)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        float d = __builtin_fmaf(acc[j][e], s, out[i][j][e]);
+        asm("" : "+v"(d));
+        out[i][j][e] = d;
+      }
+  };
+  // Row-pipelined as gg_tile_g128: the stage's B fragments stay in registers, fragment row i's
+  // group accumulators are formed by FN MFMAs and folded while row i+1's run (two sets live).
+  auto compute = [&](int buf) {
+    const uint8_t* As = lds + buf * Cfg::STAGE_BYTES + a_row;
+    const uint8_t* Bs = lds + buf * Cfg::STAGE_BYTES + Cfg::A_BYTES + b_row;
+    const float* sl = reinterpret_cast<const float*>(lds + SCL + buf * SCL_BYTES);
+    v8i b[FN];
+#pragma unroll
+    for (int j = 0; j < FN; ++j)
+      b[j] = cat_v4i(*reinterpret_cast<const v4i*>(Bs + j * 2048 + off0), *reinterpret_cast<const v4i*>(Bs + j * 2048 + off1));
+    const float sbw = sl[256 + (wn >> 1)];  // wave-uniform
+    const float* sa = sl + wm * Cfg::WTM + r16;
+    v4f acc0[FN], acc1[FN];
+#pragma unroll
+    for (int i = 0; i < FM; ++i) {
+      v4f (&acc)[FN] = (i & 1) ? acc1 : acc0;
+      const v8i a = cat_v4i(*reinterpret_cast<const v4i*>(As + i * 2048 + off0),
+                            *reinterpret_cast<const v4i*>(As + i * 2048 + off1));
+#pragma unroll
+      for (int j = 0; j < FN; ++j) acc[j] = mfma_f8_k128(b[j], a, v4f{0, 0, 0, 0});
+      if (i > 0) fold(i - 1, (i & 1) ? acc0 : acc1, sa[(i - 1) * 16], sbw);
+    }
+    fold(FM - 1, ((FM - 1) & 1) ? acc1 : acc0, sa[(FM - 1) * 16], sbw);
+  };
+
+  if (ngroups > 0) {
+    load_scales(0);
+    issue(0, 0);
+    stash_scales(0);  // waits for the scale loads only (issued before the DMA)
+    __syncthreads();  // stage 0 and its scales visible
+    for (int s = 0; s < ngroups; ++s) {
+      if (s + 1 < ngroups) {
+        load_scales(s + 1);  // before the DMA: the wait on them leaves the DMA in flight
+        issue(s + 1, (s + 1) & 1);
+      }
+      compute(s & 1);
+      if (s + 1 < ngroups) stash_scales((s + 1) & 1);  // slot last read by stage s-1 (before the last barrier)
+      __syncthreads();
+    }
+  }
+
+  // ---- epilogue (as gg_tile_g128): fp16, per-wave LDS staging, 16-B stores ----
+  int etid = threadIdx.x;
+  asm volatile("" : "+v"(etid));
+  const int elane = etid & 63, er16 = elane & 15, eg = elane >> 4;
+  uint8_t* reg = lds + wave * (Cfg::WTM * Cfg::WTN * 2);
+  const int mrow0 = m0 + wm * Cfg::WTM, ncol0 = n0 + wn * Cfg::WTN;
+#pragma unroll
+  for (int i = 0; i < FM; ++i) {
+    const int ml = i * 16 + er16;
+#pragma unroll
+    for (int j = 0; j < FN; ++j) {
+      const uint2 pk = pack4_f16(out[i][j]);
+      const int q = 2 * j + (eg >> 1);
+      *reinterpret_cast<uint2*>(reg + ml * 128 + ((q ^ (ml & 7)) << 4) + (eg & 1) * 8) = pk;
+    }
+  }
+  _Float16* const cbase = C + (int64_t)mrow0 * mt.ldc + ncol0;  // wave-uniform
+  const bool narrow = (int64_t)Cfg::WTM * mt.ldc < (int64_t)1 << 29;  // byte offsets < 2^30
+#pragma unroll 4
+  for (int it = 0; it < Cfg::WTM / 8; ++it) {
+    const int row = it * 8 + (elane >> 3), q = elane & 7;
+    const uint4 v = *reinterpret_cast<const uint4*>(reg + row * 128 + ((q ^ (row & 7)) << 4));
+    const int m = mrow0 + row, n = ncol0 + q * 8;
+    if (m < M && n < N) store_c16(cbase, (int64_t)row * mt.ldc + q * 8, narrow, v);
+  }
+}
+
 // v2 fused kernel: qtype x height-class dispatch, uniform per workgroup.
 
 
@@ -3193,6 +3370,11 @@ __global__ __launch_bounds__(512, 2) void gg_v2_kernel(GGArgs args) {
     constexpr int M8ABL = ABL & V2_B3;
     if (cls == 0) gg_tile_v2<V2Cfg<256>, QT_MXF8A, M8ABL>(mt, A, B, SA, SB, C, td.m0, td.n0, lds, sk);
     else gg_tile_v2<V2Cfg<128>, QT_MXF8A, M8ABL>(mt, A, B, SA, SB, C, td.m0, td.n0, lds, sk);  // no 64-row class
+  } else if ((QM & (1 << QT_F8G)) && mt.qtype == QT_F8G) {
+    const float* SAf = static_cast<const float*>(args.ptr_SA[td.prob]);
+    const float* SBf = static_cast<const float*>(args.ptr_SB[td.prob]);
+    if (cls == 0) gg_tile_f8g128<V2Cfg<256>>(mt, A, B, SAf, SBf, C, td.m0, td.n0, lds);
+    else gg_tile_f8g128<V2Cfg<128>>(mt, A, B, SAf, SBf, C, td.m0, td.n0, lds);  // no 64-row class
   }
   if constexpr ((ABL & V2_TRACE) != 0) {
     if (threadIdx.x == 0 && blockIdx.x < kTraceBlocks) {
@@ -3765,6 +3947,11 @@ __global__ __launch_bounds__(512, 2) void gg_v2p_kernel(GGArgs args) {
       if ((QM & (1 << QT_I4G)) && qt == QT_I4G) {
         if (cls == 0) gg_tile_g128<V2Cfg<256>>(cur.mt, cur.A, cur.B, cur.SA, cur.SB, cur.C, cur.m0, cur.n0, lds);
         else gg_tile_g128<V2Cfg<128>>(cur.mt, cur.A, cur.B, cur.SA, cur.SB, cur.C, cur.m0, cur.n0, lds);
+      } else if ((QM & (1 << QT_F8G)) && qt == QT_F8G) {  // (no persistent build holds the type today)
+        const float* SAf = reinterpret_cast<const float*>(cur.SA);
+        const float* SBf = reinterpret_cast<const float*>(cur.SB);
+        if (cls == 0) gg_tile_f8g128<V2Cfg<256>>(cur.mt, cur.A, cur.B, SAf, SBf, cur.C, cur.m0, cur.n0, lds);
+        else gg_tile_f8g128<V2Cfg<128>>(cur.mt, cur.A, cur.B, SAf, SBf, cur.C, cur.m0, cur.n0, lds);
       } else if ((QM & (1 << QT_F8)) && qt == QT_F8) {
         if (cls == 0) gg_tile_v2<V2Cfg<256>, QT_F8, 0>(cur.mt, cur.A, cur.B, cur.SA, cur.SB, cur.C, cur.m0, cur.n0, lds, sk);
         else gg_tile_v2<V2Cfg<128>, QT_F8, 0>(cur.mt, cur.A, cur.B, cur.SA, cur.SB, cur.C, cur.m0, cur.n0, lds, sk);

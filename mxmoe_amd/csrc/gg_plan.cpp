@@ -53,6 +53,7 @@ int qtype_of(int a_bits, int w_bits, int gsize, int sym, int fmt, int* qt) {
   auto take = [&](int q) { return *qt = q, (int)MXMOE_GG_OK; };
   if (fmt == MXMOE_GG_FMT_E4M3) {  // w8a8_g-1_sym_E4M3 (tile_config.py:45, 104-106, 192)
     if (a_bits == 8 && w_bits == 8 && gsize == -1 && sym) return take(QT_F8);
+    if (a_bits == 8 && w_bits == 8 && gsize == 128 && sym) return take(QT_F8G);  // block-scaled: f32 group / block scales
     return fail(MXMOE_GG_ERR_UNSUPPORTED, "quant type not supported: w%da%d_g%d_%s_E4M3 (only w8a8_g-1_sym_E4M3)",
                 w_bits, a_bits, gsize, sym ? "sym" : "asym");
   }
@@ -1066,8 +1067,8 @@ namespace {
 int64_t sa_row_bytes(int qt, int K) {
   const QTypeInfo& t = qinfo(qt);
   if (t.weight_only || t.float16) return 0;
+  if (t.group_fold) return (t.dword_scales ? 4 : 2) * ((int64_t)K / t.k_mult);  // fp16 (w4a4 g128) or f32 group scales
   if (t.dword_scales) return 16 * (((int64_t)K / 32 + 15) / 16);  // e8m0 bytes, the device layout
-  if (t.group_fold) return 2 * ((int64_t)K / t.k_mult);
   return 2;
 }
 bool dyn_variant_ok(const PlanVariant& v) {

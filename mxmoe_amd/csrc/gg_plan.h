@@ -75,7 +75,7 @@ struct QTypeInfo {
                              // fp6 MFMA (the int8 one's cycles) per 96 B of K-128; MXFP4: the int8 tile's count and cycles, so 1
   int el_bits;               // K elements per stage = bkb * 8 / el_bits (0: 128, the fp6 images' K-128 blocks)
   double rate;               // MFMA flop per LDS byte-time, fp16 = 128
-  double fold;               // per-group f32 fold on top of the MFMAs
+  double fold;               // per-group f32 fold on top of the MFMAs (measured time ratio against the type without it)
   int code_bits;             // weight-only: bits per staged B code (MXFP4: its 2 scale bytes per column are 1/16 of the codes)
   AutoClass auto_class;
   double auto_rows;          // WeightOnly / Small: the mean-M limit of the small-batch kernel
@@ -111,6 +111,8 @@ constexpr QTypeInfo kQTypes[] = {
      1.0, 0, 0, 1.0, 4, kWo, kWoSmallMeanRows, nullptr, false},
     {QT_MXF8A, "w4a8_g32_sym_MXFP8", 8, false, false, "w4a8_g32_sym_MXFP8", 32, "w4a8_g32_sym_MXFP8", true, false,
      false, true, false, 1.0, 8, 256, 1.0, 0, kSm, kSmallMeanRowsMx8, nullptr, false},
+    {QT_F8G, "w8a8_g128_sym_E4M3", 8, false, false, "w8a8_g128_sym_E4M3", 128, "w8a8_g128_sym_E4M3", false, true, false,
+     false, false, 1.0, 8, 256, 1.1, 0, kGen, 0, nullptr, true},  // fold: 1.06-1.09x per-channel E4M3's time (profiles/r23/f8g128)
 };
 constexpr bool qtypes_in_order() {
   for (int i = 0; i < QT_COUNT; ++i)
@@ -174,7 +176,7 @@ inline PlanVariant plan_v2_base(int threads = 512) {
   v.tail2_bm = 64;
   return v;
 }
-// gg_v2_kernel's tile bodies (mx: the MX types' too)
+// gg_v2_kernel's tile bodies (mx: the MX types' and the block-scaled E4M3 type's too)
 inline PlanVariant plan_v2(bool mx) {
   PlanVariant v = plan_v2_base();
   // (w4a4 g128, gg_tile_g128: 256 / 128-row classes as int4)
@@ -185,6 +187,7 @@ inline PlanVariant plan_v2(bool mx) {
   if (mx) {
     v.geom[QT_MXF4] = v.geom[QT_MXF8A] = {256, 256, 128, 512};
     v.geom[QT_MXF4W] = {256, 256, 32, 512};  // weight-only MXFP4: the 4-bit stage
+    v.geom[QT_F8G] = {256, 256, 128, 512};   // w8a8_g128_sym_E4M3 (gg_tile_f8g128): one 128-K group per stage
   }
   v.silu_epi = true;  // gg_tile_v2's epilogue
   return v;

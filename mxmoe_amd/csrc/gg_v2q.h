@@ -465,6 +465,11 @@ __global__ __launch_bounds__(512, 2) void gg_v2q_kernel(GGArgs args) {
       if ((QM & (1 << QT_I4G)) && qt == QT_I4G) {
         if (cls == 0) gg_tile_g128<V2Cfg<256>>(cur.mt, cur.A, cur.B, cur.SA, cur.SB, cur.C, cur.m0, cur.n0, lds);
         else gg_tile_g128<V2Cfg<128>>(cur.mt, cur.A, cur.B, cur.SA, cur.SB, cur.C, cur.m0, cur.n0, lds);
+      } else if ((QM & (1 << QT_F8G)) && qt == QT_F8G) {  // (no persistent build holds the type today)
+        const float* SAf = reinterpret_cast<const float*>(cur.SA);
+        const float* SBf = reinterpret_cast<const float*>(cur.SB);
+        if (cls == 0) gg_tile_f8g128<V2Cfg<256>>(cur.mt, cur.A, cur.B, SAf, SBf, cur.C, cur.m0, cur.n0, lds);
+        else gg_tile_f8g128<V2Cfg<128>>(cur.mt, cur.A, cur.B, SAf, SBf, cur.C, cur.m0, cur.n0, lds);
       } else if ((QM & (1 << QT_F8)) && qt == QT_F8) {
         if (cls == 0) gg_tile_v2<V2Cfg<256>, QT_F8, 0>(cur.mt, cur.A, cur.B, cur.SA, cur.SB, cur.C, cur.m0, cur.n0, lds, sk);
         else gg_tile_v2<V2Cfg<128>, QT_F8, 0>(cur.mt, cur.A, cur.B, cur.SA, cur.SB, cur.C, cur.m0, cur.n0, lds, sk);

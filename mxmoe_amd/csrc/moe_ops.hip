@@ -579,6 +579,39 @@ __global__ __launch_bounds__(kThreads) void act_quant_kernel(typename ActArgsOf<
       if (c * 512 + lane * 8 < width) *reinterpret_cast<uint2*>(o8 + c * 512 + lane * 8) = bad ? uint2{0u, 0u} : q[c];
     return;
   }
+  if constexpr (F8) if (sg.qtag == MXMOE_ACT_E4M3_G128) {
+    // per (token, 128-element group) e4m3 with an f32 scale (include/mxmoe_moe.h; the A operand of w8a8_g128_sym_E4M3):
+    // a group is 16 adjacent lanes of one chunk, its amax a 4-step butterfly on the bit patterns. s = f32(amax) / 448
+    // in f32, 1 for a zero group; codes from the IEEE f32 quotient x / s (an f32 scale has 24 significant bits:
+    // codes_e4m3's reciprocal-and-residual sequence is proven for fp16 scales only). Scales f32, group-major
+    // [width/128][rows] at the (even) fp16 offset scale_off.
+    uint8_t* const o8 = a.out + sg.out_off + row * (int64_t)sg.width + col0;
+    float* const so = reinterpret_cast<float*>(a.scales + sg.scale_off);
+#pragma unroll
+    for (int c = 0; c < MAXC; ++c) {
+      if (c * 512 >= width) break;  // uniform
+      const int idx = c * 512 + lane * 8;
+      uint32_t mi = amax8_bits(x[c]);
+#pragma unroll
+      for (int d = 8; d >= 1; d >>= 1) mi = max(mi, (uint32_t)__shfl_xor((int)mi, d, 64));
+      if (idx >= width) continue;
+      const bool bad = mi >= 0x7C00u;  // an Inf or a NaN in the group: NaN scale, zero codes
+      float s = (float)__builtin_bit_cast(_Float16, (uint16_t)mi) / 448.0f;
+      if (mi == 0) s = 1.0f;
+      float y[8];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) y[j] = __builtin_amdgcn_fmed3f((float)x[c][j] / s, -448.0f, 448.0f);
+      int q0 = 0, q1 = 0;  // pack_wxax's 8-bit order, as codes_e4m3
+      q0 = __builtin_amdgcn_cvt_pk_fp8_f32(y[1], y[0], q0, false);
+      q0 = __builtin_amdgcn_cvt_pk_fp8_f32(y[3], y[2], q0, true);
+      q1 = __builtin_amdgcn_cvt_pk_fp8_f32(y[5], y[4], q1, false);
+      q1 = __builtin_amdgcn_cvt_pk_fp8_f32(y[7], y[6], q1, true);
+      *reinterpret_cast<uint2*>(o8 + idx) = bad ? uint2{0u, 0u} : uint2{(uint32_t)q0, (uint32_t)q1};
+      if ((lane & 15) == 0)
+        so[(int64_t)((col0 + idx) / 128) * sg.rows + row] = bad ? __builtin_nanf("") : s;
+    }
+    return;
+  }
   const int bits = sg.qtag == MXMOE_ACT_INT8 ? 8 : 4;
   const float qmax = bits == 8 ? 127.0f : 7.0f;
   const h2_t lim = {(_Float16)qmax, (_Float16)qmax};
@@ -714,7 +747,7 @@ bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 // clamp means the counts are not route's); a clamp or a sum below T * topk (ids outside [0, E)) sets bit 0
 // of the returned status.
 __host__ __device__ inline int act_bits(int tag) {
-  return tag == MXMOE_ACT_INT8 || tag == MXMOE_ACT_MXFP8 || tag == MXMOE_ACT_E4M3 ? 8
+  return tag == MXMOE_ACT_INT8 || tag == MXMOE_ACT_MXFP8 || tag == MXMOE_ACT_E4M3 || tag == MXMOE_ACT_E4M3_G128 ? 8
          : tag == MXMOE_ACT_INT4 || tag == MXMOE_ACT_INT4_G128 || tag == MXMOE_ACT_MXFP4 ? 4 : 16;
 }
 __host__ __device__ inline int32_t fill_segments(const int32_t* counts, int E, int64_t T, int topk, bool with_shared,
@@ -732,13 +765,14 @@ __host__ __device__ inline int32_t fill_segments(const int32_t* counts, int E, i
     }
     const int tag = tb.qtags[e], w = shared ? tb.width_shared : tb.width;
     const bool mx = tag == MXMOE_ACT_MXFP4 || tag == MXMOE_ACT_MXFP8;
-    if (mx) soff += soff & 1;  // its scale bytes are read as dwords: a 4-byte aligned block
+    const bool f32g = tag == MXMOE_ACT_E4M3_G128;  // f32 group scales: two fp16 elements each
+    if (mx || f32g) soff += soff & 1;  // its scales are read as dwords: a 4-byte aligned block
     const int64_t f = shared ? ntk : first;
     tb.segs[e] = mxmoe_moe_seg{tag, (int32_t)f, (int32_t)r, w, off, soff};
     if (dyn) dyn[e] = mxmoe_gg_dyn_row{(int32_t)r, 0, off, soff * 2, shared ? 0 : f * tb.ldc * 2};
     off += (r * w * act_bits(tag) / 8 + 15) / 16 * 16;
     if (mx) soff += r * (16 * ((w / 32 + 15) / 16)) / 2;  // (fp16 elements: two e8m0 bytes each)
-    else soff += tag == MXMOE_ACT_FP16 ? 0 : r * (tag == MXMOE_ACT_INT4_G128 ? w / 128 : 1);
+    else soff += tag == MXMOE_ACT_FP16 ? 0 : r * (f32g ? w / 64 : tag == MXMOE_ACT_INT4_G128 ? w / 128 : 1);
     if (!shared) first += r;
   }
   if (first != ntk) status |= MXMOE_MOE_SEG_COUNT_MISMATCH;
@@ -910,11 +944,11 @@ static int slots_impl(const char* fn, int mode, const void* routed_in, const voi
 }
 // a tag_mask's check (MXMOE_GG_OK or the failure, under the entry point's name) and which builds' tags it names
 static int tag_mask_tags(const char* fn, uint32_t tag_mask, ActTags* tags) {
-  // (tags 5 and 7 are not assigned)
-  if (tag_mask & ~((2u << MXMOE_ACT_MXFP4) - 1u | 1u << MXMOE_ACT_MXFP8 | 1u << MXMOE_ACT_E4M3))
+  // (tags 5, 7 and 9 are not assigned)
+  if (tag_mask & ~((2u << MXMOE_ACT_MXFP4) - 1u | 1u << MXMOE_ACT_MXFP8 | 1u << MXMOE_ACT_E4M3 | 1u << MXMOE_ACT_E4M3_G128))
     return fail(MXMOE_GG_ERR_UNSUPPORTED, "%s: unknown activation tag in mask %#x", fn, tag_mask);
   tags->mx = ((tag_mask >> MXMOE_ACT_MXFP4) & 1) || ((tag_mask >> MXMOE_ACT_MXFP8) & 1);
-  tags->f8 = (tag_mask >> MXMOE_ACT_E4M3) & 1;
+  tags->f8 = ((tag_mask >> MXMOE_ACT_E4M3) & 1) || ((tag_mask >> MXMOE_ACT_E4M3_G128) & 1);  // (both in the kActF8 builds)
   return MXMOE_GG_OK;
 }
 // what mxmoe_moe_combine and mxmoe_moe_combine_bias check alike once T > 0

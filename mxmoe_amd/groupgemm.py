@@ -99,6 +99,9 @@ FP16 = QParams()
 BF16 = QParams(fmt="bf16")
 W8A8 = QParams(8, 8, -1, True)
 W8A8_E4M3 = QParams(8, 8, -1, True, "E4M3")  # w8a8_g-1_sym_E4M3: OCP fp8 operands, f32 accumulate
+# w8a8_g128_sym_E4M3: block-scaled FP8 checkpoints (e4m3 weights with one f32 scale per 128 x 128 block, e4m3
+# activations with one f32 scale per token and 128-K group), each group folded in f32 (include/mxmoe_gg.h)
+W8A8_G128_E4M3 = QParams(8, 8, 128, True, "E4M3")
 W4A4 = QParams(4, 4, -1, True)
 W4A4_F6 = QParams(4, 4, -1, True, "F6")  # w4a4_g-1_sym on fp6 images (lab library: nat.pack_f6 of A and B)
 W4A4_MXFP4 = QParams(4, 4, 32, True, "MXFP4")  # w4a4_g32_sym_MXFP4: e2m1 codes, e8m0 block scales (include/mxmoe_gg.h)
@@ -114,7 +117,7 @@ W4A16_G128_SYM = QParams(16, 4, 128, True)
 W8A16_ASYM = QParams(16, 8, -1, False)
 W2A16_G128_ASYM = QParams(16, 2, 128, False)
 
-SUPPORTED = {q.qcfg: q for q in (FP16, BF16, W8A8, W8A8_E4M3, W4A4, W4A4_MXFP4, W4A16_MXFP4, W4A8_MXFP8, W4A4_G128, W4A16_G128_ASYM, W4A16_ASYM, W4A16_G128_SYM, W8A16_ASYM,
+SUPPORTED = {q.qcfg: q for q in (FP16, BF16, W8A8, W8A8_E4M3, W8A8_G128_E4M3, W4A4, W4A4_MXFP4, W4A16_MXFP4, W4A8_MXFP8, W4A4_G128, W4A16_G128_ASYM, W4A16_ASYM, W4A16_G128_SYM, W8A16_ASYM,
                                   QParams(16, 4, -1, True), QParams(16, 8, -1, True), QParams(16, 8, 128, True),
                                   QParams(16, 8, 128, False), W2A16_G128_ASYM, QParams(16, 2, -1, False),
                                   QParams(16, 2, -1, True), QParams(16, 2, 128, True))}
@@ -128,7 +131,8 @@ class Problem:
     in pack_wxax layout, scale_a fp16 [M], scale_b fp16 [N] (w4a4_g128: [K/128][M] and [K/128][N],
     the permute_scale layout; MXFP4: codes uint8 [rows, K/2] as quant_mxfp4 returns them, scales uint8
     [rows, 16 * ceil(K/32 / 16)] in the device layout of pack_mxfp4_scales; MXFP8: A uint8 [M, K] e4m3
-    codes as quant_mxfp8 returns them, B and both scales as MXFP4's).  C fp16 [M, ldc] (ldc >= N).
+    codes as quant_mxfp8 returns them, B and both scales as MXFP4's; w8a8_g128_sym_E4M3: codes as E4M3's, scale_a
+    f32 [K/128][M], scale_b f32 [K/128][ceil(N/128)], both group-major).  C fp16 [M, ldc] (ldc >= N).
     """
 
     A: torch.Tensor
@@ -184,6 +188,15 @@ class Problem:
             need(self.B, (torch.uint8,), "B (e2m1 codes)")
             need(self.scale_a, (torch.uint8,), "scale_a (e8m0, pack_mxfp4_scales)")
             need(self.scale_b, (torch.uint8,), "scale_b (e8m0, pack_mxfp4_scales)")
+        elif self.q.is_fp8 and self.q.gsize == 128:
+            if self.K % 128:
+                raise ValueError(f"{self.q.qcfg}: K={self.K} must be a multiple of the 128-element scale group")
+            G, NB = self.K // 128, (self.N + 127) // 128
+            need(self.scale_a, (torch.float32,), "scale_a (f32 [K/128][M])")
+            need(self.scale_b, (torch.float32,), "scale_b (f32 [K/128][ceil(N/128)])")
+            for t, n, what in ((self.scale_a, G * self.M, "scale_a"), (self.scale_b, G * NB, "scale_b")):
+                if t is not None and t.numel() > 0 and t.numel() < n:
+                    raise ValueError(f"{self.q.qcfg}: {what} holds {t.numel()} scales, the problem needs {n}")
 
     def to_c(self) -> nat.GGProblemC:
         def ptr(t):

@@ -21,8 +21,8 @@ from typing import Optional, Sequence
 import torch
 
 from .groupgemm import GroupGemm, Problem, QParams
-from .quantize import (pack_e4m3, pack_mxfp4_scales, pack_weightonly_mi355x, pack_wxax, quant_e4m3, quant_mxfp4, quant_mxfp8,
-                       quant_rtn_sym, quant_weightonly)
+from .quantize import (pack_e4m3, pack_mxfp4_scales, pack_weightonly_mi355x, pack_wxax, quant_e4m3, quant_e4m3_g128,
+                       quant_mxfp4, quant_mxfp8, quant_rtn_sym, quant_weight_e4m3_g128, quant_weightonly)
 from .workload import QShape
 
 
@@ -49,6 +49,8 @@ class LayerInputs:
                 tot += 2 * s.N * (1 if s.gsize == -1 else s.K // s.gsize) * (1 if s.sym else 2)
             elif s.fmt in ("MXFP4", "MXFP8"):  # one e8m0 byte per 32-K block
                 tot += (s.M + s.N) * (s.K // 32)
+            elif s.fmt == "E4M3" and s.gsize == 128:  # f32: one per (row, group) and per 128 x 128 block
+                tot += 4 * (s.M + (s.N + 127) // 128) * (s.K // 128)
             elif not plain:
                 tot += 2 * (s.M + s.N) * (1 if s.gsize == -1 else s.K // s.gsize)
         return tot
@@ -66,7 +68,12 @@ def build_layer_inputs(shapes: Sequence[QShape], device="cuda", seed: int = 42,
         a = (torch.rand(M, K, generator=g, device=dev) * 2 - 1).to(torch.float16)
         b = (torch.rand(N, K, generator=g, device=dev) * 2 - 1).to(torch.float16)
         C = torch.empty(max(M, 1), N, dtype=torch.float16, device=dev)
-        if q.is_fp8:
+        if q.is_fp8 and q.gsize == 128:  # block-scaled: f32 scales, group-major
+            (qa, sa), (qb, sb) = quant_e4m3_g128(a), quant_weight_e4m3_g128(b)
+            probs.append(Problem(A=pack_e4m3(qa), B=pack_e4m3(qb), C=C, M=M, N=N, K=K, q=q, scale_a=sa.t().contiguous(),
+                                 scale_b=sb.t().contiguous()))
+            del qa, qb
+        elif q.is_fp8:
             qa, sa = quant_e4m3(a)
             qb, sb = quant_e4m3(b)
             probs.append(Problem(A=pack_e4m3(qa), B=pack_e4m3(qb), C=C, M=M, N=N, K=K, q=q, scale_a=sa, scale_b=sb))

@@ -36,7 +36,12 @@ from .groupgemm import DynamicGroupGemm, GroupGemm, Problem, QParams
 ACT_FP16, ACT_INT8, ACT_INT4, ACT_INT4_G128, ACT_MXFP4 = 0, 1, 2, 3, 4
 ACT_MXFP8 = 6  # MXMOE_ACT_MXFP8 (w4a8_g32_sym_MXFP8); 5 is not assigned (include/mxmoe_moe.h)
 ACT_E4M3 = 8   # MXMOE_ACT_E4M3 (w8a8_g-1_sym_E4M3: e4m3 codes, one fp16 scale per token); 7 is not assigned either
-_BITS = {ACT_FP16: 16, ACT_INT8: 8, ACT_INT4: 4, ACT_INT4_G128: 4, ACT_MXFP4: 4, ACT_MXFP8: 8, ACT_E4M3: 8}
+# MXMOE_ACT_E4M3_G128 (w8a8_g128_sym_E4M3: e4m3 codes, one f32 scale per token and 128-element group, group-major).
+# Not the free value 7: a tag_mask with bit 7 (or 9) stays "unknown activation tag", as callers have always seen it.
+ACT_E4M3_G128 = 10
+_BITS = {ACT_FP16: 16, ACT_INT8: 8, ACT_INT4: 4, ACT_INT4_G128: 4, ACT_MXFP4: 4, ACT_MXFP8: 8, ACT_E4M3: 8,
+         ACT_E4M3_G128: 8}
+_DWORD_TAGS = (ACT_MXFP4, ACT_MXFP8, ACT_E4M3_G128)  # scales read as dwords: an even scale_off
 _MX_TAGS = (ACT_MXFP4, ACT_MXFP8)  # block-scaled tags: e8m0 scale rows, the MX builds of the activation kernel
 
 
@@ -47,9 +52,11 @@ def _mx_scale_row(width: int) -> int:
 
 def _scale_elems(tag: int, width: int) -> int:
     """fp16 elements of scale store per row of a segment: the MX tags' e8m0 bytes two to an element, one scale per
-    128-element group for g128, none for fp16, else (INT8, INT4, E4M3) one per row."""
+    128-element group for g128 (E4M3_G128: an f32, two elements), none for fp16, else (INT8, INT4, E4M3) one per row."""
     if tag in _MX_TAGS:
         return _mx_scale_row(width) // 2
+    if tag == ACT_E4M3_G128:
+        return width // 64
     return width // 128 if tag == ACT_INT4_G128 else 0 if tag == ACT_FP16 else 1
 
 
@@ -72,6 +79,14 @@ def qtag_of(a_bits: int, gsize: int, fmt: str = "") -> int:
     if a_bits == 8 and gsize == 32:  # w4a8_g32_sym_MXFP8 (likewise)
         return ACT_MXFP8
     raise ValueError(f"activation quantisation a{a_bits} g{gsize} not supported")
+
+
+def act_tag(q: QParams) -> int:
+    """The activation tag of a layer's QParams: ``qtag_of``'s, and MXMOE_ACT_E4M3_G128 for w8a8_g128_sym_E4M3 — a type
+    the reference's tag function does not know, so ``qtag_of`` itself keeps refusing (8, 128) as it always has."""
+    if q.a_bits == 8 and q.gsize == 128 and q.fmt == "E4M3":
+        return ACT_E4M3_G128
+    return qtag_of(q.a_bits, q.gsize, q.fmt)
 
 
 def _tag_mask(qtags: Sequence[int]) -> int:
@@ -316,7 +331,7 @@ class ActBatch:
         v = self.scales[s.scale_off:s.scale_off + s.rows * _scale_elems(tag, s.width)]
         if tag in _MX_TAGS:  # e8m0 bytes [rows, 16 G] inside the fp16 store
             return v.view(torch.uint8).view(s.rows, _mx_scale_row(s.width))
-        return v
+        return v.view(torch.float32) if tag == ACT_E4M3_G128 else v  # (f32 [width/128][rows], flat)
 
 
 def _make_segments(rows: Sequence[int], first: Sequence[int], widths: Sequence[int], qtags: Sequence[int],
@@ -325,8 +340,8 @@ def _make_segments(rows: Sequence[int], first: Sequence[int], widths: Sequence[i
     for r, f, w, tag in zip(rows, first, widths, qtags):
         if w % 128:
             raise ValueError(f"segment width {w} must be a multiple of 128")
-        if tag in _MX_TAGS:
-            soff += soff % 2  # its scale bytes are read as dwords: a 4-byte aligned block
+        if tag in _DWORD_TAGS:
+            soff += soff % 2  # its scales are read as dwords: a 4-byte aligned block
         segs.append(nat.MoeSegC(tag, f, r, w, off, soff))
         off += (r * w * _BITS[tag] // 8 + 15) // 16 * 16  # 16-B aligned A operands
         soff += r * _scale_elems(tag, w)
@@ -345,7 +360,7 @@ _ACT_MODES = {"gather": 0, "plain": 1, "fused": 2, "interleaved": 3}
 _LEGACY_ENTRY = {"gather": "mxmoe_moe_quant_act", "plain": "mxmoe_moe_silu_mul_quant", "fused": "mxmoe_moe_quant_slots",
                  "interleaved": "mxmoe_moe_silu_mul_quant_il"}
 _MX_MASK = _tag_mask(_MX_TAGS)
-_TAGGED_MASK = _MX_MASK | _tag_mask([ACT_E4M3])  # tags only the entries with a tag_mask carry (builds of their own)
+_TAGGED_MASK = _MX_MASK | _tag_mask([ACT_E4M3, ACT_E4M3_G128])  # tags only the entries with a tag_mask carry (builds of their own)
 
 
 def _act_entry(mode: str, has_mx_tag: bool, glu: bool) -> str:
@@ -753,7 +768,7 @@ def prepare_weight(w: torch.Tensor, q: QParams, interleave: bool = False) -> Exp
     per-row scales follow their rows)."""
     from .groupgemm import interleave_gate_up
     from .quantize import (pack_e4m3, pack_mxfp4_scales, pack_weightonly_mi355x, pack_wxax, quant_e4m3, quant_mxfp4,
-                           quant_rtn_sym, quant_weightonly)
+                           quant_rtn_sym, quant_weight_e4m3_g128, quant_weightonly)
 
     N, K = w.shape
     if interleave:
@@ -766,6 +781,9 @@ def prepare_weight(w: torch.Tensor, q: QParams, interleave: bool = False) -> Exp
     if q.is_weight_only:
         codes, sz = quant_weightonly(w, q.w_bits, q.gsize, q.sym)
         return ExpertWeights(pack_weightonly_mi355x(codes, q.w_bits), sz, q, N, K)
+    if q.is_fp8 and q.gsize == 128:  # w8a8_g128_sym_E4M3: one f32 scale per 128 x 128 block, stored group-major
+        codes, sc = quant_weight_e4m3_g128(w)
+        return ExpertWeights(pack_e4m3(codes), sc.t().contiguous(), q, N, K)
     if q.is_fp8:  # w8a8_g-1_sym_E4M3: e4m3 codes in pack_wxax's 8-bit order, one fp16 scale per output row
         codes, sc = quant_e4m3(w)
         return ExpertWeights(pack_e4m3(codes), sc, q, N, K)
@@ -802,6 +820,32 @@ def prepare_weight_mx(codes: torch.Tensor, scales: torch.Tensor, q: QParams, war
         warnings.warn(f"prepare_weight_mx: {bad} of {scales.numel()} scale bytes lie outside [{lo}, {hi}]: with fp16 "
                       "activations their blocks' weights are not exact fp16 values (include/mxmoe_gg.h)", stacklevel=2)
     return ExpertWeights(codes.contiguous(), pack_mxfp4_scales(scales), q, N, K, bad)
+
+
+def prepare_weight_e4m3_g128(codes, scale_inv) -> ExpertWeights:
+    """Weights that already are block-scaled FP8 (a checkpoint's ``weight`` / ``weight_scale_inv``) -> the GroupGEMM's B
+    operand for w8a8_g128_sym_E4M3, with no requantisation: codes ``float8_e4m3fn`` or uint8 [N, K] (K % 128 == 0),
+    scale_inv f32 [ceil(N/128), K/128]. Either may be a (gate, up) pair of such tensors, which are concatenated
+    into one gate_up weight: the blocks of the two then only line up when ``inter % 128 == 0`` (ValueError otherwise)."""
+    from .groupgemm import W8A8_G128_E4M3
+    from .quantize import pack_e4m3
+
+    if isinstance(codes, (tuple, list)) != isinstance(scale_inv, (tuple, list)):
+        raise ValueError("prepare_weight_e4m3_g128: codes and scale_inv both single tensors or both (gate, up) pairs")
+    if isinstance(codes, (tuple, list)):
+        if any(c.shape[0] % 128 for c in codes):
+            raise ValueError(f"prepare_weight_e4m3_g128: gate and up of {codes[0].shape[0]} rows cannot be concatenated: "
+                             "inter % 128 != 0 leaves a scale block astride the two")
+        codes, scale_inv = torch.cat(list(codes)), torch.cat(list(scale_inv))
+    if codes.dtype == torch.float8_e4m3fn:
+        codes = codes.view(torch.uint8)
+    if codes.dtype != torch.uint8 or codes.dim() != 2 or codes.shape[1] % 128:
+        raise ValueError("prepare_weight_e4m3_g128: codes float8_e4m3fn or uint8 [N, K], K % 128 == 0")
+    N, K = codes.shape
+    if scale_inv.dtype != torch.float32 or tuple(scale_inv.shape) != ((N + 127) // 128, K // 128):
+        raise ValueError(f"prepare_weight_e4m3_g128: weight_scale_inv f32 [{(N + 127) // 128}, {K // 128}], got "
+                         f"{scale_inv.dtype} {tuple(scale_inv.shape)}")
+    return ExpertWeights(pack_e4m3(codes.contiguous()), scale_inv.t().contiguous(), W8A8_G128_E4M3, N, K)
 
 
 def prepare_weight_e4m3(codes: torch.Tensor, scales: torch.Tensor, warn: bool = True) -> ExpertWeights:
@@ -891,7 +935,7 @@ class MoEFFN:
 
     # gate_up qcfgs with the SiLU epilogue: fp16 / w8a8 / w4a4 on every product kernel, weight-only
     # on the small-batch kernel (wo3; a large call of those falls back to the interleaved form).
-    # w8a8_g-1_sym_E4M3 is not among them (its tile has no SiLU epilogue): a layer with an E4M3 gate_up is plain
+    # the E4M3 types are not among them (their tiles have no SiLU epilogue): a layer with an E4M3 gate_up is plain
     FUSE_QCFGS = ("fp16", "w8a8_g-1_sym", "w4a4_g-1_sym", "w4a8_g32_sym_MXFP8")
     FUSE_WEIGHT_ONLY = True
 
@@ -947,8 +991,8 @@ class MoEFFN:
 
         self.w1 = [prep(w, q[0], self.fuse_silu) for w, q in zip(gate_up, qcfg)]
         self.w2 = [prep(w, q[1]) for w, q in zip(down, qcfg)]
-        self.tag1 = [qtag_of(q[0].a_bits, q[0].gsize, q[0].fmt) for q in qcfg]
-        self.tag2 = [qtag_of(q[1].a_bits, q[1].gsize, q[1].fmt) for q in qcfg]
+        self.tag1 = [act_tag(q[0]) for q in qcfg]
+        self.tag2 = [act_tag(q[1]) for q in qcfg]
         self.gate_up_mode: Optional[str] = None  # None: the library decides; "interleaved": A/B override
 
     @property
@@ -1272,12 +1316,12 @@ class GraphForward:
         def stores(tags, w, ws):
             """Worst-case activation and scale stores over the tags present (16-B / dword padding per segment)."""
             nbytes = n * w * max(_BITS[t] for t in tags[:E]) // 8 + 16 * E
-            nscale = n * max(_scale_elems(t, w) for t in tags[:E]) + E
+            nscale = n * max(_scale_elems(t, w) for t in tags[:E]) + E + E % 2  # (even: an f32 view of the store)
             if shared:
                 nbytes += T * ws * _BITS[tags[E]] // 8 + 16
                 nscale += T * _scale_elems(tags[E], ws) + 1
             return (torch.zeros(nbytes, dtype=torch.uint8, device=dev),
-                    torch.zeros(max(nscale, 1), dtype=torch.float16, device=dev))
+                    torch.zeros(max(nscale + nscale % 2, 2), dtype=torch.float16, device=dev))
 
         self.a1, self.s1 = stores(ffn.tag1, H, H)
         self.a2, self.s2 = stores(ffn.tag2, N, Ns)
@@ -1289,7 +1333,8 @@ class GraphForward:
                 w = ws[e]
                 tag = tags[e]
                 A = store.view(torch.float16) if tag == ACT_FP16 else store
-                sa = None if tag == ACT_FP16 else scales.view(torch.uint8) if tag in _MX_TAGS else scales
+                sa = None if tag == ACT_FP16 else scales.view(torch.uint8) if tag in _MX_TAGS else \
+                    scales.view(torch.float32) if tag == ACT_E4M3_G128 else scales
                 ps.append(Problem(A=A, B=w.B, C=C_shared if e == E else C_routed, M=T if e == E else n, N=w.N, K=w.K,
                                   q=w.q, scale_a=sa, scale_b=w.scale_b, silu=silu))
             return DynamicGroupGemm(ps, joint=range(E), rows_total=n, device=dev)

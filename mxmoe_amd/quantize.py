@@ -106,6 +106,48 @@ def quant_e4m3(x: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
     return q.view(torch.uint8), scale
 
 
+def quant_e4m3_g128(x: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
+    """Per-(row, 128-K group) E4M3 quantisation of fp16 [rows, K] for the A operand of w8a8_g128_sym_E4M3 ->
+    (uint8 OCP e4m3 codes in logical K order, f32 scales [rows, K/128]): scale = f32(amax) / 448 in f32, 1 for an
+    all-zero group (no floor: an f32 scale cannot underflow here), code = e4m3_rn(f32(x) / scale), saturating.
+    A group holding Inf or NaN gets zero codes and a NaN scale (the MXMOE_ACT_E4M3_G128 contract,
+    include/mxmoe_moe.h). ``.t().contiguous()`` of the scales is the GroupGEMM's group-major layout."""
+    if x.dtype != torch.float16:
+        raise TypeError("quant_e4m3_g128 expects fp16 input")
+    rows, K = x.shape
+    if K % 128:
+        raise ValueError("quant_e4m3_g128: K must be a multiple of 128")
+    xg = x.float().reshape(rows, K // 128, 128)
+    amax = xg.abs().amax(dim=-1)
+    bad = ~torch.isfinite(amax)
+    scale = amax / E4M3_MAX
+    scale = torch.where(amax == 0, torch.ones_like(scale), scale)
+    q = (xg / scale[..., None]).clamp(-E4M3_MAX, E4M3_MAX)
+    q = torch.where(bad[..., None], torch.zeros_like(q), q).to(torch.float8_e4m3fn)
+    scale = torch.where(bad, torch.full_like(scale, float("nan")), scale)
+    return q.view(torch.uint8).reshape(rows, K), scale
+
+
+def quant_weight_e4m3_g128(w: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
+    """fp16 [N, K] -> (uint8 e4m3 codes [N, K], f32 scales [ceil(N/128), K/128]): one scale = amax / 448 per
+    128 x 128 block (1 for an all-zero block; the last row block may be partial), the checkpoints'
+    ``weight_scale_inv`` (moe.prepare_weight_e4m3_g128 takes the pair)."""
+    if w.dtype != torch.float16:
+        raise TypeError("quant_weight_e4m3_g128 expects fp16 input")
+    N, K = w.shape
+    if K % 128:
+        raise ValueError("quant_weight_e4m3_g128: K must be a multiple of 128")
+    NB = (N + 127) // 128
+    wp = torch.zeros(NB * 128, K, dtype=torch.float32, device=w.device)
+    wp[:N] = w.float()
+    blk = wp.reshape(NB, 128, K // 128, 128)
+    amax = blk.abs().amax(dim=(1, 3))
+    scale = amax / E4M3_MAX
+    scale = torch.where(amax == 0, torch.ones_like(scale), scale)
+    q = (blk / scale[:, None, :, None]).clamp(-E4M3_MAX, E4M3_MAX).to(torch.float8_e4m3fn)
+    return q.view(torch.uint8).reshape(NB * 128, K)[:N].contiguous(), scale
+
+
 def pack_e4m3(codes: torch.Tensor) -> torch.Tensor:
     """uint8 e4m3 codes [rows, K] -> the pack_wxax 8-bit byte order (QCFG_W8A8_E4M3: T_PACK half,
     PACK_DIM K — each 16-bit word holds elements (2j, 2j+1) with 2j in the high byte)."""

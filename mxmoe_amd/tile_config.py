@@ -23,7 +23,7 @@ log = logging.getLogger("mxmoe_amd.tile_config")
 
 SUPPORTED_QCFG = [
     "fp16", "fp16_accfp16", "bf16",
-    "w8a8_g-1_sym", "w8a8_g-1_sym_E4M3",
+    "w8a8_g-1_sym", "w8a8_g-1_sym_E4M3", "w8a8_g128_sym_E4M3",
     "w4a4_g-1_sym", "w4a4_g128_sym",
     *[f"w{wbits}a16_g{gsize}_{sym}{ty}" for wbits in [8, 4, 2] for gsize in [-1, 128] for sym in ["sym", "asym"]
       for ty in ["", "_accfp16", "_bf16"]],
@@ -31,7 +31,7 @@ SUPPORTED_QCFG = [
 
 # what the MI355X kernels implement; the _accfp16 forms run as their f32-accumulating base type
 # (MFMA has no fp16 accumulator); the weight-only _bf16 forms are not built
-MI355X_QCFG = ["fp16", "fp16_accfp16", "bf16", "w8a8_g-1_sym", "w8a8_g-1_sym_E4M3", "w4a4_g-1_sym", "w4a4_g128_sym",
+MI355X_QCFG = ["fp16", "fp16_accfp16", "bf16", "w8a8_g-1_sym", "w8a8_g-1_sym_E4M3", "w8a8_g128_sym_E4M3", "w4a4_g-1_sym", "w4a4_g128_sym",
                *[f"w{w}a16_g{g}_{s}{t}" for w in (4, 8, 2) for g in (-1, 128) for s in ("sym", "asym")
                  for t in ("", "_accfp16")]]
 
