@@ -437,7 +437,9 @@ enum { MXMOE_DECODE_FP16 = 0, MXMOE_DECODE_W8A8 = 1, MXMOE_DECODE_W4A4 = 2,
        MXMOE_DECODE_W4A16_ASYM = 8, MXMOE_DECODE_W8A16_ASYM = 9, MXMOE_DECODE_W4A16_G128_ASYM = 10,
        MXMOE_DECODE_W8A16_G128_ASYM = 11,
        /* the _lp entries only: e4m3, MXFP8 and MXFP4 activations */
-       MXMOE_DECODE_W8A8_E4M3 = 12, MXMOE_DECODE_W4A8_MXFP8 = 13, MXMOE_DECODE_W4A4_MXFP4 = 14 }; /* per linear */
+       MXMOE_DECODE_W8A8_E4M3 = 12, MXMOE_DECODE_W4A8_MXFP8 = 13, MXMOE_DECODE_W4A4_MXFP4 = 14,
+       /* the _f8g entries only: block-scaled FP8 (w8a8_g128_sym_E4M3) */
+       MXMOE_DECODE_W8A8_G128_E4M3 = 15 }; /* per linear */
 enum { MXMOE_DECODE_GU_PLAIN = 0, MXMOE_DECODE_GU_INTERLEAVED = 1 };
 enum { MXMOE_DECODE_BAD_ID = 1, MXMOE_DECODE_BAD_KIND = 2 };                   /* bits of *status */
 typedef struct mxmoe_moe_decode_expert {
@@ -551,6 +553,39 @@ int mxmoe_moe_decode_gate_up_lp(const mxmoe_moe_glu* glu, int dtype, const void*
 int mxmoe_moe_decode_down_lp(int64_t T, int topk, int E, int with_shared, const int32_t* topk_ids,
                              const mxmoe_moe_decode_expert* experts, uint32_t kind_mask, int H, int N, int N_shared,
                              const void* act, const void* act_shared, void* y, void* ys, int32_t* status, void* stream);
+
+/* The decode forward for block-scaled FP8 experts (added to ABI 7 without a version bump): layers whose experts are all
+ * w8a8_g128_sym_E4M3, the shared expert included (the format FP8 MoE checkpoints ship in), on kernels of their own
+ * (decode_f8g_kernel, mxmoe_amd/csrc/moe_decode_f8g.h). The argument lists are the _lp entries', glu included; pair
+ * order, safety and limits are those of mxmoe_moe_decode_gate_up / mxmoe_moe_decode_down; the expert record is unchanged
+ * (40 bytes). The eight entries above keep their kernels and their mask checks and refuse kind bit 15.
+ *   MXMOE_DECODE_W8A8_G128_E4M3 (w8a8_g128_sym_E4M3), the GroupGEMM's operands of that type used in place:
+ *   b1 / b2   the e4m3 codes in pack_wxax's 8-bit order, uint8 [rows][K] (16-byte aligned).
+ *   sb1 / sb2 f32 [K / 128][ceil(rows / 128)], group-major, 4-byte aligned: the GroupGEMM's scale_b. gate_up: rows = 2 N
+ *             in the plain [gate | up] layout (N % 128 == 0 puts a block on one side of the seam).
+ *   A row     the codes and f32 group scales of MXMOE_ACT_E4M3_G128, bit for bit: per 128-element group s = f32(amax) /
+ *             448 (1 for a zero group), codes from the IEEE f32 quotient clamped to +-448; a group holding an Inf or a
+ *             NaN: zero codes and a NaN scale.
+ *   v(r)      per K group g, acc_g is one v_mfma_scale_f32_16x16x128_f8f6f4 sum on a zero accumulator with unit e8m0
+ *             scales; out = fmaf(acc_g, f32_rn(sa[row][g] * sb[g][r / 128]), out), groups ascending within a wave's K
+ *             slice; the slices' partial sums are added in slice order; v = fp16_rn(out). A tile of 32 columns splits K
+ *             in two slices (each ceil(K / 256) groups, the second what remains), wider tiles in one. With one slice
+ *             this is the GroupGEMM's contract of the type (include/mxmoe_gg.h) word for word; with two it is within its
+ *             f32 summation order.
+ *   gate_up then applies the _ex entries' epilogue (SiLU, or glu's biases and clamp); down biases stay in the combine.
+ * Refusals, before any HIP call and under these entries' names: everything the first two entries check about sizes,
+ * pointers and dtype, and glu's checks; a kind_mask other than exactly 1 << 15: MXMOE_GG_ERR_UNSUPPORTED (the type is
+ * not mixed with other kinds in one launch); layout != MXMOE_DECODE_GU_PLAIN: MXMOE_GG_ERR_UNSUPPORTED (the type has no
+ * SiLU-epilogue layout). A record whose kind is not 15: MXMOE_DECODE_BAD_KIND and nothing written. An id outside [0, E):
+ * MXMOE_DECODE_BAD_ID, its rows kept. T == 0: OK, no launch. One launch each, no allocation, no synchronisation:
+ * graph-capturable. */
+int mxmoe_moe_decode_gate_up_f8g(const mxmoe_moe_glu* glu, int dtype, const void* hidden, int64_t T, int topk, int E,
+                                 int with_shared, const int32_t* topk_ids, const mxmoe_moe_decode_expert* experts,
+                                 uint32_t kind_mask, int H, int N, int N_shared, int layout, void* act, void* act_shared,
+                                 int32_t* status, void* stream);
+int mxmoe_moe_decode_down_f8g(int64_t T, int topk, int E, int with_shared, const int32_t* topk_ids,
+                              const mxmoe_moe_decode_expert* experts, uint32_t kind_mask, int H, int N, int N_shared,
+                              const void* act, const void* act_shared, void* y, void* ys, int32_t* status, void* stream);
 
 #ifdef __cplusplus
 }

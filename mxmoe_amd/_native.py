@@ -113,6 +113,8 @@ EXPORTED_SYMBOLS = (
     "mxmoe_moe_decode_gate_up_wo", "mxmoe_moe_decode_down_wo",
     # the decode forward on MFMA: experts with E4M3, MXFP8 or MXFP4 activations beside all the kinds above
     "mxmoe_moe_decode_gate_up_lp", "mxmoe_moe_decode_down_lp",
+    # the decode forward for block-scaled FP8 experts (w8a8_g128_sym_E4M3): kernels of their own
+    "mxmoe_moe_decode_gate_up_f8g", "mxmoe_moe_decode_down_f8g",
 )
 # added to ABI 7 without a version bump (additive): a product library without them is a stale build
 GPTOSS_SYMBOLS = ("mxmoe_moe_gate_ex2", "mxmoe_moe_glu_quant", "mxmoe_moe_combine_bias")
@@ -123,6 +125,7 @@ DECODE_SYMBOLS = ("mxmoe_moe_decode_gate_up", "mxmoe_moe_decode_down")  # (likew
 DECODE_EX_SYMBOLS = ("mxmoe_moe_decode_gate_up_ex", "mxmoe_moe_decode_down_ex")  # (likewise: gpt-oss layers)
 DECODE_WO_SYMBOLS = ("mxmoe_moe_decode_gate_up_wo", "mxmoe_moe_decode_down_wo")  # (likewise: weight-only experts)
 DECODE_LP_SYMBOLS = ("mxmoe_moe_decode_gate_up_lp", "mxmoe_moe_decode_down_lp")  # (likewise: low-precision activations)
+DECODE_F8G_SYMBOLS = ("mxmoe_moe_decode_gate_up_f8g", "mxmoe_moe_decode_down_f8g")  # (likewise: block-scaled FP8 experts)
 DT_FP16, DT_BF16 = 0, 1  # MXMOE_DT_* (include/mxmoe_moe.h)
 # MXMOE_DECODE_* (include/mxmoe_moe.h): the token limit, the kinds per linear, the gate_up layouts, the status bits
 DECODE_MAX_T = 16
@@ -133,6 +136,7 @@ DECODE_W4A16, DECODE_W8A16, DECODE_W4A16_G128, DECODE_W8A16_G128 = 4, 5, 6, 7
 DECODE_W4A16_ASYM, DECODE_W8A16_ASYM, DECODE_W4A16_G128_ASYM, DECODE_W8A16_G128_ASYM = 8, 9, 10, 11
 # the _lp entries only: e4m3 / MXFP8 / MXFP4 activations (w8a8_g-1_sym_E4M3, w4a8_g32_sym_MXFP8, w4a4_g32_sym_MXFP4)
 DECODE_W8A8_E4M3, DECODE_W4A8_MXFP8, DECODE_W4A4_MXFP4 = 12, 13, 14
+DECODE_W8A8_G128_E4M3 = 15  # the _f8g entries only: w8a8_g128_sym_E4M3, never mixed with another kind in a launch
 
 
 def decode_wo_kind(w_bits: int, gsize: int, sym: bool) -> int:
@@ -339,6 +343,11 @@ def _declare(lib: ctypes.CDLL) -> None:
         lib.mxmoe_moe_decode_gate_up_lp.argtypes = list(lib.mxmoe_moe_decode_gate_up_ex.argtypes)
         lib.mxmoe_moe_decode_down_lp.restype = c.c_int
         lib.mxmoe_moe_decode_down_lp.argtypes = list(lib.mxmoe_moe_decode_down_ex.argtypes)
+    if all(hasattr(lib, fn) for fn in DECODE_F8G_SYMBOLS):  # (builds before the block-scaled FP8 decode forward lack them)
+        lib.mxmoe_moe_decode_gate_up_f8g.restype = c.c_int
+        lib.mxmoe_moe_decode_gate_up_f8g.argtypes = list(lib.mxmoe_moe_decode_gate_up_ex.argtypes)
+        lib.mxmoe_moe_decode_down_f8g.restype = c.c_int
+        lib.mxmoe_moe_decode_down_f8g.argtypes = list(lib.mxmoe_moe_decode_down_ex.argtypes)
 
 
 def lib() -> ctypes.CDLL:

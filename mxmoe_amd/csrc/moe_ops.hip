@@ -824,6 +824,7 @@ int segments_check(const int32_t* counts, int E, int64_t T, int topk, const mxmo
 
 #include "moe_decode.h"  // the decode forward's kernels (after the quantiser helpers above, which they call)
 #include "moe_decode_mfma.h"  // its MFMA tile: the kinds with e4m3 / MXFP8 / MXFP4 activations (the _lp entries)
+#include "moe_decode_f8g.h"   // block-scaled FP8 experts (w8a8_g128_sym_E4M3): a kernel of their own (the _f8g entries)
 
 using namespace mxmoe;
 
@@ -1071,13 +1072,17 @@ static int glu_check(const char* fn, const mxmoe_moe_glu* glu) {
 // The two decode entries and their _ex and _wo forms: one body of checks and one launcher each. level: decode::kEx, the
 // _ex entry (kind bit 3, the _ex kernels; glu may be NULL: SiLU and no bias), decode::kWo, the _wo entry (kind bits up
 // to 11, the _wo kernels, glu likewise), decode::kLp, the _lp entry (kind bits up to 14, the _lp kernels, glu likewise);
-// decode::kFirst: glu is NULL and the first entries' kernels run.
+// decode::kFirst: glu is NULL and the first entries' kernels run. decode::kF8g: the _f8g entry (kind bit 15 alone, the
+// plain layout, decode_f8g_kernel of moe_decode_f8g.h; glu as the _ex entry's).
+static int decode_mask_check(const char* fn, int level, uint32_t kind_mask, int layout) {
+  return level == decode::kF8g ? decode::f8g_checks(fn, kind_mask, layout) : decode::kind_mask_check(fn, kind_mask, level);
+}
 static int decode_gate_up_impl(const char* fn, int level, const mxmoe_moe_glu* glu, int dtype, const void* hidden, int64_t T,
                                int topk, int E, int with_shared, const int32_t* topk_ids,
                                const mxmoe_moe_decode_expert* experts, uint32_t kind_mask, int H, int N, int N_shared,
                                int layout, void* act, void* act_shared, int32_t* status, void* stream) {
   if (int st = dtype_check(fn, "dtype", dtype)) return st;
-  if (int st = decode::kind_mask_check(fn, kind_mask, level)) return st;
+  if (int st = decode_mask_check(fn, level, kind_mask, layout)) return st;
   if (int st = decode::sizes_check(fn, T, topk, E, with_shared, H, N, N_shared)) return st;
   if (layout != MXMOE_DECODE_GU_PLAIN && layout != MXMOE_DECODE_GU_INTERLEAVED)
     return fail(MXMOE_GG_ERR_INVALID, "%s: layout must be MXMOE_DECODE_GU_PLAIN or MXMOE_DECODE_GU_INTERLEAVED (got %d)", fn,
@@ -1111,13 +1116,13 @@ static int decode_gate_up_impl(const char* fn, int level, const mxmoe_moe_glu* g
     a.c = -(glu->alpha * 1.4426950408889634f);
     a.limit = glu->limit;
   }
-  return decode::launch<false>(a, level, stream);
+  return level == decode::kF8g ? decode::launch_f8g<false>(a, stream) : decode::launch<false>(a, level, stream);
 }
 
 static int decode_down_impl(const char* fn, int level, int64_t T, int topk, int E, int with_shared, const int32_t* topk_ids,
                             const mxmoe_moe_decode_expert* experts, uint32_t kind_mask, int H, int N, int N_shared,
                             const void* act, const void* act_shared, void* y, void* ys, int32_t* status, void* stream) {
-  if (int st = decode::kind_mask_check(fn, kind_mask, level)) return st;
+  if (int st = decode_mask_check(fn, level, kind_mask, MXMOE_DECODE_GU_PLAIN)) return st;
   if (int st = decode::sizes_check(fn, T, topk, E, with_shared, H, N, N_shared)) return st;
   if (!aligned16(act) || !aligned16(act_shared) || !aligned16(y) || !aligned16(ys) || ((uintptr_t)topk_ids & 3) ||
       ((uintptr_t)experts & 7) || ((uintptr_t)status & 3))
@@ -1137,7 +1142,7 @@ static int decode_down_impl(const char* fn, int level, int64_t T, int topk, int 
   a.K = N, a.K_shared = with_shared ? N_shared : N;
   a.C = a.C_shared = H;
   a.kind_mask = kind_mask;
-  return decode::launch<true>(a, level, stream);
+  return level == decode::kF8g ? decode::launch_f8g<true>(a, stream) : decode::launch<true>(a, level, stream);
 }
 
 extern "C" {
@@ -1376,6 +1381,21 @@ int mxmoe_moe_decode_down_lp(int64_t T, int topk, int E, int with_shared, const 
                              const mxmoe_moe_decode_expert* experts, uint32_t kind_mask, int H, int N, int N_shared,
                              const void* act, const void* act_shared, void* y, void* ys, int32_t* status, void* stream) {
   return decode_down_impl("mxmoe_moe_decode_down_lp", decode::kLp, T, topk, E, with_shared, topk_ids, experts, kind_mask,
+                          H, N, N_shared, act, act_shared, y, ys, status, stream);
+}
+
+int mxmoe_moe_decode_gate_up_f8g(const mxmoe_moe_glu* glu, int dtype, const void* hidden, int64_t T, int topk, int E,
+                                 int with_shared, const int32_t* topk_ids, const mxmoe_moe_decode_expert* experts,
+                                 uint32_t kind_mask, int H, int N, int N_shared, int layout, void* act, void* act_shared,
+                                 int32_t* status, void* stream) {
+  return decode_gate_up_impl("mxmoe_moe_decode_gate_up_f8g", decode::kF8g, glu, dtype, hidden, T, topk, E, with_shared,
+                             topk_ids, experts, kind_mask, H, N, N_shared, layout, act, act_shared, status, stream);
+}
+
+int mxmoe_moe_decode_down_f8g(int64_t T, int topk, int E, int with_shared, const int32_t* topk_ids,
+                              const mxmoe_moe_decode_expert* experts, uint32_t kind_mask, int H, int N, int N_shared,
+                              const void* act, const void* act_shared, void* y, void* ys, int32_t* status, void* stream) {
+  return decode_down_impl("mxmoe_moe_decode_down_f8g", decode::kF8g, T, topk, E, with_shared, topk_ids, experts, kind_mask,
                           H, N, N_shared, act, act_shared, y, ys, status, stream);
 }
 

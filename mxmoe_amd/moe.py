@@ -1663,7 +1663,8 @@ class DecodeForwardLp(_DecodeBase):
     Which class takes which layer: ``DecodeForward`` fp16 / w8a8 / w4a4 experts with SiLU and no bias;
     ``DecodeForwardEx`` those plus w4a16_g32_sym_MXFP4, biases and ``SwigluClamp`` (gpt-oss); ``DecodeForwardWo`` all
     of that plus the eight integer weight-only types; ``DecodeForwardLp`` all of that plus the three types above.
-    Still refused, naming the qcfg: w2a16, group sizes other than -1 and 128, w4a4_g128 and bf16 experts.
+    Still refused, naming the qcfg: w2a16, group sizes other than -1 and 128 on integer codes, w4a4_g128, bf16 experts,
+    and w8a8_g128_sym_E4M3 (``DecodeForwardF8g`` takes layers made of that type alone).
 
     Device time against ``GraphForward`` (tools/decode_bench.py --scheme e4m3 / --model gpt-oss --act-bits 8): on
     qwen2_moe layer 11 with every expert E4M3 0.30x / 0.35x / 0.36x / 0.37x / 0.48x / 0.50x at T = 1 / 4 / 6 / 8 / 12 /
@@ -1694,6 +1695,52 @@ class DecodeForwardLp(_DecodeBase):
                                  f"aligned uint8 tensor of {want} bytes (the device scale layout)")
         else:
             DecodeForwardWo._check_scale(self, w, dev)
+
+
+class DecodeForwardF8g(_DecodeBase):
+    """The decode forward for block-scaled FP8 layers (DESIGN.md §4 "Decode forward: block-scaled FP8"): the same
+    constructor, ``launch`` and ``status`` on the _f8g entries (mxmoe_moe_decode_gate_up_f8g / mxmoe_moe_decode_down_f8g,
+    include/mxmoe_moe.h), for a layer whose experts are all ``w8a8_g128_sym_E4M3``, the shared expert included — what
+    ``prepare_weight`` or ``prepare_weight_e4m3_g128`` (a checkpoint's ``weight`` / ``weight_scale_inv``, byte for
+    byte) store: the codes and the f32 [K/128][ceil(rows/128)] block scales are read in place. A workgroup quantises its
+    batch of rows into LDS as the ``ACT_E4M3_G128`` pass does, bit for bit, multiplies every 128-wide K group with one
+    v_mfma_scale_f32_16x16x128_f8f6f4 and folds it into an f32 sum with the product of the two group scales — the
+    GroupGEMM's contract of the type; on 32-column tiles two wave pairs split K and add their sums through LDS, so
+    ``out`` is within the f32 summation order of ``MoEFFN.forward``'s. fp16 or bf16 ends, a ``MoEBlock``'s router, the
+    biases and ``SwigluClamp`` come with the base class.
+
+    Which class takes which layer: ``DecodeForward`` fp16 / w8a8 / w4a4 experts with SiLU and no bias;
+    ``DecodeForwardEx`` those plus w4a16_g32_sym_MXFP4, biases and ``SwigluClamp`` (gpt-oss); ``DecodeForwardWo`` all of
+    that plus the eight integer weight-only types; ``DecodeForwardLp`` all of that plus per-channel E4M3, MXFP8 and
+    MXFP4 activations; ``DecodeForwardF8g`` layers of w8a8_g128_sym_E4M3 alone. The type is not mixed with other kinds
+    in one decode launch: a layer that holds any other qcfg is refused here, naming it — run such a layer with
+    ``GraphForward``.
+
+    Device time against ``GraphForward`` (tools/decode_bench.py --scheme f8g128 / f8g128_ds): on qwen2_moe layer 11 with
+    every expert this type 0.31x / 0.32x / 0.36x / 0.40x / 0.49x / 0.52x at T = 1 / 4 / 6 / 8 / 12 / 16, no crossover;
+    within 4 % of ``DecodeForwardLp`` on the per-channel E4M3 layer of the same shapes. On a DeepSeek-V3-shaped layer
+    (H = 7168, N = 2048, top-8) 0.61x / 0.70x at T = 1 / 4 and 1.12x at T = 16, where only 7 rows of a batch fit in
+    LDS and gate_up streams most experts twice, and where ``out`` left the fp16 tolerance of the eager layer (every
+    stage within it of its own input): take ``GraphForward`` there."""
+
+    KINDS = {"w8a8_g128_sym_E4M3": nat.DECODE_W8A8_G128_E4M3}
+    ENTRIES = nat.DECODE_F8G_SYMBOLS
+    TAKES_GLU = True
+
+    def _check_layer(self, ffn: "MoEFFN") -> None:
+        for w in list(ffn.w1) + list(ffn.w2):
+            if w.q.qcfg not in self.KINDS:
+                raise ValueError(f"DecodeForwardF8g: qcfg {w.q.qcfg} is not supported: every expert, the shared one "
+                                 "included, must be w8a8_g128_sym_E4M3 (GraphForward runs mixed layers)")
+
+    def _check_scale(self, w: "ExpertWeights", dev) -> None:
+        """The kernel reads scale_b by K group and 128-row block: the buffer is checked like the weights."""
+        want = (w.K // 128) * ((w.N + 127) // 128)
+        sb = w.scale_b
+        if (sb is None or sb.device != dev or sb.dtype != torch.float32 or not sb.is_contiguous() or sb.data_ptr() % 4 or
+                sb.numel() != want):
+            raise ValueError(f"DecodeForwardF8g: the scale buffer of a {w.q.qcfg} weight [{w.N}, {w.K}] must be a "
+                             f"contiguous f32 tensor of {want} elements on the layer's device")
 
 
 def qwen2_layer_bench(*args, **kwargs) -> dict:

@@ -10,9 +10,9 @@ from typing import Optional, Sequence
 import torch
 
 from . import _native as nat
-from .groupgemm import W4A8_MXFP8, W4A16_MXFP4, W8A8_E4M3, QParams
+from .groupgemm import W4A8_MXFP8, W4A16_MXFP4, W8A8_E4M3, W8A8_G128_E4M3, QParams
 from .harness import time_launches
-from .moe import (_BITS, DecodeForward, DecodeForwardEx, DecodeForwardLp, DecodeForwardWo, GraphForward, MoEBlock, MoEFFN, PlannedForward, SwigluClamp, _launch_combine,
+from .moe import (_BITS, DecodeForward, DecodeForwardEx, DecodeForwardF8g, DecodeForwardLp, DecodeForwardWo, GraphForward, MoEBlock, MoEFFN, PlannedForward, SwigluClamp, _launch_combine,
                   _ptr, _stream, combine_into, gate, gptoss_layer, prepare_weight_mx, silu_mul_quant)
 from .workload import (ds2_mixed_qconfig, ds2_workload, load_workload, mixed_qconfig_lp1, qwen2_layer11_workload,
                        w4a16_w8a8_qconfig)
@@ -402,6 +402,34 @@ def decode_forward_e4m3_bench(batches: Sequence[int] = (1, 4, 16), rounds: int =
     for bs in batches:
         head = {"model": "qwen2_moe", "scheme": "e4m3", "bs": bs, "E": E, "topk": topk, "H": H, "N": N, "N_shared": Ns}
         yield _decode_bench(layer, DecodeForwardLp, _qwen2_decode_call(g, hist, bs, E, topk, H, dev), rounds, iters, head,
+                            "close_to_eager", weight_bytes)
+
+
+def decode_forward_f8g_bench(batches: Sequence[int] = (1, 4, 16), rounds: int = 4, iters: int = 30, deepseek: bool = False):
+    """qwen2_moe layer 11 with every expert w8a8_g128_sym_E4M3 (the shared one included; random weights, routing drawn
+    from the committed histogram) at decode sizes, ``DecodeForwardF8g`` against ``GraphForward`` of the same layer, as
+    ``decode_forward_e4m3_bench`` measures the per-channel layer (the same shapes, ids and hidden rows: the two runs
+    differ by the type alone). deepseek: a DeepSeek-V3-shaped layer instead — H = 7168, N = 2048, top-8, no shared
+    expert, E reduced from 256 to 16 (uniform routing) to bound the setup; the weight bytes of a call are those of
+    the experts its ids name, so a decode call streams what the full layer would. Weight bytes: codes and f32 block
+    scales. Sums depend on their order: compared with the eager layer within the fp16 GroupGEMM tolerance."""
+    dev, g = "cuda", torch.Generator().manual_seed(0)
+    qg = (W8A8_G128_E4M3, W8A8_G128_E4M3)
+    if deepseek:
+        topk, E, H, N, Ns = 8, 16, 7168, 2048, 0
+        mk = lambda n, k: ((torch.rand(n, k, generator=g) * 2 - 1) * 0.05).half().to(dev)
+        layer = MoEFFN([mk(2 * N, H) for _ in range(E)], [mk(H, N) for _ in range(E)], [qg] * E, num_routed=E)
+        hist = torch.ones(E, dtype=torch.float64)
+    else:
+        topk = 4
+        gate_up, down, _, hist, E, H, N, Ns = _qwen2_decode_layer(mixed_qconfig_lp1(), g, dev)
+        layer = MoEFFN(gate_up, down, [qg] * (E + 1), num_routed=E)
+        del gate_up, down
+    weight_bytes = lambda ws, es: sum(ws[e].B.numel() + 4 * ws[e].scale_b.numel() for e in es)
+    for bs in batches:
+        head = {"model": "deepseek-v3-shaped (E = 16 of 256)" if deepseek else "qwen2_moe", "scheme": "f8g128", "bs": bs, "E": E,
+                "topk": topk, "H": H, "N": N, "N_shared": Ns}
+        yield _decode_bench(layer, DecodeForwardF8g, _qwen2_decode_call(g, hist, bs, E, topk, H, dev), rounds, iters, head,
                             "close_to_eager", weight_bytes)
 
 

@@ -20,7 +20,11 @@ tolerance of the eager layer (weight-only sums depend on their order).
 and --model gpt-oss --act-bits 8: the gpt-oss layer with MXFP8 activations (w4a8_g32_sym_MXFP8): DecodeForwardLp (the
 MFMA decode kernels) against GraphForward of the same layer, compared within the fp16 tolerance.
 
-python tools/decode_bench.py [--model qwen2_moe|gpt-oss] [--scheme lp1|w4a16_w8a8|e4m3] [--act-bits 16|8] [--rounds 4]
+--model qwen2_moe --scheme f8g128: layer 11 with every expert w8a8_g128_sym_E4M3 (moe_bench.decode_forward_f8g_bench):
+DecodeForwardF8g against GraphForward of the same layer, on the rows --scheme e4m3 draws; --scheme f8g128_ds: a
+DeepSeek-V3-shaped layer of that type (H = 7168, N = 2048, top-8, E reduced to 16). Compared within the fp16 tolerance.
+
+python tools/decode_bench.py [--model qwen2_moe|gpt-oss] [--scheme lp1|w4a16_w8a8|e4m3|f8g128|f8g128_ds] [--act-bits 16|8] [--rounds 4]
                              [--iters 30] [--batches 1,4,16] [--out FILE]
 """
 from __future__ import annotations
@@ -42,7 +46,8 @@ def main():
     ap.add_argument("--batches", default="1,4,16")
     ap.add_argument("--out", default="")
     ap.add_argument("--model", default="qwen2_moe", choices=["qwen2_moe", "gpt-oss"])
-    ap.add_argument("--scheme", default="lp1", choices=["lp1", "w4a16_w8a8", "e4m3"], help="qwen2_moe: the layer's qconfig")
+    ap.add_argument("--scheme", default="lp1", choices=["lp1", "w4a16_w8a8", "e4m3", "f8g128", "f8g128_ds"],
+                    help="qwen2_moe: the layer's qconfig")
     ap.add_argument("--act-bits", type=int, default=16, choices=[16, 8], help="gpt-oss: fp16 or MXFP8 activations")
     args = ap.parse_args()
     if args.model == "gpt-oss" and args.scheme != "lp1":
@@ -54,7 +59,8 @@ def main():
     kw = {"act_bits": args.act_bits} if args.model == "gpt-oss" else {}
     bench = moe_bench.decode_forward_gptoss_bench if args.model == "gpt-oss" else \
         {"lp1": moe_bench.decode_forward_bench, "w4a16_w8a8": moe_bench.decode_forward_wo_bench,
-         "e4m3": moe_bench.decode_forward_e4m3_bench}[args.scheme]
+         "e4m3": moe_bench.decode_forward_e4m3_bench, "f8g128": moe_bench.decode_forward_f8g_bench,
+         "f8g128_ds": lambda *a: moe_bench.decode_forward_f8g_bench(*a, deepseek=True)}[args.scheme]
     for r in bench([int(b) for b in args.batches.split(",") if b], args.rounds, args.iters, **kw):
         print(json.dumps(r), flush=True)
         results.append(r)
