@@ -19,7 +19,9 @@
  *          [K/128][ceil(N/128)] — a K stage's scales are contiguous; both 4-byte aligned. K % 128 == 0; the last
  *          scale block along N may be partial. With out = 0, for g = 0 .. K/128 - 1 in order:
  *          out = fmaf(acc_g, f32_rn(sa[g][m] * sb[g][n / 128]), out), acc_g the f32 sum of the group's 128
- *          products (sum order unspecified); C = fp16_rn(out). Never split along K. Large-batch kernel (v2x) only.
+ *          products (sum order unspecified); C = fp16_rn(out). Never split along K. Large-batch kernel (v2x), and in a call
+ *          of the type alone the small-batch kernel wo3 (64 x 128 tiles; AUTO: mean M <= 80, doubled for K-skewed
+ *          calls); the two bodies give identical bits.
  *   bf16 (fmt MXMOE_GG_FMT_BF16): A,B bf16, fp32 accumulate, C = fp16_rn(acc) (C is fp16 for every
  *          type, as the reference's `half** ptr_Cs`)
  *   w4a4_g32_sym_MXFP4 (fmt MXMOE_GG_FMT_MXFP4): A,B OCP MXFP4 (e2m1 codes, e8m0 scale per 32-K block),

@@ -47,10 +47,7 @@ namespace {
     if (e_ != hipSuccess) return fail(MXMOE_GG_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
   } while (0)
 
-// the small-batch weight-only tile's loop options (gg_tile_wo)
-constexpr int kWo3 = WO_SCLATE | WO_ANDOR | WO_MSKIP | WO_SPLIT | WO_NIBPOS;
-// (the v2x flags kV2x / kV2xProduct: gg_builds.h)
-[[maybe_unused]] constexpr int kWo3Product = kWo3 | WO_PCH;
+// (the v2x flags kV2x / kV2xProduct and the small-batch kernel's kWo3 / kWo3Product: gg_builds.h)
 
 // One compiled kernel of a variant's family: the tile bodies of the quant types in `qmask`.
 struct Build {
@@ -247,12 +244,23 @@ constexpr Builds<sizeof...(QM)> wo2_rows(bool fallback = false) {
 // (same plan: placement only assumes more slots). WO_SILU builds: only the w4a16, w4a16 + w8a8 and weight-only
 // MXFP4 sets at the variant's NWG; w4a8_g32_sym_MXFP8 beside flagged problems always takes the widest.
 // (fast lab build: the w4a16, w4a16 + w8a8 and w8a16 sets only, all at the variant's NWG)
+// w8a8_g128_sym_E4M3 has one build, for calls of the type alone (gg_f8g128_small.hip, the product variant's flags and
+// NWG only): beside any other type the family has no kernel for it (pick_wo2: -1; AUTO keeps such calls on v2x).
+template <int ABL, int NWG>
+constexpr auto wo2_f8g_row() {
+#ifdef MXMOE_LAB
+  return Builds<0>{};
+#else
+  static_assert(ABL == kWo3Product && NWG == 3, "gg_f8g128_small.hip compiles the product variant's build only");
+  return Builds<1>{{Build{kF8G, false, wo2_lds_bytes<NWG>(), &launch_wo3_f8g}}};
+#endif
+}
 template <int ABL, int NWG>
 constexpr auto kWo2Builds =
 #ifdef MXMOE_LAB_FAST
     wo2_rows<ABL, NWG, false, 8, 10, 16>();
 #else
-    wo2_rows<ABL, NWG, false, 8, 64, 10, 1, 2, 4, 6, kMxW, kMx8>() + wo2_rows<ABL, 2, false, 16>() +
+    wo2_rows<ABL, NWG, false, 8, 64, 10, 1, 2, 4, 6, kMxW, kMx8>() + wo2_f8g_row<ABL, NWG>() + wo2_rows<ABL, 2, false, 16>() +
     wo2_rows<ABL, 2, false, 95, 95 | kMxW, 95 | kMxW | kMx8>(true) +
     wo2_rows<ABL, NWG, true, 8, 10, kMxW>() + wo2_rows<ABL, 2, true, 16>() +
     wo2_rows<ABL, 2, true, 95, 95 | kMxW, 95 | kMxW | kMx8>(true);
@@ -262,7 +270,9 @@ constexpr int pick_wo2(int qmask) {
 #ifdef MXMOE_LAB_FAST
   return pick_build(table_of(kWo2Builds<ABL, NWG>), qmask & 511);
 #else
-  return pick_build(table_of(kWo2Builds<ABL, NWG>), qmask & (511 | kMxW | kMx8 | kQmaskWoSilu));  // (the type bits wo2 looks at)
+  constexpr int bits = 511 | kMxW | kMx8 | kF8G | kQmaskWoSilu;  // (the type bits wo2 looks at)
+  if ((qmask & kF8G) && (qmask & bits) != kF8G) return -1;      // the block-scaled type: alone or not at all
+  return pick_build(table_of(kWo2Builds<ABL, NWG>), qmask & bits);
 #endif
 }
 #ifndef MXMOE_LAB_FAST
@@ -278,6 +288,10 @@ static_assert(wo3_picks(kMxW | (1 << QT_I8), 95 | kMxW, 2) && wo3_picks(kMx8 | k
 static_assert(wo3_picks(kS | kW4, kS | 8, 3) && wo3_picks(kS | (1 << QT_W2A16), kS | 95, 2));
 static_assert(wo3_picks(kS | kMxW | kW4, kS | 95 | kMxW, 2) && wo3_picks(kS | kMx8 | kW4, kS | 95 | kMxW | kMx8, 2));
 static_assert(wo3_picks(kS | kMx8 | kMxW, kS | 95 | kMxW | kMx8, 2));
+#ifndef MXMOE_LAB
+static_assert(wo3_picks(kF8G, kF8G, 3) && kWo2Builds<kWo3Product, 3>[pick_wo2<kWo3Product, 3>(kF8G)].launch == &launch_wo3_f8g);
+static_assert(pick_wo2<kWo3Product, 3>(kF8G | (1 << QT_F16)) < 0 && pick_wo2<kWo3Product, 3>(kF8G | kW4 | kS) < 0);
+#endif
 #endif
 template <int ABL = 0, int NWG = 2>
 Variant make_wo2(const char* name) {

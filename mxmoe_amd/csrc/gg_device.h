@@ -2145,6 +2145,143 @@ __device__ __forceinline__ void gg_tile_f8g128(const GGMeta& mt, const uint8_t* 
   }
 }
 
+// ============================================================================================
+// w8a8_g128_sym_E4M3 on the small-batch kernel (gg_wo2_kernel, three workgroups per CU): the 64 x 128
+// tile of V2Cfg<64, 128, 4, 2> — 4 x 2 waves, one 16 x 64 wave tile each (FM = 1, FN = 4). The
+// arithmetic is gg_tile_f8g128's, instruction for instruction (one K = 128 MFMA per group and 16 x 16
+// block on a zero C operand, chunks g / g + 4, the same fold expression in group order), so the two
+// bodies agree bit for bit on any operands.
+//   * LDS: two 24-KiB stages (A 8 KiB | B 16 KiB, one group each), then two 512-B scale slots
+//     [sa 64 f32 | sb replicated]: 50176 B of the 52-KiB image. The epilogue stages its 16 KiB in stage 0.
+//   * BN = 128 and n0 a multiple of 128: the tile's columns are ONE scale block, so sb is one value per
+//     stage for the whole workgroup and sa 64 contiguous f32 (SA + s * M + m0, rows clamped past M).
+//     Both ride the stage as 4-byte LDS-DMA pieces (wave 0: sa, wave 1: sb from one address in every
+//     lane), issued with the stage's A / B pieces: the barrier's wait that publishes the stage covers
+//     them, no register holds a scale across the loop and nothing waits on memory inside it.
+//   * FM = 1 leaves no fragment row to pipeline the fold against: the four column fragments alternate
+//     between two group accumulators, fragment j's fold beside fragment j + 1's MFMA.
+//   * A wave whose 16-row block lies past M (small experts: most of them) issues its DMA pieces and
+//     reaches every barrier, but reads no fragment, runs no MFMA or fold and has no epilogue.
+// ============================================================================================
+template <class Cfg>
+__device__ __forceinline__ void gg_tile_f8g128s(const GGMeta& mt, const uint8_t* __restrict__ A,
+                                                const uint8_t* __restrict__ B, const float* __restrict__ SA,
+                                                const float* __restrict__ SB, _Float16* __restrict__ C, int m0, int n0,
+                                                uint8_t* lds) {
+  constexpr int FN = Cfg::FN;
+  static_assert(Cfg::BM == 64 && Cfg::BN == 128 && Cfg::FM == 1 && Cfg::GA == 1 && Cfg::GB == 2 && Cfg::WM * Cfg::WN == 8,
+                "one 16-row block per wave, one scale block per tile, one sa piece of 64 lanes");
+  constexpr int SCL = 2 * Cfg::STAGE_BYTES, SCL_BYTES = 512;  // LDS scale slots: [buf][sa 64 | sb 64] f32
+  static_assert(Cfg::EPI_BYTES <= Cfg::STAGE_BYTES, "the epilogue staging sits in the drained ring");
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int wm = wave / Cfg::WN, wn = wave % Cfg::WN;
+  const int r16 = lane & 15, g = lane >> 4;
+  const int M = mt.M, N = mt.N, ngroups = mt.reserved;  // one 128-B stage per group
+  const int NB = (N + 127) >> 7;                        // scale blocks along N
+  const int64_t lda = mt.lda_b, ldb = mt.ldb_b;
+  const bool live = m0 + wm * Cfg::WTM < M;  // wave-uniform: the wave's row block holds a row of the problem
+
+  auto rsrc = [](const void* base) {
+    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), (short)0, 0x7fffffff, 0x00020000);
+  };
+  const __amdgpu_buffer_rsrc_t rsA = rsrc(A + (int64_t)m0 * lda), rsB = rsrc(B + (int64_t)n0 * ldb);
+  uint32_t va, vb[2];
+  {
+    const int rsub = lane >> 3, p = lane & 7;
+    const int row = wave * 8 + rsub;
+    va = (uint32_t)(min(row, M - 1 - m0) * (int)lda) + ((p ^ ((row >> 1) & 7)) << 4);
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      const int brow = (wave * 2 + j) * 8 + rsub;
+      vb[j] = (uint32_t)(min(brow, N - 1 - n0) * (int)ldb) + ((p ^ ((brow >> 1) & 7)) << 4);
+    }
+  }
+  // the scale piece of waves 0 / 1: lane l fetches sa of tile row l (clamped) / every lane the tile's sb
+  const uint32_t vs = wave == 0 ? (uint32_t)min(lane, M - 1 - m0) * 4u : 0u;
+  const float* const sbase = wave == 0 ? SA + m0 : SB + (n0 >> 7);
+  const int sstride = wave == 0 ? M : NB;
+  auto issue = [&](int s, int buf) {
+    uint8_t* As = lds + buf * Cfg::STAGE_BYTES;
+    uint8_t* Bs = As + Cfg::A_BYTES;
+    const int kb = s * Cfg::BKB;
+    bdma16(rsA, As + wave * 1024, va, kb);
+#pragma unroll
+    for (int j = 0; j < 2; ++j) bdma16(rsB, Bs + (wave * 2 + j) * 1024, vb[j], kb);
+    if (wave < 2) bdma4(rsrc(sbase + (int64_t)s * sstride), lds + SCL + buf * SCL_BYTES + wave * 256, vs, 0);
+  };
+
+  v4f out[FN];
+#pragma unroll
+  for (int j = 0; j < FN; ++j) out[j] = v4f{0, 0, 0, 0};
+
+  const int swz = (r16 >> 1) & 7;
+  const uint32_t a_row = (uint32_t)(wm * Cfg::WTM + r16) * 128u;
+  const uint32_t b_row = (uint32_t)(wn * Cfg::WTN + r16) * 128u;
+  const uint32_t off0 = (uint32_t)((g ^ swz) << 4), off1 = (uint32_t)(((4 + g) ^ swz) << 4);
+  // (the fold: gg_tile_f8g128's — the compiler's own fma on the MFMA result, kept scalar by the empty asm)
+  auto fold = [&](int j, const v4f& acc, float s) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      float d = __builtin_fmaf(acc[e], s, out[j][e]);
+      asm("" : "+v"(d));
+      out[j][e] = d;
+    }
+  };
+  auto compute = [&](int buf) {
+    const uint8_t* As = lds + buf * Cfg::STAGE_BYTES + a_row;
+    const uint8_t* Bs = lds + buf * Cfg::STAGE_BYTES + Cfg::A_BYTES + b_row;
+    const float* sl = reinterpret_cast<const float*>(lds + SCL + buf * SCL_BYTES);
+    const v8i a = cat_v4i(*reinterpret_cast<const v4i*>(As + off0), *reinterpret_cast<const v4i*>(As + off1));
+    v8i b[FN];
+#pragma unroll
+    for (int j = 0; j < FN; ++j)
+      b[j] = cat_v4i(*reinterpret_cast<const v4i*>(Bs + j * 2048 + off0), *reinterpret_cast<const v4i*>(Bs + j * 2048 + off1));
+    const float s = sl[wm * Cfg::WTM + r16] * sl[64];  // f32_rn(sa * sb)
+    v4f acc0, acc1;
+#pragma unroll
+    for (int j = 0; j < FN; ++j) {
+      v4f& acc = (j & 1) ? acc1 : acc0;
+      acc = mfma_f8_k128(b[j], a, v4f{0, 0, 0, 0});
+      if (j > 0) fold(j - 1, (j & 1) ? acc0 : acc1, s);
+    }
+    fold(FN - 1, ((FN - 1) & 1) ? acc1 : acc0, s);
+  };
+
+  if (ngroups > 0) {
+    issue(0, 0);
+    __syncthreads();  // stage 0 and its scales landed
+    for (int s = 0; s < ngroups; ++s) {
+      if (s + 1 < ngroups) issue(s + 1, (s + 1) & 1);  // into the buffer stage s-1 was read from (before the last barrier)
+      if (live) compute(s & 1);
+      __syncthreads();  // every wave's pieces of stage s+1 landed; stage s read
+    }
+  }
+  if (!live) return;  // (no barrier below)
+
+  // ---- epilogue (as gg_tile_f8g128): fp16, per-wave LDS staging in the drained ring, 16-B stores ----
+  int etid = threadIdx.x;
+  asm volatile("" : "+v"(etid));
+  const int elane = etid & 63, er16 = elane & 15, eg = elane >> 4;
+  uint8_t* reg = lds + wave * (Cfg::WTM * Cfg::WTN * 2);
+  const int mrow0 = m0 + wm * Cfg::WTM, ncol0 = n0 + wn * Cfg::WTN;
+#pragma unroll
+  for (int j = 0; j < FN; ++j) {
+    const uint2 pk = pack4_f16(out[j]);
+    const int q = 2 * j + (eg >> 1);
+    *reinterpret_cast<uint2*>(reg + er16 * 128 + ((q ^ (er16 & 7)) << 4) + (eg & 1) * 8) = pk;
+  }
+  _Float16* const cbase = C + (int64_t)mrow0 * mt.ldc + ncol0;  // wave-uniform
+  const bool narrow = (int64_t)Cfg::WTM * mt.ldc < (int64_t)1 << 29;  // byte offsets < 2^30
+#pragma unroll
+  for (int it = 0; it < Cfg::WTM / 8; ++it) {
+    const int row = it * 8 + (elane >> 3), q = elane & 7;
+    const uint4 v = *reinterpret_cast<const uint4*>(reg + row * 128 + ((q ^ (row & 7)) << 4));
+    const int m = mrow0 + row, n = ncol0 + q * 8;
+    if (m < M && n < N) store_c16(cbase, (int64_t)row * mt.ldc + q * 8, narrow, v);
+  }
+}
+
 // v2 fused kernel: qtype x height-class dispatch, uniform per workgroup.
 
 
@@ -3444,6 +3581,11 @@ __global__ __launch_bounds__(512, 2 * NWG) void gg_wo2_kernel(GGArgs args) {
     // w4a8_g32_sym_MXFP8 on the 64 x 128 tile: ring of three 16-KiB K = 128 stages (48 KiB)
     const _Float16* SA = static_cast<const _Float16*>(args.ptr_SA[td.prob]);
     gg_tile_v2<V2Cfg<64, 128, 4, 2>, QT_MXF8A, V2_B3>(mt, A, B, SA, SB, C, td.m0, td.n0, lds, sk);
+  } else if ((QM & (1 << QT_F8G)) && mt.qtype == QT_F8G) {
+    // w8a8_g128_sym_E4M3 on the 64 x 128 tile: two 24-KiB K = 128 stages + the scale slots (49.5 KiB); never split
+    static_assert(2 * V2Cfg<64, 128, 4, 2>::STAGE_BYTES + 2 * 512 <= WO2_LDS_BYTES, "stages and scale slots fit the image");
+    gg_tile_f8g128s<V2Cfg<64, 128, 4, 2>>(mt, A, B, static_cast<const float*>(args.ptr_SA[td.prob]),
+                                          reinterpret_cast<const float*>(SB), C, td.m0, td.n0, lds);
   }
   if constexpr ((ABL & V2_TRACE) != 0) {  // (as gg_v2_kernel; the class field holds the problem index)
     if (threadIdx.x == 0 && blockIdx.x < kTraceBlocks) {

@@ -214,6 +214,18 @@ int build_meta(const HostProblem& p, int idx, const PlanVariant& v, bool check_p
   return MXMOE_GG_OK;
 }
 
+int check_alone(const PlanVariant& v, const GGMeta* rows, const int* idx, int count) {
+  int mask = 0;
+  for (int i = 0; i < count; ++i) mask |= 1 << rows[i].qtype;
+  if (!(mask & v.alone_mask) || (mask & (mask - 1)) == 0) return MXMOE_GG_OK;
+  for (int i = 0; i < count; ++i)
+    if (v.alone_mask & (1 << rows[i].qtype))
+      return fail(MXMOE_GG_ERR_UNSUPPORTED,
+                  "problem %d: variant %s does not implement %s (quant type not supported) beside other quant types: "
+                  "only in a call of its own", idx[i], v.name, qinfo(rows[i].qtype).name);
+  return MXMOE_GG_OK;
+}
+
 namespace {
 // The planner's A/B switches: defaults are what the product plans with. Only the tools-only lab build
 // (-DMXMOE_LAB, libmxmoe_gg_lab.so) reads them from the environment (MXMOE_GG_<NAME>), once per plan: the
@@ -891,6 +903,11 @@ int plan_host(const std::vector<HostProblem>& probs, int variant, bool check_ptr
   std::vector<int> order;
   for (int i = 0; i < P; ++i)
     if (probs[i].M > 0 && probs[i].N > 0) order.push_back(i);
+  if (v.alone_mask) {
+    std::vector<GGMeta> rows;
+    for (int i : order) rows.push_back(all[i]);
+    if (int st = check_alone(v, rows.data(), order.data(), (int)rows.size())) return st;
+  }
   const std::vector<int> split = split_factors(v, all, order, o);
   std::vector<double> tile_cost(P, 0.0);
   for (int i : order) tile_cost[i] = stage_time(v, all[i], m_tiles(v, all[i])[0].second) * stages_of(v, all[i]) / split[i];
@@ -950,7 +967,9 @@ int resolve_variant(int variant, const std::vector<HostProblem>& hp, int* out) {
   // only variant with that body; w4a8_g32_sym_MXFP8 has a wo3 body)
   constexpr int wo_mask = auto_mask(AutoClass::WeightOnly), small_mask = wo_mask | auto_mask(AutoClass::Small);
   // (fused SiLU calls too: the small-batch kernel's fp16 / w8a8 / w4a4 bodies carry the epilogue)
-  if (mask != 0 && (mask & ~small_mask) == 0) {
+  // a SmallAlone type is Small exactly when it is the call's only type
+  const bool small_alone = (mask & auto_mask(AutoClass::SmallAlone)) == mask && (mask & (mask - 1)) == 0;
+  if (mask != 0 && ((mask & ~small_mask) == 0 || small_alone)) {
     // (w8a8 / fp16 problems may ride along: the reference's small-batch w4a16 + w8a8 pairing)
     double wsum = 0, ksum = 0, msum = 0;
     int kmax = 0;
@@ -1130,6 +1149,11 @@ int plan_dynamic_host(const mxmoe_gg_problem* problems, int P, int variant, cons
     if (t.weight_only && (m.reserved2 & META_SILU)) out->qtype_mask |= kQmaskWoSilu;
     m.M = 0;  // the device planner's columns
     m.tile_begin = 0;
+  }
+  if (v.alone_mask) {
+    std::vector<int> idx(P);
+    for (int i = 0; i < P; ++i) idx[i] = i;
+    if ((st = check_alone(v, out->meta.data(), idx.data(), P))) return st;
   }
   if (P > 0 && v.pick(out->qtype_mask) < 0)
     return fail(MXMOE_GG_ERR_UNSUPPORTED, "variant %s: quant-type mix %#x not compiled", v.name, out->qtype_mask);

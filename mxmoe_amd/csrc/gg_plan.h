@@ -44,6 +44,9 @@ constexpr double kSmallMeanRows = 80.0;
 constexpr double kSmallMeanRowsI4 = 112.0;
 // calls with a w4a8_g32_sym_MXFP8 problem (and no weight-only one): the int4 cut
 constexpr double kSmallMeanRowsMx8 = 112.0;
+// calls of w8a8_g128_sym_E4M3 problems alone: the w8a8 cut (DESIGN.md §4 "Block-scaled FP8 on the small-batch
+// kernel"; it must stay below 111.75, the mean M tests/test_f8g128_gpu.py pins to the default variant)
+constexpr double kSmallMeanRowsF8G = kSmallMeanRows;
 constexpr double kSplitCUs = 256.0;  // MI355X compute units: the planner's notion of "one CU's share"
 
 // What AUTO does with a call that has a problem of the type (resolve_variant):
@@ -51,8 +54,10 @@ constexpr double kSplitCUs = 256.0;  // MI355X compute units: the planner's noti
 //   WeightOnly the small-batch kernel (kWoSmallVariant) up to a mean M of auto_rows, v2x beyond;
 //   Small      may ride on the small-batch kernel: a call of Small types only takes it up to the
 //              largest auto_rows among them (x 2 when K-skewed), beside a weight-only problem up to that one's;
+//   SmallAlone as Small, but only in a call of this type alone (the small-batch kernel has no build that holds
+//              the type beside another): any other type present, the call is General;
 //   Alone      cannot share a call: a kernel of its own (auto_alone).
-enum class AutoClass { General, WeightOnly, Small, Alone };
+enum class AutoClass { General, WeightOnly, Small, SmallAlone, Alone };
 
 // Everything the host knows about a quant type, one row per QType.
 struct QTypeInfo {
@@ -112,7 +117,9 @@ constexpr QTypeInfo kQTypes[] = {
     {QT_MXF8A, "w4a8_g32_sym_MXFP8", 8, false, false, "w4a8_g32_sym_MXFP8", 32, "w4a8_g32_sym_MXFP8", true, false,
      false, true, false, 1.0, 8, 256, 1.0, 0, kSm, kSmallMeanRowsMx8, nullptr, false},
     {QT_F8G, "w8a8_g128_sym_E4M3", 8, false, false, "w8a8_g128_sym_E4M3", 128, "w8a8_g128_sym_E4M3", false, true, false,
-     false, false, 1.0, 8, 256, 1.1, 0, kGen, 0, nullptr, true},  // fold: 1.06-1.09x per-channel E4M3's time (profiles/r23/f8g128)
+     false, false, 1.0, 8, 256, 1.1, 0, AutoClass::SmallAlone, kSmallMeanRowsF8G, nullptr, true},
+    // (fold: 1.06-1.09x per-channel E4M3's time, profiles/r23/f8g128; no 64-row class in gg_v2_kernel — the small-batch
+    // kernel's 64 x 128 tile is its main tile, not a class)
 };
 constexpr bool qtypes_in_order() {
   for (int i = 0; i < QT_COUNT; ++i)
@@ -149,6 +156,7 @@ struct PlanVariant {
   bool silu_wo = false;     // ... and its weight-only tiles (wo2: the WO_SILU builds)
   int persist_len = 0;      // v2q: 0 = one list per CU (static); L > 0 = lists of L consecutive XCD-queue
                             // tiles, one per block, the hardware dispatching blocks as CUs free up
+  int alone_mask = 0;       // 1 << QType of the types whose only build is for a call of that type alone
   int (*pick)(int qmask);   // index among the variant's builds of the one a plan's quant-type set (1 << QType
                             // present, kQmaskWoSilu) launches: the launch and the plan info's LDS size both use it
 };
@@ -211,6 +219,8 @@ inline PlanVariant plan_wo2(int nwg, bool mx, bool silu_wo) {
   if (mx) {
     v.geom[QT_MXF4W] = {64, 256, 32, 512};   // weight-only MXFP4: the 4-bit stage
     v.geom[QT_MXF8A] = {64, 128, 128, 512};  // w4a8_g32_sym_MXFP8: 64 x 128 tiles (128-K stages)
+    v.geom[QT_F8G] = {64, 128, 128, 512};    // w8a8_g128_sym_E4M3 (gg_tile_f8g128s): one 128-K group per stage,
+    v.alone_mask = 1 << QT_F8G;              // in a call of the type alone
   }
   v.chunk = 32 * nwg;  // nwg workgroups per CU, 32 CUs per XCD
   v.tail_bm = v.tail2_bm = 0;
@@ -268,6 +278,8 @@ int qtype_of(int a_bits, int w_bits, int gsize, int sym, int fmt, int* qt);
 std::vector<HostProblem> to_host(const mxmoe_gg_problem* problems, int problem_count);
 // Validate one problem and fill its table row.
 int build_meta(const HostProblem& p, int idx, const PlanVariant& v, bool check_ptrs, GGMeta* m);
+// A call's non-empty problems (their table rows, `idx` their indices in the call) against PlanVariant::alone_mask.
+int check_alone(const PlanVariant& v, const GGMeta* rows, const int* idx, int count);
 // MXMOE_GG_VARIANT_AUTO -> concrete variant from the quant types present.
 int resolve_variant(int variant, const std::vector<HostProblem>& hp, int* out);
 // Tile generation + scheduling (a problem that fails validation leaves `plan` as it was).

@@ -6,9 +6,11 @@ per-step device times, the variants AUTO chose, and the two E4M3 activation pass
 
 python tools/fp8_layer_bench.py [--rounds 4] [--iters 30] [--batches 128,512,2048,8192] [--out FILE]
 
---gemm: instead, the layer's gate_up and down GroupGEMM calls at the first batch size with every problem block-scaled
-(w8a8_g128_sym_E4M3) against per-channel (w8a8_g-1_sym_E4M3): same process, the sides alternating over rounds; per
-call and side the median of the rounds' medians with min / max (ms), TOP/s, and the block-scaled / per-channel ratio.
+--gemm: instead, the layer's gate_up and down GroupGEMM calls at every batch size with every problem block-scaled
+(w8a8_g128_sym_E4M3), forced onto the small-batch kernel (wo3) and onto v2x, beside per-channel E4M3 and w8a8 under
+AUTO: same process, the sides alternating over rounds; per call and side the median of the rounds' medians with
+min / max (ms), TOP/s, the wo3 / v2x time ratio and the variant AUTO takes for the block-scaled call.
+--gemm --ds: the same on a DeepSeek-V3-shaped call (H = 7168, N = 2048, top-8 over 16 experts), --batches in tokens.
 """
 from __future__ import annotations
 
@@ -22,28 +24,48 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from mxmoe_amd import moe_bench  # noqa: E402
 
 
-def gemm_bench(bs: int, rounds: int, iters: int):
+GEMM_SIDES = (  # label, qstr, variant name (None: AUTO)
+    ("f8g128@wo3", "w8a8_g128_sym_E4M3", "wo3_64x256_w8_3wg"),
+    ("f8g128@v2x", "w8a8_g128_sym_E4M3", "v2x_256x256_w8_b3_buf_spread_edma"),
+    ("e4m3@auto", "w8a8_g-1_sym_E4M3", None),
+    ("w8a8@auto", "w8a8_g-1_sym", None),
+)
+
+
+def gemm_bench(batches, rounds: int, iters: int, deepseek: bool):
     import statistics
 
+    from mxmoe_amd import _native as nat
     from mxmoe_amd.groupgemm import GroupGemm
     from mxmoe_amd.harness import build_layer_inputs, time_launches
-    from mxmoe_amd.workload import layer_problems, qwen2_layer11_workload
+    from mxmoe_amd.workload import QShape, layer_problems, parse_qstr, qwen2_layer11_workload
 
-    sides = ("w8a8_g128_sym_E4M3", "w8a8_g-1_sym_E4M3")
-    for call in ("gate_up", "down"):
-        inputs = {q: build_layer_inputs(layer_problems(qwen2_layer11_workload(bs, qstr=q))[call]) for q in sides}
-        plans = {q: GroupGemm(inputs[q].problems) for q in sides}
-        ms = {q: [] for q in sides}
-        for _ in range(rounds):
-            for q in sides:
-                ms[q].append(time_launches(plans[q].launch, warmup=5, iters=iters)["median_ms"])
-        r = {"model": "qwen2_moe", "bs": bs, "call": call, "rounds": rounds, "iters": iters}
-        for q in sides:
-            med = statistics.median(ms[q])
-            r[q] = {"median_ms": round(med, 5), "min_ms": round(min(ms[q]), 5), "max_ms": round(max(ms[q]), 5),
-                    "tops": round(inputs[q].flops / (med * 1e-3) / 1e12, 1), "variant": plans[q].variant}
-        r["time_ratio"] = round(r[sides[0]]["median_ms"] / r[sides[1]]["median_ms"], 4)
-        yield r
+    names = [ln.split()[1] for ln in nat.list_variants()]
+
+    def shapes(bs, q, call):
+        if not deepseek:
+            return layer_problems(qwen2_layer11_workload(bs, qstr=q))[call]
+        E, topk, H, N = 16, 8, 7168, 2048  # tools/decode_bench.py --scheme f8g128_ds; tokens spread evenly
+        rows = [bs * topk // E + (e < bs * topk % E) for e in range(E)]
+        n, k = (2 * N, H) if call == "gate_up" else (H, N)
+        return [QShape(shape=[m, n, k], **parse_qstr(q)) for m in rows if m > 0]
+
+    for bs in batches:
+        for call in ("gate_up", "down"):
+            inputs = {lb: build_layer_inputs(shapes(bs, q, call)) for lb, q, _ in GEMM_SIDES}
+            plans = {lb: GroupGemm(inputs[lb].problems, variant=None if v is None else names.index(v)) for lb, _, v in GEMM_SIDES}
+            ms = {lb: [] for lb in plans}
+            for _ in range(rounds):
+                for lb in plans:
+                    ms[lb].append(time_launches(plans[lb].launch, warmup=5, iters=iters)["median_ms"])
+            r = {"model": "deepseek_v3_e16" if deepseek else "qwen2_moe", "bs": bs, "call": call, "rounds": rounds, "iters": iters,
+                 "auto": names[GroupGemm(inputs["f8g128@wo3"].problems).variant]}  # what AUTO takes for the block-scaled call
+            for lb in plans:
+                med = statistics.median(ms[lb])
+                r[lb] = {"median_ms": round(med, 5), "min_ms": round(min(ms[lb]), 5), "max_ms": round(max(ms[lb]), 5),
+                         "tops": round(inputs[lb].flops / (med * 1e-3) / 1e12, 1), "variant": names[plans[lb].variant]}
+            r["wo3_over_v2x"] = round(r["f8g128@wo3"]["median_ms"] / r["f8g128@v2x"]["median_ms"], 4)
+            yield r
 
 
 def main():
@@ -53,10 +75,11 @@ def main():
     ap.add_argument("--batches", default="128,512,2048,8192")
     ap.add_argument("--out", default="")
     ap.add_argument("--gemm", action="store_true")
+    ap.add_argument("--ds", action="store_true", help="--gemm: the DeepSeek-V3-shaped call")
     args = ap.parse_args()
     results = []
     batches = [int(b) for b in args.batches.split(",") if b]
-    for r in (gemm_bench(batches[0], args.rounds, args.iters) if args.gemm else
+    for r in (gemm_bench(batches, args.rounds, args.iters, args.ds) if args.gemm else
               moe_bench.fp8_layer_bench(batches, args.rounds, args.iters)):
         print(json.dumps(r), flush=True)
         results.append(r)
