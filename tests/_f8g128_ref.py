@@ -78,11 +78,69 @@ def gemm(a_codes, sa, b_codes, sb) -> np.ndarray:
     return sum(p * sa[:, g].astype(np.float64)[:, None] * sbn[:, g][None, :] for g, p in enumerate(_group_sums(a_codes, b_codes)))
 
 
+def fma32(a: np.ndarray, b: np.ndarray, c: np.ndarray) -> np.ndarray:
+    """fmaf on f32 arrays, one rounding. The product of two f32 is exact in f64; the f64 sum with c is rounded to odd
+    (the error of the sum from TwoSum; an inexact sum whose last bit is even moves to its odd neighbour on the side of
+    the error), and a value rounded to odd at 53 bits rounds to 24 bits as the exact one does. NaN and Inf pass through
+    (0 * Inf is NaN, as in the instruction)."""
+    with np.errstate(invalid="ignore", over="ignore"):
+        p = np.asarray(a, np.float32).astype(np.float64) * np.asarray(b, np.float32).astype(np.float64)
+        c = np.asarray(c, np.float32).astype(np.float64)
+        p, c = np.broadcast_arrays(p, c)
+        s = p + c
+        bb = s - p
+        err = (p - (s - bb)) + (c - bb)
+        fix = np.isfinite(s) & (err != 0) & ((s.view(np.int64) & 1) == 0)
+        s = np.where(fix, np.nextafter(s, np.where(err > 0, np.inf, -np.inf)), s)
+        return s.astype(np.float32)
+
+
+def scale_products(sa, sb, rows):
+    """f32_rn(sa[m][g] * sb[n / 128][g]) per group: [G] arrays of [M, N]."""
+    sbn = np.repeat(np.asarray(sb, np.float32), G, axis=0)[:rows]
+    with np.errstate(invalid="ignore", over="ignore"):
+        return [np.asarray(sa, np.float32)[:, g][:, None] * sbn[:, g][None, :] for g in range(sa.shape[1])]
+
+
+def fold_f32(accs, scales, order=None) -> np.ndarray:
+    """out = 0; out = fmaf(f32(acc_g), s_g, out) over the groups of ``order`` (default: ascending): the f32 sum."""
+    out = np.zeros(accs[0].shape, np.float32)
+    with np.errstate(invalid="ignore", over="ignore"):
+        for g in (range(len(accs)) if order is None else order):
+            out = fma32(accs[g].astype(np.float32), scales[g], out)
+    return out
+
+
+def to_f16(x: np.ndarray) -> np.ndarray:
+    with np.errstate(over="ignore", invalid="ignore"):
+        return np.asarray(x).astype(np.float16)
+
+
 def gemm_fold_f32(a_codes, sa, b_codes, sb) -> np.ndarray:
-    """The contract: out = fmaf(f32(acc_g), f32_rn(sa sb), out) group by group, C = fp16_rn(out)."""
-    sbn = np.repeat(sb, G, axis=0)[: b_codes.shape[0]]
-    out = np.zeros((a_codes.shape[0], b_codes.shape[0]), np.float32)
-    for g, p in enumerate(_group_sums(a_codes, b_codes)):
-        s = sa[:, g][:, None] * sbn[:, g][None, :]  # f32 x f32 -> f32, one rounding
-        out = (p.astype(np.float32).astype(np.float64) * s.astype(np.float64) + out.astype(np.float64)).astype(np.float32)
-    return out.astype(np.float16)
+    """The contract: out = fmaf(f32(acc_g), f32_rn(sa sb), out) group by group, C = fp16_rn(out). Scales may be NaN,
+    Inf, zero or negative; a NaN code makes its group's acc_g NaN for the whole row (column)."""
+    with np.errstate(invalid="ignore"):
+        accs = _group_sums(a_codes, b_codes)
+    return to_f16(fold_f32(accs, scale_products(sa, sb, b_codes.shape[0])))
+
+
+def slice_bounds(groups: int, ks: int, split=lambda g, ks: -(-g // ks)) -> list[tuple[int, int]]:
+    """[g0, g1) of each K slice of the decode kernel: ceil(G / ks) contiguous groups each, the last what remains
+    (mxmoe_amd/csrc/moe_decode_f8g.h, DESIGN.md §4 "Decode forward: block-scaled FP8", "Waves and K slices")."""
+    per = split(groups, ks)
+    return [(min(s * per, groups), min(s * per + per, groups) if s < ks - 1 else groups) for s in range(ks)]
+
+
+def gemm_fold_f32_sliced(a_codes, sa, b_codes, sb, ks: int, split=lambda g, ks: -(-g // ks)) -> np.ndarray:
+    """The decode kernel's order with ks K slices: every slice folds its own groups from zero as the contract does, the
+    slices' f32 sums are added to slice 0's in slice order (one f32 addition each), then fp16_rn. ks = 1 is
+    gemm_fold_f32. ``split``: the groups per slice (the kernel's: ceil)."""
+    with np.errstate(invalid="ignore"):
+        accs = _group_sums(a_codes, b_codes)
+    scales = scale_products(sa, sb, b_codes.shape[0])
+    parts = [fold_f32(accs, scales, range(g0, g1)) for g0, g1 in slice_bounds(len(accs), ks, split)]
+    out = parts[0]
+    with np.errstate(invalid="ignore", over="ignore"):
+        for p in parts[1:]:
+            out = out + p  # f32 + f32 -> f32
+    return to_f16(out)

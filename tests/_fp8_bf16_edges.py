@@ -77,6 +77,9 @@ def _window_rows(rng, rows: int, K: int, win) -> np.ndarray:
     return x
 
 
+window_rows = _window_rows  # (public name: tests/_f8g128_edges.py draws its windows with it)
+
+
 def exact_bound(raw: Raw) -> float:
     """max over (row, column) pairs of sum_k |a_k b_k| / (ga gb), from the operands in f64; asserts that
     every operand is a multiple of its granule. Below 2^24 every partial sum is exact in f32."""
