@@ -587,6 +587,39 @@ int mxmoe_moe_decode_down_f8g(int64_t T, int topk, int E, int with_shared, const
                               const mxmoe_moe_decode_expert* experts, uint32_t kind_mask, int H, int N, int N_shared,
                               const void* act, const void* act_shared, void* y, void* ys, int32_t* status, void* stream);
 
+/* The decode forward with fp16 activations on the fp16 MFMA (added to ABI 7 without a version bump): the _wo entries'
+ * layers — kinds 0 to 11 — on a kernel of its own (decode_a16_kernel, mxmoe_amd/csrc/moe_decode_a16.h) in which the
+ * kinds whose A row stays fp16 run v_mfma_f32_16x16x32_f16: a batch of up to 16 rows is the 16-wide side of that
+ * instruction, so a weight is dequantised once per workgroup and multiplied against all rows at once. The argument lists
+ * (glu included), pair order, safety, limits and refusals are those of mxmoe_moe_decode_gate_up_wo /
+ * mxmoe_moe_decode_down_wo, reported under these entries' names; the expert record is unchanged (40 bytes) and no kind
+ * is added. The ten entries above keep their kernels and their mask checks.
+ *   kinds 0 (MXMOE_DECODE_FP16), 3 (MXMOE_DECODE_W4A16_MX) and 4..11 (the integer weight-only kinds): B, sb1 / sb2 and the
+ *            A row as the _ex / _wo entries define them, and b[r][k] the very fp16 value defined there (fp16: the weight
+ *            itself).
+ *   v(r)     = fp16_rn(sum_k f32(x[k]) * f32(b[r][k])), accumulated in f32 by v_mfma_f32_16x16x32_f16: 32 K values per
+ *            instruction (the order inside it is the hardware's), K groups of 128 ascending within a wave's K slice; the
+ *            slices' partial sums are added in f32 in slice order. A tile of 32 columns splits K in two slices, wider
+ *            tiles in one. Rows wider than the LDS budget are staged in chunks of 512 K values (1024 for T <= 8); then a
+ *            slice owns, of every chunk, a contiguous run of ceil(groups / slices) K groups (the last what remains),
+ *            chunks ascending. This is the contract of the _ex / _wo entries for these kinds (the order of the sum is
+ *            the kernel's): on operands whose f32 partial sums are all exact the outputs equal those entries' bit for bit.
+ *   kinds 1 and 2 (w8a8, w4a4) keep the first entries' arithmetic in the same launch: outputs equal to the _wo entries'
+ *            byte for byte.
+ *   The gate_up epilogue (SiLU, or glu's biases and clamp) and everything behind it are the _ex entries'; down biases
+ *   stay in the combine.
+ * Refusals, before any HIP call and under these entries' names: everything the _wo entries check; a kind bit >= 12:
+ * MXMOE_GG_ERR_UNSUPPORTED. A record whose kind is outside the mask: MXMOE_DECODE_BAD_KIND and nothing written. An id
+ * outside [0, E): MXMOE_DECODE_BAD_ID, its rows kept. T == 0: OK, no launch. One launch each, no allocation, no
+ * synchronisation: graph-capturable. */
+int mxmoe_moe_decode_gate_up_a16(const mxmoe_moe_glu* glu, int dtype, const void* hidden, int64_t T, int topk, int E,
+                                 int with_shared, const int32_t* topk_ids, const mxmoe_moe_decode_expert* experts,
+                                 uint32_t kind_mask, int H, int N, int N_shared, int layout, void* act, void* act_shared,
+                                 int32_t* status, void* stream);
+int mxmoe_moe_decode_down_a16(int64_t T, int topk, int E, int with_shared, const int32_t* topk_ids,
+                              const mxmoe_moe_decode_expert* experts, uint32_t kind_mask, int H, int N, int N_shared,
+                              const void* act, const void* act_shared, void* y, void* ys, int32_t* status, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -115,6 +115,8 @@ EXPORTED_SYMBOLS = (
     "mxmoe_moe_decode_gate_up_lp", "mxmoe_moe_decode_down_lp",
     # the decode forward for block-scaled FP8 experts (w8a8_g128_sym_E4M3): kernels of their own
     "mxmoe_moe_decode_gate_up_f8g", "mxmoe_moe_decode_down_f8g",
+    # the decode forward with fp16 activations on the fp16 MFMA: the _wo entries' kinds on a kernel of its own
+    "mxmoe_moe_decode_gate_up_a16", "mxmoe_moe_decode_down_a16",
 )
 # added to ABI 7 without a version bump (additive): a product library without them is a stale build
 GPTOSS_SYMBOLS = ("mxmoe_moe_gate_ex2", "mxmoe_moe_glu_quant", "mxmoe_moe_combine_bias")
@@ -126,6 +128,7 @@ DECODE_EX_SYMBOLS = ("mxmoe_moe_decode_gate_up_ex", "mxmoe_moe_decode_down_ex") 
 DECODE_WO_SYMBOLS = ("mxmoe_moe_decode_gate_up_wo", "mxmoe_moe_decode_down_wo")  # (likewise: weight-only experts)
 DECODE_LP_SYMBOLS = ("mxmoe_moe_decode_gate_up_lp", "mxmoe_moe_decode_down_lp")  # (likewise: low-precision activations)
 DECODE_F8G_SYMBOLS = ("mxmoe_moe_decode_gate_up_f8g", "mxmoe_moe_decode_down_f8g")  # (likewise: block-scaled FP8 experts)
+DECODE_A16_SYMBOLS = ("mxmoe_moe_decode_gate_up_a16", "mxmoe_moe_decode_down_a16")  # (likewise: fp16 activations on MFMA)
 DT_FP16, DT_BF16 = 0, 1  # MXMOE_DT_* (include/mxmoe_moe.h)
 # MXMOE_DECODE_* (include/mxmoe_moe.h): the token limit, the kinds per linear, the gate_up layouts, the status bits
 DECODE_MAX_T = 16
@@ -348,6 +351,11 @@ def _declare(lib: ctypes.CDLL) -> None:
         lib.mxmoe_moe_decode_gate_up_f8g.argtypes = list(lib.mxmoe_moe_decode_gate_up_ex.argtypes)
         lib.mxmoe_moe_decode_down_f8g.restype = c.c_int
         lib.mxmoe_moe_decode_down_f8g.argtypes = list(lib.mxmoe_moe_decode_down_ex.argtypes)
+    if all(hasattr(lib, fn) for fn in DECODE_A16_SYMBOLS):  # (builds before the fp16-MFMA decode forward lack them)
+        lib.mxmoe_moe_decode_gate_up_a16.restype = c.c_int
+        lib.mxmoe_moe_decode_gate_up_a16.argtypes = list(lib.mxmoe_moe_decode_gate_up_ex.argtypes)
+        lib.mxmoe_moe_decode_down_a16.restype = c.c_int
+        lib.mxmoe_moe_decode_down_a16.argtypes = list(lib.mxmoe_moe_decode_down_ex.argtypes)
 
 
 def lib() -> ctypes.CDLL:

@@ -825,6 +825,7 @@ int segments_check(const int32_t* counts, int E, int64_t T, int topk, const mxmo
 #include "moe_decode.h"  // the decode forward's kernels (after the quantiser helpers above, which they call)
 #include "moe_decode_mfma.h"  // its MFMA tile: the kinds with e4m3 / MXFP8 / MXFP4 activations (the _lp entries)
 #include "moe_decode_f8g.h"   // block-scaled FP8 experts (w8a8_g128_sym_E4M3): a kernel of their own (the _f8g entries)
+#include "moe_decode_a16.h"   // fp16 activations on the fp16 MFMA: a kernel of its own (the _a16 entries)
 
 using namespace mxmoe;
 
@@ -1073,8 +1074,10 @@ static int glu_check(const char* fn, const mxmoe_moe_glu* glu) {
 // _ex entry (kind bit 3, the _ex kernels; glu may be NULL: SiLU and no bias), decode::kWo, the _wo entry (kind bits up
 // to 11, the _wo kernels, glu likewise), decode::kLp, the _lp entry (kind bits up to 14, the _lp kernels, glu likewise);
 // decode::kFirst: glu is NULL and the first entries' kernels run. decode::kF8g: the _f8g entry (kind bit 15 alone, the
-// plain layout, decode_f8g_kernel of moe_decode_f8g.h; glu as the _ex entry's).
+// plain layout, decode_f8g_kernel of moe_decode_f8g.h; glu as the _ex entry's). decode::kA16: the _a16 entry (the _wo
+// entry's kind bits and checks, decode_a16_kernel of moe_decode_a16.h).
 static int decode_mask_check(const char* fn, int level, uint32_t kind_mask, int layout) {
+  if (level == decode::kA16) return decode::kind_mask_check(fn, kind_mask, decode::kWo);
   return level == decode::kF8g ? decode::f8g_checks(fn, kind_mask, layout) : decode::kind_mask_check(fn, kind_mask, level);
 }
 static int decode_gate_up_impl(const char* fn, int level, const mxmoe_moe_glu* glu, int dtype, const void* hidden, int64_t T,
@@ -1116,6 +1119,7 @@ static int decode_gate_up_impl(const char* fn, int level, const mxmoe_moe_glu* g
     a.c = -(glu->alpha * 1.4426950408889634f);
     a.limit = glu->limit;
   }
+  if (level == decode::kA16) return decode::launch_a16<false>(a, stream);
   return level == decode::kF8g ? decode::launch_f8g<false>(a, stream) : decode::launch<false>(a, level, stream);
 }
 
@@ -1142,6 +1146,7 @@ static int decode_down_impl(const char* fn, int level, int64_t T, int topk, int 
   a.K = N, a.K_shared = with_shared ? N_shared : N;
   a.C = a.C_shared = H;
   a.kind_mask = kind_mask;
+  if (level == decode::kA16) return decode::launch_a16<true>(a, stream);
   return level == decode::kF8g ? decode::launch_f8g<true>(a, stream) : decode::launch<true>(a, level, stream);
 }
 
@@ -1396,6 +1401,21 @@ int mxmoe_moe_decode_down_f8g(int64_t T, int topk, int E, int with_shared, const
                               const mxmoe_moe_decode_expert* experts, uint32_t kind_mask, int H, int N, int N_shared,
                               const void* act, const void* act_shared, void* y, void* ys, int32_t* status, void* stream) {
   return decode_down_impl("mxmoe_moe_decode_down_f8g", decode::kF8g, T, topk, E, with_shared, topk_ids, experts, kind_mask,
+                          H, N, N_shared, act, act_shared, y, ys, status, stream);
+}
+
+int mxmoe_moe_decode_gate_up_a16(const mxmoe_moe_glu* glu, int dtype, const void* hidden, int64_t T, int topk, int E,
+                                 int with_shared, const int32_t* topk_ids, const mxmoe_moe_decode_expert* experts,
+                                 uint32_t kind_mask, int H, int N, int N_shared, int layout, void* act, void* act_shared,
+                                 int32_t* status, void* stream) {
+  return decode_gate_up_impl("mxmoe_moe_decode_gate_up_a16", decode::kA16, glu, dtype, hidden, T, topk, E, with_shared,
+                             topk_ids, experts, kind_mask, H, N, N_shared, layout, act, act_shared, status, stream);
+}
+
+int mxmoe_moe_decode_down_a16(int64_t T, int topk, int E, int with_shared, const int32_t* topk_ids,
+                              const mxmoe_moe_decode_expert* experts, uint32_t kind_mask, int H, int N, int N_shared,
+                              const void* act, const void* act_shared, void* y, void* ys, int32_t* status, void* stream) {
+  return decode_down_impl("mxmoe_moe_decode_down_a16", decode::kA16, T, topk, E, with_shared, topk_ids, experts, kind_mask,
                           H, N, N_shared, act, act_shared, y, ys, status, stream);
 }
 

@@ -1743,6 +1743,36 @@ class DecodeForwardF8g(_DecodeBase):
                              f"contiguous f32 tensor of {want} elements on the layer's device")
 
 
+class DecodeForwardA16(_DecodeBase):
+    """``DecodeForwardWo``'s layers on the fp16 MFMA (DESIGN.md §4 "Decode forward: fp16 activations on MFMA"): the
+    same constructor, ``launch`` and ``status`` on the _a16 entries (mxmoe_moe_decode_gate_up_a16 /
+    mxmoe_moe_decode_down_a16, include/mxmoe_moe.h). It takes exactly what ``DecodeForwardWo`` takes — fp16,
+    w4a16_g32_sym_MXFP4 (``gptoss_layer``) and the eight integer weight-only types, mixed freely with w8a8_g-1_sym and
+    w4a4_g-1_sym per expert and per linear (``workload.w4a16_w8a8_qconfig``), a ``MoEFFN`` or a ``MoEBlock``, fp16 or
+    bf16 ends, biases and ``SwigluClamp`` — and refuses what it refuses. The experts whose A row stays fp16 are
+    multiplied by v_mfma_f32_16x16x32_f16: a decode batch is at most 16 rows, the 16-wide side of that instruction, so
+    a weight is read and dequantised once per workgroup and meets every row of the batch in one instruction, where
+    ``DecodeForwardEx`` / ``DecodeForwardWo`` multiply it once per row on the VALU (and ``DecodeForwardWo`` streams the
+    weights again for every 5 rows). The w8a8 / w4a4 experts keep their integer dot products in the same launch, byte for
+    byte. ``out`` is within the f32 summation order of ``MoEFFN.forward``'s, and equal to ``DecodeForwardWo``'s where
+    every partial sum is exact.
+
+    Which form at which T (MI355X device time, tools/decode_bench.py --form a16, T = 1 / 4 / 8 / 12 / 16):
+    on qwen2_moe layer 11 with the w4a16 + w8a8 scheme this class takes 0.76x / 0.66x / 0.43x / 0.32x / 0.29x of
+    ``DecodeForwardWo``'s time and 0.29x / 0.33x / 0.41x / 0.42x / 0.48x of ``GraphForward``'s; on the gpt-oss layer
+    shape (MXFP4 weights, fp16 activations) 0.76x / 0.84x / 0.80x / 0.60x / 0.57x of ``DecodeForwardEx``'s and 0.41x /
+    0.58x / 0.66x / 0.68x / 0.68x of ``GraphForward``'s: take this class at every T from 1 to 16 for layers with 4-bit
+    or 8-bit weight-only experts, there is no crossover. On the same qwen2_moe layer with every expert fp16 it takes
+    1.35x / 1.27x / 1.07x of the VALU form's time at T = 1 / 4 / 8 and 0.94x / 0.92x at T = 12 / 16 (0.35x to 0.71x of
+    ``GraphForward``'s throughout): for all-fp16 layers take ``DecodeForward`` below T = 12 and this class from there."""
+
+    KINDS = DecodeForwardWo.KINDS
+    ENTRIES = nat.DECODE_A16_SYMBOLS
+    TAKES_GLU = True
+    TAKES_MX = True
+    _check_scale = DecodeForwardWo._check_scale
+
+
 def qwen2_layer_bench(*args, **kwargs) -> dict:
     """``moe_bench.qwen2_layer_bench`` under the name bench.py imports (the benchmarks live in mxmoe_amd/moe_bench.py)."""
     from .moe_bench import qwen2_layer_bench as bench

@@ -12,7 +12,7 @@ import torch
 from . import _native as nat
 from .groupgemm import W4A8_MXFP8, W4A16_MXFP4, W8A8_E4M3, W8A8_G128_E4M3, QParams
 from .harness import time_launches
-from .moe import (_BITS, DecodeForward, DecodeForwardEx, DecodeForwardF8g, DecodeForwardLp, DecodeForwardWo, GraphForward, MoEBlock, MoEFFN, PlannedForward, SwigluClamp, _launch_combine,
+from .moe import (_BITS, DecodeForward, DecodeForwardA16, DecodeForwardEx, DecodeForwardF8g, DecodeForwardLp, DecodeForwardWo, GraphForward, MoEBlock, MoEFFN, PlannedForward, SwigluClamp, _launch_combine,
                   _ptr, _stream, combine_into, gate, gptoss_layer, prepare_weight_mx, silu_mul_quant)
 from .workload import (ds2_mixed_qconfig, ds2_workload, load_workload, mixed_qconfig_lp1, qwen2_layer11_workload,
                        w4a16_w8a8_qconfig)
@@ -268,7 +268,7 @@ def fp8_layer_bench(batches: Sequence[int] = (128, 512, 2048, 8192), rounds: int
 
 
 def _decode_bench(layer: MoEFFN, cls, call, rounds: int, iters: int, head: dict, compare: str, weight_bytes,
-                  plain: Optional[MoEFFN] = None, report_used: bool = True) -> dict:
+                  plain: Optional[MoEFFN] = None, report_used: bool = True, also=None) -> dict:
     """One batch size of a decode bench: ``cls(layer)`` against ``GraphForward(layer)`` on ``call`` = (hidden, ids,
     wts), both captured and replayed, the sides alternating over rounds. Compared with the eager layer bit for bit
     (``compare`` = "bit_identical_to_eager") or within the fp16 GroupGEMM tolerance 1e-3 |ref| + 1e-3 rms(ref)
@@ -284,6 +284,8 @@ def _decode_bench(layer: MoEFFN, cls, call, rounds: int, iters: int, head: dict,
     objs = {"graph": GraphForward(layer, bs, topk), "decode": cls(layer, bs, topk)}
     if plain is not None:
         objs["decode_plain"] = cls(plain, bs, topk)
+    if also is not None:
+        objs["a16"] = also(layer, bs, topk)
     gf, df = objs["graph"], objs["decode"]
     graphs = {k: _captured(lambda o=o: o.launch(hidden, ids, wts)) for k, o in objs.items()}
     for gr in graphs.values():
@@ -296,13 +298,14 @@ def _decode_bench(layer: MoEFFN, cls, call, rounds: int, iters: int, head: dict,
         tol = 1e-3 * want.abs() + 1e-3 * want.square().mean().sqrt() + 1e-6
         same = {k: bool(((o.out.float() - want).abs() <= tol).all()) for k, o in objs.items()}
     wall, device = (lambda fn: _wall(fn, iters)), (lambda fn: _device(fn, iters))
-    st, glu = _stream(None), ((df._glu,) if df.TAKES_GLU else ())
-    gate_up_k = lambda: nat.check(nat.symbol(df.ENTRIES[0])(
-        *glu, nat.DT_FP16, _ptr(hidden), bs, topk, E, shared, _ptr(ids), _ptr(df.experts), df.mask1, layer.H, layer.N,
-        layer.Ns, df.layout, _ptr(df.act), _ptr(df.act_shared), _ptr(df.dev_status), st))
-    down_k = lambda: nat.check(nat.symbol(df.ENTRIES[1])(
+    st = _stream(None)
+    gate_up_of = lambda df: lambda: nat.check(nat.symbol(df.ENTRIES[0])(
+        *((df._glu,) if df.TAKES_GLU else ()), nat.DT_FP16, _ptr(hidden), bs, topk, E, shared, _ptr(ids), _ptr(df.experts),
+        df.mask1, layer.H, layer.N, layer.Ns, df.layout, _ptr(df.act), _ptr(df.act_shared), _ptr(df.dev_status), st))
+    down_of = lambda df: lambda: nat.check(nat.symbol(df.ENTRIES[1])(
         bs, topk, E, shared, _ptr(ids), _ptr(df.experts), df.mask2, layer.H, layer.N, layer.Ns, _ptr(df.act),
         _ptr(df.act_shared), _ptr(df.y), _ptr(df.ys), _ptr(df.dev_status), st))
+    gate_up_k, down_k = gate_up_of(df), down_of(df)
     if df._glu is not None:  # the bias combine, as DecodeForwardEx.launch calls it
         combine = {"combine_bias": lambda: device(lambda: _launch_combine(df.out, df.y, df.inv_slot, ids.view(-1), wts, None, None,
                                                                           topk, None, layer.down_bias))}
@@ -311,6 +314,8 @@ def _decode_bench(layer: MoEFFN, cls, call, rounds: int, iters: int, head: dict,
     sides = {k + "_device": (lambda gr=gr: device(gr.replay)) for k, gr in graphs.items()}
     sides.update({"graph_wall": lambda: wall(graphs["graph"].replay), "decode_wall": lambda: wall(graphs["decode"].replay),
                   "decode_gate_up": lambda: device(gate_up_k), "decode_down": lambda: device(down_k)}, **combine)
+    if also is not None:
+        sides.update({"a16_gate_up": lambda: device(gate_up_of(objs["a16"])), "a16_down": lambda: device(down_of(objs["a16"]))})
     out = dict(head, graph_gate_up_mode=gf.mode)
     out.update({k: _stat(v) for k, v in _rounds(sides, rounds).items()})
     used = sorted(set(ids.flatten().tolist())) + ([E] if shared else [])
@@ -324,6 +329,12 @@ def _decode_bench(layer: MoEFFN, cls, call, rounds: int, iters: int, head: dict,
     out["faster"] = bool(out["decode_device"]["max_us"] < out["graph_device"]["min_us"])
     out[compare] = same
     out["status"] = {"graph": gf.status(), "decode": df.status() | (objs["decode_plain"].status() if plain is not None else 0)}
+    if also is not None:
+        m = lambda k: out[k]["median_us"]
+        out["a16_over_decode_device"] = round(m("a16_device") / m("decode_device"), 4)
+        out["a16_over_graph_device"] = round(m("a16_device") / m("graph_device"), 4)
+        out["graph_device_spread"] = round((out["graph_device"]["max_us"] - out["graph_device"]["min_us"]) / m("graph_device"), 4)
+        out["status"]["a16"] = objs["a16"].status()
     return out
 
 
@@ -367,23 +378,27 @@ def decode_forward_bench(batches: Sequence[int] = (1, 4, 16), rounds: int = 4, i
                             "bit_identical_to_eager", weight_bytes, plain=plain, report_used=False)
 
 
-def decode_forward_wo_bench(batches: Sequence[int] = (1, 4, 16), rounds: int = 4, iters: int = 30):
+def decode_forward_wo_bench(batches: Sequence[int] = (1, 4, 16), rounds: int = 4, iters: int = 30, a16: bool = False,
+                            fp16: bool = False):
     """qwen2_moe layer 11 with the reference's small-batch scheme (``w4a16_w8a8_qconfig``: w4a16_g-1_asym + w8a8 per
     linear, the shared expert included; random weights, routing drawn from the committed histogram) at decode sizes,
     ``DecodeForwardWo`` against ``GraphForward`` of the same layer, as ``decode_forward_bench`` measures the LP-1 layer
     (yields one dict per batch size). Also the weight bytes (codes and scale buffers of the experts the ids name, and
     the shared expert's), the TB/s they imply and the kinds among them. Weight-only sums depend on their order, so the
-    outputs are compared with the eager layer's within the fp16 GroupGEMM tolerance, not bit for bit."""
+    outputs are compared with the eager layer's within the fp16 GroupGEMM tolerance, not bit for bit. a16:
+    ``DecodeForwardA16`` on the same layer as a further side. fp16: the same layer with every expert fp16 instead."""
     dev, topk, g = "cuda", 4, torch.Generator().manual_seed(0)
     gate_up, down, qcfg, hist, E, H, N, Ns = _qwen2_decode_layer(w4a16_w8a8_qconfig(), g, dev)
-    layer = MoEFFN(gate_up, down, qcfg, num_routed=E)
+    layer = MoEFFN(gate_up, down, [(QParams(), QParams())] * (E + 1) if fp16 else qcfg, num_routed=E)
     del gate_up, down
-    weight_bytes = lambda ws, es: sum(ws[e].B.numel() * ws[e].B.element_size() +
-                                      ws[e].scale_b.numel() * ws[e].scale_b.element_size() for e in es)
+    weight_bytes = lambda ws, es: sum(ws[e].B.numel() * ws[e].B.element_size() + (
+        0 if ws[e].scale_b is None else ws[e].scale_b.numel() * ws[e].scale_b.element_size()) for e in es)
     for bs in batches:
-        head = {"model": "qwen2_moe", "scheme": "w4a16_w8a8", "bs": bs, "E": E, "topk": topk, "H": H, "N": N, "N_shared": Ns}
+        head = {"model": "qwen2_moe", "scheme": "fp16" if fp16 else "w4a16_w8a8", "bs": bs, "E": E, "topk": topk, "H": H, "N": N,
+                "N_shared": Ns}
         call = _qwen2_decode_call(g, hist, bs, E, topk, H, dev)
-        out = _decode_bench(layer, DecodeForwardWo, call, rounds, iters, head, "close_to_eager", weight_bytes)
+        out = _decode_bench(layer, DecodeForwardWo, call, rounds, iters, head, "close_to_eager", weight_bytes,
+                            also=DecodeForwardA16 if a16 else None)
         used = sorted(set(call[1].flatten().tolist())) + [E]
         out["kinds"] = {"gate_up": sorted({layer.w1[e].q.qcfg for e in used}), "down": sorted({layer.w2[e].q.qcfg for e in used})}
         yield out
@@ -434,14 +449,14 @@ def decode_forward_f8g_bench(batches: Sequence[int] = (1, 4, 16), rounds: int = 
 
 
 def decode_forward_gptoss_bench(batches: Sequence[int] = (1, 4, 16), rounds: int = 4, iters: int = 30, E: int = 32,
-                                topk: int = 4, H: int = 2880, N: int = 2880, act_bits: int = 16):
+                                topk: int = 4, H: int = 2880, N: int = 2880, act_bits: int = 16, a16: bool = False):
     """A synthetic gpt-oss layer (``gptoss_layer``: E = 32, top-4, H = N = 2880 padded to 2944, random e2m1 codes, scale
     bytes in [118, 126], biases in +-0.5, the clamped SwiGLU) at decode sizes, ``DecodeForwardEx`` against
     ``GraphForward`` of the same layer, as ``decode_forward_bench`` measures the qwen2_moe layer (yields one dict per
     batch size), with the bias combine alone. Also the weight bytes (codes and scale bytes of the experts the ids
     name) and the TB/s they imply. MXFP4 sums depend on their order, so the outputs are compared with the eager
     layer's within the fp16 GroupGEMM tolerance, not bit for bit. act_bits = 8: the layer with MXFP8 activations
-    (w4a8_g32_sym_MXFP8) and ``DecodeForwardLp``."""
+    (w4a8_g32_sym_MXFP8) and ``DecodeForwardLp``. a16 (act_bits = 16): ``DecodeForwardA16`` as a further side."""
     dev = "cuda"
     g = torch.Generator(device=dev).manual_seed(0)
     u8 = lambda *shape, lo=0, hi=256: torch.randint(lo, hi, shape, generator=g, device=dev, dtype=torch.uint8)
@@ -457,7 +472,8 @@ def decode_forward_gptoss_bench(batches: Sequence[int] = (1, 4, 16), rounds: int
         wts = torch.softmax(torch.rand(bs, topk, generator=g, device=dev), dim=1)
         head = {"model": "gpt-oss layer (synthetic)", "act_bits": act_bits, "bs": bs, "E": E, "topk": topk, "H": layer.H,
                 "N": layer.N}
-        yield _decode_bench(layer, cls, (hidden, ids, wts), rounds, iters, head, "close_to_eager", weight_bytes)
+        yield _decode_bench(layer, cls, (hidden, ids, wts), rounds, iters, head, "close_to_eager", weight_bytes,
+                            also=DecodeForwardA16 if a16 and act_bits == 16 else None)
 
 
 def gptoss_bench(batches: Sequence[int] = (1, 16, 128, 512, 2048), act_bits: int = 16, rounds: int = 4, iters: int = 20,

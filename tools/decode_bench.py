@@ -24,8 +24,13 @@ MFMA decode kernels) against GraphForward of the same layer, compared within the
 DecodeForwardF8g against GraphForward of the same layer, on the rows --scheme e4m3 draws; --scheme f8g128_ds: a
 DeepSeek-V3-shaped layer of that type (H = 7168, N = 2048, top-8, E reduced to 16). Compared within the fp16 tolerance.
 
-python tools/decode_bench.py [--model qwen2_moe|gpt-oss] [--scheme lp1|w4a16_w8a8|e4m3|f8g128|f8g128_ds] [--act-bits 16|8] [--rounds 4]
-                             [--iters 30] [--batches 1,4,16] [--out FILE]
+--form a16: DecodeForwardA16 (fp16 activations on the fp16 MFMA) as a further side of the same rounds, beside the VALU
+form and GraphForward, on the layers it takes: --scheme w4a16_w8a8, --scheme fp16 (layer 11 with every expert fp16) and
+--model gpt-oss with fp16 activations. Reported with its two entries alone, its device median over the VALU form's and
+over GraphForward's, and GraphForward's own (max - min) / median over the rounds.
+
+python tools/decode_bench.py [--model qwen2_moe|gpt-oss] [--scheme lp1|w4a16_w8a8|fp16|e4m3|f8g128|f8g128_ds] [--act-bits 16|8]
+                             [--form valu|a16] [--rounds 4] [--iters 30] [--batches 1,4,16] [--out FILE]
 """
 from __future__ import annotations
 
@@ -46,19 +51,26 @@ def main():
     ap.add_argument("--batches", default="1,4,16")
     ap.add_argument("--out", default="")
     ap.add_argument("--model", default="qwen2_moe", choices=["qwen2_moe", "gpt-oss"])
-    ap.add_argument("--scheme", default="lp1", choices=["lp1", "w4a16_w8a8", "e4m3", "f8g128", "f8g128_ds"],
+    ap.add_argument("--scheme", default="lp1", choices=["lp1", "w4a16_w8a8", "fp16", "e4m3", "f8g128", "f8g128_ds"],
                     help="qwen2_moe: the layer's qconfig")
     ap.add_argument("--act-bits", type=int, default=16, choices=[16, 8], help="gpt-oss: fp16 or MXFP8 activations")
+    ap.add_argument("--form", default="valu", choices=["valu", "a16"], help="a16: DecodeForwardA16 as a further side")
     args = ap.parse_args()
     if args.model == "gpt-oss" and args.scheme != "lp1":
         ap.error("--scheme belongs to --model qwen2_moe")
     if args.model != "gpt-oss" and args.act_bits != 16:
         ap.error("--act-bits belongs to --model gpt-oss")
+    a16 = args.form == "a16"
+    if a16 and not (args.scheme in ("w4a16_w8a8", "fp16") or (args.model == "gpt-oss" and args.act_bits == 16)):
+        ap.error("--form a16 takes --scheme w4a16_w8a8 or fp16, or --model gpt-oss with fp16 activations")
     results = []
     wo = args.scheme != "lp1"
     kw = {"act_bits": args.act_bits} if args.model == "gpt-oss" else {}
+    if a16 or args.scheme == "fp16":
+        kw["a16"] = a16
     bench = moe_bench.decode_forward_gptoss_bench if args.model == "gpt-oss" else \
         {"lp1": moe_bench.decode_forward_bench, "w4a16_w8a8": moe_bench.decode_forward_wo_bench,
+         "fp16": lambda *a, **k: moe_bench.decode_forward_wo_bench(*a, fp16=True, **k),
          "e4m3": moe_bench.decode_forward_e4m3_bench, "f8g128": moe_bench.decode_forward_f8g_bench,
          "f8g128_ds": lambda *a: moe_bench.decode_forward_f8g_bench(*a, deepseek=True)}[args.scheme]
     for r in bench([int(b) for b in args.batches.split(",") if b], args.rounds, args.iters, **kw):
