@@ -620,6 +620,44 @@ int mxmoe_moe_decode_down_a16(int64_t T, int topk, int E, int with_shared, const
                               const mxmoe_moe_decode_expert* experts, uint32_t kind_mask, int H, int N, int N_shared,
                               const void* act, const void* act_shared, void* y, void* ys, int32_t* status, void* stream);
 
+/* The decode forward for block-scaled FP8 experts at up to 64 tokens ("wide"; added to ABI 7 without a version bump):
+ * the _f8g entries' layers, records, kind (15 alone), pair order, safety and epilogue, on kernels of their own
+ * (mxmoe_amd/csrc/moe_decode_f8g_wide.h) that take 0 <= T <= MXMOE_DECODE_WIDE_MAX_T. The A rows are quantised once per
+ * call and stage by mxmoe_moe_decode_quant_f8g into caller-owned scratch, and the tile entries read those codes and
+ * scales in place of the fp16 rows. The twelve entries above keep their kernels, their checks and MXMOE_DECODE_MAX_T.
+ * mxmoe_moe_decode_quant_f8g: rows [rows][K] of src and, in the same launch, rows2 [rows2][K2] of src2 (both `dtype`:
+ *   fp16, or bf16 converted as mxmoe_moe_gather_quant does) to e4m3 codes uint8 [rows][K] and f32 scales [rows][K / 128]
+ *   (codes2 / scales2 likewise): MXMOE_ACT_E4M3_G128's values bit for bit, as the _f8g entries define the A row. One wave
+ *   per row. rows <= 16 * MXMOE_DECODE_WIDE_MAX_T, rows2 <= MXMOE_DECODE_WIDE_MAX_T; a set of zero rows is skipped (its
+ *   pointers may be NULL), both zero: OK, no launch. K, K2 multiples of 128 and <= 16384; src and codes 16-byte, scales
+ *   4-byte aligned. Before gate_up: the T hidden rows (the shared expert reads the same codes). Before down: the
+ *   T * topk act rows and the T act_shared rows of width N_shared.
+ * mxmoe_moe_decode_gate_up_f8g_wide: mxmoe_moe_decode_gate_up_f8g with `codes` uint8 [T][H] and `scales` f32
+ *   [T][H / 128] in place of dtype and hidden: pair p reads row p / topk, the shared expert row t.
+ * mxmoe_moe_decode_down_f8g_wide: mxmoe_moe_decode_down_f8g with codes [T * topk][N] / scales [T * topk][N / 128] in
+ *   place of act (pair p reads row p) and codes_shared [T][N_shared] / scales_shared in place of act_shared.
+ *   v(r)      out = fmaf(acc_g, f32_rn(sa[row][g] * sb[g][r / 128]), out) over all K groups ascending, one slice at every
+ *             tile width (64 or 128 columns); v = fp16_rn(out): the GroupGEMM's contract of the type word for word. An
+ *             expert's rows are multiplied in batches of up to min(64, T rounded up to 16) against one pass over its
+ *             weights.
+ * Refusals, before any HIP call and under these entries' names: T > MXMOE_DECODE_WIDE_MAX_T, the _f8g entries' checks of
+ * E, topk and the widths, glu's checks, a misaligned pointer: MXMOE_GG_ERR_INVALID; a kind_mask other than exactly
+ * 1 << 15 or layout != MXMOE_DECODE_GU_PLAIN: MXMOE_GG_ERR_UNSUPPORTED. A record whose kind is not 15:
+ * MXMOE_DECODE_BAD_KIND and nothing written. An id outside [0, E): MXMOE_DECODE_BAD_ID, its rows kept. T == 0: OK, no
+ * launch. One launch each, no allocation, no synchronisation: graph-capturable. */
+enum { MXMOE_DECODE_WIDE_MAX_T = 64 };
+int mxmoe_moe_decode_quant_f8g(int dtype, const void* src, int64_t rows, int K, void* codes, float* scales,
+                               const void* src2, int64_t rows2, int K2, void* codes2, float* scales2, void* stream);
+int mxmoe_moe_decode_gate_up_f8g_wide(const mxmoe_moe_glu* glu, const void* codes, const float* scales, int64_t T, int topk,
+                                      int E, int with_shared, const int32_t* topk_ids,
+                                      const mxmoe_moe_decode_expert* experts, uint32_t kind_mask, int H, int N,
+                                      int N_shared, int layout, void* act, void* act_shared, int32_t* status,
+                                      void* stream);
+int mxmoe_moe_decode_down_f8g_wide(int64_t T, int topk, int E, int with_shared, const int32_t* topk_ids,
+                                   const mxmoe_moe_decode_expert* experts, uint32_t kind_mask, int H, int N, int N_shared,
+                                   const void* codes, const float* scales, const void* codes_shared,
+                                   const float* scales_shared, void* y, void* ys, int32_t* status, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

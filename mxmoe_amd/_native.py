@@ -117,6 +117,8 @@ EXPORTED_SYMBOLS = (
     "mxmoe_moe_decode_gate_up_f8g", "mxmoe_moe_decode_down_f8g",
     # the decode forward with fp16 activations on the fp16 MFMA: the _wo entries' kinds on a kernel of its own
     "mxmoe_moe_decode_gate_up_a16", "mxmoe_moe_decode_down_a16",
+    # block-scaled FP8 experts at up to 64 tokens: a row quantiser and the tile entries that read its codes
+    "mxmoe_moe_decode_quant_f8g", "mxmoe_moe_decode_gate_up_f8g_wide", "mxmoe_moe_decode_down_f8g_wide",
 )
 # added to ABI 7 without a version bump (additive): a product library without them is a stale build
 GPTOSS_SYMBOLS = ("mxmoe_moe_gate_ex2", "mxmoe_moe_glu_quant", "mxmoe_moe_combine_bias")
@@ -129,9 +131,13 @@ DECODE_WO_SYMBOLS = ("mxmoe_moe_decode_gate_up_wo", "mxmoe_moe_decode_down_wo") 
 DECODE_LP_SYMBOLS = ("mxmoe_moe_decode_gate_up_lp", "mxmoe_moe_decode_down_lp")  # (likewise: low-precision activations)
 DECODE_F8G_SYMBOLS = ("mxmoe_moe_decode_gate_up_f8g", "mxmoe_moe_decode_down_f8g")  # (likewise: block-scaled FP8 experts)
 DECODE_A16_SYMBOLS = ("mxmoe_moe_decode_gate_up_a16", "mxmoe_moe_decode_down_a16")  # (likewise: fp16 activations on MFMA)
+# (likewise: block-scaled FP8 experts at up to 64 tokens) the quantiser, gate_up, down
+DECODE_F8G_WIDE_SYMBOLS = ("mxmoe_moe_decode_quant_f8g", "mxmoe_moe_decode_gate_up_f8g_wide",
+                           "mxmoe_moe_decode_down_f8g_wide")
 DT_FP16, DT_BF16 = 0, 1  # MXMOE_DT_* (include/mxmoe_moe.h)
 # MXMOE_DECODE_* (include/mxmoe_moe.h): the token limit, the kinds per linear, the gate_up layouts, the status bits
 DECODE_MAX_T = 16
+DECODE_WIDE_MAX_T = 64  # MXMOE_DECODE_WIDE_MAX_T: the _f8g_wide entries only
 DECODE_FP16, DECODE_W8A8, DECODE_W4A4 = 0, 1, 2
 DECODE_W4A16_MX = 3  # (the _ex and _wo entries only)
 # the _wo entries only: kind = 4 + (w_bits == 8) + 2 * (gsize == 128) + 4 * asym
@@ -356,6 +362,15 @@ def _declare(lib: ctypes.CDLL) -> None:
         lib.mxmoe_moe_decode_gate_up_a16.argtypes = list(lib.mxmoe_moe_decode_gate_up_ex.argtypes)
         lib.mxmoe_moe_decode_down_a16.restype = c.c_int
         lib.mxmoe_moe_decode_down_a16.argtypes = list(lib.mxmoe_moe_decode_down_ex.argtypes)
+    if all(hasattr(lib, fn) for fn in DECODE_F8G_WIDE_SYMBOLS):  # (builds before the wide FP8 decode forward lack them)
+        lib.mxmoe_moe_decode_quant_f8g.restype = c.c_int
+        lib.mxmoe_moe_decode_quant_f8g.argtypes = [c.c_int, P, c.c_int64, c.c_int, P, P, P, c.c_int64, c.c_int, P, P, P]
+        lib.mxmoe_moe_decode_gate_up_f8g_wide.restype = c.c_int
+        lib.mxmoe_moe_decode_gate_up_f8g_wide.argtypes = [c.POINTER(MoeGluC), P, P, c.c_int64, c.c_int, c.c_int, c.c_int, P, P,
+                                                          c.c_uint32, c.c_int, c.c_int, c.c_int, c.c_int, P, P, P, P]
+        lib.mxmoe_moe_decode_down_f8g_wide.restype = c.c_int
+        lib.mxmoe_moe_decode_down_f8g_wide.argtypes = [c.c_int64, c.c_int, c.c_int, c.c_int, P, P, c.c_uint32, c.c_int, c.c_int,
+                                                       c.c_int, P, P, P, P, P, P, P, P]
 
 
 def lib() -> ctypes.CDLL:

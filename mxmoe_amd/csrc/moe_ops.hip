@@ -826,6 +826,7 @@ int segments_check(const int32_t* counts, int E, int64_t T, int topk, const mxmo
 #include "moe_decode_mfma.h"  // its MFMA tile: the kinds with e4m3 / MXFP8 / MXFP4 activations (the _lp entries)
 #include "moe_decode_f8g.h"   // block-scaled FP8 experts (w8a8_g128_sym_E4M3): a kernel of their own (the _f8g entries)
 #include "moe_decode_a16.h"   // fp16 activations on the fp16 MFMA: a kernel of its own (the _a16 entries)
+#include "moe_decode_f8g_wide.h"  // block-scaled FP8 experts at up to 64 tokens: a row quantiser and a tile kernel
 
 using namespace mxmoe;
 
@@ -1417,6 +1418,100 @@ int mxmoe_moe_decode_down_a16(int64_t T, int topk, int E, int with_shared, const
                               const void* act, const void* act_shared, void* y, void* ys, int32_t* status, void* stream) {
   return decode_down_impl("mxmoe_moe_decode_down_a16", decode::kA16, T, topk, E, with_shared, topk_ids, experts, kind_mask,
                           H, N, N_shared, act, act_shared, y, ys, status, stream);
+}
+
+
+int mxmoe_moe_decode_quant_f8g(int dtype, const void* src, int64_t rows, int K, void* codes, float* scales,
+                               const void* src2, int64_t rows2, int K2, void* codes2, float* scales2, void* stream) {
+  const char* fn = "mxmoe_moe_decode_quant_f8g";
+  if (int st = dtype_check(fn, "dtype", dtype)) return st;
+  if (rows < 0 || rows > decode::kWideMaxPairs || rows2 < 0 || rows2 > MXMOE_DECODE_WIDE_MAX_T)
+    return fail(MXMOE_GG_ERR_INVALID, "%s: need 0 <= rows <= %d and 0 <= rows2 <= %d (rows=%lld rows2=%lld)", fn,
+                decode::kWideMaxPairs, (int)MXMOE_DECODE_WIDE_MAX_T, (long long)rows, (long long)rows2);
+  if ((rows && !decode::width_ok(K)) || (rows2 && !decode::width_ok(K2)))
+    return fail(MXMOE_GG_ERR_INVALID, "%s: K and K2 must be multiples of 128 and <= %d (K=%d K2=%d)", fn, decode::kMaxWidthD,
+                K, K2);
+  if (!aligned16(src) || !aligned16(codes) || !aligned16(src2) || !aligned16(codes2) || ((uintptr_t)scales & 3) ||
+      ((uintptr_t)scales2 & 3))
+    return fail(MXMOE_GG_ERR_INVALID, "%s: misaligned pointer (rows and codes need 16 B, scales 4 B)", fn);
+  if (rows + rows2 == 0) return MXMOE_GG_OK;
+  if ((rows && (!src || !codes || !scales)) || (rows2 && (!src2 || !codes2 || !scales2)))
+    return fail(MXMOE_GG_ERR_INVALID, "%s: NULL pointer", fn);
+  decode::QuantArgs q{};
+  q.src = static_cast<const uint8_t*>(src), q.src2 = static_cast<const uint8_t*>(src2);
+  q.codes = static_cast<uint8_t*>(codes), q.codes2 = static_cast<uint8_t*>(codes2);
+  q.scales = scales, q.scales2 = scales2;
+  q.rows = (int)rows, q.rows2 = (int)rows2, q.K = K, q.K2 = K2, q.bf = dtype == MXMOE_DT_BF16;
+  return decode::launch_f8g_quant(q, stream);
+}
+
+int mxmoe_moe_decode_gate_up_f8g_wide(const mxmoe_moe_glu* glu, const void* codes, const float* scales, int64_t T, int topk,
+                                      int E, int with_shared, const int32_t* topk_ids,
+                                      const mxmoe_moe_decode_expert* experts, uint32_t kind_mask, int H, int N,
+                                      int N_shared, int layout, void* act, void* act_shared, int32_t* status,
+                                      void* stream) {
+  const char* fn = "mxmoe_moe_decode_gate_up_f8g_wide";
+  if (int st = decode::wide_checks(fn, T, topk, E, with_shared, H, N, N_shared, kind_mask, layout)) return st;
+  if (glu) {
+    if (int st = glu_check(fn, glu)) return st;
+    if (glu->bias_shared && !with_shared)
+      return fail(MXMOE_GG_ERR_INVALID, "%s: glu->bias_shared given without a shared expert", fn);
+  }
+  if (!aligned16(codes) || !aligned16(act) || !aligned16(act_shared) || ((uintptr_t)scales & 3) ||
+      ((uintptr_t)topk_ids & 3) || ((uintptr_t)experts & 7) || ((uintptr_t)status & 3))
+    return fail(MXMOE_GG_ERR_INVALID, "%s: misaligned pointer (codes / act / act_shared need 16 B, scales 4 B)", fn);
+  if (T == 0) return MXMOE_GG_OK;
+  if (!codes || !scales || !topk_ids || !experts || !act || (with_shared && !act_shared))
+    return fail(MXMOE_GG_ERR_INVALID, "%s: NULL pointer", fn);
+  decode::WideArgs wa{};
+  decode::Args& a = wa.a;
+  a.src = a.src_shared = codes;
+  wa.sa = wa.sa_shared = scales;
+  a.ids = topk_ids;
+  a.experts = experts;
+  a.out = static_cast<_Float16*>(act);
+  a.out_shared = static_cast<_Float16*>(act_shared);
+  a.status = status;
+  a.T = (int)T, a.topk = topk, a.E = E, a.with_shared = with_shared != 0;
+  a.K = a.K_shared = H;
+  a.C = N, a.C_shared = with_shared ? N_shared : 0;
+  a.layout = layout, a.kind_mask = kind_mask;
+  a.glu = glu && glu->act == MXMOE_GLU_SWIGLU_CLAMP ? kGluSwigluClamp : kGluSilu;
+  if (glu) {
+    a.bias_routed = static_cast<const _Float16*>(glu->bias_routed);
+    a.bias_shared = static_cast<const _Float16*>(glu->bias_shared);
+    a.c = -(glu->alpha * 1.4426950408889634f);
+    a.limit = glu->limit;
+  }
+  return decode::launch_f8g_wide<false>(wa, stream);
+}
+
+int mxmoe_moe_decode_down_f8g_wide(int64_t T, int topk, int E, int with_shared, const int32_t* topk_ids,
+                                   const mxmoe_moe_decode_expert* experts, uint32_t kind_mask, int H, int N, int N_shared,
+                                   const void* codes, const float* scales, const void* codes_shared,
+                                   const float* scales_shared, void* y, void* ys, int32_t* status, void* stream) {
+  const char* fn = "mxmoe_moe_decode_down_f8g_wide";
+  if (int st = decode::wide_checks(fn, T, topk, E, with_shared, H, N, N_shared, kind_mask, MXMOE_DECODE_GU_PLAIN)) return st;
+  if (!aligned16(codes) || !aligned16(codes_shared) || !aligned16(y) || !aligned16(ys) || ((uintptr_t)scales & 3) ||
+      ((uintptr_t)scales_shared & 3) || ((uintptr_t)topk_ids & 3) || ((uintptr_t)experts & 7) || ((uintptr_t)status & 3))
+    return fail(MXMOE_GG_ERR_INVALID, "%s: misaligned pointer (codes / codes_shared / y / ys need 16 B, scales 4 B)", fn);
+  if (T == 0) return MXMOE_GG_OK;
+  if (!codes || !scales || !topk_ids || !experts || !y || (with_shared && (!codes_shared || !scales_shared || !ys)))
+    return fail(MXMOE_GG_ERR_INVALID, "%s: NULL pointer", fn);
+  decode::WideArgs wa{};
+  decode::Args& a = wa.a;
+  a.src = codes, a.src_shared = codes_shared;
+  wa.sa = scales, wa.sa_shared = scales_shared;
+  a.ids = topk_ids;
+  a.experts = experts;
+  a.out = static_cast<_Float16*>(y);
+  a.out_shared = static_cast<_Float16*>(ys);
+  a.status = status;
+  a.T = (int)T, a.topk = topk, a.E = E, a.with_shared = with_shared != 0;
+  a.K = N, a.K_shared = with_shared ? N_shared : N;
+  a.C = a.C_shared = H;
+  a.kind_mask = kind_mask;
+  return decode::launch_f8g_wide<true>(wa, stream);
 }
 
 }  // extern "C"

@@ -1498,6 +1498,20 @@ class _DecodeBase:
             self.gate_out = (torch.zeros(T, topk, **i32), torch.zeros(T, topk, dtype=torch.float32, device=dev),
                              torch.zeros(T, dtype=torch.float32, device=dev) if self.block.w_shared_gate is not None else None)
 
+    def _stages(self, hidden: torch.Tensor, T: int, topk_ids: torch.Tensor, st) -> None:
+        """The launches between the router and the combine: the class's gate_up and down entries (a subclass whose
+        entries take other operands launches its own)."""
+        ffn, topk = self.ffn, self.topk
+        shared = int(ffn.has_shared)
+        gate_up, down = self.ENTRIES
+        glu = (self._glu,) if self.TAKES_GLU else ()
+        nat.check(nat.symbol(gate_up)(
+            *glu, _DT[self.dtype], _ptr(hidden), T, topk, ffn.E, shared, _ptr(topk_ids), _ptr(self.experts), self.mask1, ffn.H,
+            ffn.N, ffn.Ns, self.layout, _ptr(self.act), _ptr(self.act_shared), _ptr(self.dev_status), st))
+        nat.check(nat.symbol(down)(
+            T, topk, ffn.E, shared, _ptr(topk_ids), _ptr(self.experts), self.mask2, ffn.H, ffn.N, ffn.Ns, _ptr(self.act),
+            _ptr(self.act_shared), _ptr(self.y), _ptr(self.ys), _ptr(self.dev_status), st))
+
     def launch(self, hidden: torch.Tensor, topk_ids: Optional[torch.Tensor] = None,
                topk_weights: Optional[torch.Tensor] = None, shared_w: Optional[torch.Tensor] = None,
                stream: Optional[torch.cuda.Stream] = None) -> torch.Tensor:
@@ -1524,16 +1538,7 @@ class _DecodeBase:
                     continue
                 if t is None or t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous():
                     raise ValueError(f"{what} must be a contiguous {dt} {list(shape)} tensor")
-        shared = int(ffn.has_shared)
-        st = _stream(stream)
-        gate_up, down = self.ENTRIES
-        glu = (self._glu,) if self.TAKES_GLU else ()
-        nat.check(nat.symbol(gate_up)(
-            *glu, _DT[self.dtype], _ptr(hidden), T, topk, ffn.E, shared, _ptr(topk_ids), _ptr(self.experts), self.mask1, ffn.H,
-            ffn.N, ffn.Ns, self.layout, _ptr(self.act), _ptr(self.act_shared), _ptr(self.dev_status), st))
-        nat.check(nat.symbol(down)(
-            T, topk, ffn.E, shared, _ptr(topk_ids), _ptr(self.experts), self.mask2, ffn.H, ffn.N, ffn.Ns, _ptr(self.act),
-            _ptr(self.act_shared), _ptr(self.y), _ptr(self.ys), _ptr(self.dev_status), st))
+        self._stages(hidden, T, topk_ids, _stream(stream))
         out = self.out[:T]
         if self._glu is not None:  # in pair order the expert of slot p is ids[p]; an id outside [0, E) adds no bias
             _launch_combine(out, self.y, self.inv_slot, topk_ids.view(-1), topk_weights, self.ys, shared_w, topk, stream,
@@ -1741,6 +1746,61 @@ class DecodeForwardF8g(_DecodeBase):
                 sb.numel() != want):
             raise ValueError(f"DecodeForwardF8g: the scale buffer of a {w.q.qcfg} weight [{w.N}, {w.K}] must be a "
                              f"contiguous f32 tensor of {want} elements on the layer's device")
+
+
+class DecodeForwardF8gWide(_DecodeBase):
+    """``DecodeForwardF8g``'s layers — every expert ``w8a8_g128_sym_E4M3``, the shared one included — for calls of 1 to
+    64 tokens (DESIGN.md §4 "Decode forward: block-scaled FP8, wide"): the same constructor, ``launch`` and ``status``
+    on mxmoe_moe_decode_quant_f8g / mxmoe_moe_decode_gate_up_f8g_wide / mxmoe_moe_decode_down_f8g_wide
+    (include/mxmoe_moe.h). ``launch`` is quant -> gate_up -> quant -> down -> combine, launches only. The rows are
+    quantised once per call and stage, one wave per row, into the scratch tensors ``codes_hidden`` / ``scales_hidden``,
+    ``codes_act`` / ``scales_act`` and ``codes_act_shared`` / ``scales_act_shared`` (the ``ACT_E4M3_G128`` pass, bit
+    for bit), where every workgroup of ``DecodeForwardF8g`` quantises all of its expert's rows itself. A workgroup of
+    the tile kernel copies its expert's rows of codes through a double-buffered LDS chunk and multiplies each weight
+    fragment, loaded once, with up to four 16-row blocks: an expert's weights are streamed once per batch of up to 64
+    rows. There are no K slices, so every output is the GroupGEMM's fold word for word and ``y`` equals
+    ``MoEFFN.forward``'s rows bit for bit for the same ``act``. fp16 or bf16 ends, a ``MoEBlock``'s router, the biases
+    and ``SwigluClamp`` come with the base class; another qcfg, the SiLU-epilogue layout and T > 64 are refused.
+
+    Which form at which T (MI355X device time, tools/decode_bench.py --form f8g_wide): on qwen2_moe layer
+    11 this class takes 1.28x / 1.28x / 1.09x / 0.88x of ``DecodeForwardF8g``'s time at T = 1 / 4 / 8 / 16 and 0.45x to
+    0.55x of ``GraphForward``'s from 1 to 64; on a DeepSeek-V3-shaped layer 1.24x / 1.10x / 1.01x / 0.69x of
+    ``DecodeForwardF8g``'s and 0.81x to 0.92x of ``GraphForward``'s. Take ``DecodeForwardF8g`` below 8 tokens, this
+    class at 16, and at 17 to 64 this class over ``GraphForward``."""
+
+    MAX_T = nat.DECODE_WIDE_MAX_T
+    KINDS = DecodeForwardF8g.KINDS
+    ENTRIES = nat.DECODE_F8G_WIDE_SYMBOLS[1:]
+    TAKES_GLU = True
+    _check_layer = DecodeForwardF8g._check_layer
+    _check_scale = DecodeForwardF8g._check_scale
+
+    def __init__(self, layer, T: int, topk: Optional[int] = None, device=None, dtype: Optional[torch.dtype] = None):
+        super().__init__(layer, T, topk, device, dtype)
+        ffn, n, dev = self.ffn, T * self.topk, self.device
+
+        def scratch(rows, width):
+            return (torch.zeros(rows, width, dtype=torch.uint8, device=dev),
+                    torch.zeros(rows, width // 128, dtype=torch.float32, device=dev))
+        self.codes_hidden, self.scales_hidden = scratch(T, ffn.H)
+        self.codes_act, self.scales_act = scratch(n, ffn.N)
+        self.codes_act_shared, self.scales_act_shared = scratch(T, ffn.Ns) if ffn.has_shared else (None, None)
+
+    def _stages(self, hidden: torch.Tensor, T: int, topk_ids: torch.Tensor, st) -> None:
+        ffn, topk = self.ffn, self.topk
+        shared = int(ffn.has_shared)
+        quant, gate_up, down = (nat.symbol(fn) for fn in nat.DECODE_F8G_WIDE_SYMBOLS)
+        nat.check(quant(_DT[self.dtype], _ptr(hidden), T, ffn.H, _ptr(self.codes_hidden), _ptr(self.scales_hidden),
+                        None, 0, 0, None, None, st))
+        nat.check(gate_up(self._glu, _ptr(self.codes_hidden), _ptr(self.scales_hidden), T, topk, ffn.E, shared,
+                          _ptr(topk_ids), _ptr(self.experts), self.mask1, ffn.H, ffn.N, ffn.Ns, self.layout, _ptr(self.act),
+                          _ptr(self.act_shared), _ptr(self.dev_status), st))
+        nat.check(quant(nat.DT_FP16, _ptr(self.act), T * topk, ffn.N, _ptr(self.codes_act), _ptr(self.scales_act),
+                        _ptr(self.act_shared), T * shared, ffn.Ns, _ptr(self.codes_act_shared),
+                        _ptr(self.scales_act_shared), st))
+        nat.check(down(T, topk, ffn.E, shared, _ptr(topk_ids), _ptr(self.experts), self.mask2, ffn.H, ffn.N, ffn.Ns,
+                       _ptr(self.codes_act), _ptr(self.scales_act), _ptr(self.codes_act_shared),
+                       _ptr(self.scales_act_shared), _ptr(self.y), _ptr(self.ys), _ptr(self.dev_status), st))
 
 
 class DecodeForwardA16(_DecodeBase):

@@ -12,7 +12,7 @@ import torch
 from . import _native as nat
 from .groupgemm import W4A8_MXFP8, W4A16_MXFP4, W8A8_E4M3, W8A8_G128_E4M3, QParams
 from .harness import time_launches
-from .moe import (_BITS, DecodeForward, DecodeForwardA16, DecodeForwardEx, DecodeForwardF8g, DecodeForwardLp, DecodeForwardWo, GraphForward, MoEBlock, MoEFFN, PlannedForward, SwigluClamp, _launch_combine,
+from .moe import (_BITS, DecodeForward, DecodeForwardA16, DecodeForwardEx, DecodeForwardF8g, DecodeForwardF8gWide, DecodeForwardLp, DecodeForwardWo, GraphForward, MoEBlock, MoEFFN, PlannedForward, SwigluClamp, _launch_combine,
                   _ptr, _stream, combine_into, gate, gptoss_layer, prepare_weight_mx, silu_mul_quant)
 from .workload import (ds2_mixed_qconfig, ds2_workload, load_workload, mixed_qconfig_lp1, qwen2_layer11_workload,
                        w4a16_w8a8_qconfig)
@@ -420,14 +420,49 @@ def decode_forward_e4m3_bench(batches: Sequence[int] = (1, 4, 16), rounds: int =
                             "close_to_eager", weight_bytes)
 
 
-def decode_forward_f8g_bench(batches: Sequence[int] = (1, 4, 16), rounds: int = 4, iters: int = 30, deepseek: bool = False):
+def _wide_bench(layer: MoEFFN, call, rounds: int, iters: int, head: dict, weight_bytes) -> dict:
+    """One batch size of ``decode_forward_f8g_bench(wide=True)``: ``GraphForward``, ``DecodeForwardF8g`` (up to its 16
+    tokens) and ``DecodeForwardF8gWide`` on the same call, each captured and replayed, the sides alternating over
+    rounds: device time per side (median of the rounds' medians, min, max in µs), the wide form's ratios to the other
+    two, GraphForward's own spread, the weight bytes of the experts the ids name and the TB/s the wide graph implies.
+    Compared with the eager layer within the fp16 GroupGEMM tolerance."""
+    hidden, ids, wts = call
+    bs, topk = ids.shape
+    want = layer.forward(hidden, ids, wts).float()
+    objs = {"graph": GraphForward(layer, bs, topk), "wide": DecodeForwardF8gWide(layer, bs, topk)}
+    if bs <= DecodeForwardF8g.MAX_T:
+        objs["decode"] = DecodeForwardF8g(layer, bs, topk)
+    graphs = {k: _captured(lambda o=o: o.launch(hidden, ids, wts)) for k, o in objs.items()}
+    for gr in graphs.values():
+        gr.replay()
+    torch.cuda.synchronize()
+    tol = 1e-3 * want.abs() + 1e-3 * want.square().mean().sqrt() + 1e-6
+    out = dict(head, form="f8g_wide")
+    sides = {k + "_device": (lambda gr=gr: _device(gr.replay, iters)) for k, gr in graphs.items()}
+    out.update({k: _stat(v) for k, v in _rounds(sides, rounds).items()})
+    m = lambda k: out[k]["median_us"]
+    used = sorted(set(ids.flatten().tolist())) + ([layer.E] if layer.has_shared else [])
+    out["weight_mb"] = round((weight_bytes(layer.w1, used) + weight_bytes(layer.w2, used)) / 1e6, 2)
+    out["wide_implied_tb_s"] = round(out["weight_mb"] / m("wide_device"), 3)  # MB / µs = TB/s
+    out["wide_over_graph_device"] = round(m("wide_device") / m("graph_device"), 4)
+    if "decode" in objs:
+        out["wide_over_decode_device"] = round(m("wide_device") / m("decode_device"), 4)
+    out["graph_device_spread"] = round((out["graph_device"]["max_us"] - out["graph_device"]["min_us"]) / m("graph_device"), 4)
+    out["close_to_eager"] = {k: bool(((o.out.float() - want).abs() <= tol).all()) for k, o in objs.items()}
+    out["status"] = {k: o.status() for k, o in objs.items()}
+    return out
+
+
+def decode_forward_f8g_bench(batches: Sequence[int] = (1, 4, 16), rounds: int = 4, iters: int = 30, deepseek: bool = False,
+                             wide: bool = False):
     """qwen2_moe layer 11 with every expert w8a8_g128_sym_E4M3 (the shared one included; random weights, routing drawn
     from the committed histogram) at decode sizes, ``DecodeForwardF8g`` against ``GraphForward`` of the same layer, as
     ``decode_forward_e4m3_bench`` measures the per-channel layer (the same shapes, ids and hidden rows: the two runs
     differ by the type alone). deepseek: a DeepSeek-V3-shaped layer instead — H = 7168, N = 2048, top-8, no shared
     expert, E reduced from 256 to 16 (uniform routing) to bound the setup; the weight bytes of a call are those of
     the experts its ids name, so a decode call streams what the full layer would. Weight bytes: codes and f32 block
-    scales. Sums depend on their order: compared with the eager layer within the fp16 GroupGEMM tolerance."""
+    scales. Sums depend on their order: compared with the eager layer within the fp16 GroupGEMM tolerance. wide:
+    ``DecodeForwardF8gWide`` as a further side, at up to 64 tokens (``_wide_bench``)."""
     dev, g = "cuda", torch.Generator().manual_seed(0)
     qg = (W8A8_G128_E4M3, W8A8_G128_E4M3)
     if deepseek:
@@ -444,6 +479,9 @@ def decode_forward_f8g_bench(batches: Sequence[int] = (1, 4, 16), rounds: int = 
     for bs in batches:
         head = {"model": "deepseek-v3-shaped (E = 16 of 256)" if deepseek else "qwen2_moe", "scheme": "f8g128", "bs": bs, "E": E,
                 "topk": topk, "H": H, "N": N, "N_shared": Ns}
+        if wide:
+            yield _wide_bench(layer, _qwen2_decode_call(g, hist, bs, E, topk, H, dev), rounds, iters, head, weight_bytes)
+            continue
         yield _decode_bench(layer, DecodeForwardF8g, _qwen2_decode_call(g, hist, bs, E, topk, H, dev), rounds, iters, head,
                             "close_to_eager", weight_bytes)
 

@@ -29,8 +29,11 @@ form and GraphForward, on the layers it takes: --scheme w4a16_w8a8, --scheme fp1
 --model gpt-oss with fp16 activations. Reported with its two entries alone, its device median over the VALU form's and
 over GraphForward's, and GraphForward's own (max - min) / median over the rounds.
 
+--form f8g_wide: DecodeForwardF8gWide (block-scaled FP8 at up to 64 tokens) beside GraphForward and, up to 16 tokens,
+DecodeForwardF8g, on --scheme f8g128 and f8g128_ds: device time per side and the wide form's ratios to the other two.
+
 python tools/decode_bench.py [--model qwen2_moe|gpt-oss] [--scheme lp1|w4a16_w8a8|fp16|e4m3|f8g128|f8g128_ds] [--act-bits 16|8]
-                             [--form valu|a16] [--rounds 4] [--iters 30] [--batches 1,4,16] [--out FILE]
+                             [--form valu|a16|f8g_wide] [--rounds 4] [--iters 30] [--batches 1,4,16] [--out FILE]
 """
 from __future__ import annotations
 
@@ -54,7 +57,8 @@ def main():
     ap.add_argument("--scheme", default="lp1", choices=["lp1", "w4a16_w8a8", "fp16", "e4m3", "f8g128", "f8g128_ds"],
                     help="qwen2_moe: the layer's qconfig")
     ap.add_argument("--act-bits", type=int, default=16, choices=[16, 8], help="gpt-oss: fp16 or MXFP8 activations")
-    ap.add_argument("--form", default="valu", choices=["valu", "a16"], help="a16: DecodeForwardA16 as a further side")
+    ap.add_argument("--form", default="valu", choices=["valu", "a16", "f8g_wide"],
+                    help="a16: DecodeForwardA16 as a further side; f8g_wide: DecodeForwardF8gWide")
     args = ap.parse_args()
     if args.model == "gpt-oss" and args.scheme != "lp1":
         ap.error("--scheme belongs to --model qwen2_moe")
@@ -63,6 +67,9 @@ def main():
     a16 = args.form == "a16"
     if a16 and not (args.scheme in ("w4a16_w8a8", "fp16") or (args.model == "gpt-oss" and args.act_bits == 16)):
         ap.error("--form a16 takes --scheme w4a16_w8a8 or fp16, or --model gpt-oss with fp16 activations")
+    wide = args.form == "f8g_wide"
+    if wide and args.scheme not in ("f8g128", "f8g128_ds"):
+        ap.error("--form f8g_wide takes --scheme f8g128 or f8g128_ds")
     results = []
     wo = args.scheme != "lp1"
     kw = {"act_bits": args.act_bits} if args.model == "gpt-oss" else {}
@@ -71,8 +78,8 @@ def main():
     bench = moe_bench.decode_forward_gptoss_bench if args.model == "gpt-oss" else \
         {"lp1": moe_bench.decode_forward_bench, "w4a16_w8a8": moe_bench.decode_forward_wo_bench,
          "fp16": lambda *a, **k: moe_bench.decode_forward_wo_bench(*a, fp16=True, **k),
-         "e4m3": moe_bench.decode_forward_e4m3_bench, "f8g128": moe_bench.decode_forward_f8g_bench,
-         "f8g128_ds": lambda *a: moe_bench.decode_forward_f8g_bench(*a, deepseek=True)}[args.scheme]
+         "e4m3": moe_bench.decode_forward_e4m3_bench, "f8g128": lambda *a: moe_bench.decode_forward_f8g_bench(*a, wide=wide),
+         "f8g128_ds": lambda *a: moe_bench.decode_forward_f8g_bench(*a, deepseek=True, wide=wide)}[args.scheme]
     for r in bench([int(b) for b in args.batches.split(",") if b], args.rounds, args.iters, **kw):
         print(json.dumps(r), flush=True)
         results.append(r)
