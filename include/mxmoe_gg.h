@@ -26,6 +26,8 @@
  *          type, as the reference's `half** ptr_Cs`)
  *   w4a4_g32_sym_MXFP4 (fmt MXMOE_GG_FMT_MXFP4): A,B OCP MXFP4 (e2m1 codes, e8m0 scale per 32-K block),
  *          f32 accumulate on the block-scaled fp4 MFMA, C = fp16_rn(acc); layouts at MXMOE_GG_FMT_MXFP4
+ *   w6a6_g32_sym_MXFP6 (fmt MXMOE_GG_FMT_MXFP6): A,B OCP MXFP6 (e2m3 codes, e8m0 scale per 32-K block), f32
+ *          accumulate on the block-scaled fp6 MFMA, C = fp16_rn(acc); layouts at MXMOE_GG_FMT_MXFP6
  *
  * Data layout is byte-identical to the reference bench (SeaCatComplexes/MxMoE):
  *   - packed A/B words follow pack_wxax        (mxmoe/kernels/src/include/quantize.cuh:425-475)
@@ -74,8 +76,9 @@ enum {
   /* 3: fp6 images of int4 codes (tools-only lab library) */
   MXMOE_GG_FMT_MXFP4 = 4,   /* w4a4_g32_sym_MXFP4 and w4a16_g32_sym_MXFP4: OCP MXFP4, e2m1 codes + e8m0
                              * block scales (a_bits selects: 4 = both operands, 16 = fp16 A, weights only) */
-  MXMOE_GG_FMT_MXFP8 = 5    /* w4a8_g32_sym_MXFP8: OCP MXFP8 (e4m3) activations on MXFP4 weights; w_bits = 8
+  MXMOE_GG_FMT_MXFP8 = 5,   /* w4a8_g32_sym_MXFP8: OCP MXFP8 (e4m3) activations on MXFP4 weights; w_bits = 8
                              * under this format is reserved (a later w8a8_g32_sym_MXFP8) and UNSUPPORTED */
+  MXMOE_GG_FMT_MXFP6 = 6    /* w6a6_g32_sym_MXFP6: OCP MXFP6 with e2m3 elements, both operands */
 };
 
 /* MXFP4 operands (fmt MXMOE_GG_FMT_MXFP4; a_bits = w_bits = 4, gsize = 32, sym; K % 32 == 0).
@@ -95,6 +98,30 @@ enum {
  *           sum_{k in b} a[m][k] b[n][k]), accumulated in f32 by the block-scaled MFMA (summation order
  *           unspecified); no per-channel fp16 scales. Runs on the v2x variant only (AUTO picks it for
  *           every call that holds an MXFP4 problem); no SiLU epilogue. */
+
+/* MXFP6 operands (fmt MXMOE_GG_FMT_MXFP6; a_bits = w_bits = 6, gsize = 32, sym: w6a6_g32_sym_MXFP6; plan-info
+ * qtype_mask bit 14).
+ *   codes : OCP e2m3: bit 5 the sign, bits 4..3 the exponent (bias 1), bits 2..0 the mantissa. Magnitudes 0,
+ *           0.125 .. 0.875 (exponent 0: subnormal, m / 8), then 2^(e - 1) (1 + m / 8) = 1 .. 7.5. No Inf, no NaN.
+ *           The CANONICAL row (quant_mxfp6 / dequant_mxfp6) is uint8 [rows][3 K / 4]: each 32-element block is 24
+ *           bytes read as one little-endian 192-bit value, element j at bits [6 j, 6 j + 6) — the MFMA's per-lane
+ *           register image (lane l: row l & 15, the block K = [32 (l >> 4), +32) of each 128).
+ *           A / B take the DEVICE image of such rows (pack_mxfp6 / unpack_mxfp6; the same image for A and B,
+ *           lda / ldb in 16-bit words, 96 bytes per K = 128): per 128-element step b, at byte 96 b,
+ *             bytes [0, 64)  P: 16 bytes per block g (g < 4) = bytes 0..15 of block 4 b + g's 24,
+ *             bytes [64, 96) Q:  8 bytes per block g        = bytes 16..23 of it,
+ *           so a lane's fragment is one 16-byte and one 8-byte LDS read from swizzled images. The activation
+ *           quantisers (MXMOE_ACT_MXFP6) write this image directly.
+ *   scales: one e8m0 byte per block; canonical uint8 [rows][K/32], scale_a / scale_b in the MXFP4 DEVICE layout
+ *           above (pack_mxfp4_scales, unchanged: [rows][16 ceil(K/32 / 16)], pads 127), read as dwords: 4-byte
+ *           aligned. Dword g of group t holds block g's scales of four consecutive K = 128 steps.
+ *   limits: K % 128 == 0 (the MFMA's K; else MXMOE_GG_ERR_INVALID, checked before the row rule), N % 8 == 0,
+ *           A / B / C 16-byte aligned.
+ *   result: C[m][n] = fp16_rn(acc), acc = sum over blocks b of 2^(sa[m][b]-127) 2^(sb[n][b]-127)
+ *           sum_{k in b} a[m][k] b[n][k] in f32, in the MFMA's own order (the products of two e2m3 values are
+ *           exact in f32). A scale code 255 on either side makes the output NaN. Never split along K.
+ *   runs on: v2x only (256 / 128-row tiles; AUTO picks it for every call that holds the type; beside any other
+ *           type the call runs the kernel with every tile body). No SiLU epilogue, no small-batch (wo3) body. */
 
 /* Weight-only MXFP4 (fmt MXMOE_GG_FMT_MXFP4 with a_bits = 16, w_bits = 4, gsize = 32, sym: w4a16_g32_sym_MXFP4;
  * plan-info qtype_mask bit 11). fp16 activations on MXFP4 weights, on the fp16 MFMA.
@@ -189,7 +216,7 @@ typedef struct mxmoe_gg_plan_info {
   int32_t lds_bytes;
   int32_t qtype_mask;      /* bit q set if a planned problem has quant type q (0 fp16, 1 w8a8, 2 w4a4,
                             * 3 w4a16, 4 w8a16, 5 w4a4_g128, 6 w2a16, 7 w8a8 E4M3, 8 bf16, 10 MXFP4, 11 weight-only MXFP4,
-                            * 12 w4a8 MXFP8, 13 w8a8 g128 E4M3); bit 16:
+                            * 12 w4a8 MXFP8, 13 w8a8 g128 E4M3, 14 MXFP6); bit 16:
                             * a weight-only problem carries MXMOE_GG_EPI_SILU_MUL (small-batch kernel);
                             * selects the kernel specialisation at launch */
   int32_t splitk_slabs;    /* 256-KiB partial-sum slabs the plan's split-K tiles use (0: no split) */

@@ -64,7 +64,7 @@ enum {
                           * for such a row is kept). Through mxmoe_moe_act_quant, mxmoe_moe_gather_quant and
                           * mxmoe_moe_glu_quant with bit 8 of tag_mask only */
   /* 9 is NOT assigned */
-  MXMOE_ACT_E4M3_G128 = 10 /* per (token, 128-element group) OCP e4m3 (w8a8_g128_sym_E4M3, block-scaled FP8 checkpoints):
+  MXMOE_ACT_E4M3_G128 = 10, /* per (token, 128-element group) OCP e4m3 (w8a8_g128_sym_E4M3, block-scaled FP8 checkpoints):
                           * codes as MXMOE_ACT_E4M3's (one byte per element, pack_wxax 8-bit order), one F32 scale per
                           * (row, group), group-major: the float at byte 2 * scale_off + 4 * (g * rows + row) of the
                           * scale store (scale_off even; [width/128][rows], the GroupGEMM's scale_a). Per group, in
@@ -75,6 +75,15 @@ enum {
                           * quantize.quant_e4m3_g128 is the same rule. Through the same three entry points with bit
                           * 10 of tag_mask only (the builds that carry MXMOE_ACT_E4M3). The value 7, left free
                           * beside it, stays unassigned: masks with bit 7 keep failing as they always have. */
+  MXMOE_ACT_MXFP6 = 12,  /* OCP MXFP6, e2m3 elements (w6a6_g32_sym_MXFP6): [rows][width * 6 / 8] bytes in the GroupGEMM's
+                          * DEVICE image (include/mxmoe_gg.h, MXMOE_GG_FMT_MXFP6: 96 bytes per 128 elements), e8m0 scales
+                          * laid out as MXMOE_ACT_MXFP4's. Per 32-element block: e = floor(log2 amax) - 2 clamped to
+                          * [-127, 127], scale code e + 127 (an all-zero block: code 0), element = x * 2^-e (exact)
+                          * saturated at +-7.5 and rounded once to the e2m3 grid, ties to the even code; the sign of -0
+                          * and of values that round to 0 is kept. A block holding +-Inf or NaN: scale code 255, zero
+                          * codes. Bit for bit quantize.pack_mxfp6(quantize.quant_mxfp6(x)). Through the three entry
+                          * points that take a tag_mask, with bit 12 (the builds that carry the MX tags). Bit 11 stays
+                          * unassigned. */
 };
 
 /* One expert's segment of a permuted activation buffer. Slots (rows of the permuted batch) are
@@ -87,7 +96,7 @@ typedef struct mxmoe_moe_seg {
   int32_t width;       /* elements per row of this segment's output (K of the next GEMM)      */
   int64_t out_off;     /* byte offset of the segment's [rows][width * bits / 8] block in `out` */
   int64_t scale_off;   /* fp16-element offset of its scales: [rows] (INT8, INT4, E4M3) or [width/128][rows] (E4M3_G128: of f32, two elements each);
-                        * MXFP4 / MXFP8: of its [rows][16 ceil(width/32 / 16)] e8m0 bytes (even offset: the
+                        * MXFP4 / MXFP8 / MXFP6: of its [rows][16 ceil(width/32 / 16)] e8m0 bytes (even offset: the
                         * block is 4-byte aligned)                                              */
 } mxmoe_moe_seg;
 
@@ -235,7 +244,7 @@ int mxmoe_moe_route(const int32_t* topk_ids, int64_t T, int topk, int E, int32_t
  * shared expert), the routed segments' width and the shared one's. Written, per segment in expert order:
  *   segs[e]   {qtag, first_slot = rows before e (shared: T * topk), rows = counts[e] (shared: T), width,
  *              out_off, scale_off}: out_off advances by the segment's bytes rounded up to 16, scale_off by its
- *              scale elements ([rows] for INT8 / INT4 / E4M3, g128 [width/128][rows], MXFP4 / MXFP8 rows * 16 ceil(width/32 / 16) / 2
+ *              scale elements ([rows] for INT8 / INT4 / E4M3, g128 [width/128][rows], MXFP4 / MXFP8 / MXFP6 rows * 16 ceil(width/32 / 16) / 2
  *              after rounding scale_off up to even, fp16 none);
  *   dyn[e]    (optional, mxmoe_gg_dyn_row of include/mxmoe_gg.h: the row table of the GroupGEMM that reads the
  *              buffer) {rows, a_off = out_off, sa_off = 2 * scale_off, c_off = 2 * first_slot * ldc; shared: 0}.
@@ -269,8 +278,8 @@ int mxmoe_moe_quant_act(const void* hidden, int64_t T, int K, int topk, int with
                         const int32_t* sorted_expert, const int32_t* perm_token, const mxmoe_moe_seg* segs, int nseg,
                         void* out, void* scales, void* stream);
 
-/* mxmoe_moe_quant_act with the element type of hidden as an argument and mxmoe_moe_act_quant's tag_mask (bits 4 / 6 / 8
- * select the builds that carry MXMOE_ACT_MXFP4 / MXMOE_ACT_MXFP8 / MXMOE_ACT_E4M3; an unknown bit:
+/* mxmoe_moe_quant_act with the element type of hidden as an argument and mxmoe_moe_act_quant's tag_mask (bits 4 / 6 / 8 / 12
+ * select the builds that carry MXMOE_ACT_MXFP4 / MXMOE_ACT_MXFP8 / MXMOE_ACT_E4M3 / MXMOE_ACT_MXFP6; an unknown bit:
  * MXMOE_GG_ERR_UNSUPPORTED).
  * Replaces: nothing in the reference (fp16 only).
  *   dtype    MXMOE_DT_FP16: mxmoe_moe_quant_act's (mxmoe_moe_act_quant mode 0's) kernels and bytes.
@@ -318,7 +327,8 @@ int mxmoe_moe_quant_slots(const void* routed_in, const void* shared_in, int64_t 
  * entry points (and any call here without the bit) keep the builds they had before the tag existed
  * and must not be given such a segment — they would treat it as int4. MXMOE_ACT_MXFP8 segments
  * likewise need bit 6, MXMOE_ACT_E4M3 segments bit 8 (builds of their own, which carry the MX tags too: a call may
- * set bit 8 together with bit 4 or 6, a mixed layer). MXMOE_ACT_E4M3_G128 segments need bit 10 (the same builds). A mask with bit 5, 7, 9 or a bit above 10 is MXMOE_GG_ERR_UNSUPPORTED.
+ * set bit 8 together with bit 4 or 6, a mixed layer). MXMOE_ACT_E4M3_G128 segments need bit 10 (the same builds), MXMOE_ACT_MXFP6
+ * segments bit 12 (the MX builds). A mask with bit 5, 7, 9, 11 or a bit above 12 is MXMOE_GG_ERR_UNSUPPORTED.
  *   mode 0: mxmoe_moe_quant_act      (routed_in = hidden [T][N], N = K; shared_in != NULL <=> with_shared,
  *                                     its value is ignored; perm_token required)
  *   mode 1: mxmoe_moe_silu_mul_quant, 2: mxmoe_moe_quant_slots, 3: mxmoe_moe_silu_mul_quant_il

@@ -29,6 +29,7 @@ MXMOE_GG_ERR_HIP = 4
 FMT_DEFAULT, FMT_E4M3, FMT_BF16, FMT_F6 = 0, 1, 2, 3
 FMT_MXFP4 = 4  # MXMOE_GG_FMT_MXFP4: w4a4_g32_sym_MXFP4 (OCP e2m1 codes, e8m0 scale per 32-K block)
 FMT_MXFP8 = 5  # MXMOE_GG_FMT_MXFP8: w4a8_g32_sym_MXFP8 (OCP e4m3 activation codes on MXFP4 weights)
+FMT_MXFP6 = 6  # MXMOE_GG_FMT_MXFP6: w6a6_g32_sym_MXFP6 (OCP e2m3 codes in the fp6 device image, e8m0 block scales)
 EPI_SILU_MUL = 0x100  # MXMOE_GG_EPI_SILU_MUL: fmt flag, C = silu(gate) * up (include/mxmoe_gg.h)
 
 

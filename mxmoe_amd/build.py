@@ -19,7 +19,7 @@ ARCH = os.environ.get("MXMOE_OFFLOAD_ARCH", "gfx950")
 # gg_api.hip stays first (tests/test_codegen.py compiles SOURCES[0] for the device ISA); gg_plan.cpp is the
 # host-only tile planner, compiled by the same hipcc and flags as the rest
 SOURCES = [CSRC / "gg_api.hip", CSRC / "moe_ops.hip", CSRC / "gg_plan.cpp", CSRC / "gg_f8g128.hip",
-           CSRC / "gg_f8g128_small.hip"]
+           CSRC / "gg_f8g128_small.hip", CSRC / "gg_mxf6.hip"]
 # per-source device flags: the block-scaled FP8 builds keep their f32 arithmetic unpacked
 _NO_PACKED_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 SOURCE_FLAGS = {"gg_f8g128.hip": _NO_PACKED_F32, "gg_f8g128_small.hip": _NO_PACKED_F32}

@@ -140,7 +140,8 @@ constexpr Builds<sizeof...(QM)> v2_rows(bool fallback = false) {
 // plan info still reports the variant's LDS image); the 2-bit weight-only body only joins when the mix has
 // one (it costs 12 B of prologue spill there, tests/test_codegen.py), the MX bodies likewise — builds apart
 // from the narrower ones, which come out unchanged. The two builds with the w8a8_g128_sym_E4M3 body (the exact one
-// and one more widest fallback) are compiled in gg_f8g128.hip, for the product variant's flags only.
+// and one more widest fallback) are compiled in gg_f8g128.hip, for the product variant's flags only; the exact
+// w6a6_g32_sym_MXFP6 build in gg_mxf6.hip (its mixes run that widest fallback).
 // (lab builds: fp16, w8a8, w4a4, w8a8 + w4a4, w4a16, E4M3, bf16 only; fast: fp16, w8a8, w4a16)
 template <int ABL>
 constexpr Builds<1> f8g_row(bool fallback) {
@@ -149,13 +150,18 @@ constexpr Builds<1> f8g_row(bool fallback) {
   return {{Build{kF8G, false, kV2Lds<ABL>, &launch_v2x_f8g}}};
 }
 template <int ABL>
+constexpr Builds<1> mxf6_row() {
+  static_assert(ABL == kV2xProduct, "gg_mxf6.hip compiles the product variant's build only");
+  return {{Build{kMx6, false, kV2Lds<ABL>, &launch_v2x_mxf6}}};
+}
+template <int ABL>
 constexpr auto kV2Builds =
 #if defined(MXMOE_LAB) && defined(MXMOE_LAB_FAST)
     v2_rows<ABL, kV2Lds<ABL>, 1, 2, 8>();
 #elif defined(MXMOE_LAB)
     v2_rows<ABL, kV2Lds<ABL>, 1, 2, 4, 6, 8, 128, 256>();
 #else
-    v2_rows<ABL, kV2Lds<ABL>, 1, 2, 4, 6, 7, 8, 10, 16, 32, 64, 128, 256, kMx4, kMxW, kMx8>() + f8g_row<ABL>(false) +
+    v2_rows<ABL, kV2Lds<ABL>, 1, 2, 4, 6, 7, 8, 10, 16, 32, 64, 128, 256, kMx4, kMxW, kMx8>() + f8g_row<ABL>(false) + mxf6_row<ABL>() +
     v2_rows<0, kV2Lds<ABL>, 63, 127, 511, 511 | kMx4, 511 | kMx4 | kMxW, 511 | kMx4 | kMxW | kMx8>(true) + f8g_row<ABL>(true);
 #endif
 // timing ablations: int8 tiles only (kAblMask) / w4a16 tiles only (kWoAblMask), whatever the call holds
@@ -171,9 +177,9 @@ constexpr int pick_v2(int qmask) {
 #ifdef MXMOE_LAB
   return pick_build(v2_builds<ABL>(), qmask & 511);
 #else
-  // (all 14 type bits beside an MX type or the block-scaled E4M3 one, the low 9 otherwise: the only other bit is
+  // (all 15 type bits beside an MX type or the block-scaled E4M3 one, the low 9 otherwise: the only other bit is
   // the lab's fp6 type, which no product variant plans)
-  return pick_build(v2_builds<ABL>(), qmask & ((qmask & (kMx4 | kMxW | kMx8 | kF8G)) ? 16383 : 511));
+  return pick_build(v2_builds<ABL>(), qmask & ((qmask & (kMx4 | kMxW | kMx8 | kF8G | kMx6)) ? 32767 : 511));
 #endif
 }
 #ifndef MXMOE_LAB
@@ -187,7 +193,8 @@ static_assert(v2x_picked(kMx4 | (1 << QT_F16)).qmask == (511 | kMx4) && v2x_pick
 static_assert(v2x_picked(kMxW | (1 << QT_I8)).qmask == (511 | kMx4 | kMxW));
 static_assert(v2x_picked(kMx8 | (1 << QT_W4A16)).qmask == (511 | kMx4 | kMxW | kMx8) && v2x_picked(kMx8 | kMx4).qmask == v2x_picked(8191).qmask);
 static_assert(v2x_picked(kF8G).launch == &launch_v2x_f8g && v2x_picked(kV2Widest).launch == &launch_v2_widest && v2x_picked(kF8G | kMx4).qmask == kV2Widest);
-static_assert(v2x_picked(kF8G | (1 << QT_F16) | (1 << QT_I8)).qmask == kV2Widest && v2x_picked(8191).qmask == (kV2Widest & ~kF8G));
+static_assert(v2x_picked(kF8G | (1 << QT_F16) | (1 << QT_I8)).qmask == kV2Widest && v2x_picked(8191).qmask == (kV2Widest & ~(kF8G | kMx6)));
+static_assert(v2x_picked(kMx6).launch == &launch_v2x_mxf6 && v2x_picked(kMx6 | (1 << QT_F16)).qmask == kV2Widest && v2x_picked(kMx6 | kF8G).qmask == kV2Widest);
 #endif
 
 static_assert(V2Cfg<256>::BM == 256 && V2Cfg<256>::BN == 256 && V2Cfg<256>::BKB == 128 && V2Cfg<256>::NT == 512,

@@ -1,6 +1,6 @@
 // gg_builds.h — what the library's kernel translation units share: the product variant's mainloop flags, and the
 // launchers of the kernels compiled outside gg_api.hip (gg_f8g128.hip, gg_f8g128_small.hip: the builds with the
-// w8a8_g128_sym_E4M3 bodies).
+// w8a8_g128_sym_E4M3 bodies; gg_mxf6.hip: the exact w6a6_g32_sym_MXFP6 build).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -22,7 +22,8 @@ constexpr int kWo3 = WO_SCLATE | WO_ANDOR | WO_MSKIP | WO_SPLIT | WO_NIBPOS;
 [[maybe_unused]] constexpr int kMxW = 1 << QT_MXF4W;  // weight-only MXFP4
 [[maybe_unused]] constexpr int kMx8 = 1 << QT_MXF8A;  // w4a8_g32_sym_MXFP8 (gg_tile_v2's 64 x 128 body)
 [[maybe_unused]] constexpr int kF8G = 1 << QT_F8G;    // w8a8_g128_sym_E4M3 (gg_tile_f8g128; wo3 alone: gg_tile_f8g128s)
-constexpr int kV2Widest = 511 | kMx4 | kMxW | kMx8 | kF8G;  // every tile body of gg_v2_kernel
+[[maybe_unused]] constexpr int kMx6 = 1 << QT_MXF6;   // w6a6_g32_sym_MXFP6 (gg_tile_mxf6, gg_mxf6.h)
+constexpr int kV2Widest = 511 | kMx4 | kMxW | kMx8 | kF8G | kMx6;  // every tile body of gg_v2_kernel
 
 #pragma GCC visibility push(hidden)
 // gg_f8g128.hip (product library): gg_v2_kernel<kV2xProduct, kF8G> and gg_v2_kernel<0, kV2Widest>
@@ -30,6 +31,8 @@ void launch_v2x_f8g(const GGArgs& a, int grid, hipStream_t s);
 void launch_v2_widest(const GGArgs& a, int grid, hipStream_t s);
 // gg_f8g128_small.hip (product library): gg_wo2_kernel<kWo3Product, kF8G, 3>
 void launch_wo3_f8g(const GGArgs& a, int grid, hipStream_t s);
+// gg_mxf6.hip (product library): gg_v2_kernel<kV2xProduct, kMx6>
+void launch_v2x_mxf6(const GGArgs& a, int grid, hipStream_t s);
 #pragma GCC visibility pop
 
 }  // namespace mxmoe

@@ -3427,6 +3427,10 @@ __device__ __forceinline__ void gg_tile_wo(const GGMeta& mt, const uint8_t* __re
   epilogue_v3<Cfg, QT_F16, (WABL & WO_SILU) != 0>(mt, acc, nullptr, nullptr, C, m0, n0, lds);
 }
 
+}  // namespace mxmoe
+#include "gg_mxf6.h"  // gg_tile_mxf6: the w6a6_g32_sym_MXFP6 tile body
+namespace mxmoe {
+
 template <int ABL, int QM>  // QM: quant types compiled in (bit 1 << QType), as gg_v3_kernel
 __global__ __launch_bounds__(512, 2) void gg_v2_kernel(GGArgs args) {
   // + the int paths' scale stash: SA at [LDS_BYTES, +2*BM), SB at [LDS_BYTES + 512, +512)
@@ -3512,6 +3516,11 @@ __global__ __launch_bounds__(512, 2) void gg_v2_kernel(GGArgs args) {
     const float* SBf = static_cast<const float*>(args.ptr_SB[td.prob]);
     if (cls == 0) gg_tile_f8g128<V2Cfg<256>>(mt, A, B, SAf, SBf, C, td.m0, td.n0, lds);
     else gg_tile_f8g128<V2Cfg<128>>(mt, A, B, SAf, SBf, C, td.m0, td.n0, lds);  // no 64-row class
+  } else if ((QM & (1 << QT_MXF6)) && mt.qtype == QT_MXF6) {
+    const uint8_t* SA8 = static_cast<const uint8_t*>(args.ptr_SA[td.prob]);
+    const uint8_t* SB8 = static_cast<const uint8_t*>(args.ptr_SB[td.prob]);
+    if (cls == 0) gg_tile_mxf6<V2Cfg<256>>(mt, A, B, SA8, SB8, C, td.m0, td.n0, lds);
+    else gg_tile_mxf6<V2Cfg<128>>(mt, A, B, SA8, SB8, C, td.m0, td.n0, lds);  // no 64-row class
   }
   if constexpr ((ABL & V2_TRACE) != 0) {
     if (threadIdx.x == 0 && blockIdx.x < kTraceBlocks) {

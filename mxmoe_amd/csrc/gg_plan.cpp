@@ -81,6 +81,11 @@ int qtype_of(int a_bits, int w_bits, int gsize, int sym, int fmt, int* qt) {
                 w_bits, a_bits, gsize, sym ? "sym" : "asym");
   }
 #endif
+  if (fmt == MXMOE_GG_FMT_MXFP6) {  // OCP MXFP6: e2m3 codes, one e8m0 scale per 32-K block
+    if (a_bits == 6 && w_bits == 6 && gsize == 32 && sym) return take(QT_MXF6);
+    return fail(MXMOE_GG_ERR_UNSUPPORTED, "quant type not supported: w%da%d_g%d_%s_MXFP6 (only w6a6_g32_sym_MXFP6)", w_bits,
+                a_bits, gsize, sym ? "sym" : "asym");
+  }
   if (fmt != MXMOE_GG_FMT_DEFAULT) return fail(MXMOE_GG_ERR_UNSUPPORTED, "unknown operand format %d", fmt);
   if (a_bits == 16 && w_bits == 16) return take(QT_F16);
   if (a_bits == 8 && w_bits == 8 && gsize == -1 && sym) return take(QT_I8);
@@ -322,12 +327,12 @@ std::vector<int> split_factors(const PlanVariant& v, const std::vector<GGMeta>& 
   const double share = total / (kSplitCUs * v.chunk / 32);  // workgroup slots: CUs x workgroups per CU
   for (int i : order) {
     const double ratio = o.split_ratio_mul * biggest[i] / std::max(share, 1.0);
-    if (ratio > 2.0 && !qinfo(all[i].qtype).group_fold)
+    if (ratio > 2.0 && !qinfo(all[i].qtype).whole_k)
       split[i] = std::max(1, std::min({8, (int)ratio, stages_of(v, all[i]) / 4}));
   }
   if (o.splitk_all > 1)
     for (int i : order)
-      if (!qinfo(all[i].qtype).group_fold)
+      if (!qinfo(all[i].qtype).whole_k)
         split[i] = std::max(split[i], std::max(1, std::min({8, o.splitk_all, stages_of(v, all[i]) / 4})));
   return split;
 }
@@ -726,7 +731,7 @@ void split_tails(const PlanVariant& v, const TileTimer& tile_time, int mode, int
   auto splittable = [&](const TileDesc& td) {
     const QTypeInfo& t = qinfo(plan->meta[td.prob].qtype);
     // (mode 2: weight-only tiles too — the small-batch wo3 calls run ~1.3 rounds of equal tiles)
-    return ((td.cls >> 16) & 0xFF) <= 1 && (!t.weight_only || mode == 2) && !t.group_fold && td.ks1 - td.ks0 >= 6;
+    return ((td.cls >> 16) & 0xFF) <= 1 && (!t.weight_only || mode == 2) && !t.whole_k && td.ks1 - td.ks0 >= 6;
   };
   for (int x = 0; x < 8; ++x) {
     std::vector<int>& q = xq->queue[x];

@@ -86,40 +86,44 @@ struct QTypeInfo {
   double auto_rows;          // WeightOnly / Small: the mean-M limit of the small-batch kernel
   const char* auto_alone;    // the variant AUTO takes for a call of this type only (Small: unless it splits K)
   bool auto_counts_empty;    // an empty problem still counts for AUTO (only v2x plans the type; types are checked before shapes)
+  bool whole_k;              // its tiles always run all of K: a group fold (f32 partial folds would change the rounding), or a
+                             // result defined in the MFMA's own order (MXFP6)
 };
 constexpr AutoClass kGen = AutoClass::General, kWo = AutoClass::WeightOnly, kSm = AutoClass::Small;
 constexpr QTypeInfo kQTypes[] = {
-    // qt, name, bits | wo, f16 | dword scales | K rule | fold, i32, silu, 64-row | passes, el, rate, fold, code | AUTO
+    // qt, name, bits | wo, f16 | dword scales | K rule | fold, i32, silu, 64-row | passes, el, rate, fold, code | AUTO | whole K
     {QT_F16, "fp16", 16, false, true, nullptr, 0, nullptr, false, false, false, true, true,
-     1.0, 16, 128, 1.0, 0, kSm, kSmallMeanRows, nullptr, false},
+     1.0, 16, 128, 1.0, 0, kSm, kSmallMeanRows, nullptr, false, false},
     {QT_I8, "w8a8_g-1_sym", 8, false, false, nullptr, 0, nullptr, false, false, true, true, false,
-     1.0, 8, 256, 1.0, 0, kSm, kSmallMeanRows, nullptr, false},
+     1.0, 8, 256, 1.0, 0, kSm, kSmallMeanRows, nullptr, false, false},
     {QT_I4, "w4a4_g-1_sym", 4, false, false, nullptr, 0, nullptr, false, false, true, true, false,
-     2.0, 4, 256, 1.0, 0, kSm, kSmallMeanRowsI4, kInt4Variant, false},
+     2.0, 4, 256, 1.0, 0, kSm, kSmallMeanRowsI4, kInt4Variant, false, false},
     {QT_W4A16, "w4a16", 4, true, false, nullptr, 0, nullptr, false, false, false, true, true,
-     1.0, 0, 0, 1.0, 4, kWo, kWoSmallMeanRows, nullptr, false},
+     1.0, 0, 0, 1.0, 4, kWo, kWoSmallMeanRows, nullptr, false, false},
     {QT_W8A16, "w8a16", 8, true, false, nullptr, 0, nullptr, false, false, false, true, true,
-     1.0, 0, 0, 1.0, 8, kWo, kWoSmallMeanRows, nullptr, false},
+     1.0, 0, 0, 1.0, 8, kWo, kWoSmallMeanRows, nullptr, false, false},
     {QT_I4G, "w4a4_g128_sym", 4, false, false, nullptr, 128, "w4a4_g128", false, true, true, false, false,
-     2.5, 4, 256, 1.25, 0, kGen, 0, nullptr, false},
+     2.5, 4, 256, 1.25, 0, kGen, 0, nullptr, false, true},
     {QT_W2A16, "w2a16", 2, true, false, nullptr, 0, nullptr, false, false, false, true, true,
-     1.0, 0, 0, 1.0, 2, kWo, kWoSmallMeanRows, nullptr, false},
+     1.0, 0, 0, 1.0, 2, kWo, kWoSmallMeanRows, nullptr, false, false},
     {QT_F8, "w8a8_g-1_sym_E4M3", 8, false, false, nullptr, 0, nullptr, false, false, false, false, false,
-     1.0, 8, 256, 1.0, 0, kGen, 0, nullptr, false},
+     1.0, 8, 256, 1.0, 0, kGen, 0, nullptr, false, false},
     {QT_BF16, "bf16", 16, false, true, nullptr, 0, nullptr, false, false, false, false, true,
-     1.0, 16, 128, 1.0, 0, kGen, 0, nullptr, false},
+     1.0, 16, 128, 1.0, 0, kGen, 0, nullptr, false, false},
     {QT_I4F6, "w4a4_g-1_sym_F6", 6, false, false, nullptr, 0, nullptr, false, false, true, false, false,
-     128.0 / 96 / 2, 0, 512, 1.0, 0, AutoClass::Alone, 0, kF6Variant, false},
+     128.0 / 96 / 2, 0, 512, 1.0, 0, AutoClass::Alone, 0, kF6Variant, false, false},
     {QT_MXF4, "w4a4_g32_sym_MXFP4", 4, false, false, "MXFP4", 0, nullptr, false, false, false, false, false,
-     1.0, 4, 512, 1.0, 0, kGen, 0, nullptr, true},
+     1.0, 4, 512, 1.0, 0, kGen, 0, nullptr, true, false},
     {QT_MXF4W, "w4a16_g32_sym_MXFP4", 4, true, false, "MXFP4", 0, nullptr, false, false, false, true, true,
-     1.0, 0, 0, 1.0, 4, kWo, kWoSmallMeanRows, nullptr, false},
+     1.0, 0, 0, 1.0, 4, kWo, kWoSmallMeanRows, nullptr, false, false},
     {QT_MXF8A, "w4a8_g32_sym_MXFP8", 8, false, false, "w4a8_g32_sym_MXFP8", 32, "w4a8_g32_sym_MXFP8", true, false,
-     false, true, false, 1.0, 8, 256, 1.0, 0, kSm, kSmallMeanRowsMx8, nullptr, false},
+     false, true, false, 1.0, 8, 256, 1.0, 0, kSm, kSmallMeanRowsMx8, nullptr, false, false},
     {QT_F8G, "w8a8_g128_sym_E4M3", 8, false, false, "w8a8_g128_sym_E4M3", 128, "w8a8_g128_sym_E4M3", false, true, false,
-     false, false, 1.0, 8, 256, 1.1, 0, AutoClass::SmallAlone, kSmallMeanRowsF8G, nullptr, true},
+     false, false, 1.0, 8, 256, 1.1, 0, AutoClass::SmallAlone, kSmallMeanRowsF8G, nullptr, true, true},
     // (fold: 1.06-1.09x per-channel E4M3's time, profiles/r23/f8g128; no 64-row class in gg_v2_kernel — the small-batch
     // kernel's 64 x 128 tile is its main tile, not a class)
+    {QT_MXF6, "w6a6_g32_sym_MXFP6", 6, false, false, "MXFP6", 128, "w6a6_g32_sym_MXFP6", true, false, false,
+     false, false, 128.0 / 96 / 2, 0, 512, 1.0, 0, kGen, 0, nullptr, true, true},
 };
 constexpr bool qtypes_in_order() {
   for (int i = 0; i < QT_COUNT; ++i)
@@ -196,6 +200,7 @@ inline PlanVariant plan_v2(bool mx) {
     v.geom[QT_MXF4] = v.geom[QT_MXF8A] = {256, 256, 128, 512};
     v.geom[QT_MXF4W] = {256, 256, 32, 512};  // weight-only MXFP4: the 4-bit stage
     v.geom[QT_F8G] = {256, 256, 128, 512};   // w8a8_g128_sym_E4M3 (gg_tile_f8g128): one 128-K group per stage
+    v.geom[QT_MXF6] = {256, 256, 96, 512};   // w6a6_g32_sym_MXFP6 (gg_tile_mxf6): 96 B of fp6 image per K = 128 stage
   }
   v.silu_epi = true;  // gg_tile_v2's epilogue
   return v;

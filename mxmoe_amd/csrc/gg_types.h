@@ -19,10 +19,12 @@ namespace mxmoe {
 //           block-scaled MFMA with one format per operand, f32 accumulate, C = fp16_rn(acc))
 // QT_F8G: w8a8_g128_sym_E4M3 (A and B OCP fp8 e4m3; f32 scales, A's one per row and 128-K group, B's one per
 //         128 x 128 block; each group's f32 MFMA sum folded into an f32 accumulator, gg_tile_f8g128)
+// QT_MXF6: w6a6_g32_sym_MXFP6 (A and B OCP MXFP6: e2m3 codes in the fp6 device image, one e8m0 scale per 32-K
+//          block; the block-scaled fp6 MFMA applies the scales, f32 accumulate, C = fp16_rn(acc); gg_mxf6.h)
 enum QType : int32_t {
   QT_F16 = 0, QT_I8 = 1, QT_I4 = 2, QT_W4A16 = 3, QT_W8A16 = 4, QT_I4G = 5, QT_W2A16 = 6, QT_F8 = 7, QT_BF16 = 8,
-  QT_I4F6 = 9, QT_MXF4 = 10, QT_MXF4W = 11, QT_MXF8A = 12, QT_F8G = 13,
-  QT_COUNT = 14
+  QT_I4F6 = 9, QT_MXF4 = 10, QT_MXF4W = 11, QT_MXF8A = 12, QT_F8G = 13, QT_MXF6 = 14,
+  QT_COUNT = 15
 };
 // quant types whose epilogue applies the per-channel scales sa[m] * sb[n]
 constexpr bool qt_scaled(int qt) { return qt == QT_I8 || qt == QT_I4 || qt == QT_F8 || qt == QT_I4F6; }

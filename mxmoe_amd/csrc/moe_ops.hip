@@ -357,7 +357,7 @@ __device__ __forceinline__ uint2 codes_e4m3(const h8_t& x, float s, float r) {
 // GroupGEMM's fused SiLU epilogue, routed [T*topk][N], shared [T][Ns]); 3: silu_mul_quant on a
 // gate_up output whose gate / up columns alternate in 16-column blocks (the interleaved weights of
 // the fused epilogue, run through the plain epilogue: small-batch calls on wo3)
-// MX: the build that also carries the MXMOE_ACT_MXFP4 and MXMOE_ACT_MXFP8 tags (launched only for calls whose segments hold
+// MX: the build that also carries the MXMOE_ACT_MXFP4, MXMOE_ACT_MXFP8 and MXMOE_ACT_MXFP6 tags (launched only for calls whose segments hold
 // one, mxmoe_moe_act_quant: the other tags' builds stay as they are without it)
 // GLU (MODE 1 only; mxmoe_moe_glu_quant): kGluSilu / kGluSwigluClamp builds take GluArgs, add the expert's bias
 // row to the gate and up values as they are read (one f32 add each; a NULL bias: no add) and apply the named
@@ -544,6 +544,51 @@ __global__ __launch_bounds__(kThreads) void act_quant_kernel(typename ActArgsOf<
       q1 = __builtin_amdgcn_cvt_pk_fp8_f32(y[4], y[5], q1, false);
       q1 = __builtin_amdgcn_cvt_pk_fp8_f32(y[6], y[7], q1, true);
       *reinterpret_cast<uint2*>(o8 + idx) = bad ? uint2{0u, 0u} : uint2{(uint32_t)q0, (uint32_t)q1};
+      if ((lane & 3) == 0) mx_store_scale(so, (col0 + idx) >> 5, nblk, bad, e);
+    }
+    return;
+  }
+  if constexpr (MX) if (sg.qtag == MXMOE_ACT_MXFP6) {
+    // OCP MXFP6, e2m3 elements (include/mxmoe_gg.h, w6a6_g32_sym_MXFP6): blocks, amax and scale bytes as the MXFP4
+    // tag's (e2m3's largest binade is e2m1's: e = floor(log2 amax) - 2); elements scaled by 2^-e exactly, saturated
+    // at 7.5 and rounded once to the grid with v_rndne: steps of 1/8 below 2 (the subnormals and the first binade
+    // share a step), 1/4 below 4, 1/2 up to 7.5, and the code is the step count from its segment's start — an even
+    // multiple of the step is an even code in each. Written straight into the GroupGEMM's device image: per
+    // K = 128 step 96 B, block g's first 16 B at 16 g, its last 8 at 64 + 8 g. A lane's 8 codes are 48 bits of its
+    // block's 192; lane pairs merge theirs into three dwords, the block's first lane stores dwords 0-3, its third
+    // lane dwords 4-5.
+    const int srow = ((sg.width / 32 + 15) >> 4) << 4;  // scale bytes per row (device layout)
+    uint8_t* const o6 = a.out + sg.out_off + row * (int64_t)(sg.width / 4 * 3) + (col0 >> 7) * 96;
+    uint8_t* const so = reinterpret_cast<uint8_t*>(a.scales + sg.scale_off) + row * (int64_t)srow;
+    const int nblk = sg.width / 32;
+#pragma unroll
+    for (int c = 0; c < MAXC; ++c) {
+      if (c * 512 >= width) break;  // uniform
+      const int idx = c * 512 + lane * 8;
+      const uint32_t m2 = mx_block_amax(x[c]);
+      const bool bad = m2 >= 0x7C00u;  // an Inf or a NaN in the block: NaN scale, zero codes
+      float inv;
+      const int e = mx_exponent<2>(m2, inv);
+      uint32_t lo = 0, hi = 0;  // codes 0-4 and the low 2 bits of code 5 | the rest of code 5, codes 6-7
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const float y = (float)x[c][j] * inv;  // exact
+        const float ay = fminf(fabsf(y), 7.5f);
+        const float r = ay < 2.0f ? __builtin_rintf(ay * 8.0f)
+                      : ay < 4.0f ? 8.0f + __builtin_rintf(ay * 4.0f) : 16.0f + __builtin_rintf(ay * 2.0f);
+        const uint32_t code = bad ? 0u : (uint32_t)r | ((__builtin_bit_cast(uint32_t, y) >> 26) & 32u);
+        if (6 * j < 32) lo |= code << (6 * j);
+        if (6 * j + 6 > 32) hi |= 6 * j >= 32 ? code << (6 * j - 32) : code >> (32 - 6 * j);
+      }
+      // pair (p, p + 1) of the block's lanes: v_p | v_{p+1} << 48 = dwords t0 t1 t2 on the even lane
+      const uint32_t plo = (uint32_t)__shfl_xor((int)lo, 1, 64), phi = (uint32_t)__shfl_xor((int)hi, 1, 64);
+      const uint32_t t0 = lo, t1 = hi | (plo << 16), t2 = (plo >> 16) | (phi << 16);
+      const uint32_t d3 = (uint32_t)__shfl_xor((int)t0, 2, 64);  // (the block's first lane: its third lane's t0)
+      if (idx >= width) continue;
+      uint8_t* const ob = o6 + (idx >> 7) * 96;
+      const int gblk = (lane >> 2) & 3;
+      if ((lane & 3) == 0) *reinterpret_cast<uint4*>(ob + gblk * 16) = uint4{t0, t1, t2, d3};
+      if ((lane & 3) == 2) *reinterpret_cast<uint2*>(ob + 64 + gblk * 8) = uint2{t1, t2};
       if ((lane & 3) == 0) mx_store_scale(so, (col0 + idx) >> 5, nblk, bad, e);
     }
     return;
@@ -748,7 +793,8 @@ bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 // of the returned status.
 __host__ __device__ inline int act_bits(int tag) {
   return tag == MXMOE_ACT_INT8 || tag == MXMOE_ACT_MXFP8 || tag == MXMOE_ACT_E4M3 || tag == MXMOE_ACT_E4M3_G128 ? 8
-         : tag == MXMOE_ACT_INT4 || tag == MXMOE_ACT_INT4_G128 || tag == MXMOE_ACT_MXFP4 ? 4 : 16;
+         : tag == MXMOE_ACT_INT4 || tag == MXMOE_ACT_INT4_G128 || tag == MXMOE_ACT_MXFP4 ? 4
+         : tag == MXMOE_ACT_MXFP6 ? 6 : 16;
 }
 __host__ __device__ inline int32_t fill_segments(const int32_t* counts, int E, int64_t T, int topk, bool with_shared,
                                                  const mxmoe_moe_seg_table& tb) {
@@ -764,7 +810,7 @@ __host__ __device__ inline int32_t fill_segments(const int32_t* counts, int E, i
       r = r < 0 ? 0 : ntk - first;
     }
     const int tag = tb.qtags[e], w = shared ? tb.width_shared : tb.width;
-    const bool mx = tag == MXMOE_ACT_MXFP4 || tag == MXMOE_ACT_MXFP8;
+    const bool mx = tag == MXMOE_ACT_MXFP4 || tag == MXMOE_ACT_MXFP8 || tag == MXMOE_ACT_MXFP6;
     const bool f32g = tag == MXMOE_ACT_E4M3_G128;  // f32 group scales: two fp16 elements each
     if (mx || f32g) soff += soff & 1;  // its scales are read as dwords: a 4-byte aligned block
     const int64_t f = shared ? ntk : first;
@@ -857,7 +903,7 @@ static void launch_act_w(const typename ActArgsOf<GLU>::type& a, int maxw, hipSt
 constexpr int kModeGatherBf16 = 4;  // launch_act_any's number for mode 0 on bf16 rows (no mode of the C interface)
 // The tags a call's tag_mask names beyond the integer ones: which builds of the kernel run it
 struct ActTags {
-  bool mx = false;  // MXMOE_ACT_MXFP4 or MXMOE_ACT_MXFP8 (the MX builds)
+  bool mx = false;  // MXMOE_ACT_MXFP4, MXMOE_ACT_MXFP8 or MXMOE_ACT_MXFP6 (the MX builds)
   bool f8 = false;  // MXMOE_ACT_E4M3 (the kActF8 builds, which carry the MX tags as well)
 };
 // (mode, tags): which build of the kernel; ActArgs: the four passes, GluArgs: mxmoe_moe_glu_quant's (mode = MXMOE_GLU_*)
@@ -948,9 +994,10 @@ static int slots_impl(const char* fn, int mode, const void* routed_in, const voi
 // a tag_mask's check (MXMOE_GG_OK or the failure, under the entry point's name) and which builds' tags it names
 static int tag_mask_tags(const char* fn, uint32_t tag_mask, ActTags* tags) {
   // (tags 5, 7 and 9 are not assigned)
-  if (tag_mask & ~((2u << MXMOE_ACT_MXFP4) - 1u | 1u << MXMOE_ACT_MXFP8 | 1u << MXMOE_ACT_E4M3 | 1u << MXMOE_ACT_E4M3_G128))
+  if (tag_mask & ~((2u << MXMOE_ACT_MXFP4) - 1u | 1u << MXMOE_ACT_MXFP8 | 1u << MXMOE_ACT_E4M3 | 1u << MXMOE_ACT_E4M3_G128 |
+                   1u << MXMOE_ACT_MXFP6))
     return fail(MXMOE_GG_ERR_UNSUPPORTED, "%s: unknown activation tag in mask %#x", fn, tag_mask);
-  tags->mx = ((tag_mask >> MXMOE_ACT_MXFP4) & 1) || ((tag_mask >> MXMOE_ACT_MXFP8) & 1);
+  tags->mx = ((tag_mask >> MXMOE_ACT_MXFP4) & 1) || ((tag_mask >> MXMOE_ACT_MXFP8) & 1) || ((tag_mask >> MXMOE_ACT_MXFP6) & 1);
   tags->f8 = ((tag_mask >> MXMOE_ACT_E4M3) & 1) || ((tag_mask >> MXMOE_ACT_E4M3_G128) & 1);  // (both in the kActF8 builds)
   return MXMOE_GG_OK;
 }

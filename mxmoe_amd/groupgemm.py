@@ -25,7 +25,7 @@ from . import _native as nat
 
 
 FMT_CODES = {"": nat.FMT_DEFAULT, "E4M3": nat.FMT_E4M3, "bf16": nat.FMT_BF16, "F6": nat.FMT_F6,
-             "MXFP4": nat.FMT_MXFP4, "MXFP8": nat.FMT_MXFP8}
+             "MXFP4": nat.FMT_MXFP4, "MXFP8": nat.FMT_MXFP8, "MXFP6": nat.FMT_MXFP6}
 
 
 @dataclasses.dataclass(frozen=True)
@@ -39,7 +39,8 @@ class QParams:
     scale per 32-K block, ``quantize.quant_mxfp4`` / ``pack_mxfp4_scales``; with ``a_bits = 16``
     w4a16_g32_sym_MXFP4, fp16 activations on the same B codes and scales) or "MXFP8"
     (w4a8_g32_sym_MXFP8: OCP e4m3 activation codes with e8m0 block scales, ``quantize.quant_mxfp8``,
-    on the same MXFP4 B codes and scales). The reference's ``_accfp16`` strategies (fp16 MMA with an fp16
+    on the same MXFP4 B codes and scales) or "MXFP6" (w6a6_g32_sym_MXFP6: OCP e2m3 codes with e8m0 block scales on
+    both operands, ``quantize.quant_mxfp6`` / ``pack_mxfp6``). The reference's ``_accfp16`` strategies (fp16 MMA with an fp16
     accumulator, tile_config.py:94-97) run as their f32-accumulating base type: MFMA has no fp16
     accumulator, and the f32 sum is the more accurate result of the same products."""
 
@@ -76,7 +77,7 @@ class QParams:
             return "bf16" if self.fmt == "bf16" else "fp16"
         return f"w{self.w_bits}a{self.a_bits}_g{self.gsize}_{'sym' if self.sym else 'asym'}" + \
             ("_E4M3" if self.is_fp8 else "_F6" if self.fmt == "F6" else "_MXFP4" if self.fmt == "MXFP4" else
-             "_MXFP8" if self.fmt == "MXFP8" else "")
+             "_MXFP8" if self.fmt == "MXFP8" else "_MXFP6" if self.fmt == "MXFP6" else "")
 
     @staticmethod
     def from_qcfg(qcfg: str) -> "QParams":
@@ -91,7 +92,8 @@ class QParams:
         if qcfg.endswith("_bf16"):
             raise ValueError(f"{qcfg}: weight-only with bf16 activations is not built on MI355X")
         fmt = "E4M3" if qcfg.endswith("_E4M3") else "F6" if qcfg.endswith("_F6") else \
-            "MXFP4" if qcfg.endswith("_MXFP4") else "MXFP8" if qcfg.endswith("_MXFP8") else ""
+            "MXFP4" if qcfg.endswith("_MXFP4") else "MXFP8" if qcfg.endswith("_MXFP8") else \
+            "MXFP6" if qcfg.endswith("_MXFP6") else ""
         return QParams(a_bits=a, w_bits=w, gsize=g, sym="asym" not in qcfg, fmt=fmt)
 
 
@@ -109,6 +111,8 @@ W4A4_MXFP4 = QParams(4, 4, 32, True, "MXFP4")  # w4a4_g32_sym_MXFP4: e2m1 codes,
 W4A16_MXFP4 = QParams(16, 4, 32, True, "MXFP4")
 # w4a8_g32_sym_MXFP8: MXFP8 (e4m3) activations on the same MXFP4 weight tensors, one block-scaled MFMA
 W4A8_MXFP8 = QParams(8, 4, 32, True, "MXFP8")
+# w6a6_g32_sym_MXFP6: OCP MXFP6 (e2m3) on both operands, the block-scaled fp6 MFMA (include/mxmoe_gg.h)
+W6A6_MXFP6 = QParams(6, 6, 32, True, "MXFP6")
 W4A4_G128 = QParams(4, 4, 128, True)  # w4a4_g128_sym: one scale per 128-K group (cta_gemm.cuh:610-772)
 # weight-only (any group size that is -1 or a multiple of 64 dividing K, sym or asym, 2 / 4 / 8 bits)
 W4A16_G128_ASYM = QParams(16, 4, 128, False)
@@ -117,7 +121,7 @@ W4A16_G128_SYM = QParams(16, 4, 128, True)
 W8A16_ASYM = QParams(16, 8, -1, False)
 W2A16_G128_ASYM = QParams(16, 2, 128, False)
 
-SUPPORTED = {q.qcfg: q for q in (FP16, BF16, W8A8, W8A8_E4M3, W8A8_G128_E4M3, W4A4, W4A4_MXFP4, W4A16_MXFP4, W4A8_MXFP8, W4A4_G128, W4A16_G128_ASYM, W4A16_ASYM, W4A16_G128_SYM, W8A16_ASYM,
+SUPPORTED = {q.qcfg: q for q in (FP16, BF16, W8A8, W8A8_E4M3, W8A8_G128_E4M3, W4A4, W4A4_MXFP4, W4A16_MXFP4, W4A8_MXFP8, W6A6_MXFP6, W4A4_G128, W4A16_G128_ASYM, W4A16_ASYM, W4A16_G128_SYM, W8A16_ASYM,
                                   QParams(16, 4, -1, True), QParams(16, 8, -1, True), QParams(16, 8, 128, True),
                                   QParams(16, 8, 128, False), W2A16_G128_ASYM, QParams(16, 2, -1, False),
                                   QParams(16, 2, -1, True), QParams(16, 2, 128, True))}
@@ -131,7 +135,8 @@ class Problem:
     in pack_wxax layout, scale_a fp16 [M], scale_b fp16 [N] (w4a4_g128: [K/128][M] and [K/128][N],
     the permute_scale layout; MXFP4: codes uint8 [rows, K/2] as quant_mxfp4 returns them, scales uint8
     [rows, 16 * ceil(K/32 / 16)] in the device layout of pack_mxfp4_scales; MXFP8: A uint8 [M, K] e4m3
-    codes as quant_mxfp8 returns them, B and both scales as MXFP4's; w8a8_g128_sym_E4M3: codes as E4M3's, scale_a
+    codes as quant_mxfp8 returns them, B and both scales as MXFP4's; MXFP6: A / B uint8 [rows, 3K/4] in the device
+    image of pack_mxfp6, scales as MXFP4's; w8a8_g128_sym_E4M3: codes as E4M3's, scale_a
     f32 [K/128][M], scale_b f32 [K/128][ceil(N/128)], both group-major).  C fp16 [M, ldc] (ldc >= N).
     """
 
@@ -186,6 +191,11 @@ class Problem:
                 raise ValueError(f"{self.q.qcfg}: K={self.K} must be a multiple of the 32-element MX block")
             need(self.A, (torch.uint8, torch.float8_e4m3fn), "A (e4m3 codes)")
             need(self.B, (torch.uint8,), "B (e2m1 codes)")
+            need(self.scale_a, (torch.uint8,), "scale_a (e8m0, pack_mxfp4_scales)")
+            need(self.scale_b, (torch.uint8,), "scale_b (e8m0, pack_mxfp4_scales)")
+        elif self.q.fmt == "MXFP6":  # (K % 128: the planner's check, MXMOE_GG_ERR_INVALID)
+            need(self.A, (torch.uint8,), "A (e2m3 codes, pack_mxfp6)")
+            need(self.B, (torch.uint8,), "B (e2m3 codes, pack_mxfp6)")
             need(self.scale_a, (torch.uint8,), "scale_a (e8m0, pack_mxfp4_scales)")
             need(self.scale_b, (torch.uint8,), "scale_b (e8m0, pack_mxfp4_scales)")
         elif self.q.is_fp8 and self.q.gsize == 128:

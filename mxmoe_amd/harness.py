@@ -21,8 +21,8 @@ from typing import Optional, Sequence
 import torch
 
 from .groupgemm import GroupGemm, Problem, QParams
-from .quantize import (pack_e4m3, pack_mxfp4_scales, pack_weightonly_mi355x, pack_wxax, quant_e4m3, quant_e4m3_g128,
-                       quant_mxfp4, quant_mxfp8, quant_rtn_sym, quant_weight_e4m3_g128, quant_weightonly)
+from .quantize import (pack_e4m3, pack_mxfp4_scales, pack_mxfp6, pack_weightonly_mi355x, pack_wxax, quant_e4m3, quant_e4m3_g128,
+                       quant_mxfp4, quant_mxfp6, quant_mxfp8, quant_rtn_sym, quant_weight_e4m3_g128, quant_weightonly)
 from .workload import QShape
 
 
@@ -47,7 +47,7 @@ class LayerInputs:
                 tot += s.N * (s.K // 32)
             elif not plain and ab == 16:  # weight-only: scale (+ zp) per column and group
                 tot += 2 * s.N * (1 if s.gsize == -1 else s.K // s.gsize) * (1 if s.sym else 2)
-            elif s.fmt in ("MXFP4", "MXFP8"):  # one e8m0 byte per 32-K block
+            elif s.fmt in ("MXFP4", "MXFP8", "MXFP6"):  # one e8m0 byte per 32-K block
                 tot += (s.M + s.N) * (s.K // 32)
             elif s.fmt == "E4M3" and s.gsize == 128:  # f32: one per (row, group) and per 128 x 128 block
                 tot += 4 * (s.M + (s.N + 127) // 128) * (s.K // 128)
@@ -88,6 +88,10 @@ def build_layer_inputs(shapes: Sequence[QShape], device="cuda", seed: int = 42,
         elif q.fmt == "MXFP8":  # MXFP8 activations on the MXFP4 weight operand
             (qa, sa), (qb, sb) = quant_mxfp8(a), quant_mxfp4(b)
             probs.append(Problem(A=qa, B=qb, C=C, M=M, N=N, K=K, q=q, scale_a=pack_mxfp4_scales(sa),
+                                 scale_b=pack_mxfp4_scales(sb)))
+        elif q.fmt == "MXFP6":  # e2m3 codes in the device image on both sides
+            (qa, sa), (qb, sb) = quant_mxfp6(a), quant_mxfp6(b)
+            probs.append(Problem(A=pack_mxfp6(qa), B=pack_mxfp6(qb), C=C, M=M, N=N, K=K, q=q, scale_a=pack_mxfp4_scales(sa),
                                  scale_b=pack_mxfp4_scales(sb)))
         elif q.fmt == "bf16":
             probs.append(Problem(A=a.to(torch.bfloat16), B=b.to(torch.bfloat16), C=C, M=M, N=N, K=K, q=q))
@@ -211,7 +215,7 @@ def slice_scale_b(p: Problem, n0: int, n1: int) -> Optional[torch.Tensor]:
     if p.scale_b is None:
         return None
     q = p.q
-    if q.fmt in ("MXFP4", "MXFP8"):  # [N][16 ceil(K/32 / 16)] e8m0 rows
+    if q.fmt in ("MXFP4", "MXFP8", "MXFP6"):  # [N][16 ceil(K/32 / 16)] e8m0 rows
         return p.scale_b[n0:n1]
     G = 1 if q.gsize == -1 else p.K // q.gsize
     if G == 1 and not (q.is_weight_only and not q.sym):

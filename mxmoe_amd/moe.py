@@ -39,10 +39,11 @@ ACT_E4M3 = 8   # MXMOE_ACT_E4M3 (w8a8_g-1_sym_E4M3: e4m3 codes, one fp16 scale p
 # MXMOE_ACT_E4M3_G128 (w8a8_g128_sym_E4M3: e4m3 codes, one f32 scale per token and 128-element group, group-major).
 # Not the free value 7: a tag_mask with bit 7 (or 9) stays "unknown activation tag", as callers have always seen it.
 ACT_E4M3_G128 = 10
+ACT_MXFP6 = 12  # MXMOE_ACT_MXFP6 (w6a6_g32_sym_MXFP6: e2m3 codes in the GroupGEMM's fp6 image, e8m0 block scales); 11 is not assigned
 _BITS = {ACT_FP16: 16, ACT_INT8: 8, ACT_INT4: 4, ACT_INT4_G128: 4, ACT_MXFP4: 4, ACT_MXFP8: 8, ACT_E4M3: 8,
-         ACT_E4M3_G128: 8}
-_DWORD_TAGS = (ACT_MXFP4, ACT_MXFP8, ACT_E4M3_G128)  # scales read as dwords: an even scale_off
-_MX_TAGS = (ACT_MXFP4, ACT_MXFP8)  # block-scaled tags: e8m0 scale rows, the MX builds of the activation kernel
+         ACT_E4M3_G128: 8, ACT_MXFP6: 6}
+_DWORD_TAGS = (ACT_MXFP4, ACT_MXFP8, ACT_E4M3_G128, ACT_MXFP6)  # scales read as dwords: an even scale_off
+_MX_TAGS = (ACT_MXFP4, ACT_MXFP8, ACT_MXFP6)  # block-scaled tags: e8m0 scale rows, the MX builds of the activation kernel
 
 
 def _mx_scale_row(width: int) -> int:
@@ -78,6 +79,8 @@ def qtag_of(a_bits: int, gsize: int, fmt: str = "") -> int:
         return ACT_MXFP4
     if a_bits == 8 and gsize == 32:  # w4a8_g32_sym_MXFP8 (likewise)
         return ACT_MXFP8
+    if a_bits == 6 and gsize == 32:  # w6a6_g32_sym_MXFP6 (the only 6-bit type)
+        return ACT_MXFP6
     raise ValueError(f"activation quantisation a{a_bits} g{gsize} not supported")
 
 
@@ -359,8 +362,8 @@ def _make_segments(rows: Sequence[int], first: Sequence[int], widths: Sequence[i
 _ACT_MODES = {"gather": 0, "plain": 1, "fused": 2, "interleaved": 3}
 _LEGACY_ENTRY = {"gather": "mxmoe_moe_quant_act", "plain": "mxmoe_moe_silu_mul_quant", "fused": "mxmoe_moe_quant_slots",
                  "interleaved": "mxmoe_moe_silu_mul_quant_il"}
-_MX_MASK = _tag_mask(_MX_TAGS)
-_TAGGED_MASK = _MX_MASK | _tag_mask([ACT_E4M3, ACT_E4M3_G128])  # tags only the entries with a tag_mask carry (builds of their own)
+_MX_MASK = _tag_mask([ACT_MXFP4, ACT_MXFP8])
+_TAGGED_MASK = _MX_MASK | _tag_mask([ACT_E4M3, ACT_E4M3_G128, ACT_MXFP6])  # tags only the entries with a tag_mask carry (builds of their own)
 
 
 def _act_entry(mode: str, has_mx_tag: bool, glu: bool) -> str:
@@ -699,7 +702,8 @@ def gg_mxmoe_share_fused(inp: Sequence[torch.Tensor], experts: Sequence[torch.Te
         # (4, 4, 32, 1) is w4a4_g32_sym_MXFP4 and (16, 4, 32, 1) w4a16_g32_sym_MXFP4: the only g32 types, so
         # the tuple needs no format field ((8, 4, 32, 1) is w4a8_g32_sym_MXFP8)
         q = QParams(a_bits, w_bits, gsize, bool(sym), "MXFP4" if (w_bits, gsize) == (4, 32) and a_bits in (4, 16) else
-                    "MXFP8" if (a_bits, w_bits, gsize) == (8, 4, 32) else "")
+                    "MXFP8" if (a_bits, w_bits, gsize) == (8, 4, 32) else
+                    "MXFP6" if (a_bits, w_bits, gsize) == (6, 6, 32) else "")
         n, k = (shared_N, shared_K) if e == E else (N, K)
 
         def opt(t):
@@ -767,8 +771,8 @@ def prepare_weight(w: torch.Tensor, q: QParams, interleave: bool = False) -> Exp
     gate_up weight ([gate; up] rows) reordered for the fused SiLU epilogue (interleave_gate_up; the
     per-row scales follow their rows)."""
     from .groupgemm import interleave_gate_up
-    from .quantize import (pack_e4m3, pack_mxfp4_scales, pack_weightonly_mi355x, pack_wxax, quant_e4m3, quant_mxfp4,
-                           quant_rtn_sym, quant_weight_e4m3_g128, quant_weightonly)
+    from .quantize import (pack_e4m3, pack_mxfp4_scales, pack_mxfp6, pack_weightonly_mi355x, pack_wxax, quant_e4m3,
+                           quant_mxfp4, quant_mxfp6, quant_rtn_sym, quant_weight_e4m3_g128, quant_weightonly)
 
     N, K = w.shape
     if interleave:
@@ -778,6 +782,9 @@ def prepare_weight(w: torch.Tensor, q: QParams, interleave: bool = False) -> Exp
     if q.fmt in ("MXFP4", "MXFP8"):  # w4a4, w4a16 and w4a8 alike: canonical codes + device-layout scales, no repack
         codes, sc = quant_mxfp4(w)
         return ExpertWeights(codes, pack_mxfp4_scales(sc), q, N, K)
+    if q.fmt == "MXFP6":  # w6a6_g32_sym_MXFP6: e2m3 codes in the device image, scales in the MX device layout
+        codes, sc = quant_mxfp6(w)
+        return ExpertWeights(pack_mxfp6(codes), pack_mxfp4_scales(sc), q, N, K)
     if q.is_weight_only:
         codes, sz = quant_weightonly(w, q.w_bits, q.gsize, q.sym)
         return ExpertWeights(pack_weightonly_mi355x(codes, q.w_bits), sz, q, N, K)
@@ -820,6 +827,22 @@ def prepare_weight_mx(codes: torch.Tensor, scales: torch.Tensor, q: QParams, war
         warnings.warn(f"prepare_weight_mx: {bad} of {scales.numel()} scale bytes lie outside [{lo}, {hi}]: with fp16 "
                       "activations their blocks' weights are not exact fp16 values (include/mxmoe_gg.h)", stacklevel=2)
     return ExpertWeights(codes.contiguous(), pack_mxfp4_scales(scales), q, N, K, bad)
+
+
+def prepare_weight_mx6(codes: torch.Tensor, scales: torch.Tensor) -> ExpertWeights:
+    """Weights that already are canonical MXFP6 (``quantize.quant_mxfp6``'s format: codes uint8 [N, 3K/4], scales uint8
+    [N, K/32]) -> the GroupGEMM's B operand for w6a6_g32_sym_MXFP6, with no requantisation: the codes go into the device
+    image (``pack_mxfp6``), the scales into the MX device layout (``pack_mxfp4_scales``)."""
+    from .groupgemm import W6A6_MXFP6
+    from .quantize import pack_mxfp4_scales, pack_mxfp6
+
+    if codes.dtype != torch.uint8 or scales.dtype != torch.uint8 or codes.dim() != 2 or scales.dim() != 2:
+        raise ValueError("prepare_weight_mx6: codes uint8 [N, 3K/4] and scales uint8 [N, K/32]")
+    N, K = codes.shape[0], codes.shape[1] // 3 * 4
+    if K % 128 or codes.shape[1] * 4 != K * 3 or tuple(scales.shape) != (N, K // 32):
+        raise ValueError(f"prepare_weight_mx6: K = {K} must be a multiple of 128 and scales [{N}, K/32], got "
+                         f"{tuple(scales.shape)}")
+    return ExpertWeights(pack_mxfp6(codes), pack_mxfp4_scales(scales), W6A6_MXFP6, N, K)
 
 
 def prepare_weight_e4m3_g128(codes, scale_inv) -> ExpertWeights:

@@ -206,7 +206,8 @@ def graph_forward_bench(batches: Sequence[int] = (128,), model: str = "qwen2_moe
         yield one(bs)
 
 
-def fp8_layer_bench(batches: Sequence[int] = (128, 512, 2048, 8192), rounds: int = 4, iters: int = 30):
+def fp8_layer_bench(batches: Sequence[int] = (128, 512, 2048, 8192), rounds: int = 4, iters: int = 30,
+                    sides: Sequence[str] = ("e4m3", "w8a8", "fp16")):
     """FP8 layers: the qwen2_moe layer-11 shape (60 routed experts, top-4, the shared expert; routing drawn from the
     committed histogram, random weights) at every batch size of ``batches`` (yields one dict each) with every expert
     w8a8_g-1_sym_E4M3 ("e4m3"), w8a8_g-1_sym ("w8a8") or fp16, each side a ``PlannedForward`` step on the same
@@ -214,8 +215,14 @@ def fp8_layer_bench(batches: Sequence[int] = (128, 512, 2048, 8192), rounds: int
     plain gate_up layout (fuse_silu=False: the E4M3 tile has no SiLU epilogue), so the two activation passes of the
     e4m3 and w8a8 sides are the same launches on the same bytes but for the tag. Per side and stage the median of the
     rounds' medians with min / max (us), the gate_up / down variants, and per activation pass whether the e4m3 median
-    lies inside the w8a8 side's own min - max over the rounds ("parity") with the ratio of the medians."""
-    from .groupgemm import FP16, W8A8, W8A8_E4M3
+    lies inside the w8a8 side's own min - max over the rounds ("parity") with the ratio of the medians.
+    ``sides``: which of "e4m3", "w8a8", "fp16", "mxfp6" (w6a6_g32_sym_MXFP6) and "mxfp4" (w4a4_g32_sym_MXFP4) to build
+    ("fp16" is always one: the error's reference); with "mxfp6" and "e4m3" the result also holds their gate_up / down /
+    step ratios, as it does against "mxfp4"."""
+    from .groupgemm import FP16, W4A4_MXFP4, W6A6_MXFP6, W8A8, W8A8_E4M3
+
+    qs = {"e4m3": W8A8_E4M3, "w8a8": W8A8, "fp16": FP16, "mxfp6": W6A6_MXFP6, "mxfp4": W4A4_MXFP4}
+    sides = [*[s for s in sides if s != "fp16"], "fp16"]
 
     shapes, topk = load_workload(qwen2_layer11_workload(8192))["layer-11"], 4
     E = len(shapes["gate_up"]) - 1
@@ -228,7 +235,7 @@ def fp8_layer_bench(batches: Sequence[int] = (128, 512, 2048, 8192), rounds: int
     gate_up = [mk(2 * N, H) for _ in range(E)] + [mk(2 * Ns, H)]
     down = [mk(H, N) for _ in range(E)] + [mk(H, Ns)]
     layers = {name: MoEFFN(gate_up, down, [(q, q)] * (E + 1), num_routed=E, fuse_silu=False)
-              for name, q in (("e4m3", W8A8_E4M3), ("w8a8", W8A8), ("fp16", FP16))}
+              for name, q in ((s, qs[s]) for s in sides)}
     names = [ln.split()[1] for ln in nat.list_variants()]
 
     def one(bs: int) -> dict:
@@ -254,13 +261,18 @@ def fp8_layer_bench(batches: Sequence[int] = (128, 512, 2048, 8192), rounds: int
             out[n]["splitk_slabs"] = [int(st.g1.info.splitk_slabs), int(st.g2.info.splitk_slabs)]
             err = (st.out.float() - ref).norm() / ref.norm()
             out[n]["rel_err_to_fp16"] = round(float(err), 5)
-        out["act_passes_vs_w8a8"] = {}
-        for k in ("quant_act", "act_quant"):
-            e, w = out["e4m3"][k], out["w8a8"][k]
-            out["act_passes_vs_w8a8"][k] = {"parity": bool(w["min_us"] <= e["median_us"] <= w["max_us"]),
-                                            "ratio": round(e["median_us"] / w["median_us"], 4)}
-        for k in ("gate_up", "down", "step"):
-            out["act_passes_vs_w8a8"][k] = {"ratio": round(out["e4m3"][k]["median_us"] / out["w8a8"][k]["median_us"], 4)}
+        if "e4m3" in out and "w8a8" in out:
+            out["act_passes_vs_w8a8"] = {}
+            for k in ("quant_act", "act_quant"):
+                e, w = out["e4m3"][k], out["w8a8"][k]
+                out["act_passes_vs_w8a8"][k] = {"parity": bool(w["min_us"] <= e["median_us"] <= w["max_us"]),
+                                                "ratio": round(e["median_us"] / w["median_us"], 4)}
+            for k in ("gate_up", "down", "step"):
+                out["act_passes_vs_w8a8"][k] = {"ratio": round(out["e4m3"][k]["median_us"] / out["w8a8"][k]["median_us"], 4)}
+        for other in ("e4m3", "mxfp4"):
+            if "mxfp6" in out and other in out:
+                out[f"mxfp6_over_{other}"] = {k: round(out["mxfp6"][k]["median_us"] / out[other][k]["median_us"], 4)
+                                              for k in ("quant_act", "gate_up", "act_quant", "down", "step")}
         return out
 
     for bs in batches:  # (a generator: a caller can print each size as it completes)

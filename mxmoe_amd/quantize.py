@@ -381,3 +381,89 @@ def dequant_mxfp8(codes: torch.Tensor, scales: torch.Tensor) -> torch.Tensor:
     v = codes.contiguous().view(torch.float8_e4m3fn).to(torch.float64)
     s = e8m0_decode(scales)
     return (v.reshape(rows, -1, MXFP4_BLOCK) * s[..., None]).reshape(rows, K)
+
+
+# ---- OCP MXFP6, e2m3 elements (w6a6_g32_sym_MXFP6): 6-bit codes, one e8m0 scale per 32-element block ----
+E2M3_MAX = 7.5
+
+
+def _e2m3_values(device=None) -> torch.Tensor:
+    """Magnitudes of the 32 e2m3 codes (2 exponent bits, bias 1, 3 mantissa bits): m / 8 for exponent 0, else
+    2^(e - 1) (1 + m / 8); bit 5 of a code is the sign."""
+    c = torch.arange(32, device=device)
+    e, m = c >> 3, (c & 7).double()
+    return torch.where(e == 0, m / 8, torch.ldexp(1 + m / 8, e - 1))
+
+
+def quant_mxfp6(x: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
+    """fp16 [rows, K] (K % 32 == 0) -> (codes uint8 [rows, 3K/4], scales uint8 [rows, K/32]), the canonical MXFP6
+    operand format of include/mxmoe_gg.h: each block's 32 six-bit codes as one little-endian 192-bit value, code j
+    at bits [6j, 6j + 6). RTN as OCP MX v1.0, quant_mxfp4's rule on the e2m3 grid: e = floor(log2(amax)) - 2 clamped
+    to [-127, 127] (an all-zero block: -127, scale code 0), element = f32(x) / 2^e (exact) saturated at +-7.5 and
+    rounded once to the grid with ties to the even code; the sign of -0 and of values that round to 0 is kept. A
+    block holding a NaN or an Inf gets scale code 255 (NaN) and all-zero codes."""
+    if x.dtype != torch.float16:
+        raise TypeError("quant_mxfp6 expects fp16 input")
+    rows, K = x.shape
+    if K % MXFP4_BLOCK:
+        raise ValueError(f"K={K} must be a multiple of the MX block size {MXFP4_BLOCK}")
+    xf = x.float().reshape(rows, K // MXFP4_BLOCK, MXFP4_BLOCK)
+    bad = ~torch.isfinite(xf).all(dim=-1)
+    xf = torch.where(bad[..., None], torch.zeros_like(xf), xf)
+    amax = xf.abs().amax(dim=-1)
+    ex = torch.frexp(amax).exponent.to(torch.int32)  # floor(log2(amax)) = ex - 1 (quant_mxfp4)
+    e = torch.where(amax == 0, torch.full_like(ex, -127), (ex - 3).clamp(-127, 127))
+    h = torch.div(e, 2, rounding_mode="floor")  # x / 2^e in two exact steps, as quant_mxfp4
+    one = torch.ones((), dtype=torch.float32, device=x.device)
+    y = xf * torch.ldexp(one, -h)[..., None] * torch.ldexp(one, -(e - h))[..., None]
+    a = y.abs().clamp(max=E2M3_MAX)
+    # grid steps 1/8 below 2 (subnormals and the first binade), 1/4 below 4, 1/2 up to 7.5; the code is the step count
+    # from its segment's start, so an even rounded multiple (torch.round: half-to-even) is an even code in each
+    idx = torch.where(a < 2, torch.round(a * 8), torch.where(a < 4, 8 + torch.round(a * 4), 16 + torch.round(a * 2)))
+    code = idx.to(torch.uint8) | (torch.signbit(y).to(torch.uint8) << 5)
+    code = torch.where(bad[..., None], torch.zeros_like(code), code)
+    scales = torch.where(bad, torch.full_like(e, 255), e + 127).to(torch.uint8)
+    return _pack6(code.reshape(rows, K)), scales.contiguous()
+
+
+def _pack6(code: torch.Tensor) -> torch.Tensor:
+    """6-bit codes uint8 [rows, K] -> uint8 [rows, 3K/4]: four codes per three bytes, little-endian bit order."""
+    c = code.reshape(code.shape[0], -1, 4).to(torch.int32)
+    w = c[..., 0] | (c[..., 1] << 6) | (c[..., 2] << 12) | (c[..., 3] << 18)
+    return torch.stack([w & 255, (w >> 8) & 255, w >> 16], dim=-1).to(torch.uint8).reshape(code.shape[0], -1)
+
+
+def unpack_mxfp6_codes(codes: torch.Tensor) -> torch.Tensor:
+    """Canonical MXFP6 rows uint8 [rows, 3K/4] -> the 6-bit codes uint8 [rows, K]."""
+    b = codes.reshape(codes.shape[0], -1, 3).to(torch.int32)
+    w = b[..., 0] | (b[..., 1] << 8) | (b[..., 2] << 16)
+    return torch.stack([w & 63, (w >> 6) & 63, (w >> 12) & 63, w >> 18], dim=-1).to(torch.uint8).reshape(codes.shape[0], -1)
+
+
+def dequant_mxfp6(codes: torch.Tensor, scales: torch.Tensor) -> torch.Tensor:
+    """Canonical MXFP6 (codes uint8 [rows, 3K/4], scales uint8 [rows, K/32]) -> float64 [rows, K] (exact; NaN where
+    the block's scale code is 255)."""
+    c = unpack_mxfp6_codes(codes)
+    v = _e2m3_values(codes.device)[(c & 31).long()] * torch.where((c & 32) != 0, -1.0, 1.0).to(torch.float64)
+    s = e8m0_decode(scales)
+    return (v.reshape(c.shape[0], -1, MXFP4_BLOCK) * s[..., None]).reshape(c.shape)
+
+
+def pack_mxfp6(codes: torch.Tensor) -> torch.Tensor:
+    """Canonical MXFP6 rows uint8 [rows, 3K/4] (K % 128 == 0) -> the device image the GroupGEMM reads and the
+    activation kernel writes (include/mxmoe_gg.h), same shape: per 128 elements 96 bytes, the first 16 bytes of each
+    of the four blocks' 24 (64 bytes), then their last 8 (32 bytes)."""
+    rows, nb = codes.shape
+    if nb % 96:
+        raise ValueError(f"MXFP6 rows of {nb} bytes are no whole 128-element steps (K % 128 == 0)")
+    c = codes.reshape(rows, nb // 96, 4, 24)
+    return torch.cat([c[..., :16].reshape(rows, -1, 64), c[..., 16:].reshape(rows, -1, 32)], dim=-1).reshape(rows, nb).contiguous()
+
+
+def unpack_mxfp6(image: torch.Tensor) -> torch.Tensor:
+    """Inverse of pack_mxfp6: the device image uint8 [rows, 3K/4] -> canonical rows."""
+    rows, nb = image.shape
+    if nb % 96:
+        raise ValueError(f"MXFP6 rows of {nb} bytes are no whole 128-element steps (K % 128 == 0)")
+    d = image.reshape(rows, nb // 96, 96)
+    return torch.cat([d[..., :64].reshape(rows, -1, 4, 16), d[..., 64:].reshape(rows, -1, 4, 8)], dim=-1).reshape(rows, nb).contiguous()
